@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark of the HiFiGAN vocoder path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path -- mel [B, 80, T] -> waveform [B, 256*T] through
 ``iris_hifigan_forward`` -- over one batch of synthetic mels that is already resident in HBM when
 the timed region starts.
 
-N = 1   BASELINE.json configs[1]: batch 1, 80 x 1000 frames, fp32 (the headline `value`).  Outside the
+A plain run sets up, runs W untimed warm-up steps and K timed steps, writes the waveform of the last timed step
+when --dump-outputs is given (`dump_outputs`), and prints the headline line with its live `roofline` and
+`kernels`.  Everything else listed below is measured only with --full.
+
+N = 1   BASELINE.json configs[1]: batch 1, 80 x 1000 frames, fp32 (the headline `value`).  With --full, outside the
         headline's timed region the same run also measures, as sub-records of the ONE JSON line:
           grid            B = 1 x {100, 500, 1000} frames fp32 (north_star's reporting grid): ms, samples/s, RTF,
                           MRF-kernel roofline fraction
@@ -21,7 +25,8 @@ N = 1   BASELINE.json configs[1]: batch 1, 80 x 1000 frames, fp32 (the headline 
           cpu_baseline    the oracle timed on the host cores; other_modes: the other arithmetic modes
 N > 1   BASELINE.json configs[3]: a GLOBAL batch of 256 mels x 1000 frames sharded over the N ranks (strong
         scaling: total work fixed), one process per GPU, no data-path collective but the final RCCL all-gather
-        of the waveform shards, which IS inside the step; `grid` adds the same global batch at 100 and 500 frames.
+        of the waveform shards, which IS inside the step; with --full, `grid` adds the same global batch at 100 and
+        500 frames and `collective` times the all-gather on its own.
         When WORLD_SIZE is not set, ``python bench.py --gpus N`` starts the N ranks itself (torch.distributed.run
         as a child process, before this process touches the GPU) and passes rank 0's line through.
 
@@ -34,7 +39,8 @@ The JSON line also carries
                 reported beside it as ``hbm_frac``.  ``traffic`` is NOT live: it is the committed PMC
                 measurement of the same workload (``traffic_source`` names the file).
   cpu_baseline  the oracle (torch fp32 restatement of the reference, oracle/hifigan_oracle.py) timed on
-                this box's host cores on a bounded sample of the same workload; rank 0, N = 1 only.
+                this box's host cores on a bounded sample of the same workload; rank 0, N = 1, --full only
+                (null otherwise).
 """
 import argparse
 import json
@@ -72,9 +78,14 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", choices=["f32", "bf16", "f32s"], default="f32",
                     help="f32 = the parity path and the headline (default); bf16 = bf16 storage + bf16 MFMA "
                          "(BASELINE.json configs[2] with --batch 32 --frames 500)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement (no grid / host_inclusive / "
-                    "configs2 / configs3_n1 / other_modes sub-records)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the sub-records (grid, "
+                    "host_inclusive, configs2, configs4, configs3_n1, load, cpu_baseline, other_modes; N > 1: grid, "
+                    "collective); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveform of the last timed step to DIR/waveform.npy (float32; a fixed sample above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline sub-record")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no grid / host_inclusive / configs2 / configs4 / "
+                    "configs3_n1 / load / other_modes sub-records")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket launches with HIP events")
     ap.add_argument("--per-launch-events", action="store_true",
                     help="one HIP-event pair per launch (31 events per forward, ~0.1 ms of stream time) instead of one per "
@@ -224,6 +235,25 @@ def cpu_baseline(cfg, sd, mel, budget_s=24.0):
                       f"(the two fastest of {sorted(tried)} on a 100-frame clip; the box has {all_cores}); "
                       f"oracle/hifigan_oracle.py:generator_forward_torch",
             "rtf": best / (mel.shape[2] * 256 / SAMPLE_RATE) if mel.shape[0] == 1 else None}
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, wav):
+    """--dump-outputs: the waveform [items, samples] the timed path returned in its last step -> DIR/waveform.npy (float32).
+    Above DUMP_LIMIT_BYTES the file holds a fixed sample instead: the items np.random.default_rng(0) draws (in ascending
+    order) and, if one item alone is too large, every s-th sample of it.  The selection depends on the shape alone, so the
+    files of two builds run with the same arguments compare element for element."""
+    import numpy as np
+    import torch
+    items, n = wav.shape
+    keep = max(1, min(items, DUMP_LIMIT_BYTES // (4 * n)))
+    rows = np.arange(items) if keep == items else np.sort(np.random.default_rng(0).choice(items, keep, replace=False))
+    stride = -(-4 * n // DUMP_LIMIT_BYTES)
+    sample = wav[torch.as_tensor(rows, device=wav.device)][:, ::stride]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "waveform.npy"), sample.to(torch.float32).cpu().numpy())
 
 
 def summarize_records(recs, steps, cfg):
@@ -479,7 +509,8 @@ def rank_main(args):
             else:
                 out = eng.forward(mel, out=wav, dtype=args.dtype)
             if use_dist:
-                gather_waveforms(out, G, out=gathered)
+                out = gather_waveforms(out, G, out=gathered)
+            return out
 
         for _ in range(warmup):
             step()
@@ -487,7 +518,7 @@ def rank_main(args):
         eng.set_profiling(profile)
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            out = step()
         fence()
         elapsed = time.perf_counter() - t0
         recs = eng.read_profile() if profile else []
@@ -500,7 +531,7 @@ def rank_main(args):
             per_rank = [float(v) for v in every.cpu()]
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        run_sharded.last = {"per_rank_s": per_rank, "wav": wav, "gathered": gathered}
+        run_sharded.last = {"per_rank_s": per_rank, "wav": wav, "gathered": gathered, "out": out}
         return elapsed, recs, mel_np, mel
 
     # ---- the headline: W untimed warm-up steps, exactly K timed steps between barrier + synchronize -------------
@@ -511,10 +542,12 @@ def rank_main(args):
     ms_per_step = 1e3 * elapsed / args.steps
     by_kind, detail = summarize_records(recs, args.steps, cfg) if recs else ({}, {})
     roofline = roofline_of(by_kind, args.dtype, args.steps, ms_per_step, B, T) if recs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run_sharded.last["out"])
 
     per_rank_ms = [1e3 * v / args.steps for v in run_sharded.last["per_rank_s"]]
     collective = None
-    if use_dist:
+    if use_dist and args.full:
         # The one collective of the path on its own: 10 timed all-gathers of the real waveform shard (outside the
         # headline's timed region), and what the process group itself says about backend and world size -- so that
         # "RCCL saw N ranks" can be read off the line.
@@ -535,7 +568,7 @@ def rank_main(args):
 
     # ---- N > 1: the rest of the reporting grid (same global batch, 100 and 500 frames); every rank takes part --------
     grid = []
-    if strong and not args.no_extras:
+    if strong and args.full and not args.no_extras:
         for frames in (100, 500, 1000):
             if frames == T:
                 grid.append({"frames": T, "global_batch": G, "ms_per_step": ms_per_step, "samples_per_s": value})
@@ -576,8 +609,9 @@ def rank_main(args):
         "tflops_whole_path": flop_per_frame * G * T / (ms_per_step * 1e-3) / 1e12,
         "roofline": roofline, "kernels": detail,
     }
-    if use_dist:
+    if collective:
         out["collective"] = collective
+    if use_dist:
         out["per_rank_ms"] = per_rank_ms
     if args.include_h2d:
         out["h2d_in_step"] = {"bytes_per_rank": int(B * 80 * T * 4), "note": "pinned host memory -> HBM inside every timed step; not the headline"}
@@ -588,7 +622,7 @@ def rank_main(args):
     if grid:
         out["grid"] = grid
 
-    extras = world == 1 and not stub and not args.no_extras and not args.force_dist
+    extras = args.full and world == 1 and not stub and not args.no_extras and not args.force_dist
     if extras:
         # ---- north_star's reporting grid at batch 1 (outside the headline's timed region) ------------------------------
         g = []
@@ -713,7 +747,7 @@ def rank_main(args):
 
     if extras:
         out["load"] = cold_start_record(sd)                               # fresh child process; outside every timed region
-    if world == 1 and not stub and not args.no_cpu_baseline:
+    if args.full and world == 1 and not stub and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, sd, mel_np)
         if extras:
             # Beside the headline (outside its timed region): the same workload in the other arithmetic modes of the
@@ -744,6 +778,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.cold_start_child:
         cold_start_child(args.cold_start_child)
         return

@@ -10,6 +10,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 REPO = Path(__file__).resolve().parents[1]
@@ -30,7 +31,7 @@ def _json_line(stdout):
 
 @pytest.mark.parametrize("world,global_batch,extras", [(2, 256, False), (3, 7, True)])
 def test_self_launch_shards_the_global_batch(world, global_batch, extras):
-    out = _run("--gpus", str(world), "--backend", "gloo", "--stub-engine", "--steps", "2", "--warmup", "1",
+    out = _run("--gpus", str(world), "--backend", "gloo", "--stub-engine", "--steps", "2", "--warmup", "1", "--full",
                "--global-batch", str(global_batch), "--frames", "12", *([] if extras else ["--no-extras"]))
     assert out.returncode == 0, out.stderr[-3000:]
     line = _json_line(out.stdout)
@@ -52,6 +53,38 @@ def test_self_launch_shards_the_global_batch(world, global_batch, extras):
         assert all(g["global_batch"] == global_batch and g["samples_per_s"] > 0 for g in line["grid"])
     else:
         assert "grid" not in line
+
+
+def test_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes the gathered
+    waveform of the last timed step (the stand-in's output: each sample is the mean of its frame's mel bins)."""
+    out = _run("--gpus", "2", "--backend", "gloo", "--stub-engine", "--steps", "3", "--warmup", "1",
+               "--global-batch", "5", "--frames", "12", "--dump-outputs", str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = _json_line(out.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert line["value"] == pytest.approx(5 * 12 * 256 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert "collective" not in line and "grid" not in line and len(line["per_rank_ms"]) == 2
+    from iris._weights import seeded_mel
+    mels = [seeded_mel(1004 + r, n, 12) for r, n in enumerate((3, 2))]       # rank r's shard and seed
+    want = np.concatenate([m.mean(axis=1).repeat(256, axis=1) for m in mels])
+    got = np.load(tmp_path / "waveform.npy")
+    assert got.dtype == np.float32 and got.shape == (5, 12 * 256)
+    np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6)
+
+
+def test_dump_outputs_is_a_fixed_sample_below_64_mb(tmp_path):
+    """70 items x 256,000 samples is 71.7 MB of float32: the file holds the same seeded sample of items in every run."""
+    files = []
+    for i in range(2):
+        out = _run("--stub-engine", "--steps", "1", "--warmup", "0", "--batch", "70", "--frames", "1000",
+                   "--dump-outputs", str(tmp_path / str(i)))
+        assert out.returncode == 0, out.stderr[-3000:]
+        files.append(tmp_path / str(i) / "waveform.npy")
+    assert files[0].stat().st_size <= 64_000_000
+    a, b = (np.load(f) for f in files)
+    assert a.dtype == np.float32 and a.shape[1] == 1000 * 256 and 1 <= a.shape[0] < 70
+    assert np.array_equal(a, b)
 
 
 def test_launched_by_torchrun_like_the_driver():

@@ -676,6 +676,26 @@ def test_bench_collective_path_runs_on_rccl(tmp_path):
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["roofline"]["frac"] > 0
 
 
+def test_bench_dump_outputs_match_the_oracle(tmp_path):
+    """bench.py --dump-outputs writes the waveform of its last timed step: the headline path's output for bench.py's own
+    seeded weights (seed 2024) and mel (seed 1002)."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    from iris._weights import GeneratorConfig, seeded_mel, seeded_state_dict
+    repo = Path(__file__).resolve().parents[1]
+    out = subprocess.run([sys.executable, str(repo / "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
+                          "--frames", "64", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == 2
+    got = np.load(tmp_path / "waveform.npy")
+    want = orc.generator_forward_torch(orc.to_torch_folded(seeded_state_dict(GeneratorConfig(), seed=2024)),
+                                       seeded_mel(1002, 2, 64)).numpy()[:, 0, :]
+    assert got.dtype == np.float32 and got.shape == want.shape == (2, 64 * 256)
+    assert np.abs(got - want).max() <= TOL_WAV
+
+
 def test_integration_md_ctypes_stub_runs(dev):
     """The ctypes stub printed in INTEGRATION.md section 2 (what a reference maintainer would paste) is executed as
     written -- only the library name is made absolute -- against a model with the reference's attribute layout."""

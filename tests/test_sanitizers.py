@@ -75,10 +75,7 @@ for cfg in configs[:2]:
     h = ctypes.c_void_p()
     rc = lib.iris_hifigan_create(ctypes.byref(_native.make_config(cfg)), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                  ctypes.c_uint64(n), ctypes.byref(h))
-    if rc == 0:
-        lib.iris_hifigan_destroy(h)             # (a box with a GPU: fine too)
-    else:
-        assert rc in (2, 3) and "weight upload failed" in err(), (rc, err())
+    assert rc in (2, 3) and "weight upload failed" in err(), (rc, err())
     rc = lib.iris_hifigan_create(ctypes.byref(_native.make_config(cfg)), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                  ctypes.c_uint64(n - 1), ctypes.byref(h))
     assert rc == 1 and "weight blob has" in err()
@@ -101,7 +98,11 @@ def test_host_code_under_asan_and_ubsan(tmp_path):
     assert Path(runtime).exists(), runtime
     script = tmp_path / "child.py"
     script.write_text(CHILD)
+    # The child sees no GPU on any box: this build has no device code (its registration is stubbed), so with a device
+    # visible the upload would go on into the HIP runtime with nothing registered and crash there.  Hidden, every box
+    # takes the same path as a box without a GPU: the upload fails and the error path is checked.
     env = dict(os.environ, LD_PRELOAD=runtime,
+               HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=66:allocator_may_return_null=1",
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     proc = subprocess.run([sys.executable, str(script), str(ASAN_LIB), str(REPO / "iris-tts_amd")], env=env,

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Round-end measurement pass on the GPU box (through gpurun): bench lines, rocprofv3 kernel stats and HBM
-# traffic for the fp32 headline (configs[1]) and the bf16 variant (configs[2]).  Outputs under gpurun_out/<tag>_*.
+# traffic for the fp32 headline (configs[1]) and the bf16 variant (configs[2]).  Outputs as <tag>_* and <tag>/bench.json.
 set -e
 REPO=$PWD; TAG=${1:-rXX}
 export TMPDIR=/tmp
-python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+STEPS=bench TAG=$TAG tools/gpu_steps.sh                     # the --full line: <tag>/bench.json beside the files below
 python bench.py --dtype bf16 --batch 32 --frames 500 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > gpurun_out/${TAG}_bench_bf16_c3.json
 python bench.py --batch 32 --frames 500 --steps 5 --warmup 1 --no-cpu-baseline --no-extras > gpurun_out/${TAG}_bench_f32_c3.json
 python bench.py --dtype bf16 --no-cpu-baseline --no-extras > gpurun_out/${TAG}_bench_bf16_c2.json
