@@ -29,7 +29,7 @@
  *     on one stream or give each stream its own handle and workspace;
  *   - a handle belongs to the HIP device that was current in iris_hifigan_create; forward selects that device
  *     for its launches and restores the caller's, so `stream` and all *_dev pointers must belong to it;
- *   - the library reads no environment variable (diagnostic switches exist only in the `make diag` build).
+ *   - the library reads no environment variable (A/B switches are compile-time macros).
  *
  * Activations inside the library are channels-last [B, L, C], fp32 (bf16 with dtype
  * IRIS_HIFIGAN_BF16); the mel comes in as the
@@ -256,9 +256,8 @@ int32_t iris_hifigan_op_mrf_step(const float* const* x_dev, const float* const* 
  * jobs from a device counter; 2 = the same with a fixed job stride.
  * mean_dev != NULL (modes 1, 2) makes it the LAST pair of a stage: only ((y_0 + y_1) + y_2) / 3 is stored, into mean_dev
  * (hifigan_pretrained.py:131-137; y_dev is then unused).  No y_dev[i] / mean_dev may alias an x_dev[j].
- * The release library carries modes 1 / 2 in the summing form only (as plain pairs they measured slower than mode 0 at
- * every size and are compiled into the diagnostic build alone): modes 1 / 2 without mean_dev return IRIS_HIFIGAN_UNSUPPORTED
- * there, as do other shapes. */
+ * The library carries modes 1 / 2 in the summing form only (as plain pairs they measured slower than mode 0 at every
+ * size): modes 1 / 2 without mean_dev return IRIS_HIFIGAN_UNSUPPORTED, as do other shapes. */
 int32_t iris_hifigan_op_mrf_pair(const float* const* x_dev, const float* const* w1_host, const float* const* b1_host,
                                  const float* const* w2_host, const float* const* b2_host, float* const* y_dev,
                                  float* mean_dev, int32_t B, int32_t L, int32_t C, const int32_t* k, const int32_t* dil,

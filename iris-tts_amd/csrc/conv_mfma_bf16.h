@@ -28,7 +28,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include "diag_env.h"
 
 namespace iris {
 namespace b16 {
@@ -89,8 +88,6 @@ struct Launch {
                           // of the window item (item = b * n_items + tile), so that short items of a large batch qualify too
     int fold_b;           // grouped launches: the batch index is part of blockIdx.x (item = b * n_items + tile)
     int z_in_y;           // the problem index is blockIdx.y / B (heaviest problem dispatched first, over ALL tiles and batch items)
-    int ablate;           // diagnostics only (env IRIS_B16_ABLATE): 1 no staging loads, 2 no MFMA loop, 4 no stores,
-                          // 8 no residual loads, 16 every weight fragment from one (L1-resident) address.  Results are wrong.
 };
 
 // ---- small helpers -------------------------------------------------------------------------------
@@ -139,7 +136,7 @@ __device__ __forceinline__ void stage_window(const Launch& a, const Problem& p, 
             const int r = idx / PPR, pc = idx - r * PPR;
             const int row = in_row0 + r, ci = c0 + 8 * pc;
             const bool ok = idx < total && row >= 0 && row < L_in && ci < C_in;
-            voff = (ok && !(a.ablate & 1)) ? (unsigned)(row * C_in + ci) * 2u : kOob;
+            voff = ok ? (unsigned)(row * C_in + ci) * 2u : kOob;
             ldso = idx < total ? r * SB + pc * 16 : -1;
         };
         if (!mrf) {
@@ -334,10 +331,10 @@ __global__ void __launch_bounds__(256, MINB) conv_mfma_bf16_kernel(const Launch 
                 for (int e = 0; e < 4; ++e) acc[m][nt][4 * g + e] = b4[e];
         }
 
-    const unsigned q_bytes = (a.ablate & 16) ? 0u : (unsigned)a.n_ct * 1024u;   // bytes per (tap, 16-channel step)
-    const unsigned tap_bytes = (unsigned)a.Qp * q_bytes;                        // (ablation 16: weights from one address)
+    const unsigned q_bytes = (unsigned)a.n_ct * 1024u;                          // bytes per (tap, 16-channel step)
+    const unsigned tap_bytes = (unsigned)a.Qp * q_bytes;
     const char* wbase = (const char*)p.wp + (a.z_is_phase ? (size_t)z * a.phase_wp_bytes : 0);
-    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wbase, (a.ablate & 16) ? 65536u : (unsigned)ks * tap_bytes);
+    const __amdgpu_buffer_rsrc_t wr = make_rsrc(wbase, (unsigned)ks * tap_bytes);
     const unsigned wvoff = (unsigned)ct0 * 1024u + (unsigned)lane * 16u;
     const char* a_lane = lds + (wt * MT * 32 + lo) * SB + hi * 16;
     const int dil_bytes = p.dil * SB;
@@ -346,7 +343,7 @@ __global__ void __launch_bounds__(256, MINB) conv_mfma_bf16_kernel(const Launch 
         if (c0 > 0) __syncthreads();
         stage_window<CIC>(a, p, lds, b, in_row0, R, c0);
         __syncthreads();
-        if (wave_active && !(a.ablate & 2))
+        if (wave_active)
             mma_chunk<MT, NT, CIC>(acc, a_lane, dil_bytes, wr, wvoff, q_bytes, tap_bytes,
                                    (unsigned)(c0 >> 4) * q_bytes, ks);
     }
@@ -365,7 +362,7 @@ __global__ void __launch_bounds__(256, MINB) conv_mfma_bf16_kernel(const Launch 
     const unsigned out_bytes = (unsigned)a.L_out * (unsigned)a.C_out * 2u;
     const size_t ob = (size_t)b * a.L_out * a.C_out;
     const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + ob, out_bytes);
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + ob : p.y, (p.res && !(a.ablate & 8)) ? out_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + ob : p.y, p.res ? out_bytes : 0u);
     // this lane's pieces of an m-tile: q = j*64 + lane -> row q / PPRO, channels 8*(q % PPRO) .. +7 of the span
     unsigned pvoff[MT][NP];
     int pscr[NP];
@@ -416,7 +413,7 @@ __global__ void __launch_bounds__(256, MINB) conv_mfma_bf16_kernel(const Launch 
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < NP; ++j)
-            __builtin_amdgcn_raw_buffer_store_b128(outp[j], yr, (int)((a.ablate & 4) ? kOob : pvoff[m][j]), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(outp[j], yr, (int)pvoff[m][j], 0, 0);
         asm volatile("s_nop 1");       // explicit wait states behind the dwordx4 stores (see mrf_conv_mfma_f32.h)
         __builtin_amdgcn_sched_barrier(0);
         // the store data must stay live until every store of the group has issued (see the store-data note in
@@ -554,20 +551,15 @@ inline void pack_convt_bf16(const float* w, int C_in, int C_out, int k, int u, u
 struct Tile { int WT, WC, MT, NT, CIC, MINB, T_BLK, CO_BLK; };
 
 inline Tile pick_tile(int C_in, int C_out, bool phases = false) {
-    const int v32 = IRIS_DIAG_ENV("IRIS_B16_TILE32", 0), v64 = IRIS_DIAG_ENV("IRIS_B16_TILE64", 0), v128 = IRIS_DIAG_ENV("IRIS_B16_TILE128", 0);
     Tile t;
     if (C_out <= 32) {
+        // 384 rows at <= 128 VGPRs -> four blocks per CU (HBM-bound layers want requests in flight)
         t.WT = 4; t.WC = 1; t.NT = 1;
-        // default: 384 rows at <= 128 VGPRs -> four blocks per CU (HBM-bound layers want requests in flight);
-        // diagnostics: v32 = 8 -> 512 rows / 3 blocks, else bit0 -> MT=2, bits1.. -> min blocks 2/3/4
-        if (v32 == 0)      { t.MT = phases ? IRIS_B16_UPS32_MT : 3; t.MINB = 4; }
-        else if (v32 == 8) { t.MT = 4; t.MINB = 2; }
-        else               { t.MT = (v32 & 1) ? 2 : 4; t.MINB = 2 + (v32 >> 1); }
+        t.MT = phases ? IRIS_B16_UPS32_MT : 3; t.MINB = 4;
     } else if (C_out <= 64) {
-        // default: 192 rows x 64 channels as 2 x 2 waves of 96 x 32 at <= 128 VGPRs -> four blocks per CU (2-3 %
-        // ahead of 256 x 64 at three blocks); diagnostics: v64 = 8 -> 256 x 64, else bit0 -> MT=1, bits1.. -> min blocks
-        if (v64 == 0)      { t.WT = 2; t.WC = 2; t.MT = 3; t.NT = 1; t.MINB = 4; }
-        else               { t.WT = 4; t.WC = 1; t.NT = 2; t.MT = (v64 & 1) ? 1 : 2; t.MINB = v64 == 8 ? 2 : 2 + (v64 >> 1); }
+        // 192 rows x 64 channels as 2 x 2 waves of 96 x 32 at <= 128 VGPRs -> four blocks per CU (2-3 %
+        // ahead of 256 x 64 at three blocks)
+        t.WT = 2; t.WC = 2; t.MT = 3; t.NT = 1; t.MINB = 4;
     } else {
         t.WT = 2; t.WC = 2; t.NT = 2;
         t.MT = 2;             // (96 rows per wave, MT = 3: -1.5 % on the C = 256 steps of configs[2], -15 % at 1 x 1000: profiles/r04_notes.md section 15)
@@ -575,7 +567,7 @@ inline Tile pick_tile(int C_in, int C_out, bool phases = false) {
     }
     t.CIC = (C_in <= 32 && t.NT == 1 && t.WC == 1) ? 32 : 64;
     // wide layers: 128-channel chunks halve the staging round trips of a block (window 48 KB, three blocks per CU)
-    if (C_out > 64 && !(v128 & 2) && C_in % 128 == 0) t.CIC = 128;
+    if (C_out > 64 && C_in % 128 == 0) t.CIC = 128;
     t.T_BLK = t.WT * t.MT * 32;
     t.CO_BLK = t.WC * t.NT * 32;
     return t;
@@ -589,7 +581,6 @@ inline hipError_t launch_conv_bf16(Launch& a, int nz, hipStream_t stream) {
     a.n_ct = packed_cotiles(a.C_out);
     a.nz = nz;
     a.inv_n_mrf = a.n_mrf > 0 ? 1.0f / (float)a.n_mrf : 1.0f;
-    a.ablate = IRIS_DIAG_ENV("IRIS_B16_ABLATE", 0);
     int span = 0;
     const int np = a.z_is_phase ? 1 : nz;
     if (np > kMaxGroup) return hipErrorInvalidValue;
@@ -607,16 +598,15 @@ inline hipError_t launch_conv_bf16(Launch& a, int nz, hipStream_t stream) {
     const size_t lds_bytes = window_bytes > scratch_bytes ? window_bytes : scratch_bytes;
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     const int n_t = (a.n_idx + t.T_BLK - 1) / t.T_BLK;
-    a.z_in_y = !a.z_is_phase && nz > 1 && (long long)a.B * nz <= 65535 && IRIS_DIAG_ENV("IRIS_B16_ZMAJOR", 1);
+    a.z_in_y = !a.z_is_phase && nz > 1 && (long long)a.B * nz <= 65535;
     a.n_items = (a.z_is_phase || a.z_in_y) ? n_t : n_t * nz;
     a.n_share = a.z_is_phase ? a.n_co_blk * nz : a.n_co_blk;
-    const int xcd_env = IRIS_DIAG_ENV("IRIS_B16_XCDGROUP", 1);
     // grouped launches carry the batch index in blockIdx.x (item = b * n_items + tile; blockIdx.y is the z index alone
     // when z_in_y, else 1)
     a.fold_b = IRIS_B16_XCD_FOLD;
     const long long items_all = (long long)a.n_items * (a.fold_b ? a.B : 1);
     const long long gx_grouped = ((items_all + 7) / 8) * 8 * a.n_share;
-    a.xcd_group = xcd_env && a.n_share > 1 && items_all >= 64 && gx_grouped < 0x7fffffffLL;   // (a few items would leave XCDs without work)
+    a.xcd_group = a.n_share > 1 && items_all >= 64 && gx_grouped < 0x7fffffffLL;   // (a few items would leave XCDs without work)
     const long long gx = a.xcd_group ? gx_grouped : (long long)a.n_items * a.n_share;
     if (gx > 0x7fffffffLL) return hipErrorInvalidValue;
     a.fold_b = a.fold_b && a.xcd_group;
@@ -631,14 +621,11 @@ inline hipError_t launch_conv_bf16(Launch& a, int nz, hipStream_t stream) {
 #define IRIS_B16_CASE(WT_, WC_, MT_, NT_, CIC_, MINB_)                                            \
     if (t.WT == WT_ && t.WC == WC_ && t.MT == MT_ && t.NT == NT_ && t.CIC == CIC_ && t.MINB == MINB_) \
         IRIS_B16_LAUNCH(conv_mfma_bf16_kernel<WT_, WC_, MT_, NT_, CIC_, MINB_>)
-    IRIS_B16_CASE(4, 1, 4, 1, 32, 2); IRIS_B16_CASE(4, 1, 4, 1, 32, 3); IRIS_B16_CASE(4, 1, 4, 1, 32, 4);
-    IRIS_B16_CASE(4, 1, 3, 1, 32, 4); IRIS_B16_CASE(4, 1, 3, 1, 64, 4); IRIS_B16_CASE(4, 1, 1, 1, 64, 4);
-    IRIS_B16_CASE(4, 1, 2, 1, 32, 2); IRIS_B16_CASE(4, 1, 2, 1, 32, 3); IRIS_B16_CASE(4, 1, 2, 1, 32, 4);
-    IRIS_B16_CASE(4, 1, 4, 1, 64, 2); IRIS_B16_CASE(4, 1, 4, 1, 64, 3); IRIS_B16_CASE(4, 1, 4, 1, 64, 4);
-    IRIS_B16_CASE(4, 1, 2, 1, 64, 2); IRIS_B16_CASE(4, 1, 2, 1, 64, 3); IRIS_B16_CASE(4, 1, 2, 1, 64, 4);
-    IRIS_B16_CASE(4, 1, 2, 2, 64, 2); IRIS_B16_CASE(4, 1, 2, 2, 64, 3); IRIS_B16_CASE(4, 1, 2, 2, 64, 4);
-    IRIS_B16_CASE(4, 1, 1, 2, 64, 2); IRIS_B16_CASE(4, 1, 1, 2, 64, 3); IRIS_B16_CASE(4, 1, 1, 2, 64, 4);
-    IRIS_B16_CASE(2, 2, 2, 2, 64, 2); IRIS_B16_CASE(2, 2, 2, 2, 128, 2); IRIS_B16_CASE(2, 2, 3, 1, 64, 4);
+    IRIS_B16_CASE(4, 1, 3, 1, 32, 4); IRIS_B16_CASE(4, 1, 3, 1, 64, 4);
+#if IRIS_B16_UPS32_MT != 3
+    IRIS_B16_CASE(4, 1, IRIS_B16_UPS32_MT, 1, 32, 4); IRIS_B16_CASE(4, 1, IRIS_B16_UPS32_MT, 1, 64, 4);   // (A/B builds)
+#endif
+    IRIS_B16_CASE(2, 2, 3, 1, 64, 4); IRIS_B16_CASE(2, 2, 2, 2, 64, 2); IRIS_B16_CASE(2, 2, 2, 2, 128, 2);
 #undef IRIS_B16_CASE
 #undef IRIS_B16_LAUNCH
     return hipErrorInvalidValue;

@@ -37,7 +37,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <atomic>
-#include "diag_env.h"
 
 namespace iris {
 
@@ -78,9 +77,6 @@ struct ConvLaunch {
     float* sum_y;        // MRF kernel only: when set, the launch is the last conv step of a stage and stores
                          // mean_j(branch output j) here instead of the per-branch outputs
     float sum_div;       // num_kernels as float
-    unsigned long long* dbg;  // diagnostics only (stamp builds): 7 accumulators, else nullptr
-    int ablate;          // diagnostics only (env IRIS_HIFIGAN_ABLATE): 1 skip staging, 2 weights from one
-                         // address, 4 skip epilogue stores, 8 skip residual read.  Results are wrong.
     int z_serial;        // 1: every block loops over all nz_serial problems of its tile (equal-cost blocks)
     int nz_serial;
     int nz;              // problems (or phases) interleaved along blockIdx.x
@@ -89,7 +85,6 @@ struct ConvLaunch {
     int n_ct;            // number of 32-wide C_out tiles in the packed weights
     unsigned* dyn_counter;  // MRF kernel: when set (zero at launch), blocks take their 2nd, 3rd, ... tile from this
                             // counter instead of a fixed stride (large batches: evens out slow and fast CUs)
-    int stagger, stagger_mod;  // diagnostics only (IRIS_HIFIGAN_STAGGER): blocks of the second residency generation sleep first
     int zb1, zb2;           // MRF kernel, one-branch-per-block mode: blocks [0, zb1) serve branch 2 (k = 11),
                             // [zb1, zb2) branch 1 (k = 7), [zb2, gridDim.x) branch 0 (k = 3)
 };
@@ -210,11 +205,11 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
 
     const float* aptr = lds + (wt * MT * 32 + lo) * S + 4 * hi;
     const f32x4* wlane = wp + (size_t)ct * 64 + lane;
-    const size_t wstep = (a.ablate & 2) ? 0 : (size_t)a.n_ct * 64;  // f32x4 elements per (tap, group)
+    const size_t wstep = (size_t)a.n_ct * 64;  // f32x4 elements per (tap, group)
 
     for (int c0 = 0; c0 < a.C_in; c0 += CIC) {
         if (c0 > 0) __syncthreads();
-        if (!(a.ablate & 1)) stage_input<CIC>(a, p, lds, b, in_row0, R, c0);
+        stage_input<CIC>(a, p, lds, b, in_row0, R, c0);
         __syncthreads();
         if (wave_active) {
             const int g0 = c0 >> 3;
@@ -294,7 +289,7 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     f32x4 r4 = {0.f, 0.f, 0.f, 0.f};
-                    if (p.res && ok[m] && !(a.ablate & 8)) r4 = *reinterpret_cast<const f32x4*>(p.res + offs[m] + 8 * g);
+                    if (p.res && ok[m]) r4 = *reinterpret_cast<const f32x4*>(p.res + offs[m] + 8 * g);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float v = acc[m][4 * g + e] + bias4[e];
@@ -310,7 +305,7 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int co = ct * 32 + 8 * g + 4 * hi;
-                if (ok[m] && co < a.C_out && !(a.ablate & 4)) {
+                if (ok[m] && co < a.C_out) {
                     const f32x4 v = {acc[m][4 * g + 0], acc[m][4 * g + 1], acc[m][4 * g + 2], acc[m][4 * g + 3]};
                     *reinterpret_cast<f32x4*>(p.y + offs[m] + 8 * g) = v;
                 }
@@ -331,8 +326,8 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
                     const size_t off = ((size_t)b * a.L_out + o) * a.C_out + co;
                     float v = acc[m][r] + p.bias[co];
                     if (a.out_act == 1) v = tanhf(v);
-                    if (p.res && !(a.ablate & 8)) v += p.res[off];
-                    if (!(a.ablate & 4)) p.y[off] = v;
+                    if (p.res) v += p.res[off];
+                    p.y[off] = v;
                 }
             }
         }
@@ -357,13 +352,9 @@ __global__ void __launch_bounds__(256) conv_mfma_f32_kernel(const ConvLaunch a) 
     if (a.z_serial) {
         // Equal-cost blocks: one block runs ALL problems (MRF branches, k = 3/7/11) of its tile one
         // after the other, so every block of the launch costs the same whatever mix of kernel
-        // sizes the stage has.
-        // The starting branch rotates with the block index (a.z_serial == 2): blocks that share a CU
-        // are then in different phases (staging / MFMA / epilogue) instead of marching in lock-step.
-        const int rot = a.z_serial == 2 ? (int)(blockIdx.x % a.nz_serial) : 0;
+        // sizes the stage has.  Branches are taken heaviest-first (the packed order is k ascending).
         for (int zi = 0; zi < a.nz_serial; ++zi) {
-            int z = a.nz_serial - 1 - zi + rot;
-            if (z >= a.nz_serial) z -= a.nz_serial;
+            const int z = a.nz_serial - 1 - zi;
             conv_dispatch<WT, WC, MT, CIC>(a, a.p[z], a.p[z].wp, a.out_off, lds);
             if (zi + 1 < a.nz_serial) __syncthreads();
         }
@@ -491,15 +482,13 @@ inline hipError_t launch_conv(ConvLaunch& a, int nz, hipStream_t stream) {
         const int s = (a.p[j].ks - 1) * a.p[j].dil;
         if (s > span) span = s;
     }
-    const int serial_env = IRIS_DIAG_ENV("IRIS_HIFIGAN_ZSERIAL", 1);
-    a.z_serial = (!a.z_is_phase && nz > 1 && serial_env) ? serial_env : 0;
+    a.z_serial = (!a.z_is_phase && nz > 1) ? 1 : 0;
     a.nz_serial = nz;
     if (a.z_serial) nz = 1;
     a.nz = nz;
     // Small grids (conv_pre, the first upsamplers, short utterances): a launch costs one tile's serial
     // time, so when the grid cannot give every CU two blocks the tile height is halved (MT = 1).
     const int n_cu = device_cu_count();
-    const int mt_env = IRIS_DIAG_ENV("IRIS_HIFIGAN_CONV_MT", 0);
     const long long blocks2 = (long long)((a.n_idx + t.T_BLK - 1) / t.T_BLK) * a.n_co_blk * nz * a.B;
     // (the last ConvTranspose1d -- K = 2 taps x 64 channels, 32 output channels: three quarters of a block's life is window load
     //  and store -- runs better as four 35 KB blocks per CU than as two 70 KB ones: 50 -> 43 us at batch 1 x 1000 frames)
@@ -508,14 +497,13 @@ inline hipError_t launch_conv(ConvLaunch& a, int nz, hipStream_t stream) {
 #else
     const bool tall_small_k = a.z_is_phase && t.WT == 4 && a.C_in <= 64;
 #endif
-    const int MT = mt_env ? mt_env : ((blocks2 < 2LL * n_cu || tall_small_k) ? 1 : 2);
+    const int MT = (blocks2 < 2LL * n_cu || tall_small_k) ? 1 : 2;
     const int T_BLK = t.WT * MT * 32;
     // conv_pre of the V1 generator (80 mel bins, channels-first -> 512): one 80-channel chunk instead of 64 + 16.  The launch
     // has 64-128 blocks, so its time is one block's serial time, and each chunk costs a staging round trip and two barriers.
     const int CIC = (a.C_in == 80 && a.x_channels_first && t.WT == 1) ? 80 : t.CIC;
     const size_t lds_bytes = (size_t)(T_BLK + span) * (CIC + 4) * sizeof(float);
     const int n_t = (a.n_idx + T_BLK - 1) / T_BLK;
-    a.ablate = IRIS_DIAG_ENV("IRIS_HIFIGAN_ABLATE", 0);
     dim3 grid((unsigned)(n_t * a.n_co_blk * nz), (unsigned)a.B, 1u), block(256);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
 #define IRIS_LAUNCH_K(...)                                                                        \

@@ -314,7 +314,7 @@ struct ConvtTile { int MT, NT, WR, WC, CIC, MINB; };
 
 // True when LeakyReLU + ConvTranspose1d (k, u) with n_in input tensors can take the GEMM kernel.
 inline bool convt_gemm_b16_applicable(int C_in, int C_out, int k, int u, int L_in, int L_out, int B, int n_in, float slope) {
-    if (!IRIS_DIAG_ENV("IRIS_B16_CONVT_GEMM", IRIS_CONVT_GEMM_B16_DEFAULT)) return false;
+    if (!IRIS_CONVT_GEMM_B16_DEFAULT) return false;
     if (u < 1 || k != 2 * u) return false;                                  // two taps per phase (every V1 upsampler)
     if ((C_in & 63) || (C_out & 31)) return false;
     if (n_in != 1 && n_in != 3) return false;

@@ -293,7 +293,7 @@ inline int convt_blocks(const ConvtTile& t, int n_idx, int n_cols32, int B) {
 
 // True when LeakyReLU + ConvTranspose1d `l` on a single input tensor can take the GEMM kernel.
 inline bool convt_gemm_applicable(int C_in, int C_out, int k, int u, int L_in, int L_out, float slope) {
-    if (!IRIS_DIAG_ENV("IRIS_HIFIGAN_CONVT_GEMM", IRIS_CONVT_GEMM_DEFAULT)) return false;
+    if (!IRIS_CONVT_GEMM_DEFAULT) return false;
     if (u < 1 || k != 2 * u) return false;                                  // two taps per phase (every V1 upsampler)
     if ((C_in & 63) || (C_out & 31)) return false;
     if (((u * (C_out / 32)) & 1)) return false;                             // at least the 128 x 64 block shape

@@ -10,7 +10,6 @@
 #include <vector>
 
 #include "../../include/iris_hifigan.h"
-#include "diag_env.h"
 #include "device_info.h"
 #include <new>
 
@@ -70,7 +69,7 @@ struct ConvLayer {       // one Conv1d / ConvTranspose1d, weights resident on th
     size_t w_floats = 0;                              // packed size
     size_t ref_w_floats = 0;                          // size in the reference layout
     size_t w16_off = 0, w16_halfs = 0;                // bf16 path: offset/size (bf16 elements) in blob16
-    size_t ws3_off = 0;                               // split path: offset (bf16 elements) of the hi plane in blob_s3
+    size_t ws3_off = 0;                               // split path (ResBlock convs): offset (bf16 elements) of the hi plane in blob_s3
     size_t w16f_off = (size_t)-1;                     // small-problem kernel: float offset of the 16x16x4 packing in blob_w16, or -1
 };
 
@@ -214,8 +213,6 @@ int f32s_build_blob(iris_hifigan_handle* h, const float* weights_host);   // pac
 struct F32sStep { const float* x[IRIS_HIFIGAN_MAX_KERNELS]; const float* res[IRIS_HIFIGAN_MAX_KERNELS];
                   float* y[IRIS_HIFIGAN_MAX_KERNELS]; const ConvLayer* layer[IRIS_HIFIGAN_MAX_KERNELS]; };
 bool f32s_step_applicable(const iris_hifigan_handle* h, int C, int L, int nk);
-bool f32s_ups_applicable(const iris_hifigan_handle* h, const ConvLayer& l, int L_in);
-int f32s_launch_ups(iris_hifigan_handle* h, const ConvLayer& l, const float* x, float* y, int B, int L_in, hipStream_t stream);
 // sum_y: when set, the step stores only the mean of the branch outputs there (last conv step of a stage)
 int f32s_launch_step(iris_hifigan_handle* h, const F32sStep& st, int nk, int B, int L, int C, float* sum_y, hipStream_t stream);
 

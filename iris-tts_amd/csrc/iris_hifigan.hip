@@ -495,13 +495,9 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             TRY(prof.begin(1, (int)i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
                            4.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out +
                                   (double)l.ref_w_floats + l.C_out)));
-            // split-product mode: single-input upsamplers (conv_pre output, or the folded branch mean) on split products.
-            // Off in the release library: with the upsamplers split as well the worst observed waveform error grows
-            // from 2e-5 to 5e-5 -- still inside 1e-4, but the mode keeps the wider margin (diagnostic builds: S3UPS=1).
-            const int s3_ups = IRIS_DIAG_ENV("IRIS_HIFIGAN_S3UPS", 0);
-            if (s3_ups && dtype == IRIS_HIFIGAN_F32_SPLIT && a.in_act == IN_ACT_LRELU && f32s_ups_applicable(h, l, L))
-                TRY(f32s_launch_ups(h, l, a.p[0].x, a.p[0].y, B, L, stream));
-            else if ((a.in_act == IN_ACT_LRELU || (a.in_act == IN_ACT_MRF_LRELU && nk == 3)) &&
+            // (split-product mode keeps the upsamplers in fp32: split as well, they grew the worst observed waveform error
+            //  from 2e-5 to 5e-5 -- still inside 1e-4, but the mode keeps the wider margin)
+            if ((a.in_act == IN_ACT_LRELU || (a.in_act == IN_ACT_MRF_LRELU && nk == 3)) &&
                      convt_gemm_applicable(l.C_in, l.C_out, l.k, l.u, L, L_out, slope)) {
                 // the whole layer as ONE GEMM [L + 1, 2 C_in] x [2 C_in, u C_out] (convt_mfma_f32.h), bit for bit the polyphase
                 // launches below; its input is one tensor (conv_pre's output, or the MRF mean the previous stage's last step
@@ -518,8 +514,6 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
         // ---- MRF: num_kernels ResBlocks advance together (hifigan_pretrained.py:64-71,131-136) ----
         const int nd = h->cfg.num_dilations[0];
         const double n_el = fB * L_out * st.C;
-        const int use_mrf = IRIS_DIAG_ENV("IRIS_HIFIGAN_MRF", 1);
-        const int use_sum = IRIS_DIAG_ENV("IRIS_HIFIGAN_MRFSUM", 1);
         // one conv step (half 0: convs1[m], half 1: convs2[m] + residual) of all branches, separate launches
         auto fill_step = [&](ConvLaunch& a, int m, int half, double& flops, double& wbytes) {
             init_launch(a);
@@ -539,6 +533,19 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             a.B = B; a.L_in = L_out; a.L_out = L_out; a.C_in = st.C; a.C_out = st.C;
             a.n_idx = L_out; a.in_act = IN_ACT_LRELU; a.slope = slope;
             a.dyn_counter = dyn_tiles ? h->tile_counters + ((int)i * 2 * nd + 2 * m + half) : nullptr;
+        };
+        // The stage's last step `a` as the MRF kernel's summing launch *b, which forms mean_j(y_j) itself: it processes
+        // p[2], p[1], p[0]; passing the branches reversed makes that resblock 0, 1, 2 -- the reference's summation order
+        // (hifigan_pretrained.py:131-137).  The mean goes to y[0] (in place: each lane overwrites only elements it read
+        // itself as branch 0's residual).  Small problems run one branch per block -- mrf_plan's latency modes -- and
+        // cannot sum.
+        auto summing_last_step = [&](const ConvLaunch& a, ConvLaunch& b) -> bool {
+            if (nk != 3 || !mrf_kernel_applicable(a, nk)) return false;
+            const MrfPlan pq = mrf_plan(a, true);
+            b = a;
+            b.p[0] = a.p[2]; b.p[2] = a.p[0];
+            b.sum_y = ws + w.y[0]; b.sum_div = (float)nk;
+            return mrf_kernel_applicable(b, nk) && !pq.zpar && !pq.small;
         };
         // ---- fused conv pairs (mrf_pair_f32.h; C = 32 / 64, exact fp32): conv1 -> xt in LDS -> conv2 + residual in ONE launch,
         // bit for bit the two separate launches.  A fused pair cannot run in place, so the running x of a branch alternates
@@ -565,39 +572,27 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             return ok;
         };
         int n_fused = 0;
-        bool pf = false;            // the fused pairs run on the persistent kernel (mrf_pair_f32_pf.h)
-        bool fused_sum = false;     // ... and the stage's last pair forms the MRF mean itself (no persistent summing launches)
-        if (dtype == IRIS_HIFIGAN_F32 && use_mrf && !(stop.stage == (int)i && !(stop.step & 1))) {
+        bool fused_sum = false;     // the stage's last pair forms the MRF mean itself (mrf_pair_f32_pf.h; no persistent summing launches)
+        if (dtype == IRIS_HIFIGAN_F32 && !(stop.stage == (int)i && !(stop.step & 1))) {
             bool all_ok = true;
             PairLaunchF32 pa0; double f0, wb0;
             for (int m = 0; m < nd && all_ok; ++m) all_ok = fill_pair(pa0, m, f0, wb0) && pair_f32_applicable(pa0, nk);
             if (all_ok) {
-                bool sums = false;          // (the same decision as at the last step below)
-                if (use_sum && nk == 3) {
-                    ConvLaunch a; double f, wb;
-                    fill_step(a, nd - 1, 1, f, wb);
-                    if (mrf_kernel_applicable(a, nk)) {
-                        const MrfPlan pq = mrf_plan(a, true);
-                        ConvLaunch b = a;
-                        b.p[0] = a.p[2]; b.p[2] = a.p[0];
-                        b.sum_y = ws + w.y[0]; b.sum_div = (float)nk;
-                        sums = mrf_kernel_applicable(b, nk) && !pq.zpar && !pq.small;
-                    }
-                }
+                ConvLaunch a, b; double f, wb;
+                fill_step(a, nd - 1, 1, f, wb);
+                const bool sums = summing_last_step(a, b);      // (the same decision as at the last step below)
                 // The stage's LAST pair on the persistent summing kernel (mrf_pair_f32_pf.h: a block runs the three branches of
                 // its tile and stores only the MRF mean -- no xt, no per-branch outputs, one launch instead of the persistent
                 // kernel's two): taken where its whole-tile jobs fill at least four rounds of the chip well.  Measured
                 // (profiles/r03_notes.md): +3 % on the C = 32 stage and +0.6 % on the step at batch 32 x 500, neutral at
                 // batch 1 x 1000, a loss where a launch is one or two rounds (its jobs are 21 tap-units against 11 / 7 / 3).
                 // The non-summing pairs stay on the one-job-per-block kernel: as persistent, prefetching blocks they
-                // were 3-5 % slower at every size (diagnostic builds: IRIS_HIFIGAN_PAIR_PF_MODE=2).
+                // were 3-5 % slower at every size.
                 const PairPfTileF32 pt = pair_pf_f32_tile(st.C);
                 const long long tiles_pf = (long long)((L_out + (pt.M - 10) - 1) / (pt.M - 10)) * B;
-                pf = IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_PF_MODE", 0) == 2 && pair_pf_f32_applicable(pa0, nk, false);
-                const int sum_env = IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_SUM", 1);          // 0 never, 1 by size, 2 always
-                if (use_sum && sum_env != 0 && pair_pf_f32_applicable(pa0, nk, true)) {
-                    const PairPfPlanF32 sp = pair_pf_f32_plan(tiles_pf, device_cu_count(), pt.MINB, true);
-                    fused_sum = sum_env == 2 || (sp.efficiency >= 0.85 && tiles_pf >= 4LL * device_cu_count() * sp.per_cu);
+                if (pair_pf_f32_applicable(pa0, nk)) {
+                    const PairPfPlanF32 sp = pair_pf_f32_plan(tiles_pf, device_cu_count(), pt.MINB);
+                    fused_sum = sp.efficiency >= 0.85 && tiles_pf >= 4LL * device_cu_count() * sp.per_cu;
                 }
                 n_fused = (fused_sum || !sums) ? nd : nd - 1;
             }
@@ -616,11 +611,10 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
                 // algorithmic FLOP / bytes (accounting L) are those of both steps; the record carries the second step's index
                 TRY(prof.begin(2, (int)i, 2 * m + 1, flops, 4.0 * n_el * nk * 5 + wbytes));
                 // (a zeroed counter word per persistent launch: the upper half of the per-forward counters)
-                unsigned* const ctr = (pf_counters && IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_PF_DYN", 1)) ? h->tile_counters + kTileCounterWords / 2 + ((int)i * nd + m) : nullptr;
-                if ((is_sum || pf) && ctr) HIP_TRY(zero_counters());
-                if (is_sum)  HIP_TRY(launch_pair_f32_pf(pa, nk, ws + w.y[0], ctr, stream));
-                else if (pf) HIP_TRY(launch_pair_f32_pf(pa, nk, nullptr, ctr, stream));
-                else         HIP_TRY(launch_pair_f32(pa, nk, stream));
+                unsigned* const ctr = pf_counters ? h->tile_counters + kTileCounterWords / 2 + ((int)i * nd + m) : nullptr;
+                if (is_sum && ctr) HIP_TRY(zero_counters());
+                if (is_sum) HIP_TRY(launch_pair_f32_pf(pa, nk, ws + w.y[0], ctr, stream));
+                else        HIP_TRY(launch_pair_f32(pa, nk, stream));
                 TRY(prof.end());
                 for (int j = 0; j < nk; ++j) cur_x[j] = pa.p[j].y;
                 if (m == nd - 1) prev_summed = is_sum;
@@ -648,30 +642,19 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
                     }
                     // last step of the stage: the kernel folds the branch mean (written to y[0]; a lane overwrites only
                     // elements it has read itself as branch 0's residual)
-                    const bool fold = IRIS_DIAG_ENV("IRIS_HIFIGAN_S3SUM", 1) && last_step;
-                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, fold ? ws + w.y[0] : nullptr, stream));
+                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, last_step ? ws + w.y[0] : nullptr, stream));
                     launched = true;
-                    if (last_step) prev_summed = fold;
+                    if (last_step) prev_summed = true;
                 }
-                if (!launched && use_mrf && use_sum && last_step && nk == 3) {
-                    // last step of the stage: the MRF kernel can form mean_j(y_j) itself.  It processes
-                    // p[2], p[1], p[0]; passing the branches reversed makes that resblock 0, 1, 2 -- the
-                    // reference's summation order (hifigan_pretrained.py:131-137).  The mean goes to y[0]
-                    // (in place: each lane overwrites only elements it read itself as branch 0's residual).
-                    ConvLaunch b = a;
-                    b.p[0] = a.p[2]; b.p[2] = a.p[0];
-                    b.sum_y = ws + w.y[0]; b.sum_div = (float)nk;
-                    // (small problems run one branch per block -- mrf_plan's latency modes -- and cannot sum)
-                    const MrfPlan pq = mrf_kernel_applicable(a, nk) ? mrf_plan(a, true) : MrfPlan{};
-                    if (mrf_kernel_applicable(b, nk) && !pq.zpar && !pq.small) {
-                        HIP_TRY(launch_mrf_conv(b, nk, stream));
-                        launched = true; prev_summed = true;
-                    }
+                ConvLaunch b;
+                if (!launched && last_step && summing_last_step(a, b)) {
+                    HIP_TRY(launch_mrf_conv(b, nk, stream));
+                    launched = true; prev_summed = true;
                 }
                 if (!launched) {
                     if (last_step) prev_summed = false;
-                    if (use_mrf && mrf_kernel_applicable(a, nk)) HIP_TRY(launch_mrf_conv(a, nk, stream));
-                    else                                         HIP_TRY(launch_conv(a, nk, stream));
+                    if (mrf_kernel_applicable(a, nk)) HIP_TRY(launch_mrf_conv(a, nk, stream));
+                    else                              HIP_TRY(launch_conv(a, nk, stream));
                 }
                 TRY(prof.end());
                 if (stop.stage == (int)i && stop.step == 2 * m + half) {
@@ -1011,7 +994,8 @@ int32_t iris_hifigan_op_mrf_pair(const float* const* x_dev, const float* const* 
     pa.B = B; pa.L = L; pa.C = C; pa.slope = slope;
     if (!pair_f32_applicable(pa, nk)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "shape cannot take the fused fp32 pair kernel");
     if (mode == 1 || mode == 2) {
-        if (!pair_pf_f32_applicable(pa, nk, mean_dev != nullptr)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "shape cannot take the persistent pair kernel");
+        if (!mean_dev) return fail(IRIS_HIFIGAN_UNSUPPORTED, "the persistent pair kernel exists in its summing form only (mean_dev)");
+        if (!pair_pf_f32_applicable(pa, nk)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "shape cannot take the persistent pair kernel");
         struct Word { unsigned* p = nullptr; ~Word() { if (p) (void)hipFree(p); } } ctr;
         if (mode == 1) {                                    // blocks draw their jobs from a counter (mode 2: fixed stride)
             HIP_TRY(hipMalloc(&ctr.p, sizeof(unsigned)));

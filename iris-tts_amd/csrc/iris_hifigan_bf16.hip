@@ -91,8 +91,6 @@ int f32s_build_blob(iris_hifigan_handle* h, const float* weights_host) {
         if (st.C < 32 || (st.C & 31)) return IRIS_HIFIGAN_OK;          // mode unavailable for this config
     size_t off = 0;
     for (auto& st : h->stages) {
-        st.up.ws3_off = off;
-        off += (2 * s3::packed_convt_plane_halfs(st.up.C_in, st.up.C_out, st.up.k, st.up.u) + 127) & ~(size_t)127;
         for (size_t j = 0; j < st.c1.size(); ++j)
             for (int half = 0; half < 2; ++half)
                 for (auto& l : (half == 0 ? st.c1[j] : st.c2[j])) {
@@ -108,7 +106,6 @@ int f32s_build_blob(iris_hifigan_handle* h, const float* weights_host) {
         uint16_t* dst = host.data() + l.ws3_off;
         const ConvLayer* lp = &l;
         if (l.kind == 0 && &l != &h->pre) jobs.push_back([=] { s3::pack_conv1d_split(src, lp->C_in, lp->C_out, lp->k, dst); });
-        if (l.kind == 1) jobs.push_back([=] { s3::pack_convt_split(src, lp->C_in, lp->C_out, lp->k, lp->u, dst); });
         src += l.ref_w_floats + l.C_out;
     });
     run_host_jobs(jobs);
@@ -159,20 +156,6 @@ void fill_ups(s3::Launch& a, const ConvLayer& l, const float* x, const void* wp,
     a.plane_bytes[0] = (unsigned)(s3::packed_convt_plane_halfs(l.C_in, l.C_out, l.k, l.u) * 2);
 }
 }  // namespace
-
-bool f32s_ups_applicable(const iris_hifigan_handle* h, const ConvLayer& l, int L_in) {
-    if (!h->blob_s3 || l.kind != 1 || l.u > 65535) return false;
-    s3::Launch a;
-    fill_ups(a, l, nullptr, nullptr, nullptr, nullptr, 1, L_in, 0.f);
-    return s3::applicable(a, l.u) && (double)s3::packed_convt_plane_halfs(l.C_in, l.C_out, l.k, l.u) * 4.0 < 2147483648.0;
-}
-
-int f32s_launch_ups(iris_hifigan_handle* h, const ConvLayer& l, const float* x, float* y, int B, int L_in, hipStream_t stream) {
-    s3::Launch a;
-    fill_ups(a, l, x, h->blob_s3 + l.ws3_off, h->blob + l.b_off, y, B, L_in, h->cfg.lrelu_slope);
-    HIP_TRY(s3::launch(a, l.u, stream));
-    return IRIS_HIFIGAN_OK;
-}
 
 uint64_t bf16_workspace_bytes(const iris_hifigan_handle* h, int B, int T) {
     return ws16_layout(h, B, T).total * sizeof(uint16_t);

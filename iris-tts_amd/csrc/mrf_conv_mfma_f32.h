@@ -26,12 +26,6 @@
 
 namespace iris {
 
-#ifdef IRIS_MRF_DIAG
-#define IRIS_MRF_ABLATE(a) ((a).ablate)
-#else
-#define IRIS_MRF_ABLATE(a) 0
-#endif
-
 #ifndef IRIS_MRF_RING_MT1
 #define IRIS_MRF_RING_MT1 4              // weight fragments in flight (groups ahead), half-height / full-height tiles (C >= 64)
 #endif
@@ -125,15 +119,10 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
     const int n_t = (L + T_BLK - 1) / T_BLK;
     const int tiles_per_item = n_t * a.n_co_blk;
     const int n_tiles = tiles_per_item * a.B;
-    const unsigned wbytes_group = (IRIS_MRF_ABLATE(a) & 2) ? 0u : (unsigned)a.n_ct * 64u * 16u;  // bytes per (tap, group)
+    const unsigned wbytes_group = (unsigned)a.n_ct * 64u * 16u;  // bytes per (tap, group)
     const unsigned tap_bytes = (unsigned)a.Gp * wbytes_group;
     const float* aptr = lds + (wt * MT * 32 + lo) * S + 4 * hi;
     const float slope = a.slope;
-#ifdef IRIS_MRF_DIAG
-    const int ablate = a.ablate;          // diagnostic builds: runtime ablation switches
-#else
-    constexpr int ablate = 0;
-#endif
     const unsigned tensor_bytes = (unsigned)L * (unsigned)C * 4u;
     // LEAN: [3][C_out] biases behind the window(s) and the next-tile word (launch_mrf_conv sizes the dynamic LDS for it)
     float* const lds_bias = lds + BUF_FLOATS + 4;
@@ -146,17 +135,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         }
         // (visible to every wave after the prologue's barrier; the table is never rewritten)
     }
-#ifdef IRIS_MRF_BLOCKLOG
-    // diagnostic build only (make variant NAME=blocklog EXTRA=-DIRIS_MRF_BLOCKLOG): every block leaves its start / end time on the
-    // constant 100 MHz clock and the CU it ran on, for a per-CU timeline of the launch
-    const unsigned long long blk_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef IRIS_MRF_DIAG
-    // A/B (profiles/r03_notes.md): the two blocks of a CU run the same equal-cost sequence and would stay in lock-step; delay
-    // the second residency generation by a.stagger x 1,024 cycles
-    if (a.stagger > 0 && a.stagger_mod > 0 && (((int)blockIdx.x / a.stagger_mod) & 1))
-        for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(16);
-#endif
 
     // A tile = (batch item, time tile, C_out block).  Everything a phase needs to know about it:
     struct Tile {
@@ -192,7 +170,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
     f32x4 st[NQ];
     auto stage_vbase = [&](int in_row0, int c0) -> unsigned {
         const int ci = c0 + 4 * q_lane;
-        if (ci >= C || (ablate & 1)) return kOobOffset;
+        if (ci >= C) return kOobOffset;
         return (unsigned)((in_row0 + r_lane) * C + ci) * 4u;
     };
     auto stage_load_one = [&](int i, __amdgpu_buffer_rsrc_t xr, unsigned vbase, int R) {
@@ -212,24 +190,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             }
     };
 
-#ifdef IRIS_MRF_STAMPS
-    // diagnostic build only: per-wave cycle totals of [0] MFMA loops, [1] epilogues, [2] barrier before
-    // the LDS write, [3] LDS write, [4] barrier after it, [5] everything (kernel entry to exit)
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [6] ring copy + bias/residual adds, [7] SUM + stores (parts of [1])
-    auto stamp = [&]() -> unsigned long long {
-        unsigned long long t;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return t;
-    };
-    const unsigned long long t_entry = stamp();
-#define IRIS_STAMP(var) const unsigned long long var = stamp()
-#define IRIS_SEG(i, a_, b_) seg[i] += (b_) - (a_)
-#else
-#define IRIS_STAMP(var)
-#define IRIS_SEG(i, a_, b_)
-#endif
     f32x16 acc[MT];
     f32x16 sumv[MT];      // SUM kernels only: running MRF sum of the branch outputs of this tile
     f32x4 bw[DB + 1];     // ring of weight fragments; groups 0..DB-1 of a phase are requested by the
@@ -254,7 +214,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         // with channels >= C_out get an out-of-range ovoff4.  A branch without residual uses a
         // zero-length descriptor, whose loads return 0.
         const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + t.batch_off, tensor_bytes);
-        const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + t.batch_off : p.y, (p.res && !(ablate & 8)) ? tensor_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + t.batch_off : p.y, p.res ? tensor_bytes : 0u);
         // loaded here, not in the epilogue: vmcnt retires in order, so a load issued in the epilogue
         // would have to wait for every prefetch issued by the last MFMA groups
         f32x4 bias4[4];                                  // channels co4 + 8g + {0..3}
@@ -308,7 +268,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                 return buf_load4(wrn, voff_next, wsoffn + (unsigned)(n - NG) * wbytes_group);   // n-NG < DB <= GPC: tap 0
             };
             f32x4 av[LEAN ? 1 : 2][MT];
-            IRIS_STAMP(ts0);
 #pragma unroll
             for (int m = 0; m < MT; ++m) av[0][m] = *reinterpret_cast<const f32x4*>(a_ptr(0) + m * 32 * S);
             // Per group: 4*MT MFMAs of group n, and -- independent of them -- the requests for later
@@ -323,13 +282,11 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             const unsigned wvoffn_eff = has_next ? wvoffn : kOobOffset;
 #pragma unroll
             for (int n = 0; n < NG; ++n) {
-                if (!(ablate & 16)) {
-                    if (n < NQ) stage_load_one(n, xrn, vbn_eff, Rn);
+                if (n < NQ) stage_load_one(n, xrn, vbn_eff, Rn);
 #pragma unroll
-                    for (int j = 0; j < RPG; ++j)
-                        if (n * RPG + j < NRES) res_load(n * RPG + j, res_voff);
-                }
-                if (!(ablate & 32)) bw[(n + DB) % (DB + 1)] = b_load(n + DB, wvoffn_eff);
+                for (int j = 0; j < RPG; ++j)
+                    if (n * RPG + j < NRES) res_load(n * RPG + j, res_voff);
+                bw[(n + DB) % (DB + 1)] = b_load(n + DB, wvoffn_eff);
                 if constexpr (LEAN) {
                     // m-major: row tile m's four MFMAs, then its fragment of group n + 1 into the same registers
 #pragma unroll
@@ -380,8 +337,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             }
 #pragma unroll
             for (int i = NG; i < NQ; ++i) stage_load_one(i, xrn, vbn_eff, Rn);
-            IRIS_STAMP(ts1);
-            IRIS_SEG(0, ts0, ts1);
             // the next phase expects its groups 0..DB-1 in ring slots 0..DB-1: they were loaded into
             // slots (NG + d) % (DB+1)
             {
@@ -416,10 +371,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             acc[m][4 * g + e] = (acc[m][4 * g + e] + bias4[g][e]) + resv[m * 4 + g][e];
-#ifdef IRIS_MRF_STAMPS
-                const unsigned long long ts1b = stamp();
-                seg[6] += ts1b - ts1;
-#endif
                 if constexpr (SUM) {
                     // Last conv step of the stage: the block has all branch outputs of its tile, so the MRF
                     // sum and the division by num_kernels (hifigan_pretrained.py:131-137) happen here, in
@@ -445,8 +396,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                         const f32x16& src = SUM ? sumv[idx / 4] : acc[idx / 4];
                         const int g = idx % 4;
                         const f32x4 v = {src[4 * g + 0], src[4 * g + 1], src[4 * g + 2], src[4 * g + 3]};
-                        if (!(ablate & 4) || v.x == 1.2345e-30f)
-                            buf_store4(v, yo, t.ovoff4, (unsigned)((idx / 4) * 32 * C + 8 * g) * 4u);
+                        buf_store4(v, yo, t.ovoff4, (unsigned)((idx / 4) * 32 * C + 8 * g) * 4u);
                     }
                     asm volatile("s_nop 1");
                     stored = true;
@@ -463,8 +413,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int idx = 0; idx < MT * 4; ++idx)
-                        if (!(ablate & 4) || outv[idx].x == 1.2345e-30f)
-                            buf_store4(outv[idx], yo, t.ovoff4, (unsigned)((idx / 4) * 32 * C + 8 * (idx % 4)) * 4u);
+                        buf_store4(outv[idx], yo, t.ovoff4, (unsigned)((idx / 4) * 32 * C + 8 * (idx % 4)) * 4u);
                     // explicit wait states behind the store group as well: LLVM's store-data hazard handling skips MUBUF
                     // stores wider than 64 bits whose soffset is an SGPR -- exactly this form (checked in the ISA: the data
                     // registers of the group are next written only by the following branch, see the keep-alive below)
@@ -473,16 +422,9 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            IRIS_STAMP(ts2);
-            IRIS_SEG(1, ts1, ts2);
-#ifdef IRIS_MRF_STAMPS
-            if (last) seg[7] += ts2 - ts1;
-#endif
             if (has_next) {
                 __syncthreads();          // every wave is done reading this chunk's window
-                IRIS_STAMP(ts3);
                 stage_write_all(Rn);
-                IRIS_STAMP(ts4);
                 if (stored) {
                     // keep the epilogue's store-data registers allocated until here: nothing may be
                     // written into them right behind the buffer_store_dwordx4s that read them
@@ -499,8 +441,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                     }
                 }
                 __syncthreads();
-                IRIS_STAMP(ts5);
-                IRIS_SEG(2, ts2, ts3); IRIS_SEG(3, ts3, ts4); IRIS_SEG(4, ts4, ts5);
             }
         }
     };
@@ -630,23 +570,6 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             t = tn;
         }
     }
-#ifdef IRIS_MRF_BLOCKLOG
-    if (tid == 0 && a.dbg) {
-        unsigned long long* rec = a.dbg + 4 * (size_t)blockIdx.x;
-        rec[0] = blk_t0;
-        rec[1] = __builtin_amdgcn_s_memrealtime();
-        rec[2] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));      // HW_REG_HW_ID: cu / sh / se
-        rec[3] = (unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11));     // HW_REG_XCC_ID
-    }
-#endif
-#ifdef IRIS_MRF_STAMPS
-    seg[5] = stamp() - t_entry;
-    if (lane == 0 && a.dbg) {
-        for (int i = 0; i < 6; ++i) atomicAdd(a.dbg + i, seg[i]);
-        atomicAdd(a.dbg + 6, 1ull);
-        atomicAdd(a.dbg + 8, seg[6]); atomicAdd(a.dbg + 9, seg[7]);
-    }
-#endif
 }
 
 #ifndef IRIS_KERNELS_ONLY     // (register-count probes instantiate single kernels: tools/kernel_probe.sh)
@@ -700,15 +623,14 @@ inline int mrf_cu_count() { return device_cu_count(); }
 // takes  shorter + (longer - shorter) / kLoneSpeed,  the launch the slowest CU.  Half-height tiles cost 6 % per unit (more
 // window per output row), the snake order 4 % (blocks end unevenly), fixed ranges 2 %.  Over the 66 measured (shape, stage)
 // cases the model's choice is within 2.5 % of the best forced plan, 0.1 % on average.
-// `force` (>= 0: the single-step test entry point, the diagnostic build's IRIS_HIFIGAN_MRFPLAN, or a calibration build's
-// IRIS_MRF_FORCE_PLAN) pins the mode: 0 full-height tiles, 1 half-height tiles, 2 half-height + one branch per block,
+// `force` (>= 0: the single-step test entry point or a calibration build's IRIS_MRF_FORCE_PLAN) pins the mode: 0 full-height tiles, 1 half-height tiles, 2 half-height + one branch per block,
 // 3 the round-1 rule, 4 the small-problem kernel, 5 / 6 snake-ordered jobs at half / full tile height.
 constexpr double kLoneSpeed = 1.8, kHalfHeightCost = 1.06, kSnakeCost = 1.04, kFixedRangeCost = 1.02;
 
-inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_env, int per_cu) {
+inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_env) {
     const ConvTile t = pick_tile(a.C_in, a.C_out);
     const int n_cu = mrf_cu_count();
-    const long long slots = (long long)n_cu * per_cu;
+    const long long slots = (long long)n_cu * IRIS_MRF_MINWAVES;
     const int n_co_blk = (a.C_out + t.CO_BLK - 1) / t.CO_BLK;
     auto tiles = [&](int MT) { return (long long)((a.L_out + t.WT * MT * 32 - 1) / (t.WT * MT * 32)) * n_co_blk * a.B; };
     static const int cost[3] = {3, 7, 11};            // branch 0, 1, 2
@@ -767,7 +689,7 @@ inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_
     if (allow_zpar && n1 > 0 && (zpar_chain = split(slots, nb)) < 1e29) {
         zpar_units = ranges_time(nb);
         long long nb1[3] = {1, 1, 1};
-        if (nb[0] + nb[1] + nb[2] > n_cu && IRIS_DIAG_ENV("IRIS_HIFIGAN_ZPAR_ONE_PER_CU", IRIS_ZPAR_ONE_PER_CU_DEFAULT) && split(n_cu, nb1) < 1e29) {
+        if (nb[0] + nb[1] + nb[2] > n_cu && IRIS_ZPAR_ONE_PER_CU_DEFAULT && split(n_cu, nb1) < 1e29) {
             const double u1 = ranges_time(nb1);
             if (u1 < zpar_units) { zpar_units = u1; nb[0] = nb1[0]; nb[1] = nb1[1]; nb[2] = nb1[2]; }
         }
@@ -803,7 +725,7 @@ inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_
         double best = serial(2);
         { const double u = serial(1); if (u < 0.999 * best) { best = u; pl.MT = 1; } }
         if (zpar_units < 0.999 * best) { best = zpar_units; pl.MT = 1; pl.zpar = true; }
-        if (zdyn_ok && IRIS_DIAG_ENV("IRIS_HIFIGAN_ZDYN", IRIS_MRF_ZDYN_DEFAULT)) {
+        if (zdyn_ok && IRIS_MRF_ZDYN_DEFAULT) {
             for (int MT = 2; MT >= 1; --MT) {
                 const double u = snake(MT);
                 if (u < 0.999 * best) { best = u; pl.MT = MT; pl.zpar = pl.zdyn = true; }
@@ -819,8 +741,7 @@ inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_
         double longest = chain(2);
         if (chain(1) < longest) longest = chain(1);
         if (zpar_chain * 1.03 * 1.06 < longest) longest = zpar_chain * 1.03 * 1.06;
-        if (small_ok && IRIS_DIAG_ENV("IRIS_HIFIGAN_MRFSMALL", 1) &&
-            mrf_small_cycles(a, 3) < 0.9 * longest * (double)a.C_in * 32.0) {
+        if (small_ok && mrf_small_cycles(a, 3) < 0.9 * longest * (double)a.C_in * 32.0) {
             pl.small = true; pl.zpar = pl.zdyn = false; pl.MT = 1;
         }
     }
@@ -839,26 +760,20 @@ inline MrfPlan mrf_plan_uncached(const ConvLaunch& a, bool allow_zpar, int plan_
 
 // The plan of a (shape, mode) is the same in every forward: a few entries are remembered per thread.
 inline MrfPlan mrf_plan(const ConvLaunch& a, bool allow_zpar, int force = -1) {
-    const int per_cu_env = IRIS_DIAG_ENV("IRIS_HIFIGAN_PERCU", 0);
-    const int plan_env = force >= 0 ? force : IRIS_DIAG_ENV("IRIS_HIFIGAN_MRFPLAN", IRIS_MRF_FORCE_PLAN);
-    const int per_cu = per_cu_env > 0 ? per_cu_env : IRIS_MRF_MINWAVES;
-#ifdef IRIS_MRF_DIAG
-    return mrf_plan_uncached(a, allow_zpar, plan_env, per_cu);       // (environment switches may change between calls)
-#else
-    struct Entry { int key[8]; MrfPlan pl; bool used; };
+    const int plan_env = force >= 0 ? force : IRIS_MRF_FORCE_PLAN;
+    struct Entry { int key[7]; MrfPlan pl; bool used; };
     static thread_local Entry cache[16] = {};
     static thread_local int next = 0;
     const bool has16 = a.p[0].wp16 && a.p[1].wp16 && a.p[2].wp16;      // (the small-problem kernel's packing: part of its applicability)
-    const int key[8] = {a.C_in, a.C_out, a.L_out, a.B, (allow_zpar ? 1 : 0) | (has16 ? 2 : 0) | (a.sum_y ? 4 : 0), plan_env, mrf_cu_count(), per_cu};
+    const int key[7] = {a.C_in, a.C_out, a.L_out, a.B, (allow_zpar ? 1 : 0) | (has16 ? 2 : 0) | (a.sum_y ? 4 : 0), plan_env, mrf_cu_count()};
     for (const Entry& e : cache)
         if (e.used && memcmp(e.key, key, sizeof(key)) == 0) return e.pl;
     Entry& e = cache[next];
     next = (next + 1) % 16;
     memcpy(e.key, key, sizeof(key));
-    e.pl = mrf_plan_uncached(a, allow_zpar, plan_env, per_cu);
+    e.pl = mrf_plan_uncached(a, allow_zpar, plan_env);
     e.used = true;
     return e.pl;
-#endif
 }
 
 inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int force_plan = -1) {
@@ -869,9 +784,6 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
     a.z_serial = 1;
     a.nz_serial = nz;
     a.nz = 1;
-    a.ablate = IRIS_DIAG_ENV("IRIS_HIFIGAN_ABLATE", 0);
-    a.stagger = IRIS_DIAG_ENV("IRIS_HIFIGAN_STAGGER", 0);
-    a.stagger_mod = mrf_cu_count();
     const MrfPlan pl = mrf_plan(a, a.sum_y == nullptr, force_plan);
     if (pl.small) return launch_mrf_small(a, nz, stream);
     // 128-row tiles (round 4) for the tile-serial, non-summing launches of the wide stages: each weight fragment feeds four row
@@ -880,7 +792,7 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
     // 128-row tile instead of two 64-row tiles, 335 -> 328 us per step; 4 x 1000: -3 %; neutral from ~16,000 frames on.
     MrfPlan plt = pl;
     bool tall = false;
-    if (IRIS_DIAG_ENV("IRIS_HIFIGAN_MRFTALL", IRIS_MRF_TALL) && a.sum_y == nullptr && t.WT == 1 && pl.MT == 2 && !pl.zpar && !pl.zdyn && !pl.small) {
+    if (IRIS_MRF_TALL && a.sum_y == nullptr && t.WT == 1 && pl.MT == 2 && !pl.zpar && !pl.zdyn && !pl.small) {
         const long long n4 = (long long)((a.L_out + 127) / 128) * a.n_co_blk * a.B;
         const long long slots = 2LL * mrf_cu_count();
         long long g4 = n4 < slots ? n4 : slots; if (g4 < 1) g4 = 1;
@@ -893,8 +805,7 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
     size_t lds_bytes = (size_t)(T_BLK + kMrfSpanMax) * (t.CIC + 4) * sizeof(float) + 16;         // + next-tile word
     if (lean) lds_bytes += (size_t)3 * a.C_out * sizeof(float);                                   // + the bias table of the LEAN form
     // the counter only pays when a block walks several tiles (each fetch delays one wave by an atomic round trip)
-    const int dyn_env = IRIS_DIAG_ENV("IRIS_HIFIGAN_DYNTILES", 1);
-    if (!dyn_env || pl.zpar || plx.n_tiles < 4 * plx.grid) a.dyn_counter = nullptr;
+    if (pl.zpar || plx.n_tiles < 4 * plx.grid) a.dyn_counter = nullptr;
     a.zb1 = pl.zb1; a.zb2 = pl.zb2;
     const long long n_tiles = plx.n_tiles, g = plx.grid;
     if (n_tiles > 0x7fffffffLL / 3) return hipErrorInvalidValue;
@@ -926,66 +837,9 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
         else if (pl.zpar)    IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 1>);   \
         else                 IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 0>);  \
     } while (0)
-#ifdef IRIS_MRF_BLOCKLOG
-    static unsigned long long* blk_dev = nullptr;
-    if (!blk_dev) { if (hipMalloc(&blk_dev, 4096 * 4 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory; }
-    (void)hipMemsetAsync(blk_dev, 0, 4096 * 4 * sizeof(unsigned long long), stream);
-    a.dbg = g <= 4096 ? blk_dev : nullptr;
-#endif
-#ifdef IRIS_MRF_STAMPS
-    static unsigned long long* dbg_dev = nullptr;
-    if (!dbg_dev) { if (hipMalloc(&dbg_dev, 16 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory; }
-    (void)hipMemsetAsync(dbg_dev, 0, 16 * sizeof(unsigned long long), stream);
-    a.dbg = dbg_dev;
-#endif
     if (t.WT == 4)          IRIS_MRF_LAUNCH_DB(4, 1, 32, 4, 4);     // C <= 32 (mrf_kernel_applicable: CIC == 32 there)
     else if (t.WT == 2)     IRIS_MRF_LAUNCH_DB(2, 2, 64, IRIS_MRF_RING_MT1, 4);
     else                    IRIS_MRF_LAUNCH_DB(1, 4, 64, IRIS_MRF_RING_MT1, IRIS_MRF_RING_MT2);
-#ifdef IRIS_MRF_STAMPS
-    {   // diagnostic build: synchronous read-back of the per-wave cycle shares
-        unsigned long long h[16];
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h, dbg_dev, sizeof(h), hipMemcpyDeviceToHost);
-        const double tot = (double)h[5], nw = (double)h[6];
-        double mfma_cyc = 0;   // ideal MFMA cycles per wave: 64 per MFMA
-        for (int j = 0; j < nz; ++j) mfma_cyc += 2.0 * a.p[j].ks * (a.C_in / 2.0);
-        mfma_cyc *= 64.0 * (double)n_tiles / (double)g;
-        fprintf(stderr, "[stamps] C=%d L=%d grid=%lld waves=%.0f cyc/wave=%.0f ideal_mfma=%.0f (%.3f) | mfma_loop %.3f epilogue %.3f bar1 %.3f ldswrite %.3f bar2 %.3f other %.3f\n",
-                a.C_in, a.L_in, g, nw, tot / nw, mfma_cyc, mfma_cyc / (tot / nw), h[0] / tot, h[1] / tot, h[2] / tot, h[3] / tot, h[4] / tot,
-                1.0 - (h[0] + h[1] + h[2] + h[3] + h[4]) / tot);
-        fprintf(stderr, "[stamps]   of the epilogue: adds (incl. wait for residual) %.3f, whole last-chunk epilogue %.3f\n", h[8] / tot, h[9] / tot);
-    }
-#endif
-#ifdef IRIS_MRF_BLOCKLOG
-    if (a.dbg && IRIS_DIAG_ENV("IRIS_HIFIGAN_BLOCKLOG", 0)) {   // synchronous read-back: one line per launch + per-CU detail of the slowest CUs
-        static unsigned long long hrec[4096 * 4];
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(hrec, blk_dev, (size_t)g * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long tmin = ~0ull, tmax = 0; double busy = 0; int n = 0;
-        static int per_cu[8 * 64 * 16]; memset(per_cu, 0, sizeof(per_cu));
-        static unsigned long long cu_end[8 * 64 * 16]; memset(cu_end, 0, sizeof(cu_end));
-        for (long long i = 0; i < g; ++i) {
-            const unsigned long long t0 = hrec[4 * i], t1 = hrec[4 * i + 1];
-            if (!t1) continue;
-            const unsigned hw = (unsigned)hrec[4 * i + 2], xcc = (unsigned)hrec[4 * i + 3] & 15u;
-            const unsigned cu = (hw >> 8) & 15u, sh = (hw >> 12) & 1u, se = (hw >> 13) & 7u;
-            const unsigned key = ((xcc * 8 + se) * 2 + sh) * 16 + cu;
-            if (key < sizeof(per_cu) / sizeof(per_cu[0])) { per_cu[key]++; if (t1 > cu_end[key]) cu_end[key] = t1; }
-            if (t0 < tmin) tmin = t0;
-            if (t1 > tmax) tmax = t1;
-            busy += (double)(t1 - t0); ++n;
-        }
-        int cus = 0, hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        double end_sum = 0, end_min = 1e30;
-        for (size_t k = 0; k < sizeof(per_cu) / sizeof(per_cu[0]); ++k)
-            if (per_cu[k]) { ++cus; hist[per_cu[k] < 7 ? per_cu[k] : 7]++; const double e = (double)(cu_end[k] - tmin); end_sum += e; if (e < end_min) end_min = e; }
-        const double span = (double)(tmax - tmin);
-        fprintf(stderr, "[blocklog] C=%d L=%d grid=%lld blocks=%d CUs=%d blocks/CU hist 1:%d 2:%d 3:%d 4:%d 5+:%d | span %.1f us, mean block %.1f us, "
-                        "block-residency %.3f of 2 per CU over the span | CU finish: earliest %.3f mean %.3f of the span\n",
-                a.C_in, a.L_in, g, n, cus, hist[1], hist[2], hist[3], hist[4], hist[5] + hist[6] + hist[7], span / 100.0, busy / n / 100.0,
-                busy / (span * cus), end_min / span, end_sum / cus / span);
-    }
-#endif
 #undef IRIS_MRF_LAUNCH_DB
 #undef IRIS_MRF_LAUNCH_SNAKE
 #undef IRIS_MRF_LAUNCH_SNAKE_1

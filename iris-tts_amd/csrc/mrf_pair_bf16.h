@@ -80,8 +80,6 @@ struct PairLaunch {
                           // ConvTranspose1d stages -- or, sum_f32 != 0, the fp32 mean itself (conv_post's input)
     int sum_f32;
     float inv_n;          // fp32(1 / nz)
-    int ablate;           // diagnostics only: 1 no staging loads, 2 no MFMA loops, 4 no stores, 8 no residual loads
-    unsigned long long* dbg;  // diagnostics only (stamp builds): per-segment cycle sums, else nullptr
 };
 
 constexpr int kPairSpanMax = 50;   // (k-1)*d of the widest supported conv1: k = 11, d = 5
@@ -169,22 +167,6 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wt = wave / WC, wc = wave - wt * WC;
     const int lo = lane & 31, hi = lane >> 5;
-#ifdef IRIS_PAIR_STAMPS
-    // diagnostic build only: per-wave cycle totals of [0] requests + window wait + LDS write, [1] barrier, [2] conv1 loop,
-    // [3] barrier + xt write + barrier, [4] conv2 loop, [5] barrier + epilogue, [6] whole block; [7] waves counted
-    unsigned long long seg_t[8];
-    auto stamp = [&]() -> unsigned long long {
-        unsigned long long t;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return t;
-    };
-#define PAIR_STAMP(i) seg_t[i] = stamp()
-#else
-#define PAIR_STAMP(i)
-#endif
-    PAIR_STAMP(0);
 
     // job -> (tile, branch): contiguous job ranges per XCD
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -239,7 +221,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
     constexpr int PPRO = NT * 4;                       // 16-byte bf16 pieces per row of this wave's channel span
     constexpr int NP = 2 * NT;                         // pieces per lane and m-tile
     const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + item, tensor_bytes);
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.x + item, (a.ablate & 8) ? 0u : tensor_bytes);
+    const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.x + item, tensor_bytes);
     unsigned pvoff[MT][NP];
     int pscr[NP];
     auto geometry = [&](int lane_) {
@@ -273,7 +255,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
             const int idx = u * 256 + (int)threadIdx.x;
             const int r = idx / PPR, pc = idx & (PPR - 1);
             const int row = in_row0 + r;
-            const bool ok = idx < total && row >= 0 && row < L && !(a.ablate & 1);
+            const bool ok = idx < total && row >= 0 && row < L;
             v[u] = buf_load4(xr, ok ? (unsigned)(row * C + 8 * pc) * 2u : kOob, 0);
         }
 #pragma unroll
@@ -297,15 +279,12 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
 #pragma unroll
             for (int j = 0; j < NP; ++j) resv[m][j] = buf_load4(rr, pvoff[m][j], 0);
     }
-    PAIR_STAMP(1);
     __syncthreads();
-    PAIR_STAMP(2);
     // ---- 2. conv1 ---------------------------------------------------------------------------------------
     init_acc(bias4);
-    if (!(a.ablate & 2)) ring_mma_loop<MT, NT, C, D>(acc, wv, a_lane, dil * SB, wr1, wvoff, q_bytes, tap_bytes, ks);
+    ring_mma_loop<MT, NT, C, D>(acc, wv, a_lane, dil * SB, wr1, wvoff, q_bytes, tap_bytes, ks);
     ring_request<NT, C, D>(wv, wr2, wvoff, q_bytes, tap_bytes);        // conv2's first fragments travel during steps 3
     load_bias(bias4, p.b2);
-    PAIR_STAMP(3);
     __syncthreads();                                                    // every wave is done with the x window
     // ---- 3. xt -> LDS: bf16(LeakyReLU(bf16(acc))) (acc already holds the bias), zero outside [0, L) --------------------------------
 #pragma unroll
@@ -338,11 +317,9 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
         for (int j = 0; j < NP; ++j) resv[0][j] = buf_load4(rr, pvoff[0][j], 0);
     }
     __syncthreads();
-    PAIR_STAMP(4);
     // ---- 4. conv2 (dilation 1; rows M .. M+k-2 of the window hold stale bytes: they only reach outputs >= T_OUT) ----
     init_acc(bias4);
-    if (!(a.ablate & 2)) ring_mma_loop<MT, NT, C, D>(acc, wv, a_lane, SB, wr2, wvoff, q_bytes, tap_bytes, ks);
-    PAIR_STAMP(5);
+    ring_mma_loop<MT, NT, C, D>(acc, wv, a_lane, SB, wr2, wvoff, q_bytes, tap_bytes, ks);
     __syncthreads();                                   // the epilogue scratch aliases the window
     // ---- 5. epilogue: + x, one rounding to bf16.  Each wave turns its 32-row m-tiles through a private LDS scratch so that
     // residual loads and stores are 16 bytes per lane and whole 64-byte (NT = 1) / 128-byte row segments per 4 / 8 lanes.
@@ -381,7 +358,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < NP; ++j)
-            __builtin_amdgcn_raw_buffer_store_b128(outp[j], yr, (int)((a.ablate & 4) ? kOob : pvoff[m][j]), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(outp[j], yr, (int)pvoff[m][j], 0, 0);
         asm volatile("s_nop 1");       // explicit wait states behind the dwordx4 stores (see mrf_conv_mfma_f32.h)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -389,15 +366,6 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_kernel(const PairLaun
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-#ifdef IRIS_PAIR_STAMPS
-    PAIR_STAMP(6);
-    if (lane == 0 && a.dbg) {
-        for (int i = 0; i < 6; ++i) atomicAdd(a.dbg + i, seg_t[i + 1] - seg_t[i]);
-        atomicAdd(a.dbg + 6, seg_t[6] - seg_t[0]);
-        atomicAdd(a.dbg + 7, 1ull);
-    }
-#endif
-#undef PAIR_STAMP
 }
 
 // ---- the stage's LAST pair, summing: a block runs the pair of ALL THREE branches on its rows and stores only the MRF mean ----
@@ -640,24 +608,19 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_bf16_sum_kernel(const Pair
 struct PairTile { int WT, WC, MT, NT, MINB, M; };
 
 inline bool pair_tile_for(int C, PairTile* t) {
-    const int v64 = IRIS_DIAG_ENV("IRIS_B16_PAIR64", 0);
     if (C == 32) {                                                     // (512 rows at three blocks per CU: no difference)
-        *t = IRIS_DIAG_ENV("IRIS_B16_PAIR32", 0) == 1 ? PairTile{4, 1, 3, 1, 3, 384} : PairTile{4, 1, 3, 1, 4, 384};   // (A/B: three blocks per CU)
+        *t = PairTile{4, 1, 3, 1, 4, 384};
         return true;
     }
     if (C == 64) {
         // 256 rows as 2 x 2 waves of 128 x 32 at three blocks per CU: 2 % ahead of 192 rows at four (2.09 vs 2.13 ms)
-        if (v64 == 1) { *t = PairTile{4, 1, 2, 2, 3, 256}; return true; }
-        if (v64 == 2) { *t = PairTile{2, 2, 3, 1, 4, 192}; return true; }
-        if (v64 == 3) { *t = PairTile{2, 2, 4, 1, 2, 256}; return true; }   // (A/B: the default tile at two blocks per CU)
         *t = PairTile{2, 2, 4, 1, 3, 256};
         return true;
     }
     // C = 128: 192 rows at two blocks per CU beat 128 rows at three (stage 1 of configs[2]: 3.75 vs 3.95 ms): a weight
     // fragment (1 KB per wave, from L2) feeds three MFMAs per channel tile instead of two, and 10 of 192 conv2 rows are
     // thrown away instead of 10 of 128
-    if (C == 128 && IRIS_DIAG_ENV("IRIS_B16_PAIR128", 1) == 2) { *t = PairTile{2, 2, 2, 2, 3, 128}; return true; }
-    if (C == 128 && IRIS_DIAG_ENV("IRIS_B16_PAIR128", 1)) { *t = PairTile{2, 2, 3, 2, 2, 192}; return true; }
+    if (C == 128) { *t = PairTile{2, 2, 3, 2, 2, 192}; return true; }
     return false;
 }
 
@@ -674,7 +637,7 @@ inline bool pair_applicable(const PairLaunch& a, int nz) {
         if ((ks - 1) * d > kPairSpanMax) return false;                           // the kernel's staging registers are sized for this
         if ((size_t)(t.M + (ks - 1) * d) * (a.C * 2 + 16) > 66 * 1024) return false; // window must leave room for two blocks per CU
     }
-    return IRIS_DIAG_ENV("IRIS_B16_PAIR", 1) != 0;
+    return true;
 }
 
 inline hipError_t launch_pair_bf16(PairLaunch& a, int nz, hipStream_t stream) {
@@ -687,25 +650,6 @@ inline hipError_t launch_pair_bf16(PairLaunch& a, int nz, hipStream_t stream) {
     a.nz = nz;
     a.Qp = packed_qsteps(a.C);
     a.n_ct = packed_cotiles(a.C);
-    a.ablate = IRIS_DIAG_ENV("IRIS_B16_ABLATE", 0);
-    a.dbg = nullptr;
-#ifdef IRIS_PAIR_STAMPS
-    static unsigned long long* dbg_dev = nullptr;
-    if (!dbg_dev && hipMalloc(&dbg_dev, 8 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(dbg_dev, 0, 8 * sizeof(unsigned long long), stream);
-    a.dbg = dbg_dev;
-    struct StampReport {
-        unsigned long long* d; hipStream_t s; int C, L;
-        ~StampReport() {
-            unsigned long long h[8];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-            const double n = (double)h[7], tot = (double)h[6];
-            if (n > 0) fprintf(stderr, "[pair stamps] C=%d L=%d waves=%.0f cyc/wave=%.0f | window %.3f bar %.3f conv1 %.3f bar+xt+bar %.3f conv2 %.3f bar+epilogue %.3f\n",
-                               C, L, n, tot / n, h[0] / tot, h[1] / tot, h[2] / tot, h[3] / tot, h[4] / tot, h[5] / tot);
-        }
-    } report{dbg_dev, stream, a.C, a.L};
-#endif
     int span = 0, kmax = 1;
     for (int j = 0; j < nz; ++j) {
         const int s = (a.p[j].ks - 1) * a.p[j].dil;
@@ -729,12 +673,7 @@ inline hipError_t launch_pair_bf16(PairLaunch& a, int nz, hipStream_t stream) {
         return hipSuccess;                                                                                   \
     }
     IRIS_PAIR_CASE(4, 1, 3, 1, 32, 4)
-    IRIS_PAIR_CASE(4, 1, 3, 1, 32, 3)
-    IRIS_PAIR_CASE(2, 2, 3, 1, 64, 4)
-    IRIS_PAIR_CASE(4, 1, 2, 2, 64, 3)
     IRIS_PAIR_CASE(2, 2, 4, 1, 64, 3)
-    IRIS_PAIR_CASE(2, 2, 4, 1, 64, 2)
-    IRIS_PAIR_CASE(2, 2, 2, 2, 128, 3)
     IRIS_PAIR_CASE(2, 2, 3, 2, 128, 2)
 #undef IRIS_PAIR_CASE
     return hipErrorInvalidValue;
@@ -764,7 +703,7 @@ inline bool pair_sum_applicable(const PairLaunch& a, int nz, bool f32_out) {
         if ((ks - 1) * d > kPairSpanMax) return false;
         if ((size_t)(t.M + (ks - 1) * d) * (a.C * 2 + 16) > 66 * 1024) return false;
     }
-    return IRIS_DIAG_ENV("IRIS_B16_PAIR_SUM", IRIS_B16_PAIR_SUM_DEFAULT) != 0;
+    return IRIS_B16_PAIR_SUM_DEFAULT != 0;
 }
 
 inline hipError_t launch_pair_bf16_sum(PairLaunch& a, void* sum_y, bool f32_out, hipStream_t stream) {
@@ -775,8 +714,6 @@ inline hipError_t launch_pair_bf16_sum(PairLaunch& a, void* sum_y, bool f32_out,
     a.nz = 3;
     a.Qp = packed_qsteps(a.C);
     a.n_ct = packed_cotiles(a.C);
-    a.ablate = 0;
-    a.dbg = nullptr;
     a.sum_y = sum_y; a.sum_f32 = f32_out ? 1 : 0; a.inv_n = 1.0f / 3.0f;
     int span = 0, kmax = 1;
     for (int j = 0; j < 3; ++j) {

@@ -49,8 +49,6 @@ struct PairLaunchF32 {
     int nz;               // branches
     int Gp, n_ct;         // packed-weight geometry (packed_groups / packed_cotiles of C)
     int n_jobs;           // tiles x branches (tiles = ceil(L / smallest T_OUT))
-    int jobs_per_xcd;     // ceil(n_jobs / 8)
-    int z_major;          // job order: branch-major (heaviest first) instead of tile-major
 };
 
 // The MFMA loop of one conv over the LDS window: NG = KS * GPC groups of 8 channels; weight fragment n + DB is
@@ -104,21 +102,12 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunc
     const int wt = wave / WC, wc = wave - wt * WC;
     const int lo = lane & 31, hi = lane >> 5;
 
-    // job -> (tile, branch).  z_major: all jobs of the heaviest branch first (the tail of the launch is then made of the
-    // short k = 3 blocks); else tile-major with contiguous job ranges per XCD (neighbouring tiles share halo rows through
-    // that XCD's L2)
-    int tile, zr;
-    if (a.z_major) {
-        const int job = (int)blockIdx.x;
-        if (job >= a.n_jobs) return;
-        const int tiles = a.n_jobs / a.nz;
-        zr = job / tiles; tile = job - zr * tiles;
-    } else {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int job = xcd * a.jobs_per_xcd + slot;
-        if (job >= a.n_jobs) return;
-        tile = job / a.nz; zr = job - tile * a.nz;
-    }
+    // job -> (tile, branch): all jobs of the heaviest branch first, so the tail of the launch is made of the short k = 3
+    // blocks (tile-major order with contiguous job ranges per XCD was 10-20 % slower once a launch is more than one round)
+    const int job = (int)blockIdx.x;
+    if (job >= a.n_jobs) return;
+    const int tiles = a.n_jobs / a.nz;
+    const int zr = job / tiles, tile = job - zr * tiles;
     const int z = a.nz - 1 - zr;                      // heaviest branch first
     PairProblemF32 p = a.p[0];
     if (z == 1) p = a.p[1];
@@ -298,7 +287,7 @@ inline bool pair_f32_applicable(const PairLaunchF32& a, int nz) {
         if (d < 1 || (ks - 1) * d > kMrfSpanMax) return false;
         if (packed_conv1d_floats(a.C, a.C, ks) * 4u >= 0x7fffffffull) return false;
     }
-    return IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR", IRIS_PAIR_F32_DEFAULT) != 0;
+    return IRIS_PAIR_F32_DEFAULT != 0;
 }
 
 inline hipError_t launch_pair_f32(PairLaunchF32& a, int nz, hipStream_t stream) {
@@ -319,10 +308,8 @@ inline hipError_t launch_pair_f32(PairLaunchF32& a, int nz, hipStream_t stream) 
     const long long n_jobs = pl.tiles * nz;
     if (n_jobs > 0x3fffffffLL) return hipErrorInvalidValue;
     a.n_jobs = (int)n_jobs;
-    a.jobs_per_xcd = (int)((n_jobs + 7) / 8);
-    a.z_major = IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_ZMAJOR", 1);     // (tile-major: 10-20 % slower once a launch is more than one round)
     const size_t lds_bytes = (size_t)(t.M + span) * (a.C + 4) * sizeof(float);
-    dim3 grid((unsigned)(a.jobs_per_xcd * 8), (unsigned)a.B, 1u), block(256);
+    dim3 grid((unsigned)((n_jobs + 7) / 8 * 8), (unsigned)a.B, 1u), block(256);     // (whole rounds of 8: blocks past n_jobs return)
 #define IRIS_PAIR_F32_CASE(WT_, WC_, MT_, C_, MINB_)                                                         \
     if (a.C == C_ && t.WT == WT_ && t.MT == MT_) {                                                           \
         auto kfn = mrf_pair_f32_kernel<WT_, WC_, MT_, C_, MINB_>;                                            \

@@ -27,8 +27,7 @@
 //     stride or drawn jobs, C = 32 at the same four blocks per CU, C = 64 at two instead of three: the window held in
 //     registers does not fit 168 VGPRs there).  What the prefetch hides (a window wait that co-resident blocks already
 //     cover) is less than what the job loop adds (a fourth barrier per job, the decode, the ring hand-over).  The forward
-//     therefore keeps mrf_pair_f32_kernel for them; this path stays reachable through iris_hifigan_op_mrf_pair (modes 1 / 2,
-//     parity tests) and the diagnostic build's IRIS_HIFIGAN_PAIR_PF_MODE=2.
+//     therefore keeps mrf_pair_f32_kernel for them, and the library instantiates the summing form (SUM = true) alone.
 //   * SUM: wins where its whole-tile jobs (21 tap-units against 11 / 7 / 3) fill several rounds of the chip: batch 32 x 500
 //     frames, C = 32 stage +3 %, step -0.6 %; neutral at batch 1 x 1000; a loss at one or two rounds.  The forward takes it
 //     from four rounds on (iris_hifigan.hip).
@@ -405,20 +404,14 @@ inline PairPfTileF32 pair_pf_f32_tile(int C) {
     return PairPfTileF32{2, 2, 2, 2, 128};      // (three blocks per CU would spill: 48 staging + 32 residual + 64 accumulator/sum registers)
 }
 
-// Blocks of a persistent launch of `jobs` jobs.  Jobs of a SUM launch are equal and indivisible (a tile's three branches),
-// so the launch takes whole rounds: with b resident blocks per CU it lasts ceil(jobs / (n_cu * b)) rounds of b jobs sharing a
+// Blocks of a persistent SUM launch of `jobs` jobs.  Its jobs are equal and indivisible (a tile's three branches), so the
+// launch takes whole rounds: with b resident blocks per CU it lasts ceil(jobs / (n_cu * b)) rounds of b jobs sharing a
 // CU's matrix pipes, i.e. ~ ceil(jobs / (n_cu * b)) * b job times.  The block count per CU (<= MINB) with the fewest
 // job times is taken (a lone block per CU hides latencies worse: penalised); `efficiency` = jobs / n_cu over that.
 struct PairPfPlanF32 { long long blocks; int per_cu; double efficiency; };
-inline PairPfPlanF32 pair_pf_f32_plan(long long jobs, int n_cu, int minb, bool sum) {
+inline PairPfPlanF32 pair_pf_f32_plan(long long jobs, int n_cu, int minb) {
     PairPfPlanF32 pl{1, 1, 1.0};
     if (jobs < 1) jobs = 1;
-    if (!sum) {                       // mixed job sizes, heaviest first: every slot, the tail is made of short jobs
-        const long long slots = (long long)n_cu * minb;
-        pl.blocks = jobs < slots ? jobs : slots;
-        pl.per_cu = minb;
-        return pl;
-    }
     static const double penalty[5] = {0, 1.35, 1.1, 1.0, 1.0};
     double best = 1e30;
     for (int b = 1; b <= minb && b <= 4; ++b) {
@@ -431,10 +424,10 @@ inline PairPfPlanF32 pair_pf_f32_plan(long long jobs, int n_cu, int minb, bool s
     return pl;
 }
 
-// True when the pair launch `a` (nz branches) can take the persistent kernel (sum: as the stage's last pair, forming the mean).
-inline bool pair_pf_f32_applicable(const PairLaunchF32& a, int nz, bool sum) {
+// True when the pair launch `a` (nz branches) can take the persistent kernel as the stage's last pair, forming the mean.
+inline bool pair_pf_f32_applicable(const PairLaunchF32& a, int nz) {
     if (!pair_f32_applicable(a, nz)) return false;
-    if (sum && nz != 3) return false;
+    if (nz != 3) return false;
     {   // 32-bit job indices (the blocks' stride walk adds up to one grid length beyond the last job)
         const PairPfTileF32 t = pair_pf_f32_tile(a.C);
         int kmax = 1;
@@ -442,22 +435,20 @@ inline bool pair_pf_f32_applicable(const PairLaunchF32& a, int nz, bool sum) {
         const long long tiles = (a.L + (t.M - (kmax - 1)) - 1) / (t.M - (kmax - 1));
         if (tiles * a.B * nz > 0x3fffffffLL) return false;
     }
-#ifndef IRIS_MRF_DIAG
-    if (!sum) return false;        // release build: only the summing form exists (the plain persistent pairs measured 3-5 % slower)
-#endif
-    return IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_PF", IRIS_PAIR_F32_PF_DEFAULT) != 0;
+    return IRIS_PAIR_F32_PF_DEFAULT != 0;
 }
 
-// next_job: a ZEROED device word of this launch's own (blocks draw jobs from it), or nullptr for a fixed stride.
+// sum_y: where the mean goes (the library carries the summing form alone: the plain persistent pairs were 3-5 % slower than
+// one block per job at every size, profiles/r03_notes.md).  next_job: a ZEROED device word of this launch's own (blocks
+// draw jobs from it), or nullptr for a fixed stride.
 inline hipError_t launch_pair_f32_pf(const PairLaunchF32& src, int nz, float* sum_y, unsigned* next_job, hipStream_t stream) {
+    if (!sum_y) return hipErrorNotSupported;
     if (src.C != 32 && src.C != 64) return hipErrorInvalidValue;
     PairPfLaunchF32 a;
     memset(&a, 0, sizeof(a));
     for (int j = 0; j < nz; ++j) {
         a.p[j] = src.p[j];
-        for (int i = 0; i < nz; ++i)
-            if (!sum_y && src.p[j].x == src.p[i].y) return hipErrorInvalidValue;             // never in place
-        if (sum_y && src.p[j].x == sum_y) return hipErrorInvalidValue;
+        if (src.p[j].x == sum_y) return hipErrorInvalidValue;                                // never in place
     }
     a.B = src.B; a.L = src.L; a.C = src.C; a.slope = src.slope; a.nz = nz;
     a.Gp = packed_groups(a.C);
@@ -471,42 +462,24 @@ inline hipError_t launch_pair_f32_pf(const PairLaunchF32& src, int nz, float* su
     }
     const PairPfTileF32 t = pair_pf_f32_tile(a.C);
     const int t_out_min = t.M - (kmax - 1);
-    a.t_out = sum_y ? t_out_min : 0;
-    long long n_jobs = 0;
-    for (int j = 0; j < nz; ++j) {
-        const int t_out = sum_y ? t_out_min : t.M - (a.p[j].ks - 1);
-        a.tiles[j] = (a.L + t_out - 1) / t_out;
-        n_jobs += (long long)a.tiles[j] * a.B;
-    }
-    if (sum_y) n_jobs = (long long)a.tiles[0] * a.B;
+    a.t_out = t_out_min;
+    for (int j = 0; j < nz; ++j) a.tiles[j] = (a.L + t_out_min - 1) / t_out_min;
+    const long long n_jobs = (long long)a.tiles[0] * a.B;
     if (n_jobs > 0x3fffffffLL) return hipErrorInvalidValue;                                  // (pair_pf_f32_applicable)
     a.n_jobs = (int)n_jobs;
     a.next_job = next_job;
-    const PairPfPlanF32 pl = pair_pf_f32_plan(n_jobs, device_cu_count(), t.MINB, sum_y != nullptr);
-    const long long G = IRIS_DIAG_ENV("IRIS_HIFIGAN_PAIR_PF_GRID", 0) ? n_jobs : pl.blocks;        // (A/B: one job per block)
+    const PairPfPlanF32 pl = pair_pf_f32_plan(n_jobs, device_cu_count(), t.MINB);
     const size_t window_floats = (size_t)(t.M + span) * (a.C + 4);
     a.bias_off = (int)((window_floats + 3) & ~(size_t)3);
     const size_t lds_bytes = ((size_t)a.bias_off + (size_t)nz * 2 * a.C + 4) * sizeof(float);      // + the next-job word
-    dim3 grid((unsigned)G, 1u, 1u), block(256);
-    // The non-summing instantiations (plain persistent pairs: 3-5 % slower than one block per job at every size, profiles/r03_notes.md)
-    // exist in the diagnostic build only; the release library carries the summing form alone.
-#ifdef IRIS_MRF_DIAG
-#define IRIS_PAIR_PF_F32_PLAIN(WT_, WC_, MT_, C_, MINB_)                                                                 \
-        return ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel", mrf_pair_f32_pf_kernel<WT_, WC_, MT_, C_, MINB_, false>,                 \
-                                           grid, block, lds_bytes, stream, a);
-#else
-#define IRIS_PAIR_PF_F32_PLAIN(WT_, WC_, MT_, C_, MINB_) return hipErrorNotSupported;
-#endif
+    dim3 grid((unsigned)pl.blocks, 1u, 1u), block(256);
 #define IRIS_PAIR_PF_F32_CASE(WT_, WC_, MT_, C_, MINB_)                                                                  \
-    if (a.C == C_ && t.WT == WT_ && t.MT == MT_) {                                                                       \
-        if (sum_y) return ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel<sum>", mrf_pair_f32_pf_kernel<WT_, WC_, MT_, C_, MINB_, true>,  \
-                                                      grid, block, lds_bytes, stream, a);                                \
-        IRIS_PAIR_PF_F32_PLAIN(WT_, WC_, MT_, C_, MINB_)                                                                 \
-    }
+    if (a.C == C_ && t.WT == WT_ && t.MT == MT_)                                                                         \
+        return ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel<sum>", mrf_pair_f32_pf_kernel<WT_, WC_, MT_, C_, MINB_, true>,  \
+                                           grid, block, lds_bytes, stream, a);
     IRIS_PAIR_PF_F32_CASE(4, 1, 1, 32, 4)
     IRIS_PAIR_PF_F32_CASE(2, 2, 2, 64, 2)
 #undef IRIS_PAIR_PF_F32_CASE
-#undef IRIS_PAIR_PF_F32_PLAIN
     return hipErrorInvalidValue;
 }
 

@@ -269,15 +269,14 @@ def test_mrf_fused_pair_matches_oracle_and_separate_steps(lib, B, L, C, dils, mo
     _, sep = _mrf_step(lib, xt, w2, b2, xs, B, L, C, (1, 1, 1), 0, mean=False)
     small = B * L * C <= 400_000                         # (the numpy oracle is slow: large cases are checked bit for bit only)
     rc = pair(yd, None, mode)
-    if mode >= 1 and rc == 4:
-        # IRIS_HIFIGAN_UNSUPPORTED: the release library carries the persistent kernel in its summing form only (the plain
-        # persistent pairs measured slower and live in the diagnostic build) -- the summing form is checked below
-        plain = False
+    if mode >= 1:
+        # IRIS_HIFIGAN_UNSUPPORTED: the library carries the persistent kernel in its summing form only (the plain persistent
+        # pairs measured slower) -- the summing form is checked below
+        assert rc == 4, rc
     else:
         _check("op_mrf_pair", rc)
-        plain = True
     got = [t.cpu().numpy().transpose(0, 2, 1) for t in yd]
-    for j in range(3 if plain else 0):
+    for j in range(3 if mode == 0 else 0):
         assert np.isfinite(got[j]).all()
         if small:
             want_xt = orc.conv1d_np(orc.lrelu_np(xs[j], 0.1), w1[j], b1[j], dils[j]).astype(np.float32)

@@ -231,9 +231,9 @@ def test_product_never_imports_the_oracle():
 
 
 def test_release_library_reads_no_diagnostic_switch():
-    """A shipped library must not change what it computes because of a stray environment variable: every
-    diagnostic switch (IRIS_HIFIGAN_*, IRIS_B16_*, IRIS_S3_*, IRIS_MRF_*) is compiled in only with -DIRIS_MRF_DIAG
-    (csrc/diag_env.h), so none of their names may occur in the release .so, and it must not import getenv at all."""
+    """A shipped library must not change what it computes because of a stray environment variable: A/B switches are
+    compile-time macros (make relvariant), so no switch name (IRIS_HIFIGAN_*, IRIS_B16_*, IRIS_S3_*, IRIS_MRF_*) may occur
+    in the release .so, and it must not import getenv at all."""
     import subprocess
     data = _native.library_path().read_bytes()
     names = set(re.findall(rb"IRIS_(?:HIFIGAN|B16|S3|MRF)_[A-Z0-9_]+", data))
@@ -241,10 +241,13 @@ def test_release_library_reads_no_diagnostic_switch():
     syms = subprocess.run(["nm", "-D", "--undefined-only", str(_native.library_path())], capture_output=True, text=True)
     if syms.returncode == 0:
         assert not re.search(r"\bgetenv\b", syms.stdout), "the release library imports getenv"
-    # the sources name their switches only through the gated macro
+    # no source reads the environment, and no runtime-switch layer is left to compile in
     for path in (REPO / "iris-tts_amd" / "csrc").glob("*"):
-        if path.suffix in (".h", ".hip") and path.name != "diag_env.h":
-            assert "getenv" not in path.read_text(), path
+        if path.suffix in (".h", ".hip", ".cpp"):
+            text = path.read_text()
+            for word in ("getenv", "IRIS_DIAG_ENV", "IRIS_MRF_DIAG"):
+                assert word not in text, (path, word)
+    assert not (REPO / "iris-tts_amd" / "csrc" / "diag_env.h").exists()
 
 
 def test_receptive_field_from_config():
