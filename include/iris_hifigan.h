@@ -149,6 +149,20 @@ int32_t iris_hifigan_forward(iris_hifigan_handle* h, const void* mel_dev, int32_
                              void* wav_dev, void* workspace_dev, uint64_t workspace_bytes,
                              int32_t dtype, void* stream);
 
+/* Ragged batch: items of different lengths in one forward.
+ * mel_dev [B, in_channels, T] fp32, lengths_dev [B] int32 on the device (caller-owned, like mel_dev).
+ * Item b is computed exactly as iris_hifigan_forward of mel[b, :, :lengths[b]] alone would compute it,
+ * bit for bit. Mel frames >= lengths[b] are never read, so they may hold anything, NaN included.
+ * wav[b, hop*lengths[b] : hop*T] is written as 0.0f. lengths are clamped to [0, T] on the device.
+ * Workspace as iris_hifigan_workspace_bytes(B, T). Same stream, allocation and capture rules as forward.
+ * The host never reads the lengths: the launch plan is the one of iris_hifigan_forward(B, T), and tiles past an
+ * item's length return at once on the device. Profiling records still count the work of B*T frames.
+ * dtype: IRIS_HIFIGAN_F32 only; others return IRIS_HIFIGAN_UNSUPPORTED. lengths_dev == NULL (B, T > 0) returns
+ * IRIS_HIFIGAN_INVALID_ARGUMENT. */
+int32_t iris_hifigan_forward_ragged(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                    const int32_t* lengths_dev, void* wav_dev, void* workspace_dev,
+                                    uint64_t workspace_bytes, int32_t dtype, void* stream);
+
 /* ---- intermediates (parity tests of the layers inside a forward; not needed by a caller) ----
  * forward_until queues the same launches as forward up to and including MRF step `stop_step`
  * (0 .. 2*num_dilations-1: even = convs1[m], odd = convs2[m] + residual, hifigan_pretrained.py:64-71) of

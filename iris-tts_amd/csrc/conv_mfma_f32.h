@@ -87,6 +87,9 @@ struct ConvLaunch {
                             // counter instead of a fixed stride (large batches: evens out slow and fast CUs)
     int zb1, zb2;           // MRF kernel, one-branch-per-block mode: blocks [0, zb1) serve branch 2 (k = 11),
                             // [zb1, zb2) branch 1 (k = 7), [zb2, gridDim.x) branch 0 (k = 3)
+    const int32_t* lengths; // ragged forward: mel frames of each batch item [B] (device), or nullptr (all items L_in rows)
+    int row_scale;          // rows of L_in per mel frame (L_out has row_scale * L_out / L_in): item b has
+                            // ragged_rows(lengths, b, row_scale, L_in) input rows; rows past them read 0 and are never stored
 };
 
 __device__ __forceinline__ float lrelu1(float v, float slope) { return v > 0.f ? v : v * slope; }
@@ -99,9 +102,10 @@ __device__ __forceinline__ f32x4 lrelu4(f32x4 v, float slope) {
 
 // ---------------------------------------------------------------------------------------------
 // Stage rows [in_row0, in_row0 + R) x channels [c0, c0 + CIC) of the (activated) input into LDS.
+// Rows at or past Lb_in (the item's rows of a ragged forward; L_in otherwise) read 0.
 template <int CIC>
 __device__ __forceinline__ void stage_input(const ConvLaunch& a, const ConvProblem& p, float* lds,
-                                            int b, int in_row0, int R, int c0) {
+                                            int b, int in_row0, int R, int c0, int Lb_in) {
     constexpr int S = CIC + 4;
     constexpr int QPR = CIC / 4;  // 16-byte quads per LDS row
     const int tid = threadIdx.x;
@@ -112,7 +116,7 @@ __device__ __forceinline__ void stage_input(const ConvLaunch& a, const ConvProbl
             const int r = idx / QPR, q = idx - r * QPR;
             const int row = in_row0 + r, ci = c0 + 4 * q;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row >= 0 && row < L_in && ci < C_in) {
+            if (row >= 0 && row < Lb_in && ci < C_in) {
                 const size_t off = ((size_t)b * L_in + row) * C_in + ci;
                 if (a.in_act == IN_ACT_MRF_LRELU) {
                     v = *reinterpret_cast<const f32x4*>(a.xmrf[0] + off);
@@ -140,7 +144,7 @@ __device__ __forceinline__ void stage_input(const ConvLaunch& a, const ConvProbl
                     const int idx = base + u * 256;
                     const int c = idx / R, r = idx - c * R;         // lanes run along time
                     const int row = in_row0 + r, ci = c0 + c;
-                    const bool ok = idx < total && row >= 0 && row < L_in && ci < C_in;
+                    const bool ok = idx < total && row >= 0 && row < Lb_in && ci < C_in;
                     v[u] = ok ? p.x[((size_t)b * C_in + ci) * L_in + row] : 0.f;
                 }
 #pragma unroll
@@ -160,7 +164,7 @@ __device__ __forceinline__ void stage_input(const ConvLaunch& a, const ConvProbl
             else                    { r = idx / CIC; c = idx - r * CIC; }
             const int row = in_row0 + r, ci = c0 + c;
             float v = 0.f;
-            if (row >= 0 && row < L_in && ci < C_in) {
+            if (row >= 0 && row < Lb_in && ci < C_in) {
                 const size_t off = a.x_channels_first ? ((size_t)b * C_in + ci) * L_in + row
                                                       : ((size_t)b * L_in + row) * C_in + ci;
                 if (a.in_act == IN_ACT_MRF_LRELU) {
@@ -179,7 +183,8 @@ __device__ __forceinline__ void stage_input(const ConvLaunch& a, const ConvProbl
 
 // ---------------------------------------------------------------------------------------------
 // KS > 0: taps known at compile time (fully unrolled);  KS == 0: runtime tap count.
-template <int KS, int WT, int WC, int MT, int CIC>
+// RAGGED: the item's rows come from a.lengths (ragged forward); otherwise every item has L_in / L_out rows.
+template <bool RAGGED, int KS, int WT, int WC, int MT, int CIC>
 __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem& p,
                                           const f32x4* __restrict__ wp, int out_off, float* lds) {
     constexpr int S = CIC + 4;
@@ -196,6 +201,11 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
     const int ct = tile_co * WC + wc;          // this wave's 32-wide C_out tile
     const bool wave_active = ct < a.n_ct;      // wave-uniform
     const int lo = lane & 31, hi = lane >> 5;
+    // ragged forward: this item's rows; a tile whose first output row is past them has nothing to compute (block-uniform)
+    const int32_t* const lengths = RAGGED ? a.lengths : nullptr;
+    const int Lb_in = ragged_rows(lengths, b, a.row_scale, a.L_in);
+    const int Lb_out = RAGGED ? ragged_rows(lengths, b, a.row_scale * (a.L_out / a.L_in), a.L_out) : a.L_out;
+    if (RAGGED && i0 * a.out_stride + out_off >= Lb_out) return;
 
     f32x16 acc[MT];
 #pragma unroll
@@ -209,7 +219,7 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
 
     for (int c0 = 0; c0 < a.C_in; c0 += CIC) {
         if (c0 > 0) __syncthreads();
-        stage_input<CIC>(a, p, lds, b, in_row0, R, c0);
+        stage_input<CIC>(a, p, lds, b, in_row0, R, c0, Lb_in);
         __syncthreads();
         if (wave_active) {
             const int g0 = c0 >> 3;
@@ -278,7 +288,7 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
         for (int m = 0; m < MT; ++m) {
             const int im = i + m * 32;
             const int o = im * a.out_stride + out_off;
-            ok[m] = im < a.n_idx && o >= 0 && o < a.L_out;
+            ok[m] = im < a.n_idx && o >= 0 && o < Lb_out;
             offs[m] = ((size_t)b * a.L_out + (ok[m] ? o : 0)) * a.C_out + ct * 32 + 4 * hi;
         }
 #pragma unroll
@@ -318,7 +328,7 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
         for (int m = 0; m < MT; ++m) {
             const int im = i + m * 32;
             const int o = im * a.out_stride + out_off;
-            if (!(im < a.n_idx && o >= 0 && o < a.L_out)) continue;
+            if (!(im < a.n_idx && o >= 0 && o < Lb_out)) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -334,19 +344,21 @@ __device__ __forceinline__ void conv_body(const ConvLaunch& a, const ConvProblem
     }
 }
 
-template <int WT, int WC, int MT, int CIC>
+template <bool RAGGED, int WT, int WC, int MT, int CIC>
 __device__ __forceinline__ void conv_dispatch(const ConvLaunch& a, const ConvProblem& p, const f32x4* wp,
                                               int out_off, float* lds) {
     switch (p.ks) {
-        case 2:  conv_body<2,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
-        case 3:  conv_body<3,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
-        case 7:  conv_body<7,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
-        case 11: conv_body<11, WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
-        default: conv_body<0,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
+        case 2:  conv_body<RAGGED, 2,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
+        case 3:  conv_body<RAGGED, 3,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
+        case 7:  conv_body<RAGGED, 7,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
+        case 11: conv_body<RAGGED, 11, WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
+        default: conv_body<RAGGED, 0,  WT, WC, MT, CIC>(a, p, wp, out_off, lds); break;
     }
 }
 
-template <int WT, int WC, int MT, int CIC>
+// RAGGED: the ragged forward's instantiation (per-item bounds from a.lengths); false: the plain forward's, whose code
+// has no trace of them
+template <bool RAGGED, int WT, int WC, int MT, int CIC>
 __global__ void __launch_bounds__(256) conv_mfma_f32_kernel(const ConvLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (a.z_serial) {
@@ -355,7 +367,7 @@ __global__ void __launch_bounds__(256) conv_mfma_f32_kernel(const ConvLaunch a) 
         // sizes the stage has.  Branches are taken heaviest-first (the packed order is k ascending).
         for (int zi = 0; zi < a.nz_serial; ++zi) {
             const int z = a.nz_serial - 1 - zi;
-            conv_dispatch<WT, WC, MT, CIC>(a, a.p[z], a.p[z].wp, a.out_off, lds);
+            conv_dispatch<RAGGED, WT, WC, MT, CIC>(a, a.p[z], a.p[z].wp, a.out_off, lds);
             if (zi + 1 < a.nz_serial) __syncthreads();
         }
         return;
@@ -368,7 +380,7 @@ __global__ void __launch_bounds__(256) conv_mfma_f32_kernel(const ConvLaunch a) 
     const ConvProblem& p = a.p[a.z_is_phase ? 0 : z];
     const f32x4* wp = p.wp + (a.z_is_phase ? (int64_t)z * a.phase_wp_stride : 0);
     const int out_off = a.out_off + (a.z_is_phase ? z : 0);
-    conv_dispatch<WT, WC, MT, CIC>(a, p, wp, out_off, lds);
+    conv_dispatch<RAGGED, WT, WC, MT, CIC>(a, p, wp, out_off, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -506,20 +518,28 @@ inline hipError_t launch_conv(ConvLaunch& a, int nz, hipStream_t stream) {
     const int n_t = (a.n_idx + T_BLK - 1) / T_BLK;
     dim3 grid((unsigned)(n_t * a.n_co_blk * nz), (unsigned)a.B, 1u), block(256);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-#define IRIS_LAUNCH_K(...)                                                                        \
+#define IRIS_LAUNCH_STR(...) #__VA_ARGS__
+#define IRIS_LAUNCH_NK(NAME_, ...)                                                                \
     do {                                                                                          \
         auto kfn = __VA_ARGS__;                                                                   \
-        { const hipError_t e__ = ::iris::launch_kernel_named(#__VA_ARGS__, kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
+        { const hipError_t e__ = ::iris::launch_kernel_named(NAME_, kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
     } while (0)
+#define IRIS_LAUNCH_R(...)                                                                        \
+    do { if (a.lengths) IRIS_LAUNCH_NK("conv_mfma_f32_kernel_ragged<" IRIS_LAUNCH_STR(__VA_ARGS__) ">",         \
+                                       conv_mfma_f32_kernel<true, __VA_ARGS__>);                  \
+         else           IRIS_LAUNCH_NK("conv_mfma_f32_kernel<" IRIS_LAUNCH_STR(__VA_ARGS__) ">",                \
+                                       conv_mfma_f32_kernel<false, __VA_ARGS__>); } while (0)
 #define IRIS_LAUNCH(WT_, WC_, CIC_)                                                               \
-    do { if (MT == 1) IRIS_LAUNCH_K(conv_mfma_f32_kernel<WT_, WC_, 1, CIC_>);                     \
-         else         IRIS_LAUNCH_K(conv_mfma_f32_kernel<WT_, WC_, 2, CIC_>); } while (0)
+    do { if (MT == 1) IRIS_LAUNCH_R(WT_, WC_, 1, CIC_);                                           \
+         else         IRIS_LAUNCH_R(WT_, WC_, 2, CIC_); } while (0)
     if (t.WT == 4 && CIC == 32)        IRIS_LAUNCH(4, 1, 32);
     else if (t.WT == 4)                IRIS_LAUNCH(4, 1, 64);
     else if (t.WT == 2)                IRIS_LAUNCH(2, 2, 64);
     else if (CIC == 80)                IRIS_LAUNCH(1, 4, 80);
     else                               IRIS_LAUNCH(1, 4, 64);
-#undef IRIS_LAUNCH_K
+#undef IRIS_LAUNCH_R
+#undef IRIS_LAUNCH_NK
+#undef IRIS_LAUNCH_STR
 #undef IRIS_LAUNCH
     return hipSuccess;       // (every launch above has reported its own status)
 }

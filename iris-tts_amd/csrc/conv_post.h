@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "device_info.h"
 
 namespace iris {
 namespace post {      // self-contained: included by the fp32 and the bf16 translation unit
@@ -37,6 +38,9 @@ struct ConvPostLaunch {
     float slope;
     float inv_n;                // bf16 path: 1 / n_in
     int tiles_per_item;         // rows kernel: ceil(L / kPostTile)
+    const int32_t* lengths;     // ragged forward (fp32): mel frames of each batch item [B] (device), or nullptr
+    int row_scale;              // samples per mel frame (hop): item b has ragged_rows(lengths, b, row_scale, L) samples; the
+                                // rest of its row of y is written as 0
 };
 
 constexpr int kPostTile = 256;
@@ -67,6 +71,13 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunc
     const int t0 = ((int)blockIdx.x - b * a.tiles_per_item) * kPostTile;
     const int R = kPostTile + k - 1;
     const int total = R * PPR;
+    // ragged forward: samples past the item's length read no input and are stored as 0 (block-uniform early exit)
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);
+    if (t0 >= Lb) {
+        const int t = t0 + (int)threadIdx.x;
+        if (t < a.L) a.y[(size_t)b * a.L + t] = 0.f;
+        return;
+    }
     const unsigned tensor_bytes = (unsigned)a.L * (unsigned)(C * ESZ);
     const size_t boff = (size_t)b * a.L * C * ESZ;
     const int n_in = a.n_in;
@@ -93,7 +104,7 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunc
             const int idx = base + u * 256 + (int)threadIdx.x;
             const int r = idx / PPR, pc = idx & (PPR - 1);   // PPR is a compile-time power of two
             const int row = t0 - pad + r;
-            const unsigned voff = (idx < total && row >= 0 && row < a.L) ? (unsigned)(row * C + EPP * pc) * ESZ : kOob;
+            const unsigned voff = (idx < total && row >= 0 && row < Lb) ? (unsigned)(row * C + EPP * pc) * ESZ : kOob;
             ldso[u] = idx < total ? r * S + EPP * pc : -1;
             v0[u] = __builtin_amdgcn_raw_buffer_load_b128(r0, (int)voff, 0, 0);
             if (n_in > 1) {                                   // uniform branch
@@ -130,6 +141,7 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunc
     __syncthreads();
     const int t = t0 + (int)threadIdx.x;
     if (t >= a.L) return;
+    if (t >= Lb) { a.y[(size_t)b * a.L + t] = 0.f; return; }
     const float* __restrict__ w = a.w;
     float acc = a.bias[0];
     const float* row = lds + threadIdx.x * S;
@@ -154,11 +166,17 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const ConvPostLaunc
     const int t0 = ((int)blockIdx.x - b * a.tiles_per_item) * kPostTile;
     const int R = kPostTile + k - 1;
     const int total = R * C;
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);     // (ragged forward: as in conv_post_rows_kernel)
+    if (t0 >= Lb) {
+        const int t = t0 + (int)threadIdx.x;
+        if (t < a.L) a.y[(size_t)b * a.L + t] = 0.f;
+        return;
+    }
     for (int idx = threadIdx.x; idx < total; idx += 256) {
         const int r = idx / C, c = idx - r * C;
         const int row = t0 - pad + r;
         float v = 0.f;
-        if (row >= 0 && row < a.L) {
+        if (row >= 0 && row < Lb) {
             const size_t off = ((size_t)b * a.L + row) * C + c;
             v = ((const float*)a.x[0])[off];
             for (int j = 1; j < a.n_in; ++j) v += ((const float*)a.x[j])[off];
@@ -170,6 +188,7 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const ConvPostLaunc
     __syncthreads();
     const int t = t0 + threadIdx.x;
     if (t >= a.L) return;
+    if (t >= Lb) { a.y[(size_t)b * a.L + t] = 0.f; return; }
     const float* __restrict__ w = a.w;
     float acc = a.bias[0];
     for (int kap = 0; kap < k; ++kap) {

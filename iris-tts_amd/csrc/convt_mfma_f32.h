@@ -44,10 +44,16 @@ struct ConvtLaunch {
                              // then fetches it once); else one job list over the whole grid
     int jobs_per_xcd;        // xcd_order: ceil(n_items / 8) * n_col_blk; else n_tiles
     float slope;
+    const int32_t* lengths;  // ragged forward: mel frames of each batch item [B] (device), or nullptr
+    int row_scale;           // rows of L_in per mel frame: item b has ragged_rows(lengths, b, row_scale, L_in) input rows and
+                             // u times as many output rows; tiles wholly past them are skipped
 };
 
-template <int MT, int NT, int WR, int WC, int TAPS, int NIN>
+// RAGGED: the ragged forward's instantiation (per-item bounds from a.lengths); false: the plain forward's, whose code
+// has no trace of them
+template <bool RAGGED, int MT, int NT, int WR, int WC, int TAPS, int NIN>
 __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunch a) {
+    const int32_t* const lengths = RAGGED ? a.lengths : nullptr;   // ragged forward only (nullptr: every item L rows)
     static_assert(NIN == 1 || NIN == 3, "one input tensor, or the three branch outputs of the previous stage");
     static_assert(WR * WC == 4, "four waves per block");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -113,7 +119,7 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
     };
 
     // ---- a tile = (batch item, row tile, column block); column blocks fastest ----
-    struct Tile { size_t x_off, y_off; int i0; unsigned wvoff[NT]; int ch[NT]; int ph[NT]; };
+    struct Tile { size_t x_off, y_off; int i0; unsigned wvoff[NT]; int ch[NT]; int ph[NT]; unsigned in_bytes; int lb_out; };
     const int xmul = a.xcd_order ? 8 : 1;
     const int xcd = a.xcd_order ? (int)(blockIdx.x & 7) : 0;
     const int slots = a.xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;
@@ -126,6 +132,10 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
         t.x_off = (size_t)b * a.L_in * C;
         t.y_off = (size_t)b * a.L_out * a.C_out;
         t.i0 = rt * R_BLK;
+        // (ragged forward: the window reads 0 past the item's rows, the epilogue stores none of them)
+        const int lb_in = ragged_rows(lengths, b, a.row_scale, a.L_in);
+        t.in_bytes = lengths ? (unsigned)lb_in * (unsigned)C * 4u : in_bytes;
+        t.lb_out = lengths ? lb_in * a.u : a.L_out;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int gct = (cb * WC + wc) * NT + nt;        // 32-wide column tile of the u * C_out columns
@@ -141,13 +151,16 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
     f32x16 acc[MT][NT];
     f32x4 bw[DB + 1][NT];
 
+    // ragged forward: a job whose first output row is past its item's rows computes nothing and is passed over
+    auto job_live = [&](int job) { if (!lengths) return true; const Tile x = make_tile(job); return x.i0 * a.u + a.out_off < x.lb_out; };
     int tile = a.xcd_order ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;       // (a job index of this block's list)
+    while (job_valid(tile) && !job_live(tile)) tile += slots;
     if (!job_valid(tile)) return;
     Tile t = make_tile(tile);
     {   // prologue: the first window and the first weight fragments
         const unsigned vb0 = stage_vbase(t.i0 - (TAPS - 1), 0);
 #pragma unroll
-        for (int i = 0; i < NQ; ++i) stage_load_one(i, t.x_off, in_bytes, vb0);
+        for (int i = 0; i < NQ; ++i) stage_load_one(i, t.x_off, t.in_bytes, vb0);
 #pragma unroll
         for (int d = 0; d < DB; ++d)
 #pragma unroll
@@ -156,7 +169,8 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
         __syncthreads();
     }
     for (;;) {
-        const int tile_next = tile + slots;
+        int tile_next = tile + slots;
+        while (job_valid(tile_next) && !job_live(tile_next)) tile_next += slots;
         const bool more = job_valid(tile_next);
         const Tile tn = make_tile(more ? tile_next : tile);
 #pragma unroll
@@ -172,7 +186,7 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
             // the phase that follows: the next chunk of this tile, or chunk 0 of the block's next tile
             const Tile& tq = last ? tn : t;
             const int cq = last ? 0 : chunk + 1;
-            const unsigned in_bytes_n = has_next ? in_bytes : 0u;       // (nothing follows: zero-length descriptors, the loads return 0)
+            const unsigned in_bytes_n = has_next ? tq.in_bytes : 0u;    // (nothing follows: zero-length descriptors, the loads return 0)
             const unsigned vbn = stage_vbase(tq.i0 - (TAPS - 1), cq * CIC);
             const unsigned wsoff0 = (unsigned)(chunk * GPC) * wbytes_group;
             const unsigned wsoffn = (unsigned)(cq * GPC) * wbytes_group;
@@ -249,7 +263,7 @@ __global__ void __launch_bounds__(256, 2) convt_mfma_f32_kernel(const ConvtLaunc
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         const int o = i * a.u + a.out_off + t.ph[nt];
-                        const bool ok = i < a.n_idx && o >= 0 && o < a.L_out;
+                        const bool ok = i < a.n_idx && o >= 0 && o < t.lb_out;
                         const unsigned voff = ok ? (unsigned)(o * a.C_out + t.ch[nt]) * 4u : kOobOffset;
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
@@ -355,10 +369,14 @@ inline hipError_t launch_convt_gemm(ConvtLaunch& a, int k, hipStream_t stream) {
     const bool three = three_in;
 #define IRIS_CONVT_CASE(MT_, NT_, WR_, WC_)                                                                                   \
     if (t.MT == MT_ && t.NT == NT_ && t.WR == WR_) {                                                                          \
+        if (a.lengths && three) return ::iris::launch_kernel_named("convt_mfma_f32_kernel_ragged<" #MT_ ", " #NT_ ", " #WR_ ", " #WC_ ", 2, 3>", \
+                                           convt_mfma_f32_kernel<true, MT_, NT_, WR_, WC_, 2, 3>, grid, block, lds_bytes, stream, a); \
+        if (a.lengths) return ::iris::launch_kernel_named("convt_mfma_f32_kernel_ragged<" #MT_ ", " #NT_ ", " #WR_ ", " #WC_ ", 2, 1>", \
+                                           convt_mfma_f32_kernel<true, MT_, NT_, WR_, WC_, 2, 1>, grid, block, lds_bytes, stream, a); \
         if (three) return ::iris::launch_kernel_named("convt_mfma_f32_kernel<" #MT_ ", " #NT_ ", " #WR_ ", " #WC_ ", 2, 3>", \
-                                           convt_mfma_f32_kernel<MT_, NT_, WR_, WC_, 2, 3>, grid, block, lds_bytes, stream, a); \
+                                           convt_mfma_f32_kernel<false, MT_, NT_, WR_, WC_, 2, 3>, grid, block, lds_bytes, stream, a); \
         return ::iris::launch_kernel_named("convt_mfma_f32_kernel<" #MT_ ", " #NT_ ", " #WR_ ", " #WC_ ", 2, 1>",            \
-                                           convt_mfma_f32_kernel<MT_, NT_, WR_, WC_, 2, 1>, grid, block, lds_bytes, stream, a); \
+                                           convt_mfma_f32_kernel<false, MT_, NT_, WR_, WC_, 2, 1>, grid, block, lds_bytes, stream, a); \
     }
     IRIS_CONVT_CASE(2, 2, 1, 4)
     IRIS_CONVT_CASE(2, 1, 1, 4)

@@ -1,9 +1,20 @@
 // device_info.h -- per-device facts the launch plans are sized by, and the one place kernels are launched from.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <atomic>
 
 namespace iris {
+
+// Ragged batches (iris_hifigan_forward_ragged): rows of batch item b that a layer of L rows computes, i.e. lengths[b] mel
+// frames of `row_scale` rows each, clamped to [0, L]; L when `lengths` is null (the plain forward: every item is L rows).
+// b is block-uniform, so the length is one scalar load per tile.  Every read and store of the item is bounded by it, which
+// computes the item exactly as a forward of lengths[b] frames would (zero padding at each layer's end).
+__device__ __forceinline__ int ragged_rows(const int32_t* lengths, int b, int row_scale, int L) {
+    if (!lengths) return L;
+    const long long n = (long long)__builtin_amdgcn_readfirstlane(lengths[b]) * row_scale;
+    return n <= 0 ? 0 : (n < (long long)L ? (int)n : L);
+}
 
 // A dry run (iris_hifigan_describe_plan: host-only, no device needed) walks the same forward code -- argument checks,
 // workspace layout, every launch plan -- and records what WOULD be launched instead of launching it.

@@ -420,8 +420,12 @@ int check_forward_args(const iris_hifigan_handle* h, const void* mel_dev, int32_
 
 // The fp32 / split-product forward.  `stop` (forward_until only): return after MRF step stop.step of stage
 // stop.stage has been queued; *mean_in_y0 then says where that stage's result lies (forward_until's contract).
+// `lengths` (iris_hifigan_forward_ragged, fp32 only; nullptr otherwise): mel frames of each batch item on the device.
+// Every launch carries it with its rows per mel frame (`row_scale`), and every kernel bounds the item's reads and stores
+// by them: the plan is the one of (B, T), each item is computed as a forward of its own length would compute it.
 int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, void* wav_dev, void* workspace_dev,
-                uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop, int32_t* until_flags) {
+                uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop, int32_t* until_flags,
+                const int32_t* lengths) {
     const WsLayout w = ws_layout(h, B, T);
     if (workspace_bytes < w.total * sizeof(float))
         return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
@@ -458,6 +462,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
         a.p[0].ks = l.k; a.p[0].dil = 1; a.p[0].pad_left = (l.k - 1) / 2;
         a.B = B; a.L_in = T; a.L_out = T; a.C_in = l.C_in; a.C_out = l.C_out; a.n_idx = T;
         a.in_act = IN_ACT_NONE; a.x_channels_first = 1; a.slope = slope;
+        a.lengths = lengths; a.row_scale = 1;
         TRY(prof.begin(0, -1, 0, 2.0 * fB * T * l.C_in * l.C_out * l.k,
                        4.0 * (fB * T * (l.C_in + l.C_out) + (double)l.ref_w_floats + l.C_out)));
         HIP_TRY(launch_conv(a, 1, stream));
@@ -465,10 +470,12 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
     }
 
     int L = T;
+    int scale = 1;              // rows per mel frame of L (ragged bounds)
     bool prev_summed = false;   // the previous stage left mean(branches) in y[0] (MRF kernel's summing step)
     for (size_t i = 0; i < h->stages.size(); ++i) {
         const Stage& st = h->stages[i];
         const int L_out = L * st.rate;
+        const int scale_out = scale * st.rate;
         // ---- LeakyReLU + ConvTranspose1d (hifigan_pretrained.py:127-128) ----
         {
             ConvLaunch a; init_launch(a);
@@ -492,6 +499,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             a.z_is_phase = 1;
             a.phase_wp_stride = (int64_t)(packed_convt_phase_floats(l.C_in, l.C_out, l.k, l.u) / 4);
             a.slope = slope;
+            a.lengths = lengths; a.row_scale = scale;
             TRY(prof.begin(1, (int)i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
                            4.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out +
                                   (double)l.ref_w_floats + l.C_out)));
@@ -506,6 +514,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
                 c.x = a.p[0].x; c.wp = a.p[0].wp; c.bias = a.p[0].bias; c.y = a.p[0].y;
                 if (a.in_act == IN_ACT_MRF_LRELU) { c.x = a.xmrf[0]; c.x1 = a.xmrf[1]; c.x2 = a.xmrf[2]; }
                 c.B = B; c.L_in = L; c.L_out = L_out; c.C_in = l.C_in; c.C_out = l.C_out; c.u = l.u; c.slope = slope;
+                c.lengths = lengths; c.row_scale = scale;
                 HIP_TRY(launch_convt_gemm(c, l.k, stream));
             } else
                 HIP_TRY(launch_conv(a, l.u, stream));
@@ -532,6 +541,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             }
             a.B = B; a.L_in = L_out; a.L_out = L_out; a.C_in = st.C; a.C_out = st.C;
             a.n_idx = L_out; a.in_act = IN_ACT_LRELU; a.slope = slope;
+            a.lengths = lengths; a.row_scale = scale_out;
             a.dyn_counter = dyn_tiles ? h->tile_counters + ((int)i * 2 * nd + 2 * m + half) : nullptr;
         };
         // The stage's last step `a` as the MRF kernel's summing launch *b, which forms mean_j(y_j) itself: it processes
@@ -569,6 +579,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
                 wbytes += 4.0 * ((double)c1.ref_w_floats + c1.C_out + (double)c2.ref_w_floats + c2.C_out);
             }
             pa.B = B; pa.L = L_out; pa.C = st.C; pa.slope = slope;
+            pa.lengths = lengths; pa.row_scale = scale_out;
             return ok;
         };
         int n_fused = 0;
@@ -665,6 +676,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
             }
         }
         L = L_out;
+        scale = scale_out;
     }
 
     // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141) ----
@@ -675,6 +687,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
         else { for (int j = 0; j < nk; ++j) a.x[j] = ws + w.y[j]; a.n_in = nk; }
         a.w = blob + l.w_off; a.bias = blob + l.b_off; a.y = (float*)wav_dev;
         a.B = B; a.L = L; a.C = l.C_in; a.k = l.k; a.slope = slope; a.inv_n = 1.0f / (float)nk;
+        a.lengths = lengths; a.row_scale = scale;
         TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
                        4.0 * (fB * L * l.C_in * nk + fB * L + (double)l.ref_w_floats + 1)));
         HIP_TRY(post::launch_conv_post(a, stream));
@@ -709,7 +722,36 @@ int32_t iris_hifigan_forward(iris_hifigan_handle* h, const void* mel_dev, int32_
         if (dtype == IRIS_HIFIGAN_BF16)
             TRY(bf16_forward(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, (hipStream_t)stream_, none, nullptr));
         else
-            TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, none, nullptr));
+            TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, none, nullptr, nullptr));
+    }
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_hifigan_forward_ragged(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                    const int32_t* lengths_dev, void* wav_dev, void* workspace_dev,
+                                    uint64_t workspace_bytes, int32_t dtype, void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(check_forward_args(h, mel_dev, B, T, workspace_dev, dtype));
+    if (dtype != IRIS_HIFIGAN_F32)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "the ragged forward supports fp32 (dtype 0) only, got dtype %d: the bf16-storage "
+                    "and split-product paths have no per-item lengths", dtype);
+    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    if (!lengths_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
+    if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    TRY(ensure_prepared(h, dtype, (hipStream_t)stream_, true));
+    // the plan of (B, T), as iris_hifigan_forward: the lengths are never read on the host (fp32 plans are bitwise
+    // plan-independent, so each item still gets the bits of a forward of its own length)
+    const ForwardStop none{-1, -1};
+    const int Bp = pass_items(B, T);
+    for (int b0 = 0; b0 < B; b0 += Bp) {
+        const int nb = B - b0 < Bp ? B - b0 : Bp;
+        const float* mel_p = (const float*)mel_dev + (size_t)b0 * h->cfg.in_channels * T;
+        float* wav_p = (float*)wav_dev + (size_t)b0 * h->hop * T;
+        TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, none, nullptr,
+                        lengths_dev + b0));
     }
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
@@ -733,7 +775,7 @@ int32_t iris_hifigan_forward_until(iris_hifigan_handle* h, const void* mel_dev, 
     const ForwardStop stop{stop_stage, stop_step};
     if (dtype == IRIS_HIFIGAN_BF16)
         return bf16_forward(h, mel_dev, B, T, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream_, stop, flags);
-    return forward_f32(h, mel_dev, B, T, nullptr, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, stop, flags);
+    return forward_f32(h, mel_dev, B, T, nullptr, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, stop, flags, nullptr);
     IRIS_ABI_END
 }
 
@@ -775,7 +817,7 @@ int32_t iris_hifigan_describe_plan(const iris_hifigan_config* cfg, int32_t B, in
     for (int b0 = 0; b0 < B && rc == IRIS_HIFIGAN_OK; b0 += Bp) {          // (the launches of every pass are recorded)
         const int nb = B - b0 < Bp ? B - b0 : Bp;
         rc = dtype == IRIS_HIFIGAN_BF16 ? bf16_forward(&h, mel, nb, T, wav, ws, need, nullptr, none, nullptr)
-                                        : forward_f32(&h, mel, nb, T, wav, ws, need, dtype, nullptr, none, nullptr);
+                                        : forward_f32(&h, mel, nb, T, wav, ws, need, dtype, nullptr, none, nullptr, nullptr);
     }
     out->n_launches = dry.n;
     for (int i = 0; i < dry.n && i < IRIS_HIFIGAN_MAX_PLAN_LAUNCHES; ++i) {

@@ -95,8 +95,11 @@ __device__ __forceinline__ T* uniform_ptr_mrf(T* p) {     // a block-uniform poi
 //     then of row tile 1), and row tile m's fragment of the NEXT group is requested as soon as its four MFMAs have issued
 //     (256 cycles ahead of its use).  v_mfma_f32_32x32x2_f32 chains on one accumulator back to back (SrcC forwarding).
 // Every output element is the same fmaf chain in the same order as in the MINW = 2 form: bit-identical.
-template <int WT, int WC, int MT, int CIC, int DB, int KA, int KB, int KC, bool SUM, int ZPAR, int MINW = IRIS_MRF_MINWAVES, bool LEANP = (MINW >= 3)>
+// RAGGED: the ragged forward's instantiation (per-item bounds from a.lengths); false: the plain forward's, whose code
+// has no trace of them
+template <bool RAGGED, int WT, int WC, int MT, int CIC, int DB, int KA, int KB, int KC, bool SUM, int ZPAR, int MINW = IRIS_MRF_MINWAVES, bool LEANP = (MINW >= 3)>
 __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const ConvLaunch a) {
+    const int32_t* const lengths = RAGGED ? a.lengths : nullptr;   // ragged forward only (nullptr: every item L rows)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool LEAN = LEANP;
     constexpr int S = CIC + 4;
@@ -144,6 +147,8 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         unsigned ovoff4;    // byte offset of this lane's 16-byte output piece for (m=0, g=0): row
                             // i0 + wave rows + lo, channels co4..co4+3 (co4 = tile base + 4*hi); out of range if unused
         int co4;
+        unsigned tbytes;    // num_records of the item's descriptors: its rows x C x 4 (ragged forward: rows past its length
+                            // read 0 and their stores are dropped -- the zero padding of a forward of that length)
     };
     auto make_tile = [&](int tile) {
         Tile t;
@@ -158,7 +163,14 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         t.co4 = ct * 32 + 4 * hi;
         t.ovoff4 = (active && t.co4 < a.C_out)
                        ? (unsigned)((t.i0 + wt * MT * 32 + lo) * C + t.co4) * 4u : kOobOffset;
+        t.tbytes = lengths ? (unsigned)ragged_rows(lengths, b, a.row_scale, L) * (unsigned)C * 4u : tensor_bytes;
         return t;
+    };
+    // ragged forward: a tile whose first row is past its item's rows has nothing to compute and is passed over
+    auto tile_live = [&](int tile) {
+        if (!lengths) return true;
+        const int b = tile / tiles_per_item, tile_t = (tile - b * tiles_per_item) / a.n_co_blk;
+        return tile_t * T_BLK < ragged_rows(lengths, b, a.row_scale, L);
     };
 
     // One staged quad = 16 bytes of row (in_row0 + r_lane + i*RPI), channels [c0+4q, c0+4q+4).
@@ -197,7 +209,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
 
     // What follows a branch's last chunk: the next branch of the same tile, a branch of the block's next tile or job -- or
     // nothing (valid == false) at the very end.
-    struct NextJob { bool valid; size_t batch_off; int i0; unsigned wvoff; const float* x; const f32x4* wp; int ks, dil, pad_left; };
+    struct NextJob { bool valid; size_t batch_off; int i0; unsigned wvoff; unsigned tbytes; const float* x; const f32x4* wp; int ks, dil, pad_left; };
 
     // One branch (problem p, KS taps) of tile `t`: all C_in chunks, then its epilogue.  get_next() is called once, at the
     // start of the branch's LAST chunk, and says which
@@ -213,8 +225,8 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         // goes into the scalar offset, rows >= L fall outside num_records (store dropped, load 0), lanes
         // with channels >= C_out get an out-of-range ovoff4.  A branch without residual uses a
         // zero-length descriptor, whose loads return 0.
-        const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + t.batch_off, tensor_bytes);
-        const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + t.batch_off : p.y, p.res ? tensor_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y + t.batch_off, t.tbytes);
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(p.res ? p.res + t.batch_off : p.y, p.res ? t.tbytes : 0u);
         // loaded here, not in the epilogue: vmcnt retires in order, so a load issued in the epilogue
         // would have to wait for every prefetch issued by the last MFMA groups
         f32x4 bias4[4];                                  // channels co4 + 8g + {0..3}
@@ -238,7 +250,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         for (int chunk = 0; chunk < n_chunks; ++chunk) {
             const bool last = chunk + 1 == n_chunks;
             NextJob nj;
-            nj.valid = false; nj.batch_off = t.batch_off; nj.i0 = t.i0; nj.wvoff = t.wvoff;
+            nj.valid = false; nj.batch_off = t.batch_off; nj.i0 = t.i0; nj.wvoff = t.wvoff; nj.tbytes = t.tbytes;
             nj.x = p.x; nj.wp = p.wp; nj.ks = KS; nj.dil = p.dil; nj.pad_left = p.pad_left;
             if (last) nj = get_next();
             const bool next_valid = nj.valid;
@@ -253,7 +265,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             const int dilq = cross ? nj.dil : p.dil;
             const int padq = cross ? nj.pad_left : p.pad_left;
             const int i0q = cross ? nj.i0 : t.i0;
-            const __amdgpu_buffer_rsrc_t xrn = make_rsrc(xq, tensor_bytes);
+            const __amdgpu_buffer_rsrc_t xrn = make_rsrc(xq, cross ? nj.tbytes : t.tbytes);
             const __amdgpu_buffer_rsrc_t wrn = make_rsrc(wq, (unsigned)(ksq * a.Gp) * wbytes_group);
             const int Rn = T_BLK + (ksq - 1) * dilq;
             const unsigned vbn = stage_vbase(i0q - padq, last ? 0 : (chunk + 1) * CIC);
@@ -390,7 +402,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                 if constexpr (LEAN && (!SUM || PI == 0)) {
                     // straight from the accumulators / the running sum: these registers are next written by the zero-init of
                     // the following branch, i.e. behind the LDS write and both barriers below (keep-alive there)
-                    const __amdgpu_buffer_rsrc_t yo = SUM ? make_rsrc(a.sum_y + t.batch_off, tensor_bytes) : yr;
+                    const __amdgpu_buffer_rsrc_t yo = SUM ? make_rsrc(a.sum_y + t.batch_off, t.tbytes) : yr;
 #pragma unroll
                     for (int idx = 0; idx < MT * 4; ++idx) {
                         const f32x16& src = SUM ? sumv[idx / 4] : acc[idx / 4];
@@ -401,7 +413,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
                     asm volatile("s_nop 1");
                     stored = true;
                 } else if constexpr (!SUM || PI == 0) {
-                    const __amdgpu_buffer_rsrc_t yo = SUM ? make_rsrc(a.sum_y + t.batch_off, tensor_bytes) : yr;
+                    const __amdgpu_buffer_rsrc_t yo = SUM ? make_rsrc(a.sum_y + t.batch_off, t.tbytes) : yr;
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -452,7 +464,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
     // block exposes)
     auto prologue = [&](const float* x0, const f32x4* wp0, int ks0, int dil0, int pad0, const Tile& t) {
         const int R0 = T_BLK + (ks0 - 1) * dil0;
-        const __amdgpu_buffer_rsrc_t xr0 = make_rsrc(x0 + t.batch_off, tensor_bytes);
+        const __amdgpu_buffer_rsrc_t xr0 = make_rsrc(x0 + t.batch_off, t.tbytes);
         const __amdgpu_buffer_rsrc_t wr0 = make_rsrc(wp0, (unsigned)(ks0 * a.Gp) * wbytes_group);
         const unsigned vb0 = stage_vbase(t.i0 - pad0, 0);
 #pragma unroll
@@ -467,7 +479,7 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         constexpr int PN = decltype(pn_tag)::value;
         // (pinned to SGPRs here: a select between fields of the kernel-argument struct is otherwise turned into a load from a
         //  selected ADDRESS, i.e. a table in private memory)
-        return NextJob{valid, tn.batch_off, tn.i0, tn.wvoff, uniform_ptr_mrf(a.p[PN].x), uniform_ptr_mrf(a.p[PN].wp),
+        return NextJob{valid, tn.batch_off, tn.i0, tn.wvoff, tn.tbytes, uniform_ptr_mrf(a.p[PN].x), uniform_ptr_mrf(a.p[PN].wp),
                        __builtin_amdgcn_readfirstlane(a.p[PN].ks), __builtin_amdgcn_readfirstlane(a.p[PN].dil),
                        __builtin_amdgcn_readfirstlane(a.p[PN].pad_left)};
     };
@@ -476,6 +488,23 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         // equal-cost blocks: every block runs all three branches of its tiles, heaviest first:
         // p[2] (KC taps), p[1] (KB), p[0] (KA); persistent over tiles
         int tile = blockIdx.x;
+        // (ragged forward: a tile past its item's rows is replaced at once -- by the block's next stride, or by draws from the
+        //  counter, which thread 0 makes until it holds a live tile or none is left)
+        auto draw = [&]() {
+            unsigned n = gridDim.x + atomicAdd(a.dyn_counter, 1u);
+            while (n < (unsigned)n_tiles && !tile_live((int)n)) n = gridDim.x + atomicAdd(a.dyn_counter, 1u);
+            return n;
+        };
+        if (lengths && tile < n_tiles && !tile_live(tile)) {
+            if (a.dyn_counter) {
+                if (tid == 0) *next_slot = draw();
+                __syncthreads();
+                tile = (int)*next_slot;
+                __syncthreads();
+            } else {
+                while (tile < n_tiles && !tile_live(tile)) tile += (int)gridDim.x;
+            }
+        }
         if (tile >= n_tiles) return;
         Tile t = make_tile(tile);
         prologue(a.p[2].x, a.p[2].wp, KC, a.p[2].dil, a.p[2].pad_left, t);        // (the host orders the branches: p[2] has KC taps)
@@ -483,9 +512,10 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         // it at the start of a tile and leaves it in an LDS word behind the window; everybody reads it after the
         // barriers that end the first branch -- long before the last branch needs it for its prefetch.
         for (;;) {
-            if (a.dyn_counter && tid == 0) *next_slot = gridDim.x + atomicAdd(a.dyn_counter, 1u);
+            if (a.dyn_counter && tid == 0) *next_slot = draw();
             run_branch(std::integral_constant<int, KC>{}, I2{}, t, [&] { return next_of(I1{}, true, t); });
-            const int tile_next = a.dyn_counter ? (int)*next_slot : tile + (int)gridDim.x;
+            int tile_next = a.dyn_counter ? (int)*next_slot : tile + (int)gridDim.x;
+            if (!a.dyn_counter) while (tile_next < n_tiles && !tile_live(tile_next)) tile_next += (int)gridDim.x;
             const bool more = (unsigned)tile_next < (unsigned)n_tiles;
             const Tile tn = make_tile(more ? tile_next : tile);
             run_branch(std::integral_constant<int, KB>{}, I1{}, t, [&] { return next_of(I0{}, true, t); });
@@ -504,13 +534,15 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         const int zb = bx < a.zb1 ? 2 : (bx < a.zb2 ? 1 : 0);
         const int step = zb == 2 ? a.zb1 : (zb == 1 ? a.zb2 - a.zb1 : (int)gridDim.x - a.zb2);
         int tile = zb == 2 ? bx : (zb == 1 ? bx - a.zb1 : bx - a.zb2);
+        while (tile < n_tiles && !tile_live(tile)) tile += step;
         if (tile >= n_tiles) return;
         Tile t = make_tile(tile);
         auto walk = [&](auto ks_tag, auto pi_tag) {
             constexpr int PI = decltype(pi_tag)::value;
             prologue(a.p[PI].x, a.p[PI].wp, decltype(ks_tag)::value, a.p[PI].dil, a.p[PI].pad_left, t);
             for (;;) {
-                const int tile_next = tile + step;
+                int tile_next = tile + step;
+                while (tile_next < n_tiles && !tile_live(tile_next)) tile_next += step;
                 const bool more = tile_next < n_tiles;
                 const Tile tn = make_tile(more ? tile_next : tile);
                 run_branch(ks_tag, pi_tag, t, [&] { return next_of(pi_tag, more, tn); });
@@ -533,7 +565,11 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
         //  trip, 2-4 us on jobs of 12-50 us; profiles/r03_notes.md.)
         const int n_jobs = 3 * n_tiles;
         const int G = (int)gridDim.x, bx = (int)blockIdx.x;
-        if (bx >= n_jobs) return;
+        auto job_of = [&](int r) { return r * G + ((r & 1) ? G - 1 - bx : bx); };
+        int round = 0;
+        int job = bx;
+        while (job < n_jobs && !tile_live(job % n_tiles)) job = job_of(++round);      // (ragged forward: jobs past an item's rows)
+        if (job >= n_jobs) return;
         // the problem of branch z, every field pinned to an SGPR before the selection (a plain select over kernel-argument
         // structs becomes a per-lane table lookup: mrf_pair_f32_pf.h)
         auto problem_of = [&](int z, const Tile& tn, bool valid) __attribute__((always_inline)) {
@@ -543,20 +579,19 @@ __global__ void __launch_bounds__(256, MINW) mrf_conv_mfma_f32_kernel(const Conv
             auto sel_p = [&](auto p0, auto p1, auto p2) { auto v = uniform_ptr_mrf(p0);
                                                           if (z == 1) v = uniform_ptr_mrf(p1);
                                                           if (z == 2) v = uniform_ptr_mrf(p2); return v; };
-            return NextJob{valid, tn.batch_off, tn.i0, tn.wvoff, sel_p(a.p[0].x, a.p[1].x, a.p[2].x), sel_p(a.p[0].wp, a.p[1].wp, a.p[2].wp),
+            return NextJob{valid, tn.batch_off, tn.i0, tn.wvoff, tn.tbytes, sel_p(a.p[0].x, a.p[1].x, a.p[2].x), sel_p(a.p[0].wp, a.p[1].wp, a.p[2].wp),
                            sel_i(a.p[0].ks, a.p[1].ks, a.p[2].ks), sel_i(a.p[0].dil, a.p[1].dil, a.p[2].dil),
                            sel_i(a.p[0].pad_left, a.p[1].pad_left, a.p[2].pad_left)};
         };
-        int round = 0;
-        int z = 2 - bx / n_tiles;
-        Tile t = make_tile(bx - (2 - z) * n_tiles);
+        int z = 2 - job / n_tiles;
+        Tile t = make_tile(job - (2 - z) * n_tiles);
         {
             const NextJob first = problem_of(z, t, true);
             prologue(first.x, first.wp, first.ks, first.dil, first.pad_left, t);
         }
         for (;;) {
-            ++round;
-            const int job_next = round * G + ((round & 1) ? G - 1 - bx : bx);
+            int job_next = job_of(++round);
+            while (job_next < n_jobs && !tile_live(job_next % n_tiles)) job_next = job_of(++round);
             const bool more = job_next < n_jobs;
             const int zn = more ? 2 - job_next / n_tiles : z;
             const Tile tn = make_tile(more ? job_next - (2 - zn) * n_tiles : 0);
@@ -810,19 +845,26 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
     const long long n_tiles = plx.n_tiles, g = plx.grid;
     if (n_tiles > 0x7fffffffLL / 3) return hipErrorInvalidValue;
     dim3 grid((unsigned)g, 1u, 1u), block(256);
-#define IRIS_MRF_LAUNCH_K(...)                                                                    \
+    // the plain forward's kernel, or its ragged twin (iris_hifigan_forward_ragged)
+#define IRIS_MRF_STR(...) #__VA_ARGS__
+#define IRIS_MRF_LAUNCH_NK(NAME_, ...)                                                            \
     do {                                                                                          \
         auto kfn = __VA_ARGS__;                                                                   \
-        { const hipError_t e__ = ::iris::launch_kernel_named(#__VA_ARGS__, kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
+        { const hipError_t e__ = ::iris::launch_kernel_named(NAME_, kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
     } while (0)
+#define IRIS_MRF_LAUNCH_KR(...)                                                                   \
+    do { if (a.lengths) IRIS_MRF_LAUNCH_NK("mrf_conv_mfma_f32_kernel_ragged<" IRIS_MRF_STR(__VA_ARGS__) ">",   \
+                                           mrf_conv_mfma_f32_kernel<true, __VA_ARGS__>);          \
+         else           IRIS_MRF_LAUNCH_NK("mrf_conv_mfma_f32_kernel<" IRIS_MRF_STR(__VA_ARGS__) ">",          \
+                                           mrf_conv_mfma_f32_kernel<false, __VA_ARGS__>); } while (0)
     // (the 128-row form exists for the wide tile only: IRIS_MRF_LAUNCH_TALL refuses the others)
 #define IRIS_MRF_LAUNCH_TALL(WT_, WC_, CIC_) IRIS_MRF_LAUNCH_TALL_##WT_(WC_, CIC_)
-#define IRIS_MRF_LAUNCH_TALL_1(WC_, CIC_) IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<1, WC_, 4, CIC_, 2, 3, 7, 11, false, 0, 2, true>)
+#define IRIS_MRF_LAUNCH_TALL_1(WC_, CIC_) IRIS_MRF_LAUNCH_KR(1, WC_, 4, CIC_, 2, 3, 7, 11, false, 0, 2, true)
 #define IRIS_MRF_LAUNCH_TALL_2(WC_, CIC_) return hipErrorInvalidValue
 #define IRIS_MRF_LAUNCH_TALL_4(WC_, CIC_) return hipErrorInvalidValue
     // (snake-ordered jobs need two or more C_in chunks -- mrf_plan's zdyn_ok: the wide tile only; the narrow tiles are not instantiated)
 #define IRIS_MRF_LAUNCH_SNAKE(WT_, WC_, MT_, CIC_, D_) IRIS_MRF_LAUNCH_SNAKE_##WT_(WC_, MT_, CIC_, D_)
-#define IRIS_MRF_LAUNCH_SNAKE_1(WC_, MT_, CIC_, D_) IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<1, WC_, MT_, CIC_, D_, 3, 7, 11, false, 2>)
+#define IRIS_MRF_LAUNCH_SNAKE_1(WC_, MT_, CIC_, D_) IRIS_MRF_LAUNCH_KR(1, WC_, MT_, CIC_, D_, 3, 7, 11, false, 2)
 #define IRIS_MRF_LAUNCH_SNAKE_2(WC_, MT_, CIC_, D_) return hipErrorInvalidValue
 #define IRIS_MRF_LAUNCH_SNAKE_4(WC_, MT_, CIC_, D_) return hipErrorInvalidValue
 #define IRIS_MRF_LAUNCH_DB(WT_, WC_, CIC_, D1_, D2_)                                                       \
@@ -830,12 +872,12 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
         if (tall) IRIS_MRF_LAUNCH_TALL(WT_, WC_, CIC_);                                            \
         else if (pl.MT == 2) {                                                                    \
             if (pl.zdyn) IRIS_MRF_LAUNCH_SNAKE(WT_, WC_, 2, CIC_, D2_);                           \
-            else if (a.sum_y) IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 2, CIC_, D2_, 11, 7, 3, true, 0>);   \
-            else         IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 2, CIC_, D2_, 3, 7, 11, false, 0>);  \
-        } else if (a.sum_y)  IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 1, CIC_, D1_, 11, 7, 3, true, 0>);   \
+            else if (a.sum_y) IRIS_MRF_LAUNCH_KR(WT_, WC_, 2, CIC_, D2_, 11, 7, 3, true, 0);   \
+            else         IRIS_MRF_LAUNCH_KR(WT_, WC_, 2, CIC_, D2_, 3, 7, 11, false, 0);  \
+        } else if (a.sum_y)  IRIS_MRF_LAUNCH_KR(WT_, WC_, 1, CIC_, D1_, 11, 7, 3, true, 0);   \
         else if (pl.zdyn)    IRIS_MRF_LAUNCH_SNAKE(WT_, WC_, 1, CIC_, D1_);                       \
-        else if (pl.zpar)    IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 1>);   \
-        else                 IRIS_MRF_LAUNCH_K(mrf_conv_mfma_f32_kernel<WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 0>);  \
+        else if (pl.zpar)    IRIS_MRF_LAUNCH_KR(WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 1);   \
+        else                 IRIS_MRF_LAUNCH_KR(WT_, WC_, 1, CIC_, D1_, 3, 7, 11, false, 0);  \
     } while (0)
     if (t.WT == 4)          IRIS_MRF_LAUNCH_DB(4, 1, 32, 4, 4);     // C <= 32 (mrf_kernel_applicable: CIC == 32 there)
     else if (t.WT == 2)     IRIS_MRF_LAUNCH_DB(2, 2, 64, IRIS_MRF_RING_MT1, 4);
@@ -849,7 +891,9 @@ inline hipError_t launch_mrf_conv(ConvLaunch& a, int nz, hipStream_t stream, int
 #undef IRIS_MRF_LAUNCH_TALL_1
 #undef IRIS_MRF_LAUNCH_TALL_2
 #undef IRIS_MRF_LAUNCH_TALL_4
-#undef IRIS_MRF_LAUNCH_K
+#undef IRIS_MRF_LAUNCH_KR
+#undef IRIS_MRF_LAUNCH_NK
+#undef IRIS_MRF_STR
     return hipSuccess;       // (every launch above has reported its own status)
 }
 #endif  // IRIS_KERNELS_ONLY

@@ -49,6 +49,8 @@ struct PairLaunchF32 {
     int nz;               // branches
     int Gp, n_ct;         // packed-weight geometry (packed_groups / packed_cotiles of C)
     int n_jobs;           // tiles x branches (tiles = ceil(L / smallest T_OUT))
+    const int32_t* lengths;  // ragged forward: mel frames of each batch item [B] (device), or nullptr
+    int row_scale;           // rows of L per mel frame: item b has ragged_rows(lengths, b, row_scale, L) rows
 };
 
 // The MFMA loop of one conv over the LDS window: NG = KS * GPC groups of 8 channels; weight fragment n + DB is
@@ -88,8 +90,11 @@ __device__ __forceinline__ void pair_f32_mma(f32x16 (&acc)[MT], f32x4 (&bw)[DB +
     }
 }
 
-template <int WT, int WC, int MT, int C, int MINB>
+// RAGGED: the ragged forward's instantiation (per-item bounds from a.lengths); false: the plain forward's, whose code
+// has no trace of them
+template <bool RAGGED, int WT, int WC, int MT, int C, int MINB>
 __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunchF32 a) {
+    const int32_t* const lengths = RAGGED ? a.lengths : nullptr;   // ragged forward only (nullptr: every item L rows)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     static_assert(WT * WC == 4 && WC * 32 == C, "a block owns all C channels");
     constexpr int S = C + 4;
@@ -118,8 +123,11 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunc
     const int T_OUT = M - (ks - 1);
     const int o0 = tile * T_OUT;
     const int L = a.L;
-    if (o0 >= L) return;                              // (tiles are counted for the smallest T_OUT of the launch)
     const int b = blockIdx.y;
+    // the item's rows (ragged forward; L otherwise): the window reads 0 past them, conv2 sees xt as 0 there (its zero
+    // padding), and no output row past them is stored
+    const int Lb = ragged_rows(lengths, b, a.row_scale, L);
+    if (o0 >= Lb) return;                             // (tiles are counted for the smallest T_OUT of the launch)
     const float slope = a.slope;
 
     const unsigned tensor_bytes = (unsigned)L * (unsigned)C * 4u;
@@ -149,7 +157,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunc
             const int idx = u * 256 + tid;
             const int r = idx / QPR, q = idx & (QPR - 1);
             const int row = in_row0 + r;
-            const bool ok = idx < total && row >= 0 && row < L;
+            const bool ok = idx < total && row >= 0 && row < Lb;
             st[u] = buf_load4(xr, ok ? (unsigned)(row * C + 4 * q) * 4u : kOobOffset, 0);
         }
 #pragma unroll
@@ -193,7 +201,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunc
     for (int m = 0; m < MT; ++m) {
         const int im = (wt * MT + m) * 32 + lo;
         const int o = o0 + im;
-        ovoff[m] = (im < T_OUT && o < L) ? (unsigned)(o * C + co4) * 4u : kOobOffset;
+        ovoff[m] = (im < T_OUT && o < Lb) ? (unsigned)(o * C + co4) * 4u : kOobOffset;
 #pragma unroll
         for (int g = 0; g < 4; ++g) resv[m * 4 + g] = buf_load4(xr, ovoff[m], (unsigned)(8 * g) * 4u);
     }
@@ -203,7 +211,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_kernel(const PairLaunc
     for (int m = 0; m < MT; ++m) {
         const int row_l = (wt * MT + m) * 32 + lo;
         const int row_g = o0 - h2 + row_l;
-        const bool inside = row_g >= 0 && row_g < L;
+        const bool inside = row_g >= 0 && row_g < Lb;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             f32x4 v;
@@ -312,7 +320,9 @@ inline hipError_t launch_pair_f32(PairLaunchF32& a, int nz, hipStream_t stream) 
     dim3 grid((unsigned)((n_jobs + 7) / 8 * 8), (unsigned)a.B, 1u), block(256);     // (whole rounds of 8: blocks past n_jobs return)
 #define IRIS_PAIR_F32_CASE(WT_, WC_, MT_, C_, MINB_)                                                         \
     if (a.C == C_ && t.WT == WT_ && t.MT == MT_) {                                                           \
-        auto kfn = mrf_pair_f32_kernel<WT_, WC_, MT_, C_, MINB_>;                                            \
+        if (a.lengths) return ::iris::launch_kernel_named("mrf_pair_f32_kernel_ragged", mrf_pair_f32_kernel<true, WT_, WC_, MT_, C_, MINB_>, \
+                                                          grid, block, lds_bytes, stream, a);                \
+        auto kfn = mrf_pair_f32_kernel<false, WT_, WC_, MT_, C_, MINB_>;                                            \
         { const hipError_t e__ = ::iris::launch_kernel_named("mrf_pair_f32_kernel", kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
         return hipSuccess;                                                                                   \
     }

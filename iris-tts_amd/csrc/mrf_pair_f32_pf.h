@@ -50,6 +50,8 @@ struct PairPfLaunchF32 {
     int bias_off;         // float offset of the bias table in LDS
     float* sum_y;         // SUM: [B, L, C] mean of the branch outputs
     float sum_div;        // SUM: num_kernels
+    const int32_t* lengths;  // ragged forward: mel frames of each batch item [B] (device), or nullptr
+    int row_scale;           // rows of L per mel frame: item b has ragged_rows(lengths, b, row_scale, L) rows
 };
 
 // One conv over the LDS window, unrolled for KS taps: NG = KS * GPC groups of 8 channels.  Ring slot n % (DB+1) holds
@@ -111,8 +113,11 @@ __device__ __forceinline__ T* uniform_ptr_f32(T* p) {
     return (T*)(((unsigned long long)hi << 32) | lo);
 }
 
-template <int WT, int WC, int MT, int C, int MINB, bool SUM>
+// RAGGED: the ragged forward's instantiation (per-item bounds from a.lengths); false: the plain forward's, whose code
+// has no trace of them
+template <bool RAGGED, int WT, int WC, int MT, int C, int MINB, bool SUM>
 __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPfLaunchF32 a) {
+    const int32_t* const lengths = RAGGED ? a.lengths : nullptr;   // ragged forward only (nullptr: every item L rows)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     static_assert(WT * WC == 4 && WC * 32 == C, "a block owns all C channels");
     constexpr int S = C + 4;
@@ -127,7 +132,6 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
     const int lo = lane & 31, hi = lane >> 5;
     const int L = a.L;
     const float slope = a.slope;
-    const unsigned tensor_bytes = (unsigned)L * (unsigned)C * 4u;
     const unsigned wbytes_group = (unsigned)a.n_ct * 64u * 16u;
     const unsigned tap_bytes = (unsigned)a.Gp * wbytes_group;
     const unsigned wvoff = (unsigned)(wc * 64 + lane) * 16u;              // this wave's 32-wide channel tile = wc
@@ -156,7 +160,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
     // A block starts with job blockIdx.x and draws every further job from a device counter (longest jobs first + first come
     // first served = the launch ends on short jobs, whatever speed each CU runs at); without a counter it walks a fixed stride.
     const int G = (int)gridDim.x;
-    struct Step { const float* x; const f32x4* w1; const f32x4* w2; float* y; int ks, dil, b, o0, z, job; };
+    struct Step { const float* x; const f32x4* w1; const f32x4* w2; float* y; int ks, dil, b, o0, z, job, lb; };   // lb: the item's rows
     // (always_inline: called from two places; left out of line, the closure's pointer to the kernel arguments would force
     //  hipcc to keep them -- and everything derived from them -- in scratch instead of SGPRs)
     auto load_step = [&](int job, int z_sum, Step& s) __attribute__((always_inline)) {
@@ -202,6 +206,21 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
         s.b = bb;
         s.o0 = tile * (SUM ? a.t_out : M - (s.ks - 1));
         s.z = z; s.job = job;
+        s.lb = ragged_rows(lengths, bb, a.row_scale, L);
+    };
+    // num_records of a step's item descriptors: its rows x C x 4 (ragged forward: rows past them read 0, their stores drop)
+    auto item_bytes = [&](const Step& s) -> unsigned { return (unsigned)s.lb * (unsigned)C * 4u; };
+    // ragged forward: a job whose first output row is past its item's rows computes nothing and is passed over
+    auto job_live = [&](int job) __attribute__((always_inline)) {
+        if (!lengths) return true;
+        if constexpr (SUM) {
+            const int bb = job / a.tiles[0];
+            return (job - bb * a.tiles[0]) * a.t_out < ragged_rows(lengths, bb, a.row_scale, L);
+        } else {
+            Step s;
+            load_step(job, 0, s);
+            return s.o0 < s.lb;
+        }
     };
     int* const next_slot = reinterpret_cast<int*>(lds_bias + a.nz * 2 * C);     // LDS word: the job drawn for this block's next step
     auto window_vbase = [&](const Step& s) -> unsigned {
@@ -236,11 +255,28 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
     };
 
     Step J;
-    if ((int)blockIdx.x >= a.n_jobs) return;
-    load_step((int)blockIdx.x, 0, J);
+    int first = (int)blockIdx.x;
+    if (lengths && first < a.n_jobs && !job_live(first)) {
+        // (a job past its item's rows is replaced at once: by draws from the counter, which thread 0 makes until it holds a
+        //  live job or none is left, or by the block's next stride)
+        if (a.next_job) {
+            if (tid == 0) {
+                int n;
+                do n = G + (int)atomicAdd(a.next_job, 1u); while (n < a.n_jobs && !job_live(n));
+                *next_slot = n;
+            }
+            __syncthreads();
+            first = __builtin_amdgcn_readfirstlane(*next_slot);
+            __syncthreads();
+        } else {
+            while (first < a.n_jobs && !job_live(first)) first += G;
+        }
+    }
+    if (first >= a.n_jobs) return;
+    load_step(first, 0, J);
     // ---- prologue: the only window wait a block exposes ---------------------------------------------------------------
     {
-        const __amdgpu_buffer_rsrc_t xr = make_rsrc(J.x + (size_t)J.b * L * C, tensor_bytes);
+        const __amdgpu_buffer_rsrc_t xr = make_rsrc(J.x + (size_t)J.b * L * C, item_bytes(J));
         const __amdgpu_buffer_rsrc_t wr1 = make_rsrc(J.w1, (unsigned)J.ks * tap_bytes);
 #pragma unroll
         for (int d = 0; d < DB; ++d) bw[d] = buf_load4(wr1, wvoff, (unsigned)d * wbytes_group);
@@ -258,13 +294,14 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
         bool more = false;
         const bool new_job = !SUM || J.z + 1 >= a.nz;
         int drawn = J.job + G;                                            // fixed stride, unless a counter is given
+        if (!a.next_job) while (drawn < a.n_jobs && !job_live(drawn)) drawn += G;
         const int ks = J.ks, dil = J.dil;
         const int h2 = (ks - 1) / 2;
         const int T_OUT = SUM ? a.t_out : M - (ks - 1);
         const int o0 = J.o0;
         const size_t item = (size_t)J.b * L * C;
-        const __amdgpu_buffer_rsrc_t xr = make_rsrc(J.x + item, tensor_bytes);
-        const __amdgpu_buffer_rsrc_t yr = make_rsrc((SUM ? a.sum_y : J.y) + item, tensor_bytes);
+        const __amdgpu_buffer_rsrc_t xr = make_rsrc(J.x + item, item_bytes(J));
+        const __amdgpu_buffer_rsrc_t yr = make_rsrc((SUM ? a.sum_y : J.y) + item, item_bytes(J));
         const __amdgpu_buffer_rsrc_t wr1 = make_rsrc(J.w1, (unsigned)ks * tap_bytes);
         const __amdgpu_buffer_rsrc_t wr2 = make_rsrc(J.w2, (unsigned)ks * tap_bytes);
         __amdgpu_buffer_rsrc_t xrn = xr, wr1n = wr1;
@@ -283,7 +320,9 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
             zero_acc();
             pair_pf_f32_mma<KS, MT, GPC, DB, 0>(acc, bw, aptr, dil * S, S, wr1, wr2, wvoff, wbytes_group, tap_bytes, [](int) {});
             // draw the next job (one lane; the answer is picked up behind the xt step)
-            if (a.next_job && new_job && tid == 0) drawn = G + (int)atomicAdd(a.next_job, 1u);
+            if (a.next_job && new_job && tid == 0) {
+                do drawn = G + (int)atomicAdd(a.next_job, 1u); while (lengths && drawn < a.n_jobs && !job_live(drawn));
+            }
             // the residual pieces travel during step 3 and conv2
             unsigned ovoff[MT];                                           // piece (m, g = 0) of this lane, or out of range
             f32x4 resv[MT * 4];
@@ -291,7 +330,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
             for (int m = 0; m < MT; ++m) {
                 const int im = (wt * MT + m) * 32 + lo;
                 const int o = o0 + im;
-                ovoff[m] = (im < T_OUT && o < L) ? (unsigned)(o * C + co4) * 4u : kOobOffset;
+                ovoff[m] = (im < T_OUT && o < J.lb) ? (unsigned)(o * C + co4) * 4u : kOobOffset;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) resv[m * 4 + g] = buf_load4(xr, ovoff[m], (unsigned)(8 * g) * 4u);
             }
@@ -301,7 +340,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
             for (int m = 0; m < MT; ++m) {
                 const int row_l = (wt * MT + m) * 32 + lo;
                 const int row_g = o0 - h2 + row_l;
-                const bool inside = row_g >= 0 && row_g < L;
+                const bool inside = row_g >= 0 && row_g < J.lb;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 b4 = *reinterpret_cast<const f32x4*>(b1p + 8 * g);
@@ -322,7 +361,7 @@ __global__ void __launch_bounds__(256, MINB) mrf_pair_f32_pf_kernel(const PairPf
                 if (new_job) nj = __builtin_amdgcn_readfirstlane(a.next_job ? *next_slot : drawn);
                 more = nj < a.n_jobs;
                 if (more) load_step(nj, new_job ? 0 : J.z + 1, Jn);
-                xrn = make_rsrc(Jn.x + (size_t)Jn.b * L * C, more ? tensor_bytes : 0u);
+                xrn = make_rsrc(Jn.x + (size_t)Jn.b * L * C, more ? item_bytes(Jn) : 0u);
                 wr1n = make_rsrc(Jn.w1, more ? (unsigned)Jn.ks * tap_bytes : 0u);
                 vbn = window_vbase(Jn);
                 Rn = M + (Jn.ks - 1) * Jn.dil;
@@ -451,6 +490,7 @@ inline hipError_t launch_pair_f32_pf(const PairLaunchF32& src, int nz, float* su
         if (src.p[j].x == sum_y) return hipErrorInvalidValue;                                // never in place
     }
     a.B = src.B; a.L = src.L; a.C = src.C; a.slope = src.slope; a.nz = nz;
+    a.lengths = src.lengths; a.row_scale = src.row_scale;
     a.Gp = packed_groups(a.C);
     a.n_ct = packed_cotiles(a.C);
     a.sum_y = sum_y; a.sum_div = (float)nz;
@@ -475,8 +515,11 @@ inline hipError_t launch_pair_f32_pf(const PairLaunchF32& src, int nz, float* su
     dim3 grid((unsigned)pl.blocks, 1u, 1u), block(256);
 #define IRIS_PAIR_PF_F32_CASE(WT_, WC_, MT_, C_, MINB_)                                                                  \
     if (a.C == C_ && t.WT == WT_ && t.MT == MT_)                                                                         \
-        return ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel<sum>", mrf_pair_f32_pf_kernel<WT_, WC_, MT_, C_, MINB_, true>,  \
-                                           grid, block, lds_bytes, stream, a);
+        return a.lengths ? ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel_ragged<sum>",                            \
+                                                       mrf_pair_f32_pf_kernel<true, WT_, WC_, MT_, C_, MINB_, true>,     \
+                                                       grid, block, lds_bytes, stream, a)                                 \
+                         : ::iris::launch_kernel_named("mrf_pair_f32_pf_kernel<sum>", mrf_pair_f32_pf_kernel<false, WT_, WC_, MT_, C_, MINB_, true>,  \
+                                                       grid, block, lds_bytes, stream, a);
     IRIS_PAIR_PF_F32_CASE(4, 1, 1, 32, 4)
     IRIS_PAIR_PF_F32_CASE(2, 2, 2, 64, 2)
 #undef IRIS_PAIR_PF_F32_CASE

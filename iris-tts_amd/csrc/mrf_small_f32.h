@@ -59,6 +59,8 @@ __global__ void __launch_bounds__(256) mrf_small_f32_kernel(const ConvLaunch a) 
     const int b = blockIdx.y;
     const int ks = p.ks, dil = p.dil;
     const int i0 = rb * kSmallRows;
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, L);   // ragged forward: this item's rows (L otherwise)
+    if (i0 >= Lb) return;                                        // (block-uniform: nothing of this block is inside them)
     const int R = kSmallRows + (ks - 1) * dil;
     const int in_row0 = i0 - p.pad_left;
     const size_t item = (size_t)b * L * C;
@@ -87,7 +89,7 @@ __global__ void __launch_bounds__(256) mrf_small_f32_kernel(const ConvLaunch a) 
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int r = r_lane + i * RPI, row = in_row0 + r;
-            const bool ok = r < R && row >= 0 && row < L && ci < C;
+            const bool ok = r < R && row >= 0 && row < Lb && ci < C;
             st[i] = buf_load4(xr, ok ? (unsigned)(row * C + ci) * 4u : kOobOffset, 0);
         }
     };
@@ -151,7 +153,7 @@ __global__ void __launch_bounds__(256) mrf_small_f32_kernel(const ConvLaunch a) 
     // ---- epilogue: D[row 4 kq + r][col t]: this lane has channels co0 .. co0+3 of row i0 + 16 wave + t ----
     const int row = i0 + wave * 16 + t;
     const int co0 = ct16 * 16 + 4 * kq;
-    if (row < L) {
+    if (row < Lb) {
         const f32x4 bias4 = *reinterpret_cast<const f32x4*>(p.bias + co0);
         const size_t off = item + (size_t)row * C + co0;
         f32x4 res4 = {0.f, 0.f, 0.f, 0.f};

@@ -34,6 +34,23 @@ def _dtype_code(dtype: str) -> int:
         raise ValueError(f"dtype must be one of {sorted(DTYPES)}, got {dtype!r}") from None
 
 
+def _check_lengths(lengths, batch: int, frames: int) -> np.ndarray:
+    """Per-item frame counts of a ragged forward, validated on the host: int32 numpy array [batch], 0 <= l <= frames."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths must be integers, got {lengths.dtype}")
+        arr = lengths.detach().cpu().numpy()
+    else:
+        arr = np.asarray(lengths)
+        if arr.size and not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"lengths must be integers, got {arr.dtype}")
+    if arr.shape != (batch,):
+        raise ValueError(f"lengths must have shape [{batch}], got {list(arr.shape)}")
+    if batch and (arr.min() < 0 or arr.max() > frames):
+        raise ValueError(f"lengths must lie in [0, {frames}], got min {int(arr.min())} max {int(arr.max())}")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
 def require_gpu() -> torch.device:
     if not torch.cuda.is_available():
         raise RuntimeError(
@@ -127,11 +144,17 @@ class GeneratorEngine:
         self._graphs = {}
         self._workspace = None
 
-    def forward(self, mel: torch.Tensor, out: Optional[torch.Tensor] = None, dtype: Optional[str] = None) -> torch.Tensor:
+    def forward(self, mel: torch.Tensor, out: Optional[torch.Tensor] = None, dtype: Optional[str] = None,
+                lengths=None) -> torch.Tensor:
         """mel: fp32 device tensor [B, in_channels, T] -> waveform fp32 [B, hop*T] (asynchronous on
         the current stream).  ``dtype`` selects the storage/arithmetic of the layers in between: "f32" (the
         parity path, <= 1e-4 against the reference) or "bf16" (bf16 activations and weights, fp32
-        accumulation; BASELINE.json configs[2]); None = the engine's default_dtype."""
+        accumulation; BASELINE.json configs[2]); None = the engine's default_dtype.
+
+        ``lengths`` (a ragged batch; "f32" only): the mel frames of each item, a sequence or integer tensor [B] with
+        0 <= lengths[b] <= T.  Item b is then computed bit for bit as ``forward(mel[b:b+1, :, :lengths[b]])`` would compute
+        it -- frames past its length are never read -- and ``out[b, hop*lengths[b]:]`` is 0 (``iris_hifigan_forward_ragged``).
+        Always eager: a ragged forward never replays a captured graph."""
         dtype = dtype or self.default_dtype
         code = _dtype_code(dtype)
         if mel.dim() != 3 or mel.shape[1] != self.cfg.in_channels:
@@ -140,12 +163,15 @@ class GeneratorEngine:
             raise ValueError(f"mel is on {mel.device}, engine on {self.device}")
         mel = mel.to(torch.float32).contiguous()
         batch, _, frames = mel.shape
+        lengths_host = None if lengths is None else _check_lengths(lengths, batch, frames)
         if out is None:
             out = torch.empty((batch, frames * self.hop_length), dtype=torch.float32, device=self.device)
         elif out.shape != (batch, frames * self.hop_length) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous fp32 tensor [B, hop*T]")
         if batch == 0 or frames == 0:
             return out
+        if lengths_host is not None:
+            return self._forward_ragged(mel, lengths_host, out, dtype)
         if (batch * frames <= self.graph_max_frames and not self._profiling
                 and not torch.cuda.is_current_stream_capturing()):
             # short inputs: one graph launch instead of 24-30 kernel launches.  The graph owns static buffers; the result is
@@ -159,6 +185,19 @@ class GeneratorEngine:
         _native.check("iris_hifigan_forward", self.lib.iris_hifigan_forward(
             self._handle, ctypes.c_void_p(mel.data_ptr()), batch, frames, ctypes.c_void_p(out.data_ptr()),
             ctypes.c_void_p(ws.data_ptr()), ctypes.c_uint64(ws.numel()), code,
+            ctypes.c_void_p(stream)))
+        return out
+
+    def _forward_ragged(self, mel: torch.Tensor, lengths_host: np.ndarray, out: torch.Tensor, dtype: str) -> torch.Tensor:
+        batch, _, frames = mel.shape
+        nbytes = self.workspace_bytes(batch, frames, dtype)
+        ws = self._get_workspace(nbytes)
+        # (a stream-ordered allocation: the caching allocator hands the block out again only behind this stream's kernels)
+        lengths_dev = torch.from_numpy(lengths_host).to(self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check("iris_hifigan_forward_ragged", self.lib.iris_hifigan_forward_ragged(
+            self._handle, ctypes.c_void_p(mel.data_ptr()), batch, frames, ctypes.c_void_p(lengths_dev.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ctypes.c_uint64(ws.numel()), _dtype_code(dtype),
             ctypes.c_void_p(stream)))
         return out
 

@@ -21,6 +21,8 @@ DTYPE_F32 = 0
 DTYPE_BF16 = 1
 DTYPE_F32_SPLIT = 2
 
+STATUS_INVALID_ARGUMENT = 1
+STATUS_UNSUPPORTED = 4
 STATUS_WORKSPACE_TOO_SMALL = 5
 STATUS_NOT_PREPARED = 6
 
@@ -128,6 +130,7 @@ SYMBOLS = {
     "iris_hifigan_describe_plan": (_i32, [_c.POINTER(Config), _i32, _i32, _i32, _i32, _c.POINTER(Plan)]),
     "iris_hifigan_workspace_bytes": (_i32, [_vp, _i32, _i32, _i32, _c.POINTER(_u64)]),
     "iris_hifigan_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _u64, _i32, _vp]),
+    "iris_hifigan_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _i32, _vp]),
     "iris_hifigan_workspace_layout": (_i32, [_vp, _i32, _i32, _i32, _c.POINTER(WorkspaceMap)]),
     "iris_hifigan_forward_until": (_i32, [_vp, _vp, _i32, _i32, _vp, _u64, _i32, _i32, _i32, _c.POINTER(_i32), _vp]),
     "iris_hifigan_hop_length": (_i32, [_vp, _c.POINTER(_i32)]),

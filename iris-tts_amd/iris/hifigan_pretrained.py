@@ -32,11 +32,12 @@ import torch
 import torch.nn as nn
 
 from ._engine import LAST_LOAD_TIMINGS, GeneratorEngine, require_gpu
+from .batching import pack_mels, split_waveforms
 from ._weights import GeneratorConfig, layer_specs, extract_state_dict
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["ResBlock", "HiFiGANModel", "HiFiGANGenerator", "get_pretrained_hifigan", "infer_hifigan"]
+__all__ = ["ResBlock", "HiFiGANModel", "HiFiGANGenerator", "get_pretrained_hifigan", "infer_hifigan", "infer_hifigan_batch"]
 
 
 class _WeightNormedConv(nn.Module):
@@ -290,6 +291,17 @@ class HiFiGANGenerator:
             audio = audio[0]
         return audio
 
+    def infer_batch(self, mels: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """List of mels [n_mels, T_i] of any lengths -> list of waveforms [hop * T_i], in ONE ragged fp32 forward
+        (iris.batching).  Each waveform is bit for bit what ``self(mel)`` returns for that mel alone."""
+        mels = [np.asarray(m) for m in mels]
+        if not mels:
+            return []
+        padded, lengths = pack_mels([torch.from_numpy(np.ascontiguousarray(m)).float() for m in mels])
+        eng = self.model.engine()
+        wav = eng.forward(padded.to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
+        return [w.copy() for w in split_waveforms(wav, lengths, eng.hop_length)]
+
 
 _vocoder_instance: Optional[HiFiGANGenerator] = None
 _vocoder_checkpoint_path: Optional[Path] = None
@@ -323,3 +335,9 @@ def infer_hifigan(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length
     if audio.ndim == 2 and audio.shape[0] == 1:
         audio = audio[0]
     return audio
+
+
+def infer_hifigan_batch(mels: Sequence[np.ndarray], checkpoint_path: Optional[Union[str, Path]] = None) -> List[np.ndarray]:
+    """Batched ``infer_hifigan``: list of mels [n_mels, T_i] -> list of 1-D waveforms, one ragged forward for all of
+    them (``HiFiGANGenerator.infer_batch``); each equals ``infer_hifigan(mel)`` bit for bit."""
+    return get_pretrained_hifigan(checkpoint_path).infer_batch(mels)

@@ -24,12 +24,13 @@ from __future__ import annotations
 
 import logging
 from pathlib import Path
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ._engine import GeneratorEngine, require_gpu
+from .batching import pack_mels, split_waveforms
 from ._weights import (GeneratorConfig, LayerSpec, keras_to_reference_layout, layer_specs)
 
 logger = logging.getLogger(__name__)
@@ -231,6 +232,17 @@ class HiFiGANVocoder:
         if squeeze_batch:
             audio = audio[0]
         return audio
+
+    def infer_batch(self, mels: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """List of mels [mel_channels, time_i] of any lengths -> list of waveforms [time_i * hop], in ONE ragged fp32
+        forward (iris.batching); each is bit for bit what ``infer(mel)`` returns for that mel alone."""
+        mels = [np.asarray(m, dtype=np.float32) for m in mels]
+        if not mels:
+            return []
+        padded, lengths = pack_mels(mels)
+        eng = self.model.engine()
+        wav = eng.forward(torch.from_numpy(padded).to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
+        return [w.copy() for w in split_waveforms(wav, lengths, eng.hop_length)]
 
     def __call__(self, mel: np.ndarray) -> np.ndarray:
         return self.infer(mel)
