@@ -28,7 +28,8 @@ against them.  The Keras/JAX twin cannot be executed anywhere in this pipeline: 
 is the same function under the documented parameter map -- "parity unpinned" for that twin.
 ``generator_forward_bf16`` restates the bf16-storage variant (BASELINE.json configs[2]); the reference
 has no bf16 path, so that function is "parity unpinned" too: it defines the variant's rounding points and
-tests report its distance to the pinned fp32 functions.
+tests report its distance to the pinned fp32 functions.  The same holds for ``split_bf16`` / ``conv1d_split`` /
+``generator_forward_f32s``: the definition of the split-product mode (dtype "f32s"), which the reference does not have.
 """
 from __future__ import annotations
 
@@ -284,6 +285,128 @@ def generator_forward_bf16(folded_t: Mapping[str, object], mel, cfg: Optional[Or
                     r = r16(F.conv1d(r16(F.leaky_relu(xt, slope)), w2, b2, padding=int((kk - 1) / 2)) + r)
                 xs = r if xs is None else xs + r
             x = xs * inv_n                      # fp32, unrounded: rounded where the next conv stages it
+            if taps is not None:
+                taps[f"mrf.{i}"] = x
+        x = F.leaky_relu(x, slope)
+        kp = folded_t["conv_post.weight"].shape[-1]
+        x = F.conv1d(x, folded_t["conv_post.weight"], folded_t["conv_post.bias"], padding=(kp - 1) // 2)
+        return torch.tanh(x)
+
+
+# ------------------------------------------------------------------------------------------------
+# split-product mode (dtype "f32s", csrc/conv_mfma_f32s.h): the definition of its arithmetic
+# ------------------------------------------------------------------------------------------------
+def split_bf16(v):
+    """fp32 tensor -> (hi, mid) fp32 tensors with bf16 values: hi = bf16_rne(v), mid = bf16_rne(v - hi), the
+    subtraction in fp32 (it is exact: v and hi agree in sign, exponent and the leading 8 significand bits).  This is
+    what the kernel does to an activated input while it stages it (v_cvt_pk_bf16_f32, round to nearest even) and what
+    the host packer does to the weights.  v = hi + mid + O(2^-17 |v|)."""
+    import torch
+
+    v = torch.as_tensor(v).float()
+    hi = v.to(torch.bfloat16).to(torch.float32)
+    mid = (v - hi).to(torch.bfloat16).to(torch.float32)
+    return hi, mid
+
+
+def _acc_dtype(acc):
+    import torch
+
+    return {np.float64: torch.float64, np.float32: torch.float32, float: torch.float64,
+            "float64": torch.float64, "float32": torch.float32}.get(acc, acc)
+
+
+def conv1d_split(x_act, w, b, dilation: int = 1, acc=np.float64, x_planes=None, w_planes=None):
+    """One ResBlock conv of the split-product mode on an ALREADY ACTIVATED fp32 input (LeakyReLU is applied in fp32
+    before the split, as the kernel does):
+
+        y = (conv(x_hi, w_mid) + conv(x_mid, w_hi)) + conv(x_hi, w_hi) + b          -- smallest terms first
+
+    with (x_hi, x_mid) = split_bf16(x_act), (w_hi, w_mid) = split_bf16(w); the mid*mid term is dropped.  Every factor is
+    a bf16 value, so with ``acc=float64`` the three sums are exact to fp64 rounding and this IS the layer; with
+    ``acc=float32`` it is a CPU stand-in for the kernel's fp32 accumulation (another summation order than the MFMA's).
+    x_act [N, C_in, L], w [C_out, C_in, k] (odd k), 'same' zero padding -> fp32 [N, C_out, L].
+    ``x_planes`` / ``w_planes``: (hi, mid) to use instead of the split of x_act / w (tests build wrong schemes with them)."""
+    import torch
+    import torch.nn.functional as F
+
+    dt = _acc_dtype(acc)
+    with torch.no_grad():
+        xh, xm = x_planes if x_planes is not None else split_bf16(x_act)
+        wh, wm = w_planes if w_planes is not None else split_bf16(w)
+        k = wh.shape[-1]
+        pad = int((k * dilation - dilation) / 2)
+        xh, xm, wh, wm = (torch.as_tensor(t).to(dt) for t in (xh, xm, wh, wm))
+
+        def conv(xx, ww):
+            return F.conv1d(xx, ww, None, dilation=dilation, padding=pad)
+
+        y = (conv(xh, wm) + conv(xm, wh)) + conv(xh, wh)
+        y = y + torch.as_tensor(b).to(dt)[None, :, None]
+        return y.float()
+
+
+def conv_transpose1d_split(x_act, w, b, stride: int, padding: int, acc=np.float64):
+    """ConvTranspose1d with split products (``iris_hifigan_op_conv_transpose1d_f32s``; the forward itself keeps its
+    upsamplers in plain fp32): the same three terms in the same order as ``conv1d_split``.  w [C_in, C_out, k]."""
+    import torch
+    import torch.nn.functional as F
+
+    dt = _acc_dtype(acc)
+    with torch.no_grad():
+        xh, xm = (t.to(dt) for t in split_bf16(x_act))
+        wh, wm = (t.to(dt) for t in split_bf16(w))
+
+        def convt(xx, ww):
+            return F.conv_transpose1d(xx, ww, None, stride=stride, padding=padding)
+
+        y = (convt(xh, wm) + convt(xm, wh)) + convt(xh, wh)
+        y = y + torch.as_tensor(b).to(dt)[None, :, None]
+        return y.float()
+
+
+def generator_forward_f32s(folded_t: Mapping[str, object], mel, cfg: Optional[OracleConfig] = None,
+                           taps: Optional[dict] = None, slope: float = LRELU_SLOPE, acc=np.float32):
+    """The generator in split-product mode restated on the CPU: ``generator_forward_torch`` with the ResBlock convs --
+    and only those: conv_pre, the upsamplers and conv_post stay plain fp32, as in the device forward -- replaced by
+    ``conv1d_split``.  Activations are fp32, the residual is added in fp32 and the MRF mean is ((y0 + y1) + y2) / n in
+    fp32 with a true division.  ``acc``: accumulation type of the split convs (float32: what the device does up to
+    summation order; float64: the exact scheme).  The reference has no such mode: this function defines it, and tests
+    report its distance to ``generator_forward_torch``.  mel [B, in_channels, T] -> [B, 1, hop*T] fp32 tensor."""
+    import torch
+    import torch.nn.functional as F
+
+    cfg = cfg or OracleConfig()
+    with torch.no_grad():
+        x = torch.as_tensor(mel).float()
+        k = folded_t["conv_pre.weight"].shape[-1]
+        x = F.conv1d(x, folded_t["conv_pre.weight"], folded_t["conv_pre.bias"], padding=(k - 1) // 2)
+        if taps is not None:
+            taps["conv_pre"] = x
+        planes = {}
+
+        def wsplit(name):
+            if name not in planes:
+                planes[name] = split_bf16(folded_t[name + ".weight"])
+            return planes[name]
+
+        for i, (u, ku) in enumerate(zip(cfg.upsample_rates, cfg.upsample_kernel_sizes)):
+            x = F.leaky_relu(x, slope)
+            x = F.conv_transpose1d(x, folded_t[f"ups.{i}.weight"], folded_t[f"ups.{i}.bias"], stride=u,
+                                   padding=(ku - u) // 2)
+            if taps is not None:
+                taps[f"ups.{i}"] = x
+            xs = None
+            for j in range(cfg.num_kernels):
+                p = f"resblocks.{i * cfg.num_kernels + j}"
+                r = x
+                for m, d in enumerate(cfg.resblock_dilation_sizes[j]):
+                    n1, n2 = f"{p}.convs1.{m}", f"{p}.convs2.{m}"
+                    xt = conv1d_split(F.leaky_relu(r, slope), None, folded_t[n1 + ".bias"], d, acc, w_planes=wsplit(n1))
+                    xt = conv1d_split(F.leaky_relu(xt, slope), None, folded_t[n2 + ".bias"], 1, acc, w_planes=wsplit(n2))
+                    r = xt + r
+                xs = r if xs is None else xs + r
+            x = xs / cfg.num_kernels
             if taps is not None:
                 taps[f"mrf.{i}"] = x
         x = F.leaky_relu(x, slope)

@@ -30,7 +30,7 @@ def test_pipeline_control_flow_cpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype,exact", [("f32", True), ("bf16", True)])
+@pytest.mark.parametrize("dtype,exact", [("f32", True), ("bf16", True), ("f32s", True)])
 def test_pipeline_on_gpu_equals_separate_stages(dtype, exact):
     """configs[4] shape: one utterance, 256-frame chunks.  The chained pipeline (mel stays in HBM) equals
     PostNet -> host -> one-shot vocoder bit for bit."""
