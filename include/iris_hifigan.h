@@ -334,6 +334,21 @@ int32_t iris_postnet_workspace_bytes(const iris_postnet_handle* h, int32_t B, in
 int32_t iris_postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T,
                              void* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* Ragged batch: mels of different lengths refined in one call (the PostNet half of iris_hifigan_forward_ragged).
+ * mel_dev, out_dev [B, n_mels, T] fp32 channels-first, lengths_dev [B] int32 on the device (caller-owned, like mel_dev);
+ * lengths are clamped to [0, T] on the device.
+ * Item b is computed exactly as iris_postnet_forward of mel[b, :, :lengths[b]] alone would compute it, bit for bit: every
+ * layer's 'same' padding ends at the item's own length. Mel frames >= lengths[b] are never read, so they may hold
+ * anything, NaN included. out[b, :, lengths[b]:T] is written as 0.0f.
+ * The host never reads the lengths: the launch plan is the one of iris_postnet_forward(B, T), and tiles past an item's
+ * length return at once on the device. Workspace as iris_postnet_workspace_bytes(B, T).
+ * Asynchronous on `stream`, allocates nothing, safe inside a stream capture.
+ * lengths_dev == NULL (B, T > 0) returns IRIS_HIFIGAN_INVALID_ARGUMENT; B > 65535 returns IRIS_HIFIGAN_UNSUPPORTED, as
+ * iris_postnet_forward does. */
+int32_t iris_postnet_forward_ragged(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                    const int32_t* lengths_dev, void* out_dev,
+                                    void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1135,12 +1135,19 @@ int32_t iris_postnet_workspace_bytes(const iris_postnet_handle* h, int32_t B, in
     return IRIS_HIFIGAN_OK;
 }
 
-int32_t iris_postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T,
-                             void* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
-    IRIS_ABI_BEGIN
+}  // extern "C"
+
+namespace {
+
+// The PostNet forward.  `lengths` (iris_postnet_forward_ragged; nullptr otherwise): frames of each batch item on the device.
+// `ragged` says which entry point is calling: the plan is that of (B, T) either way, every conv bounds the item's reads and
+// stores by its length (row_scale 1: 'same' convolutions keep one row per frame), and the residual kernel zeroes the rest.
+int postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T, bool ragged, const int32_t* lengths,
+                    void* out_dev, void* workspace_dev, uint64_t workspace_bytes, hipStream_t stream) {
     if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
     if (B < 0 || T < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    if (ragged && !lengths) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
     if (!mel_dev || !out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
     if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
     uint64_t need = 0;
@@ -1150,7 +1157,6 @@ int32_t iris_postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_
                     (unsigned long long)workspace_bytes, (unsigned long long)need);
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    hipStream_t stream = (hipStream_t)stream_;
     const size_t frames = (size_t)B * T;
     const size_t hid = (frames * h->channels + 63) & ~(size_t)63;
     float* ws = (float*)workspace_dev;
@@ -1167,13 +1173,32 @@ int32_t iris_postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_
         a.B = B; a.L_in = T; a.L_out = T; a.C_in = l.C_in; a.C_out = l.C_out; a.n_idx = T;
         a.in_act = IN_ACT_NONE; a.x_channels_first = i == 0 ? 1 : 0;   // the mel arrives [B, n_mels, T]
         a.out_act = last ? 0 : 1;                                       // tanh (postnet.py:59)
+        a.lengths = lengths; a.row_scale = 1;
         HIP_TRY(launch_conv(a, 1, stream));
         x = a.p[0].y;
     }
     dim3 grid((unsigned)((T + 255) / 256), (unsigned)B), block(256);
     HIP_TRY(launch_kernel(postnet_residual_kernel, grid, block, 0, stream, (const float*)mel_dev, (const float*)res,
-                          (float*)out_dev, h->n_mels, T));              // x + res (postnet.py:67)
+                          (float*)out_dev, h->n_mels, T, lengths));     // x + res (postnet.py:67)
     return IRIS_HIFIGAN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t iris_postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                             void* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
+    IRIS_ABI_BEGIN
+    return postnet_forward(h, mel_dev, B, T, false, nullptr, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
+    IRIS_ABI_END
+}
+
+int32_t iris_postnet_forward_ragged(iris_postnet_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                    const int32_t* lengths_dev, void* out_dev, void* workspace_dev,
+                                    uint64_t workspace_bytes, void* stream_) {
+    IRIS_ABI_BEGIN
+    return postnet_forward(h, mel_dev, B, T, true, lengths_dev, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
     IRIS_ABI_END
 }
 

@@ -155,6 +155,7 @@ SYMBOLS = {
     "iris_postnet_destroy": (_i32, [_vp]),
     "iris_postnet_workspace_bytes": (_i32, [_vp, _i32, _i32, _c.POINTER(_u64)]),
     "iris_postnet_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _u64, _vp]),
+    "iris_postnet_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

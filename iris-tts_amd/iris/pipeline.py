@@ -5,15 +5,20 @@ and returns a numpy mel, ``:171-216`` converts it again and calls the vocoder). 
 HBM: ``PostNet.forward_device`` writes a device tensor that the vocoder engine reads chunk by chunk
 (``iris.streaming``: 256-frame chunks + 13-frame halo, seams identical to the one-shot forward), so the first
 audio is available after one chunk instead of after the whole utterance.
+
+Three ways in: ``infer`` / ``stream`` take one complete mel; ``infer_batch`` takes a list of mels of different lengths and
+runs ONE ragged PostNet pass and ONE ragged vocoder forward over all of them; ``session()`` takes the mel of one utterance
+piece by piece from a producer that is still running, and refines and vocodes each chunk as soon as its context exists.
 """
 from __future__ import annotations
 
-from typing import Callable, Iterator, Optional
+from typing import Callable, Iterator, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .streaming import StreamingVocoder
+from .batching import pack_mels, split_waveforms
+from .streaming import StreamingSession, StreamingVocoder
 
 
 class MelToWavePipeline:
@@ -30,22 +35,29 @@ class MelToWavePipeline:
         self.device = device
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
+        self.config = config
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
                                          halo_frames=halo_frames, group_chunks=group_chunks, config=config)
 
-    def refine(self, mel) -> torch.Tensor:
-        """Host or device mel ``[B, n_mels, T]`` -> refined device mel (one PostNet pass over the whole utterance:
-        0.3 % of the vocoder's work)."""
+    def _to_device(self, mel) -> torch.Tensor:
         if not isinstance(mel, torch.Tensor):
             mel = torch.from_numpy(np.ascontiguousarray(np.asarray(mel, dtype=np.float32)))
         if mel.dim() != 3:
             raise ValueError(f"expected mel [B, n_mels, T], got shape {tuple(mel.shape)}")
         if self.device is not None:
             mel = mel.to(self.device)
+        return mel
+
+    def _refine_fn(self) -> Optional[Callable]:
+        return None if self.postnet is None else getattr(self.postnet, "forward_device", self.postnet)
+
+    def refine(self, mel) -> torch.Tensor:
+        """Host or device mel ``[B, n_mels, T]`` -> refined device mel (one PostNet pass over the whole utterance:
+        0.3 % of the vocoder's work)."""
+        mel = self._to_device(mel)
         if self.postnet is None:
             return mel
-        fwd = getattr(self.postnet, "forward_device", self.postnet)
-        return fwd(mel)
+        return self._refine_fn()(mel)
 
     def stream(self, mel) -> Iterator[torch.Tensor]:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``."""
@@ -55,3 +67,138 @@ class MelToWavePipeline:
         return self.streamer.infer(self.refine(mel))
 
     __call__ = infer
+
+    def infer_batch(self, mels: Sequence) -> List[torch.Tensor]:
+        """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform
+        ``[hop * T_i]`` per utterance, with ONE PostNet pass and ONE vocoder forward for the whole list: the mels are padded
+        to the longest (``pack_mels``) and both stages bound every layer of item i by ``T_i`` (``forward_device(...,
+        lengths=)``, ``vocode(..., lengths=)``), so item i is bit for bit ``infer(mels[i][None])[0]`` -- padding alone would
+        let the padded frames reach the last frames of every short item (``iris.batching``).  The stages must take
+        ``lengths``; a vocoder dtype without a ragged forward (bf16, f32s) fails as ``engine.forward(lengths=...)`` does."""
+        mels = list(mels)
+        if not mels:
+            return []
+        padded, lengths = pack_mels(mels)
+        padded = self._to_device(padded)
+        if self.postnet is not None:
+            padded = self._refine_fn()(padded, lengths=lengths)
+        wav = self.streamer.forward(padded, lengths=lengths)
+        return split_waveforms(wav, lengths, self.streamer.hop_length)
+
+    def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
+        """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
+        PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own."""
+        return PipelineSession(self, postnet_halo_frames)
+
+
+class PipelineSession:
+    """Pushed input for ``MelToWavePipeline``: the raw mel of ONE utterance arrives piece by piece (``push``), refined and
+    vocoded audio leaves chunk by chunk, ``flush`` ends the utterance.  The concatenation of everything returned equals
+    ``pipeline.infer`` of the concatenated mel.
+
+    The PostNet is a finite stack of 'same' convolutions (src/iris/postnet.py:48-67): refined frame t depends on the raw mel
+    within +-hp frames only (``PostNet.receptive_field_frames``, 6 for the 3 x k5 net), so it is final once raw frames up to
+    t + hp have arrived, or the utterance has ended.  Final refined frames go into an ordinary ``StreamingSession``, which
+    cuts the chunks and keeps the generator's own halo hv (13 for V1).  A refinement window starts hp raw frames before the
+    first frame not yet refined (clamped at 0: frame 0 is the true start, its zero padding is the one-shot's own) and ends
+    at the last raw frame received; the frames within hp of a window edge that is not an edge of the utterance have seen
+    zero padding where the utterance has frames, and are dropped.
+
+    Latency: chunk ``[s, s + chunk)`` is returned by the push that brings ``frames_received`` to ``s + chunk + hv + hp``.
+    Work: the PostNet runs only in a push that returns at least one chunk, and once in ``flush`` -- a producer that pushes
+    single frames does not cause a pass per frame.  Memory: at most ``chunk + 2 * (hv + hp)`` frames are buffered (raw ones
+    not yet refined with their left-hand context, refined ones not yet emitted with theirs) plus the piece just pushed."""
+
+    def __init__(self, pipeline: MelToWavePipeline, postnet_halo_frames: Optional[int] = None):
+        sv = pipeline.streamer
+        if sv.chunk_frames < 1:
+            raise ValueError(f"chunk_frames >= 1 is required, got {sv.chunk_frames}")
+        postnet = pipeline.postnet
+        if postnet_halo_frames is not None and postnet_halo_frames < 0:
+            raise ValueError(f"postnet_halo_frames >= 0 is required, got {postnet_halo_frames}")
+        if postnet is None:
+            hp = 0
+        elif hasattr(postnet, "receptive_field_frames"):
+            hp = int(postnet.receptive_field_frames)
+            if postnet_halo_frames is not None:
+                if postnet_halo_frames < hp:
+                    raise ValueError(f"postnet_halo_frames={postnet_halo_frames} is smaller than the PostNet's receptive "
+                                     f"field ({hp} frames): window seams would differ from the one-shot output")
+                hp = int(postnet_halo_frames)
+        elif postnet_halo_frames is not None:
+            hp = int(postnet_halo_frames)
+        else:
+            raise ValueError("the PostNet has no receptive_field_frames: pass postnet_halo_frames (the frames on either "
+                             "side that reach one refined frame); a guess would make the window seams silently wrong")
+        self._pipeline = pipeline
+        self._refine = pipeline._refine_fn()
+        self.postnet_halo_frames = hp
+        self._inner = StreamingSession(sv.forward, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames,
+                                       halo_frames=sv.halo_frames, config=pipeline.config)
+        self.hop_length, self.chunk_frames, self.halo_frames = sv.hop_length, sv.chunk_frames, sv.halo_frames
+        self._raw: list = []          # raw pieces [B, n_mels, t]; together they cover raw frames [self._base, self._total)
+        self._base = 0
+        self._total = 0               # raw frames received so far
+        self._refined = 0             # first raw frame not yet refined (== frames pushed into the inner session)
+        self._lead = None             # (B, n_mels) of the utterance
+        self._closed = False
+
+    @property
+    def frames_received(self) -> int:
+        return self._total
+
+    @property
+    def frames_emitted(self) -> int:
+        return self._inner.frames_emitted
+
+    @property
+    def frames_buffered(self) -> int:
+        """Frames held between calls: raw ones (with the left-hand PostNet context) + refined ones in the vocoder session."""
+        return (self._total - self._base) + (self._inner._total - self._inner._base)
+
+    def _advance(self, final: bool) -> List:
+        """Refines every frame that is final now and hands it to the vocoder session."""
+        hp = self.postnet_halo_frames
+        stop = self._total if final else self._total - hp        # refined frames [self._refined, stop) are final
+        if stop <= self._refined:
+            return []
+        buf = self._raw[0] if len(self._raw) == 1 else torch.cat(self._raw, dim=2)
+        win_start = max(0, self._refined - hp)
+        window = buf[:, :, win_start - self._base:]
+        if self._refine is not None:
+            window = self._refine(window)
+        piece = window[:, :, self._refined - win_start:stop - win_start]
+        self._refined = stop
+        keep_from = max(0, stop - hp)                             # the next window's left-hand context
+        self._raw = [buf[:, :, keep_from - self._base:]]
+        self._base = keep_from
+        return self._inner.push(piece)
+
+    def push(self, mel_piece) -> List[torch.Tensor]:
+        """Appends the raw ``mel_piece [B, n_mels, t]`` (t >= 0, host or device) and returns the waveform chunks
+        ``[B, hop * chunk]`` that became computable, in order (possibly none)."""
+        if self._closed:
+            raise RuntimeError("the session was flushed: start a new one for the next utterance")
+        mel_piece = self._pipeline._to_device(mel_piece)
+        if self._lead is not None and tuple(mel_piece.shape[:2]) != self._lead:
+            raise ValueError("every piece of an utterance must have the same batch size and mel bins")
+        if mel_piece.shape[2] > 0:
+            self._lead = tuple(mel_piece.shape[:2])
+            self._raw.append(mel_piece)
+            self._total += int(mel_piece.shape[2])
+        # the PostNet runs only when its output completes a chunk: the vocoder session emits [s, s + chunk) once it holds
+        # refined frames up to s + chunk + hv, and those are final hp raw frames later
+        if self._total - self.postnet_halo_frames < self._inner.frames_emitted + self.chunk_frames + self.halo_frames:
+            return []
+        return self._advance(final=False)
+
+    def flush(self) -> List[torch.Tensor]:
+        """Ends the utterance: refines the frames that were waiting for context -- the right edge of this last window is the
+        true end of the mel, as in the one-shot pass -- and returns the remaining chunks (the last may be shorter)."""
+        if self._closed:
+            return []
+        out = self._advance(final=True)
+        out += self._inner.flush()
+        self._closed = True
+        self._raw = []
+        return out

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._engine import require_gpu
+from ._engine import _check_lengths, require_gpu
 
 BN_EPSILON = 1e-3  # keras.layers.BatchNormalization default
 
@@ -128,13 +128,25 @@ class PostNet:
             self._handle = h
         return _native.load()
 
-    def forward_device(self, mel: torch.Tensor) -> torch.Tensor:
-        """[B, n_mels, T] fp32 device tensor -> refined mel, same shape (asynchronous on the current stream)."""
+    @property
+    def receptive_field_frames(self) -> int:
+        """Mel frames on either side that can reach one refined frame: every layer is a 'same' convolution that widens the
+        dependence by (kernel_size - 1) / 2 (6 for the 3 x k5 net of scripts/synthesize.py:152-158)."""
+        return self.num_layers * (self.kernel_size - 1) // 2
+
+    def forward_device(self, mel: torch.Tensor, lengths=None) -> torch.Tensor:
+        """[B, n_mels, T] fp32 device tensor -> refined mel, same shape (asynchronous on the current stream).
+
+        ``lengths`` (a ragged batch): the frames of each item, a sequence or integer tensor [B] with
+        0 <= lengths[b] <= T.  Item b is then refined bit for bit as ``forward_device(mel[b:b+1, :, :lengths[b]])`` would
+        refine it -- frames past its length are never read -- and ``out[b, :, lengths[b]:]`` is 0
+        (``iris_postnet_forward_ragged``)."""
         lib = self._ensure()
         if mel.dim() != 3 or mel.shape[1] != self.n_mels:
             raise ValueError(f"expected mel [B, {self.n_mels}, T], got {tuple(mel.shape)}")
         mel = mel.to(device=self._device, dtype=torch.float32).contiguous()
         B, _, T = mel.shape
+        lengths_host = None if lengths is None else _check_lengths(lengths, B, T)
         out = torch.empty_like(mel)
         if B == 0 or T == 0:
             return out
@@ -142,10 +154,18 @@ class PostNet:
         _native.check("iris_postnet_workspace_bytes", lib.iris_postnet_workspace_bytes(self._handle, B, T, ctypes.byref(n)))
         if self._workspace is None or self._workspace.numel() < n.value:
             self._workspace = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=self._device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        if lengths_host is not None:
+            # (a stream-ordered allocation: the caching allocator hands the block out again only behind this stream's kernels)
+            lengths_dev = torch.from_numpy(lengths_host).to(self._device)
+            _native.check("iris_postnet_forward_ragged", lib.iris_postnet_forward_ragged(
+                self._handle, ctypes.c_void_p(mel.data_ptr()), B, T, ctypes.c_void_p(lengths_dev.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._workspace.data_ptr()),
+                ctypes.c_uint64(self._workspace.numel()), stream))
+            return out
         _native.check("iris_postnet_forward", lib.iris_postnet_forward(
             self._handle, ctypes.c_void_p(mel.data_ptr()), B, T, ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()),
-            ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)))
+            ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream))
         return out
 
     def __call__(self, mels_bt_f, training: bool = False) -> np.ndarray:
