@@ -9,6 +9,11 @@ What is checked instead:
     (``generator_forward_bf16``): bf16 storage noise, bounded by TOL_BF16_MAX / TOL_BF16_MEAN below
     (observed: max 2.2e-2, mean 1.8e-3 on waveforms of rms 0.74);
   * size-independent properties at the full configs[2] size: determinism, batch independence (bit-exact).
+The single-layer tests go through the ``iris_hifigan_op_*_bf16`` entry points (one problem, one input tensor, LeakyReLU or
+nothing).  The forms only ``bf16_forward`` launches -- the fp32 mel staged by conv_pre, ConvTranspose1d on the mean of two
+or three branch tensors or on the summing pair's output, the grouped launch of all branches, the conv_post kernels -- are
+held to the same one-ulp bar launch by launch, on the GPU's own input tensors, by tests/test_gpu_bf16_steps.py; the
+whole-waveform bars below only bound the variant's storage noise.
 """
 import ctypes
 
