@@ -121,7 +121,10 @@ def test_conv_transpose1d_matches_oracle(lib, B, L, Ci, Co, k, u):
     assert np.abs(got - want).max() <= TOL_LAYER * max(1.0, np.abs(want).max())
 
 
-@pytest.mark.parametrize("B,L,C,k,three", [(1, 700, 32, 7, True), (2, 300, 32, 7, False), (1, 100, 6, 7, True), (1, 3, 32, 7, True)])
+CONV_POST_CASES = [(1, 700, 32, 7, True), (2, 300, 32, 7, False), (1, 100, 6, 7, True), (1, 3, 32, 7, True)]      # (B, L, C, k, three)
+
+
+@pytest.mark.parametrize("B,L,C,k,three", CONV_POST_CASES)
 def test_conv_post_matches_oracle(lib, B, L, C, k, three):
     rng = np.random.default_rng(L + C)
     xs = [rng.standard_normal((B, C, L)).astype(np.float32) * 2 for _ in range(3 if three else 1)]
@@ -215,8 +218,11 @@ def test_mrf_job_mode_agrees_bitwise_when_blocks_draw_many_jobs(lib, B, L, C, di
             assert np.array_equal(want[j], got[j]), (j, plan)
 
 
+MRF_SUM_CASES = [(1, 700, 32), (1, 300, 64), (2, 130, 128), (1, 90, 256)]      # (B, L, C)
+
+
 @pytest.mark.parametrize("plan", [0, 1, 2])
-@pytest.mark.parametrize("B,L,C", [(1, 700, 32), (1, 300, 64), (2, 130, 128), (1, 90, 256)])
+@pytest.mark.parametrize("B,L,C", MRF_SUM_CASES)
 def test_mrf_summing_step_matches_oracle(lib, B, L, C, plan):
     """The last step of a stage stores only ((y0 + y1) + y2) / 3 (hifigan_pretrained.py:131-137, the reference's
     order and a true division)."""
@@ -236,10 +242,14 @@ def test_mrf_summing_step_matches_oracle(lib, B, L, C, plan):
     assert np.array_equal(got, ((sep[0] + sep[1]) + sep[2]) / np.float32(3))
 
 
+MRF_PAIR_CASES = [(1, 700, 32, (1, 1, 1)), (2, 333, 32, (5, 5, 5)), (1, 520, 64, (3, 3, 3)), (3, 190, 64, (5, 5, 5)),      # (B, L, C, dils)
+                  (1, 5, 32, (3, 3, 3)), (2, 11000, 64, (3, 3, 3)),    # (128-row tiles at C = 64)
+                  (5, 30000, 32, (3, 3, 3))]   # 3,810 jobs: persistent blocks walk several jobs each
+MRF_PAIR_SMALL = 400_000     # B L C up to which the pair is also held to the CPU oracles (they are slow)
+
+
 @pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("B,L,C,dils", [(1, 700, 32, (1, 1, 1)), (2, 333, 32, (5, 5, 5)), (1, 520, 64, (3, 3, 3)), (3, 190, 64, (5, 5, 5)),
-                                        (1, 5, 32, (3, 3, 3)), (2, 11000, 64, (3, 3, 3)),    # (128-row tiles at C = 64)
-                                        (5, 30000, 32, (3, 3, 3))])   # 3,810 jobs: persistent blocks walk several jobs each
+@pytest.mark.parametrize("B,L,C,dils", MRF_PAIR_CASES)
 def test_mrf_fused_pair_matches_oracle_and_separate_steps(lib, B, L, C, dils, mode):
     """The fused fp32 conv pair (csrc/mrf_pair_f32.h, mode 0; its persistent, prefetching form csrc/mrf_pair_f32_pf.h, modes 1 / 2 = jobs drawn from a
     counter / fixed stride:
@@ -267,7 +277,7 @@ def test_mrf_fused_pair_matches_oracle_and_separate_steps(lib, B, L, C, dils, mo
 
     _, xt = _mrf_step(lib, xs, w1, b1, None, B, L, C, dils, 0, mean=False)
     _, sep = _mrf_step(lib, xt, w2, b2, xs, B, L, C, (1, 1, 1), 0, mean=False)
-    small = B * L * C <= 400_000                         # (the numpy oracle is slow: large cases are checked bit for bit only)
+    small = B * L * C <= MRF_PAIR_SMALL                  # (the numpy oracle is slow: large cases are checked bit for bit only)
     rc = pair(yd, None, mode)
     if mode >= 1:
         # IRIS_HIFIGAN_UNSUPPORTED: the library carries the persistent kernel in its summing form only (the plain persistent
