@@ -28,7 +28,8 @@ struct DeviceGuard {
     int prev = -1;
     bool switched = false;
     hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
+    explicit DeviceGuard(int dev, bool active = true) {      // (!active: a host-only handle has no device to select)
+        if (!active) return;
         err = hipGetDevice(&prev);
         if (err == hipSuccess && prev != dev) {
             err = hipSetDevice(dev);
@@ -199,10 +200,55 @@ struct Prof {
     }
 };
 
+// ---- workspace layout of one pass of B x T mel frames, in elements of the dtype's storage ----
+struct WsLayout {
+    size_t pre;   // conv_pre output                [B, T, C0]
+    size_t up;    // upsample output of a stage     [B, L, C]     (max over stages)
+    size_t y[IRIS_HIFIGAN_MAX_KERNELS];   // running x of branch j
+    size_t xt[IRIS_HIFIGAN_MAX_KERNELS];  // conv1 output of branch j
+    size_t total;
+    size_t elem_bytes;                    // 2 (bf16 storage) or 4; every buffer starts on a multiple of 256 bytes
+    uint64_t bytes() const { return (uint64_t)total * elem_bytes; }
+};
+
+inline WsLayout ws_layout(const iris_hifigan_handle* h, int B, int T, int32_t dtype) {
+    WsLayout w;
+    w.elem_bytes = dtype == IRIS_HIFIGAN_BF16 ? 2 : 4;
+    const size_t round = 256 / w.elem_bytes - 1;
+    const size_t frames = (size_t)B * T;
+    size_t per_frame_max = 0, L = 1;
+    for (const auto& st : h->stages) {
+        L *= st.rate;
+        const size_t e = L * st.C;
+        if (e > per_frame_max) per_frame_max = e;
+    }
+    size_t off = 0;
+    auto take = [&](size_t elems) { size_t o = off; off += (elems + round) & ~round; return o; };
+    w.pre = take(frames * h->pre.C_out);
+    w.up = take(frames * per_frame_max);
+    for (int j = 0; j < h->cfg.num_kernels; ++j) {
+        w.y[j] = take(frames * per_frame_max);
+        w.xt[j] = take(frames * per_frame_max);
+    }
+    w.total = off;
+    return w;
+}
+
+// Device memory of a single-layer entry point (packed weights, a bias): freed when the call returns.
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t upload(const void* src, size_t bytes) {
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    }
+    template <class T> hipError_t upload(const std::vector<T>& v) { return upload(v.data(), v.size() * sizeof(T)); }
+    const float* f32() const { return (const float*)p; }
+};
+
 // ---- bf16-storage path (iris_hifigan_bf16.hip) ----
 int bf16_build_blob(iris_hifigan_handle* h, const float* weights_host);   // packs + uploads blob16 (host_only: packs only)
-uint64_t bf16_workspace_bytes(const iris_hifigan_handle* h, int B, int T);
-int bf16_workspace_map(const iris_hifigan_handle* h, int B, int T, iris_hifigan_workspace_map* out);
 int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void* wav_dev,
                  void* workspace_dev, uint64_t workspace_bytes, hipStream_t stream, const ForwardStop& stop,
                  int32_t* until_flags);

@@ -4,15 +4,18 @@
 // Keras twin src/iris/vocoder.py:103-130):
 //   conv_pre -> for each stage { LeakyReLU -> ConvTranspose1d -> MRF(3 ResBlocks) / 3 } -> LeakyReLU
 //   -> conv_post -> tanh.
-// Launch plan for one forward (V1 config: 30 launches):
+// Launches of one forward:
 //   1            conv_pre, reading the channels-first mel directly
-//   per stage:   1 upsample launch (all u phases as blockIdx.z; input = LeakyReLU of conv_pre, or
-//                LeakyReLU(mean of the previous stage's branch outputs) fused into the LDS staging)
-//                2*num_dilations grouped launches: launch s runs conv (s even: convs1[s/2], dilated;
-//                s odd: convs2[s/2] + residual) of ALL MRF branches at once (blockIdx.z = branch)
-//   1            conv_post + tanh, reading the mean of the last stage's branch outputs.
-// The MRF sum and the division by num_kernels (hifigan_pretrained.py:131-137) are never
-// materialised: the consumer of a stage reads the branch outputs and forms ((b0+b1)+b2)/3 itself.
+//   per stage:   1 upsample launch (one GEMM, or all u phases as blockIdx.z; input = LeakyReLU of conv_pre's output, of the
+//                MRF mean the previous stage stored, or of the mean of its branch outputs formed in the LDS staging)
+//                the MRF steps plan_mrf_stage lists: per dilation a fused conv pair, or convs1[m] and convs2[m] + residual
+//                as two grouped launches of ALL branches; the stage's last launch stores only the MRF mean where a block
+//                holds all branch outputs of its tile (summing forms)
+//   1            conv_post + tanh, reading that mean or the last stage's branch outputs.
+// Where no summing form runs, the MRF sum and the division by num_kernels (hifigan_pretrained.py:131-137) are never
+// materialised: the consumer of a stage reads the branch outputs and forms ((b0+b1)+b2)/3 itself.  DESIGN.md sections 2, 5.
+// Host structure: entry point (own argument checks) -> run_forward (device, weight packing, passes) -> forward_f32 /
+// bf16_forward; launch descriptors come from one builder per kind, shared with the single-layer entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -136,38 +139,85 @@ uint64_t ref_weight_count(iris_hifigan_handle* h) {
     return n;
 }
 
-// ---- workspace layout (floats per mel frame, times B*T) ----
-struct WsLayout {
-    size_t pre;   // conv_pre output                [B, T, C0]
-    size_t up;    // upsample output of a stage     [B, L, C]     (max over stages)
-    size_t y[IRIS_HIFIGAN_MAX_KERNELS];   // running x of branch j
-    size_t xt[IRIS_HIFIGAN_MAX_KERNELS];  // conv1 output of branch j
-    size_t total; // floats
-};
-
-WsLayout ws_layout(const iris_hifigan_handle* h, int B, int T) {
-    WsLayout w;
-    const size_t frames = (size_t)B * T;
-    size_t per_frame_max = 0;
-    size_t L = 1;
-    for (const auto& st : h->stages) {
-        L *= st.rate;
-        const size_t e = L * st.C;
-        if (e > per_frame_max) per_frame_max = e;
-    }
-    size_t off = 0;
-    auto take = [&](size_t floats) { size_t o = off; off += (floats + 63) & ~(size_t)63; return o; };
-    w.pre = take(frames * h->pre.C_out);
-    w.up = take(frames * per_frame_max);
-    for (int j = 0; j < h->cfg.num_kernels; ++j) {
-        w.y[j] = take(frames * per_frame_max);
-        w.xt[j] = take(frames * per_frame_max);
-    }
-    w.total = off;
-    return w;
+// ---- launch descriptors: one builder per kind, shared by the forwards and the single-layer entry points ----
+ConvProblem conv_problem(const float* x, const float* w, const float* bias, const float* res, float* y, int k, int dil,
+                         const float* w16 = nullptr) {
+    ConvProblem p; memset(&p, 0, sizeof(p));
+    p.x = x; p.wp = (const f32x4*)w; p.bias = bias; p.res = res; p.y = y;
+    p.ks = k; p.dil = dil; p.pad_left = dil * (k - 1) / 2;
+    p.wp16 = (const f32x4*)w16;
+    return p;
 }
 
-void init_launch(ConvLaunch& a) { memset(&a, 0, sizeof(a)); a.out_stride = 1; }
+// nz 'same'-padding convs [B, L, C_in] -> [B, L, C_out] in one launch: a single layer (conv_pre, PostNet), or one conv step
+// of all MRF branches.  `lengths` / `row_scale`: the ragged forward's bounds (ConvLaunch).
+ConvLaunch conv_launch(const ConvProblem* p, int nz, int B, int L, int C_in, int C_out, int in_act, float slope,
+                       const int32_t* lengths = nullptr, int row_scale = 1) {
+    ConvLaunch a; memset(&a, 0, sizeof(a));
+    for (int j = 0; j < nz; ++j) a.p[j] = p[j];
+    a.B = B; a.L_in = L; a.L_out = L; a.C_in = C_in; a.C_out = C_out; a.n_idx = L; a.out_stride = 1;
+    a.in_act = in_act; a.slope = slope;
+    a.lengths = lengths; a.row_scale = row_scale;
+    return a;
+}
+
+// The grouped step `a` as the MRF kernel's summing launch, which forms mean_j(y_j) itself: it processes p[2], p[1], p[0];
+// passing the branches reversed makes that resblock 0, 1, 2 -- the reference's summation order
+// (hifigan_pretrained.py:131-137).
+void to_summing(ConvLaunch& a, float* mean, int nk) {
+    std::swap(a.p[0], a.p[2]);
+    a.sum_y = mean; a.sum_div = (float)nk;
+}
+
+// ConvTranspose1d [B, L, C_in] -> [B, L * u, C_out] of x[0] (in_act IN_ACT_NONE / IN_ACT_LRELU) or of LeakyReLU(mean of the
+// n_in branch outputs x[]) (IN_ACT_MRF_LRELU), and which kernel takes it.
+struct ConvtF32 { bool gemm; ConvtLaunch c; ConvLaunch a; int k, u; };
+
+ConvtF32 convt_launch(const float* const* x, int n_in, int in_act, const float* w, const float* bias, float* y, int B, int L,
+                      int C_in, int C_out, int k, int u, float slope, const int32_t* lengths = nullptr, int row_scale = 1) {
+    ConvtF32 d; memset(&d, 0, sizeof(d));
+    d.k = k; d.u = u;
+    const bool mrf = in_act == IN_ACT_MRF_LRELU;
+    // (split-product mode keeps the upsamplers in fp32: split as well, they grew the worst observed waveform error
+    //  from 2e-5 to 5e-5 -- still inside 1e-4, but the mode keeps the wider margin)
+    d.gemm = (in_act == IN_ACT_LRELU || (mrf && n_in == 3)) && convt_gemm_applicable(C_in, C_out, k, u, L, L * u, slope);
+    if (d.gemm) {
+        // the whole layer as ONE GEMM [L + 1, 2 C_in] x [2 C_in, u C_out] (convt_mfma_f32.h), bit for bit the polyphase
+        // launches below; its input is one tensor (conv_pre's output, or the MRF mean the previous stage's last step
+        // stored) or the previous stage's three branch outputs, whose mean is then formed while the window is staged
+        ConvtLaunch& c = d.c;
+        c.x = x[0]; c.wp = (const f32x4*)w; c.bias = bias; c.y = y;
+        if (mrf) { c.x1 = x[1]; c.x2 = x[2]; }
+        c.B = B; c.L_in = L; c.L_out = L * u; c.C_in = C_in; c.C_out = C_out; c.u = u; c.slope = slope;
+        c.lengths = lengths; c.row_scale = row_scale;
+        return d;
+    }
+    // all u phases in one grid (blockIdx.z), each a conv of `taps` taps over the input
+    const int taps = convt_taps(k, u);
+    ConvProblem p = conv_problem(x[0], w, bias, nullptr, y, taps, 1);
+    p.pad_left = taps - 1;
+    ConvLaunch& a = d.a;
+    a = conv_launch(&p, 1, B, L, C_in, C_out, in_act, slope, lengths, row_scale);
+    a.L_out = L * u; a.n_idx = L + taps - 1; a.out_stride = u; a.out_off = -(k - u) / 2;
+    a.z_is_phase = 1;
+    a.phase_wp_stride = (int64_t)(packed_convt_phase_floats(C_in, C_out, k, u) / 4);
+    if (mrf) { a.n_mrf = n_in; for (int j = 0; j < n_in; ++j) a.xmrf[j] = x[j]; }
+    return d;
+}
+
+hipError_t launch_convt(ConvtF32& d, hipStream_t stream) {
+    return d.gemm ? launch_convt_gemm(d.c, d.k, stream) : launch_conv(d.a, d.u, stream);
+}
+
+// conv1 -> conv2 + residual of all branches in one launch (mrf_pair_f32.h)
+PairLaunchF32 pair_launch(const PairProblemF32* p, int nk, int B, int L, int C, float slope, const int32_t* lengths = nullptr,
+                          int row_scale = 1) {
+    PairLaunchF32 pa; memset(&pa, 0, sizeof(pa));
+    for (int j = 0; j < nk && j < kMaxGroup; ++j) pa.p[j] = p[j];
+    pa.B = B; pa.L = L; pa.C = C; pa.slope = slope;
+    pa.lengths = lengths; pa.row_scale = row_scale;
+    return pa;
+}
 
 // second packing of the ResBlock conv weights for the small-problem kernel (mrf_small_f32.h): float offsets of each layer's
 // 16 x 16 fragments in blob_w16 (layers whose channel counts are not multiples of 16 keep -1: they never take that kernel)
@@ -361,11 +411,9 @@ int32_t iris_hifigan_workspace_bytes(const iris_hifigan_handle* h, int32_t B, in
                                      int32_t dtype, uint64_t* bytes) {
     if (!h || !bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 0 || T < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    B = pass_items(B, T);                                   // a large batch runs as passes over sub-batches sharing the workspace
-    if (dtype == IRIS_HIFIGAN_BF16) { *bytes = bf16_workspace_bytes(h, B, T); return IRIS_HIFIGAN_OK; }
-    if (dtype != IRIS_HIFIGAN_F32 && dtype != IRIS_HIFIGAN_F32_SPLIT)
+    if (dtype != IRIS_HIFIGAN_F32 && dtype != IRIS_HIFIGAN_BF16 && dtype != IRIS_HIFIGAN_F32_SPLIT)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "dtype %d not supported", dtype);
-    *bytes = ws_layout(h, B, T).total * sizeof(float);
+    *bytes = ws_layout(h, pass_items(B, T), T, dtype).bytes();   // a large batch runs as passes over sub-batches sharing the workspace
     return IRIS_HIFIGAN_OK;
 }
 
@@ -403,7 +451,291 @@ int32_t iris_hifigan_read_profile(iris_hifigan_handle* h, iris_hifigan_launch_re
 
 namespace {
 
-// Checks shared by forward and forward_until.
+// ---- MRF: the launches of one stage, decided once ----
+enum WsBuf : uint8_t { WS_NONE, WS_UP, WS_Y, WS_XT };        // the stage's upsample output; y[j] / xt[j] of branch j
+enum StepKind : uint8_t {
+    STEP_PAIR,        // conv1 -> conv2 + residual of one dilation in ONE launch (mrf_pair_f32.h)
+    STEP_PAIR_SUM,    // ... the stage's last pair on the persistent kernel, which stores only the MRF mean (mrf_pair_f32_pf.h)
+    STEP_CONV1,       // convs1[m] of all branches
+    STEP_CONV2,       // convs2[m] + residual of all branches
+    STEP_CONV2_SUM,   // ... the stage's last step, storing only the MRF mean
+};
+struct MrfStep {
+    StepKind kind;
+    bool split;             // the conv steps on split-bf16 products (conv_mfma_f32s.h)
+    int m, half;            // MRF step 2 * m + half of the stage (a pair carries its second step's index)
+    WsBuf x, res, y;        // per branch: what the step reads, adds as the residual (conv2) and writes
+    bool mean_in_y0;        // the step leaves mean_j(branch j) in y[0] and no branch outputs
+};
+struct MrfStagePlan { int n; MrfStep s[2 * IRIS_HIFIGAN_MAX_DILATIONS]; };
+
+struct StageCtx {           // what the MRF launches of stage i share in one pass
+    const iris_hifigan_handle* h;
+    int i, B, L;            // L: rows per item after the stage's upsample
+    float *up, *y[IRIS_HIFIGAN_MAX_KERNELS], *xt[IRIS_HIFIGAN_MAX_KERNELS];
+    const int32_t* lengths; int row_scale;
+    bool dyn_tiles;
+    const Stage& st() const { return h->stages[i]; }
+    float* buf(WsBuf r, int j) const { return r == WS_UP ? up : r == WS_Y ? y[j] : r == WS_XT ? xt[j] : nullptr; }
+    double n_el() const { return (double)B * L * st().C; }
+};
+
+// one conv step (half 0: convs1[m], half 1: convs2[m] + residual) of all branches, separate launches
+ConvLaunch step_launch(const StageCtx& c, const MrfStep& s, double& flops, double& wbytes) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const int nk = h->cfg.num_kernels;
+    ConvProblem p[kMaxGroup];
+    flops = 0; wbytes = 0;
+    for (int j = 0; j < nk; ++j) {
+        const ConvLayer& l = s.half == 0 ? st.c1[j][s.m] : st.c2[j][s.m];
+        p[j] = conv_problem(c.buf(s.x, j), h->blob + l.w_off, h->blob + l.b_off, c.buf(s.res, j), c.buf(s.y, j), l.k, l.dil,
+                            (h->blob_w16 && l.w16f_off != (size_t)-1) ? h->blob_w16 + l.w16f_off : nullptr);
+        flops += 2.0 * c.n_el() * l.C_in * l.k;
+        wbytes += 4.0 * ((double)l.ref_w_floats + l.C_out);
+    }
+    ConvLaunch a = conv_launch(p, nk, c.B, c.L, st.C, st.C, IN_ACT_LRELU, h->cfg.lrelu_slope, c.lengths, c.row_scale);
+    a.dyn_counter = c.dyn_tiles ? h->tile_counters + (c.i * 2 * h->cfg.num_dilations[0] + 2 * s.m + s.half) : nullptr;
+    return a;
+}
+
+// the pair of dilation s.m; *ok: the layers are what the pair kernels take (equal kernel sizes, conv2 undilated)
+PairLaunchF32 stage_pair_launch(const StageCtx& c, const MrfStep& s, double& flops, double& wbytes, bool* ok = nullptr) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const int nk = h->cfg.num_kernels;
+    PairProblemF32 p[kMaxGroup];
+    flops = 0; wbytes = 0;
+    bool good = nk <= kMaxGroup;
+    for (int j = 0; j < nk && good; ++j) {
+        const ConvLayer& c1 = st.c1[j][s.m];
+        const ConvLayer& c2 = st.c2[j][s.m];
+        good = c1.k == c2.k && c2.dil == 1 && c1.C_in == st.C && c1.C_out == st.C && c2.C_in == st.C && c2.C_out == st.C;
+        p[j] = PairProblemF32{c.buf(s.x, j), (const f32x4*)(h->blob + c1.w_off), (const f32x4*)(h->blob + c2.w_off),
+                              h->blob + c1.b_off, h->blob + c2.b_off, c.buf(s.y, j), c1.k, c1.dil};
+        flops += 2.0 * c.n_el() * st.C * (c1.k + c2.k);
+        wbytes += 4.0 * ((double)c1.ref_w_floats + c1.C_out + (double)c2.ref_w_floats + c2.C_out);
+    }
+    if (ok) *ok = good;
+    return pair_launch(p, good ? nk : 0, c.B, c.L, st.C, h->cfg.lrelu_slope, c.lengths, c.row_scale);
+}
+
+// The steps of stage c.i, in order, with the buffers each reads and writes.  Pure: nothing is launched or recorded here.
+MrfStagePlan plan_mrf_stage(const StageCtx& c, int32_t dtype, const ForwardStop& stop) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const int nk = h->cfg.num_kernels, nd = h->cfg.num_dilations[0];
+    double f, wb;
+    // fp32 storage, split-bf16 products (conv_mfma_f32s.h): every step separate; at the last step of the stage the kernel
+    // folds the branch mean (written to y[0]; a lane overwrites only elements it has read itself as branch 0's residual)
+    const bool split = dtype == IRIS_HIFIGAN_F32_SPLIT && f32s_step_applicable(h, st.C, c.L, nk);
+    // The stage's last step as the MRF kernel's summing launch (to_summing).  The mean goes to y[0] (in place: each lane
+    // overwrites only elements it read itself as branch 0's residual).  Small problems run one branch per block -- mrf_plan's
+    // latency modes -- and cannot sum.
+    bool sums = split;
+    if (!split && nk == 3) {
+        const ConvLaunch a = step_launch(c, MrfStep{STEP_CONV2, false, nd - 1, 1, WS_XT, WS_Y, WS_Y, false}, f, wb);
+        if (mrf_kernel_applicable(a, nk)) {
+            const MrfPlan pq = mrf_plan(a, true);
+            ConvLaunch b = a;
+            to_summing(b, c.y[0], nk);
+            sums = mrf_kernel_applicable(b, nk) && !pq.zpar && !pq.small;
+        }
+    }
+    // ---- fused conv pairs (mrf_pair_f32.h; C = 32 / 64, exact fp32): conv1 -> xt in LDS -> conv2 + residual in ONE launch,
+    // bit for bit the two separate launches.  A fused pair cannot run in place, so the running x of a branch alternates
+    // between its y and xt buffers, arranged so that the last fused pair leaves it in y (where the separate launches and
+    // the next layer expect it).  The last pair of the stage stays separate when its second step is the persistent
+    // kernel's summing launch (which forms the MRF mean; large problems).  forward_until asking for a state after a
+    // conv1 gets the separate launches for that stage.
+    int n_fused = 0;
+    bool fused_sum = false;     // the stage's last pair forms the MRF mean itself (mrf_pair_f32_pf.h; no persistent summing launches)
+    if (dtype == IRIS_HIFIGAN_F32 && !(stop.stage == c.i && !(stop.step & 1))) {
+        bool all_ok = true;
+        PairLaunchF32 pa;
+        for (int m = 0; m < nd && all_ok; ++m) {
+            pa = stage_pair_launch(c, MrfStep{STEP_PAIR, false, m, 1, WS_UP, WS_NONE, WS_Y, false}, f, wb, &all_ok);
+            all_ok = all_ok && pair_f32_applicable(pa, nk);
+        }
+        if (all_ok) {
+            // The stage's LAST pair on the persistent summing kernel (mrf_pair_f32_pf.h: a block runs the three branches of
+            // its tile and stores only the MRF mean -- no xt, no per-branch outputs, one launch instead of the persistent
+            // kernel's two): taken where its whole-tile jobs fill at least four rounds of the chip well.  Measured
+            // (profiles/r03_notes.md): +3 % on the C = 32 stage and +0.6 % on the step at batch 32 x 500, neutral at
+            // batch 1 x 1000, a loss where a launch is one or two rounds (its jobs are 21 tap-units against 11 / 7 / 3).
+            // The non-summing pairs stay on the one-job-per-block kernel: as persistent, prefetching blocks they
+            // were 3-5 % slower at every size.
+            const PairPfTileF32 pt = pair_pf_f32_tile(st.C);
+            const long long tiles_pf = (long long)((c.L + (pt.M - 10) - 1) / (pt.M - 10)) * c.B;
+            if (pair_pf_f32_applicable(pa, nk)) {
+                const PairPfPlanF32 sp = pair_pf_f32_plan(tiles_pf, device_cu_count(), pt.MINB);
+                fused_sum = sp.efficiency >= 0.85 && tiles_pf >= 4LL * device_cu_count() * sp.per_cu;
+            }
+            n_fused = (fused_sum || !sums) ? nd : nd - 1;
+        }
+    }
+    MrfStagePlan pl;
+    pl.n = 0;
+    auto add = [&](StepKind kind, int m, int half, WsBuf x, WsBuf res, WsBuf y) {
+        pl.s[pl.n++] = MrfStep{kind, split, m, half, x, res, y, kind == STEP_PAIR_SUM || kind == STEP_CONV2_SUM};
+    };
+    // never in place: the running x of a branch alternates between its y and xt buffers, arranged so that the last
+    // fused pair ends in y -- or, in front of the summing pair (which writes the mean to y[0]), in xt
+    const int last_pair = fused_sum ? nd - 2 : n_fused - 1;
+    const WsBuf last_to = fused_sum ? WS_XT : WS_Y, other = fused_sum ? WS_Y : WS_XT;
+    WsBuf cur = WS_UP;          // where the running x of every branch lies
+    for (int m = 0; m < nd; ++m) {
+        if (m < n_fused && fused_sum && m == nd - 1) {
+            add(STEP_PAIR_SUM, m, 1, cur, WS_NONE, WS_Y);
+        } else if (m < n_fused) {
+            const WsBuf to = ((last_pair - m) & 1) ? other : last_to;
+            add(STEP_PAIR, m, 1, cur, WS_NONE, to);
+            cur = to;
+        } else {
+            add(STEP_CONV1, m, 0, cur, WS_NONE, WS_XT);
+            add(m == nd - 1 && sums ? STEP_CONV2_SUM : STEP_CONV2, m, 1, WS_XT, cur, WS_Y);
+            cur = WS_Y;
+        }
+    }
+    return pl;
+}
+
+// The fp32 / split-product forward.  `stop` (forward_until only): return after MRF step stop.step of stage
+// stop.stage has been queued; *until_flags then says where that stage's result lies (forward_until's contract).
+// `lengths` (iris_hifigan_forward_ragged, fp32 only; nullptr otherwise): mel frames of each batch item on the device.
+// Every launch carries it with its rows per mel frame (`row_scale`), and every kernel bounds the item's reads and stores
+// by them: the plan is the one of (B, T), each item is computed as a forward of its own length would compute it.
+int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, void* wav_dev, void* workspace_dev,
+                uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop, int32_t* until_flags,
+                const int32_t* lengths) {
+    const WsLayout w = ws_layout(h, B, T, dtype);
+    if (workspace_bytes < w.bytes())
+        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
+                    (unsigned long long)workspace_bytes, (unsigned long long)w.bytes());
+    float* ws = (float*)workspace_dev;
+    const float* blob = h->blob;
+    const float slope = h->cfg.lrelu_slope;
+    const int nk = h->cfg.num_kernels, nd = h->cfg.num_dilations[0];
+    Prof prof{h, stream, (h->profiling && !h->profiling_paused) ? h->n_rec : 0};
+    const double fB = (double)B;
+    // large batches: the MRF kernel's blocks draw tiles from per-launch counters (mrf_conv_mfma_f32.h); one
+    // memset per forward zeroes them.  Below ~2000 frames no launch has enough tiles per block to use them.
+    const bool dyn_tiles = h->tile_counters && (long long)B * T >= 2000 &&
+                           (int)h->stages.size() * 2 * nd <= kTileCounterWords / 2;
+    // the persistent pair kernels draw jobs from one counter word per launch (upper half of the array); a forward too short
+    // to use either kind of counter skips the memset
+    const bool pf_counters = h->tile_counters && (long long)B * T >= 100 &&
+                             (int)h->stages.size() * nd <= kTileCounterWords / 2;
+    // (zeroed where the first launch that reads them is about to be issued: a batch-1 forward of a few hundred frames has none)
+    bool counters_zeroed = false;
+    auto zero_counters = [&]() -> hipError_t {
+        if (counters_zeroed || h->host_only) return hipSuccess;
+        counters_zeroed = true;
+        return hipMemsetAsync(h->tile_counters, 0, kTileCounterWords * sizeof(unsigned), stream);
+    };
+    if (dyn_tiles) HIP_TRY(zero_counters());
+
+    // ---- conv_pre (hifigan_pretrained.py:124) ----
+    {
+        const ConvLayer& l = h->pre;
+        const ConvProblem p = conv_problem((const float*)mel_dev, blob + l.w_off, blob + l.b_off, nullptr, ws + w.pre, l.k, 1);
+        ConvLaunch a = conv_launch(&p, 1, B, T, l.C_in, l.C_out, IN_ACT_NONE, slope, lengths, 1);
+        a.x_channels_first = 1;
+        TRY(prof.begin(0, -1, 0, 2.0 * fB * T * l.C_in * l.C_out * l.k,
+                       4.0 * (fB * T * (l.C_in + l.C_out) + (double)l.ref_w_floats + l.C_out)));
+        HIP_TRY(launch_conv(a, 1, stream));
+        TRY(prof.end());
+    }
+
+    StageCtx c;
+    c.h = h; c.B = B; c.L = T; c.lengths = lengths; c.row_scale = 1; c.dyn_tiles = dyn_tiles;
+    c.up = ws + w.up;
+    for (int j = 0; j < nk; ++j) { c.y[j] = ws + w.y[j]; c.xt[j] = ws + w.xt[j]; }
+    bool prev_summed = false;   // the previous stage left mean(branches) in y[0]
+    for (c.i = 0; c.i < (int)h->stages.size(); ++c.i) {
+        const Stage& st = c.st();
+        const int L = c.L, L_out = L * st.rate;
+        // ---- LeakyReLU + ConvTranspose1d (hifigan_pretrained.py:127-128) ----
+        {
+            const ConvLayer& l = st.up;
+            // bytes are reported in accounting L (SURVEY.md 8d: the MRF accumulation costs one extra read
+            // per additional branch) whether or not the summing step already folded the mean
+            const int n_in = c.i == 0 ? 1 : nk;
+            const float* const one = c.i == 0 ? ws + w.pre : c.y[0];
+            const bool mrf = c.i > 0 && !prev_summed;
+            ConvtF32 d = convt_launch(mrf ? c.y : &one, nk, mrf ? IN_ACT_MRF_LRELU : IN_ACT_LRELU, blob + l.w_off, blob + l.b_off,
+                                      c.up, B, L, l.C_in, l.C_out, l.k, l.u, slope, lengths, c.row_scale);
+            TRY(prof.begin(1, c.i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
+                           4.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out + (double)l.ref_w_floats + l.C_out)));
+            HIP_TRY(launch_convt(d, stream));
+            TRY(prof.end());
+        }
+        // ---- MRF: num_kernels ResBlocks advance together (hifigan_pretrained.py:64-71,131-136) ----
+        c.L = L_out;
+        c.row_scale *= st.rate;
+        const MrfStagePlan plan = plan_mrf_stage(c, dtype, stop);
+        for (int n = 0; n < plan.n; ++n) {
+            const MrfStep& s = plan.s[n];
+            double flops, wbytes;
+            if (s.kind == STEP_PAIR || s.kind == STEP_PAIR_SUM) {
+                PairLaunchF32 pa = stage_pair_launch(c, s, flops, wbytes);
+                // algorithmic FLOP / bytes (accounting L) are those of both steps; the record carries the second step's index
+                TRY(prof.begin(2, c.i, 2 * s.m + 1, flops, 4.0 * c.n_el() * nk * 5 + wbytes));
+                if (s.kind == STEP_PAIR_SUM) {
+                    // (a zeroed counter word per persistent launch: the upper half of the per-forward counters)
+                    unsigned* const ctr = pf_counters ? h->tile_counters + kTileCounterWords / 2 + (c.i * nd + s.m) : nullptr;
+                    if (ctr) HIP_TRY(zero_counters());
+                    HIP_TRY(launch_pair_f32_pf(pa, nk, c.y[0], ctr, stream));
+                } else
+                    HIP_TRY(launch_pair_f32(pa, nk, stream));
+            } else {
+                ConvLaunch a = step_launch(c, s, flops, wbytes);
+                TRY(prof.begin(2, c.i, 2 * s.m + s.half, flops, 4.0 * c.n_el() * nk * (s.half == 0 ? 2 : 3) + wbytes));
+                if (s.split) {
+                    F32sStep step;
+                    for (int j = 0; j < nk; ++j) {
+                        step.x[j] = a.p[j].x; step.res[j] = a.p[j].res; step.y[j] = a.p[j].y;
+                        step.layer[j] = s.half == 0 ? &st.c1[j][s.m] : &st.c2[j][s.m];
+                    }
+                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, s.mean_in_y0 ? c.y[0] : nullptr, stream));
+                } else {
+                    if (s.mean_in_y0) to_summing(a, c.y[0], nk);
+                    if (mrf_kernel_applicable(a, nk)) HIP_TRY(launch_mrf_conv(a, nk, stream));
+                    else                              HIP_TRY(launch_conv(a, nk, stream));
+                }
+            }
+            TRY(prof.end());
+            prev_summed = s.mean_in_y0;
+            if (stop.stage == c.i && stop.step == 2 * s.m + s.half) {
+                if (until_flags)
+                    *until_flags = s.mean_in_y0 ? IRIS_HIFIGAN_UNTIL_MEAN_IN_Y0
+                                                : (s.kind == STEP_PAIR && s.y == WS_XT ? IRIS_HIFIGAN_UNTIL_X_IN_XT : 0);
+                TRY(prof.finish());
+                return IRIS_HIFIGAN_OK;
+            }
+        }
+    }
+
+    // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141) ----
+    {
+        post::ConvPostLaunch a; memset(&a, 0, sizeof(a));
+        const ConvLayer& l = h->post;
+        const int L = c.L;
+        if (prev_summed) { a.x[0] = c.y[0]; a.n_in = 1; }
+        else { for (int j = 0; j < nk; ++j) a.x[j] = c.y[j]; a.n_in = nk; }
+        a.w = blob + l.w_off; a.bias = blob + l.b_off; a.y = (float*)wav_dev;
+        a.B = B; a.L = L; a.C = l.C_in; a.k = l.k; a.slope = slope; a.inv_n = 1.0f / (float)nk;
+        a.lengths = lengths; a.row_scale = c.row_scale;
+        TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
+                       4.0 * (fB * L * l.C_in * nk + fB * L + (double)l.ref_w_floats + 1)));
+        HIP_TRY(post::launch_conv_post(a, stream));
+        TRY(prof.end());
+    }
+    TRY(prof.finish());
+    return IRIS_HIFIGAN_OK;
+}
+
+// Checks shared by the forwards, forward_until and describe_plan.
 int check_forward_args(const iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, const void* workspace_dev,
                        int32_t dtype) {
     if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
@@ -418,282 +750,29 @@ int check_forward_args(const iris_hifigan_handle* h, const void* mel_dev, int32_
     return IRIS_HIFIGAN_OK;
 }
 
-// The fp32 / split-product forward.  `stop` (forward_until only): return after MRF step stop.step of stage
-// stop.stage has been queued; *mean_in_y0 then says where that stage's result lies (forward_until's contract).
-// `lengths` (iris_hifigan_forward_ragged, fp32 only; nullptr otherwise): mel frames of each batch item on the device.
-// Every launch carries it with its rows per mel frame (`row_scale`), and every kernel bounds the item's reads and stores
-// by them: the plan is the one of (B, T), each item is computed as a forward of its own length would compute it.
-int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, void* wav_dev, void* workspace_dev,
-                uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop, int32_t* until_flags,
-                const int32_t* lengths) {
-    const WsLayout w = ws_layout(h, B, T);
-    if (workspace_bytes < w.total * sizeof(float))
-        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)(w.total * sizeof(float)));
-    float* ws = (float*)workspace_dev;
-    const float* blob = h->blob;
-    const float slope = h->cfg.lrelu_slope;
-    const int nk = h->cfg.num_kernels;
-    Prof prof{h, stream, (h->profiling && !h->profiling_paused) ? h->n_rec : 0};
-    const double fB = (double)B;
-    // large batches: the MRF kernel's blocks draw tiles from per-launch counters (mrf_conv_mfma_f32.h); one
-    // memset per forward zeroes them.  Below ~2000 frames no launch has enough tiles per block to use them.
-    const bool dyn_tiles = h->tile_counters && (long long)B * T >= 2000 &&
-                           (int)h->stages.size() * 2 * h->cfg.num_dilations[0] <= kTileCounterWords / 2;
-    // the persistent pair kernels draw jobs from one counter word per launch (upper half of the array); a forward too short
-    // to use either kind of counter skips the memset
-    const bool pf_counters = h->tile_counters && (long long)B * T >= 100 &&
-                             (int)h->stages.size() * h->cfg.num_dilations[0] <= kTileCounterWords / 2;
-    // (zeroed where the first launch that reads them is about to be issued: a batch-1 forward of a few hundred frames has none)
-    bool counters_zeroed = false;
-    auto zero_counters = [&]() -> hipError_t {
-        if (counters_zeroed || h->host_only) return hipSuccess;
-        counters_zeroed = true;
-        return hipMemsetAsync(h->tile_counters, 0, kTileCounterWords * sizeof(unsigned), stream);
-    };
-    if (dyn_tiles) HIP_TRY(zero_counters());
-
-    // ---- conv_pre (hifigan_pretrained.py:124) ----
-    {
-        ConvLaunch a; init_launch(a);
-        const ConvLayer& l = h->pre;
-        a.p[0].x = (const float*)mel_dev; a.p[0].wp = (const f32x4*)(blob + l.w_off);
-        a.p[0].bias = blob + l.b_off; a.p[0].res = nullptr; a.p[0].y = ws + w.pre;
-        a.p[0].ks = l.k; a.p[0].dil = 1; a.p[0].pad_left = (l.k - 1) / 2;
-        a.B = B; a.L_in = T; a.L_out = T; a.C_in = l.C_in; a.C_out = l.C_out; a.n_idx = T;
-        a.in_act = IN_ACT_NONE; a.x_channels_first = 1; a.slope = slope;
-        a.lengths = lengths; a.row_scale = 1;
-        TRY(prof.begin(0, -1, 0, 2.0 * fB * T * l.C_in * l.C_out * l.k,
-                       4.0 * (fB * T * (l.C_in + l.C_out) + (double)l.ref_w_floats + l.C_out)));
-        HIP_TRY(launch_conv(a, 1, stream));
-        TRY(prof.end());
+// What every forward does once its own argument checks have passed: the handle's device, the weight packing of the dtype,
+// then the passes (pass_items).  `lengths_dev`: the ragged forward's; `stop` / `until_flags`: forward_until's (one pass).
+// A host-only handle (describe_plan) has no device and every packing's offsets.
+int run_forward(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, const int32_t* lengths_dev, void* wav_dev,
+                void* workspace_dev, uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop,
+                int32_t* until_flags) {
+    DeviceGuard guard(h->device, !h->host_only);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    TRY(ensure_prepared(h, dtype, stream, true));
+    if (dtype == IRIS_HIFIGAN_F32_SPLIT && !h->blob_s3)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "split-product mode needs ResBlock channel counts that are multiples of 32");
+    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    const int Bp = pass_items(B, T);
+    for (int b0 = 0; b0 < B; b0 += Bp) {
+        const int nb = B - b0 < Bp ? B - b0 : Bp;
+        const float* mel_p = (const float*)mel_dev + (size_t)b0 * h->cfg.in_channels * T;
+        float* wav_p = (float*)wav_dev + (size_t)b0 * h->hop * T;
+        if (dtype == IRIS_HIFIGAN_BF16)
+            TRY(bf16_forward(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, stream, stop, until_flags));
+        else
+            TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, stream, stop, until_flags,
+                            lengths_dev ? lengths_dev + b0 : nullptr));
     }
-
-    int L = T;
-    int scale = 1;              // rows per mel frame of L (ragged bounds)
-    bool prev_summed = false;   // the previous stage left mean(branches) in y[0] (MRF kernel's summing step)
-    for (size_t i = 0; i < h->stages.size(); ++i) {
-        const Stage& st = h->stages[i];
-        const int L_out = L * st.rate;
-        const int scale_out = scale * st.rate;
-        // ---- LeakyReLU + ConvTranspose1d (hifigan_pretrained.py:127-128) ----
-        {
-            ConvLaunch a; init_launch(a);
-            const ConvLayer& l = st.up;
-            const int taps = convt_taps(l.k, l.u);
-            a.p[0].wp = (const f32x4*)(blob + l.w_off); a.p[0].bias = blob + l.b_off;
-            a.p[0].res = nullptr; a.p[0].y = ws + w.up;
-            a.p[0].ks = taps; a.p[0].dil = 1; a.p[0].pad_left = taps - 1;
-            // bytes are reported in accounting L (SURVEY.md 8d: the MRF accumulation costs one extra read
-            // per additional branch) whether or not the summing step already folded the mean
-            const int n_in = i == 0 ? 1 : nk;
-            if (i == 0) { a.p[0].x = ws + w.pre; a.in_act = IN_ACT_LRELU; }
-            else if (prev_summed) { a.p[0].x = ws + w.y[0]; a.in_act = IN_ACT_LRELU; }
-            else {
-                a.in_act = IN_ACT_MRF_LRELU; a.n_mrf = nk;
-                for (int j = 0; j < nk; ++j) a.xmrf[j] = ws + w.y[j];
-                a.p[0].x = a.xmrf[0];
-            }
-            a.B = B; a.L_in = L; a.L_out = L_out; a.C_in = l.C_in; a.C_out = l.C_out;
-            a.n_idx = L + taps - 1; a.out_stride = l.u; a.out_off = -(l.k - l.u) / 2;
-            a.z_is_phase = 1;
-            a.phase_wp_stride = (int64_t)(packed_convt_phase_floats(l.C_in, l.C_out, l.k, l.u) / 4);
-            a.slope = slope;
-            a.lengths = lengths; a.row_scale = scale;
-            TRY(prof.begin(1, (int)i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
-                           4.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out +
-                                  (double)l.ref_w_floats + l.C_out)));
-            // (split-product mode keeps the upsamplers in fp32: split as well, they grew the worst observed waveform error
-            //  from 2e-5 to 5e-5 -- still inside 1e-4, but the mode keeps the wider margin)
-            if ((a.in_act == IN_ACT_LRELU || (a.in_act == IN_ACT_MRF_LRELU && nk == 3)) &&
-                     convt_gemm_applicable(l.C_in, l.C_out, l.k, l.u, L, L_out, slope)) {
-                // the whole layer as ONE GEMM [L + 1, 2 C_in] x [2 C_in, u C_out] (convt_mfma_f32.h), bit for bit the polyphase
-                // launches below; its input is one tensor (conv_pre's output, or the MRF mean the previous stage's last step
-                // stored) or the previous stage's three branch outputs, whose mean is then formed while the window is staged
-                ConvtLaunch c; memset(&c, 0, sizeof(c));
-                c.x = a.p[0].x; c.wp = a.p[0].wp; c.bias = a.p[0].bias; c.y = a.p[0].y;
-                if (a.in_act == IN_ACT_MRF_LRELU) { c.x = a.xmrf[0]; c.x1 = a.xmrf[1]; c.x2 = a.xmrf[2]; }
-                c.B = B; c.L_in = L; c.L_out = L_out; c.C_in = l.C_in; c.C_out = l.C_out; c.u = l.u; c.slope = slope;
-                c.lengths = lengths; c.row_scale = scale;
-                HIP_TRY(launch_convt_gemm(c, l.k, stream));
-            } else
-                HIP_TRY(launch_conv(a, l.u, stream));
-            TRY(prof.end());
-        }
-        // ---- MRF: num_kernels ResBlocks advance together (hifigan_pretrained.py:64-71,131-136) ----
-        const int nd = h->cfg.num_dilations[0];
-        const double n_el = fB * L_out * st.C;
-        // one conv step (half 0: convs1[m], half 1: convs2[m] + residual) of all branches, separate launches
-        auto fill_step = [&](ConvLaunch& a, int m, int half, double& flops, double& wbytes) {
-            init_launch(a);
-            flops = 0; wbytes = 0;
-            for (int j = 0; j < nk; ++j) {
-                const ConvLayer& l = half == 0 ? st.c1[j][m] : st.c2[j][m];
-                ConvProblem& p = a.p[j];
-                const float* cur = (m == 0) ? ws + w.up : ws + w.y[j];  // x entering this pair
-                if (half == 0) { p.x = cur; p.res = nullptr; p.y = ws + w.xt[j]; }
-                else           { p.x = ws + w.xt[j]; p.res = cur; p.y = ws + w.y[j]; }
-                p.wp = (const f32x4*)(blob + l.w_off); p.bias = blob + l.b_off;
-                p.wp16 = (h->blob_w16 && l.w16f_off != (size_t)-1) ? (const f32x4*)(h->blob_w16 + l.w16f_off) : nullptr;
-                p.ks = l.k; p.dil = l.dil; p.pad_left = l.dil * (l.k - 1) / 2;
-                flops += 2.0 * n_el * l.C_in * l.k;
-                wbytes += 4.0 * ((double)l.ref_w_floats + l.C_out);
-            }
-            a.B = B; a.L_in = L_out; a.L_out = L_out; a.C_in = st.C; a.C_out = st.C;
-            a.n_idx = L_out; a.in_act = IN_ACT_LRELU; a.slope = slope;
-            a.lengths = lengths; a.row_scale = scale_out;
-            a.dyn_counter = dyn_tiles ? h->tile_counters + ((int)i * 2 * nd + 2 * m + half) : nullptr;
-        };
-        // The stage's last step `a` as the MRF kernel's summing launch *b, which forms mean_j(y_j) itself: it processes
-        // p[2], p[1], p[0]; passing the branches reversed makes that resblock 0, 1, 2 -- the reference's summation order
-        // (hifigan_pretrained.py:131-137).  The mean goes to y[0] (in place: each lane overwrites only elements it read
-        // itself as branch 0's residual).  Small problems run one branch per block -- mrf_plan's latency modes -- and
-        // cannot sum.
-        auto summing_last_step = [&](const ConvLaunch& a, ConvLaunch& b) -> bool {
-            if (nk != 3 || !mrf_kernel_applicable(a, nk)) return false;
-            const MrfPlan pq = mrf_plan(a, true);
-            b = a;
-            b.p[0] = a.p[2]; b.p[2] = a.p[0];
-            b.sum_y = ws + w.y[0]; b.sum_div = (float)nk;
-            return mrf_kernel_applicable(b, nk) && !pq.zpar && !pq.small;
-        };
-        // ---- fused conv pairs (mrf_pair_f32.h; C = 32 / 64, exact fp32): conv1 -> xt in LDS -> conv2 + residual in ONE launch,
-        // bit for bit the two separate launches.  A fused pair cannot run in place, so the running x of a branch alternates
-        // between its y and xt buffers, arranged so that the last fused pair leaves it in y (where the separate launches and
-        // the next layer expect it).  The last pair of the stage stays separate when its second step is the persistent
-        // kernel's summing launch (which forms the MRF mean; large problems).  forward_until asking for a state after a
-        // conv1 gets the separate launches for that stage.
-        auto fill_pair = [&](PairLaunchF32& pa, int m, double& flops, double& wbytes) -> bool {
-            memset(&pa, 0, sizeof(pa));
-            flops = 0; wbytes = 0;
-            bool ok = nk <= kMaxGroup;
-            for (int j = 0; j < nk && ok; ++j) {
-                const ConvLayer& c1 = st.c1[j][m];
-                const ConvLayer& c2 = st.c2[j][m];
-                ok = c1.k == c2.k && c2.dil == 1 && c1.C_in == st.C && c1.C_out == st.C && c2.C_in == st.C && c2.C_out == st.C;
-                PairProblemF32& p = pa.p[j];
-                p.w1 = (const f32x4*)(blob + c1.w_off); p.b1 = blob + c1.b_off;
-                p.w2 = (const f32x4*)(blob + c2.w_off); p.b2 = blob + c2.b_off;
-                p.ks = c1.k; p.dil = c1.dil;
-                flops += 2.0 * n_el * st.C * (c1.k + c2.k);
-                wbytes += 4.0 * ((double)c1.ref_w_floats + c1.C_out + (double)c2.ref_w_floats + c2.C_out);
-            }
-            pa.B = B; pa.L = L_out; pa.C = st.C; pa.slope = slope;
-            pa.lengths = lengths; pa.row_scale = scale_out;
-            return ok;
-        };
-        int n_fused = 0;
-        bool fused_sum = false;     // the stage's last pair forms the MRF mean itself (mrf_pair_f32_pf.h; no persistent summing launches)
-        if (dtype == IRIS_HIFIGAN_F32 && !(stop.stage == (int)i && !(stop.step & 1))) {
-            bool all_ok = true;
-            PairLaunchF32 pa0; double f0, wb0;
-            for (int m = 0; m < nd && all_ok; ++m) all_ok = fill_pair(pa0, m, f0, wb0) && pair_f32_applicable(pa0, nk);
-            if (all_ok) {
-                ConvLaunch a, b; double f, wb;
-                fill_step(a, nd - 1, 1, f, wb);
-                const bool sums = summing_last_step(a, b);      // (the same decision as at the last step below)
-                // The stage's LAST pair on the persistent summing kernel (mrf_pair_f32_pf.h: a block runs the three branches of
-                // its tile and stores only the MRF mean -- no xt, no per-branch outputs, one launch instead of the persistent
-                // kernel's two): taken where its whole-tile jobs fill at least four rounds of the chip well.  Measured
-                // (profiles/r03_notes.md): +3 % on the C = 32 stage and +0.6 % on the step at batch 32 x 500, neutral at
-                // batch 1 x 1000, a loss where a launch is one or two rounds (its jobs are 21 tap-units against 11 / 7 / 3).
-                // The non-summing pairs stay on the one-job-per-block kernel: as persistent, prefetching blocks they
-                // were 3-5 % slower at every size.
-                const PairPfTileF32 pt = pair_pf_f32_tile(st.C);
-                const long long tiles_pf = (long long)((L_out + (pt.M - 10) - 1) / (pt.M - 10)) * B;
-                if (pair_pf_f32_applicable(pa0, nk)) {
-                    const PairPfPlanF32 sp = pair_pf_f32_plan(tiles_pf, device_cu_count(), pt.MINB);
-                    fused_sum = sp.efficiency >= 0.85 && tiles_pf >= 4LL * device_cu_count() * sp.per_cu;
-                }
-                n_fused = (fused_sum || !sums) ? nd : nd - 1;
-            }
-        }
-        const float* cur_x[kMaxGroup];
-        for (int j = 0; j < nk && j < kMaxGroup; ++j) cur_x[j] = ws + w.up;
-        for (int m = 0; m < nd; ++m) {
-            if (m < n_fused) {
-                PairLaunchF32 pa; double flops, wbytes;
-                (void)fill_pair(pa, m, flops, wbytes);
-                const bool is_sum = fused_sum && m == nd - 1;
-                // never in place: the running x of a branch alternates between its y and xt buffers, arranged so that the last
-                // fused pair ends in y -- or, in front of the summing pair (which writes the mean to y[0]), in xt
-                const bool to_y = fused_sum ? (((nd - 2 - m) & 1) != 0) : (((n_fused - 1 - m) & 1) == 0);
-                for (int j = 0; j < nk; ++j) { pa.p[j].x = cur_x[j]; pa.p[j].y = to_y ? ws + w.y[j] : ws + w.xt[j]; }
-                // algorithmic FLOP / bytes (accounting L) are those of both steps; the record carries the second step's index
-                TRY(prof.begin(2, (int)i, 2 * m + 1, flops, 4.0 * n_el * nk * 5 + wbytes));
-                // (a zeroed counter word per persistent launch: the upper half of the per-forward counters)
-                unsigned* const ctr = pf_counters ? h->tile_counters + kTileCounterWords / 2 + ((int)i * nd + m) : nullptr;
-                if (is_sum && ctr) HIP_TRY(zero_counters());
-                if (is_sum) HIP_TRY(launch_pair_f32_pf(pa, nk, ws + w.y[0], ctr, stream));
-                else        HIP_TRY(launch_pair_f32(pa, nk, stream));
-                TRY(prof.end());
-                for (int j = 0; j < nk; ++j) cur_x[j] = pa.p[j].y;
-                if (m == nd - 1) prev_summed = is_sum;
-                if (stop.stage == (int)i && stop.step == 2 * m + 1) {
-                    if (until_flags) *until_flags = is_sum ? IRIS_HIFIGAN_UNTIL_MEAN_IN_Y0 : (to_y ? 0 : IRIS_HIFIGAN_UNTIL_X_IN_XT);
-                    TRY(prof.finish());
-                    return IRIS_HIFIGAN_OK;
-                }
-                continue;
-            }
-            for (int half = 0; half < 2; ++half) {
-                ConvLaunch a;
-                double flops = 0, wbytes = 0;
-                fill_step(a, m, half, flops, wbytes);
-                TRY(prof.begin(2, (int)i, 2 * m + half, flops,
-                               4.0 * n_el * nk * (half == 0 ? 2 : 3) + wbytes));
-                const bool last_step = m == nd - 1 && half == 1;
-                bool launched = false;
-                if (dtype == IRIS_HIFIGAN_F32_SPLIT && f32s_step_applicable(h, st.C, L_out, nk)) {
-                    // fp32 storage, split-bf16 products (conv_mfma_f32s.h); the branch mean is left to the consumer
-                    F32sStep step;
-                    for (int j = 0; j < nk; ++j) {
-                        step.x[j] = a.p[j].x; step.res[j] = a.p[j].res; step.y[j] = a.p[j].y;
-                        step.layer[j] = half == 0 ? &st.c1[j][m] : &st.c2[j][m];
-                    }
-                    // last step of the stage: the kernel folds the branch mean (written to y[0]; a lane overwrites only
-                    // elements it has read itself as branch 0's residual)
-                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, last_step ? ws + w.y[0] : nullptr, stream));
-                    launched = true;
-                    if (last_step) prev_summed = true;
-                }
-                ConvLaunch b;
-                if (!launched && last_step && summing_last_step(a, b)) {
-                    HIP_TRY(launch_mrf_conv(b, nk, stream));
-                    launched = true; prev_summed = true;
-                }
-                if (!launched) {
-                    if (last_step) prev_summed = false;
-                    if (mrf_kernel_applicable(a, nk)) HIP_TRY(launch_mrf_conv(a, nk, stream));
-                    else                              HIP_TRY(launch_conv(a, nk, stream));
-                }
-                TRY(prof.end());
-                if (stop.stage == (int)i && stop.step == 2 * m + half) {
-                    if (until_flags) *until_flags = (last_step && prev_summed) ? IRIS_HIFIGAN_UNTIL_MEAN_IN_Y0 : 0;
-                    TRY(prof.finish());
-                    return IRIS_HIFIGAN_OK;
-                }
-            }
-        }
-        L = L_out;
-        scale = scale_out;
-    }
-
-    // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141) ----
-    {
-        post::ConvPostLaunch a; memset(&a, 0, sizeof(a));
-        const ConvLayer& l = h->post;
-        if (prev_summed) { a.x[0] = ws + w.y[0]; a.n_in = 1; }
-        else { for (int j = 0; j < nk; ++j) a.x[j] = ws + w.y[j]; a.n_in = nk; }
-        a.w = blob + l.w_off; a.bias = blob + l.b_off; a.y = (float*)wav_dev;
-        a.B = B; a.L = L; a.C = l.C_in; a.k = l.k; a.slope = slope; a.inv_n = 1.0f / (float)nk;
-        a.lengths = lengths; a.row_scale = scale;
-        TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
-                       4.0 * (fB * L * l.C_in * nk + fB * L + (double)l.ref_w_floats + 1)));
-        HIP_TRY(post::launch_conv_post(a, stream));
-        TRY(prof.end());
-    }
-    TRY(prof.finish());
     return IRIS_HIFIGAN_OK;
 }
 
@@ -708,23 +787,8 @@ int32_t iris_hifigan_forward(iris_hifigan_handle* h, const void* mel_dev, int32_
     TRY(check_forward_args(h, mel_dev, B, T, workspace_dev, dtype));
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;  // empty batch / empty mel -> empty waveform
     if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    TRY(ensure_prepared(h, dtype, (hipStream_t)stream_, true));
-    if (dtype == IRIS_HIFIGAN_F32_SPLIT && !h->blob_s3)
-        return fail(IRIS_HIFIGAN_UNSUPPORTED, "split-product mode needs ResBlock channel counts that are multiples of 32");
-    const ForwardStop none{-1, -1};
-    const int Bp = pass_items(B, T);
-    for (int b0 = 0; b0 < B; b0 += Bp) {
-        const int nb = B - b0 < Bp ? B - b0 : Bp;
-        const float* mel_p = (const float*)mel_dev + (size_t)b0 * h->cfg.in_channels * T;
-        float* wav_p = (float*)wav_dev + (size_t)b0 * h->hop * T;
-        if (dtype == IRIS_HIFIGAN_BF16)
-            TRY(bf16_forward(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, (hipStream_t)stream_, none, nullptr));
-        else
-            TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, none, nullptr, nullptr));
-    }
-    return IRIS_HIFIGAN_OK;
+    return run_forward(h, mel_dev, B, T, nullptr, wav_dev, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+                       ForwardStop{-1, -1}, nullptr);
     IRIS_ABI_END
 }
 
@@ -739,21 +803,10 @@ int32_t iris_hifigan_forward_ragged(iris_hifigan_handle* h, const void* mel_dev,
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     if (!lengths_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
     if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    TRY(ensure_prepared(h, dtype, (hipStream_t)stream_, true));
     // the plan of (B, T), as iris_hifigan_forward: the lengths are never read on the host (fp32 plans are bitwise
     // plan-independent, so each item still gets the bits of a forward of its own length)
-    const ForwardStop none{-1, -1};
-    const int Bp = pass_items(B, T);
-    for (int b0 = 0; b0 < B; b0 += Bp) {
-        const int nb = B - b0 < Bp ? B - b0 : Bp;
-        const float* mel_p = (const float*)mel_dev + (size_t)b0 * h->cfg.in_channels * T;
-        float* wav_p = (float*)wav_dev + (size_t)b0 * h->hop * T;
-        TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, none, nullptr,
-                        lengths_dev + b0));
-    }
-    return IRIS_HIFIGAN_OK;
+    return run_forward(h, mel_dev, B, T, lengths_dev, wav_dev, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+                       ForwardStop{-1, -1}, nullptr);
     IRIS_ABI_END
 }
 
@@ -767,15 +820,8 @@ int32_t iris_hifigan_forward_until(iris_hifigan_handle* h, const void* mel_dev, 
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "no MRF step %d in stage %d", stop_step, stop_stage);
     if (pass_items(B, T) != B)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "forward_until takes shapes that run in one pass (B * T <= %d frames)", kPassFrames);
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    TRY(ensure_prepared(h, dtype, (hipStream_t)stream_, true));
-    if (dtype == IRIS_HIFIGAN_F32_SPLIT && !h->blob_s3)
-        return fail(IRIS_HIFIGAN_UNSUPPORTED, "split-product mode needs ResBlock channel counts that are multiples of 32");
-    const ForwardStop stop{stop_stage, stop_step};
-    if (dtype == IRIS_HIFIGAN_BF16)
-        return bf16_forward(h, mel_dev, B, T, nullptr, workspace_dev, workspace_bytes, (hipStream_t)stream_, stop, flags);
-    return forward_f32(h, mel_dev, B, T, nullptr, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_, stop, flags, nullptr);
+    return run_forward(h, mel_dev, B, T, nullptr, nullptr, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+                       ForwardStop{stop_stage, stop_step}, flags);
     IRIS_ABI_END
 }
 
@@ -800,26 +846,15 @@ int32_t iris_hifigan_describe_plan(const iris_hifigan_config* cfg, int32_t B, in
     void* const wav = reinterpret_cast<void*>((uintptr_t)0x50000000);
     void* const ws = reinterpret_cast<void*>((uintptr_t)0x100000000ull);
     TRY(check_forward_args(&h, mel, B, T, ws, dtype));
-    if (dtype == IRIS_HIFIGAN_F32_SPLIT && !h.blob_s3)
-        return fail(IRIS_HIFIGAN_UNSUPPORTED, "split-product mode needs ResBlock channel counts that are multiples of 32");
-    uint64_t need = 0;
-    TRY(iris_hifigan_workspace_bytes(&h, B, T, dtype, &need));
-    out->workspace_bytes = need;
-    out->cu_count = cu_count > 0 ? cu_count : 256;
-    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     DryRunLaunch recs[IRIS_HIFIGAN_MAX_PLAN_LAUNCHES];
-    DryRun dry{recs, IRIS_HIFIGAN_MAX_PLAN_LAUNCHES, 0, out->cu_count};
+    DryRun dry{recs, IRIS_HIFIGAN_MAX_PLAN_LAUNCHES, 0, cu_count > 0 ? cu_count : 256};
     struct Scope { DryRun* prev; Scope(DryRun* d) : prev(dry_run_slot()) { dry_run_slot() = d; } ~Scope() { dry_run_slot() = prev; } } scope(&dry);
-    const ForwardStop none{-1, -1};
-    int rc = IRIS_HIFIGAN_OK;
     const int Bp = pass_items(B, T);
-    out->passes = (B + Bp - 1) / Bp;
-    for (int b0 = 0; b0 < B && rc == IRIS_HIFIGAN_OK; b0 += Bp) {          // (the launches of every pass are recorded)
-        const int nb = B - b0 < Bp ? B - b0 : Bp;
-        rc = dtype == IRIS_HIFIGAN_BF16 ? bf16_forward(&h, mel, nb, T, wav, ws, need, nullptr, none, nullptr)
-                                        : forward_f32(&h, mel, nb, T, wav, ws, need, dtype, nullptr, none, nullptr, nullptr);
-    }
-    out->n_launches = dry.n;
+    out->workspace_bytes = ws_layout(&h, Bp, T, dtype).bytes();
+    out->cu_count = dry.cu_count;
+    if (B > 0 && T > 0) out->passes = (B + Bp - 1) / Bp;
+    const int rc = run_forward(&h, mel, B, T, nullptr, wav, ws, out->workspace_bytes, dtype, nullptr, ForwardStop{-1, -1}, nullptr);
+    out->n_launches = dry.n;                                    // (the launches of every pass are recorded)
     for (int i = 0; i < dry.n && i < IRIS_HIFIGAN_MAX_PLAN_LAUNCHES; ++i) {
         iris_hifigan_plan_launch& o = out->launches[i];
         strncpy(o.kernel, recs[i].kernel ? recs[i].kernel : "", sizeof(o.kernel) - 1);
@@ -835,32 +870,19 @@ int32_t iris_hifigan_workspace_layout(const iris_hifigan_handle* h, int32_t B, i
     if (!h || !out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 0 || T < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
     memset(out, 0, sizeof(*out));
-    B = pass_items(B, T);                                   // (the layout of one pass; forward_until takes single-pass shapes only)
-    if (dtype == IRIS_HIFIGAN_BF16) return bf16_workspace_map(h, B, T, out);
-    if (dtype != IRIS_HIFIGAN_F32 && dtype != IRIS_HIFIGAN_F32_SPLIT)
+    if (dtype != IRIS_HIFIGAN_F32 && dtype != IRIS_HIFIGAN_BF16 && dtype != IRIS_HIFIGAN_F32_SPLIT)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "dtype %d not supported", dtype);
-    const WsLayout w = ws_layout(h, B, T);
-    out->element_bytes = 4;
-    out->pre_offset = w.pre * 4; out->up_offset = w.up * 4; out->total_bytes = w.total * 4;
-    for (int j = 0; j < h->cfg.num_kernels; ++j) { out->y_offset[j] = w.y[j] * 4; out->xt_offset[j] = w.xt[j] * 4; }
+    const WsLayout w = ws_layout(h, pass_items(B, T), T, dtype);   // (the layout of one pass; forward_until takes single-pass shapes only)
+    const uint64_t e = w.elem_bytes;
+    out->element_bytes = (int32_t)e;
+    out->pre_offset = w.pre * e; out->up_offset = w.up * e; out->total_bytes = w.total * e;
+    for (int j = 0; j < h->cfg.num_kernels; ++j) { out->y_offset[j] = w.y[j] * e; out->xt_offset[j] = w.xt[j] * e; }
     return IRIS_HIFIGAN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // single-layer entry points
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct DevBuf {
-    float* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t upload(const std::vector<float>& v) {
-        hipError_t e = hipMalloc(&p, v.size() * sizeof(float));
-        if (e != hipSuccess) return e;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice);
-    }
-};
-}  // namespace
-
 int32_t iris_hifigan_op_conv1d(const float* x_dev, const float* w_host, const float* bias_host,
                                const float* res_dev, float* y_dev, int32_t B, int32_t L,
                                int32_t C_in, int32_t C_out, int32_t k, int32_t dilation,
@@ -876,11 +898,9 @@ int32_t iris_hifigan_op_conv1d(const float* x_dev, const float* w_host, const fl
     memcpy(packed.data() + boff, bias_host, sizeof(float) * C_out);
     DevBuf wb;
     HIP_TRY(wb.upload(packed));
-    ConvLaunch a; init_launch(a);
-    a.p[0].x = x_dev; a.p[0].wp = (const f32x4*)wb.p; a.p[0].bias = wb.p + boff; a.p[0].res = res_dev;
-    a.p[0].y = y_dev; a.p[0].ks = k; a.p[0].dil = dilation; a.p[0].pad_left = dilation * (k - 1) / 2;
-    a.B = B; a.L_in = L; a.L_out = L; a.C_in = C_in; a.C_out = C_out; a.n_idx = L;
-    a.in_act = in_act ? IN_ACT_LRELU : IN_ACT_NONE; a.x_channels_first = x_channels_first; a.slope = slope;
+    const ConvProblem p = conv_problem(x_dev, wb.f32(), wb.f32() + boff, res_dev, y_dev, k, dilation);
+    ConvLaunch a = conv_launch(&p, 1, B, L, C_in, C_out, in_act ? IN_ACT_LRELU : IN_ACT_NONE, slope);
+    a.x_channels_first = x_channels_first;
     HIP_TRY(launch_conv(a, 1, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
@@ -903,21 +923,9 @@ int32_t iris_hifigan_op_conv_transpose1d(const float* x_dev, const float* w_host
     memcpy(packed.data() + boff, bias_host, sizeof(float) * C_out);
     DevBuf wb;
     HIP_TRY(wb.upload(packed));
-    const int taps = convt_taps(k, u);
-    ConvLaunch a; init_launch(a);
-    a.p[0].x = x_dev; a.p[0].wp = (const f32x4*)wb.p; a.p[0].bias = wb.p + boff; a.p[0].res = nullptr;
-    a.p[0].y = y_dev; a.p[0].ks = taps; a.p[0].dil = 1; a.p[0].pad_left = taps - 1;
-    a.B = B; a.L_in = L; a.L_out = L * u; a.C_in = C_in; a.C_out = C_out; a.n_idx = L + taps - 1;
-    a.out_stride = u; a.out_off = -(k - u) / 2; a.z_is_phase = 1;
-    a.phase_wp_stride = (int64_t)(phase_floats / 4);
-    a.in_act = in_act ? IN_ACT_LRELU : IN_ACT_NONE; a.slope = slope;
-    if (in_act && convt_gemm_applicable(C_in, C_out, k, u, L, L * u, slope)) {       // (what the forward launches for this layer)
-        ConvtLaunch c; memset(&c, 0, sizeof(c));
-        c.x = x_dev; c.wp = a.p[0].wp; c.bias = a.p[0].bias; c.y = y_dev;
-        c.B = B; c.L_in = L; c.L_out = L * u; c.C_in = C_in; c.C_out = C_out; c.u = u; c.slope = slope;
-        HIP_TRY(launch_convt_gemm(c, k, stream));
-    } else
-        HIP_TRY(launch_conv(a, u, stream));
+    ConvtF32 d = convt_launch(&x_dev, 1, in_act ? IN_ACT_LRELU : IN_ACT_NONE, wb.f32(), wb.f32() + boff, y_dev, B, L, C_in, C_out,
+                              k, u, slope);
+    HIP_TRY(launch_convt(d, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
@@ -943,7 +951,7 @@ int32_t iris_hifigan_op_conv_post(const float* x0_dev, const float* x1_dev, cons
     post::ConvPostLaunch a; memset(&a, 0, sizeof(a));
     a.x[0] = x0_dev; a.n_in = 1;
     if (x1_dev) { a.x[1] = x1_dev; a.x[2] = x2_dev; a.n_in = 3; }
-    a.w = wb.p; a.bias = wb.p + (size_t)k * C_in; a.y = y_dev;
+    a.w = wb.f32(); a.bias = wb.f32() + (size_t)k * C_in; a.y = y_dev;
     a.B = B; a.L = L; a.C = C_in; a.k = k; a.slope = slope; a.inv_n = 1.0f / (float)a.n_in;
     HIP_TRY(post::launch_conv_post(a, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -966,30 +974,24 @@ int32_t iris_hifigan_op_mrf_step(const float* const* x_dev, const float* const* 
     }
     hipStream_t stream = (hipStream_t)stream_;
     DevBuf wb[3], wb16[3];
-    size_t boff[3];
-    ConvLaunch a; init_launch(a);
+    ConvProblem p[3];
     for (int j = 0; j < nk; ++j) {
         std::vector<float> packed(packed_conv1d_floats(C, C, k[j]) + ((size_t)C + 3 & ~(size_t)3));
         pack_conv1d_weights(w_host[j], C, C, k[j], packed.data());
-        boff[j] = packed_conv1d_floats(C, C, k[j]);
-        memcpy(packed.data() + boff[j], bias_host[j], sizeof(float) * C);
+        const size_t boff = packed_conv1d_floats(C, C, k[j]);
+        memcpy(packed.data() + boff, bias_host[j], sizeof(float) * C);
         HIP_TRY(wb[j].upload(packed));
         if ((C & 15) == 0) {
             std::vector<float> p16(packed16_conv1d_floats(C, C, k[j]));
             pack_conv1d_weights16(w_host[j], C, C, k[j], p16.data());
             HIP_TRY(wb16[j].upload(p16));
         }
-        ConvProblem& p = a.p[j];
-        p.wp16 = (const f32x4*)wb16[j].p;
-        p.x = x_dev[j]; p.res = res_dev ? res_dev[j] : nullptr; p.y = y_dev ? y_dev[j] : nullptr;
-        p.wp = (const f32x4*)wb[j].p; p.bias = wb[j].p + boff[j];
-        p.ks = k[j]; p.dil = dil[j]; p.pad_left = dil[j] * (k[j] - 1) / 2;
+        p[j] = conv_problem(x_dev[j], wb[j].f32(), wb[j].f32() + boff, res_dev ? res_dev[j] : nullptr, y_dev ? y_dev[j] : nullptr,
+                            k[j], dil[j], wb16[j].f32());
     }
-    a.B = B; a.L_in = L; a.L_out = L; a.C_in = C; a.C_out = C; a.n_idx = L; a.in_act = IN_ACT_LRELU; a.slope = slope;
+    ConvLaunch a = conv_launch(p, nk, B, L, C, C, IN_ACT_LRELU, slope);
     if (mean_dev) {
-        // the summing step takes the branches reversed so that they are processed as resblock 0, 1, 2 (see forward)
-        std::swap(a.p[0], a.p[2]);
-        a.sum_y = mean_dev; a.sum_div = (float)nk;
+        to_summing(a, mean_dev, nk);
         for (int j = 0; j < nk; ++j) if (!a.p[j].y) a.p[j].y = mean_dev;     // never written; keeps descriptors valid
     }
     if (!mrf_kernel_applicable(a, nk)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "shape cannot take the MRF kernel");
@@ -1015,7 +1017,7 @@ int32_t iris_hifigan_op_mrf_pair(const float* const* x_dev, const float* const* 
     const int nk = 3;
     hipStream_t stream = (hipStream_t)stream_;
     DevBuf wb[3];
-    PairLaunchF32 pa; memset(&pa, 0, sizeof(pa));
+    PairProblemF32 p[3];
     for (int j = 0; j < nk; ++j) {
         if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j] || (!mean_dev && !y_dev[j]))
             return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
@@ -1027,13 +1029,12 @@ int32_t iris_hifigan_op_mrf_pair(const float* const* x_dev, const float* const* 
         memcpy(packed.data() + 2 * wf, b1_host[j], sizeof(float) * C);
         memcpy(packed.data() + 2 * wf + cpad, b2_host[j], sizeof(float) * C);
         HIP_TRY(wb[j].upload(packed));
-        PairProblemF32& p = pa.p[j];
-        p.x = x_dev[j]; p.y = mean_dev ? mean_dev : y_dev[j];      // (summing launch: the branch outputs are never written)
-        p.w1 = (const f32x4*)wb[j].p; p.w2 = (const f32x4*)(wb[j].p + wf);
-        p.b1 = wb[j].p + 2 * wf; p.b2 = wb[j].p + 2 * wf + cpad;
-        p.ks = k[j]; p.dil = dil[j];
+        const float* const w = wb[j].f32();
+        p[j] = PairProblemF32{x_dev[j], (const f32x4*)w, (const f32x4*)(w + wf), w + 2 * wf, w + 2 * wf + cpad,
+                              mean_dev ? mean_dev : y_dev[j],      // (summing launch: the branch outputs are never written)
+                              k[j], dil[j]};
     }
-    pa.B = B; pa.L = L; pa.C = C; pa.slope = slope;
+    PairLaunchF32 pa = pair_launch(p, nk, B, L, C, slope);
     if (!pair_f32_applicable(pa, nk)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "shape cannot take the fused fp32 pair kernel");
     if (mode == 1 || mode == 2) {
         if (!mean_dev) return fail(IRIS_HIFIGAN_UNSUPPORTED, "the persistent pair kernel exists in its summing form only (mean_dev)");
@@ -1166,16 +1167,12 @@ int postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int3
     for (int i = 0; i < h->num_layers; ++i) {
         const ConvLayer& l = h->layers[i];
         const bool last = i == h->num_layers - 1;
-        ConvLaunch a; init_launch(a);
-        a.p[0].x = x; a.p[0].wp = (const f32x4*)(h->blob + l.w_off); a.p[0].bias = h->blob + l.b_off;
-        a.p[0].res = nullptr; a.p[0].y = last ? res : hbuf[i & 1];
-        a.p[0].ks = l.k; a.p[0].dil = 1; a.p[0].pad_left = (l.k - 1) / 2;
-        a.B = B; a.L_in = T; a.L_out = T; a.C_in = l.C_in; a.C_out = l.C_out; a.n_idx = T;
-        a.in_act = IN_ACT_NONE; a.x_channels_first = i == 0 ? 1 : 0;   // the mel arrives [B, n_mels, T]
+        const ConvProblem p = conv_problem(x, h->blob + l.w_off, h->blob + l.b_off, nullptr, last ? res : hbuf[i & 1], l.k, 1);
+        ConvLaunch a = conv_launch(&p, 1, B, T, l.C_in, l.C_out, IN_ACT_NONE, 0.f, lengths, 1);
+        a.x_channels_first = i == 0 ? 1 : 0;                            // the mel arrives [B, n_mels, T]
         a.out_act = last ? 0 : 1;                                       // tanh (postnet.py:59)
-        a.lengths = lengths; a.row_scale = 1;
         HIP_TRY(launch_conv(a, 1, stream));
-        x = a.p[0].y;
+        x = p.y;
     }
     dim3 grid((unsigned)((T + 255) / 256), (unsigned)B), block(256);
     HIP_TRY(launch_kernel(postnet_residual_kernel, grid, block, 0, stream, (const float*)mel_dev, (const float*)res,

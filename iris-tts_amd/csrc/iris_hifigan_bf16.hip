@@ -18,32 +18,45 @@ using namespace b16;
 
 namespace {
 
-struct Ws16 {            // bf16 elements
-    size_t pre, up, y[IRIS_HIFIGAN_MAX_KERNELS], xt[IRIS_HIFIGAN_MAX_KERNELS], total;
-};
-
-Ws16 ws16_layout(const iris_hifigan_handle* h, int B, int T) {
-    Ws16 w;
-    const size_t frames = (size_t)B * T;
-    size_t per_frame_max = 0, L = 1;
-    for (const auto& st : h->stages) {
-        L *= st.rate;
-        const size_t e = L * st.C;
-        if (e > per_frame_max) per_frame_max = e;
-    }
-    size_t off = 0;
-    auto take = [&](size_t halfs) { size_t o = off; off += (halfs + 127) & ~(size_t)127; return o; };
-    w.pre = take(frames * h->pre.C_out);
-    w.up = take(frames * per_frame_max);
-    for (int j = 0; j < h->cfg.num_kernels; ++j) {
-        w.y[j] = take(frames * per_frame_max);
-        w.xt[j] = take(frames * per_frame_max);
-    }
-    w.total = off;
-    return w;
+// ---- launch descriptors: one builder per kind, shared by the forward and the single-layer entry points ----
+Problem conv_problem(const void* x, const void* w, const float* bias, const uint16_t* res, uint16_t* y, int k, int dil) {
+    Problem p; memset(&p, 0, sizeof(p));
+    p.x = x; p.wp = w; p.bias = bias; p.res = res; p.y = y;
+    p.ks = k; p.dil = dil; p.pad_left = dil * (k - 1) / 2;
+    return p;
 }
 
-void init_launch(Launch& a) { memset(&a, 0, sizeof(a)); a.out_stride = 1; }
+// nz 'same'-padding convs [B, L, C_in] -> [B, L, C_out] in one launch: a single layer, or one conv step of all MRF branches
+Launch conv_launch(const Problem* p, int nz, int B, int L, int C_in, int C_out, int in_act, float slope) {
+    Launch a; memset(&a, 0, sizeof(a));
+    for (int j = 0; j < nz; ++j) a.p[j] = p[j];
+    a.B = B; a.L_in = L; a.L_out = L; a.C_in = C_in; a.C_out = C_out; a.n_idx = L; a.out_stride = 1;
+    a.in_act = in_act; a.slope = slope;
+    return a;
+}
+
+// ConvTranspose1d [B, L, C_in] -> [B, L * u, C_out] of x[0] (in_act IN_ACT_NONE / IN_ACT_LRELU) or of LeakyReLU(mean of the
+// n_in branch outputs x[]) (IN_ACT_MRF_LRELU): the u phases as one grid; launch_convt_bf16 takes the GEMM kernel where it applies
+Launch convt_launch(const uint16_t* const* x, int n_in, int in_act, const void* w, const float* bias, uint16_t* y, int B, int L,
+                    int C_in, int C_out, int k, int u, float slope) {
+    const int taps = convt_taps(k, u);
+    Problem p = conv_problem(x[0], w, bias, nullptr, y, taps, 1);
+    p.pad_left = taps - 1;
+    Launch a = conv_launch(&p, 1, B, L, C_in, C_out, in_act, slope);
+    a.L_out = L * u; a.n_idx = L + taps - 1; a.out_stride = u; a.out_off = -(k - u) / 2;
+    a.z_is_phase = 1;
+    a.phase_wp_bytes = (unsigned)(packed_convt_phase_halfs(C_in, C_out, k, u) * 2);
+    if (in_act == IN_ACT_MRF_LRELU) { a.n_mrf = n_in; for (int j = 0; j < n_in; ++j) a.xmrf[j] = x[j]; }
+    return a;
+}
+
+// conv1 -> conv2 + residual of all branches in one launch (mrf_pair_bf16.h)
+PairLaunch pair_launch(const PairProblem* p, int nz, int B, int L, int C, float slope) {
+    PairLaunch pa; memset(&pa, 0, sizeof(pa));
+    for (int j = 0; j < nz && j < kMaxGroup; ++j) pa.p[j] = p[j];
+    pa.B = B; pa.L = L; pa.C = C; pa.slope = slope;
+    return pa;
+}
 
 }  // namespace
 
@@ -157,18 +170,6 @@ void fill_ups(s3::Launch& a, const ConvLayer& l, const float* x, const void* wp,
 }
 }  // namespace
 
-uint64_t bf16_workspace_bytes(const iris_hifigan_handle* h, int B, int T) {
-    return ws16_layout(h, B, T).total * sizeof(uint16_t);
-}
-
-int bf16_workspace_map(const iris_hifigan_handle* h, int B, int T, iris_hifigan_workspace_map* out) {
-    const Ws16 w = ws16_layout(h, B, T);
-    out->element_bytes = 2;
-    out->pre_offset = w.pre * 2; out->up_offset = w.up * 2; out->total_bytes = w.total * 2;
-    for (int j = 0; j < h->cfg.num_kernels; ++j) { out->y_offset[j] = w.y[j] * 2; out->xt_offset[j] = w.xt[j] * 2; }
-    return IRIS_HIFIGAN_OK;
-}
-
 int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void* wav_dev,
                  void* workspace_dev, uint64_t workspace_bytes, hipStream_t stream, const ForwardStop& stop,
                  int32_t* until_flags) {
@@ -181,10 +182,10 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
             return fail(IRIS_HIFIGAN_UNSUPPORTED, "bf16 path: %d frames make a single item's activations 2^31 bytes or more; "
                         "split the utterance (iris.streaming) or use fp32", T);
     }
-    const Ws16 w = ws16_layout(h, B, T);
-    if (workspace_bytes < w.total * sizeof(uint16_t))
+    const WsLayout w = ws_layout(h, B, T, IRIS_HIFIGAN_BF16);
+    if (workspace_bytes < w.bytes())
         return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)(w.total * sizeof(uint16_t)));
+                    (unsigned long long)workspace_bytes, (unsigned long long)w.bytes());
     uint16_t* ws = (uint16_t*)workspace_dev;
     const uint16_t* wb = h->blob16;
     const float* blob = h->blob;
@@ -195,13 +196,10 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
 
     // ---- conv_pre (hifigan_pretrained.py:124): fp32 mel in, bf16 out ----
     {
-        Launch a; init_launch(a);
         const ConvLayer& l = h->pre;
-        a.p[0].x = mel_dev; a.p[0].wp = wb + l.w16_off; a.p[0].bias = blob + l.b_off;
-        a.p[0].res = nullptr; a.p[0].y = ws + w.pre;
-        a.p[0].ks = l.k; a.p[0].dil = 1; a.p[0].pad_left = (l.k - 1) / 2;
-        a.B = B; a.L_in = T; a.L_out = T; a.C_in = l.C_in; a.C_out = l.C_out; a.n_idx = T;
-        a.in_act = IN_ACT_NONE; a.x_f32_cf = 1; a.slope = slope;
+        const Problem p = conv_problem(mel_dev, wb + l.w16_off, blob + l.b_off, nullptr, ws + w.pre, l.k, 1);
+        Launch a = conv_launch(&p, 1, B, T, l.C_in, l.C_out, IN_ACT_NONE, slope);
+        a.x_f32_cf = 1;
         TRY(prof.begin(0, -1, 0, 2.0 * fB * T * l.C_in * l.C_out * l.k,
                        fB * T * (4.0 * l.C_in + 2.0 * l.C_out) + 2.0 * (double)l.ref_w_floats + 4.0 * l.C_out));
         HIP_TRY(launch_conv_bf16(a, 1, stream));
@@ -220,25 +218,13 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
         const int L_out = L * st.rate;
         // ---- LeakyReLU + ConvTranspose1d (hifigan_pretrained.py:127-128) ----
         {
-            Launch a; init_launch(a);
             const ConvLayer& l = st.up;
-            const int taps = convt_taps(l.k, l.u);
-            a.p[0].wp = wb + l.w16_off; a.p[0].bias = blob + l.b_off;
-            a.p[0].res = nullptr; a.p[0].y = ws + w.up;
-            a.p[0].ks = taps; a.p[0].dil = 1; a.p[0].pad_left = taps - 1;
             const int n_in = i == 0 ? 1 : nk;       // (accounting L counts the reference's three branch tensors whatever was fused)
-            if (i == 0) { a.p[0].x = ws + w.pre; a.in_act = IN_ACT_LRELU; }
-            else if (mean16) { a.p[0].x = mean16; a.in_act = IN_ACT_NONE; }      // already activated and rounded
-            else {
-                a.in_act = IN_ACT_MRF_LRELU; a.n_mrf = nk;
-                for (int j = 0; j < nk; ++j) a.xmrf[j] = cur[j];
-                a.p[0].x = a.xmrf[0];
-            }
-            a.B = B; a.L_in = L; a.L_out = L_out; a.C_in = l.C_in; a.C_out = l.C_out;
-            a.n_idx = L + taps - 1; a.out_stride = l.u; a.out_off = -(l.k - l.u) / 2;
-            a.z_is_phase = 1;
-            a.phase_wp_bytes = (unsigned)(packed_convt_phase_halfs(l.C_in, l.C_out, l.k, l.u) * 2);
-            a.slope = slope;
+            const uint16_t* const one = i == 0 ? ws + w.pre : mean16;
+            const bool mrf = i > 0 && !mean16;
+            // (the summing pair's mean16 is already activated and rounded)
+            Launch a = convt_launch(mrf ? cur : &one, nk, mrf ? IN_ACT_MRF_LRELU : (i == 0 ? IN_ACT_LRELU : IN_ACT_NONE),
+                                    wb + l.w16_off, blob + l.b_off, ws + w.up, B, L, l.C_in, l.C_out, l.k, l.u, slope);
             TRY(prof.begin(1, (int)i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
                            2.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out + (double)l.ref_w_floats) + 4.0 * l.C_out));
             HIP_TRY(launch_convt_bf16(a, l.k, l.u, stream));      // one GEMM launch (convt_mfma_bf16.h) where it applies
@@ -259,21 +245,17 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
             // carries the index of the pair's second step.  (forward_until asking for the state after conv1 gets the
             // two separate launches for that pair.)
             {
-                PairLaunch pa; memset(&pa, 0, sizeof(pa));
+                PairProblem pp[kMaxGroup];
                 double flops = 0, wbytes = 0;
                 for (int j = 0; j < nk && j < kMaxGroup; ++j) {
                     const ConvLayer& l1 = st.c1[j][m];
                     const ConvLayer& l2 = st.c2[j][m];
-                    PairProblem& p = pa.p[j];
-                    p.x = cur[j];
-                    p.y = (cur[j] == ws + w.y[j]) ? ws + w.xt[j] : ws + w.y[j];
-                    p.w1 = wb + l1.w16_off; p.b1 = blob + l1.b_off;
-                    p.w2 = wb + l2.w16_off; p.b2 = blob + l2.b_off;
-                    p.ks = l1.k; p.dil = l1.dil;
+                    pp[j] = PairProblem{cur[j], wb + l1.w16_off, wb + l2.w16_off, blob + l1.b_off, blob + l2.b_off,
+                                        (cur[j] == ws + w.y[j]) ? ws + w.xt[j] : ws + w.y[j], l1.k, l1.dil};
                     flops += 2.0 * n_el * (l1.C_in * l1.k + l2.C_in * l2.k);
                     wbytes += 2.0 * (double)(l1.ref_w_floats + l2.ref_w_floats) + 4.0 * (l1.C_out + l2.C_out);
                 }
-                pa.B = B; pa.L = L_out; pa.C = st.C; pa.slope = slope;
+                PairLaunch pa = pair_launch(pp, nk, B, L_out, st.C, slope);
                 const bool want_xt = stop.stage == (int)i && stop.step == 2 * m;
                 bool same_k = true;
                 for (int j = 0; j < nk; ++j) same_k = same_k && st.c1[j][m].k == st.c2[j][m].k && st.c2[j][m].dil == 1;
@@ -312,24 +294,20 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
                 }
             }
             for (int half = 0; half < 2; ++half) {
-                Launch a; init_launch(a);
+                Problem p[kMaxGroup];
                 double flops = 0, wbytes = 0;
                 for (int j = 0; j < nk; ++j) {
                     const ConvLayer& l = half == 0 ? st.c1[j][m] : st.c2[j][m];
-                    Problem& p = a.p[j];
                     // x entering this pair is cur[j]; conv1 writes the branch's other buffer, conv2 (own rows only:
                     // in place is safe) writes back to cur[j], or to y[j] when cur[j] is the shared upsample output
                     uint16_t* tmp = (cur[j] == ws + w.xt[j]) ? ws + w.y[j] : ws + w.xt[j];
                     uint16_t* dst = (cur[j] == ws + w.up) ? ws + w.y[j] : const_cast<uint16_t*>(cur[j]);
-                    if (half == 0) { p.x = cur[j]; p.res = nullptr; p.y = tmp; }
-                    else           { p.x = tmp; p.res = cur[j]; p.y = dst; }
-                    p.wp = wb + l.w16_off; p.bias = blob + l.b_off;
-                    p.ks = l.k; p.dil = l.dil; p.pad_left = l.dil * (l.k - 1) / 2;
+                    p[j] = half == 0 ? conv_problem(cur[j], wb + l.w16_off, blob + l.b_off, nullptr, tmp, l.k, l.dil)
+                                     : conv_problem(tmp, wb + l.w16_off, blob + l.b_off, cur[j], dst, l.k, l.dil);
                     flops += 2.0 * n_el * l.C_in * l.k;
                     wbytes += 2.0 * (double)l.ref_w_floats + 4.0 * l.C_out;
                 }
-                a.B = B; a.L_in = L_out; a.L_out = L_out; a.C_in = st.C; a.C_out = st.C;
-                a.n_idx = L_out; a.in_act = IN_ACT_LRELU; a.slope = slope;
+                Launch a = conv_launch(p, nk, B, L_out, st.C, st.C, IN_ACT_LRELU, slope);
                 TRY(prof.begin(2, (int)i, 2 * m + half, flops, 2.0 * n_el * nk * (half == 0 ? 2 : 3) + wbytes));
                 HIP_TRY(launch_conv_bf16(a, nk, stream));
                 TRY(prof.end());
@@ -383,15 +361,22 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
 // single-layer entry points (parity tests of the bf16 kernel)
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct DevBytes {
-    void* p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-    hipError_t upload(const void* src, size_t bytes) {
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    }
-};
+using namespace iris;
+using namespace iris::b16;
+
+// Packs and uploads one branch's pair weights (the two pair entry points) and points `p` at them.
+struct PairWeights { DevBuf w1, w2, b1, b2; };
+int upload_pair_weights(PairWeights& d, PairProblem& p, const float* w1, const float* b1, const float* w2, const float* b2, int C) {
+    std::vector<uint16_t> packed(packed_conv1d_halfs(C, C, p.ks));
+    pack_conv1d_bf16(w1, C, C, p.ks, packed.data());
+    HIP_TRY(d.w1.upload(packed));
+    pack_conv1d_bf16(w2, C, C, p.ks, packed.data());
+    HIP_TRY(d.w2.upload(packed));
+    HIP_TRY(d.b1.upload(b1, sizeof(float) * C));
+    HIP_TRY(d.b2.upload(b2, sizeof(float) * C));
+    p.w1 = d.w1.p; p.w2 = d.w2.p; p.b1 = d.b1.f32(); p.b2 = d.b2.f32();
+    return IRIS_HIFIGAN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -401,8 +386,6 @@ int32_t iris_hifigan_op_conv1d_bf16(const void* x_dev, const float* w_host, cons
                                     int32_t C_out, int32_t k, int32_t dilation, int32_t in_act, float slope,
                                     void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
-    using namespace iris::b16;
     if (!x_dev || !w_host || !bias_host || !y_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 1 || L < 1 || C_in < 1 || C_out < 1 || k < 1 || !(k & 1) || dilation < 1 || B > 65535)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad conv1d shape");
@@ -411,14 +394,11 @@ int32_t iris_hifigan_op_conv1d_bf16(const void* x_dev, const float* w_host, cons
     hipStream_t stream = (hipStream_t)stream_;
     std::vector<uint16_t> packed(packed_conv1d_halfs(C_in, C_out, k));
     pack_conv1d_bf16(w_host, C_in, C_out, k, packed.data());
-    DevBytes wb, bb;
-    HIP_TRY(wb.upload(packed.data(), packed.size() * sizeof(uint16_t)));
+    DevBuf wb, bb;
+    HIP_TRY(wb.upload(packed));
     HIP_TRY(bb.upload(bias_host, sizeof(float) * C_out));
-    Launch a; memset(&a, 0, sizeof(a)); a.out_stride = 1;
-    a.p[0].x = x_dev; a.p[0].wp = wb.p; a.p[0].bias = (const float*)bb.p; a.p[0].res = (const uint16_t*)res_dev;
-    a.p[0].y = (uint16_t*)y_dev; a.p[0].ks = k; a.p[0].dil = dilation; a.p[0].pad_left = dilation * (k - 1) / 2;
-    a.B = B; a.L_in = L; a.L_out = L; a.C_in = C_in; a.C_out = C_out; a.n_idx = L;
-    a.in_act = in_act ? IN_ACT_LRELU : IN_ACT_NONE; a.slope = slope;
+    const Problem p = conv_problem(x_dev, wb.p, bb.f32(), (const uint16_t*)res_dev, (uint16_t*)y_dev, k, dilation);
+    Launch a = conv_launch(&p, 1, B, L, C_in, C_out, in_act ? IN_ACT_LRELU : IN_ACT_NONE, slope);
     HIP_TRY(launch_conv_bf16(a, 1, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
@@ -430,36 +410,23 @@ int32_t iris_hifigan_op_mrf_pair_bf16(const void* const* x_dev, const float* con
                                       int32_t n_branches, int32_t B, int32_t L, int32_t C, const int32_t* k, const int32_t* dil,
                                       float slope, void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
-    using namespace iris::b16;
     if (!x_dev || !w1_host || !b1_host || !w2_host || !b2_host || !y_dev || !k || !dil)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (n_branches < 1 || n_branches > kMaxGroup || B < 1 || L < 1 || C < 1 || B > 65535)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad mrf_pair shape");
     hipStream_t stream = (hipStream_t)stream_;
-    PairLaunch a; memset(&a, 0, sizeof(a));
-    DevBytes w1b[kMaxGroup], w2b[kMaxGroup], b1b[kMaxGroup], b2b[kMaxGroup];
+    PairProblem p[kMaxGroup];
     for (int j = 0; j < n_branches; ++j) {
         if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j] || !y_dev[j])
             return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
         if (k[j] < 1 || !(k[j] & 1) || dil[j] < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad kernel size / dilation");
-        a.p[j].ks = k[j]; a.p[j].dil = dil[j];
+        p[j] = PairProblem{(const uint16_t*)x_dev[j], nullptr, nullptr, nullptr, nullptr, (uint16_t*)y_dev[j], k[j], dil[j]};
     }
-    a.B = B; a.L = L; a.C = C; a.slope = slope;
+    PairLaunch a = pair_launch(p, n_branches, B, L, C, slope);
     if (!pair_applicable(a, n_branches))
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the fused pair kernel takes C = 32, 64 or 128 and windows up to 64 KB");
-    for (int j = 0; j < n_branches; ++j) {
-        std::vector<uint16_t> packed(packed_conv1d_halfs(C, C, k[j]));
-        pack_conv1d_bf16(w1_host[j], C, C, k[j], packed.data());
-        HIP_TRY(w1b[j].upload(packed.data(), packed.size() * sizeof(uint16_t)));
-        pack_conv1d_bf16(w2_host[j], C, C, k[j], packed.data());
-        HIP_TRY(w2b[j].upload(packed.data(), packed.size() * sizeof(uint16_t)));
-        HIP_TRY(b1b[j].upload(b1_host[j], sizeof(float) * C));
-        HIP_TRY(b2b[j].upload(b2_host[j], sizeof(float) * C));
-        a.p[j].x = (const uint16_t*)x_dev[j]; a.p[j].y = (uint16_t*)y_dev[j];
-        a.p[j].w1 = w1b[j].p; a.p[j].w2 = w2b[j].p;
-        a.p[j].b1 = (const float*)b1b[j].p; a.p[j].b2 = (const float*)b2b[j].p;
-    }
+    PairWeights wts[kMaxGroup];
+    for (int j = 0; j < n_branches; ++j) TRY(upload_pair_weights(wts[j], a.p[j], w1_host[j], b1_host[j], w2_host[j], b2_host[j], C));
     HIP_TRY(launch_pair_bf16(a, n_branches, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
@@ -471,37 +438,24 @@ int32_t iris_hifigan_op_mrf_pair_mean_bf16(const void* const* x_dev, const float
                                            int32_t mean_f32, int32_t B, int32_t L, int32_t C, const int32_t* k, const int32_t* dil,
                                            float slope, void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
-    using namespace iris::b16;
     if (!x_dev || !w1_host || !b1_host || !w2_host || !b2_host || !mean_dev || !k || !dil)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 1 || L < 1 || C < 1 || B > 65535) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad mrf_pair shape");
     const int nz = 3;
     hipStream_t stream = (hipStream_t)stream_;
-    PairLaunch a; memset(&a, 0, sizeof(a));
-    DevBytes w1b[kMaxGroup], w2b[kMaxGroup], b1b[kMaxGroup], b2b[kMaxGroup];
+    PairProblem p[kMaxGroup];
     for (int j = 0; j < nz; ++j) {
         if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j])
             return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
         if (k[j] < 1 || !(k[j] & 1) || dil[j] < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad kernel size / dilation");
         if (x_dev[j] == mean_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "the mean must not overwrite an input");
-        a.p[j].ks = k[j]; a.p[j].dil = dil[j];
+        p[j] = PairProblem{(const uint16_t*)x_dev[j], nullptr, nullptr, nullptr, nullptr, nullptr, k[j], dil[j]};
     }
-    a.B = B; a.L = L; a.C = C; a.slope = slope;
+    PairLaunch a = pair_launch(p, nz, B, L, C, slope);
     if (!pair_sum_applicable(a, nz, mean_f32 != 0))
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the summing pair kernel takes C = 32 or 64, three branches and windows up to 64 KB");
-    for (int j = 0; j < nz; ++j) {
-        std::vector<uint16_t> packed(packed_conv1d_halfs(C, C, k[j]));
-        pack_conv1d_bf16(w1_host[j], C, C, k[j], packed.data());
-        HIP_TRY(w1b[j].upload(packed.data(), packed.size() * sizeof(uint16_t)));
-        pack_conv1d_bf16(w2_host[j], C, C, k[j], packed.data());
-        HIP_TRY(w2b[j].upload(packed.data(), packed.size() * sizeof(uint16_t)));
-        HIP_TRY(b1b[j].upload(b1_host[j], sizeof(float) * C));
-        HIP_TRY(b2b[j].upload(b2_host[j], sizeof(float) * C));
-        a.p[j].x = (const uint16_t*)x_dev[j]; a.p[j].y = nullptr;
-        a.p[j].w1 = w1b[j].p; a.p[j].w2 = w2b[j].p;
-        a.p[j].b1 = (const float*)b1b[j].p; a.p[j].b2 = (const float*)b2b[j].p;
-    }
+    PairWeights wts[kMaxGroup];
+    for (int j = 0; j < nz; ++j) TRY(upload_pair_weights(wts[j], a.p[j], w1_host[j], b1_host[j], w2_host[j], b2_host[j], C));
     HIP_TRY(launch_pair_bf16_sum(a, mean_dev, mean_f32 != 0, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
@@ -512,7 +466,6 @@ int32_t iris_hifigan_op_conv1d_f32s(const float* x_dev, const float* w_host, con
                                     float* y_dev, int32_t B, int32_t L, int32_t C, int32_t k, int32_t dilation, float slope,
                                     void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
     if (!x_dev || !w_host || !bias_host || !y_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 1 || L < 1 || C < 1 || k < 1 || !(k & 1) || dilation < 1 || B > 65535)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad conv1d shape");
@@ -522,10 +475,10 @@ int32_t iris_hifigan_op_conv1d_f32s(const float* x_dev, const float* w_host, con
     hipStream_t stream = (hipStream_t)stream_;
     std::vector<uint16_t> packed(2 * s3::packed_plane_halfs(C, C, k));
     s3::pack_conv1d_split(w_host, C, C, k, packed.data());
-    DevBytes wb, bb;
-    HIP_TRY(wb.upload(packed.data(), packed.size() * sizeof(uint16_t)));
+    DevBuf wb, bb;
+    HIP_TRY(wb.upload(packed));
     HIP_TRY(bb.upload(bias_host, sizeof(float) * C));
-    a.p[0].x = x_dev; a.p[0].wp = wb.p; a.p[0].bias = (const float*)bb.p; a.p[0].res = res_dev; a.p[0].y = y_dev;
+    a.p[0].x = x_dev; a.p[0].wp = wb.p; a.p[0].bias = bb.f32(); a.p[0].res = res_dev; a.p[0].y = y_dev;
     a.p[0].ks = k; a.p[0].dil = dilation; a.p[0].pad_left = dilation * (k - 1) / 2;
     HIP_TRY(s3::launch(a, 1, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -537,7 +490,6 @@ int32_t iris_hifigan_op_conv_transpose1d_f32s(const float* x_dev, const float* w
                                               int32_t B, int32_t L, int32_t C_in, int32_t C_out, int32_t k, int32_t u,
                                               float slope, void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
     if (!x_dev || !w_host || !bias_host || !y_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 1 || L < 1 || C_in < 1 || C_out < 1 || u < 1 || k < u || ((k - u) & 1) || B > 65535 || u > 65535)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad conv_transpose1d shape");
@@ -548,10 +500,10 @@ int32_t iris_hifigan_op_conv_transpose1d_f32s(const float* x_dev, const float* w
     hipStream_t stream = (hipStream_t)stream_;
     std::vector<uint16_t> packed(2 * s3::packed_convt_plane_halfs(C_in, C_out, k, u));
     s3::pack_convt_split(w_host, C_in, C_out, k, u, packed.data());
-    DevBytes wb, bb;
-    HIP_TRY(wb.upload(packed.data(), packed.size() * sizeof(uint16_t)));
+    DevBuf wb, bb;
+    HIP_TRY(wb.upload(packed));
     HIP_TRY(bb.upload(bias_host, sizeof(float) * C_out));
-    fill_ups(a, l, x_dev, wb.p, (const float*)bb.p, y_dev, B, L, slope);
+    fill_ups(a, l, x_dev, wb.p, bb.f32(), y_dev, B, L, slope);
     HIP_TRY(s3::launch(a, u, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
@@ -562,8 +514,6 @@ int32_t iris_hifigan_op_conv_transpose1d_bf16(const void* x_dev, const float* w_
                                               void* y_dev, int32_t B, int32_t L, int32_t C_in, int32_t C_out,
                                               int32_t k, int32_t u, int32_t in_act, float slope, void* stream_) {
     IRIS_ABI_BEGIN
-    using namespace iris;
-    using namespace iris::b16;
     if (!x_dev || !w_host || !bias_host || !y_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 1 || L < 1 || C_in < 1 || C_out < 1 || u < 1 || k < u || ((k - u) & 1) || B > 65535 || u > 65535)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad conv_transpose1d shape");
@@ -573,17 +523,11 @@ int32_t iris_hifigan_op_conv_transpose1d_bf16(const void* x_dev, const float* w_
     const size_t phase_halfs = packed_convt_phase_halfs(C_in, C_out, k, u);
     std::vector<uint16_t> packed(phase_halfs * u);
     pack_convt_bf16(w_host, C_in, C_out, k, u, packed.data());
-    DevBytes wb, bb;
-    HIP_TRY(wb.upload(packed.data(), packed.size() * sizeof(uint16_t)));
+    DevBuf wb, bb;
+    HIP_TRY(wb.upload(packed));
     HIP_TRY(bb.upload(bias_host, sizeof(float) * C_out));
-    const int taps = convt_taps(k, u);
-    Launch a; memset(&a, 0, sizeof(a));
-    a.p[0].x = x_dev; a.p[0].wp = wb.p; a.p[0].bias = (const float*)bb.p; a.p[0].res = nullptr;
-    a.p[0].y = (uint16_t*)y_dev; a.p[0].ks = taps; a.p[0].dil = 1; a.p[0].pad_left = taps - 1;
-    a.B = B; a.L_in = L; a.L_out = L * u; a.C_in = C_in; a.C_out = C_out; a.n_idx = L + taps - 1;
-    a.out_stride = u; a.out_off = -(k - u) / 2; a.z_is_phase = 1;
-    a.phase_wp_bytes = (unsigned)(phase_halfs * 2);
-    a.in_act = in_act ? IN_ACT_LRELU : IN_ACT_NONE; a.slope = slope;
+    const uint16_t* const x = (const uint16_t*)x_dev;
+    Launch a = convt_launch(&x, 1, in_act ? IN_ACT_LRELU : IN_ACT_NONE, wb.p, bb.f32(), (uint16_t*)y_dev, B, L, C_in, C_out, k, u, slope);
     HIP_TRY(launch_convt_bf16(a, k, u, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
