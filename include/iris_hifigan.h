@@ -34,7 +34,8 @@
  * Activations inside the library are channels-last [B, L, C], fp32 (bf16 with dtype
  * IRIS_HIFIGAN_BF16); the mel comes in as the
  * reference hands it over, channels-first [B, n_mels, T] (hifigan_pretrained.py:228), and the
- * waveform goes out as [B, prod(upsample_rates) * T] (hifigan_pretrained.py:235-236).
+ * waveform goes out as [B, prod(upsample_rates) * T] (hifigan_pretrained.py:235-236) -- fp32, or 16-bit PCM
+ * (iris_hifigan_forward_pcm16).
  */
 #ifndef IRIS_HIFIGAN_H
 #define IRIS_HIFIGAN_H
@@ -163,6 +164,33 @@ int32_t iris_hifigan_forward_ragged(iris_hifigan_handle* h, const void* mel_dev,
                                     const int32_t* lengths_dev, void* wav_dev, void* workspace_dev,
                                     uint64_t workspace_bytes, int32_t dtype, void* stream);
 
+/* The forward with the output stage on the device: 16-bit PCM, optionally peak-normalised per item.  What a caller of the
+ * reference does with the fp32 waveform on the host (scripts/synthesize.py writes a 16-bit WAV; demo_vocoder.py first
+ * scales to 0.95 / (max|w| + 1e-8)) happens in the forward's last launch instead, so half the bytes cross to the host.
+ *   normalize == 0:  pcm[b, i] = (int16) rintf(clamp(w, -1, 1) * 32767), w the sample iris_hifigan_forward would store
+ *                    -- bit for bit numpy's round(clip(w, -1, 1) * 32767) (half to even); conv_post stores it in place of
+ *                    the waveform.  wav_dev, peak_dev and peak_target are ignored (may be NULL).
+ *   normalize != 0:  q = (w / (peak[b] + 1e-8f)) * peak_target, pcm = (int16) rintf(clamp(q, -1, 1) * 32767), every
+ *                    operation its own fp32 rounding, the division correctly rounded; peak[b] = max |w| over the item's
+ *                    own samples.  Afterwards wav_dev [B, hop*T] holds the fp32 waveform, bit for bit
+ *                    iris_hifigan_forward's (iris_hifigan_forward_ragged's with lengths), and peak_dev [B] the per-item
+ *                    peaks (0 for an empty or silent item, whose PCM is 0).  conv_post reduces the peaks beside its store
+ *                    (one vector atomic max per block; deterministic) and a second kernel converts.  NULL wav_dev or
+ *                    peak_dev, or peak_target outside (0, 1], returns IRIS_HIFIGAN_INVALID_ARGUMENT.
+ * lengths_dev: NULL = a plain batch (every dtype); else [B] int32 on the device as in iris_hifigan_forward_ragged --
+ * IRIS_HIFIGAN_F32 only (others return IRIS_HIFIGAN_UNSUPPORTED); pcm[b, hop*lengths[b]:] is 0 and the item's peak covers
+ * its own samples only.  B == 0 or T == 0 returns IRIS_HIFIGAN_OK.
+ * Workspace as iris_hifigan_workspace_bytes(B, T, dtype); same stream, allocation, synchronisation and capture rules as
+ * iris_hifigan_forward (a normalising call also queues one memset of its peaks per pass).  Batches above 65,536 frames run
+ * as passes; every buffer advances per pass. */
+int32_t iris_hifigan_forward_pcm16(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                   const int32_t* lengths_dev /* NULL = plain batch */,
+                                   int16_t* pcm_dev           /* [B, hop*T] */,
+                                   float* wav_dev             /* [B, hop*T]; required iff normalize, else may be NULL */,
+                                   float* peak_dev            /* [B]; required iff normalize, else may be NULL */,
+                                   int32_t normalize, float peak_target,
+                                   void* workspace_dev, uint64_t workspace_bytes, int32_t dtype, void* stream);
+
 /* ---- intermediates (parity tests of the layers inside a forward; not needed by a caller) ----
  * forward_until queues the same launches as forward up to and including MRF step `stop_step`
  * (0 .. 2*num_dilations-1: even = convs1[m], odd = convs2[m] + residual, hifigan_pretrained.py:64-71) of
@@ -247,6 +275,14 @@ int32_t iris_hifigan_op_conv_post(const float* x0_dev, const float* x1_dev, cons
                                   const float* w_host, const float* bias_host, float* y_dev,
                                   int32_t B, int32_t L, int32_t C_in, int32_t k, float slope,
                                   void* stream);
+
+/* The stand-alone half of the output stage on its own (csrc/pcm_out.h): fp32 wav_dev [B, L] -> int16 pcm_dev [B, L] by the
+ * formulas of iris_hifigan_forward_pcm16.  normalize != 0 first reduces peak_dev [B] (written; may be NULL otherwise) from
+ * wav_dev.  lengths_dev (may be NULL) and row_scale >= 1: item b has min(L, lengths[b] * row_scale) samples; the rest of
+ * its PCM is 0 and does not count towards its peak.  Items need no alignment (odd L is fine). */
+int32_t iris_hifigan_op_pcm16(const float* wav_dev, const int32_t* lengths_dev, int32_t row_scale,
+                              int16_t* pcm_dev, float* peak_dev, int32_t B, int32_t L,
+                              int32_t normalize, float peak_target, void* stream);
 
 /* One grouped MRF step of the fp32 path -- the hot kernel -- on its own: the three ResBlock branches
  * (kernel sizes k[j] = 3, 7, 11; hifigan_pretrained.py:64-71,130-136) each run

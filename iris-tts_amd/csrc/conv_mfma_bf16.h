@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include "pcm_out.h"
 
 namespace iris {
 namespace b16 {
@@ -431,13 +432,16 @@ struct PostLaunch {
     int n_in;
     const float* w;                // [k][C] fp32
     const float* bias;             // [1]
-    float* y;                      // [B, L] fp32
+    float* y;                      // [B, L] fp32 waveform (pcm_out.h: OUT_F32, OUT_F32_PEAK)
+    int16_t* pcm;                  // [B, L] 16-bit PCM (OUT_PCM16)
+    unsigned* peak;                // [B] bit pattern of max |y[b, :]|, zeroed by the caller (OUT_F32_PEAK)
     int B, L, C, k;
     float slope, inv_n;
 };
 
 constexpr int kPostTile = 256;
 
+template <int OUT>      // output form (pcm_out.h); OUT_F32 is the plain forward's
 __global__ void __launch_bounds__(256) conv_post_tanh_bf16_kernel(const PostLaunch a) {
     extern __shared__ __attribute__((aligned(16))) char lds_b16[];
     float* lds = reinterpret_cast<float*>(lds_b16);
@@ -470,22 +474,35 @@ __global__ void __launch_bounds__(256) conv_post_tanh_bf16_kernel(const PostLaun
     }
     __syncthreads();
     const int t = t0 + threadIdx.x;
-    if (t >= a.L) return;
-    const float* __restrict__ w = a.w;
-    float acc = a.bias[0];
-    for (int kap = 0; kap < k; ++kap) {
-        const float* row = lds + (threadIdx.x + kap) * S;
-        for (int c = 0; c < C; ++c) acc = fmaf(row[c], w[kap * C + c], acc);
+    constexpr bool PEAK = OUT == pcm::OUT_F32_PEAK;      // every thread stays for the block's peak; one without a sample adds 0
+    if constexpr (!PEAK) {
+        if (t >= a.L) return;
     }
-    a.y[(size_t)b * a.L + t] = tanhf(acc);
+    float wv = 0.f;
+    if (!PEAK || t < a.L) {
+        const float* __restrict__ w = a.w;
+        float acc = a.bias[0];
+        for (int kap = 0; kap < k; ++kap) {
+            const float* row = lds + (threadIdx.x + kap) * S;
+            for (int c = 0; c < C; ++c) acc = fmaf(row[c], w[kap * C + c], acc);
+        }
+        wv = tanhf(acc);
+    }
+    if constexpr (PEAK) {
+        if (t < a.L) a.y[(size_t)b * a.L + t] = wv;
+        pcm::block_peak_max(pcm::abs_bits(wv), a.peak + b);
+    } else {
+        pcm::store_sample<OUT>(a, (size_t)b * a.L + t, wv);
+    }
 }
 
 inline hipError_t launch_conv_post_bf16(const PostLaunch& a, hipStream_t stream) {
     const size_t lds_bytes = (size_t)(kPostTile + a.k - 1) * (a.C | 1) * sizeof(float);
     if (lds_bytes > 160 * 1024 || (a.C & 7)) return hipErrorInvalidValue;
     dim3 grid((unsigned)((a.L + kPostTile - 1) / kPostTile), (unsigned)a.B), block(256);
-    { const hipError_t e__ = ::iris::launch_kernel(conv_post_tanh_bf16_kernel, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; }
-    return hipSuccess;       
+    auto kfn = a.pcm ? conv_post_tanh_bf16_kernel<pcm::OUT_PCM16>
+                     : (a.peak ? conv_post_tanh_bf16_kernel<pcm::OUT_F32_PEAK> : conv_post_tanh_bf16_kernel<pcm::OUT_F32>);
+    return ::iris::launch_kernel_named("conv_post_tanh_bf16_kernel", kfn, grid, block, lds_bytes, stream, a);
 }
 
 // ---- host side: weight packing ---------------------------------------------------------------------

@@ -15,10 +15,13 @@
 //   conv_post_tanh_kernel              any C (scalar staging): the fallback for generic configurations.
 // Both accumulate in the same order (bias, then taps ascending, channels ascending: one fmaf chain),
 // so they produce identical bits.  Weights are wave-uniform and come through the scalar cache.
+// Output form (template parameter OUT, pcm_out.h): the fp32 waveform (the plain forward), int16 PCM in its place, or the
+// fp32 waveform plus the item's peak |w| for the normalising pass.  OUT_F32 is the kernel the plain forward always had.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "device_info.h"
+#include "pcm_out.h"
 
 namespace iris {
 namespace post {      // self-contained: included by the fp32 and the bf16 translation unit
@@ -33,14 +36,16 @@ struct ConvPostLaunch {
     int n_in;
     const float* w;             // [k][C]  (w_ref[0][ci][kap] transposed)
     const float* bias;          // [1]
-    float* y;                   // [B, L]
+    float* y;                   // [B, L] fp32 waveform (OUT_F32, OUT_F32_PEAK)
+    int16_t* pcm;               // [B, L] 16-bit PCM (OUT_PCM16)
+    unsigned* peak;             // [B] bit pattern of max |y[b, :]|, zeroed by the caller (OUT_F32_PEAK)
     int B, L, C, k;
     float slope;
     float inv_n;                // bf16 path: 1 / n_in
     int tiles_per_item;         // rows kernel: ceil(L / kPostTile)
     const int32_t* lengths;     // ragged forward (fp32): mel frames of each batch item [B] (device), or nullptr
     int row_scale;              // samples per mel frame (hop): item b has ragged_rows(lengths, b, row_scale, L) samples; the
-                                // rest of its row of y is written as 0
+                                // rest of its row of y / pcm is written as 0
 };
 
 constexpr int kPostTile = 256;
@@ -57,7 +62,7 @@ __device__ __forceinline__ float bf_hi(unsigned w) { return __builtin_bit_cast(f
 constexpr unsigned kOob = 0x80000000u;
 }  // namespace detail
 
-template <int C, bool BF16_IN>
+template <int C, bool BF16_IN, int OUT = pcm::OUT_F32>
 __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunch a) {
     using namespace detail;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -75,7 +80,7 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunc
     const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);
     if (t0 >= Lb) {
         const int t = t0 + (int)threadIdx.x;
-        if (t < a.L) a.y[(size_t)b * a.L + t] = 0.f;
+        if (t < a.L) pcm::store_sample<OUT>(a, (size_t)b * a.L + t, 0.f);
         return;
     }
     const unsigned tensor_bytes = (unsigned)a.L * (unsigned)(C * ESZ);
@@ -140,24 +145,36 @@ __global__ void __launch_bounds__(256) conv_post_rows_kernel(const ConvPostLaunc
     }
     __syncthreads();
     const int t = t0 + (int)threadIdx.x;
-    if (t >= a.L) return;
-    if (t >= Lb) { a.y[(size_t)b * a.L + t] = 0.f; return; }
-    const float* __restrict__ w = a.w;
-    float acc = a.bias[0];
-    const float* row = lds + threadIdx.x * S;
-    for (int kap = 0; kap < k; ++kap, row += S) {
-#pragma unroll
-        for (int q = 0; q < C / 4; ++q) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = fmaf(v[e], w[kap * C + 4 * q + e], acc);
-        }
+    constexpr bool PEAK = OUT == pcm::OUT_F32_PEAK;      // every thread stays for the block's peak; one without a sample adds 0
+    if constexpr (!PEAK) {
+        if (t >= a.L) return;
+        if (t >= Lb) { pcm::store_sample<OUT>(a, (size_t)b * a.L + t, 0.f); return; }
     }
-    a.y[(size_t)b * a.L + t] = tanhf(acc);
+    float wv = 0.f;
+    if (!PEAK || t < Lb) {
+        const float* __restrict__ w = a.w;
+        float acc = a.bias[0];
+        const float* row = lds + threadIdx.x * S;
+        for (int kap = 0; kap < k; ++kap, row += S) {
+#pragma unroll
+            for (int q = 0; q < C / 4; ++q) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = fmaf(v[e], w[kap * C + 4 * q + e], acc);
+            }
+        }
+        wv = tanhf(acc);
+    }
+    if constexpr (PEAK) {
+        if (t < a.L) a.y[(size_t)b * a.L + t] = wv;
+        pcm::block_peak_max(pcm::abs_bits(wv), a.peak + b);
+    } else {
+        pcm::store_sample<OUT>(a, (size_t)b * a.L + t, wv);
+    }
 }
 
-// Generic fallback (any C, fp32 input): scalar staging.  (A template only so that both translation units may include it.)
-template <int UNUSED>
+// Generic fallback (any C, fp32 input): scalar staging.  (A template also so that both translation units may include it.)
+template <int OUT>
 __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const ConvPostLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int C = a.C, k = a.k, pad = (k - 1) / 2;
@@ -169,7 +186,7 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const ConvPostLaunc
     const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);     // (ragged forward: as in conv_post_rows_kernel)
     if (t0 >= Lb) {
         const int t = t0 + (int)threadIdx.x;
-        if (t < a.L) a.y[(size_t)b * a.L + t] = 0.f;
+        if (t < a.L) pcm::store_sample<OUT>(a, (size_t)b * a.L + t, 0.f);
         return;
     }
     for (int idx = threadIdx.x; idx < total; idx += 256) {
@@ -187,15 +204,27 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const ConvPostLaunc
     }
     __syncthreads();
     const int t = t0 + threadIdx.x;
-    if (t >= a.L) return;
-    if (t >= Lb) { a.y[(size_t)b * a.L + t] = 0.f; return; }
-    const float* __restrict__ w = a.w;
-    float acc = a.bias[0];
-    for (int kap = 0; kap < k; ++kap) {
-        const float* row = lds + (threadIdx.x + kap) * S;
-        for (int c = 0; c < C; ++c) acc = fmaf(row[c], w[kap * C + c], acc);
+    constexpr bool PEAK = OUT == pcm::OUT_F32_PEAK;      // (as in conv_post_rows_kernel)
+    if constexpr (!PEAK) {
+        if (t >= a.L) return;
+        if (t >= Lb) { pcm::store_sample<OUT>(a, (size_t)b * a.L + t, 0.f); return; }
     }
-    a.y[(size_t)b * a.L + t] = tanhf(acc);
+    float wv = 0.f;
+    if (!PEAK || t < Lb) {
+        const float* __restrict__ w = a.w;
+        float acc = a.bias[0];
+        for (int kap = 0; kap < k; ++kap) {
+            const float* row = lds + (threadIdx.x + kap) * S;
+            for (int c = 0; c < C; ++c) acc = fmaf(row[c], w[kap * C + c], acc);
+        }
+        wv = tanhf(acc);
+    }
+    if constexpr (PEAK) {
+        if (t < a.L) a.y[(size_t)b * a.L + t] = wv;
+        pcm::block_peak_max(pcm::abs_bits(wv), a.peak + b);
+    } else {
+        pcm::store_sample<OUT>(a, (size_t)b * a.L + t, wv);
+    }
 }
 
 // True when the 16-byte-staging kernel can take the launch (32-bit buffer offsets inside one batch item's tensor).
@@ -205,8 +234,11 @@ inline bool conv_post_rows_ok(const ConvPostLaunch& a, bool bf16_in) {
            (double)a.L * a.C * (bf16_in ? 2 : 4) < 2147483648.0;
 }
 
-template <bool BF16_IN>
-inline hipError_t launch_conv_post_t(ConvPostLaunch a, hipStream_t stream) {
+// The output form a launch asks for: a.pcm -> OUT_PCM16, else a.peak -> OUT_F32_PEAK, else the fp32 waveform.
+inline int conv_post_out(const ConvPostLaunch& a) { return a.pcm ? pcm::OUT_PCM16 : (a.peak ? pcm::OUT_F32_PEAK : pcm::OUT_F32); }
+
+template <bool BF16_IN, int OUT>
+inline hipError_t launch_conv_post_o(ConvPostLaunch a, hipStream_t stream) {
     a.tiles_per_item = (a.L + kPostTile - 1) / kPostTile;
     const long long blocks = (long long)a.tiles_per_item * a.B;
     if (blocks < 1 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -217,7 +249,7 @@ inline hipError_t launch_conv_post_t(ConvPostLaunch a, hipStream_t stream) {
         if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
 #define IRIS_POST_CASE(C_)                                                                                   \
         if (a.C == C_) {                                                                                     \
-            auto kfn = conv_post_rows_kernel<C_, BF16_IN>;                                                   \
+            auto kfn = conv_post_rows_kernel<C_, BF16_IN, OUT>;                                                 \
             { const hipError_t e__ = ::iris::launch_kernel_named("conv_post_rows_kernel", kfn, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; } \
             return hipSuccess;                                                                               \
         }
@@ -227,8 +259,17 @@ inline hipError_t launch_conv_post_t(ConvPostLaunch a, hipStream_t stream) {
     if (BF16_IN) return hipErrorInvalidValue;      // the bf16-storage path has no scalar fallback (C % 8 == 0 there)
     const size_t lds_bytes = (size_t)(kPostTile + a.k - 1) * (a.C | 1) * sizeof(float);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    { const hipError_t e__ = ::iris::launch_kernel(conv_post_tanh_kernel<0>, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; }
-    return hipSuccess;       
+    { const hipError_t e__ = ::iris::launch_kernel_named("conv_post_tanh_kernel<0>", conv_post_tanh_kernel<OUT>, grid, block, lds_bytes, stream, a); if (e__ != hipSuccess) return e__; }
+    return hipSuccess;
+}
+
+template <bool BF16_IN>
+inline hipError_t launch_conv_post_t(const ConvPostLaunch& a, hipStream_t stream) {
+    switch (conv_post_out(a)) {
+        case pcm::OUT_PCM16:    return launch_conv_post_o<BF16_IN, pcm::OUT_PCM16>(a, stream);
+        case pcm::OUT_F32_PEAK: return launch_conv_post_o<BF16_IN, pcm::OUT_F32_PEAK>(a, stream);
+        default:                return launch_conv_post_o<BF16_IN, pcm::OUT_F32>(a, stream);
+    }
 }
 
 inline hipError_t launch_conv_post(const ConvPostLaunch& a, hipStream_t stream) { return launch_conv_post_t<false>(a, stream); }

@@ -22,6 +22,30 @@ constexpr int kTileCounterWords = 256;   // per-launch next-tile counters of one
 // forward_until: stop after MRF step `step` of stage `stage` has been queued (stage < 0: run the whole forward)
 struct ForwardStop { int stage; int step; };
 
+// What one forward leaves behind, i.e. what its conv_post stores (pcm_out.h).  The plain forward: `wav` alone.
+// iris_hifigan_forward_pcm16: `pcm` alone (conv_post stores int16 in place of the waveform), or -- normalising -- all three:
+// conv_post stores `wav` and reduces `peak`, and a second kernel writes `pcm` from them.  forward_until: nothing.
+struct ForwardOut {
+    float* wav = nullptr;       // [B, hop*T] fp32
+    int16_t* pcm = nullptr;     // [B, hop*T]
+    float* peak = nullptr;      // [B] per-item max |wav|; non-null = peak-normalised PCM
+    float target = 0.f;         // the peak's value after normalisation, in (0, 1]
+    bool normalize() const { return peak != nullptr; }
+    ForwardOut advanced(size_t items, size_t samples_per_item) const {      // the same buffers from batch item `items` on
+        ForwardOut o = *this;
+        if (wav) o.wav += items * samples_per_item;
+        if (pcm) o.pcm += items * samples_per_item;
+        if (peak) o.peak += items;
+        return o;
+    }
+    // fills the output fields of a conv_post launch descriptor (post::ConvPostLaunch, b16::PostLaunch)
+    template <class A> void to_post(A& a) const {
+        a.y = wav;
+        a.pcm = normalize() ? nullptr : pcm;
+        a.peak = normalize() ? reinterpret_cast<unsigned*>(peak) : nullptr;
+    }
+};
+
 // Runs the rest of the scope under the handle's device and restores the caller's (a process may hold generators on
 // several GPUs; launches, events and the CU-count-based launch plans must all refer to the handle's device).
 struct DeviceGuard {
@@ -249,7 +273,7 @@ struct DevBuf {
 
 // ---- bf16-storage path (iris_hifigan_bf16.hip) ----
 int bf16_build_blob(iris_hifigan_handle* h, const float* weights_host);   // packs + uploads blob16 (host_only: packs only)
-int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void* wav_dev,
+int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, const ForwardOut& out,
                  void* workspace_dev, uint64_t workspace_bytes, hipStream_t stream, const ForwardStop& stop,
                  int32_t* until_flags);
 

@@ -605,7 +605,7 @@ MrfStagePlan plan_mrf_stage(const StageCtx& c, int32_t dtype, const ForwardStop&
 // `lengths` (iris_hifigan_forward_ragged, fp32 only; nullptr otherwise): mel frames of each batch item on the device.
 // Every launch carries it with its rows per mel frame (`row_scale`), and every kernel bounds the item's reads and stores
 // by them: the plan is the one of (B, T), each item is computed as a forward of its own length would compute it.
-int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, void* wav_dev, void* workspace_dev,
+int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, const ForwardOut& out, void* workspace_dev,
                 uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop, int32_t* until_flags,
                 const int32_t* lengths) {
     const WsLayout w = ws_layout(h, B, T, dtype);
@@ -723,7 +723,7 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
         const int L = c.L;
         if (prev_summed) { a.x[0] = c.y[0]; a.n_in = 1; }
         else { for (int j = 0; j < nk; ++j) a.x[j] = c.y[j]; a.n_in = nk; }
-        a.w = blob + l.w_off; a.bias = blob + l.b_off; a.y = (float*)wav_dev;
+        a.w = blob + l.w_off; a.bias = blob + l.b_off; out.to_post(a);
         a.B = B; a.L = L; a.C = l.C_in; a.k = l.k; a.slope = slope; a.inv_n = 1.0f / (float)nk;
         a.lengths = lengths; a.row_scale = c.row_scale;
         TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
@@ -752,8 +752,10 @@ int check_forward_args(const iris_hifigan_handle* h, const void* mel_dev, int32_
 
 // What every forward does once its own argument checks have passed: the handle's device, the weight packing of the dtype,
 // then the passes (pass_items).  `lengths_dev`: the ragged forward's; `stop` / `until_flags`: forward_until's (one pass).
+// `out`: what the forward leaves behind (ForwardOut); a normalising pass zeroes its items' peaks in front of the forward and
+// converts its waveform behind it (pcm_out.h), all on `stream`.
 // A host-only handle (describe_plan) has no device and every packing's offsets.
-int run_forward(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, const int32_t* lengths_dev, void* wav_dev,
+int run_forward(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T, const int32_t* lengths_dev, const ForwardOut& out,
                 void* workspace_dev, uint64_t workspace_bytes, int32_t dtype, hipStream_t stream, const ForwardStop& stop,
                 int32_t* until_flags) {
     DeviceGuard guard(h->device, !h->host_only);
@@ -766,12 +768,17 @@ int run_forward(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
     for (int b0 = 0; b0 < B; b0 += Bp) {
         const int nb = B - b0 < Bp ? B - b0 : Bp;
         const float* mel_p = (const float*)mel_dev + (size_t)b0 * h->cfg.in_channels * T;
-        float* wav_p = (float*)wav_dev + (size_t)b0 * h->hop * T;
+        const ForwardOut out_p = out.advanced((size_t)b0, (size_t)h->hop * T);
+        const int32_t* const lengths_p = lengths_dev ? lengths_dev + b0 : nullptr;
+        if (out_p.normalize() && !h->host_only) HIP_TRY(hipMemsetAsync(out_p.peak, 0, sizeof(float) * nb, stream));
         if (dtype == IRIS_HIFIGAN_BF16)
-            TRY(bf16_forward(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, stream, stop, until_flags));
+            TRY(bf16_forward(h, mel_p, nb, T, out_p, workspace_dev, workspace_bytes, stream, stop, until_flags));
         else
-            TRY(forward_f32(h, mel_p, nb, T, wav_p, workspace_dev, workspace_bytes, dtype, stream, stop, until_flags,
-                            lengths_dev ? lengths_dev + b0 : nullptr));
+            TRY(forward_f32(h, mel_p, nb, T, out_p, workspace_dev, workspace_bytes, dtype, stream, stop, until_flags, lengths_p));
+        if (out_p.normalize()) {
+            const pcm::PcmLaunch q{out_p.wav, lengths_p, h->hop, out_p.pcm, out_p.peak, nb, h->hop * T, out_p.target};
+            HIP_TRY(pcm::launch_pcm_normalize(q, true, stream));
+        }
     }
     return IRIS_HIFIGAN_OK;
 }
@@ -787,7 +794,8 @@ int32_t iris_hifigan_forward(iris_hifigan_handle* h, const void* mel_dev, int32_
     TRY(check_forward_args(h, mel_dev, B, T, workspace_dev, dtype));
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;  // empty batch / empty mel -> empty waveform
     if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    return run_forward(h, mel_dev, B, T, nullptr, wav_dev, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+    ForwardOut out; out.wav = (float*)wav_dev;
+    return run_forward(h, mel_dev, B, T, nullptr, out, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
                        ForwardStop{-1, -1}, nullptr);
     IRIS_ABI_END
 }
@@ -805,7 +813,31 @@ int32_t iris_hifigan_forward_ragged(iris_hifigan_handle* h, const void* mel_dev,
     if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
     // the plan of (B, T), as iris_hifigan_forward: the lengths are never read on the host (fp32 plans are bitwise
     // plan-independent, so each item still gets the bits of a forward of its own length)
-    return run_forward(h, mel_dev, B, T, lengths_dev, wav_dev, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+    ForwardOut out; out.wav = (float*)wav_dev;
+    return run_forward(h, mel_dev, B, T, lengths_dev, out, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+                       ForwardStop{-1, -1}, nullptr);
+    IRIS_ABI_END
+}
+
+int32_t iris_hifigan_forward_pcm16(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t T,
+                                   const int32_t* lengths_dev, int16_t* pcm_dev, float* wav_dev, float* peak_dev,
+                                   int32_t normalize, float peak_target, void* workspace_dev, uint64_t workspace_bytes,
+                                   int32_t dtype, void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(check_forward_args(h, mel_dev, B, T, workspace_dev, dtype));
+    if (lengths_dev && dtype != IRIS_HIFIGAN_F32)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "per-item lengths are supported in fp32 (dtype 0) only, got dtype %d: the bf16-storage "
+                    "and split-product paths have no per-item lengths", dtype);
+    if (normalize && !(peak_target > 0.f && peak_target <= 1.f))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "peak_target must lie in (0, 1], got %g", (double)peak_target);
+    if (normalize && (!wav_dev || !peak_dev))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "normalize needs wav_dev and peak_dev");
+    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    if (!pcm_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    ForwardOut out;
+    out.pcm = pcm_dev;
+    if (normalize) { out.wav = wav_dev; out.peak = peak_dev; out.target = peak_target; }
+    return run_forward(h, mel_dev, B, T, lengths_dev, out, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
                        ForwardStop{-1, -1}, nullptr);
     IRIS_ABI_END
 }
@@ -820,7 +852,7 @@ int32_t iris_hifigan_forward_until(iris_hifigan_handle* h, const void* mel_dev, 
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "no MRF step %d in stage %d", stop_step, stop_stage);
     if (pass_items(B, T) != B)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "forward_until takes shapes that run in one pass (B * T <= %d frames)", kPassFrames);
-    return run_forward(h, mel_dev, B, T, nullptr, nullptr, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
+    return run_forward(h, mel_dev, B, T, nullptr, ForwardOut{}, workspace_dev, workspace_bytes, dtype, (hipStream_t)stream_,
                        ForwardStop{stop_stage, stop_step}, flags);
     IRIS_ABI_END
 }
@@ -853,7 +885,8 @@ int32_t iris_hifigan_describe_plan(const iris_hifigan_config* cfg, int32_t B, in
     out->workspace_bytes = ws_layout(&h, Bp, T, dtype).bytes();
     out->cu_count = dry.cu_count;
     if (B > 0 && T > 0) out->passes = (B + Bp - 1) / Bp;
-    const int rc = run_forward(&h, mel, B, T, nullptr, wav, ws, out->workspace_bytes, dtype, nullptr, ForwardStop{-1, -1}, nullptr);
+    ForwardOut fo; fo.wav = (float*)wav;
+    const int rc = run_forward(&h, mel, B, T, nullptr, fo, ws, out->workspace_bytes, dtype, nullptr, ForwardStop{-1, -1}, nullptr);
     out->n_launches = dry.n;                                    // (the launches of every pass are recorded)
     for (int i = 0; i < dry.n && i < IRIS_HIFIGAN_MAX_PLAN_LAUNCHES; ++i) {
         iris_hifigan_plan_launch& o = out->launches[i];
@@ -954,6 +987,25 @@ int32_t iris_hifigan_op_conv_post(const float* x0_dev, const float* x1_dev, cons
     a.w = wb.f32(); a.bias = wb.f32() + (size_t)k * C_in; a.y = y_dev;
     a.B = B; a.L = L; a.C = C_in; a.k = k; a.slope = slope; a.inv_n = 1.0f / (float)a.n_in;
     HIP_TRY(post::launch_conv_post(a, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_hifigan_op_pcm16(const float* wav_dev, const int32_t* lengths_dev, int32_t row_scale, int16_t* pcm_dev,
+                              float* peak_dev, int32_t B, int32_t L, int32_t normalize, float peak_target, void* stream_) {
+    IRIS_ABI_BEGIN
+    if (!wav_dev || !pcm_dev || (normalize && !peak_dev)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    if (B < 1 || L < 1 || B > 65535 || row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad pcm16 shape");
+    if (normalize && !(peak_target > 0.f && peak_target <= 1.f))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "peak_target must lie in (0, 1], got %g", (double)peak_target);
+    hipStream_t stream = (hipStream_t)stream_;
+    const pcm::PcmLaunch q{wav_dev, lengths_dev, row_scale, pcm_dev, peak_dev, B, L, peak_target};
+    if (normalize) {
+        HIP_TRY(hipMemsetAsync(peak_dev, 0, sizeof(float) * B, stream));
+        HIP_TRY(pcm::launch_pcm_peak(q, stream));
+    }
+    HIP_TRY(pcm::launch_pcm_normalize(q, normalize != 0, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END

@@ -170,7 +170,7 @@ void fill_ups(s3::Launch& a, const ConvLayer& l, const float* x, const void* wp,
 }
 }  // namespace
 
-int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void* wav_dev,
+int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, const ForwardOut& out,
                  void* workspace_dev, uint64_t workspace_bytes, hipStream_t stream, const ForwardStop& stop,
                  int32_t* until_flags) {
     if (!h->blob16)
@@ -321,7 +321,7 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
         L = L_out;
     }
 
-    // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141): bf16 in, fp32 waveform out ----
+    // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141): bf16 in, fp32 waveform (or what `out` asks for) out ----
     {
         const ConvLayer& l = h->post;
         TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
@@ -330,7 +330,7 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
         post::ConvPostLaunch ar; memset(&ar, 0, sizeof(ar));
         for (int j = 0; j < nk && j < 4; ++j) ar.x[j] = cur[j];
         ar.n_in = nk; ar.inv_n = 1.0f / (float)nk;
-        ar.w = blob + l.w_off; ar.bias = blob + l.b_off; ar.y = (float*)wav_dev;
+        ar.w = blob + l.w_off; ar.bias = blob + l.b_off; out.to_post(ar);
         ar.B = B; ar.L = L; ar.C = C; ar.k = l.k; ar.slope = slope;
         if (mean32) {
             // the summing pair left the fp32 mean: conv_post as in the fp32 path (one fp32 input, LeakyReLU in fp32)
@@ -345,7 +345,7 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, void
             PostLaunch a; memset(&a, 0, sizeof(a));
             for (int j = 0; j < nk; ++j) a.x[j] = cur[j];
             a.n_in = nk; a.inv_n = 1.0f / (float)nk;
-            a.w = blob + l.w_off; a.bias = blob + l.b_off; a.y = (float*)wav_dev;
+            a.w = blob + l.w_off; a.bias = blob + l.b_off; out.to_post(a);
             a.B = B; a.L = L; a.C = C; a.k = l.k; a.slope = slope;
             HIP_TRY(launch_conv_post_bf16(a, stream));
         }

@@ -203,6 +203,56 @@ class GeneratorEngine:
 
     __call__ = forward
 
+    def forward_pcm16(self, mel: torch.Tensor, out: Optional[torch.Tensor] = None, dtype: Optional[str] = None,
+                      lengths=None, normalize: bool = False, peak_target: float = 0.95,
+                      wav: Optional[torch.Tensor] = None):
+        """mel: fp32 device tensor [B, in_channels, T] -> 16-bit PCM, an int16 device tensor [B, hop*T] (asynchronous on the
+        current stream): the forward with the output stage on the device (``iris_hifigan_forward_pcm16``), bit for bit
+        ``synthesis_output.pcm16_from_float(forward(mel, ...))``.  ``dtype`` and ``lengths`` as in ``forward`` (lengths:
+        "f32" only; ``pcm[b, hop*lengths[b]:]`` is 0).
+
+        ``normalize=True`` scales every item to ``peak_target / (max|w| + 1e-8)`` first (the reference demo's scheme, per
+        item) and returns ``(pcm, peaks)``: ``peaks`` is the fp32 device tensor [B] of the items' max |w| (0 for an empty
+        or silent item, whose PCM is 0).  ``wav`` (normalize only): a contiguous fp32 tensor [B, hop*T] that receives the
+        waveform itself, bit for bit ``forward``'s, for a caller who wants both.  Always eager; it allocates before it launches, so inside a caller's
+        ``torch.cuda.graph`` capture it works once ``prepare(dtype)`` has run and the workspace has its size (one eager
+        call of the shape)."""
+        dtype = dtype or self.default_dtype
+        code = _dtype_code(dtype)
+        if mel.dim() != 3 or mel.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"expected mel [B, {self.cfg.in_channels}, T], got {tuple(mel.shape)}")
+        if normalize and not 0.0 < float(peak_target) <= 1.0:
+            raise ValueError(f"peak_target must lie in (0, 1], got {peak_target}")
+        if mel.device != self.device:
+            raise ValueError(f"mel is on {mel.device}, engine on {self.device}")
+        mel = mel.to(torch.float32).contiguous()
+        batch, _, frames = mel.shape
+        lengths_host = None if lengths is None else _check_lengths(lengths, batch, frames)
+        samples = frames * self.hop_length
+        if out is None:
+            out = torch.empty((batch, samples), dtype=torch.int16, device=self.device)
+        elif out.shape != (batch, samples) or out.dtype != torch.int16 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous int16 tensor [B, hop*T] on the engine's device")
+        peaks = torch.zeros((batch,), dtype=torch.float32, device=self.device) if normalize else None
+        if batch == 0 or frames == 0:
+            return (out, peaks) if normalize else out
+        if wav is not None and (not normalize or wav.shape != (batch, samples) or wav.dtype != torch.float32
+                                or not wav.is_contiguous() or wav.device != self.device):
+            raise ValueError("wav goes with normalize=True and must be a contiguous fp32 tensor [B, hop*T] on the engine's device")
+        if normalize and wav is None:
+            wav = torch.empty((batch, samples), dtype=torch.float32, device=self.device)
+        lengths_dev = None if lengths_host is None else torch.from_numpy(lengths_host).to(self.device)
+        ws = self._get_workspace(self.workspace_bytes(batch, frames, dtype))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+        _native.check("iris_hifigan_forward_pcm16", self.lib.iris_hifigan_forward_pcm16(
+            self._handle, ptr(mel), batch, frames, ptr(lengths_dev), ptr(out), ptr(wav), ptr(peaks), int(bool(normalize)),
+            ctypes.c_float(float(peak_target)), ptr(ws), ctypes.c_uint64(ws.numel()), code, ctypes.c_void_p(stream)))
+        return (out, peaks) if normalize else out
+
     # -- hipGraph replay ---------------------------------------------------------------------------
     def forward_graph(self, mel: torch.Tensor, dtype: Optional[str] = None) -> torch.Tensor:
         """Same result as ``forward`` but the launches of one forward are captured once per

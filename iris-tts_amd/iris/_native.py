@@ -131,6 +131,7 @@ SYMBOLS = {
     "iris_hifigan_workspace_bytes": (_i32, [_vp, _i32, _i32, _i32, _c.POINTER(_u64)]),
     "iris_hifigan_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _u64, _i32, _vp]),
     "iris_hifigan_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _i32, _vp]),
+    "iris_hifigan_forward_pcm16": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f, _vp, _u64, _i32, _vp]),
     "iris_hifigan_workspace_layout": (_i32, [_vp, _i32, _i32, _i32, _c.POINTER(WorkspaceMap)]),
     "iris_hifigan_forward_until": (_i32, [_vp, _vp, _i32, _i32, _vp, _u64, _i32, _i32, _i32, _c.POINTER(_i32), _vp]),
     "iris_hifigan_hop_length": (_i32, [_vp, _c.POINTER(_i32)]),
@@ -139,6 +140,7 @@ SYMBOLS = {
     "iris_hifigan_op_conv1d": (_i32, [_vp, _fp, _fp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32, _vp]),
     "iris_hifigan_op_conv_transpose1d": (_i32, [_vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _vp]),
     "iris_hifigan_op_conv_post": (_i32, [_vp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _f, _vp]),
+    "iris_hifigan_op_pcm16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _f, _vp]),
     "iris_hifigan_op_mrf_step": (_i32, [_c.POINTER(_vp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_vp), _c.POINTER(_vp), _vp,
                                        _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32), _f, _i32, _vp]),
     "iris_hifigan_op_mrf_pair": (_i32, [_c.POINTER(_vp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_fp),

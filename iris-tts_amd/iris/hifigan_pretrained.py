@@ -12,6 +12,8 @@ Same call surface as the reference (``/root/reference/src/iris/hifigan_pretraine
                                     numpy in -> numpy out, squeeze rules
     ``get_pretrained_hifigan``      module-global singleton keyed on the path   245-283
     ``infer_hifigan``               ``(mel, sample_rate, hop_length, ckpt)``    286-317
+    ``infer_hifigan_pcm16``         the same convention, 16-bit PCM converted   (not in the reference)
+                                    on the GPU; ``HiFiGANGenerator.infer_pcm16``
     ==============================  ==========================================  =====================
 
 What differs: the forward runs in hand-written HIP on a gfx950 GPU behind the C-ABI of
@@ -37,7 +39,8 @@ from ._weights import GeneratorConfig, layer_specs, extract_state_dict
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["ResBlock", "HiFiGANModel", "HiFiGANGenerator", "get_pretrained_hifigan", "infer_hifigan", "infer_hifigan_batch"]
+__all__ = ["ResBlock", "HiFiGANModel", "HiFiGANGenerator", "get_pretrained_hifigan", "infer_hifigan", "infer_hifigan_batch",
+           "infer_hifigan_pcm16"]
 
 
 class _WeightNormedConv(nn.Module):
@@ -291,15 +294,31 @@ class HiFiGANGenerator:
             audio = audio[0]
         return audio
 
-    def infer_batch(self, mels: Sequence[np.ndarray]) -> List[np.ndarray]:
+    def infer_pcm16(self, mel: np.ndarray, normalize: bool = False, peak_target: float = 0.95) -> np.ndarray:
+        """``__call__`` with the output stage on the GPU: [batch, n_mels, time] -> int16 [batch, samples], [n_mels, time] ->
+        int16 [samples], bit for bit ``synthesis_output.pcm16_from_float(self(mel), normalize, peak_target)`` (``normalize``:
+        every item scaled to ``peak_target`` at its own peak first); half the bytes come back to the host."""
+        mel = np.asarray(mel)
+        squeeze_batch = mel.ndim == 2
+        if squeeze_batch:
+            mel = mel[np.newaxis, ...]
+        eng = self.model.engine()
+        mel_tensor = torch.from_numpy(np.ascontiguousarray(mel)).float().to(eng.device)
+        pcm = eng.forward_pcm16(mel_tensor, normalize=normalize, peak_target=peak_target)
+        pcm = (pcm[0] if normalize else pcm).cpu().numpy()
+        return pcm[0] if squeeze_batch else pcm
+
+    def infer_batch(self, mels: Sequence[np.ndarray], pcm16: bool = False) -> List[np.ndarray]:
         """List of mels [n_mels, T_i] of any lengths -> list of waveforms [hop * T_i], in ONE ragged fp32 forward
-        (iris.batching).  Each waveform is bit for bit what ``self(mel)`` returns for that mel alone."""
+        (iris.batching).  Each waveform is bit for bit what ``self(mel)`` returns for that mel alone; ``pcm16=True``: what
+        ``self.infer_pcm16(mel)`` returns (int16, converted on the GPU)."""
         mels = [np.asarray(m) for m in mels]
         if not mels:
             return []
         padded, lengths = pack_mels([torch.from_numpy(np.ascontiguousarray(m)).float() for m in mels])
         eng = self.model.engine()
-        wav = eng.forward(padded.to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
+        fwd = eng.forward_pcm16 if pcm16 else eng.forward
+        wav = fwd(padded.to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
         return [w.copy() for w in split_waveforms(wav, lengths, eng.hop_length)]
 
 
@@ -335,6 +354,21 @@ def infer_hifigan(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length
     if audio.ndim == 2 and audio.shape[0] == 1:
         audio = audio[0]
     return audio
+
+
+def infer_hifigan_pcm16(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length: Optional[int] = None,
+                        checkpoint_path: Optional[Union[str, Path]] = None, normalize: bool = False,
+                        peak_target: float = 0.95) -> np.ndarray:
+    """``infer_hifigan`` returning 16-bit PCM (int16) converted on the GPU -- the entry point for
+    ``--vocoder_entry iris.hifigan_pretrained:infer_hifigan_pcm16`` (``python -m iris.synthesis_output --pcm16``), same calling
+    convention.  ``normalize``: scale the utterance to ``peak_target`` at its peak first (``HiFiGANGenerator.infer_pcm16``)."""
+    pcm = get_pretrained_hifigan(checkpoint_path).infer_pcm16(mel, normalize=normalize, peak_target=peak_target)
+    if pcm.ndim == 2 and pcm.shape[0] == 1:
+        pcm = pcm[0]
+    return pcm
+
+
+infer_hifigan_pcm16.returns_pcm16 = True        # synthesis_output.vocode_to_wav: normalisation happens inside the entry
 
 
 def infer_hifigan_batch(mels: Sequence[np.ndarray], checkpoint_path: Optional[Union[str, Path]] = None) -> List[np.ndarray]:

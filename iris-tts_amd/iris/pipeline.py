@@ -63,18 +63,42 @@ class MelToWavePipeline:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``."""
         yield from self.streamer.stream(self.refine(mel))
 
-    def infer(self, mel) -> torch.Tensor:
-        return self.streamer.infer(self.refine(mel))
+    def _pcm16_fn(self) -> Callable:
+        fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_pcm16", None)
+        if fn is None:
+            raise ValueError("pcm16=True needs a vocoder with a device output stage: construct the pipeline with a bound "
+                             "GeneratorEngine.forward")
+        return fn
+
+    def infer(self, mel, pcm16: bool = False, normalize: bool = False):
+        """The whole utterance.  ``pcm16=True``: an int16 device tensor, converted by the vocoder's last launch
+        (``GeneratorEngine.forward_pcm16``), chunked like the fp32 path.  ``normalize=True`` (with pcm16): every item scaled
+        to 0.95 at its own peak first; the peak is the whole utterance's, so the refined mel is vocoded in ONE forward,
+        and ``(pcm, peaks)`` is returned."""
+        if normalize and not pcm16:
+            raise ValueError("normalize=True goes with pcm16=True")
+        if not pcm16:
+            return self.streamer.infer(self.refine(mel))
+        fwd = self._pcm16_fn()
+        if normalize:
+            return fwd(self.refine(mel), normalize=True)
+        sv = self.streamer
+        return StreamingVocoder(fwd, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames, halo_frames=sv.halo_frames,
+                                group_chunks=sv.group_chunks, config=self.config).infer(self.refine(mel))
 
     __call__ = infer
 
-    def infer_batch(self, mels: Sequence) -> List[torch.Tensor]:
+    def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform
         ``[hop * T_i]`` per utterance, with ONE PostNet pass and ONE vocoder forward for the whole list: the mels are padded
         to the longest (``pack_mels``) and both stages bound every layer of item i by ``T_i`` (``forward_device(...,
         lengths=)``, ``vocode(..., lengths=)``), so item i is bit for bit ``infer(mels[i][None])[0]`` -- padding alone would
         let the padded frames reach the last frames of every short item (``iris.batching``).  The stages must take
-        ``lengths``; a vocoder dtype without a ragged forward (bf16, f32s) fails as ``engine.forward(lengths=...)`` does."""
+        ``lengths``; a vocoder dtype without a ragged forward (bf16, f32s) fails as ``engine.forward(lengths=...)`` does.
+        ``pcm16=True``: int16 waveforms from ``GeneratorEngine.forward_pcm16``; with ``normalize=True`` each is scaled to
+        0.95 at its own peak first."""
+        if normalize and not pcm16:
+            raise ValueError("normalize=True goes with pcm16=True")
         mels = list(mels)
         if not mels:
             return []
@@ -82,7 +106,11 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        wav = self.streamer.forward(padded, lengths=lengths)
+        if pcm16:
+            wav = self._pcm16_fn()(padded, lengths=lengths, normalize=normalize)
+            wav = wav[0] if normalize else wav
+        else:
+            wav = self.streamer.forward(padded, lengths=lengths)
         return split_waveforms(wav, lengths, self.streamer.hop_length)
 
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
@@ -107,7 +135,10 @@ class PipelineSession:
     Latency: chunk ``[s, s + chunk)`` is returned by the push that brings ``frames_received`` to ``s + chunk + hv + hp``.
     Work: the PostNet runs only in a push that returns at least one chunk, and once in ``flush`` -- a producer that pushes
     single frames does not cause a pass per frame.  Memory: at most ``chunk + 2 * (hv + hp)`` frames are buffered (raw ones
-    not yet refined with their left-hand context, refined ones not yet emitted with theirs) plus the piece just pushed."""
+    not yet refined with their left-hand context, refined ones not yet emitted with theirs) plus the piece just pushed.
+
+    A pipeline built on ``engine.forward_pcm16`` yields int16 chunks.  No peak normalisation here: it needs the peak of an
+    utterance that has not ended yet."""
 
     def __init__(self, pipeline: MelToWavePipeline, postnet_halo_frames: Optional[int] = None):
         sv = pipeline.streamer

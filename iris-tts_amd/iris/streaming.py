@@ -77,7 +77,10 @@ class StreamingVocoder:
     """Vocodes ``mel [B, n_mels, T]`` chunk by chunk.
 
     ``forward`` maps a window ``[B, n_mels, W]`` to ``[B, hop*W]`` (e.g. ``GeneratorEngine.forward``);
-    inputs/outputs may be torch tensors or numpy arrays -- they are only sliced along the last axis.
+    inputs/outputs may be torch tensors or numpy arrays -- they are only sliced along the last axis, so the chunks
+    have whatever dtype ``forward`` returns: fp32, or int16 with ``GeneratorEngine.forward_pcm16``.  Peak normalisation
+    needs the peak of the whole utterance, which no chunk knows: the streaming classes do not offer it (pass a forward
+    without ``normalize``; normalise one-shot with ``forward_pcm16(mel, normalize=True)``).
     """
 
     def __init__(self, forward: Callable, hop_length: Optional[int] = None, chunk_frames: int = 256,
@@ -150,7 +153,10 @@ class StreamingSession:
     The reference has no streaming (``TTSPipeline`` is a stub, src/iris/model.py:17-27); BASELINE.json configs[4] asks for
     256-frame chunks.  ``StreamingVocoder`` covers a mel that is already complete; this class is for a producer (an
     acoustic model emitting frames) that is still running.  Latency: a chunk is emitted ``halo`` frames (13 for V1 = 0.15 s
-    of audio) after its last frame has arrived.  At most ``chunk + 2 * halo`` frames are buffered."""
+    of audio) after its last frame has arrived.  At most ``chunk + 2 * halo`` frames are buffered.
+
+    The chunks have the dtype ``forward`` returns (int16 with ``GeneratorEngine.forward_pcm16``).  No peak normalisation
+    here: it needs the peak of an utterance that has not ended yet."""
 
     def __init__(self, forward: Callable, hop_length: Optional[int] = None, chunk_frames: int = 256,
                  halo_frames: Optional[int] = None, config=None):

@@ -26,6 +26,7 @@ import numpy as np
 logger = logging.getLogger(__name__)
 
 DEFAULT_VOCODER_ENTRY = "iris.hifigan_pretrained:infer_hifigan"
+PCM16_VOCODER_ENTRY = "iris.hifigan_pretrained:infer_hifigan_pcm16"    # 16-bit PCM converted on the device (--pcm16)
 VocoderEntry = Callable[..., np.ndarray]
 
 
@@ -56,25 +57,61 @@ def to_mono_float32(audio) -> np.ndarray:
     return audio
 
 
+def _check_peak_target(peak_target) -> np.float32:
+    if not 0.0 < float(peak_target) <= 1.0:
+        raise ValueError(f"peak_target must lie in (0, 1], got {peak_target}")
+    return np.float32(peak_target)
+
+
+def pcm16_from_float(audio, normalize: bool = False, peak_target: float = 0.95) -> np.ndarray:
+    """float waveform -> 16-bit PCM (little-endian int16, same shape), in float32 arithmetic throughout:
+
+        ``pcm = round(clip(w, -1, 1) * 32767)``            (``np.round``: half to even)
+
+    and with ``normalize`` first ``w = (w / (peak + 1e-8)) * peak_target``, ``peak`` the largest ``|w|`` along the last
+    axis -- per item of a batch; the scheme of the reference's demo_vocoder.py, 0.95 / (max|w| + 1e-8), restated with
+    every operation a float32 rounding of its own.  A silent or empty item has peak 0 and stays 0.  This is the host
+    restatement of the device output stage (``GeneratorEngine.forward_pcm16``, csrc/pcm_out.h): the two agree bit for bit."""
+    w = np.asarray(audio, dtype=np.float32)
+    if normalize:
+        target = _check_peak_target(peak_target)
+        peak = np.max(np.abs(w), axis=-1, keepdims=True, initial=np.float32(0.0)) if w.ndim else np.abs(w)
+        w = (w / (peak.astype(np.float32) + np.float32(1e-8))) * target
+    return np.round(np.clip(w, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)).astype("<i2")
+
+
 def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 22050) -> Path:
-    """Writes a mono WAV.  ``soundfile`` is used when importable (the reference's writer,
-    ``synthesize.py:211-213``); otherwise the standard-library ``wave`` module writes 16-bit PCM, which is
-    also what soundfile's default WAV subtype produces.  On failure the samples are saved as ``.npy``
-    next to the requested path, like the reference (:214-216).  Returns the path actually written."""
+    """Writes a mono WAV.  Float samples: ``soundfile`` is used when importable (the reference's writer,
+    ``synthesize.py:211-213``); otherwise the standard-library ``wave`` module writes 16-bit PCM
+    (``pcm16_from_float``), which is also what soundfile's default WAV subtype produces.  An int16 array (one waveform
+    after squeeze; what ``forward_pcm16`` / ``infer_hifigan_pcm16`` return) already is that PCM and is written verbatim
+    by ``wave``.  On failure the samples are saved as ``.npy`` next to the requested path, like the reference
+    (:214-216).  Returns the path actually written."""
     out_path = Path(path)
     out_path.parent.mkdir(parents=True, exist_ok=True)
-    audio = to_mono_float32(audio)
+    is_pcm = isinstance(audio, np.ndarray) and audio.dtype == np.int16
+    if is_pcm:
+        audio = audio.squeeze() if audio.ndim > 1 else audio
+        if audio.ndim != 1:
+            raise ValueError(f"expected a single waveform after squeeze, got shape {audio.shape}")
+    else:
+        audio = to_mono_float32(audio)
+    def write_pcm(pcm: np.ndarray) -> None:
+        with wave.open(str(out_path), "wb") as w:
+            w.setnchannels(1)
+            w.setsampwidth(2)
+            w.setframerate(int(sample_rate))
+            w.writeframes(pcm.astype("<i2", copy=False).tobytes())
+
     try:
-        try:
-            import soundfile as sf  # optional dependency
-            sf.write(str(out_path), audio, sample_rate)
-        except ImportError:
-            pcm = np.round(np.clip(audio, -1.0, 1.0) * 32767.0).astype("<i2")
-            with wave.open(str(out_path), "wb") as w:
-                w.setnchannels(1)
-                w.setsampwidth(2)
-                w.setframerate(int(sample_rate))
-                w.writeframes(pcm.tobytes())
+        if is_pcm:
+            write_pcm(audio)
+        else:
+            try:
+                import soundfile as sf  # optional dependency
+                sf.write(str(out_path), audio, sample_rate)
+            except ImportError:
+                write_pcm(pcm16_from_float(audio))
         logger.info(f"Wrote {out_path}")
         return out_path
     except Exception as exc:  # same fallback as the reference
@@ -85,18 +122,35 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 
 
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
-                  sample_rate: int = 22050, hop_length: int = 256) -> np.ndarray:
-    """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples."""
+                  sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None) -> np.ndarray:
+    """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
+    int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
+    ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
+    ``normalize=True, peak_target=`` (an entry that converts on the device, ``infer_hifigan_pcm16``) when it returns PCM; a float result is
+    normalised on the host (``pcm16_from_float``)."""
     fn = resolve_vocoder_entry(vocoder_entry)
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
-    audio = to_mono_float32(fn(mel, sample_rate, hop_length))
+    if normalize_peak is not None:
+        _check_peak_target(normalize_peak)
+    if normalize_peak is not None and getattr(fn, "returns_pcm16", False):
+        audio = fn(mel, sample_rate, hop_length, normalize=True, peak_target=float(normalize_peak))
+    else:
+        audio = fn(mel, sample_rate, hop_length)
+    if isinstance(audio, np.ndarray) and audio.dtype == np.int16:
+        audio = audio.squeeze() if audio.ndim > 1 else audio
+        if audio.ndim != 1:
+            raise ValueError(f"expected a single waveform after squeeze, got shape {audio.shape}")
+    else:
+        audio = to_mono_float32(audio)
+        if normalize_peak is not None:
+            audio = pcm16_from_float(audio, normalize=True, peak_target=normalize_peak)
     logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / sample_rate:.2f}s")
     write_wav(output_wav, audio, sample_rate)
     return audio
 
 
-def main(argv: Optional[list] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Vocode a mel-spectrogram (.npy) to a WAV file")
     parser.add_argument("--mel", required=True, help=".npy file with a mel [n_mels, T] or [1, n_mels, T]")
     parser.add_argument("--output_wav", type=str, default="outputs/sample.wav")        # synthesize.py:67
@@ -104,10 +158,23 @@ def main(argv: Optional[list] = None) -> int:
     parser.add_argument("--vocoder_entry", type=str, default=DEFAULT_VOCODER_ENTRY)
     parser.add_argument("--sample_rate", type=int, default=22050)                       # synthesize.py:77
     parser.add_argument("--hop_length", type=int, default=256)                          # synthesize.py:78
+    parser.add_argument("--pcm16", action="store_true",
+                        help=f"convert to 16-bit PCM on the GPU (vocoder entry {PCM16_VOCODER_ENTRY} unless --vocoder_entry is given)")
+    parser.add_argument("--normalize_peak", type=float, default=None, metavar="X",
+                        help="scale the utterance so that its peak is X, 0 < X <= 1 (the reference demo uses 0.95)")
+    return parser
+
+
+def main(argv: Optional[list] = None) -> int:
+    parser = build_parser()
     args = parser.parse_args(argv)
+    if args.normalize_peak is not None and not 0.0 < args.normalize_peak <= 1.0:
+        parser.error(f"--normalize_peak must lie in (0, 1], got {args.normalize_peak}")
+    if args.pcm16 and args.vocoder_entry == DEFAULT_VOCODER_ENTRY:
+        args.vocoder_entry = PCM16_VOCODER_ENTRY
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
-    vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length)
+    vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak)
     return 0
 
 

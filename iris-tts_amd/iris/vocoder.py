@@ -233,15 +233,17 @@ class HiFiGANVocoder:
             audio = audio[0]
         return audio
 
-    def infer_batch(self, mels: Sequence[np.ndarray]) -> List[np.ndarray]:
+    def infer_batch(self, mels: Sequence[np.ndarray], pcm16: bool = False) -> List[np.ndarray]:
         """List of mels [mel_channels, time_i] of any lengths -> list of waveforms [time_i * hop], in ONE ragged fp32
-        forward (iris.batching); each is bit for bit what ``infer(mel)`` returns for that mel alone."""
+        forward (iris.batching); each is bit for bit what ``infer(mel)`` returns for that mel alone.  ``pcm16=True``: int16
+        PCM converted on the GPU (``GeneratorEngine.forward_pcm16``), bit for bit ``pcm16_from_float`` of those waveforms."""
         mels = [np.asarray(m, dtype=np.float32) for m in mels]
         if not mels:
             return []
         padded, lengths = pack_mels(mels)
         eng = self.model.engine()
-        wav = eng.forward(torch.from_numpy(padded).to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
+        fwd = eng.forward_pcm16 if pcm16 else eng.forward
+        wav = fwd(torch.from_numpy(padded).to(eng.device), dtype="f32", lengths=lengths).cpu().numpy()
         return [w.copy() for w in split_waveforms(wav, lengths, eng.hop_length)]
 
     def __call__(self, mel: np.ndarray) -> np.ndarray:
