@@ -385,6 +385,57 @@ int32_t iris_postnet_forward_ragged(iris_postnet_handle* h, const void* mel_dev,
                                     const int32_t* lengths_dev, void* out_dev,
                                     void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- sample-rate conversion behind conv_post (csrc/resample.h) ---------------------------------------
+ * The generator produces 22 050 Hz; the reference never resamples (it only labels the WAV with --sample_rate), so there
+ * is no reference for this stage: the contract is the filter below and its exact host restatement
+ * (iris.resample.resample_host), which the device matches bit for bit.
+ *   g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g, s = min(1, up / down), fc = rolloff * s,
+ *   Hw = ceil(zeros / s) (half_width), taps = 2 * Hw
+ *   bank[p][j] = fc * sinc(fc * t) * I0(beta * sqrt(1 - (t / Hw)^2)) / I0(beta),  t = (j - Hw + 1) - p / up,
+ *                sinc(x) = sin(pi x) / (pi x), 0 where |t| > Hw; evaluated in double, rounded once to fp32
+ *   out[n]     = the chain over j = 0 .. taps - 1, ascending, of acc = fmaf(x[i0 - Hw + 1 + j], bank[p][j], acc) from
+ *                acc = 0.0f, with i0 = floor(n * down / up) and p = (n * down) mod up
+ * n and the index of x are utterance-global: a call passes `origin` >= 0, the global index of wav[:, 0], and its L
+ * samples produce exactly the outputs n with origin <= n * down / up < origin + L, i.e.
+ * n_lo = ceil(origin * up / down) .. ceil((origin + L) * up / down) - 1 (with origin 0: ceil(L * up / down) of them), so
+ * consecutive windows partition the output, and a window that carries Hw samples of context on each side reproduces the
+ * one-shot samples of its interior.  x outside the item's own samples reads as 0.
+ * zeros, beta, rolloff: 0 takes the default (16, 9.0, 0.945); negative values, rolloff > 1, rates < 1 and
+ * rate_out == rate_in return IRIS_HIFIGAN_INVALID_ARGUMENT.  Configurations outside 4000 <= rate_out <= 192000,
+ * up <= 640, taps <= 256 (or whose input span of 1024 outputs exceeds 64 KB) return IRIS_HIFIGAN_UNSUPPORTED; from
+ * 22 050 Hz that admits 8000, 11 025, 16 000, 24 000, 32 000, 44 100 and 48 000. */
+typedef struct iris_resampler_handle iris_resampler_handle;
+
+/* Host only (no device): the sizes, and with bank_host != NULL (capacity >= up * taps floats) the bank [up][taps]. */
+int32_t iris_resampler_design(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta, double rolloff,
+                              int32_t* up, int32_t* down, int32_t* taps, float* bank_host, uint64_t capacity);
+/* Designs the bank by the same function and uploads it to the current HIP device. */
+int32_t iris_resampler_create(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta, double rolloff,
+                              iris_resampler_handle** out);
+int32_t iris_resampler_destroy(iris_resampler_handle* h);
+int32_t iris_resampler_info(const iris_resampler_handle* h, int32_t* up, int32_t* down, int32_t* taps, int32_t* half_width);
+/* Host only: the first global output and the number of outputs of a window of L samples at `origin` (both in [0, 2^40]). */
+int32_t iris_resampler_out_range(const iris_resampler_handle* h, int64_t origin, int64_t L, int64_t* n_lo, int64_t* n_count);
+/* wav_dev [B, L] fp32 -> [B, n_count] (iris_resampler_out_range(origin, L)), in ONE of three forms:
+ *   normalize == 0, out_f32_dev:  the fp32 samples;
+ *   normalize == 0, out_pcm_dev:  int16, (int16) rintf(clamp(out, -1, 1) * 32767) -- the output stage's plain formula;
+ *   normalize != 0:               out_f32_dev receives the fp32 samples, peak_dev [B] the items' max |out| over their own
+ *                                 outputs (0 for an empty item) and out_pcm_dev the output stage's normalised formula
+ *                                 applied to them, q = (out / (peak[b] + 1e-8f)) * peak_target; all three are required and
+ *                                 peak_target must lie in (0, 1].  The kernel reduces the peaks beside its store and the
+ *                                 output stage's second kernel converts.
+ * Giving neither or both outputs without normalize, or NULL wav_dev (B, L > 0), returns IRIS_HIFIGAN_INVALID_ARGUMENT.
+ * lengths_dev (may be NULL) and row_scale >= 1 as in iris_hifigan_op_pcm16: item b owns min(L, lengths[b] * row_scale)
+ * input samples; samples past that are never read (they may hold NaN), the item is computed bit for bit as a call on its
+ * own samples alone, and its outputs past its own count ceil((origin + own) * up / down) - n_lo are 0.
+ * Asynchronous on `stream`, allocates nothing, safe inside a stream capture (a normalising call queues one memset of its
+ * peaks).  B == 0 or L == 0 returns IRIS_HIFIGAN_OK; B > 65535, L > 2^30 or more than 2^31 - 1 outputs per item return
+ * IRIS_HIFIGAN_UNSUPPORTED.  The handle belongs to the device that was current in iris_resampler_create. */
+int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t L,
+                               const int32_t* lengths_dev /* NULL = plain batch */, int32_t row_scale, int64_t origin,
+                               float* out_f32_dev, int16_t* out_pcm_dev, float* peak_dev,
+                               int32_t normalize, float peak_target, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include "mrf_pair_f32_pf.h"
 #include "conv_post.h"
 #include "postnet.h"
+#include "resample.h"
 
 using namespace iris;
 
@@ -1248,6 +1249,145 @@ int32_t iris_postnet_forward_ragged(iris_postnet_handle* h, const void* mel_dev,
                                     uint64_t workspace_bytes, void* stream_) {
     IRIS_ABI_BEGIN
     return postnet_forward(h, mel_dev, B, T, true, lengths_dev, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
+    IRIS_ABI_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Sample-rate conversion behind conv_post (csrc/resample.h)
+// ------------------------------------------------------------------------------------------------
+struct iris_resampler_handle {
+    resample::Design d;
+    float* bank = nullptr;      // [up][row_stride(taps)] on the device
+    int device = 0;
+};
+
+namespace {
+
+int resampler_plan(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta, double rolloff, resample::Design* d) {
+    const int rc = resample::plan(rate_in, rate_out, zeros, beta, rolloff, d);
+    if (rc == IRIS_HIFIGAN_INVALID_ARGUMENT)
+        return fail(rc, "resampler needs rate_in != rate_out, both >= 1, zeros >= 0, beta >= 0, 0 <= rolloff <= 1 (0 = default), "
+                        "got %d -> %d Hz, zeros %d, beta %g, rolloff %g", rate_in, rate_out, zeros, beta, rolloff);
+    if (rc != 0 || resample::lds_floats(d->up, d->down, d->taps) * sizeof(float) > 64 * 1024)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "resampler %d -> %d Hz (zeros %d) is outside %d <= rate_out <= %d, up <= %d, taps <= %d "
+                    "or needs more than 64 KB of LDS", rate_in, rate_out, zeros, resample::kMinRateOut, resample::kMaxRateOut,
+                    resample::kMaxUp, resample::kMaxTaps);
+    return IRIS_HIFIGAN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t iris_resampler_design(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta, double rolloff,
+                              int32_t* up, int32_t* down, int32_t* taps, float* bank_host, uint64_t capacity) {
+    IRIS_ABI_BEGIN
+    if (!up || !down || !taps) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    resample::Design d;
+    TRY(resampler_plan(rate_in, rate_out, zeros, beta, rolloff, &d));
+    *up = d.up; *down = d.down; *taps = d.taps;
+    if (!bank_host) return IRIS_HIFIGAN_OK;
+    if (capacity < (uint64_t)d.up * d.taps)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bank_host holds %llu values, the bank has %llu",
+                    (unsigned long long)capacity, (unsigned long long)d.up * d.taps);
+    resample::fill_bank(d, bank_host);
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_resampler_create(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta, double rolloff,
+                              iris_resampler_handle** out) {
+    IRIS_ABI_BEGIN
+    if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    resample::Design d;
+    TRY(resampler_plan(rate_in, rate_out, zeros, beta, rolloff, &d));
+    std::vector<float> bank((size_t)d.up * d.taps);
+    resample::fill_bank(d, bank.data());
+    const int stride = resample::row_stride(d.taps);
+    std::vector<float> padded((size_t)d.up * stride, 0.f);             // rows start on 16-byte boundaries
+    for (int p = 0; p < d.up; ++p) memcpy(padded.data() + (size_t)p * stride, bank.data() + (size_t)p * d.taps, sizeof(float) * d.taps);
+    iris_resampler_handle* h = new (std::nothrow) iris_resampler_handle;
+    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    h->d = d;
+    hipError_t e = hipGetDevice(&h->device);
+    if (e == hipSuccess) e = hipMalloc(&h->bank, padded.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->bank, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->bank) (void)hipFree(h->bank);
+        delete h;
+        return fail(IRIS_HIFIGAN_HIP_ERROR, "resampler bank upload failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_resampler_destroy(iris_resampler_handle* h) {
+    if (!h) return IRIS_HIFIGAN_OK;
+    if (h->bank) (void)hipFree(h->bank);
+    delete h;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_resampler_info(const iris_resampler_handle* h, int32_t* up, int32_t* down, int32_t* taps, int32_t* half_width) {
+    if (!h || !up || !down || !taps || !half_width) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    *up = h->d.up; *down = h->d.down; *taps = h->d.taps; *half_width = h->d.half_width;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_resampler_out_range(const iris_resampler_handle* h, int64_t origin, int64_t L, int64_t* n_lo, int64_t* n_count) {
+    if (!h || !n_lo || !n_count) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    if (origin < 0 || L < 0 || origin > resample::kMaxOrigin || L > resample::kMaxOrigin)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin and L must lie in [0, 2^40], got %lld and %lld", (long long)origin, (long long)L);
+    long long lo = 0, count = 0;
+    resample::out_range(h->d, origin, L, &lo, &count);
+    *n_lo = lo; *n_count = count;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev,
+                               int32_t row_scale, int64_t origin, float* out_f32_dev, int16_t* out_pcm_dev, float* peak_dev,
+                               int32_t normalize, float peak_target, void* stream_) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (origin < 0 || origin > resample::kMaxOrigin)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin must lie in [0, 2^40], got %lld", (long long)origin);
+    if (normalize && !(peak_target > 0.f && peak_target <= 1.f))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "peak_target must lie in (0, 1], got %g", (double)peak_target);
+    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
+    if (!wav_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "wav_dev is NULL");
+    if (normalize && (!out_f32_dev || !out_pcm_dev || !peak_dev))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "normalising needs out_f32_dev, out_pcm_dev and peak_dev");
+    if (!normalize && !out_f32_dev && !out_pcm_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "no output: out_f32_dev and out_pcm_dev are NULL");
+    if (!normalize && out_f32_dev && out_pcm_dev)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "one output form per call: fp32 or int16 (both only when normalising)");
+    if (lengths_dev && row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale must be >= 1, got %d", row_scale);
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    if (L > (1 << 30)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%d samples per item exceed 2^30", L);
+    long long n_lo = 0, n_count = 0;
+    resample::out_range(h->d, origin, L, &n_lo, &n_count);
+    if (n_count > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%lld outputs per item exceed 2^31 - 1", n_count);
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (normalize) HIP_TRY(hipMemsetAsync(peak_dev, 0, sizeof(float) * B, stream));
+    if (n_count == 0) return IRIS_HIFIGAN_OK;                       // (a short window between two output positions)
+    resample::ResampleLaunch a;
+    a.wav = wav_dev; a.lengths = lengths_dev; a.row_scale = lengths_dev ? row_scale : 1; a.bank = h->bank;
+    a.y = out_f32_dev; a.pcm = normalize ? nullptr : out_pcm_dev; a.peak = normalize ? reinterpret_cast<unsigned*>(peak_dev) : nullptr;
+    a.B = B; a.L = L; a.N = (int)n_count;
+    a.up = h->d.up; a.down = h->d.down; a.taps = h->d.taps; a.half_width = h->d.half_width;
+    a.origin = origin; a.n_lo = n_lo;
+    HIP_TRY(resample::launch_resample(a, stream));
+    if (normalize) {
+        // every item's row is already 0 past its own outputs, so the plain form of the output stage converts it
+        const pcm::PcmLaunch q{out_f32_dev, nullptr, 1, out_pcm_dev, peak_dev, B, (int)n_count, peak_target};
+        HIP_TRY(pcm::launch_pcm_normalize(q, true, stream));
+    }
+    return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 

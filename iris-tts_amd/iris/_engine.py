@@ -102,6 +102,7 @@ class GeneratorEngine:
         _native.check("iris_hifigan_hop_length", self.lib.iris_hifigan_hop_length(self._handle, ctypes.byref(hop)))
         self.hop_length = int(hop.value)
         self._workspace: Optional[torch.Tensor] = None
+        self._wave: Optional[torch.Tensor] = None      # forward_resampled: the fp32 waveform between the two stages
         self._graphs: dict = {}
         self._profiling = 0
         # 0 = always eager; the environment variable switches the drop-in wrappers (which construct engines themselves)
@@ -116,6 +117,7 @@ class GeneratorEngine:
             self._handle = ctypes.c_void_p()
         self._graphs = {}
         self._workspace = None
+        self._wave = None
 
     def __del__(self):
         try:
@@ -143,6 +145,7 @@ class GeneratorEngine:
         captured graphs that point into it; the next forward allocates what it needs."""
         self._graphs = {}
         self._workspace = None
+        self._wave = None
 
     def forward(self, mel: torch.Tensor, out: Optional[torch.Tensor] = None, dtype: Optional[str] = None,
                 lengths=None) -> torch.Tensor:
@@ -252,6 +255,37 @@ class GeneratorEngine:
             self._handle, ptr(mel), batch, frames, ptr(lengths_dev), ptr(out), ptr(wav), ptr(peaks), int(bool(normalize)),
             ctypes.c_float(float(peak_target)), ptr(ws), ctypes.c_uint64(ws.numel()), code, ctypes.c_void_p(stream)))
         return (out, peaks) if normalize else out
+
+    def forward_resampled(self, mel: torch.Tensor, resampler, dtype: Optional[str] = None, lengths=None,
+                          origin_frames: int = 0, pcm16: bool = False, normalize: bool = False, peak_target: float = 0.95):
+        """The forward with the sample-rate conversion stage behind it: mel [B, in_channels, T] -> the waveform at
+        ``resampler.rate_out``, ``[B, n_count]`` with ``n_count = resampler.out_range(origin_frames * hop, hop * T)[1]``, bit
+        for bit ``resampler.forward(self.forward(mel, ...), ...)``.  The generator writes its fp32 waveform into a buffer the
+        engine owns (it grows to the largest shape seen) and ``resampler`` (an ``iris.resample.Resampler`` on this device)
+        reads it on the same stream: nothing crosses to the host in between.
+
+        ``dtype`` and ``lengths`` as in ``forward`` (lengths: "f32" only, refused otherwise exactly as there); the second
+        stage bounds item b by ``hop * lengths[b]`` samples, so its outputs past its own count are 0.  ``origin_frames``: the
+        utterance-global index of ``mel[:, :, 0]`` for a window of a longer mel (``StreamingVocoder``).  ``pcm16``,
+        ``normalize``, ``peak_target`` as in ``Resampler.forward``.  Inside a caller's ``torch.cuda.graph`` capture it works
+        once one eager call of the shape has sized the buffers (and ``prepare(dtype)`` has run)."""
+        if resampler.device != self.device:
+            raise ValueError(f"resampler is on {resampler.device}, engine on {self.device}")
+        if mel.dim() != 3 or mel.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"expected mel [B, {self.cfg.in_channels}, T], got {tuple(mel.shape)}")
+        if int(origin_frames) < 0:
+            raise ValueError(f"origin_frames must be >= 0, got {origin_frames}")
+        batch, _, frames = mel.shape
+        lengths_host = None if lengths is None else _check_lengths(lengths, batch, frames)
+        n = batch * frames * self.hop_length
+        if self._wave is None or self._wave.numel() < n:
+            self._wave = None  # release before growing
+            self._wave = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+        wav = self._wave[:n].view(batch, frames * self.hop_length)
+        self.forward(mel, out=wav, dtype=dtype, lengths=lengths_host)
+        return resampler.forward(wav, lengths=lengths_host, row_scale=self.hop_length,
+                                 origin=int(origin_frames) * self.hop_length, pcm16=pcm16, normalize=normalize,
+                                 peak_target=peak_target)
 
     # -- hipGraph replay ---------------------------------------------------------------------------
     def forward_graph(self, mel: torch.Tensor, dtype: Optional[str] = None) -> torch.Tensor:

@@ -160,6 +160,18 @@ SYMBOLS = {
     "iris_postnet_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
 }
 
+# the sample-rate conversion stage (iris.resample): bound by load() like SYMBOLS
+_i64, _d = _c.c_int64, _c.c_double
+_ip, _i64p = _c.POINTER(_i32), _c.POINTER(_i64)
+RESAMPLER_SYMBOLS = {
+    "iris_resampler_design": (_i32, [_i32, _i32, _i32, _d, _d, _ip, _ip, _ip, _fp, _u64]),
+    "iris_resampler_create": (_i32, [_i32, _i32, _i32, _d, _d, _c.POINTER(_vp)]),
+    "iris_resampler_destroy": (_i32, [_vp]),
+    "iris_resampler_info": (_i32, [_vp, _ip, _ip, _ip, _ip]),
+    "iris_resampler_out_range": (_i32, [_vp, _i64, _i64, _i64p, _i64p]),
+    "iris_resampler_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _f, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -185,7 +197,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in SYMBOLS.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

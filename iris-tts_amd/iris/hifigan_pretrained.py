@@ -308,6 +308,23 @@ class HiFiGANGenerator:
         pcm = (pcm[0] if normalize else pcm).cpu().numpy()
         return pcm[0] if squeeze_batch else pcm
 
+    def infer_resampled(self, mel: np.ndarray, sample_rate_out: int, pcm16: bool = False, normalize: bool = False,
+                        peak_target: float = 0.95) -> np.ndarray:
+        """``__call__`` with the waveform converted from 22 050 Hz to ``sample_rate_out`` on the GPU
+        (``GeneratorEngine.forward_resampled`` with the default filter of ``iris.resample``): float32, or int16 with
+        ``pcm16`` (``normalize``: every item scaled to ``peak_target`` at its own peak first)."""
+        from .resample import shared_resampler
+        mel = np.asarray(mel)
+        squeeze_batch = mel.ndim == 2
+        if squeeze_batch:
+            mel = mel[np.newaxis, ...]
+        eng = self.model.engine()
+        mel_tensor = torch.from_numpy(np.ascontiguousarray(mel)).float().to(eng.device)
+        out = eng.forward_resampled(mel_tensor, shared_resampler(sample_rate_out, eng.device), pcm16=pcm16,
+                                    normalize=normalize, peak_target=peak_target)
+        out = (out[0] if normalize else out).cpu().numpy()
+        return out[0] if squeeze_batch else out
+
     def infer_batch(self, mels: Sequence[np.ndarray], pcm16: bool = False) -> List[np.ndarray]:
         """List of mels [n_mels, T_i] of any lengths -> list of waveforms [hop * T_i], in ONE ragged fp32 forward
         (iris.batching).  Each waveform is bit for bit what ``self(mel)`` returns for that mel alone; ``pcm16=True``: what
@@ -346,11 +363,12 @@ def get_pretrained_hifigan(checkpoint_path: Optional[Union[str, Path]] = None,
 
 
 def infer_hifigan(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length: Optional[int] = None,
-                  checkpoint_path: Optional[Union[str, Path]] = None) -> np.ndarray:
+                  checkpoint_path: Optional[Union[str, Path]] = None, sample_rate_out: Optional[int] = None) -> np.ndarray:
     """Entry point for ``--vocoder_entry iris.hifigan_pretrained:infer_hifigan`` (reference :286-317).
-    ``sample_rate`` and ``hop_length`` are accepted and ignored, as in the reference."""
+    ``sample_rate`` and ``hop_length`` are accepted and ignored, as in the reference.  ``sample_rate_out``: the waveform
+    converted from the generator's 22 050 Hz to that rate on the GPU (``HiFiGANGenerator.infer_resampled``)."""
     vocoder = get_pretrained_hifigan(checkpoint_path)
-    audio = vocoder(mel)
+    audio = vocoder(mel) if sample_rate_out is None else vocoder.infer_resampled(mel, sample_rate_out)
     if audio.ndim == 2 and audio.shape[0] == 1:
         audio = audio[0]
     return audio
@@ -358,11 +376,15 @@ def infer_hifigan(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length
 
 def infer_hifigan_pcm16(mel: np.ndarray, sample_rate: Optional[int] = None, hop_length: Optional[int] = None,
                         checkpoint_path: Optional[Union[str, Path]] = None, normalize: bool = False,
-                        peak_target: float = 0.95) -> np.ndarray:
+                        peak_target: float = 0.95, sample_rate_out: Optional[int] = None) -> np.ndarray:
     """``infer_hifigan`` returning 16-bit PCM (int16) converted on the GPU -- the entry point for
     ``--vocoder_entry iris.hifigan_pretrained:infer_hifigan_pcm16`` (``python -m iris.synthesis_output --pcm16``), same calling
     convention.  ``normalize``: scale the utterance to ``peak_target`` at its peak first (``HiFiGANGenerator.infer_pcm16``)."""
-    pcm = get_pretrained_hifigan(checkpoint_path).infer_pcm16(mel, normalize=normalize, peak_target=peak_target)
+    voc = get_pretrained_hifigan(checkpoint_path)
+    if sample_rate_out is None:
+        pcm = voc.infer_pcm16(mel, normalize=normalize, peak_target=peak_target)
+    else:
+        pcm = voc.infer_resampled(mel, sample_rate_out, pcm16=True, normalize=normalize, peak_target=peak_target)
     if pcm.ndim == 2 and pcm.shape[0] == 1:
         pcm = pcm[0]
     return pcm

@@ -70,13 +70,31 @@ class MelToWavePipeline:
                              "GeneratorEngine.forward")
         return fn
 
-    def infer(self, mel, pcm16: bool = False, normalize: bool = False):
+    def _resampled_fn(self) -> Callable:
+        fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_resampled", None)
+        if fn is None:
+            raise ValueError("resampler= needs a vocoder with a device resampling stage: construct the pipeline with a bound "
+                             "GeneratorEngine.forward")
+        return fn
+
+    def infer(self, mel, pcm16: bool = False, normalize: bool = False, resampler=None):
         """The whole utterance.  ``pcm16=True``: an int16 device tensor, converted by the vocoder's last launch
         (``GeneratorEngine.forward_pcm16``), chunked like the fp32 path.  ``normalize=True`` (with pcm16): every item scaled
         to 0.95 at its own peak first; the peak is the whole utterance's, so the refined mel is vocoded in ONE forward,
-        and ``(pcm, peaks)`` is returned."""
+        and ``(pcm, peaks)`` is returned.
+
+        ``resampler`` (an ``iris.resample.Resampler``): the waveform at its rate instead of 22 050 Hz
+        (``GeneratorEngine.forward_resampled``) -- fp32 chunked like the plain path, each window at its own origin, so the
+        result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
+        if resampler is not None:
+            fwd = self._resampled_fn()
+            if pcm16:
+                return fwd(self.refine(mel), resampler, pcm16=True, normalize=normalize)
+            sv = self.streamer
+            return StreamingVocoder(sv.forward, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames,
+                                    halo_frames=sv.halo_frames, group_chunks=sv.group_chunks, config=self.config, resampler=resampler).infer(self.refine(mel))
         if not pcm16:
             return self.streamer.infer(self.refine(mel))
         fwd = self._pcm16_fn()
@@ -88,7 +106,7 @@ class MelToWavePipeline:
 
     __call__ = infer
 
-    def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False) -> List[torch.Tensor]:
+    def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False, resampler=None) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform
         ``[hop * T_i]`` per utterance, with ONE PostNet pass and ONE vocoder forward for the whole list: the mels are padded
         to the longest (``pack_mels``) and both stages bound every layer of item i by ``T_i`` (``forward_device(...,
@@ -96,7 +114,8 @@ class MelToWavePipeline:
         let the padded frames reach the last frames of every short item (``iris.batching``).  The stages must take
         ``lengths``; a vocoder dtype without a ragged forward (bf16, f32s) fails as ``engine.forward(lengths=...)`` does.
         ``pcm16=True``: int16 waveforms from ``GeneratorEngine.forward_pcm16``; with ``normalize=True`` each is scaled to
-        0.95 at its own peak first."""
+        0.95 at its own peak first.  ``resampler``: every waveform at its rate (``GeneratorEngine.forward_resampled`` with the
+        same lengths: item i has ``resampler.out_range(0, hop * T_i)[1]`` samples, bit for bit its one-item conversion)."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
         mels = list(mels)
@@ -106,6 +125,11 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
+        if resampler is not None:
+            wav = self._resampled_fn()(padded, resampler, lengths=lengths, pcm16=pcm16, normalize=normalize)
+            wav = wav[0] if normalize else wav
+            hop = self.streamer.hop_length
+            return [wav[i, :resampler.out_range(0, hop * int(t))[1]] for i, t in enumerate(lengths)]
         if pcm16:
             wav = self._pcm16_fn()(padded, lengths=lengths, normalize=normalize)
             wav = wav[0] if normalize else wav

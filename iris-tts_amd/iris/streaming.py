@@ -19,9 +19,10 @@ from typing import Callable, Iterator, List, Optional
 RECEPTIVE_FIELD_FRAMES = 13  # ceil(12.64); V1 config (== receptive_field_frames(GeneratorConfig()))
 
 
-def receptive_field_frames(cfg) -> int:
+def receptive_field_frames(cfg, extra_samples: int = 0) -> int:
     """Mel frames of context on either side that can reach the samples of one frame, for any generator
-    configuration (``GeneratorConfig`` or an object with the same attributes).
+    configuration (``GeneratorConfig`` or an object with the same attributes).  ``extra_samples``: the frame's samples
+    and that many more on either side -- what a filter behind the generator reads (``iris.resample``).
 
     Exact interval propagation from the output back to the mel through the layers of
     ``HiFiGANModel.forward`` (src/iris/hifigan_pretrained.py:123-143): a Conv1d(k, dilation d, 'same')
@@ -33,7 +34,7 @@ def receptive_field_frames(cfg) -> int:
     for u in cfg.upsample_rates:
         hop *= int(u)
     c = 4096                                    # any frame far from the edges
-    a, b = c * hop, c * hop + hop - 1
+    a, b = c * hop - int(extra_samples), c * hop + hop - 1 + int(extra_samples)
     post = (int(getattr(cfg, "post_kernel_size", 7)) - 1) // 2
     a, b = a - post, b + post
     branches = list(zip(cfg.resblock_kernel_sizes, cfg.resblock_dilation_sizes))
@@ -81,14 +82,36 @@ class StreamingVocoder:
     have whatever dtype ``forward`` returns: fp32, or int16 with ``GeneratorEngine.forward_pcm16``.  Peak normalisation
     needs the peak of the whole utterance, which no chunk knows: the streaming classes do not offer it (pass a forward
     without ``normalize``; normalise one-shot with ``forward_pcm16(mel, normalize=True)``).
+
+    ``resampler`` (an ``iris.resample.Resampler``; ``forward`` must then be a bound ``GeneratorEngine.forward``): every
+    window goes through ``engine.forward_resampled`` with the window's first frame as its origin, so the filter runs at the
+    utterance's own phase, and a chunk ``[start, stop)`` yields the global outputs ``n_lo(start * hop) ..
+    n_lo(stop * hop) - 1`` at the resampler's rate: the chunks partition the one-shot ``forward_resampled`` output and
+    equal it bit for bit.  The halo must cover the filter's ``half_width`` input samples beside the generator's own
+    receptive field (for V1 and the default halo: up to 93 samples, which every default filter from 8 kHz up stays under).
     """
 
     def __init__(self, forward: Callable, hop_length: Optional[int] = None, chunk_frames: int = 256,
-                 halo_frames: Optional[int] = None, group_chunks: int = 1, config=None):
+                 halo_frames: Optional[int] = None, group_chunks: int = 1, config=None, resampler=None):
         """``config``: the generator's ``GeneratorConfig``; when given, the hop length and the minimal halo are
         computed from it (``receptive_field_frames``), otherwise the V1 values (256, 13) are assumed -- pass the
         config for any other architecture, or the seams silently differ from the one-shot output."""
-        need = receptive_field_frames(config) if config is not None else RECEPTIVE_FIELD_FRAMES
+        self._resampled = None
+        if resampler is None:
+            need = receptive_field_frames(config) if config is not None else RECEPTIVE_FIELD_FRAMES
+        else:
+            engine = getattr(forward, "__self__", None)
+            self._resampled = getattr(engine, "forward_resampled", None)
+            if self._resampled is None:
+                raise ValueError("resampler= needs a bound GeneratorEngine.forward as the forward")
+            if config is None:
+                config = engine.cfg
+            hw, hop = int(resampler.half_width), int(config.hop_length)
+            if halo_frames is not None and hw > halo_frames * hop:
+                raise ValueError(f"the resampler reads {hw} samples on either side of an output, more than the halo of "
+                                 f"{halo_frames} frames ({halo_frames * hop} samples)")
+            need = receptive_field_frames(config, extra_samples=hw)     # the generator's context of the samples the filter reads
+        self.resampler = resampler
         if halo_frames is None:
             halo_frames = need
         if halo_frames < need:
@@ -126,16 +149,22 @@ class StreamingVocoder:
             n = 1 if (self.group_chunks == 1 or i == 0) else min(self.group_chunks, len(chunks) - i)
             group = chunks[i:i + n]
             win_start, win_stop = group[0].win_start, group[-1].win_stop
-            wav = self.forward(mel[:, :, win_start:win_stop])
-            for c in group:
-                yield wav[:, (c.start - win_start) * self.hop_length:(c.stop - win_start) * self.hop_length]
+            if self.resampler is None:
+                wav = self.forward(mel[:, :, win_start:win_stop])
+                for c in group:
+                    yield wav[:, (c.start - win_start) * self.hop_length:(c.stop - win_start) * self.hop_length]
+            else:
+                wav = self._resampled(mel[:, :, win_start:win_stop], self.resampler, origin_frames=win_start)
+                n_lo = [self.resampler.out_range(f * self.hop_length, 0)[0] for f in (win_start, *(c.start for c in group), group[-1].stop)]
+                for k in range(len(group)):
+                    yield wav[:, n_lo[k + 1] - n_lo[0]:n_lo[k + 2] - n_lo[0]]
             i += n
 
     def infer(self, mel):
         """Concatenation of ``stream(mel)``; equals the one-shot forward of the whole mel."""
         parts = list(self.stream(mel))
         if not parts:
-            return self.forward(mel)
+            return self.forward(mel) if self.resampler is None else self._resampled(mel, self.resampler)
         if hasattr(parts[0], "detach"):
             import torch
             return torch.cat(parts, dim=1)

@@ -80,6 +80,16 @@ def pcm16_from_float(audio, normalize: bool = False, peak_target: float = 0.95) 
     return np.round(np.clip(w, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)).astype("<i2")
 
 
+RESAMPLE_TO_RANGE = (4000, 192000)     # what the device resampler admits (include/iris_hifigan.h)
+
+
+def check_resample_to(hz) -> int:
+    """``--resample_to``: an integer rate inside ``RESAMPLE_TO_RANGE`` (the library decides the rest: up <= 640, taps <= 256)."""
+    if isinstance(hz, bool) or int(hz) != hz or not RESAMPLE_TO_RANGE[0] <= int(hz) <= RESAMPLE_TO_RANGE[1]:
+        raise ValueError(f"resample_to must be an integer rate in [{RESAMPLE_TO_RANGE[0]}, {RESAMPLE_TO_RANGE[1]}] Hz, got {hz}")
+    return int(hz)
+
+
 def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 22050) -> Path:
     """Writes a mono WAV.  Float samples: ``soundfile`` is used when importable (the reference's writer,
     ``synthesize.py:211-213``); otherwise the standard-library ``wave`` module writes 16-bit PCM
@@ -122,21 +132,31 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 
 
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
-                  sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None) -> np.ndarray:
+                  sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None,
+                  resample_to: Optional[int] = None) -> np.ndarray:
     """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
     int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
     ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
     ``normalize=True, peak_target=`` (an entry that converts on the device, ``infer_hifigan_pcm16``) when it returns PCM; a float result is
-    normalised on the host (``pcm16_from_float``)."""
+    normalised on the host (``pcm16_from_float``).
+    ``resample_to``: the entry is called with ``sample_rate_out=`` (``infer_hifigan`` / ``infer_hifigan_pcm16`` then convert
+    the generator's 22 050 Hz on the GPU, ``iris.resample``) and the WAV header carries that rate; ``sample_rate`` keeps
+    labelling only, as in the reference."""
     fn = resolve_vocoder_entry(vocoder_entry)
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
     if normalize_peak is not None:
         _check_peak_target(normalize_peak)
-    if normalize_peak is not None and getattr(fn, "returns_pcm16", False):
-        audio = fn(mel, sample_rate, hop_length, normalize=True, peak_target=float(normalize_peak))
+    extra = {}
+    if resample_to is not None:
+        extra["sample_rate_out"] = check_resample_to(resample_to)
+        wav_rate = extra["sample_rate_out"]
     else:
-        audio = fn(mel, sample_rate, hop_length)
+        wav_rate = sample_rate
+    if normalize_peak is not None and getattr(fn, "returns_pcm16", False):
+        audio = fn(mel, sample_rate, hop_length, normalize=True, peak_target=float(normalize_peak), **extra)
+    else:
+        audio = fn(mel, sample_rate, hop_length, **extra)
     if isinstance(audio, np.ndarray) and audio.dtype == np.int16:
         audio = audio.squeeze() if audio.ndim > 1 else audio
         if audio.ndim != 1:
@@ -145,8 +165,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
         audio = to_mono_float32(audio)
         if normalize_peak is not None:
             audio = pcm16_from_float(audio, normalize=True, peak_target=normalize_peak)
-    logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / sample_rate:.2f}s")
-    write_wav(output_wav, audio, sample_rate)
+    logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / wav_rate:.2f}s")
+    write_wav(output_wav, audio, wav_rate)
     return audio
 
 
@@ -162,6 +182,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help=f"convert to 16-bit PCM on the GPU (vocoder entry {PCM16_VOCODER_ENTRY} unless --vocoder_entry is given)")
     parser.add_argument("--normalize_peak", type=float, default=None, metavar="X",
                         help="scale the utterance so that its peak is X, 0 < X <= 1 (the reference demo uses 0.95)")
+    parser.add_argument("--resample_to", type=int, default=None, metavar="HZ",
+                        help="convert the generator's 22050 Hz waveform to HZ on the GPU (8000, 16000, 44100, 48000, ...); the "
+                             "WAV header then carries HZ (--sample_rate keeps labelling only)")
     return parser
 
 
@@ -170,11 +193,17 @@ def main(argv: Optional[list] = None) -> int:
     args = parser.parse_args(argv)
     if args.normalize_peak is not None and not 0.0 < args.normalize_peak <= 1.0:
         parser.error(f"--normalize_peak must lie in (0, 1], got {args.normalize_peak}")
+    if args.resample_to is not None:
+        try:
+            check_resample_to(args.resample_to)
+        except ValueError as exc:
+            parser.error(f"--{exc}")
     if args.pcm16 and args.vocoder_entry == DEFAULT_VOCODER_ENTRY:
         args.vocoder_entry = PCM16_VOCODER_ENTRY
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
-    vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak)
+    vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak,
+                  args.resample_to)
     return 0
 
 

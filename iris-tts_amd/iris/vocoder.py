@@ -218,9 +218,16 @@ class HiFiGANVocoder:
         self.model.save_weights(weights_path)
         logger.info(f"Saved weights to {weights_path}")
 
-    def infer(self, mel: np.ndarray) -> np.ndarray:
-        """[mel_channels, time] -> [samples];  [batch, mel_channels, time] -> [batch, samples]."""
+    def infer(self, mel: np.ndarray, sample_rate_out: Optional[int] = None) -> np.ndarray:
+        """[mel_channels, time] -> [samples];  [batch, mel_channels, time] -> [batch, samples].  ``sample_rate_out``: the
+        waveform converted from 22 050 Hz to that rate on the GPU (``GeneratorEngine.forward_resampled``, default filter)."""
         mel = np.asarray(mel)
+        if sample_rate_out is not None:
+            from .resample import shared_resampler
+            eng = self.model.engine()
+            x = torch.from_numpy(np.ascontiguousarray(mel if mel.ndim == 3 else mel[np.newaxis], dtype=np.float32)).to(eng.device)
+            audio = eng.forward_resampled(x, shared_resampler(sample_rate_out, eng.device)).cpu().numpy()
+            return audio[0] if mel.ndim == 2 else audio
         squeeze_batch = False
         if mel.ndim == 2:
             mel = mel.T[np.newaxis, ...]            # -> [1, time, mel]
