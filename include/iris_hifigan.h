@@ -436,6 +436,51 @@ int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, i
                                float* out_f32_dev, int16_t* out_pcm_dev, float* peak_dev,
                                int32_t normalize, float peak_target, void* stream);
 
+/* ---- VAE decoder in front of the PostNet (csrc/vae_decoder.h) ------------------------------------------
+ * The inference half of the reference's TextConditionedVAE (src/iris/vae.py:448-482, generate()): frame-level text
+ * conditioning [B, T, cond_dim] and a latent prior sample [B, T / 2^down_stages, latent_dim] in, the mel [B, n_mels, T]
+ * (channels-first: what iris_postnet_forward and iris_hifigan_forward read) and optionally the frame residual
+ * [B, T, cond_dim] out.  fp32 throughout.
+ * weights_host, in this order, every tensor followed by its bias (Dense and Conv1D kernels transposed to
+ * [C_out][C_in][k] unless stated; iris.vae.TextConditionedVAE.blob() writes it, iris_vae_decoder_weight_count sizes it):
+ *   down_cond_proj; downsample.blocks[s] (k = 5) for each stage;
+ *   per coupling j: cond_proj [latent/2][C]; then in the Keras layouts net_pre [3][latent/2][flow_hidden],
+ *                   net_post [flow_hidden][latent/2], film.proj [latent/2][latent];
+ *   latent_dec_proj in the Keras layout [latent][C];
+ *   per decoder block: conv (k = wavenet_kernel_size, dilation 2^(i % 4)); film.proj [2C][C]; res_proj;
+ *   upsample.refine[s] (k = 5) for each stage; out_proj; residual_proj.
+ * Configurations the kernels cannot take -- cond_dim or model_channels not a multiple of 4, model_channels > 256, an even
+ * wavenet_kernel_size, a tile beyond the 160 KB LDS -- return IRIS_HIFIGAN_UNSUPPORTED; an odd latent_dim, a wrong blob size
+ * and a T that is not a multiple of 2^down_stages return IRIS_HIFIGAN_INVALID_ARGUMENT (the caller pads, as
+ * scripts/synthesize.py:117-122 does); a short workspace returns IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches. */
+typedef struct iris_vae_decoder_config {
+    int32_t n_mels, cond_dim, model_channels, latent_dim, decoder_blocks, wavenet_kernel_size, down_stages, flow_layers,
+            flow_hidden;
+} iris_vae_decoder_config;
+typedef struct iris_vae_decoder_handle iris_vae_decoder_handle;
+
+/* Host only. */
+int32_t iris_vae_decoder_weight_count(const iris_vae_decoder_config* cfg, uint64_t* count);
+int32_t iris_vae_decoder_create(const iris_vae_decoder_config* cfg, const float* weights_host, uint64_t n_weights,
+                                iris_vae_decoder_handle** out);
+int32_t iris_vae_decoder_destroy(iris_vae_decoder_handle* h);
+int32_t iris_vae_decoder_workspace_bytes(const iris_vae_decoder_handle* h, int32_t B, int32_t T, uint64_t* bytes);
+/* Asynchronous on `stream`, allocates nothing.  residual_out_dev may be NULL: residual_proj is then not launched and the
+ * mel is bit for bit the same. */
+int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
+                                 float* mel_out_dev, float* residual_out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                 void* stream);
+/* Host only: kernel launches of one forward that asks for the residual (one fewer without it):
+ * 3 + 2 * down_stages + decoder_blocks + 2. */
+int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n);
+/* Host only, for tests: where a forward of (B, T) leaves an intermediate [B, T / 2^down_stages, model_channels] in its
+ * workspace (valid until the next forward on that workspace). */
+#define IRIS_VAE_TAP_LAT_COND 0   /* downsample(down_cond_proj(cond)) */
+#define IRIS_VAE_TAP_DEC_IN 1     /* latent_dec_proj(flow(z_prior, reverse)) */
+#define IRIS_VAE_TAP_DEC_OUT 2    /* after the last decoder block */
+int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
+                             uint64_t* floats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,324 @@
+// iris_vae_decoder.hip -- the iris_vae_decoder_* entry points of include/iris_hifigan.h over csrc/vae_decoder.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <new>
+#include <vector>
+
+#include "generator_internal.h"
+#define IRIS_KERNELS_ONLY      // conv_mfma_f32.h: types and weight packers only -- its kernels and launch code live in iris_hifigan.o
+#include "conv_mfma_f32.h"
+#undef IRIS_KERNELS_ONLY
+#include "vae_decoder.h"
+
+using namespace iris;
+
+// ------------------------------------------------------------------------------------------------
+// VAE decoder in front of the PostNet (TextConditionedVAE.generate, src/iris/vae.py:448-482; csrc/vae_decoder.h)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct VaeConv { int C_in = 0, C_out = 0, k = 1; size_t w_off = 0, b_off = 0; };   // float offsets into the device blob
+
+}  // namespace
+
+struct iris_vae_decoder_handle {
+    iris_vae_decoder_config cfg;
+    VaeConv cond_proj, out_proj, residual_proj, cond_gemm;
+    std::vector<VaeConv> down, up, dec_conv, dec_res;
+    size_t flow_off = 0, dec_proj_off = 0;       // raw (Keras-layout) flow couplings; latent_dec_proj kernel + bias
+    int film_cols = 0, ce_off = 0, ce_stride = 0;  // columns of the conditioning GEMM; where the couplings' cond_proj start
+    float* blob = nullptr;
+    size_t blob_floats = 0;
+    int device = 0;
+    bool host_only = false;
+};
+
+namespace {
+
+int vae_validate(const iris_vae_decoder_config* c) {
+    if (!c) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "config is NULL");
+    if (c->n_mels < 1 || c->cond_dim < 1 || c->model_channels < 1 || c->latent_dim < 1 || c->decoder_blocks < 0 ||
+        c->wavenet_kernel_size < 1 || c->down_stages < 0 || c->flow_layers < 0 || c->flow_hidden < 1)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "VAE decoder sizes must be positive");
+    if (c->latent_dim & 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "latent_dim %d must be even (vae.py:223)", c->latent_dim);
+    if ((c->cond_dim & 3) || (c->model_channels & 3))
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "cond_dim %d and model_channels %d must be multiples of 4 (16-byte rows)",
+                    c->cond_dim, c->model_channels);
+    if (c->model_channels > 32 * vae::kGemmMaxWaves)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "model_channels %d exceeds %d (one block holds a WaveNet block's whole row)",
+                    c->model_channels, 32 * vae::kGemmMaxWaves);
+    if (!(c->wavenet_kernel_size & 1))
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "wavenet_kernel_size %d must be odd (symmetric 'same' padding)", c->wavenet_kernel_size);
+    if (c->down_stages > 8 || c->decoder_blocks > 64 || c->flow_layers > 64 || c->latent_dim > 256 || c->flow_hidden > 1024)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "down_stages <= 8, decoder_blocks, flow_layers <= 64, latent_dim <= 256, flow_hidden <= 1024");
+    const int C = c->model_channels;
+    const int dmax = c->decoder_blocks >= 4 ? 8 : (1 << (c->decoder_blocks > 0 ? c->decoder_blocks - 1 : 0));
+    const size_t lds_max = 160 * 1024;
+    if (vae::gemm_lds_bytes(C, C, c->wavenet_kernel_size, dmax, 1, true) > lds_max || vae::gemm_lds_bytes(C, C, 5, 1, 2, false) > lds_max ||
+        vae::gemm_lds_bytes(c->cond_dim, C, 1, 1, 1, false) > lds_max || vae::flow_lds_bytes(c->latent_dim, c->flow_hidden) > 64 * 1024)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "a tile of this configuration does not fit the 160 KB LDS");
+    return IRIS_HIFIGAN_OK;
+}
+
+uint64_t vae_weight_count(const iris_vae_decoder_config& c) {
+    const uint64_t C = c.model_channels, half = c.latent_dim / 2, FH = c.flow_hidden, k = c.wavenet_kernel_size;
+    uint64_t n = C * c.cond_dim + C;                                            // down_cond_proj
+    n += (uint64_t)c.down_stages * (C * C * 5 + C);                             // downsample.blocks
+    n += (uint64_t)c.flow_layers * (half * C + half + vae::flow_coupling_floats((int)half, (int)FH));
+    n += (uint64_t)c.latent_dim * C + C;                                        // latent_dec_proj
+    n += (uint64_t)c.decoder_blocks * ((C * C * k + C) + (2 * C * C + 2 * C) + (C * C + C));
+    n += (uint64_t)c.down_stages * (C * C * 5 + C);                             // upsample.refine
+    n += (uint64_t)c.n_mels * C + c.n_mels;                                     // out_proj
+    n += (uint64_t)c.cond_dim * C + c.cond_dim;                                 // residual_proj
+    return n;
+}
+
+struct VaeWs { size_t p, q, latcond, film, d0, da, db, total; };   // float offsets; every buffer starts on 256 bytes
+
+VaeWs vae_ws(const iris_vae_decoder_handle* h, int B, int T) {
+    const size_t C = h->cfg.model_channels, frames = (size_t)B * T, lat = frames >> h->cfg.down_stages;
+    VaeWs w;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
+    w.p = take(frames * C); w.q = take(frames * C);
+    w.latcond = take(lat * C); w.film = take(lat * h->film_cols);
+    w.d0 = take(lat * C); w.da = take(lat * C); w.db = take(lat * C);
+    w.total = off;
+    return w;
+}
+
+int vae_check_shape(const iris_vae_decoder_handle* h, int32_t B, int32_t T) {
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    if (B < 0 || T < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (T & ((1 << h->cfg.down_stages) - 1))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "T = %d is not a multiple of 2^down_stages = %d (pad the conditioning first)",
+                    T, 1 << h->cfg.down_stages);
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.z)", B);
+    if ((uint64_t)B * T * (uint64_t)h->cfg.model_channels > 0x7fffffffull * 64)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "B * T too large");
+    return IRIS_HIFIGAN_OK;
+}
+
+// the decoder block whose output is the last one: d0 -> da -> db -> da ...
+float* vae_dec_out(float* ws, const VaeWs& w, int i) { return ws + ((i & 1) ? w.db : w.da); }
+
+// Queues the launches of one forward (or, in a dry run, counts them).
+int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, int B, int T, float* mel, float* residual,
+                float* ws, hipStream_t stream) {
+    const iris_vae_decoder_config& c = h->cfg;
+    const int C = c.model_channels, S = c.down_stages, Tq = T >> S;
+    const VaeWs w = vae_ws(h, B, T);
+    const float* blob = h->blob;
+    auto gemm = [&](const float* x, const VaeConv& l, float* y, int L_in, int L_out) {
+        vae::GemmLaunch a; memset(&a, 0, sizeof(a));
+        a.x = x; a.wp = (const f32x4*)(blob + l.w_off); a.bias = blob + l.b_off; a.y = y;
+        a.L_in = L_in; a.L_out = L_out; a.C_in = l.C_in; a.C_out = l.C_out;
+        a.ks = l.k; a.dil = 1; a.stride = 1; a.pad_left = (l.k - 1) / 2;
+        return a;
+    };
+    // lat_cond = downsample(down_cond_proj(frame_cond))                                    vae.py:360-364
+    float* pq[2] = {ws + w.p, ws + w.q};
+    {
+        vae::GemmLaunch a = gemm(cond, h->cond_proj, S == 0 ? ws + w.latcond : pq[0], T, T);
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+    }
+    for (int s = 0; s < S; ++s) {
+        // Conv1D(k5, strides 2, 'same') on an even length: pad (1, 2), y[i] = sum_kap x[2i - 1 + kap] W[kap]; then GELU
+        vae::GemmLaunch a = gemm(pq[s & 1], h->down[s], s == S - 1 ? ws + w.latcond : pq[(s + 1) & 1], T >> s, T >> (s + 1));
+        a.stride = 2; a.pad_left = 1; a.gelu = 1;
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+    }
+    // every Dense(lat_cond) of the decoder at once: FiLM rows of each block, cond_proj of each coupling
+    {
+        vae::GemmLaunch a = gemm(ws + w.latcond, h->cond_gemm, ws + w.film, Tq, Tq);
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+    }
+    {   // z = flow(z_prior, reverse); d = latent_dec_proj(z)                                vae.py:466-468
+        vae::FlowLaunch f; memset(&f, 0, sizeof(f));
+        f.z = z; f.cond = ws + w.film; f.w = blob + h->flow_off; f.wdec = blob + h->dec_proj_off; f.y = ws + w.d0;
+        f.Tq = Tq; f.latent = c.latent_dim; f.FH = c.flow_hidden; f.n_flow = c.flow_layers; f.C = C;
+        f.ld = h->film_cols; f.ce_off = h->ce_off; f.ce_stride = h->ce_stride;
+        HIP_TRY(vae::launch_flow(f, B, stream));
+    }
+    const float* d = ws + w.d0;
+    for (int i = 0; i < c.decoder_blocks; ++i) {                                            // vae.py:57-67, 469-470
+        float* y = vae_dec_out(ws, w, i);
+        vae::GemmLaunch a = gemm(d, h->dec_conv[i], y, Tq, Tq);
+        a.dil = 1 << (i % 4); a.pad_left = a.dil * (a.ks - 1) / 2; a.gelu = 1;
+        a.film = ws + w.film; a.ld_film = h->film_cols; a.gamma_off = i * 2 * C; a.beta_off = i * 2 * C + C;
+        a.wp2 = (const f32x4*)(blob + h->dec_res[i].w_off); a.bias2 = blob + h->dec_res[i].b_off; a.res = d;
+        HIP_TRY(vae::launch_gemm(a, B, true, stream));
+        d = y;
+    }
+    for (int s = 0; s < S; ++s) {                                                           // vae.py:141-147
+        vae::GemmLaunch a = gemm(d, h->up[s], pq[s & 1], Tq << s, Tq << (s + 1));
+        a.up = 1; a.gelu = 1;
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+        d = pq[s & 1];
+    }
+    {
+        vae::GemmLaunch a = gemm(d, h->out_proj, mel, T, T);
+        a.y_channels_first = 1;                                                             // recon [B, n_mels, T], vae.py:480
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+    }
+    if (residual) {
+        vae::GemmLaunch a = gemm(d, h->residual_proj, residual, T, T);
+        HIP_TRY(vae::launch_gemm(a, B, false, stream));
+    }
+    return IRIS_HIFIGAN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t iris_vae_decoder_weight_count(const iris_vae_decoder_config* cfg, uint64_t* count) {
+    if (!count) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(vae_validate(cfg));
+    *count = vae_weight_count(*cfg);
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_decoder_create(const iris_vae_decoder_config* cfg, const float* weights_host, uint64_t n_weights,
+                                iris_vae_decoder_handle** out) {
+    IRIS_ABI_BEGIN
+    if (!weights_host || !out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(vae_validate(cfg));
+    const uint64_t expect = vae_weight_count(*cfg);
+    if (n_weights != expect)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "weight blob has %llu values, the VAE decoder needs %llu",
+                    (unsigned long long)n_weights, (unsigned long long)expect);
+    iris_vae_decoder_handle* h = new (std::nothrow) iris_vae_decoder_handle;
+    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    h->cfg = *cfg;
+    const iris_vae_decoder_config& c = h->cfg;
+    const int C = c.model_channels, half = c.latent_dim / 2, FH = c.flow_hidden;
+    const int hp = (half + 3) & ~3;                            // a coupling's cond_proj columns, padded to a 16-byte piece
+    h->film_cols = c.decoder_blocks * 2 * C + c.flow_layers * hp;
+    h->ce_off = c.decoder_blocks * 2 * C; h->ce_stride = hp;
+    std::vector<float> host;
+    auto reserve = [&](size_t n) { size_t o = host.size(); host.resize(o + ((n + 3) & ~(size_t)3), 0.f); return o; };
+    const float* src = weights_host;
+    // a conv in the layout [C_out][C_in][k] followed by its bias -> packed fragments + bias
+    auto conv = [&](VaeConv& l, int C_in, int C_out, int k) {
+        l.C_in = C_in; l.C_out = C_out; l.k = k;
+        l.w_off = reserve(packed_conv1d_floats(C_in, C_out, k));
+        pack_conv1d_weights(src, C_in, C_out, k, host.data() + l.w_off);
+        src += (size_t)C_in * C_out * k;
+        l.b_off = reserve(C_out);
+        memcpy(host.data() + l.b_off, src, sizeof(float) * C_out);
+        src += C_out;
+    };
+    conv(h->cond_proj, c.cond_dim, C, 1);
+    h->down.resize(c.down_stages); h->up.resize(c.down_stages);
+    h->dec_conv.resize(c.decoder_blocks); h->dec_res.resize(c.decoder_blocks);
+    for (auto& l : h->down) conv(l, C, C, 5);
+    // the conditioning GEMM: rows = output columns [film_cols][C]; dec block i at 2C i, coupling j at ce_off + hp j
+    std::vector<float> cw((size_t)h->film_cols * C, 0.f), cb(h->film_cols, 0.f);
+    const size_t per = vae::flow_coupling_floats(half, FH);
+    h->flow_off = reserve(per * c.flow_layers);
+    for (int j = 0; j < c.flow_layers; ++j) {
+        memcpy(cw.data() + (size_t)(h->ce_off + j * hp) * C, src, sizeof(float) * half * C); src += (size_t)half * C;
+        memcpy(cb.data() + h->ce_off + j * hp, src, sizeof(float) * half); src += half;
+        memcpy(host.data() + h->flow_off + j * per, src, sizeof(float) * per); src += per;
+    }
+    h->dec_proj_off = reserve((size_t)c.latent_dim * C + C);
+    memcpy(host.data() + h->dec_proj_off, src, sizeof(float) * ((size_t)c.latent_dim * C + C)); src += (size_t)c.latent_dim * C + C;
+    for (int i = 0; i < c.decoder_blocks; ++i) {
+        conv(h->dec_conv[i], C, C, c.wavenet_kernel_size);
+        memcpy(cw.data() + (size_t)i * 2 * C * C, src, sizeof(float) * 2 * C * C); src += (size_t)2 * C * C;
+        memcpy(cb.data() + (size_t)i * 2 * C, src, sizeof(float) * 2 * C); src += 2 * C;
+        conv(h->dec_res[i], C, C, 1);
+    }
+    for (auto& l : h->up) conv(l, C, C, 5);
+    conv(h->out_proj, C, c.n_mels, 1);
+    conv(h->residual_proj, C, c.cond_dim, 1);
+    {
+        VaeConv& l = h->cond_gemm;
+        l.C_in = C; l.C_out = h->film_cols; l.k = 1;
+        l.w_off = reserve(packed_conv1d_floats(C, h->film_cols, 1));
+        if (h->film_cols) pack_conv1d_weights(cw.data(), C, h->film_cols, 1, host.data() + l.w_off);
+        l.b_off = reserve(h->film_cols);
+        if (h->film_cols) memcpy(host.data() + l.b_off, cb.data(), sizeof(float) * h->film_cols);
+    }
+    h->blob_floats = host.size();
+    hipError_t e = hipGetDevice(&h->device);
+    if (e == hipSuccess) e = hipMalloc(&h->blob, h->blob_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->blob, host.data(), h->blob_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->blob) (void)hipFree(h->blob);
+        delete h;
+        return fail(IRIS_HIFIGAN_HIP_ERROR, "VAE decoder weight upload failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_vae_decoder_destroy(iris_vae_decoder_handle* h) {
+    if (!h) return IRIS_HIFIGAN_OK;
+    if (h->blob) (void)hipFree(h->blob);
+    delete h;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_decoder_workspace_bytes(const iris_vae_decoder_handle* h, int32_t B, int32_t T, uint64_t* bytes) {
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(vae_check_shape(h, B, T));
+    *bytes = (uint64_t)vae_ws(h, B, T).total * sizeof(float);
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
+                             uint64_t* floats) {
+    if (!byte_offset || !floats) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(vae_check_shape(h, B, T));
+    const VaeWs w = vae_ws(h, B, T);
+    size_t off;
+    if (which == IRIS_VAE_TAP_LAT_COND) off = w.latcond;
+    else if (which == IRIS_VAE_TAP_DEC_IN) off = w.d0;
+    else if (which == IRIS_VAE_TAP_DEC_OUT) off = h->cfg.decoder_blocks == 0 ? w.d0 : (((h->cfg.decoder_blocks - 1) & 1) ? w.db : w.da);
+    else return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "unknown tap %d", which);
+    *byte_offset = (uint64_t)off * sizeof(float);
+    *floats = ((uint64_t)B * T >> h->cfg.down_stages) * h->cfg.model_channels;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
+                                 float* mel_out_dev, float* residual_out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                 void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(vae_check_shape(h, B, T));
+    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    if (!cond_dev || !z_prior_dev || !mel_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    const uint64_t need = (uint64_t)vae_ws(h, B, T).total * sizeof(float);
+    if (workspace_bytes < need)
+        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
+                    (unsigned long long)workspace_bytes, (unsigned long long)need);
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    return vae_forward(h, cond_dev, z_prior_dev, B, T, mel_out_dev, residual_out_dev, (float*)workspace_dev, (hipStream_t)stream_);
+    IRIS_ABI_END
+}
+
+int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(vae_check_shape(h, B, T));
+    *n = 0;
+    if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
+    // the forward's own code in a dry run: every launch is counted instead of issued (no pointer is dereferenced)
+    DryRun d{nullptr, 0, 0, 256};
+    DryRun* const prev = dry_run_slot();
+    dry_run_slot() = &d;
+    float* const fake = reinterpret_cast<float*>(uintptr_t(256));
+    const int rc = vae_forward(const_cast<iris_vae_decoder_handle*>(h), fake, fake, B, T, fake, fake, fake, nullptr);
+    dry_run_slot() = prev;
+    TRY(rc);
+    *n = d.n;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+}  // extern "C"

@@ -1,0 +1,346 @@
+// vae_decoder.h -- the inference half of the text-conditioned VAE (TextConditionedVAE.generate, reference
+// src/iris/vae.py:448-482) for gfx950: frame-level conditioning [B, T, cond_dim] -> mel [B, n_mels, T].
+//
+// Two kernels carry the whole stage.
+//
+// vae_gemm_kernel: channels-last implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 with the fragment-ordered weights of
+// conv_mfma_f32.h (pack_conv1d_weights).  What it adds to that kernel's formulation:
+//   * the input row of output row i, tap kappa is  stride * i - pad_left + kappa * dil  (the stride-2 'same' convs of
+//     TemporalDownsample, vae.py:80-105), optionally over the nearest-neighbour x2 repeat of the input, which is folded
+//     into the LDS staging (x_up[r] = x[r >> 1], TemporalUpsample vae.py:134-147): the repeated tensor is never written;
+//   * a GELU (tanh form) epilogue, and a FiLM epilogue  gamma * h + beta  whose rows come from the conditioning GEMM;
+//   * FUSED: the WaveNetResBlock (vae.py:57-67) in one launch -- the FiLM'ed tile stays in LDS and is the A operand of a
+//     second GEMM (res_proj, 1x1) whose epilogue adds the block's input;
+//   * a channels-first store, [B, C_out, L], for out_proj (the layout PostNet and the vocoder read).
+// A block owns 32 output rows and one 32-wide C_out tile per wave (up to 8 waves); all of C_in is staged at once (the
+// stage's channel counts are <= 256) and blockIdx.y walks further C_out tiles (the conditioning GEMM has 2C columns per
+// decoder block).
+//
+// vae_flow_kernel: the reverse volume-preserving flow (vae.py:162-243) and latent_dec_proj in plain FMAs -- 8 / 16 / 64
+// channels are far below an MFMA tile.  APCoupling never permutes channels, so x1 = z[..., :latent/2] is the SAME tensor
+// in every coupling and only x2 changes: t_j depends on x1 and the conditioning alone, and the k3 net_pre therefore needs
+// one halo row per side for the whole stack, not one per coupling.  x2 is updated in LDS in the reference's order
+// (last coupling first); z never goes to HBM.
+//
+// Rows outside an item read 0 and are never stored; every loop bound is a kernel argument.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "conv_mfma_f32.h"
+
+namespace iris {
+namespace vae {
+
+// keras.ops.gelu default (approximate=True): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))
+__device__ __forceinline__ float gelu_tanh(float x) {
+    const float u = 0.7978845608028654f * (x + 0.044715f * (x * x * x));
+    return 0.5f * x * (1.f + tanhf(u));
+}
+
+struct GemmLaunch {
+    const float* x;       // input  [B, L_in, C_in] channels-last
+    const f32x4* wp;      // packed weights (pack_conv1d_weights), Gp groups x n_ct C_out tiles per tap
+    const float* bias;    // [C_out]
+    float* y;             // output [B, L_out, C_out], or [B, C_out, L_out] when y_channels_first
+    const float* film;    // FiLM rows [B * L_out, ld_film]: gamma at column gamma_off + co, beta at beta_off + co; or nullptr
+    const f32x4* wp2;     // FUSED: packed 1x1 weights C_out -> C_out (same n_ct, Gp2 groups)
+    const float* bias2;   // FUSED: [C_out]
+    const float* res;     // FUSED: residual [B, L_out, C_out] added after the second GEMM
+    int L_in, L_out, C_in, C_out;
+    int ks, dil, stride, pad_left;
+    int up;               // 1: the conv runs over the x2 nearest-neighbour repeat of x (2 * L_in virtual rows)
+    int Gp, n_ct, Gp2;
+    int gelu;             // 1: GELU on (acc + bias), before FiLM
+    int ld_film, gamma_off, beta_off;
+    int y_channels_first;
+};
+
+constexpr int kGemmRows = 32;        // output rows of a block
+constexpr int kGemmMaxWaves = 8;     // C_out tiles of a block
+
+inline int gemm_window_rows(int ks, int dil, int stride) { return (kGemmRows - 1) * stride + (ks - 1) * dil + 1; }
+inline int gemm_row_floats(int C) { return ((C + 7) & ~7) + 4; }      // 4 * odd: conflict-free 16-byte rows
+inline size_t gemm_lds_bytes(int C_in, int C_out, int ks, int dil, int stride, bool fused) {
+    size_t f = (size_t)gemm_window_rows(ks, dil, stride) * gemm_row_floats(C_in);
+    if (fused) f += (size_t)kGemmRows * gemm_row_floats(C_out);
+    return f * sizeof(float);
+}
+
+// acc += A (32 rows x K, LDS) * W (K x 32, fragment order).  One group = 8 input channels of one tap = 4 MFMAs; the weight
+// fragments run four groups ahead in registers, the LDS fragment one group ahead.
+__device__ __forceinline__ void mma_loop(f32x16& acc, const float* abase, int tapstep, const f32x4* __restrict__ wlane,
+                                         size_t wstep, int Gp, int ks, int gpc) {
+    const int NG = ks * gpc;
+    auto a_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return abase + kk * tapstep + 8 * g; };
+    auto b_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return wlane + ((size_t)kk * Gp + g) * wstep; };
+    constexpr int D = 4;
+    f32x4 bw[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) bw[d] = *b_ptr(d < NG ? d : NG - 1);
+    f32x4 av = *reinterpret_cast<const f32x4*>(a_ptr(0));
+    for (int n0 = 0; n0 < NG; n0 += D) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int n = n0 + d;
+            if (n < NG) {                                           // wave-uniform
+                const f32x4 a_cur = av, b_cur = bw[d];
+                av = *reinterpret_cast<const f32x4*>(a_ptr(n + 1 < NG ? n + 1 : n));
+                bw[d] = *b_ptr(n + D < NG ? n + D : NG - 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b_cur[e], a_cur[e], acc, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const GemmLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
+    const int lo = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.z;
+    const int i0 = blockIdx.x * kGemmRows;
+    const int ct = blockIdx.y * nw + wave;                 // this wave's 32-wide C_out tile
+    const bool active = ct < a.n_ct;                       // wave-uniform
+    const int Cp = (a.C_in + 7) & ~7, S = Cp + 4;
+    const int R = (kGemmRows - 1) * a.stride + (a.ks - 1) * a.dil + 1;
+    const int v0 = i0 * a.stride - a.pad_left;             // first (virtual) input row of the window
+    const int Lv = a.up ? 2 * a.L_in : a.L_in;
+
+    {   // stage the window: virtual row v of the item is row v >> up of x, 0 outside [0, Lv)
+        const int QPR = Cp >> 2, total = R * QPR;
+        for (int idx = tid; idx < total; idx += nthr) {
+            const int r = idx / QPR, q = idx - r * QPR;
+            const int v = v0 + r, ci = 4 * q;
+            f32x4 val = {0.f, 0.f, 0.f, 0.f};
+            if (v >= 0 && v < Lv && ci < a.C_in) {
+                const int src = a.up ? (v >> 1) : v;
+                val = *reinterpret_cast<const f32x4*>(a.x + ((size_t)b * a.L_in + src) * a.C_in + ci);
+            }
+            *reinterpret_cast<f32x4*>(lds + r * S + ci) = val;
+        }
+    }
+    __syncthreads();
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if (active)
+        mma_loop(acc, lds + lo * a.stride * S + 4 * hi, a.dil * S, a.wp + (size_t)ct * 64 + lane, (size_t)a.n_ct * 64, a.Gp,
+                 a.ks, Cp >> 3);
+
+    // Epilogue.  D[co][t]: lane & 31 = time row, registers 4g .. 4g+3 = channels ct*32 + 8g + 4*(lane >> 5) + {0..3}.
+    const int t = i0 + lo;
+    const bool ok = active && t < a.L_out;
+    const size_t row = (size_t)b * a.L_out + (ok ? t : 0);
+    if (active) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int co = ct * 32 + 8 * g + 4 * hi;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = 0.f;
+                if (co + e < a.C_out) {
+                    v = acc[4 * g + e] + a.bias[co + e];
+                    if (a.gelu) v = gelu_tanh(v);
+                    if (a.film && ok) {
+                        const float* f = a.film + row * a.ld_film + co + e;
+                        v = f[a.gamma_off] * v + f[a.beta_off];
+                    }
+                }
+                acc[4 * g + e] = v;
+            }
+        }
+    }
+
+    if constexpr (FUSED) {
+        // the FiLM'ed tile h [32, C_out] -> LDS (behind the window), then y = x + res_proj(h)
+        const int Cp2 = (a.C_out + 7) & ~7, S2 = Cp2 + 4;
+        float* hl = lds + R * S;
+        if (active) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int co = ct * 32 + 8 * g + 4 * hi;
+                if (co < Cp2) {
+                    const f32x4 v = {acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+                    *reinterpret_cast<f32x4*>(hl + lo * S2 + co) = v;
+                }
+            }
+        }
+        __syncthreads();
+        f32x16 acc2;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+        if (active)
+            mma_loop(acc2, hl + lo * S2 + 4 * hi, 0, a.wp2 + (size_t)ct * 64 + lane, (size_t)a.n_ct * 64, a.Gp2, 1, Cp2 >> 3);
+        if (ok) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int co = ct * 32 + 8 * g + 4 * hi;
+                if (co < a.C_out) {
+                    const f32x4 r4 = *reinterpret_cast<const f32x4*>(a.res + row * a.C_out + co);
+                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias2 + co);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc2[4 * g + e] = r4[e] + (acc2[4 * g + e] + b4[e]);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (ok) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int co = ct * 32 + 8 * g + 4 * hi;
+                if (co < a.C_out) {
+                    const f32x4 v = {acc2[4 * g + 0], acc2[4 * g + 1], acc2[4 * g + 2], acc2[4 * g + 3]};
+                    *reinterpret_cast<f32x4*>(a.y + row * a.C_out + co) = v;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        __builtin_amdgcn_sched_barrier(0);
+        if (ok) {
+            if (a.y_channels_first) {
+                // [B, C_out, L_out]: the 32 lanes of a half-wave store 32 consecutive frames of one channel
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int co = ct * 32 + 8 * g + 4 * hi + e;
+                        if (co < a.C_out) a.y[((size_t)b * a.C_out + co) * a.L_out + t] = acc[4 * g + e];
+                    }
+            } else {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int co = ct * 32 + 8 * g + 4 * hi;
+                    if (co < a.C_out) {                    // C_out % 4 == 0 (checked on the host)
+                        const f32x4 v = {acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+                        *reinterpret_cast<f32x4*>(a.y + row * a.C_out + co) = v;
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Reverse flow + latent_dec_proj.
+// Per coupling j the weights lie in Keras layouts, in this order (flow_coupling_floats):
+//   net_pre.kernel [3][half][FH], net_pre.bias [FH], net_post.kernel [FH][half], net_post.bias [half],
+//   film.proj.kernel [half][2 half], film.proj.bias [2 half]
+// cond_proj(lat_cond) of every coupling (before its GELU) is a column block of the conditioning GEMM's output.
+struct FlowLaunch {
+    const float* z;        // z_prior [B, Tq, latent]
+    const float* cond;     // conditioning GEMM output [B * Tq, ld]; coupling j's cond_proj at column ce_off + j * ce_stride
+    const float* w;        // couplings, flow_coupling_floats() apart
+    const float* wdec;     // latent_dec_proj kernel [latent][C], then bias [C]
+    float* y;              // [B, Tq, C]
+    int Tq, latent, FH, n_flow, C, ld, ce_off, ce_stride;
+};
+
+constexpr int kFlowRows = 16;
+__host__ __device__ inline size_t flow_coupling_floats(int half, int FH) {
+    return (size_t)3 * half * FH + FH + (size_t)FH * half + half + (size_t)half * 2 * half + 2 * half;
+}
+inline size_t flow_lds_bytes(int latent, int FH) {
+    const int half = latent / 2;
+    return ((size_t)kFlowRows * latent + 2 * (size_t)(kFlowRows + 2) * half + (size_t)kFlowRows * FH) * sizeof(float);
+}
+
+__global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int TT = kFlowRows;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int b = blockIdx.y, r0 = blockIdx.x * TT;
+    const int latent = a.latent, half = latent >> 1, FH = a.FH, Tq = a.Tq;
+    float* zt = lds;                              // [TT][latent]      the tile of z (x1 | x2)
+    float* ce = zt + TT * latent;                 // [TT + 2][half]    gelu(cond_proj(lat_cond)), rows r0 - 1 ..
+    float* hin = ce + (TT + 2) * half;            // [TT + 2][half]    x1 + ce, 0 outside the item ('same' padding)
+    float* hid = hin + (TT + 2) * half;           // [TT][FH]          gelu(net_pre(hin))
+    const size_t per = flow_coupling_floats(half, FH);
+
+    for (int idx = tid; idx < TT * latent; idx += nthr) {
+        const int r = idx / latent, c = idx - r * latent, t = r0 + r;
+        zt[idx] = t < Tq ? a.z[((size_t)b * Tq + t) * latent + c] : 0.f;
+    }
+    for (int jj = a.n_flow - 1; jj >= 0; --jj) {                      // reversed(layers_list), vae.py:237-239
+        const float* wpre = a.w + (size_t)jj * per;
+        const float* bpre = wpre + 3 * half * FH;
+        const float* wpost = bpre + FH;
+        const float* bpost = wpost + FH * half;
+        const float* wfilm = bpost + half;
+        const float* bfilm = wfilm + half * 2 * half;
+        __syncthreads();
+        for (int idx = tid; idx < (TT + 2) * half; idx += nthr) {
+            const int r = idx / half, c = idx - r * half, t = r0 - 1 + r;
+            float cev = 0.f, hv = 0.f;
+            if (t >= 0 && t < Tq) {
+                const size_t grow = (size_t)b * Tq + t;
+                cev = gelu_tanh(a.cond[grow * a.ld + a.ce_off + jj * a.ce_stride + c]);
+                hv = a.z[grow * latent + c] + cev;                   // x1 is z_prior's first half in every coupling
+            }
+            ce[idx] = cev;
+            hin[idx] = hv;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < TT * FH; idx += nthr) {
+            const int r = idx / FH, f = idx - r * FH;
+            float acc = bpre[f];
+            for (int kap = 0; kap < 3; ++kap)
+                for (int c = 0; c < half; ++c)
+                    acc = fmaf(hin[(r + kap) * half + c], wpre[(kap * half + c) * FH + f], acc);
+            hid[idx] = gelu_tanh(acc);
+        }
+        __syncthreads();
+        for (int idx = tid; idx < TT * half; idx += nthr) {
+            const int r = idx / half, c = idx - r * half;
+            float tv = bpost[c];
+            for (int f = 0; f < FH; ++f) tv = fmaf(hid[r * FH + f], wpost[f * half + c], tv);
+            float gam = bfilm[c], bet = bfilm[half + c];
+            for (int k = 0; k < half; ++k) {
+                const float cv = ce[(r + 1) * half + k];
+                gam = fmaf(cv, wfilm[k * 2 * half + c], gam);
+                bet = fmaf(cv, wfilm[k * 2 * half + half + c], bet);
+            }
+            zt[r * latent + half + c] -= gam * tv + bet;             // y2 = x2 - t (reverse), vae.py:203-204
+        }
+    }
+    __syncthreads();
+    const float* bdec = a.wdec + (size_t)latent * a.C;
+    for (int idx = tid; idx < TT * a.C; idx += nthr) {
+        const int r = idx / a.C, co = idx - r * a.C, t = r0 + r;
+        if (t >= Tq) continue;
+        float acc = bdec[co];
+        for (int l = 0; l < latent; ++l) acc = fmaf(zt[r * latent + l], a.wdec[(size_t)l * a.C + co], acc);
+        a.y[((size_t)b * Tq + t) * a.C + co] = acc;
+    }
+}
+
+#ifndef IRIS_KERNELS_ONLY
+// Fills Gp / n_ct and launches.  FUSED launches need every C_out tile in one block (C_out <= 32 * kGemmMaxWaves).
+inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stream) {
+    a.Gp = packed_groups(a.C_in);
+    a.n_ct = packed_cotiles(a.C_out);
+    a.Gp2 = packed_groups(a.C_out);
+    const int nw = a.n_ct < kGemmMaxWaves ? a.n_ct : kGemmMaxWaves;
+    if (fused && a.n_ct > kGemmMaxWaves) return hipErrorInvalidValue;
+    const size_t lds_bytes = gemm_lds_bytes(a.C_in, a.C_out, a.ks, a.dil, a.stride, fused);
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((a.L_out + kGemmRows - 1) / kGemmRows), (unsigned)((a.n_ct + nw - 1) / nw), (unsigned)B);
+    dim3 block((unsigned)(64 * nw));
+    if (fused) return launch_kernel_named("vae_gemm_kernel<fused>", vae_gemm_kernel<true>, grid, block, lds_bytes, stream, a);
+    return launch_kernel_named("vae_gemm_kernel", vae_gemm_kernel<false>, grid, block, lds_bytes, stream, a);
+}
+
+inline hipError_t launch_flow(const FlowLaunch& a, int B, hipStream_t stream) {
+    dim3 grid((unsigned)((a.Tq + kFlowRows - 1) / kFlowRows), (unsigned)B), block(256);
+    return launch_kernel_named("vae_flow_kernel", vae_flow_kernel, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
+}
+#endif
+
+}  // namespace vae
+}  // namespace iris

@@ -172,6 +172,29 @@ RESAMPLER_SYMBOLS = {
     "iris_resampler_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _f, _vp]),
 }
 
+
+
+class VaeDecoderConfig(ctypes.Structure):
+    """``iris_vae_decoder_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_mels", "cond_dim", "model_channels", "latent_dim", "decoder_blocks",
+                                             "wavenet_kernel_size", "down_stages", "flow_layers", "flow_hidden")]
+
+
+VAE_TAP_LAT_COND, VAE_TAP_DEC_IN, VAE_TAP_DEC_OUT = 0, 1, 2
+
+# the VAE decoder stage (iris.vae): bound by load() like SYMBOLS
+_u64p = _c.POINTER(_u64)
+VAE_SYMBOLS = {
+    "iris_vae_decoder_weight_count": (_i32, [_c.POINTER(VaeDecoderConfig), _u64p]),
+    "iris_vae_decoder_create": (_i32, [_c.POINTER(VaeDecoderConfig), _fp, _u64, _c.POINTER(_vp)]),
+    "iris_vae_decoder_destroy": (_i32, [_vp]),
+    "iris_vae_decoder_workspace_bytes": (_i32, [_vp, _i32, _i32, _u64p]),
+    "iris_vae_decoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_vae_decoder_launch_count": (_i32, [_vp, _i32, _i32, _ip]),
+    "iris_vae_decoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -197,7 +220,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

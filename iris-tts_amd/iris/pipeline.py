@@ -26,12 +26,14 @@ class MelToWavePipeline:
     refined one), or None to vocode the mel as it is.  ``vocode``: ``GeneratorEngine.forward`` (or any callable
     ``[B, n_mels, W] -> [B, hop*W]``).  ``config``: the generator's ``GeneratorConfig`` -- hop length and the
     minimal halo are derived from it (V1 values when omitted; ``vocode.__self__.cfg`` is picked up when ``vocode``
-    is a bound ``GeneratorEngine.forward``)."""
+    is a bound ``GeneratorEngine.forward``).  ``acoustic``: an ``iris.vae.TextConditionedVAE`` (or any callable
+    ``(frame_cond, z_prior) -> (device mel [B, n_mels, T], ...)``) for ``infer_from_cond``, or None."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
-                 group_chunks: int = 1, config=None):
+                 group_chunks: int = 1, config=None, acoustic=None):
         self.postnet = postnet
+        self.acoustic = acoustic
         self.device = device
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
@@ -105,6 +107,17 @@ class MelToWavePipeline:
                                 group_chunks=sv.group_chunks, config=self.config).infer(self.refine(mel))
 
     __call__ = infer
+
+    def infer_from_cond(self, frame_cond, z_prior=None, **kw):
+        """Frame-level text conditioning ``[B, T, cond_dim]`` (and optionally the latent prior sample) -> what ``infer`` returns
+        for the mel the acoustic stage generates from it (``TextConditionedVAE.generate_device``, reference
+        scripts/synthesize.py:125-166): VAE decoder, PostNet and vocoder on one stream, the mel never leaves the device.
+        ``**kw`` goes to ``infer`` (``pcm16``, ``normalize``, ``resampler``)."""
+        if self.acoustic is None:
+            raise ValueError("infer_from_cond needs an acoustic stage: construct the pipeline with acoustic=TextConditionedVAE(...)")
+        gen = getattr(self.acoustic, "generate_device", None)
+        mel = gen(frame_cond, z_prior, want_residual=False)[0] if gen is not None else self.acoustic(frame_cond, z_prior)[0]
+        return self.infer(mel, **kw)
 
     def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False, resampler=None) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform

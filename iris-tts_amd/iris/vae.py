@@ -1,0 +1,274 @@
+"""MI355X drop-in for the inference half of the reference module ``iris.vae`` (TextConditionedVAE, Keras/JAX).
+
+Call surface kept from the reference's ``src/iris/vae.py``: the constructor ``TextConditionedVAE(n_mels, cond_dim,
+model_channels=192, latent_dim=16, num_wavenet_blocks=8, decoder_blocks=4, wavenet_kernel_size=5, down_stages=2,
+flow_layers=4, flow_hidden=64, dropout=0.1, name=None)`` (:263-351) and ``generate(frame_text_cond, z_prior=None) ->
+(mel [B, n_mels, T], residual [B, T, cond_dim])`` (:448-482), which ``scripts/synthesize.py:125-145`` calls right before
+the PostNet.  The encoder half (``in_proj``, ``enc_blocks``, ``latent_*_proj``, ``call()``) is training-side and is not
+built: ``__call__`` raises, and encoder-side keys in a weight file are ignored.
+
+    lat_cond = downsample(down_cond_proj(frame_cond))   # 1x1 conv, then S x (Conv1D k5 stride 2 'same' + gelu)   :360-364
+    z = z_prior                                         # [B, T / 2^S, latent_dim]
+    for coupling in reversed(flow layers):              # APCoupling, reverse=True                               :182-208
+        x1, x2 = split(z); ce = gelu(cond_proj(lat_cond))
+        t = net_post(gelu(net_pre(x1 + ce)));  g, b = split(film.proj(ce));  z = concat(x1, x2 - (g * t + b))
+    d = latent_dec_proj(z)
+    for i, block in enumerate(dec_blocks):              # WaveNetResBlock, dilation 2^(i % 4)                    :57-67
+        h = gelu(conv(d)); g, b = split(film.proj(lat_cond)); d = d + res_proj(g * h + b)
+    for each upsample stage: d = gelu(Conv1D_k5_same(repeat_each_row_twice(d)))                                  :141-147
+    mel = transpose(out_proj(d));  residual = residual_proj(d)
+
+Keras cannot run in this pipeline, so the conventions below are ASSUMPTIONS read from the Keras 3 / XLA documentation,
+pinned by the numpy restatement the tests compare against (``tests/vae_restatement.py``) -- "parity unpinned", as for
+``iris.postnet``:
+  * ``Conv1D`` kernels are ``[k, C_in, C_out]`` and the layer is a cross-correlation.
+  * ``padding='same'``, stride 1: ``dilation * (k - 1) / 2`` zeros on both sides.
+  * ``padding='same'``, stride 2, k = 5, even input length: 1 zero on the left and 2 on the right, i.e.
+    ``y[i] = sum_kappa x[2 i - 1 + kappa] W[kappa]`` (the TF/XLA SAME rule, ``pad_left = total // 2``).
+  * ``Dense`` is ``x @ kernel[in, out] + bias``.
+  * ``ops.split(x, 2, axis=-1)`` returns the first half of the channels first (gamma, then beta).
+  * ``ops.gelu`` is the tanh approximation (Keras 3 default ``approximate=True``):
+    ``0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))``.
+  * ``Dropout`` is the identity at inference.
+
+Parameters are kept in the Keras layouts under attribute-path names (``down_cond_proj.kernel``,
+``downsample.blocks.0.bias``, ``vpflow.ap_2.net_pre.kernel``, ``dec_block_1.film.proj.kernel``,
+``upsample.refine.0.kernel``, ...).  ``generate`` assumes ``T % 2^down_stages == 0`` as the reference does
+(``synthesize.py:117-122`` pads to it); other lengths raise ``ValueError`` -- nothing is padded silently.
+``.weights.h5`` files need h5py; ``load_weights`` / ``save_weights`` use ``.npz``.
+"""
+from __future__ import annotations
+
+import ctypes
+from pathlib import Path
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _native
+from ._engine import require_gpu
+
+
+class TextConditionedVAE:
+    def __init__(self, n_mels: int, cond_dim: int, model_channels: int = 192, latent_dim: int = 16,
+                 num_wavenet_blocks: int = 8, decoder_blocks: int = 4, wavenet_kernel_size: int = 5, down_stages: int = 2,
+                 flow_layers: int = 4, flow_hidden: int = 64, dropout: float = 0.1, name: Optional[str] = None,
+                 seed: Optional[int] = None):
+        if latent_dim % 2:
+            raise ValueError("Flow channels must be even.")                      # vae.py:223
+        self.n_mels, self.cond_dim, self.model_channels, self.latent_dim = n_mels, cond_dim, model_channels, latent_dim
+        self.num_wavenet_blocks, self.decoder_blocks = num_wavenet_blocks, decoder_blocks      # (the first: encoder side)
+        self.wavenet_kernel_size, self.down_stages = wavenet_kernel_size, down_stages
+        self.flow_layers, self.flow_hidden = flow_layers, flow_hidden
+        self.dropout_rate, self.name = dropout, name or "text_conditioned_vae"
+        rng = np.random.default_rng(seed)
+        self.weights: Dict[str, np.ndarray] = {}
+
+        def conv(prefix, k, c_in, c_out, zero=False):
+            limit = np.sqrt(6.0 / ((c_in + c_out) * k))                          # glorot_uniform
+            w = np.zeros((k, c_in, c_out)) if zero else rng.uniform(-limit, limit, (k, c_in, c_out))
+            self.weights[f"{prefix}.kernel"] = w.astype(np.float32)
+            self.weights[f"{prefix}.bias"] = np.zeros(c_out, np.float32)
+
+        def dense(prefix, c_in, c_out):
+            limit = np.sqrt(6.0 / (c_in + c_out))
+            self.weights[f"{prefix}.kernel"] = rng.uniform(-limit, limit, (c_in, c_out)).astype(np.float32)
+            self.weights[f"{prefix}.bias"] = np.zeros(c_out, np.float32)
+
+        C, half = model_channels, latent_dim // 2
+        conv("down_cond_proj", 1, cond_dim, C)
+        for s in range(down_stages):
+            conv(f"downsample.blocks.{s}", 5, C, C)
+        for j in range(flow_layers):
+            p = f"vpflow.ap_{j}"
+            dense(f"{p}.cond_proj", C, half)
+            conv(f"{p}.net_pre", 3, half, flow_hidden)
+            conv(f"{p}.net_post", 1, flow_hidden, half, zero=True)               # zero-initialised, vae.py:172-178
+            dense(f"{p}.film.proj", half, 2 * half)
+        dense("latent_dec_proj", latent_dim, C)
+        for i in range(decoder_blocks):
+            p = f"dec_block_{i}"
+            conv(f"{p}.conv", wavenet_kernel_size, C, C)
+            dense(f"{p}.film.proj", C, 2 * C)
+            conv(f"{p}.res_proj", 1, C, C)
+        for s in range(down_stages):
+            conv(f"upsample.refine.{s}", 5, C, C)
+        conv("out_proj", 1, C, n_mels)
+        dense("residual_proj", C, cond_dim)
+        self._handle = None
+        self._workspace = None
+        self._device = None
+
+    def get_config(self) -> dict:
+        return {"n_mels": self.n_mels, "cond_dim": self.cond_dim, "model_channels": self.model_channels,
+                "latent_dim": self.latent_dim, "num_wavenet_blocks": self.num_wavenet_blocks,
+                "decoder_blocks": self.decoder_blocks, "wavenet_kernel_size": self.wavenet_kernel_size,
+                "down_stages": self.down_stages, "flow_layers": self.flow_layers, "flow_hidden": self.flow_hidden,
+                "dropout": self.dropout_rate}
+
+    @property
+    def downsample_factor(self) -> int:
+        return 2 ** self.down_stages
+
+    # -- parameters --------------------------------------------------------------------------
+    def set_weights_dict(self, weights: Dict[str, np.ndarray]) -> None:
+        """Takes every decoder-side tensor from ``weights``; other keys (the encoder half of a full checkpoint) are ignored."""
+        for key, cur in self.weights.items():
+            if key not in weights:
+                raise KeyError(f"weights are missing {key}")
+            arr = np.asarray(weights[key], dtype=np.float32)
+            if arr.shape != cur.shape:
+                raise ValueError(f"{key}: shape {arr.shape} != expected {cur.shape}")
+            self.weights[key] = np.ascontiguousarray(arr)
+        self._drop()
+
+    def save_weights(self, path: str) -> None:
+        if Path(path).suffix in (".h5", ".keras"):
+            raise NotImplementedError("Keras .h5/.keras files need h5py, which this build does not use; save to .npz")
+        np.savez(str(path), **self.weights)
+
+    def load_weights(self, path: str) -> None:
+        if Path(path).suffix in (".h5", ".keras"):
+            raise NotImplementedError(f"{Path(path).name}: reading Keras weight files needs h5py, which is not available")
+        with np.load(str(path), allow_pickle=False) as data:
+            self.set_weights_dict({k: data[k] for k in data.files})
+
+    def native_config(self) -> "_native.VaeDecoderConfig":
+        return _native.VaeDecoderConfig(self.n_mels, self.cond_dim, self.model_channels, self.latent_dim, self.decoder_blocks,
+                                        self.wavenet_kernel_size, self.down_stages, self.flow_layers, self.flow_hidden)
+
+    def blob_size(self) -> int:
+        """Values in ``blob()`` (``iris_vae_decoder_weight_count`` computes the same on the C side)."""
+        return sum(int(v.size) for v in self.weights.values())
+
+    def blob(self) -> np.ndarray:
+        """The weights in the order and layouts ``iris_vae_decoder_create`` reads (include/iris_hifigan.h): convolutions and
+        Dense layers that run as GEMMs transposed to ``[C_out][C_in][k]``, the flow's small tensors as Keras stores them."""
+        w = self.weights
+        parts = []
+
+        def gemm(prefix):                        # Conv1D [k, in, out] or Dense [in, out] -> [out][in][k]
+            k = w[f"{prefix}.kernel"]
+            k = k[None] if k.ndim == 2 else k
+            parts.extend([np.ascontiguousarray(k.transpose(2, 1, 0)).ravel(), w[f"{prefix}.bias"].ravel()])
+
+        def raw(prefix):
+            parts.extend([w[f"{prefix}.kernel"].ravel(), w[f"{prefix}.bias"].ravel()])
+
+        gemm("down_cond_proj")
+        for s in range(self.down_stages):
+            gemm(f"downsample.blocks.{s}")
+        for j in range(self.flow_layers):
+            p = f"vpflow.ap_{j}"
+            gemm(f"{p}.cond_proj")
+            raw(f"{p}.net_pre"); raw(f"{p}.net_post"); raw(f"{p}.film.proj")
+        raw("latent_dec_proj")
+        for i in range(self.decoder_blocks):
+            p = f"dec_block_{i}"
+            gemm(f"{p}.conv"); gemm(f"{p}.film.proj"); gemm(f"{p}.res_proj")
+        for s in range(self.down_stages):
+            gemm(f"upsample.refine.{s}")
+        gemm("out_proj")
+        gemm("residual_proj")
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+    # -- execution ---------------------------------------------------------------------------
+    def _drop(self) -> None:
+        if self._handle is not None:
+            _native.load().iris_vae_decoder_destroy(self._handle)
+        self._handle = None
+        self._workspace = None
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+    def _ensure(self):
+        if self._handle is None:
+            lib = _native.load()
+            self._device = require_gpu()
+            blob = self.blob()
+            cfg = self.native_config()
+            h = ctypes.c_void_p()
+            with torch.cuda.device(self._device):
+                _native.check("iris_vae_decoder_create", lib.iris_vae_decoder_create(
+                    ctypes.byref(cfg), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.c_uint64(blob.size),
+                    ctypes.byref(h)))
+            self._handle = h
+        return _native.load()
+
+    def _check_cond(self, shape) -> Tuple[int, int]:
+        if len(shape) != 3 or shape[2] != self.cond_dim:
+            raise ValueError(f"expected frame_text_cond [B, T, {self.cond_dim}], got {tuple(shape)}")
+        B, T = int(shape[0]), int(shape[1])
+        if T % self.downsample_factor:
+            raise ValueError(f"T = {T} is not a multiple of 2^down_stages = {self.downsample_factor}: pad the conditioning "
+                             "first (scripts/synthesize.py:117-122 does); nothing is padded silently")
+        return B, T
+
+    def launch_count(self, B: int, T: int) -> int:
+        """Kernel launches of one ``generate_device(..., want_residual=True)`` (one fewer without the residual)."""
+        lib = self._ensure()
+        n = ctypes.c_int32()
+        _native.check("iris_vae_decoder_launch_count", lib.iris_vae_decoder_launch_count(self._handle, B, T, ctypes.byref(n)))
+        return int(n.value)
+
+    def generate_device(self, cond: torch.Tensor, z_prior: Optional[torch.Tensor] = None, want_residual: bool = True,
+                        generator: Optional[torch.Generator] = None):
+        """``cond [B, T, cond_dim]``, ``z_prior [B, T / 2^S, latent_dim]`` (fp32 device tensors) -> ``(mel [B, n_mels, T],
+        residual [B, T, cond_dim] or None)``, asynchronous on the current stream; the mel is contiguous and channels-first,
+        as ``PostNet.forward_device`` and ``GeneratorEngine.forward`` read it.  ``z_prior=None`` draws ``torch.randn`` on the
+        device (from ``generator`` when given): a standard normal as in the reference, but NOT the numbers JAX would draw
+        from ``SeedGenerator(1337)`` -- pass ``z_prior`` to reproduce a reference run."""
+        B, T = self._check_cond(tuple(cond.shape))
+        lib = self._ensure()
+        cond = cond.to(device=self._device, dtype=torch.float32).contiguous()
+        Tq = T // self.downsample_factor
+        if z_prior is None:
+            z_prior = torch.randn((B, Tq, self.latent_dim), device=self._device, dtype=torch.float32, generator=generator)
+        elif tuple(z_prior.shape) != (B, Tq, self.latent_dim):
+            raise ValueError(f"expected z_prior [{B}, {Tq}, {self.latent_dim}], got {tuple(z_prior.shape)}")
+        z_prior = z_prior.to(device=self._device, dtype=torch.float32).contiguous()
+        mel = torch.empty((B, self.n_mels, T), dtype=torch.float32, device=self._device)
+        residual = torch.empty((B, T, self.cond_dim), dtype=torch.float32, device=self._device) if want_residual else None
+        if B == 0 or T == 0:
+            return mel, residual
+        n = ctypes.c_uint64()
+        _native.check("iris_vae_decoder_workspace_bytes", lib.iris_vae_decoder_workspace_bytes(self._handle, B, T, ctypes.byref(n)))
+        if self._workspace is None or self._workspace.numel() < n.value:
+            self._workspace = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=self._device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(
+            self._handle, ctypes.c_void_p(cond.data_ptr()), ctypes.c_void_p(z_prior.data_ptr()), B, T,
+            ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(residual.data_ptr() if want_residual else None),
+            ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream))
+        return mel, residual
+
+    def generate(self, frame_text_cond, z_prior=None, generator: Optional[torch.Generator] = None):
+        """Reference ``generate`` (vae.py:448-482): numpy in -> numpy out, device tensors in -> device tensors out."""
+        if isinstance(frame_text_cond, torch.Tensor):
+            return self.generate_device(frame_text_cond, z_prior, True, generator)
+        cond = np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32))
+        self._check_cond(cond.shape)
+        self._ensure()
+        z = None if z_prior is None else torch.from_numpy(np.ascontiguousarray(np.asarray(z_prior, dtype=np.float32))).to(self._device)
+        mel, residual = self.generate_device(torch.from_numpy(cond).to(self._device), z, True, generator)
+        return mel.cpu().numpy(), residual.cpu().numpy()
+
+    def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:
+        """Test-only: the intermediate ``which`` (``_native.VAE_TAP_*``) the last ``generate_device`` of shape (B, T) left in
+        the workspace, ``[B, T / 2^S, model_channels]`` (a copy)."""
+        lib = self._ensure()
+        off, n = ctypes.c_uint64(), ctypes.c_uint64()
+        _native.check("iris_vae_decoder_tap", lib.iris_vae_decoder_tap(self._handle, B, T, which, ctypes.byref(off), ctypes.byref(n)))
+        raw = self._workspace[off.value:off.value + 4 * n.value].clone()
+        return raw.view(torch.float32).view(B, T // self.downsample_factor, self.model_channels)
+
+    def __call__(self, mels_bt_f=None, frame_text_cond=None, training: bool = False):
+        raise NotImplementedError("the MI355X build holds the inference half only (generate()): the encoder of "
+                                  "TextConditionedVAE.call() and training are not built")
+
+    call = __call__
