@@ -481,6 +481,75 @@ int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t 
 int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
                              uint64_t* floats);
 
+/* ---- Phoneme encoder, duration head and length regulator in front of the VAE decoder (csrc/text_encoder.h) ----
+ * The text side of the reference's scripts/synthesize.py:93-122: phoneme ids [B, P] -> encoder output [B, P, embed_dim]
+ * (PhonemeEncoder, src/iris/encoder.py:115-212) -> softplus duration output [B, P] and integer frames
+ * clip(rint(exp(pred) - 1), 1, max_frames_per_phoneme) (DurationPredictor, :228-315; predict_durations,
+ * synthesize.py:41-45) -> frame conditioning [B, T_pad, embed_dim] (length regulator, synthesize.py:48-61, 112-122),
+ * which iris_vae_decoder_forward reads.  fp32, inference only (dropout is the identity).
+ * lengths_dev (int32 [B], may be NULL = every item has P phonemes): item b owns its first lengths[b] positions.  Keys past
+ * them have attention weight exactly 0, the duration head's 'same' padding starts at them, and every output row past them
+ * is 0 (frames included): item b is bit for bit what a batch of one computes from its own ids.
+ * Encoder weights_host, in this order (iris.encoder.PhonemeEncoder.blob() writes it): phoneme_embedding [vocab][E];
+ * position_embedding [max_length][E]; per block: query|key|value kernels as one [3E][E] matrix (row = output column
+ * h * key_dim + d of q, then of k, then of v) and its bias [3E]; attention output [E][H * key_dim] + bias; attention_norm
+ * gamma, beta; ffn.0 [F][E] + bias; ffn.2 [E][F] + bias; ffn_norm gamma, beta; then encoder_output_norm gamma, beta.
+ * Duration weights_host (iris.encoder.DurationPredictor.blob()): per layer duration_conv [hidden][C_in][k] + bias and
+ * duration_norm gamma, beta; then duration_output [C] + bias [1].
+ * Configurations the kernels cannot take -- embed_dim not a multiple of num_heads, key_dim not a multiple of 8 or above 128,
+ * a channel count that is not a multiple of 4, embed_dim or hidden_dim above 256, an even kernel_size -- return
+ * IRIS_HIFIGAN_UNSUPPORTED; P < 1, P > max_length, a wrong blob size and a NULL pointer return
+ * IRIS_HIFIGAN_INVALID_ARGUMENT; a short workspace returns IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches.
+ * The ids must lie in [0, vocab_size): the kernel clamps, so a bad id reads a wrong row but never outside the table. */
+typedef struct iris_phoneme_encoder_config {
+    int32_t vocab_size, embed_dim, num_blocks, num_heads, ffn_dim, max_length;
+} iris_phoneme_encoder_config;
+typedef struct iris_duration_predictor_config {
+    int32_t in_dim, hidden_dim, num_layers, kernel_size, max_frames_per_phoneme;
+} iris_duration_predictor_config;
+typedef struct iris_phoneme_encoder_handle iris_phoneme_encoder_handle;
+typedef struct iris_duration_predictor_handle iris_duration_predictor_handle;
+
+/* Host only (no device is needed): sizes, and the kernel launches of one forward -- 5 * num_blocks + 2 for the encoder,
+ * num_layers + 2 for the duration head (its scan included). */
+int32_t iris_phoneme_encoder_weight_count(const iris_phoneme_encoder_config* cfg, uint64_t* count);
+int32_t iris_phoneme_encoder_workspace_bytes(const iris_phoneme_encoder_config* cfg, int32_t B, int32_t P, uint64_t* bytes);
+int32_t iris_phoneme_encoder_launch_count(const iris_phoneme_encoder_config* cfg, int32_t B, int32_t P, int32_t* n);
+int32_t iris_phoneme_encoder_create(const iris_phoneme_encoder_config* cfg, const float* weights_host, uint64_t n_weights,
+                                    iris_phoneme_encoder_handle** out);
+int32_t iris_phoneme_encoder_destroy(iris_phoneme_encoder_handle* h);
+/* Asynchronous on `stream`, allocates nothing. */
+int32_t iris_phoneme_encoder_forward(iris_phoneme_encoder_handle* h, const int32_t* ids_dev, const int32_t* lengths_dev, int32_t B,
+                                     int32_t P, float* enc_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+/* Host only, for tests: where a forward of (B, P) leaves the output of block 0, [B, P, embed_dim], in its workspace. */
+int32_t iris_phoneme_encoder_tap(const iris_phoneme_encoder_config* cfg, int32_t B, int32_t P, uint64_t* byte_offset, uint64_t* floats);
+
+int32_t iris_duration_predictor_weight_count(const iris_duration_predictor_config* cfg, uint64_t* count);
+int32_t iris_duration_predictor_workspace_bytes(const iris_duration_predictor_config* cfg, int32_t B, int32_t P, uint64_t* bytes);
+int32_t iris_duration_predictor_launch_count(const iris_duration_predictor_config* cfg, int32_t B, int32_t P, int32_t* n);
+int32_t iris_duration_predictor_create(const iris_duration_predictor_config* cfg, const float* weights_host, uint64_t n_weights,
+                                       iris_duration_predictor_handle** out);
+int32_t iris_duration_predictor_destroy(iris_duration_predictor_handle* h);
+/* enc_out [B, P, in_dim] -> pred float [B, P], frames int32 [B, P], offsets int32 [B, P + 1] (the exclusive prefix sum of
+ * the item's frames; entries from lengths[b] on hold the total) and totals int32 [B].  P * max_frames_per_phoneme must fit
+ * int32 (IRIS_HIFIGAN_INVALID_ARGUMENT otherwise).  Asynchronous on `stream`, allocates nothing. */
+int32_t iris_duration_predictor_forward(iris_duration_predictor_handle* h, const float* enc_out_dev, const int32_t* lengths_dev,
+                                        int32_t B, int32_t P, float* pred_dev, int32_t* frames_dev, int32_t* offsets_dev,
+                                        int32_t* totals_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+/* Host only, for tests: where a forward of (B, P) leaves the output of the first layer, [B, P, hidden_dim]. */
+int32_t iris_duration_predictor_tap(const iris_duration_predictor_config* cfg, int32_t B, int32_t P, uint64_t* byte_offset,
+                                    uint64_t* floats);
+
+/* Stateless.  iris_length_scan: the head's scan alone, for frames that come from elsewhere (an aligner): negative entries
+ * count as 0 and the caller keeps each item's sum within int32.  iris_length_regulate: cond[b, t, :] = enc_out[b, p, :]
+ * for offsets[b, p] <= t < offsets[b, p + 1], and 0 for totals[b] <= t < T_pad; E must be a multiple of 4.  The caller
+ * chooses T_pad (ceil(max(totals) / 2^down_stages) * 2^down_stages for the VAE decoder), which takes the one read-back
+ * of the stage: totals. */
+int32_t iris_length_scan(const int32_t* frames_dev, const int32_t* lengths_dev, int32_t B, int32_t P, int32_t* offsets_dev,
+                         int32_t* totals_dev, void* stream);
+int32_t iris_length_regulate(const float* enc_out_dev, const int32_t* offsets_dev, const int32_t* totals_dev, int32_t B, int32_t P,
+                             int32_t E, int32_t T_pad, float* cond_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,41 @@ VAE_SYMBOLS = {
     "iris_vae_decoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
 }
 
+
+
+class PhonemeEncoderConfig(ctypes.Structure):
+    """``iris_phoneme_encoder_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("vocab_size", "embed_dim", "num_blocks", "num_heads", "ffn_dim", "max_length")]
+
+
+class DurationPredictorConfig(ctypes.Structure):
+    """``iris_duration_predictor_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("in_dim", "hidden_dim", "num_layers", "kernel_size", "max_frames_per_phoneme")]
+
+
+# the text stage (iris.encoder): bound by load() like SYMBOLS
+_pec, _dpc = _c.POINTER(PhonemeEncoderConfig), _c.POINTER(DurationPredictorConfig)
+TEXT_SYMBOLS = {
+    "iris_phoneme_encoder_weight_count": (_i32, [_pec, _u64p]),
+    "iris_phoneme_encoder_workspace_bytes": (_i32, [_pec, _i32, _i32, _u64p]),
+    "iris_phoneme_encoder_launch_count": (_i32, [_pec, _i32, _i32, _ip]),
+    "iris_phoneme_encoder_create": (_i32, [_pec, _fp, _u64, _c.POINTER(_vp)]),
+    "iris_phoneme_encoder_destroy": (_i32, [_vp]),
+    "iris_phoneme_encoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _u64, _vp]),
+    "iris_phoneme_encoder_tap": (_i32, [_pec, _i32, _i32, _u64p, _u64p]),
+    "iris_duration_predictor_weight_count": (_i32, [_dpc, _u64p]),
+    "iris_duration_predictor_workspace_bytes": (_i32, [_dpc, _i32, _i32, _u64p]),
+    "iris_duration_predictor_launch_count": (_i32, [_dpc, _i32, _i32, _ip]),
+    "iris_duration_predictor_create": (_i32, [_dpc, _fp, _u64, _c.POINTER(_vp)]),
+    "iris_duration_predictor_destroy": (_i32, [_vp]),
+    "iris_duration_predictor_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "iris_duration_predictor_tap": (_i32, [_dpc, _i32, _i32, _u64p, _u64p]),
+    "iris_length_scan": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "iris_length_regulate": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -220,7 +255,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **TEXT_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -27,13 +27,15 @@ class MelToWavePipeline:
     ``[B, n_mels, W] -> [B, hop*W]``).  ``config``: the generator's ``GeneratorConfig`` -- hop length and the
     minimal halo are derived from it (V1 values when omitted; ``vocode.__self__.cfg`` is picked up when ``vocode``
     is a bound ``GeneratorEngine.forward``).  ``acoustic``: an ``iris.vae.TextConditionedVAE`` (or any callable
-    ``(frame_cond, z_prior) -> (device mel [B, n_mels, T], ...)``) for ``infer_from_cond``, or None."""
+    ``(frame_cond, z_prior) -> (device mel [B, n_mels, T], ...)``) for ``infer_from_cond``, or None.  ``text``: a pair
+    ``(iris.encoder.PhonemeEncoder, iris.encoder.DurationPredictor)`` for ``infer_from_phonemes``, or None."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
-                 group_chunks: int = 1, config=None, acoustic=None):
+                 group_chunks: int = 1, config=None, acoustic=None, text=None):
         self.postnet = postnet
         self.acoustic = acoustic
+        self.text = text
         self.device = device
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
@@ -118,6 +120,36 @@ class MelToWavePipeline:
         gen = getattr(self.acoustic, "generate_device", None)
         mel = gen(frame_cond, z_prior, want_residual=False)[0] if gen is not None else self.acoustic(frame_cond, z_prior)[0]
         return self.infer(mel, **kw)
+
+    def infer_from_phonemes(self, ids, lengths=None, durations=None, z_prior=None, **kw):
+        """Phoneme ids ``[B, P]`` -> ``(what infer returns, frames_per_item)``: phoneme encoder, duration head and length
+        regulator (``iris.encoder.frame_conditioning``, reference scripts/synthesize.py:93-122), then ``infer_from_cond``.
+        The conditioning is padded to ``acoustic.downsample_factor`` frames, as the reference pads it, and so is the audio:
+        item i has ``hop * ceil(frames_per_item[i] / factor) * factor`` samples.  ``durations`` (integer ``[B, P]``)
+        replaces the duration head's prediction.
+
+        ``B == 1``: one chain on one stream; the only read-back is the frame total.  ``B > 1``: the encoder and the head
+        run ONCE over the ragged batch (``lengths``); the VAE decoder has no ragged form, so each item's conditioning --
+        padded from its own total -- goes through it on its own, and the mels go through ``infer_batch``.  The result is
+        then a list, item i bit for bit the ``B == 1`` call on ``ids[i, :lengths[i]]``; ``z_prior`` is a list of per-item
+        priors (or None), and ``**kw`` goes to ``infer`` / ``infer_batch``."""
+        if self.text is None or self.acoustic is None:
+            raise ValueError("infer_from_phonemes needs text=(PhonemeEncoder, DurationPredictor) and acoustic=TextConditionedVAE(...)")
+        from .encoder import frame_conditioning
+        encoder, head = self.text
+        factor = int(getattr(self.acoustic, "downsample_factor", 1))
+        cond, per_item = frame_conditioning(encoder, head, ids, lengths=lengths, durations=durations, factor=factor)
+        if cond.shape[0] == 1:
+            return self.infer_from_cond(cond, z_prior, **kw), per_item
+        if z_prior is not None and len(z_prior) != cond.shape[0]:
+            raise ValueError(f"z_prior must be a list of {cond.shape[0]} per-item priors")
+        gen = getattr(self.acoustic, "generate_device", None)
+        mels = []
+        for i, total in enumerate(per_item):
+            c = cond[i:i + 1, :-(-total // factor) * factor]
+            z = None if z_prior is None else z_prior[i]
+            mels.append((gen(c, z, want_residual=False)[0] if gen is not None else self.acoustic(c, z)[0])[0])
+        return self.infer_batch(mels, **kw), per_item
 
     def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False, resampler=None) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform
