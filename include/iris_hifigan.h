@@ -470,11 +470,33 @@ int32_t iris_vae_decoder_workspace_bytes(const iris_vae_decoder_handle* h, int32
 int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
                                  float* mel_out_dev, float* residual_out_dev, void* workspace_dev, uint64_t workspace_bytes,
                                  void* stream);
+
+/* Ragged batch: utterances of different lengths decoded in one call (the VAE half of iris_postnet_forward_ragged).
+ * cond_dev [B, T, cond_dim], z_prior_dev [B, T / 2^down_stages, latent_dim], mel_out_dev [B, n_mels, T], residual_out_dev
+ * [B, T, cond_dim] (may be NULL) as in iris_vae_decoder_forward; lengths_dev [B] int32 on the device (caller-owned, like
+ * cond_dev): item b's frames at the full rate.  Lengths are sanitised on the device: clamped to [0, T], then rounded down
+ * to a multiple of 2^down_stages (the stride-2 'same' padding is defined for even lengths, and the caller pads an
+ * utterance to that multiple as for the dense call), giving len_b.
+ * Item b is computed exactly as iris_vae_decoder_forward of cond[b, :len_b] and z_prior[b, :len_b >> down_stages] alone
+ * would compute it, bit for bit: at every level of the stack -- conditioning and mel rows, the rows after each stride-2
+ * stage and each x2 upsample, the latent rows -- the 'same' padding ends at the item's own length.  cond[b, len_b:, :]
+ * and z_prior[b, len_b >> down_stages:, :] are never read, so they may hold anything, NaN included.
+ * mel[b, :, len_b:T] and residual[b, len_b:T, :] are written as 0.0f.
+ * The host never reads the lengths: launch plan, launch count and workspace are those of iris_vae_decoder_forward(B, T)
+ * (iris_vae_decoder_launch_count, iris_vae_decoder_workspace_bytes), and blocks past an item's length return at once on
+ * the device.  Workspace rows past an item's length are neither written nor read.
+ * Asynchronous on `stream`, allocates nothing, safe inside a stream capture.
+ * lengths_dev == NULL (B, T > 0) returns IRIS_HIFIGAN_INVALID_ARGUMENT; shape and workspace errors are those of
+ * iris_vae_decoder_forward.  No failing call launches. */
+int32_t iris_vae_decoder_forward_ragged(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B,
+                                        int32_t T, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
+                                        void* workspace_dev, uint64_t workspace_bytes, void* stream);
 /* Host only: kernel launches of one forward that asks for the residual (one fewer without it):
  * 3 + 2 * down_stages + decoder_blocks + 2. */
 int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n);
 /* Host only, for tests: where a forward of (B, T) leaves an intermediate [B, T / 2^down_stages, model_channels] in its
- * workspace (valid until the next forward on that workspace). */
+ * workspace (valid until the next forward on that workspace).  After iris_vae_decoder_forward_ragged the rows of item b
+ * from len_b >> down_stages on are undefined: the ragged call neither writes nor reads them. */
 #define IRIS_VAE_TAP_LAT_COND 0   /* downsample(down_cond_proj(cond)) */
 #define IRIS_VAE_TAP_DEC_IN 1     /* latent_dec_proj(flow(z_prior, reverse)) */
 #define IRIS_VAE_TAP_DEC_OUT 2    /* after the last decoder block */

@@ -103,15 +103,18 @@ int vae_check_shape(const iris_vae_decoder_handle* h, int32_t B, int32_t T) {
 // the decoder block whose output is the last one: d0 -> da -> db -> da ...
 float* vae_dec_out(float* ws, const VaeWs& w, int i) { return ws + ((i & 1) ? w.db : w.da); }
 
-// Queues the launches of one forward (or, in a dry run, counts them).
-int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, int B, int T, float* mel, float* residual,
-                float* ws, hipStream_t stream) {
+// Queues the launches of one forward (or, in a dry run, counts them).  `lengths` (device, or nullptr for the dense forward)
+// selects the ragged kernels: the same launches over the same grids and buffers, each bounded by the items' own rows at
+// its level -- sh_in / sh_out count the halvings of the launch's input and output below the full rate.
+int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, int B, int T, const int32_t* lengths, float* mel,
+                float* residual, float* ws, hipStream_t stream) {
     const iris_vae_decoder_config& c = h->cfg;
     const int C = c.model_channels, S = c.down_stages, Tq = T >> S;
     const VaeWs w = vae_ws(h, B, T);
     const float* blob = h->blob;
-    auto gemm = [&](const float* x, const VaeConv& l, float* y, int L_in, int L_out) {
+    auto gemm = [&](const float* x, const VaeConv& l, float* y, int L_in, int L_out, int sh_in, int sh_out) {
         vae::GemmLaunch a; memset(&a, 0, sizeof(a));
+        a.lengths = lengths; a.len_T = T; a.len_shift = S; a.sh_in = sh_in; a.sh_out = sh_out;
         a.x = x; a.wp = (const f32x4*)(blob + l.w_off); a.bias = blob + l.b_off; a.y = y;
         a.L_in = L_in; a.L_out = L_out; a.C_in = l.C_in; a.C_out = l.C_out;
         a.ks = l.k; a.dil = 1; a.stride = 1; a.pad_left = (l.k - 1) / 2;
@@ -120,18 +123,18 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
     // lat_cond = downsample(down_cond_proj(frame_cond))                                    vae.py:360-364
     float* pq[2] = {ws + w.p, ws + w.q};
     {
-        vae::GemmLaunch a = gemm(cond, h->cond_proj, S == 0 ? ws + w.latcond : pq[0], T, T);
+        vae::GemmLaunch a = gemm(cond, h->cond_proj, S == 0 ? ws + w.latcond : pq[0], T, T, 0, 0);
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     for (int s = 0; s < S; ++s) {
         // Conv1D(k5, strides 2, 'same') on an even length: pad (1, 2), y[i] = sum_kap x[2i - 1 + kap] W[kap]; then GELU
-        vae::GemmLaunch a = gemm(pq[s & 1], h->down[s], s == S - 1 ? ws + w.latcond : pq[(s + 1) & 1], T >> s, T >> (s + 1));
+        vae::GemmLaunch a = gemm(pq[s & 1], h->down[s], s == S - 1 ? ws + w.latcond : pq[(s + 1) & 1], T >> s, T >> (s + 1), s, s + 1);
         a.stride = 2; a.pad_left = 1; a.gelu = 1;
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     // every Dense(lat_cond) of the decoder at once: FiLM rows of each block, cond_proj of each coupling
     {
-        vae::GemmLaunch a = gemm(ws + w.latcond, h->cond_gemm, ws + w.film, Tq, Tq);
+        vae::GemmLaunch a = gemm(ws + w.latcond, h->cond_gemm, ws + w.film, Tq, Tq, S, S);
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     {   // z = flow(z_prior, reverse); d = latent_dec_proj(z)                                vae.py:466-468
@@ -139,12 +142,13 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
         f.z = z; f.cond = ws + w.film; f.w = blob + h->flow_off; f.wdec = blob + h->dec_proj_off; f.y = ws + w.d0;
         f.Tq = Tq; f.latent = c.latent_dim; f.FH = c.flow_hidden; f.n_flow = c.flow_layers; f.C = C;
         f.ld = h->film_cols; f.ce_off = h->ce_off; f.ce_stride = h->ce_stride;
+        f.lengths = lengths; f.len_T = T; f.len_shift = S;
         HIP_TRY(vae::launch_flow(f, B, stream));
     }
     const float* d = ws + w.d0;
     for (int i = 0; i < c.decoder_blocks; ++i) {                                            // vae.py:57-67, 469-470
         float* y = vae_dec_out(ws, w, i);
-        vae::GemmLaunch a = gemm(d, h->dec_conv[i], y, Tq, Tq);
+        vae::GemmLaunch a = gemm(d, h->dec_conv[i], y, Tq, Tq, S, S);
         a.dil = 1 << (i % 4); a.pad_left = a.dil * (a.ks - 1) / 2; a.gelu = 1;
         a.film = ws + w.film; a.ld_film = h->film_cols; a.gamma_off = i * 2 * C; a.beta_off = i * 2 * C + C;
         a.wp2 = (const f32x4*)(blob + h->dec_res[i].w_off); a.bias2 = blob + h->dec_res[i].b_off; a.res = d;
@@ -152,18 +156,20 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
         d = y;
     }
     for (int s = 0; s < S; ++s) {                                                           // vae.py:141-147
-        vae::GemmLaunch a = gemm(d, h->up[s], pq[s & 1], Tq << s, Tq << (s + 1));
+        vae::GemmLaunch a = gemm(d, h->up[s], pq[s & 1], Tq << s, Tq << (s + 1), S - s, S - s - 1);
         a.up = 1; a.gelu = 1;
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
         d = pq[s & 1];
     }
     {
-        vae::GemmLaunch a = gemm(d, h->out_proj, mel, T, T);
+        vae::GemmLaunch a = gemm(d, h->out_proj, mel, T, T, 0, 0);
+        a.zero_tail = 1;                                                                    // ragged: mel[b, :, len_b:T] = 0
         a.y_channels_first = 1;                                                             // recon [B, n_mels, T], vae.py:480
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     if (residual) {
-        vae::GemmLaunch a = gemm(d, h->residual_proj, residual, T, T);
+        vae::GemmLaunch a = gemm(d, h->residual_proj, residual, T, T, 0, 0);
+        a.zero_tail = 1;                                                                    // ragged: residual[b, len_b:T, :] = 0
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     return IRIS_HIFIGAN_OK;
@@ -285,21 +291,38 @@ int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_
     return IRIS_HIFIGAN_OK;
 }
 
-int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
-                                 float* mel_out_dev, float* residual_out_dev, void* workspace_dev, uint64_t workspace_bytes,
-                                 void* stream_) {
+// The dense and the ragged entry point: the same checks in the same order, then the same plan.
+static int32_t vae_forward_checked(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
+                                   bool ragged, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
+                                   void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
     IRIS_ABI_BEGIN
     TRY(vae_check_shape(h, B, T));
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     if (!cond_dev || !z_prior_dev || !mel_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (ragged && !lengths_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
     const uint64_t need = (uint64_t)vae_ws(h, B, T).total * sizeof(float);
     if (workspace_bytes < need)
         return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
                     (unsigned long long)workspace_bytes, (unsigned long long)need);
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    return vae_forward(h, cond_dev, z_prior_dev, B, T, mel_out_dev, residual_out_dev, (float*)workspace_dev, (hipStream_t)stream_);
+    return vae_forward(h, cond_dev, z_prior_dev, B, T, ragged ? lengths_dev : nullptr, mel_out_dev, residual_out_dev,
+                       (float*)workspace_dev, (hipStream_t)stream_);
     IRIS_ABI_END
+}
+
+int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
+                                 float* mel_out_dev, float* residual_out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                 void* stream_) {
+    return vae_forward_checked(h, cond_dev, z_prior_dev, B, T, false, nullptr, mel_out_dev, residual_out_dev, workspace_dev,
+                               workspace_bytes, stream_);
+}
+
+int32_t iris_vae_decoder_forward_ragged(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B,
+                                        int32_t T, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
+                                        void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
+    return vae_forward_checked(h, cond_dev, z_prior_dev, B, T, true, lengths_dev, mel_out_dev, residual_out_dev, workspace_dev,
+                               workspace_bytes, stream_);
 }
 
 int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n) {
@@ -313,7 +336,7 @@ int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t 
     DryRun* const prev = dry_run_slot();
     dry_run_slot() = &d;
     float* const fake = reinterpret_cast<float*>(uintptr_t(256));
-    const int rc = vae_forward(const_cast<iris_vae_decoder_handle*>(h), fake, fake, B, T, fake, fake, fake, nullptr);
+    const int rc = vae_forward(const_cast<iris_vae_decoder_handle*>(h), fake, fake, B, T, nullptr, fake, fake, fake, nullptr);
     dry_run_slot() = prev;
     TRY(rc);
     *n = d.n;

@@ -23,6 +23,15 @@
 // (last coupling first); z never goes to HBM.
 //
 // Rows outside an item read 0 and are never stored; every loop bound is a kernel argument.
+//
+// Ragged form (RAGGED instantiations, iris_vae_decoder_forward_ragged): a device array lengths[B] gives each item's frames
+// at the full rate.  item_frames() sanitises it on the device, and an item's rows at a level `sh` halvings below the full
+// rate are  item_frames >> sh.  These per-item counts replace L_in / L_out / Tq as BOUNDS only -- what is staged, what
+// reads 0, what is stored; row strides and buffer offsets keep coming from the padded shape, so item b lies where the
+// dense forward puts it and a block still owns the same 32 rows counted from the item's row 0.  Inside its length an item
+// therefore runs the dense form's loads, MFMAs and FMAs in the dense form's order: bit for bit the batch-of-one result.
+// A block whose rows all lie past its item's length returns before its first barrier; the two output launches store 0.0f
+// there instead (zero_tail).  The dense instantiations contain none of this.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,7 +62,36 @@ struct GemmLaunch {
     int gelu;             // 1: GELU on (acc + bias), before FiLM
     int ld_film, gamma_off, beta_off;
     int y_channels_first;
+    // RAGGED only
+    const int32_t* lengths;   // [B] frames of each item at the full rate (device), sanitised by item_frames()
+    int len_T, len_shift;     // the padded frame count T and down_stages
+    int sh_in, sh_out;        // item rows of x: item_frames >> sh_in (before `up`); of y: item_frames >> sh_out
+    int zero_tail;            // 1: rows [item rows, L_out) of y are stored as 0.0f (out_proj, residual_proj)
 };
+
+// Frames of item b: lengths[b] clamped to [0, T], then rounded down to a multiple of 2^S -- the stride-2 'same' rule (pad 1
+// left, 2 right) holds for even lengths only, and a multiple of 2^S is even at every level.
+__device__ __forceinline__ int item_frames(const int32_t* __restrict__ lengths, int b, int T, int S) {
+    int len = lengths[b];
+    len = len < 0 ? 0 : (len > T ? T : len);
+    return (len >> S) << S;
+}
+
+// zero_tail: row t of item b (t < L_out, past the item's rows) of this wave's C_out tile as 0.0f, in y's layout
+__device__ __forceinline__ void store_zero_row(const GemmLaunch& a, int b, int ct, int t, int hi) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int co = ct * 32 + 8 * g + 4 * hi;
+        if (a.y_channels_first) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (co + e < a.C_out) a.y[((size_t)b * a.C_out + co + e) * a.L_out + t] = 0.f;
+        } else if (co < a.C_out) {                         // C_out % 4 == 0 (checked on the host)
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(a.y + ((size_t)b * a.L_out + t) * a.C_out + co) = zero;
+        }
+    }
+}
 
 constexpr int kGemmRows = 32;        // output rows of a block
 constexpr int kGemmMaxWaves = 8;     // C_out tiles of a block
@@ -95,7 +133,7 @@ __device__ __forceinline__ void mma_loop(f32x16& acc, const float* abase, int ta
     }
 }
 
-template <bool FUSED>
+template <bool FUSED, bool RAGGED>
 __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const GemmLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -108,7 +146,17 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
     const int Cp = (a.C_in + 7) & ~7, S = Cp + 4;
     const int R = (kGemmRows - 1) * a.stride + (a.ks - 1) * a.dil + 1;
     const int v0 = i0 * a.stride - a.pad_left;             // first (virtual) input row of the window
-    const int Lv = a.up ? 2 * a.L_in : a.L_in;
+    int Lb_in = a.L_in, Lb_out = a.L_out;                  // the item's rows: bounds, never strides
+    if constexpr (RAGGED) {
+        const int len = item_frames(a.lengths, b, a.len_T, a.len_shift);
+        Lb_in = len >> a.sh_in;
+        Lb_out = len >> a.sh_out;
+        if (i0 >= Lb_out) {                                // block-uniform, before the first barrier
+            if (!FUSED && a.zero_tail && active && i0 + lo < a.L_out) store_zero_row(a, b, ct, i0 + lo, hi);
+            return;
+        }
+    }
+    const int Lv = a.up ? 2 * Lb_in : Lb_in;
 
     {   // stage the window: virtual row v of the item is row v >> up of x, 0 outside [0, Lv)
         const int QPR = Cp >> 2, total = R * QPR;
@@ -134,7 +182,7 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
 
     // Epilogue.  D[co][t]: lane & 31 = time row, registers 4g .. 4g+3 = channels ct*32 + 8g + 4*(lane >> 5) + {0..3}.
     const int t = i0 + lo;
-    const bool ok = active && t < a.L_out;
+    const bool ok = active && t < Lb_out;
     const size_t row = (size_t)b * a.L_out + (ok ? t : 0);
     if (active) {
 #pragma unroll
@@ -224,6 +272,9 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
             }
         }
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (RAGGED) {
+            if (a.zero_tail && active && t >= Lb_out && t < a.L_out) store_zero_row(a, b, ct, t, hi);
+        }
     }
 }
 
@@ -240,6 +291,9 @@ struct FlowLaunch {
     const float* wdec;     // latent_dec_proj kernel [latent][C], then bias [C]
     float* y;              // [B, Tq, C]
     int Tq, latent, FH, n_flow, C, ld, ce_off, ce_stride;
+    // RAGGED only: item b has item_frames(lengths, b, len_T, len_shift) >> len_shift latent rows
+    const int32_t* lengths;
+    int len_T, len_shift;
 };
 
 constexpr int kFlowRows = 16;
@@ -251,12 +305,18 @@ inline size_t flow_lds_bytes(int latent, int FH) {
     return ((size_t)kFlowRows * latent + 2 * (size_t)(kFlowRows + 2) * half + (size_t)kFlowRows * FH) * sizeof(float);
 }
 
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int TT = kFlowRows;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int b = blockIdx.y, r0 = blockIdx.x * TT;
-    const int latent = a.latent, half = latent >> 1, FH = a.FH, Tq = a.Tq;
+    const int latent = a.latent, half = latent >> 1, FH = a.FH, Tq = a.Tq;   // Tq: the row stride of an item
+    int Tb = Tq;                                                              // the item's rows: the bound
+    if constexpr (RAGGED) {
+        Tb = item_frames(a.lengths, b, a.len_T, a.len_shift) >> a.len_shift;
+        if (r0 >= Tb) return;                                                 // block-uniform, before the first barrier
+    }
     float* zt = lds;                              // [TT][latent]      the tile of z (x1 | x2)
     float* ce = zt + TT * latent;                 // [TT + 2][half]    gelu(cond_proj(lat_cond)), rows r0 - 1 ..
     float* hin = ce + (TT + 2) * half;            // [TT + 2][half]    x1 + ce, 0 outside the item ('same' padding)
@@ -265,7 +325,7 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
 
     for (int idx = tid; idx < TT * latent; idx += nthr) {
         const int r = idx / latent, c = idx - r * latent, t = r0 + r;
-        zt[idx] = t < Tq ? a.z[((size_t)b * Tq + t) * latent + c] : 0.f;
+        zt[idx] = t < Tb ? a.z[((size_t)b * Tq + t) * latent + c] : 0.f;
     }
     for (int jj = a.n_flow - 1; jj >= 0; --jj) {                      // reversed(layers_list), vae.py:237-239
         const float* wpre = a.w + (size_t)jj * per;
@@ -278,7 +338,7 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
         for (int idx = tid; idx < (TT + 2) * half; idx += nthr) {
             const int r = idx / half, c = idx - r * half, t = r0 - 1 + r;
             float cev = 0.f, hv = 0.f;
-            if (t >= 0 && t < Tq) {
+            if (t >= 0 && t < Tb) {
                 const size_t grow = (size_t)b * Tq + t;
                 cev = gelu_tanh(a.cond[grow * a.ld + a.ce_off + jj * a.ce_stride + c]);
                 hv = a.z[grow * latent + c] + cev;                   // x1 is z_prior's first half in every coupling
@@ -313,7 +373,7 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
     const float* bdec = a.wdec + (size_t)latent * a.C;
     for (int idx = tid; idx < TT * a.C; idx += nthr) {
         const int r = idx / a.C, co = idx - r * a.C, t = r0 + r;
-        if (t >= Tq) continue;
+        if (t >= Tb) continue;
         float acc = bdec[co];
         for (int l = 0; l < latent; ++l) acc = fmaf(zt[r * latent + l], a.wdec[(size_t)l * a.C + co], acc);
         a.y[((size_t)b * Tq + t) * a.C + co] = acc;
@@ -332,13 +392,19 @@ inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stre
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     dim3 grid((unsigned)((a.L_out + kGemmRows - 1) / kGemmRows), (unsigned)((a.n_ct + nw - 1) / nw), (unsigned)B);
     dim3 block((unsigned)(64 * nw));
-    if (fused) return launch_kernel_named("vae_gemm_kernel<fused>", vae_gemm_kernel<true>, grid, block, lds_bytes, stream, a);
-    return launch_kernel_named("vae_gemm_kernel", vae_gemm_kernel<false>, grid, block, lds_bytes, stream, a);
+    if (a.lengths) {
+        if (fused) return launch_kernel_named("vae_gemm_kernel_ragged<fused>", vae_gemm_kernel<true, true>, grid, block, lds_bytes, stream, a);
+        return launch_kernel_named("vae_gemm_kernel_ragged", vae_gemm_kernel<false, true>, grid, block, lds_bytes, stream, a);
+    }
+    if (fused) return launch_kernel_named("vae_gemm_kernel<fused>", vae_gemm_kernel<true, false>, grid, block, lds_bytes, stream, a);
+    return launch_kernel_named("vae_gemm_kernel", vae_gemm_kernel<false, false>, grid, block, lds_bytes, stream, a);
 }
 
 inline hipError_t launch_flow(const FlowLaunch& a, int B, hipStream_t stream) {
     dim3 grid((unsigned)((a.Tq + kFlowRows - 1) / kFlowRows), (unsigned)B), block(256);
-    return launch_kernel_named("vae_flow_kernel", vae_flow_kernel, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
+    if (a.lengths)
+        return launch_kernel_named("vae_flow_kernel_ragged", vae_flow_kernel<true>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
+    return launch_kernel_named("vae_flow_kernel", vae_flow_kernel<false>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
 }
 #endif
 

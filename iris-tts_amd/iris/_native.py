@@ -191,6 +191,7 @@ VAE_SYMBOLS = {
     "iris_vae_decoder_destroy": (_i32, [_vp]),
     "iris_vae_decoder_workspace_bytes": (_i32, [_vp, _i32, _i32, _u64p]),
     "iris_vae_decoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_vae_decoder_forward_ragged": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_launch_count": (_i32, [_vp, _i32, _i32, _ip]),
     "iris_vae_decoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
 }

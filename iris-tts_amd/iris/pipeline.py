@@ -128,11 +128,14 @@ class MelToWavePipeline:
         item i has ``hop * ceil(frames_per_item[i] / factor) * factor`` samples.  ``durations`` (integer ``[B, P]``)
         replaces the duration head's prediction.
 
-        ``B == 1``: one chain on one stream; the only read-back is the frame total.  ``B > 1``: the encoder and the head
-        run ONCE over the ragged batch (``lengths``); the VAE decoder has no ragged form, so each item's conditioning --
-        padded from its own total -- goes through it on its own, and the mels go through ``infer_batch``.  The result is
-        then a list, item i bit for bit the ``B == 1`` call on ``ids[i, :lengths[i]]``; ``z_prior`` is a list of per-item
-        priors (or None), and ``**kw`` goes to ``infer`` / ``infer_batch``."""
+        ``B == 1``: one chain on one stream; the only read-back is the frame total.  ``B > 1``: every stage runs ONCE over
+        the ragged batch -- the encoder and the head (``lengths``), then the VAE decoder over the whole conditioning with
+        item i's length ``ceil(frames_per_item[i] / factor) * factor`` (``generate_device(..., lengths=)``), then
+        ``infer_batch`` over slices of its one mel.  The result is then a list, item i bit for bit the ``B == 1`` call on
+        ``ids[i, :lengths[i]]``; ``z_prior`` is a list of per-item priors ``[1, T_i / factor, latent_dim]`` (or None: they
+        are drawn per item, in item order, as the ``B == 1`` calls would draw them), and ``**kw`` goes to ``infer`` /
+        ``infer_batch``.  An acoustic stage without ``takes_lengths`` (a plain callable) gets each item's conditioning --
+        cut at its own padded total -- on its own instead."""
         if self.text is None or self.acoustic is None:
             raise ValueError("infer_from_phonemes needs text=(PhonemeEncoder, DurationPredictor) and acoustic=TextConditionedVAE(...)")
         from .encoder import frame_conditioning
@@ -144,12 +147,32 @@ class MelToWavePipeline:
         if z_prior is not None and len(z_prior) != cond.shape[0]:
             raise ValueError(f"z_prior must be a list of {cond.shape[0]} per-item priors")
         gen = getattr(self.acoustic, "generate_device", None)
+        padded = [-(-total // factor) * factor for total in per_item]
+        if gen is not None and getattr(self.acoustic, "takes_lengths", False):
+            mel = gen(cond, self._pack_priors(z_prior, cond, padded, factor), want_residual=False, lengths=padded)[0]
+            return self.infer_batch([mel[i, :, :n] for i, n in enumerate(padded)], **kw), per_item
         mels = []
-        for i, total in enumerate(per_item):
-            c = cond[i:i + 1, :-(-total // factor) * factor]
+        for i, n in enumerate(padded):
+            c = cond[i:i + 1, :n]
             z = None if z_prior is None else z_prior[i]
             mels.append((gen(c, z, want_residual=False)[0] if gen is not None else self.acoustic(c, z)[0])[0])
         return self.infer_batch(mels, **kw), per_item
+
+    def _pack_priors(self, z_prior, cond: torch.Tensor, padded: Sequence[int], factor: int) -> torch.Tensor:
+        """Per-item priors ``[1, padded[i] / factor, latent_dim]`` -> one ``[B, T / factor, latent_dim]`` for the ragged VAE
+        call; rows past an item's own stay 0 and are never read.  ``z_prior=None``: each item's prior is drawn here, in item
+        order and in the shape its own ``generate_device`` call would draw, so the random stream consumed is the same."""
+        latent = int(self.acoustic.latent_dim)
+        packed = torch.zeros((len(padded), cond.shape[1] // factor, latent), dtype=torch.float32, device=cond.device)
+        for i, n in enumerate(padded):
+            if z_prior is None:
+                z = torch.randn((1, n // factor, latent), device=cond.device, dtype=torch.float32)
+            else:
+                z = torch.as_tensor(z_prior[i])
+                if tuple(z.shape) != (1, n // factor, latent):
+                    raise ValueError(f"expected z_prior[{i}] [1, {n // factor}, {latent}], got {tuple(z.shape)}")
+            packed[i, :n // factor] = z[0]
+        return packed
 
     def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False, resampler=None) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform

@@ -51,6 +51,9 @@ from ._engine import require_gpu
 
 
 class TextConditionedVAE:
+    #: ``generate`` / ``generate_device`` take ``lengths=`` (a ragged batch in one forward); ``MelToWavePipeline`` checks this
+    takes_lengths = True
+
     def __init__(self, n_mels: int, cond_dim: int, model_channels: int = 192, latent_dim: int = 16,
                  num_wavenet_blocks: int = 8, decoder_blocks: int = 4, wavenet_kernel_size: int = 5, down_stages: int = 2,
                  flow_layers: int = 4, flow_hidden: int = 64, dropout: float = 0.1, name: Optional[str] = None,
@@ -209,6 +212,27 @@ class TextConditionedVAE:
                              "first (scripts/synthesize.py:117-122 does); nothing is padded silently")
         return B, T
 
+    def _check_lengths(self, lengths, B: int, T: int):
+        """``lengths`` of a ragged call -> an int32 device tensor, passed through unread, or a validated int32 host array.
+        Host lengths are checked here, before any device work; a device tensor is sanitised by the kernels instead."""
+        if isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu":
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+                raise ValueError(f"device lengths must be an int32 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+            return lengths
+        arr = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
+        if arr.ndim != 1 or arr.shape[0] != B:
+            raise ValueError(f"lengths must hold {B} frame counts (one per item), got shape {tuple(arr.shape)}")
+        if arr.size and not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"lengths must be integers, got {arr.dtype}")
+        arr = arr.astype(np.int64)
+        for b, n in enumerate(arr.tolist()):
+            if not 0 <= n <= T:
+                raise ValueError(f"lengths[{b}] = {n} is outside [0, T = {T}]")
+            if n % self.downsample_factor:
+                raise ValueError(f"lengths[{b}] = {n} is not a multiple of 2^down_stages = {self.downsample_factor}: pad the "
+                                 "item's conditioning first; nothing is padded silently")
+        return arr.astype(np.int32)
+
     def launch_count(self, B: int, T: int) -> int:
         """Kernel launches of one ``generate_device(..., want_residual=True)`` (one fewer without the residual)."""
         lib = self._ensure()
@@ -217,13 +241,22 @@ class TextConditionedVAE:
         return int(n.value)
 
     def generate_device(self, cond: torch.Tensor, z_prior: Optional[torch.Tensor] = None, want_residual: bool = True,
-                        generator: Optional[torch.Generator] = None):
+                        generator: Optional[torch.Generator] = None, lengths=None):
         """``cond [B, T, cond_dim]``, ``z_prior [B, T / 2^S, latent_dim]`` (fp32 device tensors) -> ``(mel [B, n_mels, T],
         residual [B, T, cond_dim] or None)``, asynchronous on the current stream; the mel is contiguous and channels-first,
         as ``PostNet.forward_device`` and ``GeneratorEngine.forward`` read it.  ``z_prior=None`` draws ``torch.randn`` on the
         device (from ``generator`` when given): a standard normal as in the reference, but NOT the numbers JAX would draw
-        from ``SeedGenerator(1337)`` -- pass ``z_prior`` to reproduce a reference run."""
+        from ``SeedGenerator(1337)`` -- pass ``z_prior`` to reproduce a reference run.
+
+        ``lengths`` (``B`` frame counts: a host sequence or numpy array, or an int32 device tensor) makes the batch ragged in
+        ONE forward (``iris_vae_decoder_forward_ragged``): item b is bit for bit the batch-of-one call on ``cond[b:b+1,
+        :lengths[b]]`` and ``z_prior[b:b+1, :lengths[b] / 2^S]``, ``mel[b, :, lengths[b]:]`` and ``residual[b, lengths[b]:]``
+        are 0, and ``cond`` / ``z_prior`` rows past an item's length are never read.  Host lengths must lie in ``[0, T]`` and
+        be multiples of ``2^S`` (``ValueError`` otherwise, before any device work); a device tensor is never read by the
+        host -- the kernels clamp it to ``[0, T]`` and round it down to a multiple of ``2^S``."""
         B, T = self._check_cond(tuple(cond.shape))
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, B, T)
         lib = self._ensure()
         cond = cond.to(device=self._device, dtype=torch.float32).contiguous()
         Tq = T // self.downsample_factor
@@ -241,21 +274,32 @@ class TextConditionedVAE:
         if self._workspace is None or self._workspace.numel() < n.value:
             self._workspace = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=self._device)
         stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
-        _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(
+        out = (ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(residual.data_ptr() if want_residual else None),
+               ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream)
+        if lengths is None:
+            _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(
+                self._handle, ctypes.c_void_p(cond.data_ptr()), ctypes.c_void_p(z_prior.data_ptr()), B, T, *out))
+            return mel, residual
+        if not isinstance(lengths, torch.Tensor):
+            lengths = torch.from_numpy(lengths)
+        lengths = lengths.to(self._device).contiguous()
+        _native.check("iris_vae_decoder_forward_ragged", lib.iris_vae_decoder_forward_ragged(
             self._handle, ctypes.c_void_p(cond.data_ptr()), ctypes.c_void_p(z_prior.data_ptr()), B, T,
-            ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(residual.data_ptr() if want_residual else None),
-            ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream))
+            ctypes.c_void_p(lengths.data_ptr()), *out))
         return mel, residual
 
-    def generate(self, frame_text_cond, z_prior=None, generator: Optional[torch.Generator] = None):
-        """Reference ``generate`` (vae.py:448-482): numpy in -> numpy out, device tensors in -> device tensors out."""
+    def generate(self, frame_text_cond, z_prior=None, generator: Optional[torch.Generator] = None, lengths=None):
+        """Reference ``generate`` (vae.py:448-482): numpy in -> numpy out, device tensors in -> device tensors out.
+        ``lengths``: a ragged batch, as in ``generate_device``."""
         if isinstance(frame_text_cond, torch.Tensor):
-            return self.generate_device(frame_text_cond, z_prior, True, generator)
+            return self.generate_device(frame_text_cond, z_prior, True, generator, lengths)
         cond = np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32))
-        self._check_cond(cond.shape)
+        B, T = self._check_cond(cond.shape)
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, B, T)
         self._ensure()
         z = None if z_prior is None else torch.from_numpy(np.ascontiguousarray(np.asarray(z_prior, dtype=np.float32))).to(self._device)
-        mel, residual = self.generate_device(torch.from_numpy(cond).to(self._device), z, True, generator)
+        mel, residual = self.generate_device(torch.from_numpy(cond).to(self._device), z, True, generator, lengths)
         return mel.cpu().numpy(), residual.cpu().numpy()
 
     def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:

@@ -3,10 +3,16 @@
 ops (F.conv1d / F.linear, same weights) on the same GPU.
 
     python tools/vae_decoder_bench.py [--shapes 1x1024 8x1024] [--iters 200] [--rounds 5] [--out profiles/vae_decoder_bench.json]
+    python tools/vae_decoder_bench.py --ragged [--iters 200] [--rounds 5] [--out profiles/vae_ragged_bench.json]
 
 Device events around `iters` back-to-back forwards, after a warm-up of every shape; the two implementations alternate in
 every round and the median round is reported with the spread.  Both produce mel and residual; outputs are compared at the
 timed shape before timing.  Needs a GPU: there is no CPU fallback and no number without one.
+
+--ragged times a batch of 8 utterances of 128, 256, ..., 1024 frames three ways, alternating in every round: ONE ragged call
+(generate_device(..., lengths=)), eight batch-of-one calls at the items' own lengths (what a host loop over the items
+costs), and the dense 8 x 1024 call (what the ragged call's launches cost when every block has work).  Before timing,
+every item of the ragged call is compared with its batch-of-one call bit for bit.
 """
 from __future__ import annotations
 
@@ -87,16 +93,63 @@ def time_ms(fn, iters, dev):
     return start.elapsed_time(end) / iters
 
 
+def ragged_main(args, dev):
+    vae = TextConditionedVAE(80, 256, seed=1)
+    randomise(vae, 101)
+    lengths = [128 * (i + 1) for i in range(8)]
+    B, T, f = len(lengths), max(lengths), vae.downsample_factor
+    g = torch.Generator(device="cpu").manual_seed(B * 1000 + T)
+    cond = torch.randn(B, T, vae.cond_dim, generator=g).to(dev)
+    z = torch.randn(B, T // f, vae.latent_dim, generator=g).to(dev)
+    lengths_dev = torch.tensor(lengths, dtype=torch.int32, device=dev)
+    items = [(cond[b:b + 1, :n].contiguous(), z[b:b + 1, :n // f].contiguous()) for b, n in enumerate(lengths)]
+    ragged = lambda: vae.generate_device(cond, z, lengths=lengths_dev)
+
+    def loop():
+        return [vae.generate_device(c, zz) for c, zz in items]
+    dense = lambda: vae.generate_device(cond, z)
+    with torch.no_grad():
+        (mel, res), singles = ragged(), loop()
+        for b, n in enumerate(lengths):
+            if not (torch.equal(mel[b, :, :n], singles[b][0][0]) and torch.equal(res[b, :n], singles[b][1][0])):
+                raise SystemExit(f"item {b}: the ragged call differs from its batch-of-one call")
+            if mel[b, :, n:].any() or res[b, n:].any():
+                raise SystemExit(f"item {b}: rows past its length are not 0")
+        for _ in range(20):
+            ragged(); loop(); dense()
+        rounds = [(time_ms(ragged, args.iters, dev), time_ms(loop, args.iters, dev), time_ms(dense, args.iters, dev))
+                  for _ in range(args.rounds)]
+    r = np.array(rounds)
+    med = np.median(r, axis=0)
+    keys = ("ragged_ms", "loop_of_8_ms", "dense_8x1024_ms")
+    rec = {"lengths": lengths, "T": T}
+    for i, k in enumerate(keys):
+        rec[k] = float(med[i])
+        rec[k + "_min_max"] = [float(r[:, i].min()), float(r[:, i].max())]
+    rec.update({"ratio_loop_over_ragged": float(med[1] / med[0]), "ratio_ragged_over_dense": float(med[0] / med[2]),
+                "launches_ragged": vae.launch_count(B, T), "launches_loop": sum(vae.launch_count(1, n) for n in lengths),
+                "items_bit_for_bit_their_batch_of_one_calls": True, "iters": args.iters, "rounds": args.rounds,
+                "timing": "device events around `iters` back-to-back calls (launch gaps included), median of rounds; "
+                          "the three ways alternate in every round; lengths are a device tensor made once"})
+    print(json.dumps(rec), flush=True)
+    out = Path(args.out or REPO / "profiles" / "vae_ragged_bench.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps({"gpu": torch.cuda.get_device_name(dev), "results": [rec]}, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", action="store_true", help="time the ragged batch of 8 against the loop and the dense call")
     ap.add_argument("--shapes", nargs="+", default=["1x1024", "8x1024"])
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=str(REPO / "profiles" / "vae_decoder_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/vae_decoder_bench.json (vae_ragged_bench.json with --ragged)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vae_decoder_bench needs a HIP device: nothing is measured without one")
     dev = torch.device("cuda", 0)
+    if args.ragged:
+        return ragged_main(args, dev)
     vae = TextConditionedVAE(80, 256, seed=1)
     randomise(vae, 101)
     graph = TorchGraph(vae, dev)
@@ -126,7 +179,7 @@ def main():
                "timing": "device events around `iters` back-to-back forwards (launch gaps included), median of rounds"}
         print(json.dumps(rec), flush=True)
         results.append(rec)
-    out = Path(args.out)
+    out = Path(args.out or REPO / "profiles" / "vae_decoder_bench.json")
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"gpu": torch.cuda.get_device_name(dev), "results": results}, indent=1) + "\n")
 
