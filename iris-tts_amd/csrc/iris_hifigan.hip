@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "generator_internal.h"
+#include "stage_host.h"
 #include "host_parallel.h"
 #include "conv_mfma_f32.h"
 #include "mrf_conv_mfma_f32.h"
@@ -1112,13 +1113,27 @@ int32_t iris_hifigan_op_mrf_pair(const float* const* x_dev, const float* const* 
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"
 
-struct iris_postnet_handle {
+struct iris_postnet_handle : StageHandle {
     int n_mels = 0, num_layers = 0, channels = 0, k = 0;
-    std::vector<ConvLayer> layers;
-    float* blob = nullptr;
-    size_t blob_floats = 0;
-    int device = 0;
+    std::vector<PackedGemm> layers;
 };
+
+namespace {
+
+// workspace: two ping-pong hidden buffers [B, T, channels] and the residual [B, T, n_mels]
+struct PostnetWs { size_t hid[2], res, total; };   // float offsets; every buffer starts on 256 bytes
+
+PostnetWs postnet_ws(const iris_postnet_handle* h, int B, int T) {
+    const size_t frames = (size_t)B * T;
+    PostnetWs w;
+    WsTaker t;
+    w.hid[0] = t.take(frames * h->channels); w.hid[1] = t.take(frames * h->channels);
+    w.res = t.take(frames * h->n_mels);
+    w.total = t.off;
+    return w;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1128,64 +1143,38 @@ int32_t iris_postnet_create(int32_t n_mels, int32_t num_layers, int32_t channels
     if (!weights_host || !out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (n_mels < 1 || channels < 1 || num_layers < 2 || num_layers > 64 || kernel_size < 1 || !(kernel_size & 1))
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "PostNet needs n_mels, channels >= 1, 2 <= num_layers <= 64, odd kernel_size");
-    iris_postnet_handle* h = new (std::nothrow) iris_postnet_handle;
+    std::unique_ptr<iris_postnet_handle> h(new (std::nothrow) iris_postnet_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->n_mels = n_mels; h->num_layers = num_layers; h->channels = channels; h->k = kernel_size;
+    h->layers.resize(num_layers);
     uint64_t expect = 0;
-    size_t off = 0;
     for (int i = 0; i < num_layers; ++i) {
-        ConvLayer l;
+        PackedGemm& l = h->layers[i];
         l.C_in = i == 0 ? n_mels : channels;
         l.C_out = i == num_layers - 1 ? n_mels : channels;
         l.k = kernel_size;
-        l.ref_w_floats = (size_t)l.C_in * l.C_out * l.k;
-        l.w_floats = packed_conv1d_floats(l.C_in, l.C_out, l.k);
-        l.w_off = off; off += (l.w_floats + 3) & ~(size_t)3;
-        l.b_off = off; off += ((size_t)l.C_out + 3) & ~(size_t)3;
-        expect += l.ref_w_floats + l.C_out;
-        h->layers.push_back(l);
+        expect += (uint64_t)l.C_in * l.C_out * l.k + l.C_out;
     }
-    h->blob_floats = off;
-    if (n_weights != expect) {
-        delete h;
+    if (n_weights != expect)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "weight blob has %llu values, PostNet needs %llu",
                     (unsigned long long)n_weights, (unsigned long long)expect);
-    }
-    std::vector<float> host(h->blob_floats, 0.f);
-    const float* src = weights_host;
-    for (const ConvLayer& l : h->layers) {
-        pack_conv1d_weights(src, l.C_in, l.C_out, l.k, host.data() + l.w_off);
-        src += l.ref_w_floats;
-        memcpy(host.data() + l.b_off, src, sizeof(float) * l.C_out);
-        src += l.C_out;
-    }
-    hipError_t e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->blob, h->blob_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->blob, host.data(), h->blob_floats * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->blob) (void)hipFree(h->blob);
-        delete h;
-        return fail(IRIS_HIFIGAN_HIP_ERROR, "PostNet weight upload failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    BlobBuilder bb(weights_host);
+    for (PackedGemm& l : h->layers) bb.dense(l, l.C_in, l.C_out, l.k);
+    TRY(upload(bb.host, h.get(), "PostNet"));
+    *out = h.release();
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 
 int32_t iris_postnet_destroy(iris_postnet_handle* h) {
-    if (!h) return IRIS_HIFIGAN_OK;
-    if (h->blob) (void)hipFree(h->blob);
     delete h;
     return IRIS_HIFIGAN_OK;
 }
 
-// workspace: two ping-pong hidden buffers [B, T, channels] and the residual [B, T, n_mels]
 int32_t iris_postnet_workspace_bytes(const iris_postnet_handle* h, int32_t B, int32_t T, uint64_t* bytes) {
     if (!h || !bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     if (B < 0 || T < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    const size_t frames = (size_t)B * T;
-    const size_t hid = (frames * h->channels + 63) & ~(size_t)63, res = (frames * h->n_mels + 63) & ~(size_t)63;
-    *bytes = (2 * hid + res) * sizeof(float);
+    *bytes = (uint64_t)postnet_ws(h, B, T).total * sizeof(float);
     return IRIS_HIFIGAN_OK;
 }
 
@@ -1204,21 +1193,15 @@ int postnet_forward(iris_postnet_handle* h, const void* mel_dev, int32_t B, int3
     if (ragged && !lengths) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
     if (!mel_dev || !out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
     if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
-    uint64_t need = 0;
-    TRY(iris_postnet_workspace_bytes(h, B, T, &need));
-    if (workspace_bytes < need)
-        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)need);
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
-    const size_t frames = (size_t)B * T;
-    const size_t hid = (frames * h->channels + 63) & ~(size_t)63;
+    const PostnetWs w = postnet_ws(h, B, T);
+    ForwardScope scope(*h, workspace_bytes, w.total);
+    TRY(scope.rc);
     float* ws = (float*)workspace_dev;
-    float* hbuf[2] = {ws, ws + hid};
-    float* res = ws + 2 * hid;
+    float* hbuf[2] = {ws + w.hid[0], ws + w.hid[1]};
+    float* res = ws + w.res;
     const float* x = (const float*)mel_dev;
     for (int i = 0; i < h->num_layers; ++i) {
-        const ConvLayer& l = h->layers[i];
+        const PackedGemm& l = h->layers[i];
         const bool last = i == h->num_layers - 1;
         const ConvProblem p = conv_problem(x, h->blob + l.w_off, h->blob + l.b_off, nullptr, last ? res : hbuf[i & 1], l.k, 1);
         ConvLaunch a = conv_launch(&p, 1, B, T, l.C_in, l.C_out, IN_ACT_NONE, 0.f, lengths, 1);

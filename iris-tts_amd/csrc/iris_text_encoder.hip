@@ -7,51 +7,21 @@
 #include <new>
 #include <vector>
 
-#include "generator_internal.h"
-#define IRIS_KERNELS_ONLY      // conv_mfma_f32.h: types and weight packers only -- its kernels and launch code live in iris_hifigan.o
-#include "conv_mfma_f32.h"
-#undef IRIS_KERNELS_ONLY
+#include "stage_host.h"
 #include "text_encoder.h"
 
 using namespace iris;
 
 namespace {
 
-struct TxtDense { int C_in = 0, C_out = 0, k = 1; size_t w_off = 0, b_off = 0; };   // float offsets into the device blob
 struct TxtNorm { size_t g_off = 0, b_off = 0; };
-struct TxtBlock { TxtDense qkv, out, ffn1, ffn2; TxtNorm attn_norm, ffn_norm; };
+struct TxtBlock { PackedGemm qkv, out, ffn1, ffn2; TxtNorm attn_norm, ffn_norm; };
 
 constexpr float kLayerNormEps = 1e-6f;                     // layers.LayerNormalization(epsilon=1e-6), encoder.py:71,80,184,275
 
-// Packs the blob's tensors into the device image: GEMM weights in fragment order, everything else as it comes.
-struct BlobBuilder {
-    std::vector<float> host;
-    const float* src;
-    size_t reserve(size_t n) { size_t o = host.size(); host.resize(o + ((n + 3) & ~(size_t)3), 0.f); return o; }
-    size_t raw(size_t n) { const size_t o = reserve(n); memcpy(host.data() + o, src, sizeof(float) * n); src += n; return o; }
-    void dense(TxtDense& l, int C_in, int C_out, int k) {  // [C_out][C_in][k], then the bias
-        l.C_in = C_in; l.C_out = C_out; l.k = k;
-        l.w_off = reserve(packed_conv1d_floats(C_in, C_out, k));
-        pack_conv1d_weights(src, C_in, C_out, k, host.data() + l.w_off);
-        src += (size_t)C_in * C_out * k;
-        l.b_off = raw(C_out);
-    }
-    void norm(TxtNorm& n, int C) { n.g_off = raw(C); n.b_off = raw(C); }
-};
+void pack_norm(BlobBuilder& bb, TxtNorm& n, int C) { n.g_off = bb.raw(C); n.b_off = bb.raw(C); }
 
-int upload(const std::vector<float>& host, float** blob, int* device, const char* what) {
-    hipError_t e = hipGetDevice(device);
-    if (e == hipSuccess) e = hipMalloc(blob, host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(*blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (*blob) (void)hipFree(*blob);
-        *blob = nullptr;
-        return fail(IRIS_HIFIGAN_HIP_ERROR, "%s weight upload failed: %s", what, hipGetErrorString(e));
-    }
-    return IRIS_HIFIGAN_OK;
-}
-
-txt::GemmLaunch gemm_args(const float* blob, const float* x, const TxtDense& l, float* y, const int32_t* lengths, int P) {
+txt::GemmLaunch gemm_args(const float* blob, const float* x, const PackedGemm& l, float* y, const int32_t* lengths, int P) {
     txt::GemmLaunch a; memset(&a, 0, sizeof(a));
     a.x = x; a.wp = (const f32x4*)(blob + l.w_off); a.bias = blob + l.b_off; a.y = y; a.lengths = lengths;
     a.P = P; a.C_in = l.C_in; a.C_out = l.C_out; a.ks = l.k; a.eps = kLayerNormEps;
@@ -66,30 +36,16 @@ int check_shape(int32_t B, int32_t P) {
     return IRIS_HIFIGAN_OK;
 }
 
-// counts the launches of `run` instead of issuing them (no pointer is dereferenced)
-template <class Fn> int count_launches(Fn run, int32_t* n) {
-    DryRun d{nullptr, 0, 0, 256};
-    DryRun* const prev = dry_run_slot();
-    dry_run_slot() = &d;
-    const int rc = run(reinterpret_cast<float*>(uintptr_t(256)));
-    dry_run_slot() = prev;
-    TRY(rc);
-    *n = d.n;
-    return IRIS_HIFIGAN_OK;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // Phoneme encoder (PhonemeEncoder, src/iris/encoder.py:115-212)
 // ------------------------------------------------------------------------------------------------
-struct iris_phoneme_encoder_handle {
+struct iris_phoneme_encoder_handle : StageHandle {
     iris_phoneme_encoder_config cfg;
     size_t tok_off = 0, pos_off = 0;
     std::vector<TxtBlock> blocks;
     TxtNorm final_norm;
-    float* blob = nullptr;
-    int device = 0;
 };
 
 namespace {
@@ -124,11 +80,10 @@ struct EncWs { size_t x0, x1, t0, qkv, attn, ffn, total; };   // float offsets; 
 EncWs enc_ws(const iris_phoneme_encoder_config& c, int B, int P) {
     const size_t rows = (size_t)B * P, E = c.embed_dim;
     EncWs w;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
-    w.x0 = take(rows * E); w.x1 = take(rows * E); w.t0 = take(rows * E);
-    w.qkv = take(rows * 3 * E); w.attn = take(rows * E); w.ffn = take(rows * c.ffn_dim);
-    w.total = off;
+    WsTaker t;
+    w.x0 = t.take(rows * E); w.x1 = t.take(rows * E); w.t0 = t.take(rows * E);
+    w.qkv = t.take(rows * 3 * E); w.attn = t.take(rows * E); w.ffn = t.take(rows * c.ffn_dim);
+    w.total = t.off;
     return w;
 }
 
@@ -194,8 +149,8 @@ void enc_layout(iris_phoneme_encoder_handle* h, BlobBuilder* bb) {
     h->blocks.resize(c.num_blocks);
     if (!bb) {
         for (auto& k : h->blocks) {
-            k.qkv = TxtDense{E, 3 * E, 1, 0, 0}; k.out = TxtDense{E, E, 1, 0, 0};
-            k.ffn1 = TxtDense{E, F, 1, 0, 0}; k.ffn2 = TxtDense{F, E, 1, 0, 0};
+            k.qkv = PackedGemm{E, 3 * E, 1, 0, 0}; k.out = PackedGemm{E, E, 1, 0, 0};
+            k.ffn1 = PackedGemm{E, F, 1, 0, 0}; k.ffn2 = PackedGemm{F, E, 1, 0, 0};
         }
         return;
     }
@@ -204,12 +159,12 @@ void enc_layout(iris_phoneme_encoder_handle* h, BlobBuilder* bb) {
     for (auto& k : h->blocks) {
         bb->dense(k.qkv, E, 3 * E, 1);
         bb->dense(k.out, E, E, 1);
-        bb->norm(k.attn_norm, E);
+        pack_norm(*bb, k.attn_norm, E);
         bb->dense(k.ffn1, E, F, 1);
         bb->dense(k.ffn2, F, E, 1);
-        bb->norm(k.ffn_norm, E);
+        pack_norm(*bb, k.ffn_norm, E);
     }
-    bb->norm(h->final_norm, E);
+    pack_norm(*bb, h->final_norm, E);
 }
 
 }  // namespace
@@ -217,13 +172,11 @@ void enc_layout(iris_phoneme_encoder_handle* h, BlobBuilder* bb) {
 // ------------------------------------------------------------------------------------------------
 // Duration head (DurationPredictor, encoder.py:228-315; predict_durations, scripts/synthesize.py:41-45)
 // ------------------------------------------------------------------------------------------------
-struct iris_duration_predictor_handle {
+struct iris_duration_predictor_handle : StageHandle {
     iris_duration_predictor_config cfg;
-    std::vector<TxtDense> conv;
+    std::vector<PackedGemm> conv;
     std::vector<TxtNorm> norm;
     size_t out_off = 0;                                    // duration_output kernel [C], then its bias
-    float* blob = nullptr;
-    int device = 0;
 };
 
 namespace {
@@ -256,10 +209,9 @@ struct DurWs { size_t d[3]; size_t total; };
 
 DurWs dur_ws(const iris_duration_predictor_config& c, int B, int P) {
     DurWs w;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
-    for (int i = 0; i < 3; ++i) w.d[i] = take((size_t)B * P * c.hidden_dim);
-    w.total = off;
+    WsTaker t;
+    for (int i = 0; i < 3; ++i) w.d[i] = t.take((size_t)B * P * c.hidden_dim);
+    w.total = t.off;
     return w;
 }
 
@@ -303,9 +255,9 @@ void dur_layout(iris_duration_predictor_handle* h, BlobBuilder* bb) {
     h->conv.resize(c.num_layers); h->norm.resize(c.num_layers);
     for (int i = 0; i < c.num_layers; ++i) {
         const int C_in = i == 0 ? c.in_dim : c.hidden_dim;
-        if (!bb) { h->conv[i] = TxtDense{C_in, c.hidden_dim, c.kernel_size, 0, 0}; continue; }
+        if (!bb) { h->conv[i] = PackedGemm{C_in, c.hidden_dim, c.kernel_size, 0, 0}; continue; }
         bb->dense(h->conv[i], C_in, c.hidden_dim, c.kernel_size);
-        bb->norm(h->norm[i], c.hidden_dim);
+        pack_norm(*bb, h->norm[i], c.hidden_dim);
     }
     if (bb) h->out_off = bb->raw((size_t)dur_out_channels(c) + 1);
 }
@@ -330,21 +282,18 @@ int32_t iris_phoneme_encoder_create(const iris_phoneme_encoder_config* cfg, cons
     if (n_weights != expect)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "weight blob has %llu values, the phoneme encoder needs %llu",
                     (unsigned long long)n_weights, (unsigned long long)expect);
-    iris_phoneme_encoder_handle* h = new (std::nothrow) iris_phoneme_encoder_handle;
+    std::unique_ptr<iris_phoneme_encoder_handle> h(new (std::nothrow) iris_phoneme_encoder_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
-    BlobBuilder bb; bb.src = weights_host;
-    enc_layout(h, &bb);
-    const int rc = upload(bb.host, &h->blob, &h->device, "phoneme encoder");
-    if (rc != IRIS_HIFIGAN_OK) { delete h; return rc; }
-    *out = h;
+    BlobBuilder bb(weights_host);
+    enc_layout(h.get(), &bb);
+    TRY(upload(bb.host, h.get(), "phoneme encoder"));
+    *out = h.release();
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 
 int32_t iris_phoneme_encoder_destroy(iris_phoneme_encoder_handle* h) {
-    if (!h) return IRIS_HIFIGAN_OK;
-    if (h->blob) (void)hipFree(h->blob);
     delete h;
     return IRIS_HIFIGAN_OK;
 }
@@ -374,12 +323,8 @@ int32_t iris_phoneme_encoder_forward(iris_phoneme_encoder_handle* h, const int32
     TRY(enc_check_shape(h->cfg, B, P));
     if (B == 0) return IRIS_HIFIGAN_OK;
     if (!ids_dev || !enc_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    const uint64_t need = (uint64_t)enc_ws(h->cfg, B, P).total * sizeof(float);
-    if (workspace_bytes < need)
-        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)need);
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    ForwardScope scope(*h, workspace_bytes, enc_ws(h->cfg, B, P).total);
+    TRY(scope.rc);
     return enc_forward(h, ids_dev, lengths_dev, B, P, enc_out_dev, (float*)workspace_dev, (hipStream_t)stream_);
     IRIS_ABI_END
 }
@@ -415,21 +360,18 @@ int32_t iris_duration_predictor_create(const iris_duration_predictor_config* cfg
     if (n_weights != expect)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "weight blob has %llu values, the duration predictor needs %llu",
                     (unsigned long long)n_weights, (unsigned long long)expect);
-    iris_duration_predictor_handle* h = new (std::nothrow) iris_duration_predictor_handle;
+    std::unique_ptr<iris_duration_predictor_handle> h(new (std::nothrow) iris_duration_predictor_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
-    BlobBuilder bb; bb.src = weights_host;
-    dur_layout(h, &bb);
-    const int rc = upload(bb.host, &h->blob, &h->device, "duration predictor");
-    if (rc != IRIS_HIFIGAN_OK) { delete h; return rc; }
-    *out = h;
+    BlobBuilder bb(weights_host);
+    dur_layout(h.get(), &bb);
+    TRY(upload(bb.host, h.get(), "duration predictor"));
+    *out = h.release();
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 
 int32_t iris_duration_predictor_destroy(iris_duration_predictor_handle* h) {
-    if (!h) return IRIS_HIFIGAN_OK;
-    if (h->blob) (void)hipFree(h->blob);
     delete h;
     return IRIS_HIFIGAN_OK;
 }
@@ -462,12 +404,8 @@ int32_t iris_duration_predictor_forward(iris_duration_predictor_handle* h, const
     if (B == 0) return IRIS_HIFIGAN_OK;
     if (!enc_out_dev || !pred_dev || !frames_dev || !offsets_dev || !totals_dev || !workspace_dev)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    const uint64_t need = (uint64_t)dur_ws(h->cfg, B, P).total * sizeof(float);
-    if (workspace_bytes < need)
-        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)need);
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    ForwardScope scope(*h, workspace_bytes, dur_ws(h->cfg, B, P).total);
+    TRY(scope.rc);
     return dur_forward(h, enc_out_dev, lengths_dev, B, P, pred_dev, frames_dev, offsets_dev, totals_dev, (float*)workspace_dev,
                        (hipStream_t)stream_);
     IRIS_ABI_END

@@ -5,10 +5,7 @@
 #include <new>
 #include <vector>
 
-#include "generator_internal.h"
-#define IRIS_KERNELS_ONLY      // conv_mfma_f32.h: types and weight packers only -- its kernels and launch code live in iris_hifigan.o
-#include "conv_mfma_f32.h"
-#undef IRIS_KERNELS_ONLY
+#include "stage_host.h"
 #include "vae_decoder.h"
 
 using namespace iris;
@@ -16,22 +13,12 @@ using namespace iris;
 // ------------------------------------------------------------------------------------------------
 // VAE decoder in front of the PostNet (TextConditionedVAE.generate, src/iris/vae.py:448-482; csrc/vae_decoder.h)
 // ------------------------------------------------------------------------------------------------
-namespace {
-
-struct VaeConv { int C_in = 0, C_out = 0, k = 1; size_t w_off = 0, b_off = 0; };   // float offsets into the device blob
-
-}  // namespace
-
-struct iris_vae_decoder_handle {
+struct iris_vae_decoder_handle : StageHandle {
     iris_vae_decoder_config cfg;
-    VaeConv cond_proj, out_proj, residual_proj, cond_gemm;
-    std::vector<VaeConv> down, up, dec_conv, dec_res;
+    PackedGemm cond_proj, out_proj, residual_proj, cond_gemm;
+    std::vector<PackedGemm> down, up, dec_conv, dec_res;
     size_t flow_off = 0, dec_proj_off = 0;       // raw (Keras-layout) flow couplings; latent_dec_proj kernel + bias
     int film_cols = 0, ce_off = 0, ce_stride = 0;  // columns of the conditioning GEMM; where the couplings' cond_proj start
-    float* blob = nullptr;
-    size_t blob_floats = 0;
-    int device = 0;
-    bool host_only = false;
 };
 
 namespace {
@@ -79,12 +66,11 @@ struct VaeWs { size_t p, q, latcond, film, d0, da, db, total; };   // float offs
 VaeWs vae_ws(const iris_vae_decoder_handle* h, int B, int T) {
     const size_t C = h->cfg.model_channels, frames = (size_t)B * T, lat = frames >> h->cfg.down_stages;
     VaeWs w;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 63) & ~(size_t)63; return o; };
-    w.p = take(frames * C); w.q = take(frames * C);
-    w.latcond = take(lat * C); w.film = take(lat * h->film_cols);
-    w.d0 = take(lat * C); w.da = take(lat * C); w.db = take(lat * C);
-    w.total = off;
+    WsTaker t;
+    w.p = t.take(frames * C); w.q = t.take(frames * C);
+    w.latcond = t.take(lat * C); w.film = t.take(lat * h->film_cols);
+    w.d0 = t.take(lat * C); w.da = t.take(lat * C); w.db = t.take(lat * C);
+    w.total = t.off;
     return w;
 }
 
@@ -112,7 +98,7 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
     const int C = c.model_channels, S = c.down_stages, Tq = T >> S;
     const VaeWs w = vae_ws(h, B, T);
     const float* blob = h->blob;
-    auto gemm = [&](const float* x, const VaeConv& l, float* y, int L_in, int L_out, int sh_in, int sh_out) {
+    auto gemm = [&](const float* x, const PackedGemm& l, float* y, int L_in, int L_out, int sh_in, int sh_out) {
         vae::GemmLaunch a; memset(&a, 0, sizeof(a));
         a.lengths = lengths; a.len_T = T; a.len_shift = S; a.sh_in = sh_in; a.sh_out = sh_out;
         a.x = x; a.wp = (const f32x4*)(blob + l.w_off); a.bias = blob + l.b_off; a.y = y;
@@ -195,7 +181,7 @@ int32_t iris_vae_decoder_create(const iris_vae_decoder_config* cfg, const float*
     if (n_weights != expect)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "weight blob has %llu values, the VAE decoder needs %llu",
                     (unsigned long long)n_weights, (unsigned long long)expect);
-    iris_vae_decoder_handle* h = new (std::nothrow) iris_vae_decoder_handle;
+    std::unique_ptr<iris_vae_decoder_handle> h(new (std::nothrow) iris_vae_decoder_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
     const iris_vae_decoder_config& c = h->cfg;
@@ -203,68 +189,38 @@ int32_t iris_vae_decoder_create(const iris_vae_decoder_config* cfg, const float*
     const int hp = (half + 3) & ~3;                            // a coupling's cond_proj columns, padded to a 16-byte piece
     h->film_cols = c.decoder_blocks * 2 * C + c.flow_layers * hp;
     h->ce_off = c.decoder_blocks * 2 * C; h->ce_stride = hp;
-    std::vector<float> host;
-    auto reserve = [&](size_t n) { size_t o = host.size(); host.resize(o + ((n + 3) & ~(size_t)3), 0.f); return o; };
-    const float* src = weights_host;
-    // a conv in the layout [C_out][C_in][k] followed by its bias -> packed fragments + bias
-    auto conv = [&](VaeConv& l, int C_in, int C_out, int k) {
-        l.C_in = C_in; l.C_out = C_out; l.k = k;
-        l.w_off = reserve(packed_conv1d_floats(C_in, C_out, k));
-        pack_conv1d_weights(src, C_in, C_out, k, host.data() + l.w_off);
-        src += (size_t)C_in * C_out * k;
-        l.b_off = reserve(C_out);
-        memcpy(host.data() + l.b_off, src, sizeof(float) * C_out);
-        src += C_out;
-    };
-    conv(h->cond_proj, c.cond_dim, C, 1);
+    BlobBuilder bb(weights_host);
+    bb.dense(h->cond_proj, c.cond_dim, C, 1);
     h->down.resize(c.down_stages); h->up.resize(c.down_stages);
     h->dec_conv.resize(c.decoder_blocks); h->dec_res.resize(c.decoder_blocks);
-    for (auto& l : h->down) conv(l, C, C, 5);
+    for (auto& l : h->down) bb.dense(l, C, C, 5);
     // the conditioning GEMM: rows = output columns [film_cols][C]; dec block i at 2C i, coupling j at ce_off + hp j
     std::vector<float> cw((size_t)h->film_cols * C, 0.f), cb(h->film_cols, 0.f);
     const size_t per = vae::flow_coupling_floats(half, FH);
-    h->flow_off = reserve(per * c.flow_layers);
+    h->flow_off = bb.reserve(per * c.flow_layers);
     for (int j = 0; j < c.flow_layers; ++j) {
-        memcpy(cw.data() + (size_t)(h->ce_off + j * hp) * C, src, sizeof(float) * half * C); src += (size_t)half * C;
-        memcpy(cb.data() + h->ce_off + j * hp, src, sizeof(float) * half); src += half;
-        memcpy(host.data() + h->flow_off + j * per, src, sizeof(float) * per); src += per;
+        bb.take(cw.data() + (size_t)(h->ce_off + j * hp) * C, (size_t)half * C);
+        bb.take(cb.data() + h->ce_off + j * hp, half);
+        bb.take(bb.host.data() + h->flow_off + j * per, per);
     }
-    h->dec_proj_off = reserve((size_t)c.latent_dim * C + C);
-    memcpy(host.data() + h->dec_proj_off, src, sizeof(float) * ((size_t)c.latent_dim * C + C)); src += (size_t)c.latent_dim * C + C;
+    h->dec_proj_off = bb.raw((size_t)c.latent_dim * C + C);
     for (int i = 0; i < c.decoder_blocks; ++i) {
-        conv(h->dec_conv[i], C, C, c.wavenet_kernel_size);
-        memcpy(cw.data() + (size_t)i * 2 * C * C, src, sizeof(float) * 2 * C * C); src += (size_t)2 * C * C;
-        memcpy(cb.data() + (size_t)i * 2 * C, src, sizeof(float) * 2 * C); src += 2 * C;
-        conv(h->dec_res[i], C, C, 1);
+        bb.dense(h->dec_conv[i], C, C, c.wavenet_kernel_size);
+        bb.take(cw.data() + (size_t)i * 2 * C * C, (size_t)2 * C * C);
+        bb.take(cb.data() + (size_t)i * 2 * C, 2 * C);
+        bb.dense(h->dec_res[i], C, C, 1);
     }
-    for (auto& l : h->up) conv(l, C, C, 5);
-    conv(h->out_proj, C, c.n_mels, 1);
-    conv(h->residual_proj, C, c.cond_dim, 1);
-    {
-        VaeConv& l = h->cond_gemm;
-        l.C_in = C; l.C_out = h->film_cols; l.k = 1;
-        l.w_off = reserve(packed_conv1d_floats(C, h->film_cols, 1));
-        if (h->film_cols) pack_conv1d_weights(cw.data(), C, h->film_cols, 1, host.data() + l.w_off);
-        l.b_off = reserve(h->film_cols);
-        if (h->film_cols) memcpy(host.data() + l.b_off, cb.data(), sizeof(float) * h->film_cols);
-    }
-    h->blob_floats = host.size();
-    hipError_t e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->blob, h->blob_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->blob, host.data(), h->blob_floats * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->blob) (void)hipFree(h->blob);
-        delete h;
-        return fail(IRIS_HIFIGAN_HIP_ERROR, "VAE decoder weight upload failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    for (auto& l : h->up) bb.dense(l, C, C, 5);
+    bb.dense(h->out_proj, C, c.n_mels, 1);
+    bb.dense(h->residual_proj, C, c.cond_dim, 1);
+    bb.dense(h->cond_gemm, cw.data(), cb.data(), C, h->film_cols, 1);
+    TRY(upload(bb.host, h.get(), "VAE decoder"));
+    *out = h.release();
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 
 int32_t iris_vae_decoder_destroy(iris_vae_decoder_handle* h) {
-    if (!h) return IRIS_HIFIGAN_OK;
-    if (h->blob) (void)hipFree(h->blob);
     delete h;
     return IRIS_HIFIGAN_OK;
 }
@@ -300,12 +256,8 @@ static int32_t vae_forward_checked(iris_vae_decoder_handle* h, const float* cond
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     if (!cond_dev || !z_prior_dev || !mel_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
     if (ragged && !lengths_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
-    const uint64_t need = (uint64_t)vae_ws(h, B, T).total * sizeof(float);
-    if (workspace_bytes < need)
-        return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu",
-                    (unsigned long long)workspace_bytes, (unsigned long long)need);
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    ForwardScope scope(*h, workspace_bytes, vae_ws(h, B, T).total);
+    TRY(scope.rc);
     return vae_forward(h, cond_dev, z_prior_dev, B, T, ragged ? lengths_dev : nullptr, mel_out_dev, residual_out_dev,
                        (float*)workspace_dev, (hipStream_t)stream_);
     IRIS_ABI_END
@@ -331,16 +283,8 @@ int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t 
     TRY(vae_check_shape(h, B, T));
     *n = 0;
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
-    // the forward's own code in a dry run: every launch is counted instead of issued (no pointer is dereferenced)
-    DryRun d{nullptr, 0, 0, 256};
-    DryRun* const prev = dry_run_slot();
-    dry_run_slot() = &d;
-    float* const fake = reinterpret_cast<float*>(uintptr_t(256));
-    const int rc = vae_forward(const_cast<iris_vae_decoder_handle*>(h), fake, fake, B, T, nullptr, fake, fake, fake, nullptr);
-    dry_run_slot() = prev;
-    TRY(rc);
-    *n = d.n;
-    return IRIS_HIFIGAN_OK;
+    return count_launches([&](float* fake) {
+        return vae_forward(const_cast<iris_vae_decoder_handle*>(h), fake, fake, B, T, nullptr, fake, fake, fake, nullptr); }, n);
     IRIS_ABI_END
 }
 

@@ -4,8 +4,7 @@
 //
 // txt_embed_kernel     x[b, p, :] = phoneme_embedding[clamp(id)] + position_embedding[p]
 // txt_gemm_kernel      channels-last implicit GEMM on v_mfma_f32_32x32x2_f32 over rows [B * P, C_in] with the fragment-ordered
-//                      weights of conv_mfma_f32.h and the MFMA loop of vae_decoder.h (restated below: that header defines a
-//                      plain __global__ function, so a second translation unit cannot include it).  C_in is staged in slices of at most 256
+//                      weights of packed_conv_f32.h and the MFMA loop of gemm_tile_f32.h.  C_in is staged in slices of at most 256
 //                      channels (the second FFN layer has C_in = 1024: the whole 32 x 1028-float window would leave one block
 //                      per CU).  Epilogue: bias, then optionally ReLU, a residual row and LayerNorm (epsilon, gamma, beta,
 //                      biased variance, mean first and the squared deviations second).  A LayerNorm launch holds every C_out
@@ -26,7 +25,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "conv_mfma_f32.h"
+#include "device_info.h"
+#include "gemm_tile_f32.h"
 
 namespace iris {
 namespace txt {
@@ -85,36 +85,7 @@ struct GemmLaunch {
 
 inline int gemm_slice(int C_in) { const int Cp = (C_in + 7) & ~7; return Cp < kSlice ? Cp : kSlice; }
 inline size_t gemm_lds_bytes(int C_in, int ks) {
-    return ((size_t)(kRows + ks - 1) * (gemm_slice(C_in) + 4) + 2 * 64 * kMaxWaves) * sizeof(float);
-}
-
-// acc += A (32 rows x K, LDS) * W (K x 32, fragment order): vae::mma_loop (vae_decoder.h), statement for statement.  One group =
-// 8 input channels of one tap = 4 MFMAs; the weight fragments run four groups ahead in registers, the LDS fragment one.
-__device__ __forceinline__ void mma_loop(f32x16& acc, const float* abase, int tapstep, const f32x4* __restrict__ wlane,
-                                         size_t wstep, int Gp, int ks, int gpc) {
-    const int NG = ks * gpc;
-    auto a_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return abase + kk * tapstep + 8 * g; };
-    auto b_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return wlane + ((size_t)kk * Gp + g) * wstep; };
-    constexpr int D = 4;
-    f32x4 bw[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) bw[d] = *b_ptr(d < NG ? d : NG - 1);
-    f32x4 av = *reinterpret_cast<const f32x4*>(a_ptr(0));
-    for (int n0 = 0; n0 < NG; n0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const int n = n0 + d;
-            if (n < NG) {                                           // wave-uniform
-                const f32x4 a_cur = av, b_cur = bw[d];
-                av = *reinterpret_cast<const f32x4*>(a_ptr(n + 1 < NG ? n + 1 : n));
-                bw[d] = *b_ptr(n + D < NG ? n + D : NG - 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b_cur[e], a_cur[e], acc, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
+    return ((size_t)(kRows + ks - 1) * lds_row_floats(gemm_slice(C_in)) + 2 * 64 * kMaxWaves) * sizeof(float);
 }
 
 __global__ void __launch_bounds__(64 * kMaxWaves) txt_gemm_kernel(const GemmLaunch a) {

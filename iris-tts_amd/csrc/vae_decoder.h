@@ -4,7 +4,7 @@
 // Two kernels carry the whole stage.
 //
 // vae_gemm_kernel: channels-last implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 with the fragment-ordered weights of
-// conv_mfma_f32.h (pack_conv1d_weights).  What it adds to that kernel's formulation:
+// packed_conv_f32.h (pack_conv1d_weights) and the MFMA loop of gemm_tile_f32.h.  What it adds to conv_mfma_f32.h's formulation:
 //   * the input row of output row i, tap kappa is  stride * i - pad_left + kappa * dil  (the stride-2 'same' convs of
 //     TemporalDownsample, vae.py:80-105), optionally over the nearest-neighbour x2 repeat of the input, which is folded
 //     into the LDS staging (x_up[r] = x[r >> 1], TemporalUpsample vae.py:134-147): the repeated tensor is never written;
@@ -35,7 +35,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "conv_mfma_f32.h"
+#include "device_info.h"
+#include "gemm_tile_f32.h"
 
 namespace iris {
 namespace vae {
@@ -97,40 +98,10 @@ constexpr int kGemmRows = 32;        // output rows of a block
 constexpr int kGemmMaxWaves = 8;     // C_out tiles of a block
 
 inline int gemm_window_rows(int ks, int dil, int stride) { return (kGemmRows - 1) * stride + (ks - 1) * dil + 1; }
-inline int gemm_row_floats(int C) { return ((C + 7) & ~7) + 4; }      // 4 * odd: conflict-free 16-byte rows
 inline size_t gemm_lds_bytes(int C_in, int C_out, int ks, int dil, int stride, bool fused) {
-    size_t f = (size_t)gemm_window_rows(ks, dil, stride) * gemm_row_floats(C_in);
-    if (fused) f += (size_t)kGemmRows * gemm_row_floats(C_out);
+    size_t f = (size_t)gemm_window_rows(ks, dil, stride) * lds_row_floats(C_in);
+    if (fused) f += (size_t)kGemmRows * lds_row_floats(C_out);
     return f * sizeof(float);
-}
-
-// acc += A (32 rows x K, LDS) * W (K x 32, fragment order).  One group = 8 input channels of one tap = 4 MFMAs; the weight
-// fragments run four groups ahead in registers, the LDS fragment one group ahead.
-__device__ __forceinline__ void mma_loop(f32x16& acc, const float* abase, int tapstep, const f32x4* __restrict__ wlane,
-                                         size_t wstep, int Gp, int ks, int gpc) {
-    const int NG = ks * gpc;
-    auto a_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return abase + kk * tapstep + 8 * g; };
-    auto b_ptr = [&](int n) { const int kk = n / gpc, g = n - kk * gpc; return wlane + ((size_t)kk * Gp + g) * wstep; };
-    constexpr int D = 4;
-    f32x4 bw[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) bw[d] = *b_ptr(d < NG ? d : NG - 1);
-    f32x4 av = *reinterpret_cast<const f32x4*>(a_ptr(0));
-    for (int n0 = 0; n0 < NG; n0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const int n = n0 + d;
-            if (n < NG) {                                           // wave-uniform
-                const f32x4 a_cur = av, b_cur = bw[d];
-                av = *reinterpret_cast<const f32x4*>(a_ptr(n + 1 < NG ? n + 1 : n));
-                bw[d] = *b_ptr(n + D < NG ? n + D : NG - 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b_cur[e], a_cur[e], acc, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
 }
 
 template <bool FUSED, bool RAGGED>

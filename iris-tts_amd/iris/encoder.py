@@ -46,24 +46,16 @@ tensor are not read back -- the kernel clamps them into the table.
 from __future__ import annotations
 
 import ctypes
-from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
 from ._engine import require_gpu
+from ._native_model import _NativeModel, _ptr, _stream
 
 DEFAULT_MAX_FRAMES = 65536          # frames of one utterance batch item that frame_conditioning accepts by default
-
-
-def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def create_padding_mask(lengths, max_len: int) -> np.ndarray:
@@ -94,49 +86,15 @@ def _lengths_from(mask, lengths, B: int, P: int) -> Optional[np.ndarray]:
     return lengths.astype(np.int32)
 
 
-class _NativeModel:
-    """Weights in Keras layouts + a native handle built on first use (shared by the two models)."""
-
-    _prefix = ""                                        # iris_<prefix>_create, ...
-
-    def __init__(self):
-        self.weights: Dict[str, np.ndarray] = {}
-        self._handle = None
-        self._workspace = None
-        self._device = None
-
-    # -- parameters --------------------------------------------------------------------------
-    def set_weights_dict(self, weights: Dict[str, np.ndarray]) -> None:
-        """Takes every tensor of this model from ``weights``; other keys are ignored."""
-        for key, cur in self.weights.items():
-            if key not in weights:
-                raise KeyError(f"weights are missing {key}")
-            arr = np.asarray(weights[key], dtype=np.float32)
-            if arr.shape != cur.shape:
-                raise ValueError(f"{key}: shape {arr.shape} != expected {cur.shape}")
-            self.weights[key] = np.ascontiguousarray(arr)
-        self._drop()
-
-    def save_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError("Keras .h5/.keras files need h5py, which this build does not use; save to .npz")
-        np.savez(str(path), **self.weights)
-
-    def load_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError(f"{Path(path).name}: reading Keras weight files needs h5py, which is not available")
-        with np.load(str(path), allow_pickle=False) as data:
-            self.set_weights_dict({k: data[k] for k in data.files})
-
-    def blob_size(self) -> int:
-        return sum(int(v.size) for v in self.weights.values())
+class _TextModel(_NativeModel):
+    """The two models of the text stage: their host-only queries and their tap take the config, not the handle."""
 
     # -- host-only queries -------------------------------------------------------------------
     def _query(self, what: str, B: int, P: int, ctype):
         lib = _native.load()
         out = ctype()
         cfg = self.native_config()
-        name = f"iris_{self._prefix}_{what}"
+        name = f"iris_{self._abi_name}_{what}"
         _native.check(name, getattr(lib, name)(ctypes.byref(cfg), B, P, ctypes.byref(out)))
         return int(out.value)
 
@@ -147,39 +105,6 @@ class _NativeModel:
     def workspace_bytes(self, B: int, P: int) -> int:
         return self._query("workspace_bytes", B, P, ctypes.c_uint64)
 
-    # -- execution ---------------------------------------------------------------------------
-    def _drop(self) -> None:
-        if self._handle is not None:
-            getattr(_native.load(), f"iris_{self._prefix}_destroy")(self._handle)
-        self._handle = None
-        self._workspace = None
-
-    def __del__(self):
-        try:
-            self._drop()
-        except Exception:
-            pass
-
-    def _ensure(self):
-        lib = _native.load()
-        if self._handle is None:
-            self._device = require_gpu()
-            blob = self.blob()
-            cfg = self.native_config()
-            h = ctypes.c_void_p()
-            name = f"iris_{self._prefix}_create"
-            with torch.cuda.device(self._device):
-                _native.check(name, getattr(lib, name)(ctypes.byref(cfg), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                       ctypes.c_uint64(blob.size), ctypes.byref(h)))
-            self._handle = h
-        return lib
-
-    def _ws(self, B: int, P: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, P)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        return self._workspace
-
     def _lengths_dev(self, lengths: Optional[np.ndarray]) -> Optional[torch.Tensor]:
         return None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(self._device)
 
@@ -187,14 +112,14 @@ class _NativeModel:
         lib = self._ensure()
         off, n = ctypes.c_uint64(), ctypes.c_uint64()
         cfg = self.native_config()
-        name = f"iris_{self._prefix}_tap"
+        name = f"iris_{self._abi_name}_tap"
         _native.check(name, getattr(lib, name)(ctypes.byref(cfg), B, P, ctypes.byref(off), ctypes.byref(n)))
         raw = self._workspace[off.value:off.value + 4 * n.value].clone()
         return raw.view(torch.float32).view(B, P, channels)
 
 
-class PhonemeEncoder(_NativeModel):
-    _prefix = "phoneme_encoder"
+class PhonemeEncoder(_TextModel):
+    _abi_name = "phoneme_encoder"
 
     def __init__(self, vocab_size: int, embed_dim: int = 256, num_blocks: int = 4, num_heads: int = 4,
                  ffn_dim: Optional[int] = None, max_length: int = 1000, dropout: float = 0.1, name: Optional[str] = None,
@@ -318,11 +243,11 @@ class PhonemeEncoder(_NativeModel):
         return self._read_tap(B, P, self.embed_dim)
 
 
-class DurationPredictor(_NativeModel):
+class DurationPredictor(_TextModel):
     """``in_dim``: channels of the encoder output (Keras builds the first conv lazily; ``hidden_dim`` when omitted, as in the
     reference's scripts).  ``max_frames_per_phoneme``: the upper clip of ``predict_durations`` (1e6 in the reference)."""
 
-    _prefix = "duration_predictor"
+    _abi_name = "duration_predictor"
 
     def __init__(self, hidden_dim: int = 256, num_layers: int = 2, kernel_size: int = 3, dropout: float = 0.1,
                  in_dim: Optional[int] = None, max_frames_per_phoneme: int = 1_000_000, name: Optional[str] = None,

@@ -19,14 +19,14 @@ the reference ships no vectors for it: the device path is checked against ``orac
 from __future__ import annotations
 
 import ctypes
-from pathlib import Path
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _native
-from ._engine import _check_lengths, require_gpu
+from ._engine import _check_lengths
+from ._native_model import _NativeModel, _ptr, _stream
 
 BN_EPSILON = 1e-3  # keras.layers.BatchNormalization default
 
@@ -41,14 +41,16 @@ def fold_batchnorm(kernel: np.ndarray, bias: np.ndarray, gamma: np.ndarray, beta
     return np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
 
 
-class PostNet:
+class PostNet(_NativeModel):
+    _abi_name = "postnet"
+
     def __init__(self, n_mels: int, num_layers: int = 4, channels: int = 256, kernel_size: int = 5,
                  dropout: float = 0.5, name: Optional[str] = None, seed: Optional[int] = None):
         assert num_layers >= 2, "PostNet needs at least 2 layers"
         self.n_mels, self.num_layers, self.channels = n_mels, num_layers, channels
         self.kernel_size, self.dropout_rate, self.name = kernel_size, dropout, name or "post_net"
+        super().__init__()
         rng = np.random.default_rng(seed)
-        self.weights: Dict[str, np.ndarray] = {}
         for i in range(num_layers):
             c_in = n_mels if i == 0 else channels
             c_out = n_mels if i == num_layers - 1 else channels
@@ -60,9 +62,6 @@ class PostNet:
             self.weights[f"{p}.beta"] = np.zeros(c_out, np.float32)
             self.weights[f"{p}.moving_mean"] = np.zeros(c_out, np.float32)
             self.weights[f"{p}.moving_variance"] = np.ones(c_out, np.float32)
-        self._handle = None
-        self._workspace = None
-        self._device = None
 
     def _prefix(self, i: int) -> str:
         return "conv_out" if i == self.num_layers - 1 else f"convs.{i}"
@@ -70,28 +69,6 @@ class PostNet:
     def get_config(self) -> dict:
         return {"n_mels": self.n_mels, "num_layers": self.num_layers, "channels": self.channels,
                 "kernel_size": self.kernel_size, "dropout": self.dropout_rate}
-
-    # -- parameters --------------------------------------------------------------------------
-    def set_weights_dict(self, weights: Dict[str, np.ndarray]) -> None:
-        for key, cur in self.weights.items():
-            if key not in weights:
-                raise KeyError(f"weights are missing {key}")
-            arr = np.asarray(weights[key], dtype=np.float32)
-            if arr.shape != cur.shape:
-                raise ValueError(f"{key}: shape {arr.shape} != expected {cur.shape}")
-            self.weights[key] = np.ascontiguousarray(arr)
-        self._drop()
-
-    def save_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError("Keras .h5/.keras files need h5py, which this build does not use; save to .npz")
-        np.savez(str(path), **self.weights)
-
-    def load_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError(f"{Path(path).name}: reading Keras weight files needs h5py, which is not available")
-        with np.load(str(path), allow_pickle=False) as data:
-            self.set_weights_dict({k: data[k] for k in data.files})
 
     def folded_blob(self) -> np.ndarray:
         parts = []
@@ -103,30 +80,11 @@ class PostNet:
         return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
 
     # -- execution ---------------------------------------------------------------------------
-    def _drop(self) -> None:
-        if self._handle is not None:
-            _native.load().iris_postnet_destroy(self._handle)
-        self._handle = None
-        self._workspace = None
+    def _upload_blob(self) -> np.ndarray:
+        return self.folded_blob()
 
-    def __del__(self):
-        try:
-            self._drop()
-        except Exception:
-            pass
-
-    def _ensure(self):
-        if self._handle is None:
-            lib = _native.load()
-            self._device = require_gpu()
-            blob = self.folded_blob()
-            h = ctypes.c_void_p()
-            with torch.cuda.device(self._device):
-                _native.check("iris_postnet_create", lib.iris_postnet_create(
-                    self.n_mels, self.num_layers, self.channels, self.kernel_size,
-                    blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.c_uint64(blob.size), ctypes.byref(h)))
-            self._handle = h
-        return _native.load()
+    def _create(self, lib, weights, n_weights, handle_ref) -> int:
+        return lib.iris_postnet_create(self.n_mels, self.num_layers, self.channels, self.kernel_size, weights, n_weights, handle_ref)
 
     @property
     def receptive_field_frames(self) -> int:
@@ -150,22 +108,16 @@ class PostNet:
         out = torch.empty_like(mel)
         if B == 0 or T == 0:
             return out
-        n = ctypes.c_uint64()
-        _native.check("iris_postnet_workspace_bytes", lib.iris_postnet_workspace_bytes(self._handle, B, T, ctypes.byref(n)))
-        if self._workspace is None or self._workspace.numel() < n.value:
-            self._workspace = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=self._device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        ws = self._ws(B, T)
         if lengths_host is not None:
             # (a stream-ordered allocation: the caching allocator hands the block out again only behind this stream's kernels)
             lengths_dev = torch.from_numpy(lengths_host).to(self._device)
             _native.check("iris_postnet_forward_ragged", lib.iris_postnet_forward_ragged(
-                self._handle, ctypes.c_void_p(mel.data_ptr()), B, T, ctypes.c_void_p(lengths_dev.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self._workspace.data_ptr()),
-                ctypes.c_uint64(self._workspace.numel()), stream))
+                self._handle, _ptr(mel), B, T, _ptr(lengths_dev), _ptr(out), _ptr(ws), ctypes.c_uint64(ws.numel()),
+                _stream(self._device)))
             return out
         _native.check("iris_postnet_forward", lib.iris_postnet_forward(
-            self._handle, ctypes.c_void_p(mel.data_ptr()), B, T, ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream))
+            self._handle, _ptr(mel), B, T, _ptr(out), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device)))
         return out
 
     def __call__(self, mels_bt_f, training: bool = False) -> np.ndarray:

@@ -40,17 +40,18 @@ Parameters are kept in the Keras layouts under attribute-path names (``down_cond
 from __future__ import annotations
 
 import ctypes
-from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
-from ._engine import require_gpu
+from ._native_model import _NativeModel, _ptr, _stream
 
 
-class TextConditionedVAE:
+class TextConditionedVAE(_NativeModel):
+    _abi_name = "vae_decoder"
+
     #: ``generate`` / ``generate_device`` take ``lengths=`` (a ragged batch in one forward); ``MelToWavePipeline`` checks this
     takes_lengths = True
 
@@ -65,8 +66,8 @@ class TextConditionedVAE:
         self.wavenet_kernel_size, self.down_stages = wavenet_kernel_size, down_stages
         self.flow_layers, self.flow_hidden = flow_layers, flow_hidden
         self.dropout_rate, self.name = dropout, name or "text_conditioned_vae"
+        super().__init__()
         rng = np.random.default_rng(seed)
-        self.weights: Dict[str, np.ndarray] = {}
 
         def conv(prefix, k, c_in, c_out, zero=False):
             limit = np.sqrt(6.0 / ((c_in + c_out) * k))                          # glorot_uniform
@@ -99,9 +100,6 @@ class TextConditionedVAE:
             conv(f"upsample.refine.{s}", 5, C, C)
         conv("out_proj", 1, C, n_mels)
         dense("residual_proj", C, cond_dim)
-        self._handle = None
-        self._workspace = None
-        self._device = None
 
     def get_config(self) -> dict:
         return {"n_mels": self.n_mels, "cond_dim": self.cond_dim, "model_channels": self.model_channels,
@@ -114,36 +112,10 @@ class TextConditionedVAE:
     def downsample_factor(self) -> int:
         return 2 ** self.down_stages
 
-    # -- parameters --------------------------------------------------------------------------
-    def set_weights_dict(self, weights: Dict[str, np.ndarray]) -> None:
-        """Takes every decoder-side tensor from ``weights``; other keys (the encoder half of a full checkpoint) are ignored."""
-        for key, cur in self.weights.items():
-            if key not in weights:
-                raise KeyError(f"weights are missing {key}")
-            arr = np.asarray(weights[key], dtype=np.float32)
-            if arr.shape != cur.shape:
-                raise ValueError(f"{key}: shape {arr.shape} != expected {cur.shape}")
-            self.weights[key] = np.ascontiguousarray(arr)
-        self._drop()
-
-    def save_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError("Keras .h5/.keras files need h5py, which this build does not use; save to .npz")
-        np.savez(str(path), **self.weights)
-
-    def load_weights(self, path: str) -> None:
-        if Path(path).suffix in (".h5", ".keras"):
-            raise NotImplementedError(f"{Path(path).name}: reading Keras weight files needs h5py, which is not available")
-        with np.load(str(path), allow_pickle=False) as data:
-            self.set_weights_dict({k: data[k] for k in data.files})
-
+    # -- parameters (set_weights_dict ignores the encoder half of a full checkpoint) ----------
     def native_config(self) -> "_native.VaeDecoderConfig":
         return _native.VaeDecoderConfig(self.n_mels, self.cond_dim, self.model_channels, self.latent_dim, self.decoder_blocks,
                                         self.wavenet_kernel_size, self.down_stages, self.flow_layers, self.flow_hidden)
-
-    def blob_size(self) -> int:
-        """Values in ``blob()`` (``iris_vae_decoder_weight_count`` computes the same on the C side)."""
-        return sum(int(v.size) for v in self.weights.values())
 
     def blob(self) -> np.ndarray:
         """The weights in the order and layouts ``iris_vae_decoder_create`` reads (include/iris_hifigan.h): convolutions and
@@ -177,32 +149,6 @@ class TextConditionedVAE:
         return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
 
     # -- execution ---------------------------------------------------------------------------
-    def _drop(self) -> None:
-        if self._handle is not None:
-            _native.load().iris_vae_decoder_destroy(self._handle)
-        self._handle = None
-        self._workspace = None
-
-    def __del__(self):
-        try:
-            self._drop()
-        except Exception:
-            pass
-
-    def _ensure(self):
-        if self._handle is None:
-            lib = _native.load()
-            self._device = require_gpu()
-            blob = self.blob()
-            cfg = self.native_config()
-            h = ctypes.c_void_p()
-            with torch.cuda.device(self._device):
-                _native.check("iris_vae_decoder_create", lib.iris_vae_decoder_create(
-                    ctypes.byref(cfg), blob.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.c_uint64(blob.size),
-                    ctypes.byref(h)))
-            self._handle = h
-        return _native.load()
-
     def _check_cond(self, shape) -> Tuple[int, int]:
         if len(shape) != 3 or shape[2] != self.cond_dim:
             raise ValueError(f"expected frame_text_cond [B, T, {self.cond_dim}], got {tuple(shape)}")
@@ -269,23 +215,16 @@ class TextConditionedVAE:
         residual = torch.empty((B, T, self.cond_dim), dtype=torch.float32, device=self._device) if want_residual else None
         if B == 0 or T == 0:
             return mel, residual
-        n = ctypes.c_uint64()
-        _native.check("iris_vae_decoder_workspace_bytes", lib.iris_vae_decoder_workspace_bytes(self._handle, B, T, ctypes.byref(n)))
-        if self._workspace is None or self._workspace.numel() < n.value:
-            self._workspace = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=self._device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
-        out = (ctypes.c_void_p(mel.data_ptr()), ctypes.c_void_p(residual.data_ptr() if want_residual else None),
-               ctypes.c_void_p(self._workspace.data_ptr()), ctypes.c_uint64(self._workspace.numel()), stream)
+        ws = self._ws(B, T)
+        out = (_ptr(mel), _ptr(residual), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device))
         if lengths is None:
-            _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(
-                self._handle, ctypes.c_void_p(cond.data_ptr()), ctypes.c_void_p(z_prior.data_ptr()), B, T, *out))
+            _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(self._handle, _ptr(cond), _ptr(z_prior), B, T, *out))
             return mel, residual
         if not isinstance(lengths, torch.Tensor):
             lengths = torch.from_numpy(lengths)
         lengths = lengths.to(self._device).contiguous()
         _native.check("iris_vae_decoder_forward_ragged", lib.iris_vae_decoder_forward_ragged(
-            self._handle, ctypes.c_void_p(cond.data_ptr()), ctypes.c_void_p(z_prior.data_ptr()), B, T,
-            ctypes.c_void_p(lengths.data_ptr()), *out))
+            self._handle, _ptr(cond), _ptr(z_prior), B, T, _ptr(lengths), *out))
         return mel, residual
 
     def generate(self, frame_text_cond, z_prior=None, generator: Optional[torch.Generator] = None, lengths=None):

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Register / spill / scratch table of single kernel instantiations, in seconds (no GPU): the device pass of a tiny translation
 # unit that includes the kernel headers with -DIRIS_KERNELS_ONLY (host launch code hidden) and explicitly instantiates what is
-# asked for.  usage: tools/kernel_probe.sh 'mrf_conv_mfma_f32_kernel<1, 4, 4, 64, 2, 3, 7, 11, false, 0, 2, true>(const ConvLaunch)' \
-#                                          'convt_mfma_f32_kernel<2, 2, 1, 4, 2, 3>(const ConvtLaunch)' ... [-- extra hipcc flags]
+# asked for.  usage: tools/kernel_probe.sh 'mrf_conv_mfma_f32_kernel<false, 1, 4, 4, 64, 2, 3, 7, 11, false, 0, 2, true>(const ConvLaunch)' \
+#                                          'convt_mfma_f32_kernel<false, 2, 2, 1, 4, 2, 3>(const ConvtLaunch)' ... [-- extra hipcc flags]
 set -e
 REPO=$(cd "$(dirname "$0")/.." && pwd); TMP=$(mktemp -d)
 { echo '#include <hip/hip_runtime.h>'; echo '#include "generator_internal.h"'; echo '#include "conv_mfma_f32.h"'
