@@ -491,6 +491,13 @@ int32_t iris_vae_decoder_forward(iris_vae_decoder_handle* h, const float* cond_d
 int32_t iris_vae_decoder_forward_ragged(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B,
                                         int32_t T, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
                                         void* workspace_dev, uint64_t workspace_bytes, void* stream);
+/* The decoder half of TextConditionedVAE.call(training=False) (vae.py:401-422): z_dev [B, T / 2^down_stages, latent_dim] is a
+ * posterior latent (the mean that iris_vae_encoder_forward writes) and the flow runs FORWARDS -- couplings 0 .. n - 1,
+ * y2 = x2 + t -- where iris_vae_decoder_forward runs it in reverse.  Everything else is iris_vae_decoder_forward: the same
+ * plan, launches (iris_vae_decoder_launch_count), workspace, outputs, checks and errors.  Dense batches only. */
+int32_t iris_vae_decoder_forward_posterior(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_dev, int32_t B, int32_t T,
+                                           float* mel_out_dev, float* residual_out_dev, void* workspace_dev,
+                                           uint64_t workspace_bytes, void* stream);
 /* Host only: kernel launches of one forward that asks for the residual (one fewer without it):
  * 3 + 2 * down_stages + decoder_blocks + 2. */
 int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n);
@@ -501,6 +508,46 @@ int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t 
 #define IRIS_VAE_TAP_DEC_IN 1     /* latent_dec_proj(flow(z_prior, reverse)) */
 #define IRIS_VAE_TAP_DEC_OUT 2    /* after the last decoder block */
 int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
+                             uint64_t* floats);
+
+/* ---- VAE posterior encoder (csrc/iris_vae_encoder.hip over csrc/vae_decoder.h) ------------------------------------
+ * The encoder half of TextConditionedVAE.call(training=False) (src/iris/vae.py:381-398): a mel [B, n_mels, T] (channels-first,
+ * as the PostNet and the vocoder hold it; it is never transposed in memory) and its frame conditioning [B, T, cond_dim] in,
+ * the posterior statistics mean and logvar, [B, T / 2^down_stages, latent_dim] each, out.  z = mean at inference, so
+ * iris_vae_decoder_forward_posterior(cond, mean) completes call(): reconstruction and residual.  fp32, inference only.
+ * weights_host, in this order, every tensor followed by its bias (Dense and Conv1D kernels transposed to [C_out][C_in][k]):
+ *   in_proj [C][n_mels][1];
+ *   per encoder block i: conv (k = wavenet_kernel_size, dilation 2^(i % 4)); film.proj [2C][cond_dim]; res_proj;
+ *   downsample.blocks[s] (k = 5) for each stage -- the tensors the decoder's blob holds too: the reference has one set;
+ *   latent_mean_proj [latent_dim][C]; latent_logvar_proj [latent_dim][C].
+ * num_wavenet_blocks + down_stages + 3 launches (one fewer with no block: there is no FiLM GEMM then).
+ * Configurations the kernels cannot take -- n_mels, cond_dim, model_channels or latent_dim not a multiple of 4,
+ * model_channels > 256, an even wavenet_kernel_size, a tile beyond the 160 KB LDS -- return IRIS_HIFIGAN_UNSUPPORTED; a wrong
+ * blob size and a T that is not a multiple of 2^down_stages return IRIS_HIFIGAN_INVALID_ARGUMENT; a short workspace returns
+ * IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches. */
+typedef struct iris_vae_encoder_config {
+    int32_t n_mels, cond_dim, model_channels, latent_dim, num_wavenet_blocks, wavenet_kernel_size, down_stages;
+} iris_vae_encoder_config;
+typedef struct iris_vae_encoder_handle iris_vae_encoder_handle;
+
+/* Host only. */
+int32_t iris_vae_encoder_weight_count(const iris_vae_encoder_config* cfg, uint64_t* count);
+int32_t iris_vae_encoder_create(const iris_vae_encoder_config* cfg, const float* weights_host, uint64_t n_weights,
+                                iris_vae_encoder_handle** out);
+int32_t iris_vae_encoder_destroy(iris_vae_encoder_handle* h);
+int32_t iris_vae_encoder_workspace_bytes(const iris_vae_encoder_handle* h, int32_t B, int32_t T, uint64_t* bytes);
+/* Asynchronous on `stream`, allocates nothing.  mel_dev and cond_dev are only read. */
+int32_t iris_vae_encoder_forward(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
+                                 float* mean_out_dev, float* logvar_out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                 void* stream);
+/* Host only: kernel launches of one forward (a dry run of the forward's own code). */
+int32_t iris_vae_encoder_launch_count(const iris_vae_encoder_handle* h, int32_t B, int32_t T, int32_t* n);
+/* Host only, for tests: where a forward of (B, T) leaves an intermediate in its workspace (valid until the next forward on
+ * that workspace): [B, T, model_channels], or [B, T / 2^down_stages, model_channels] for LAT_H. */
+#define IRIS_VAE_ENC_TAP_H_IN 0    /* in_proj(mel^T) */
+#define IRIS_VAE_ENC_TAP_H_OUT 1   /* after the last encoder block */
+#define IRIS_VAE_ENC_TAP_LAT_H 2   /* downsample(h) */
+int32_t iris_vae_encoder_tap(const iris_vae_encoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
                              uint64_t* floats);
 
 /* ---- Phoneme encoder, duration head and length regulator in front of the VAE decoder (csrc/text_encoder.h) ----

@@ -92,8 +92,9 @@ float* vae_dec_out(float* ws, const VaeWs& w, int i) { return ws + ((i & 1) ? w.
 // Queues the launches of one forward (or, in a dry run, counts them).  `lengths` (device, or nullptr for the dense forward)
 // selects the ragged kernels: the same launches over the same grids and buffers, each bounded by the items' own rows at
 // its level -- sh_in / sh_out count the halvings of the launch's input and output below the full rate.
+// `posterior`: z is a posterior latent and the flow runs forwards (TextConditionedVAE.call, vae.py:401); dense only.
 int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, int B, int T, const int32_t* lengths, float* mel,
-                float* residual, float* ws, hipStream_t stream) {
+                float* residual, float* ws, hipStream_t stream, bool posterior = false) {
     const iris_vae_decoder_config& c = h->cfg;
     const int C = c.model_channels, S = c.down_stages, Tq = T >> S;
     const VaeWs w = vae_ws(h, B, T);
@@ -123,13 +124,13 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
         vae::GemmLaunch a = gemm(ws + w.latcond, h->cond_gemm, ws + w.film, Tq, Tq, S, S);
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
-    {   // z = flow(z_prior, reverse); d = latent_dec_proj(z)                                vae.py:466-468
+    {   // z = flow(z_prior, reverse) -- or flow(z, forward) -- ; d = latent_dec_proj(z)     vae.py:466-468, 401-404
         vae::FlowLaunch f; memset(&f, 0, sizeof(f));
         f.z = z; f.cond = ws + w.film; f.w = blob + h->flow_off; f.wdec = blob + h->dec_proj_off; f.y = ws + w.d0;
         f.Tq = Tq; f.latent = c.latent_dim; f.FH = c.flow_hidden; f.n_flow = c.flow_layers; f.C = C;
         f.ld = h->film_cols; f.ce_off = h->ce_off; f.ce_stride = h->ce_stride;
         f.lengths = lengths; f.len_T = T; f.len_shift = S;
-        HIP_TRY(vae::launch_flow(f, B, stream));
+        HIP_TRY(vae::launch_flow(f, B, stream, posterior));
     }
     const float* d = ws + w.d0;
     for (int i = 0; i < c.decoder_blocks; ++i) {                                            // vae.py:57-67, 469-470
@@ -250,7 +251,7 @@ int32_t iris_vae_decoder_tap(const iris_vae_decoder_handle* h, int32_t B, int32_
 // The dense and the ragged entry point: the same checks in the same order, then the same plan.
 static int32_t vae_forward_checked(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_prior_dev, int32_t B, int32_t T,
                                    bool ragged, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
-                                   void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
+                                   void* workspace_dev, uint64_t workspace_bytes, void* stream_, bool posterior = false) {
     IRIS_ABI_BEGIN
     TRY(vae_check_shape(h, B, T));
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
@@ -259,7 +260,7 @@ static int32_t vae_forward_checked(iris_vae_decoder_handle* h, const float* cond
     ForwardScope scope(*h, workspace_bytes, vae_ws(h, B, T).total);
     TRY(scope.rc);
     return vae_forward(h, cond_dev, z_prior_dev, B, T, ragged ? lengths_dev : nullptr, mel_out_dev, residual_out_dev,
-                       (float*)workspace_dev, (hipStream_t)stream_);
+                       (float*)workspace_dev, (hipStream_t)stream_, posterior);
     IRIS_ABI_END
 }
 
@@ -275,6 +276,13 @@ int32_t iris_vae_decoder_forward_ragged(iris_vae_decoder_handle* h, const float*
                                         void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
     return vae_forward_checked(h, cond_dev, z_prior_dev, B, T, true, lengths_dev, mel_out_dev, residual_out_dev, workspace_dev,
                                workspace_bytes, stream_);
+}
+
+int32_t iris_vae_decoder_forward_posterior(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_dev, int32_t B, int32_t T,
+                                           float* mel_out_dev, float* residual_out_dev, void* workspace_dev,
+                                           uint64_t workspace_bytes, void* stream_) {
+    return vae_forward_checked(h, cond_dev, z_dev, B, T, false, nullptr, mel_out_dev, residual_out_dev, workspace_dev,
+                               workspace_bytes, stream_, true);
 }
 
 int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n) {

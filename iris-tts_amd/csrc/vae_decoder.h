@@ -22,6 +22,9 @@
 // one halo row per side for the whole stack, not one per coupling.  x2 is updated in LDS in the reference's order
 // (last coupling first); z never goes to HBM.
 //
+// The FORWARD instantiation runs the couplings in order with x2 + t instead (TextConditionedVAE.call, vae.py:401): x1 still
+// never changes, so the same halo argument holds.  iris_vae_decoder_forward_posterior launches it.
+//
 // Rows outside an item read 0 and are never stored; every loop bound is a kernel argument.
 //
 // Ragged form (RAGGED instantiations, iris_vae_decoder_forward_ragged): a device array lengths[B] gives each item's frames
@@ -68,7 +71,17 @@ struct GemmLaunch {
     int len_T, len_shift;     // the padded frame count T and down_stages
     int sh_in, sh_out;        // item rows of x: item_frames >> sh_in (before `up`); of y: item_frames >> sh_out
     int zero_tail;            // 1: rows [item rows, L_out) of y are stored as 0.0f (out_proj, residual_proj)
+    // kGemmSplitOut only
+    float* y2;                // columns [split, C_out) go to y2 [B, L_out, C_out - split]; columns [0, split) to y [B, L_out, split]
+    int split;                // a multiple of 4 (checked on the host)
 };
+
+// Forms of vae_gemm_kernel beside the plain one (posterior encoder, vae_encoder.h).  The plain form contains none of them.
+//   kGemmMelIn:    x is channels-first, [B, C_in, L_in] (the mel as the PostNet and the vocoder hold it): the staging loop
+//                  runs lanes along time, so a half-wave reads the block's 32 consecutive frames of one channel (128 bytes)
+//                  and writes them down an LDS column.  ks = stride = 1, no `up` (checked on the host).
+//   kGemmSplitOut: the output columns are two contiguous tensors, y and y2 (the latent heads: mean | logvar).
+constexpr int kGemmPlain = 0, kGemmMelIn = 1, kGemmSplitOut = 2;
 
 // Frames of item b: lengths[b] clamped to [0, T], then rounded down to a multiple of 2^S -- the stride-2 'same' rule (pad 1
 // left, 2 right) holds for even lengths only, and a multiple of 2^S is even at every level.
@@ -104,7 +117,7 @@ inline size_t gemm_lds_bytes(int C_in, int C_out, int ks, int dil, int stride, b
     return f * sizeof(float);
 }
 
-template <bool FUSED, bool RAGGED>
+template <bool FUSED, bool RAGGED, int FORM = kGemmPlain>
 __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const GemmLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -129,7 +142,17 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
     }
     const int Lv = a.up ? 2 * Lb_in : Lb_in;
 
-    {   // stage the window: virtual row v of the item is row v >> up of x, 0 outside [0, Lv)
+    if constexpr (FORM == kGemmMelIn) {
+        // stage the window from [B, C_in, L_in]: idx -> (channel, row) with the row fastest, 0 outside [0, Lv) and past C_in
+        const int total = R * Cp;
+        for (int idx = tid; idx < total; idx += nthr) {
+            const int ci = idx / R, r = idx - ci * R;
+            const int v = v0 + r;
+            float val = 0.f;
+            if (v >= 0 && v < Lv && ci < a.C_in) val = a.x[((size_t)b * a.C_in + ci) * a.L_in + v];
+            lds[r * S + ci] = val;
+        }
+    } else {   // stage the window: virtual row v of the item is row v >> up of x, 0 outside [0, Lv)
         const int QPR = Cp >> 2, total = R * QPR;
         for (int idx = tid; idx < total; idx += nthr) {
             const int r = idx / QPR, q = idx - r * QPR;
@@ -222,7 +245,18 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
     } else {
         __builtin_amdgcn_sched_barrier(0);
         if (ok) {
-            if (a.y_channels_first) {
+            if constexpr (FORM == kGemmSplitOut) {
+                // a group of 4 columns lies on one side of `split` (split % 4 == 0): one 16-byte store into y or y2
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int co = ct * 32 + 8 * g + 4 * hi;
+                    if (co < a.C_out) {
+                        const f32x4 v = {acc[4 * g + 0], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+                        float* dst = co < a.split ? a.y + row * a.split + co : a.y2 + row * (a.C_out - a.split) + (co - a.split);
+                        *reinterpret_cast<f32x4*>(dst) = v;
+                    }
+                }
+            } else if (a.y_channels_first) {
                 // [B, C_out, L_out]: the 32 lanes of a half-wave store 32 consecutive frames of one channel
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -276,7 +310,7 @@ inline size_t flow_lds_bytes(int latent, int FH) {
     return ((size_t)kFlowRows * latent + 2 * (size_t)(kFlowRows + 2) * half + (size_t)kFlowRows * FH) * sizeof(float);
 }
 
-template <bool RAGGED>
+template <bool RAGGED, bool FORWARD = false>
 __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int TT = kFlowRows;
@@ -298,7 +332,8 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
         const int r = idx / latent, c = idx - r * latent, t = r0 + r;
         zt[idx] = t < Tb ? a.z[((size_t)b * Tq + t) * latent + c] : 0.f;
     }
-    for (int jj = a.n_flow - 1; jj >= 0; --jj) {                      // reversed(layers_list), vae.py:237-239
+    // reverse: reversed(layers_list), vae.py:237-239; FORWARD: couplings 0 .. n - 1, vae.py:240-242
+    for (int jj = FORWARD ? 0 : a.n_flow - 1; FORWARD ? jj < a.n_flow : jj >= 0; jj += FORWARD ? 1 : -1) {
         const float* wpre = a.w + (size_t)jj * per;
         const float* bpre = wpre + 3 * half * FH;
         const float* wpost = bpre + FH;
@@ -337,7 +372,8 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
                 gam = fmaf(cv, wfilm[k * 2 * half + c], gam);
                 bet = fmaf(cv, wfilm[k * 2 * half + half + c], bet);
             }
-            zt[r * latent + half + c] -= gam * tv + bet;             // y2 = x2 - t (reverse), vae.py:203-204
+            if constexpr (FORWARD) zt[r * latent + half + c] += gam * tv + bet;   // y2 = x2 + t, vae.py:205-206
+            else zt[r * latent + half + c] -= gam * tv + bet;        // y2 = x2 - t (reverse), vae.py:203-204
         }
     }
     __syncthreads();
@@ -353,7 +389,7 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
 
 #ifndef IRIS_KERNELS_ONLY
 // Fills Gp / n_ct and launches.  FUSED launches need every C_out tile in one block (C_out <= 32 * kGemmMaxWaves).
-inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stream) {
+inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stream, int form = kGemmPlain) {
     a.Gp = packed_groups(a.C_in);
     a.n_ct = packed_cotiles(a.C_out);
     a.Gp2 = packed_groups(a.C_out);
@@ -363,6 +399,15 @@ inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stre
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     dim3 grid((unsigned)((a.L_out + kGemmRows - 1) / kGemmRows), (unsigned)((a.n_ct + nw - 1) / nw), (unsigned)B);
     dim3 block((unsigned)(64 * nw));
+    if (form != kGemmPlain) {                              // dense, unfused forms of the posterior encoder
+        if (fused || a.lengths || a.up || a.y_channels_first) return hipErrorInvalidValue;
+        if (form == kGemmMelIn) {
+            if (a.ks != 1 || a.stride != 1 || a.pad_left != 0) return hipErrorInvalidValue;
+            return launch_kernel_named("vae_gemm_kernel<mel_in>", vae_gemm_kernel<false, false, kGemmMelIn>, grid, block, lds_bytes, stream, a);
+        }
+        if (form != kGemmSplitOut || !a.y2 || a.split <= 0 || a.split >= a.C_out || (a.split & 3)) return hipErrorInvalidValue;
+        return launch_kernel_named("vae_gemm_kernel<split_out>", vae_gemm_kernel<false, false, kGemmSplitOut>, grid, block, lds_bytes, stream, a);
+    }
     if (a.lengths) {
         if (fused) return launch_kernel_named("vae_gemm_kernel_ragged<fused>", vae_gemm_kernel<true, true>, grid, block, lds_bytes, stream, a);
         return launch_kernel_named("vae_gemm_kernel_ragged", vae_gemm_kernel<false, true>, grid, block, lds_bytes, stream, a);
@@ -371,8 +416,12 @@ inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stre
     return launch_kernel_named("vae_gemm_kernel", vae_gemm_kernel<false, false>, grid, block, lds_bytes, stream, a);
 }
 
-inline hipError_t launch_flow(const FlowLaunch& a, int B, hipStream_t stream) {
+inline hipError_t launch_flow(const FlowLaunch& a, int B, hipStream_t stream, bool forward = false) {
     dim3 grid((unsigned)((a.Tq + kFlowRows - 1) / kFlowRows), (unsigned)B), block(256);
+    if (forward) {                                         // the posterior decode is dense
+        if (a.lengths) return hipErrorInvalidValue;
+        return launch_kernel_named("vae_flow_kernel<forward>", vae_flow_kernel<false, true>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
+    }
     if (a.lengths)
         return launch_kernel_named("vae_flow_kernel_ragged", vae_flow_kernel<true>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
     return launch_kernel_named("vae_flow_kernel", vae_flow_kernel<false>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);

@@ -192,8 +192,30 @@ VAE_SYMBOLS = {
     "iris_vae_decoder_workspace_bytes": (_i32, [_vp, _i32, _i32, _u64p]),
     "iris_vae_decoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_forward_ragged": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "iris_vae_decoder_forward_posterior": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_launch_count": (_i32, [_vp, _i32, _i32, _ip]),
     "iris_vae_decoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
+}
+
+
+class VaeEncoderConfig(ctypes.Structure):
+    """``iris_vae_encoder_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_mels", "cond_dim", "model_channels", "latent_dim", "num_wavenet_blocks",
+                                             "wavenet_kernel_size", "down_stages")]
+
+
+VAE_ENC_TAP_H_IN, VAE_ENC_TAP_H_OUT, VAE_ENC_TAP_LAT_H = 0, 1, 2
+
+# the VAE posterior encoder stage (iris.vae.VAEPosteriorEncoder): bound by load() like SYMBOLS
+VAE_ENCODER_SYMBOLS = {
+    "iris_vae_encoder_weight_count": (_i32, [_c.POINTER(VaeEncoderConfig), _u64p]),
+    "iris_vae_encoder_create": (_i32, [_c.POINTER(VaeEncoderConfig), _fp, _u64, _c.POINTER(_vp)]),
+    "iris_vae_encoder_destroy": (_i32, [_vp]),
+    "iris_vae_encoder_workspace_bytes": (_i32, [_vp, _i32, _i32, _u64p]),
+    "iris_vae_encoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_vae_encoder_launch_count": (_i32, [_vp, _i32, _i32, _ip]),
+    "iris_vae_encoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
 }
 
 
@@ -256,7 +278,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **TEXT_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **TEXT_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

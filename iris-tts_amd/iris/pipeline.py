@@ -28,14 +28,17 @@ class MelToWavePipeline:
     minimal halo are derived from it (V1 values when omitted; ``vocode.__self__.cfg`` is picked up when ``vocode``
     is a bound ``GeneratorEngine.forward``).  ``acoustic``: an ``iris.vae.TextConditionedVAE`` (or any callable
     ``(frame_cond, z_prior) -> (device mel [B, n_mels, T], ...)``) for ``infer_from_cond``, or None.  ``text``: a pair
-    ``(iris.encoder.PhonemeEncoder, iris.encoder.DurationPredictor)`` for ``infer_from_phonemes``, or None."""
+    ``(iris.encoder.PhonemeEncoder, iris.encoder.DurationPredictor)`` for ``infer_from_phonemes``, or None.  ``posterior``:
+    an ``iris.vae.VAEPosteriorEncoder`` (or any callable ``(mel, frame_cond) -> (device recon [B, n_mels, T], ...)``) for
+    ``resynthesize``, or None."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
-                 group_chunks: int = 1, config=None, acoustic=None, text=None):
+                 group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None):
         self.postnet = postnet
         self.acoustic = acoustic
         self.text = text
+        self.posterior = posterior
         self.device = device
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
@@ -120,6 +123,25 @@ class MelToWavePipeline:
         gen = getattr(self.acoustic, "generate_device", None)
         mel = gen(frame_cond, z_prior, want_residual=False)[0] if gen is not None else self.acoustic(frame_cond, z_prior)[0]
         return self.infer(mel, **kw)
+
+    def resynthesize(self, mel, frame_cond, **kw):
+        """Copy-synthesis: a recorded mel ``[B, n_mels, T]`` and its frame conditioning ``[B, T, cond_dim]`` -> what ``infer``
+        returns for the VAE's reconstruction of it (``iris.vae.reconstruct``: posterior encoder, forward flow, decoder), all
+        on one stream -- what the acoustic model loses, heard apart from what the text side loses.  ``**kw`` goes to
+        ``infer`` (``pcm16``, ``normalize``, ``resampler``)."""
+        if self.posterior is None:
+            raise ValueError("resynthesize needs a posterior encoder: construct the pipeline with posterior=VAEPosteriorEncoder(...)")
+        if hasattr(self.posterior, "encode_device"):
+            if self.acoustic is None:
+                raise ValueError("resynthesize needs the decoder too: construct the pipeline with acoustic=TextConditionedVAE(...)")
+            from .vae import reconstruct
+            mel = self._to_device(mel)
+            if not isinstance(frame_cond, torch.Tensor):
+                frame_cond = torch.from_numpy(np.ascontiguousarray(np.asarray(frame_cond, dtype=np.float32)))
+            recon = reconstruct(self.posterior, self.acoustic, mel, frame_cond.to(mel.device))[0]
+        else:
+            recon = self.posterior(mel, frame_cond)[0]
+        return self.infer(recon, **kw)
 
     def infer_from_phonemes(self, ids, lengths=None, durations=None, z_prior=None, **kw):
         """Phoneme ids ``[B, P]`` -> ``(what infer returns, frames_per_item)``: phoneme encoder, duration head and length

@@ -4,8 +4,18 @@ Call surface kept from the reference's ``src/iris/vae.py``: the constructor ``Te
 model_channels=192, latent_dim=16, num_wavenet_blocks=8, decoder_blocks=4, wavenet_kernel_size=5, down_stages=2,
 flow_layers=4, flow_hidden=64, dropout=0.1, name=None)`` (:263-351) and ``generate(frame_text_cond, z_prior=None) ->
 (mel [B, n_mels, T], residual [B, T, cond_dim])`` (:448-482), which ``scripts/synthesize.py:125-145`` calls right before
-the PostNet.  The encoder half (``in_proj``, ``enc_blocks``, ``latent_*_proj``, ``call()``) is training-side and is not
-built: ``__call__`` raises, and encoder-side keys in a weight file are ignored.
+the PostNet.  ``TextConditionedVAE`` holds the decoder half only: its ``__call__`` raises, and encoder-side keys in a
+weight file are ignored by it.  The encoder half (``in_proj``, ``enc_blocks``, ``latent_*_proj``) is
+``VAEPosteriorEncoder``, and ``reconstruct(encoder, vae, mels, frame_text_cond)`` is the reference's
+``call(training=False)`` (:366-422) over the two: posterior statistics, forward flow, decoded reconstruction.
+
+    h = in_proj(mels^T)                                 # the mel arrives channels-first [B, n_mels, T]           :382-385
+    for i, block in enumerate(enc_blocks):              # WaveNetResBlock, dilation 2^(i % 4), FiLM on frame_cond :388-389
+        g, b = split(block.film.proj(frame_cond)); h = h + block.res_proj(g * gelu(block.conv(h)) + b)
+    lat_h = downsample(h)                               # the weights lat_cond goes through                       :393
+    mean, logvar = latent_mean_proj(lat_h), latent_logvar_proj(lat_h);  z = mean                                 :396-398
+    z_flow = flow(z, lat_cond, reverse=False)           # couplings in order, x2 + (g * t + b)                    :401
+    then latent_dec_proj, dec_blocks, upsample, out_proj / residual_proj as in generate() below.
 
     lat_cond = downsample(down_cond_proj(frame_cond))   # 1x1 conv, then S x (Conv1D k5 stride 2 'same' + gelu)   :360-364
     z = z_prior                                         # [B, T / 2^S, latent_dim]
@@ -241,6 +251,27 @@ class TextConditionedVAE(_NativeModel):
         mel, residual = self.generate_device(torch.from_numpy(cond).to(self._device), z, True, generator, lengths)
         return mel.cpu().numpy(), residual.cpu().numpy()
 
+    def decode_posterior_device(self, cond: torch.Tensor, z: torch.Tensor, want_residual: bool = True):
+        """The decoder half of the reference's ``call(training=False)`` (vae.py:401-422): ``z [B, T / 2^S, latent_dim]`` is a
+        posterior latent (``VAEPosteriorEncoder.encode_device``'s mean) and the flow runs forwards; shapes, outputs and
+        launches are ``generate_device``'s (``iris_vae_decoder_forward_posterior``)."""
+        B, T = self._check_cond(tuple(cond.shape))
+        Tq = T // self.downsample_factor
+        if tuple(z.shape) != (B, Tq, self.latent_dim):
+            raise ValueError(f"expected z [{B}, {Tq}, {self.latent_dim}], got {tuple(z.shape)}")
+        lib = self._ensure()
+        cond = cond.to(device=self._device, dtype=torch.float32).contiguous()
+        z = z.to(device=self._device, dtype=torch.float32).contiguous()
+        mel = torch.empty((B, self.n_mels, T), dtype=torch.float32, device=self._device)
+        residual = torch.empty((B, T, self.cond_dim), dtype=torch.float32, device=self._device) if want_residual else None
+        if B == 0 or T == 0:
+            return mel, residual
+        ws = self._ws(B, T)
+        _native.check("iris_vae_decoder_forward_posterior", lib.iris_vae_decoder_forward_posterior(
+            self._handle, _ptr(cond), _ptr(z), B, T, _ptr(mel), _ptr(residual), _ptr(ws), ctypes.c_uint64(ws.numel()),
+            _stream(self._device)))
+        return mel, residual
+
     def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:
         """Test-only: the intermediate ``which`` (``_native.VAE_TAP_*``) the last ``generate_device`` of shape (B, T) left in
         the workspace, ``[B, T / 2^S, model_channels]`` (a copy)."""
@@ -255,3 +286,171 @@ class TextConditionedVAE(_NativeModel):
                                   "TextConditionedVAE.call() and training are not built")
 
     call = __call__
+
+
+class VAEPosteriorEncoder(_NativeModel):
+    """The encoder half of the reference's ``TextConditionedVAE`` (vae.py:294-325, 381-398): mel ``[B, n_mels, T]`` and frame
+    conditioning ``[B, T, cond_dim]`` -> posterior ``(mean, logvar)``, ``[B, T / 2^S, latent_dim]`` each.  Weights under the
+    reference's attribute paths: ``in_proj.*``, ``enc_block_{i}.conv.*`` / ``.film.proj.*`` / ``.res_proj.*``,
+    ``downsample.blocks.{s}.*`` (the tensors ``TextConditionedVAE`` holds too: the reference has one set),
+    ``latent_mean_proj.*``, ``latent_logvar_proj.*``.  One full-checkpoint ``.npz`` loads into both classes."""
+
+    _abi_name = "vae_encoder"
+
+    def __init__(self, n_mels: int, cond_dim: int, model_channels: int = 192, latent_dim: int = 16,
+                 num_wavenet_blocks: int = 8, wavenet_kernel_size: int = 5, down_stages: int = 2,
+                 seed: Optional[int] = None):
+        self.n_mels, self.cond_dim, self.model_channels, self.latent_dim = n_mels, cond_dim, model_channels, latent_dim
+        self.num_wavenet_blocks, self.wavenet_kernel_size, self.down_stages = num_wavenet_blocks, wavenet_kernel_size, down_stages
+        super().__init__()
+        rng = np.random.default_rng(seed)
+
+        def conv(prefix, k, c_in, c_out):
+            limit = np.sqrt(6.0 / ((c_in + c_out) * k))                          # glorot_uniform
+            self.weights[f"{prefix}.kernel"] = rng.uniform(-limit, limit, (k, c_in, c_out)).astype(np.float32)
+            self.weights[f"{prefix}.bias"] = np.zeros(c_out, np.float32)
+
+        def dense(prefix, c_in, c_out, zero=False):
+            limit = np.sqrt(6.0 / (c_in + c_out))
+            w = np.zeros((c_in, c_out)) if zero else rng.uniform(-limit, limit, (c_in, c_out))
+            self.weights[f"{prefix}.kernel"] = w.astype(np.float32)
+            self.weights[f"{prefix}.bias"] = np.zeros(c_out, np.float32)
+
+        C = model_channels
+        conv("in_proj", 1, n_mels, C)
+        for i in range(num_wavenet_blocks):
+            p = f"enc_block_{i}"
+            conv(f"{p}.conv", wavenet_kernel_size, C, C)
+            dense(f"{p}.film.proj", cond_dim, 2 * C)
+            conv(f"{p}.res_proj", 1, C, C)
+        for s in range(down_stages):
+            conv(f"downsample.blocks.{s}", 5, C, C)
+        dense("latent_mean_proj", C, latent_dim)
+        dense("latent_logvar_proj", C, latent_dim, zero=True)                    # zero-initialised, vae.py:320-325
+
+    def get_config(self) -> dict:
+        return {"n_mels": self.n_mels, "cond_dim": self.cond_dim, "model_channels": self.model_channels,
+                "latent_dim": self.latent_dim, "num_wavenet_blocks": self.num_wavenet_blocks,
+                "wavenet_kernel_size": self.wavenet_kernel_size, "down_stages": self.down_stages}
+
+    @property
+    def downsample_factor(self) -> int:
+        return 2 ** self.down_stages
+
+    def native_config(self) -> "_native.VaeEncoderConfig":
+        return _native.VaeEncoderConfig(self.n_mels, self.cond_dim, self.model_channels, self.latent_dim, self.num_wavenet_blocks,
+                                        self.wavenet_kernel_size, self.down_stages)
+
+    def blob(self) -> np.ndarray:
+        """The weights in the order ``iris_vae_encoder_create`` reads (include/iris_hifigan.h), every kernel transposed to
+        ``[C_out][C_in][k]``."""
+        w = self.weights
+        parts = []
+
+        def gemm(prefix):                        # Conv1D [k, in, out] or Dense [in, out] -> [out][in][k]
+            k = w[f"{prefix}.kernel"]
+            k = k[None] if k.ndim == 2 else k
+            parts.extend([np.ascontiguousarray(k.transpose(2, 1, 0)).ravel(), w[f"{prefix}.bias"].ravel()])
+
+        gemm("in_proj")
+        for i in range(self.num_wavenet_blocks):
+            p = f"enc_block_{i}"
+            gemm(f"{p}.conv"); gemm(f"{p}.film.proj"); gemm(f"{p}.res_proj")
+        for s in range(self.down_stages):
+            gemm(f"downsample.blocks.{s}")
+        gemm("latent_mean_proj")
+        gemm("latent_logvar_proj")
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+    def _check_inputs(self, mel_shape, cond_shape) -> Tuple[int, int]:
+        if len(mel_shape) != 3 or mel_shape[1] != self.n_mels:
+            raise ValueError(f"expected mels [B, {self.n_mels}, T], got {tuple(mel_shape)}")
+        B, T = int(mel_shape[0]), int(mel_shape[2])
+        if tuple(cond_shape) != (B, T, self.cond_dim):
+            raise ValueError(f"expected frame_text_cond [{B}, {T}, {self.cond_dim}], got {tuple(cond_shape)}")
+        if T % self.downsample_factor:
+            raise ValueError(f"T = {T} is not a multiple of 2^down_stages = {self.downsample_factor}: pad the mel and the "
+                             "conditioning first (the reference's training script does); nothing is padded silently")
+        return B, T
+
+    def launch_count(self, B: int, T: int) -> int:
+        """Kernel launches of one ``encode_device``: ``num_wavenet_blocks + down_stages + 3``."""
+        lib = self._ensure()
+        n = ctypes.c_int32()
+        _native.check("iris_vae_encoder_launch_count", lib.iris_vae_encoder_launch_count(self._handle, B, T, ctypes.byref(n)))
+        return int(n.value)
+
+    def encode_device(self, mel: torch.Tensor, cond: torch.Tensor):
+        """``mel [B, n_mels, T]`` (channels-first, read as it lies), ``cond [B, T, cond_dim]`` (fp32 device tensors) ->
+        ``(mean, logvar)``, ``[B, T / 2^S, latent_dim]`` each, asynchronous on the current stream.  Neither input is written."""
+        B, T = self._check_inputs(tuple(mel.shape), tuple(cond.shape))
+        lib = self._ensure()
+        mel = mel.to(device=self._device, dtype=torch.float32).contiguous()
+        cond = cond.to(device=self._device, dtype=torch.float32).contiguous()
+        Tq = T // self.downsample_factor
+        mean = torch.empty((B, Tq, self.latent_dim), dtype=torch.float32, device=self._device)
+        logvar = torch.empty_like(mean)
+        if B == 0 or T == 0:
+            return mean, logvar
+        ws = self._ws(B, T)
+        _native.check("iris_vae_encoder_forward", lib.iris_vae_encoder_forward(
+            self._handle, _ptr(mel), _ptr(cond), B, T, _ptr(mean), _ptr(logvar), _ptr(ws), ctypes.c_uint64(ws.numel()),
+            _stream(self._device)))
+        return mean, logvar
+
+    def encode(self, mels, frame_text_cond):
+        """numpy in -> numpy out, device tensors in -> device tensors out."""
+        if isinstance(mels, torch.Tensor):
+            return self.encode_device(mels, frame_text_cond)
+        mels = np.ascontiguousarray(np.asarray(mels, dtype=np.float32))
+        cond = np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32))
+        self._check_inputs(mels.shape, cond.shape)
+        self._ensure()
+        mean, logvar = self.encode_device(torch.from_numpy(mels).to(self._device), torch.from_numpy(cond).to(self._device))
+        return mean.cpu().numpy(), logvar.cpu().numpy()
+
+    def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:
+        """Test-only: the intermediate ``which`` (``_native.VAE_ENC_TAP_*``) the last ``encode_device`` of shape (B, T) left in
+        the workspace, ``[B, T, model_channels]`` (``LAT_H``: ``[B, T / 2^S, model_channels]``), a copy."""
+        lib = self._ensure()
+        off, n = ctypes.c_uint64(), ctypes.c_uint64()
+        _native.check("iris_vae_encoder_tap", lib.iris_vae_encoder_tap(self._handle, B, T, which, ctypes.byref(off), ctypes.byref(n)))
+        raw = self._workspace[off.value:off.value + 4 * n.value].clone()
+        return raw.view(torch.float32).view(B, -1, self.model_channels)
+
+
+_SHARED_SIZES = ("n_mels", "cond_dim", "model_channels", "latent_dim", "down_stages")
+
+
+def check_pair(encoder: VAEPosteriorEncoder, vae: TextConditionedVAE) -> None:
+    """``ValueError`` unless the two halves belong to one model: equal sizes and the same ``downsample.blocks.*`` tensors."""
+    for name in _SHARED_SIZES:
+        if getattr(encoder, name) != getattr(vae, name):
+            raise ValueError(f"the encoder and the decoder disagree on {name}: {getattr(encoder, name)} != {getattr(vae, name)}")
+    for s in range(vae.down_stages):
+        for leaf in ("kernel", "bias"):
+            key = f"downsample.blocks.{s}.{leaf}"
+            if not np.array_equal(encoder.weights[key], vae.weights[key]):
+                raise ValueError(f"the encoder and the decoder hold different {key}: the reference has one downsample stack, "
+                                 "load both halves from the same checkpoint")
+
+
+def reconstruct(encoder: VAEPosteriorEncoder, vae: TextConditionedVAE, mels, frame_text_cond):
+    """The reference's ``TextConditionedVAE.call(mels, frame_text_cond, training=False)`` (vae.py:366-422) ->
+    ``(recon [B, n_mels, T], (mean, logvar), residual [B, T, cond_dim])``: ``encode_device`` then
+    ``decode_posterior_device(cond, mean)`` on the current stream, nothing returning to the host in between.  numpy in ->
+    numpy out, device tensors in -> device tensors out."""
+    check_pair(encoder, vae)
+    on_host = not isinstance(mels, torch.Tensor)
+    if on_host:
+        mels = torch.from_numpy(np.ascontiguousarray(np.asarray(mels, dtype=np.float32)))
+        frame_text_cond = torch.from_numpy(np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32)))
+    encoder._check_inputs(tuple(mels.shape), tuple(frame_text_cond.shape))
+    if on_host:
+        encoder._ensure()
+        mels, frame_text_cond = mels.to(encoder._device), frame_text_cond.to(encoder._device)
+    mean, logvar = encoder.encode_device(mels, frame_text_cond)
+    recon, residual = vae.decode_posterior_device(frame_text_cond, mean)
+    if on_host:
+        return recon.cpu().numpy(), (mean.cpu().numpy(), logvar.cpu().numpy()), residual.cpu().numpy()
+    return recon, (mean, logvar), residual
