@@ -258,6 +258,35 @@ inline WsLayout ws_layout(const iris_hifigan_handle* h, int B, int T, int32_t dt
     return w;
 }
 
+// ---- MRF: the launches of one stage as data (plan_mrf_stage, iris_hifigan.hip; plan_mrf_stage_bf16, iris_hifigan_bf16.hip) ----
+enum WsBuf : uint8_t { WS_NONE, WS_UP, WS_Y, WS_XT };        // the stage's upsample output; y[j] / xt[j] of branch j
+enum StepKind : uint8_t {
+    STEP_PAIR,        // conv1 -> conv2 + residual of one dilation in ONE launch (mrf_pair_f32.h, mrf_pair_bf16.h)
+    STEP_PAIR_SUM,    // ... the stage's last pair on a kernel that stores only the MRF mean (mrf_pair_f32_pf.h, mrf_pair_bf16.h)
+    STEP_CONV1,       // convs1[m] of all branches
+    STEP_CONV2,       // convs2[m] + residual of all branches
+    STEP_CONV2_SUM,   // ... the stage's last step, storing only the MRF mean (fp32 storage)
+};
+enum StepMean : uint8_t {
+    MEAN_NONE,        // the step writes every branch's output to `y`
+    MEAN_IN_Y,        // it leaves mean_j(branch j) in `y` of branch 0 and no branch outputs (bf16 storage: activated and rounded)
+    MEAN_F32_IN_UP,   // bf16 storage, last stage: the fp32 mean over `up` + y[0], adjacent in the workspace (`y` is WS_UP)
+};
+struct MrfStep {
+    StepKind kind;
+    bool split;             // the conv steps on split-bf16 products (conv_mfma_f32s.h)
+    int m, half;            // MRF step 2 * m + half of the stage (a pair carries its second step's index)
+    WsBuf x, res, y;        // per branch: what the step reads, adds as the residual (conv2) and writes
+    StepMean mean;
+};
+// What a stage hands to the next layer: every branch's output in `buf` (MEAN_NONE; the consumer forms the mean), or the mean.
+struct StageOut { StepMean mean; WsBuf buf; };
+struct MrfStagePlan {
+    int n;
+    MrfStep s[2 * IRIS_HIFIGAN_MAX_DILATIONS];
+    StageOut out() const { return StageOut{s[n - 1].mean, s[n - 1].y}; }
+};
+
 // Device memory of a single-layer entry point (packed weights, a bias): freed when the call returns.
 struct DevBuf {
     void* p = nullptr;

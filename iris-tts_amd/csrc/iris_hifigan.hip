@@ -453,24 +453,7 @@ int32_t iris_hifigan_read_profile(iris_hifigan_handle* h, iris_hifigan_launch_re
 
 namespace {
 
-// ---- MRF: the launches of one stage, decided once ----
-enum WsBuf : uint8_t { WS_NONE, WS_UP, WS_Y, WS_XT };        // the stage's upsample output; y[j] / xt[j] of branch j
-enum StepKind : uint8_t {
-    STEP_PAIR,        // conv1 -> conv2 + residual of one dilation in ONE launch (mrf_pair_f32.h)
-    STEP_PAIR_SUM,    // ... the stage's last pair on the persistent kernel, which stores only the MRF mean (mrf_pair_f32_pf.h)
-    STEP_CONV1,       // convs1[m] of all branches
-    STEP_CONV2,       // convs2[m] + residual of all branches
-    STEP_CONV2_SUM,   // ... the stage's last step, storing only the MRF mean
-};
-struct MrfStep {
-    StepKind kind;
-    bool split;             // the conv steps on split-bf16 products (conv_mfma_f32s.h)
-    int m, half;            // MRF step 2 * m + half of the stage (a pair carries its second step's index)
-    WsBuf x, res, y;        // per branch: what the step reads, adds as the residual (conv2) and writes
-    bool mean_in_y0;        // the step leaves mean_j(branch j) in y[0] and no branch outputs
-};
-struct MrfStagePlan { int n; MrfStep s[2 * IRIS_HIFIGAN_MAX_DILATIONS]; };
-
+// ---- MRF: the launches of one stage, decided once (MrfStep / MrfStagePlan: generator_internal.h) ----
 struct StageCtx {           // what the MRF launches of stage i share in one pass
     const iris_hifigan_handle* h;
     int i, B, L;            // L: rows per item after the stage's upsample
@@ -536,7 +519,7 @@ MrfStagePlan plan_mrf_stage(const StageCtx& c, int32_t dtype, const ForwardStop&
     // latency modes -- and cannot sum.
     bool sums = split;
     if (!split && nk == 3) {
-        const ConvLaunch a = step_launch(c, MrfStep{STEP_CONV2, false, nd - 1, 1, WS_XT, WS_Y, WS_Y, false}, f, wb);
+        const ConvLaunch a = step_launch(c, MrfStep{STEP_CONV2, false, nd - 1, 1, WS_XT, WS_Y, WS_Y, MEAN_NONE}, f, wb);
         if (mrf_kernel_applicable(a, nk)) {
             const MrfPlan pq = mrf_plan(a, true);
             ConvLaunch b = a;
@@ -556,7 +539,7 @@ MrfStagePlan plan_mrf_stage(const StageCtx& c, int32_t dtype, const ForwardStop&
         bool all_ok = true;
         PairLaunchF32 pa;
         for (int m = 0; m < nd && all_ok; ++m) {
-            pa = stage_pair_launch(c, MrfStep{STEP_PAIR, false, m, 1, WS_UP, WS_NONE, WS_Y, false}, f, wb, &all_ok);
+            pa = stage_pair_launch(c, MrfStep{STEP_PAIR, false, m, 1, WS_UP, WS_NONE, WS_Y, MEAN_NONE}, f, wb, &all_ok);
             all_ok = all_ok && pair_f32_applicable(pa, nk);
         }
         if (all_ok) {
@@ -579,7 +562,7 @@ MrfStagePlan plan_mrf_stage(const StageCtx& c, int32_t dtype, const ForwardStop&
     MrfStagePlan pl;
     pl.n = 0;
     auto add = [&](StepKind kind, int m, int half, WsBuf x, WsBuf res, WsBuf y) {
-        pl.s[pl.n++] = MrfStep{kind, split, m, half, x, res, y, kind == STEP_PAIR_SUM || kind == STEP_CONV2_SUM};
+        pl.s[pl.n++] = MrfStep{kind, split, m, half, x, res, y, kind == STEP_PAIR_SUM || kind == STEP_CONV2_SUM ? MEAN_IN_Y : MEAN_NONE};
     };
     // never in place: the running x of a branch alternates between its y and xt buffers, arranged so that the last
     // fused pair ends in y -- or, in front of the summing pair (which writes the mean to y[0]), in xt
@@ -699,18 +682,18 @@ int forward_f32(iris_hifigan_handle* h, const void* mel_dev, int32_t B, int32_t 
                         step.x[j] = a.p[j].x; step.res[j] = a.p[j].res; step.y[j] = a.p[j].y;
                         step.layer[j] = s.half == 0 ? &st.c1[j][s.m] : &st.c2[j][s.m];
                     }
-                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, s.mean_in_y0 ? c.y[0] : nullptr, stream));
+                    TRY(f32s_launch_step(h, step, nk, B, L_out, st.C, s.mean == MEAN_IN_Y ? c.y[0] : nullptr, stream));
                 } else {
-                    if (s.mean_in_y0) to_summing(a, c.y[0], nk);
+                    if (s.mean == MEAN_IN_Y) to_summing(a, c.y[0], nk);
                     if (mrf_kernel_applicable(a, nk)) HIP_TRY(launch_mrf_conv(a, nk, stream));
                     else                              HIP_TRY(launch_conv(a, nk, stream));
                 }
             }
             TRY(prof.end());
-            prev_summed = s.mean_in_y0;
+            prev_summed = s.mean == MEAN_IN_Y;
             if (stop.stage == c.i && stop.step == 2 * s.m + s.half) {
                 if (until_flags)
-                    *until_flags = s.mean_in_y0 ? IRIS_HIFIGAN_UNTIL_MEAN_IN_Y0
+                    *until_flags = s.mean == MEAN_IN_Y ? IRIS_HIFIGAN_UNTIL_MEAN_IN_Y0
                                                 : (s.kind == STEP_PAIR && s.y == WS_XT ? IRIS_HIFIGAN_UNTIL_X_IN_XT : 0);
                 TRY(prof.finish());
                 return IRIS_HIFIGAN_OK;

@@ -58,6 +58,19 @@ PairLaunch pair_launch(const PairProblem* p, int nz, int B, int L, int C, float 
     return pa;
 }
 
+// a packed weight blob of create / prepare onto the device; *dev stays null when it fails
+int upload_blob(uint16_t** dev, const std::vector<uint16_t>& host, const char* what) {
+    hipError_t e = hipMalloc(dev, host.size() * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMemcpy(*dev, host.data(), host.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (*dev) (void)hipFree(*dev);
+        *dev = nullptr;
+        return fail(e == hipErrorOutOfMemory ? IRIS_HIFIGAN_OUT_OF_MEMORY : IRIS_HIFIGAN_HIP_ERROR,
+                    "%s weight upload failed: %s", what, hipGetErrorString(e));
+    }
+    return IRIS_HIFIGAN_OK;
+}
+
 }  // namespace
 
 int bf16_build_blob(iris_hifigan_handle* h, const float* weights_host) {
@@ -86,15 +99,7 @@ int bf16_build_blob(iris_hifigan_handle* h, const float* weights_host) {
         src += l.ref_w_floats + l.C_out;
     });
     run_host_jobs(jobs);
-    hipError_t e = hipMalloc(&h->blob16, off * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMemcpy(h->blob16, host.data(), off * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->blob16) (void)hipFree(h->blob16);
-        h->blob16 = nullptr;
-        return fail(e == hipErrorOutOfMemory ? IRIS_HIFIGAN_OUT_OF_MEMORY : IRIS_HIFIGAN_HIP_ERROR,
-                    "bf16 weight upload failed: %s", hipGetErrorString(e));
-    }
-    return IRIS_HIFIGAN_OK;
+    return upload_blob(&h->blob16, host, "bf16");
 }
 
 // ---- split-product mode: hi/mid planes of every ResBlock conv -------------------------------------------
@@ -122,15 +127,7 @@ int f32s_build_blob(iris_hifigan_handle* h, const float* weights_host) {
         src += l.ref_w_floats + l.C_out;
     });
     run_host_jobs(jobs);
-    hipError_t e = hipMalloc(&h->blob_s3, off * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMemcpy(h->blob_s3, host.data(), off * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->blob_s3) (void)hipFree(h->blob_s3);
-        h->blob_s3 = nullptr;
-        return fail(e == hipErrorOutOfMemory ? IRIS_HIFIGAN_OUT_OF_MEMORY : IRIS_HIFIGAN_HIP_ERROR,
-                    "split-product weight upload failed: %s", hipGetErrorString(e));
-    }
-    return IRIS_HIFIGAN_OK;
+    return upload_blob(&h->blob_s3, host, "split-product");
 }
 
 bool f32s_step_applicable(const iris_hifigan_handle* h, int C, int L, int nk) {
@@ -167,6 +164,114 @@ void fill_ups(s3::Launch& a, const ConvLayer& l, const float* x, const void* wp,
     a.out_stride = l.u; a.out_off = -(l.k - l.u) / 2; a.z_is_phase = 1;
     a.phase_bytes = (unsigned)(b16::packed_convt_phase_halfs(l.C_in, l.C_out, l.k, l.u) * 2);
     a.plane_bytes[0] = (unsigned)(s3::packed_convt_plane_halfs(l.C_in, l.C_out, l.k, l.u) * 2);
+}
+
+// ---- MRF: the launches of one stage, decided once (MrfStep / MrfStagePlan: generator_internal.h) ----
+struct StageCtx16 {         // what the MRF launches of stage i share
+    const iris_hifigan_handle* h;
+    int i, B, L;            // L: rows per item after the stage's upsample
+    uint16_t* ws;           // the workspace and its layout
+    const WsLayout* w;
+    const Stage& st() const { return h->stages[i]; }
+    uint16_t* buf(WsBuf r, int j) const {
+        return r == WS_UP ? ws + w->up : r == WS_Y ? ws + w->y[j] : r == WS_XT ? ws + w->xt[j] : nullptr;
+    }
+    double n_el() const { return (double)B * L * st().C; }
+};
+
+// the pair of dilation s.m in one launch; algorithmic FLOP / bytes (accounting L) are those of both steps
+PairLaunch stage_pair_launch(const StageCtx16& c, const MrfStep& s, double& flops, double& bytes) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const int nk = h->cfg.num_kernels;
+    PairProblem p[kMaxGroup];
+    flops = 0; bytes = 2.0 * c.n_el() * nk * 5;
+    for (int j = 0; j < nk; ++j) {
+        const ConvLayer& l1 = st.c1[j][s.m];
+        const ConvLayer& l2 = st.c2[j][s.m];
+        // (a summing pair has no branch outputs: its one tensor is the launch's sum_y)
+        p[j] = PairProblem{c.buf(s.x, j), h->blob16 + l1.w16_off, h->blob16 + l2.w16_off, h->blob + l1.b_off, h->blob + l2.b_off,
+                           s.mean == MEAN_NONE ? c.buf(s.y, j) : nullptr, l1.k, l1.dil};
+        flops += 2.0 * c.n_el() * (l1.C_in * l1.k + l2.C_in * l2.k);
+        bytes += 2.0 * (double)(l1.ref_w_floats + l2.ref_w_floats) + 4.0 * (l1.C_out + l2.C_out);
+    }
+    return pair_launch(p, nk, c.B, c.L, st.C, h->cfg.lrelu_slope);
+}
+
+// one conv step (half 0: convs1[m], half 1: convs2[m] + residual) of all branches
+Launch stage_conv_launch(const StageCtx16& c, const MrfStep& s, double& flops, double& bytes) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const int nk = h->cfg.num_kernels;
+    Problem p[kMaxGroup];
+    flops = 0; bytes = 2.0 * c.n_el() * nk * (s.half == 0 ? 2 : 3);
+    for (int j = 0; j < nk; ++j) {
+        const ConvLayer& l = s.half == 0 ? st.c1[j][s.m] : st.c2[j][s.m];
+        p[j] = conv_problem(c.buf(s.x, j), h->blob16 + l.w16_off, h->blob + l.b_off, c.buf(s.res, j), c.buf(s.y, j), l.k, l.dil);
+        flops += 2.0 * c.n_el() * l.C_in * l.k;
+        bytes += 2.0 * (double)l.ref_w_floats + 4.0 * l.C_out;
+    }
+    return conv_launch(p, nk, c.B, c.L, st.C, st.C, IN_ACT_LRELU, h->cfg.lrelu_slope);
+}
+
+// The steps of stage c.i, in order, with the buffers each reads and writes.  Pure: nothing is launched or recorded here, and no
+// buffer is resolved to an address (of the context it reads the handle, the stage, B, L and the layout's offsets).
+MrfStagePlan plan_mrf_stage_bf16(const StageCtx16& c, const ForwardStop& stop) {
+    const iris_hifigan_handle* h = c.h;
+    const Stage& st = c.st();
+    const WsLayout& w = *c.w;
+    const int i = c.i, nk = h->cfg.num_kernels, nd = h->cfg.num_dilations[0];
+    const bool last_stage = i + 1 == (int)h->stages.size();
+    MrfStagePlan pl;
+    pl.n = 0;
+    auto add = [&](StepKind kind, int m, int half, WsBuf x, WsBuf res, WsBuf y, StepMean mean) {
+        pl.s[pl.n++] = MrfStep{kind, false, m, half, x, res, y, mean};
+    };
+    WsBuf cur = WS_UP;          // where the running x of every branch lies
+    for (int m = 0; m < nd; ++m) {
+        // C <= 128: conv1 and conv2 of the pair in ONE launch, xt stays in LDS (mrf_pair_bf16.h): two tensor passes over HBM
+        // instead of five.  It cannot work in place (a block's input window overlaps its neighbours' output rows), so its
+        // output alternates between the y and the xt buffer of the branch.
+        const WsBuf to = cur == WS_Y ? WS_XT : WS_Y;
+        double f, by;
+        const PairLaunch pa = stage_pair_launch(c, MrfStep{STEP_PAIR, false, m, 1, WS_NONE, WS_NONE, WS_NONE, MEAN_NONE}, f, by);
+        bool same_k = true;     // what the pair kernels take: equal kernel sizes, conv2 undilated
+        for (int j = 0; j < nk; ++j) same_k = same_k && st.c1[j][m].k == st.c2[j][m].k && st.c2[j][m].dil == 1;
+        // The stage's LAST pair: one block runs the three branches of its rows and stores only the MRF mean, as the operand of
+        // the layer that follows (bf16, activated) or -- last stage -- as the fp32 mean conv_post takes.  Not when the caller
+        // asked for a state of this stage (forward_until returns branch tensors).
+        if (m == nd - 1 && stop.stage != i && same_k && nk == 3) {
+            bool room = true;
+            if (last_stage) {
+                // The fp32 mean is twice a bf16 tensor: it goes over `up` + y[0], which must be adjacent and both free, i.e. the
+                // pair reads xt[j] (so after an odd number of pairs; otherwise conv_post reads three tensors), and conv_post
+                // must take one fp32 input of this shape.
+                const size_t n_el = (size_t)c.n_el();
+                room = w.y[0] >= w.up && (w.y[0] - w.up) * 2 >= n_el * 2 && (w.y[0] - w.up) <= n_el + 128 && cur == WS_XT;
+                post::ConvPostLaunch probe; memset(&probe, 0, sizeof(probe));
+                probe.B = c.B; probe.L = c.L; probe.C = st.C; probe.n_in = 1; probe.k = h->post.k;
+                room = room && h->post.C_in == st.C && post::conv_post_rows_ok(probe, false);
+            }
+            if (room && pair_sum_applicable(pa, nk, last_stage)) {
+                add(STEP_PAIR_SUM, m, 1, cur, WS_NONE, last_stage ? WS_UP : to, last_stage ? MEAN_F32_IN_UP : MEAN_IN_Y);
+                continue;
+            }
+        }
+        // (forward_until asking for the state after conv1 gets the two separate launches for that pair)
+        const bool want_xt = stop.stage == i && stop.step == 2 * m;
+        if (!want_xt && same_k && pair_applicable(pa, nk)) {
+            add(STEP_PAIR, m, 1, cur, WS_NONE, to, MEAN_NONE);
+            cur = to;
+            continue;
+        }
+        // conv1 writes the branch's other buffer; conv2 (own rows only: in place is safe) writes back over x, or to y[j]
+        // when x is the shared upsample output
+        const WsBuf tmp = cur == WS_XT ? WS_Y : WS_XT, dst = cur == WS_UP ? WS_Y : cur;
+        add(STEP_CONV1, m, 0, cur, WS_NONE, tmp, MEAN_NONE);
+        add(STEP_CONV2, m, 1, tmp, cur, dst, MEAN_NONE);
+        cur = dst;
+    }
+    return pl;
 }
 }  // namespace
 
@@ -206,135 +311,70 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, cons
         TRY(prof.end());
     }
 
-    int L = T;
-    // where the running x of branch j lives: the fused pair kernel cannot work in place (a block's input window
-    // overlaps its neighbours' output rows), so its output alternates between the y and the xt buffer of the branch
-    const uint16_t* cur[IRIS_HIFIGAN_MAX_KERNELS] = {nullptr};
-    // the previous stage's last pair ran on the summing kernel (mrf_pair_bf16.h): its ONE output is the next layer's operand
-    const uint16_t* mean16 = nullptr;     // bf16(LeakyReLU(MRF mean)), for the next ConvTranspose1d
-    const float* mean32 = nullptr;        // the fp32 MRF mean of the last stage, for conv_post
-    for (size_t i = 0; i < h->stages.size(); ++i) {
-        const Stage& st = h->stages[i];
-        const int L_out = L * st.rate;
+    StageCtx16 c{h, 0, B, T, ws, &w};
+    StageOut prev{MEAN_NONE, WS_NONE};      // what the previous stage handed over (stage 0 reads conv_pre's output)
+    for (c.i = 0; c.i < (int)h->stages.size(); ++c.i) {
+        const Stage& st = c.st();
+        const int L = c.L, L_out = L * st.rate;
         // ---- LeakyReLU + ConvTranspose1d (hifigan_pretrained.py:127-128) ----
         {
             const ConvLayer& l = st.up;
-            const int n_in = i == 0 ? 1 : nk;       // (accounting L counts the reference's three branch tensors whatever was fused)
-            const uint16_t* const one = i == 0 ? ws + w.pre : mean16;
-            const bool mrf = i > 0 && !mean16;
-            // (the summing pair's mean16 is already activated and rounded)
-            Launch a = convt_launch(mrf ? cur : &one, nk, mrf ? IN_ACT_MRF_LRELU : (i == 0 ? IN_ACT_LRELU : IN_ACT_NONE),
+            const int n_in = c.i == 0 ? 1 : nk;     // (accounting L counts the reference's three branch tensors whatever was fused)
+            // the branch tensors (the kernel forms their mean), or ONE tensor: conv_pre's, or the summing pair's mean, which is
+            // already activated and rounded
+            const bool mrf = c.i > 0 && prev.mean == MEAN_NONE;
+            const uint16_t* x[IRIS_HIFIGAN_MAX_KERNELS];
+            for (int j = 0; j < nk; ++j) x[j] = c.i == 0 ? ws + w.pre : c.buf(prev.buf, j);
+            Launch a = convt_launch(x, nk, mrf ? IN_ACT_MRF_LRELU : (c.i == 0 ? IN_ACT_LRELU : IN_ACT_NONE),
                                     wb + l.w16_off, blob + l.b_off, ws + w.up, B, L, l.C_in, l.C_out, l.k, l.u, slope);
-            TRY(prof.begin(1, (int)i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
+            TRY(prof.begin(1, c.i, 0, 2.0 * fB * L * l.C_in * l.C_out * l.k,
                            2.0 * (fB * L * l.C_in * n_in + fB * L_out * l.C_out + (double)l.ref_w_floats) + 4.0 * l.C_out));
             HIP_TRY(launch_convt_bf16(a, l.k, l.u, stream));      // one GEMM launch (convt_mfma_bf16.h) where it applies
             TRY(prof.end());
         }
         // ---- MRF: num_kernels ResBlocks advance together (hifigan_pretrained.py:64-71,131-136) ----
-        const int nd = h->cfg.num_dilations[0];
-        const double n_el = fB * L_out * st.C;
-        for (int j = 0; j < nk; ++j) cur[j] = ws + w.up;
-        mean16 = nullptr;
-        auto report_stop = [&]() -> int {
-            if (until_flags) *until_flags = (cur[0] == ws + w.xt[0]) ? IRIS_HIFIGAN_UNTIL_X_IN_XT : 0;
-            return prof.finish();
-        };
-        for (int m = 0; m < nd; ++m) {
-            // C <= 64: conv1 and conv2 of the pair in ONE launch, xt stays in LDS (mrf_pair_bf16.h): two tensor passes
-            // over HBM instead of five.  Algorithmic FLOP / bytes (accounting L) are those of both steps; the record
-            // carries the index of the pair's second step.  (forward_until asking for the state after conv1 gets the
-            // two separate launches for that pair.)
-            {
-                PairProblem pp[kMaxGroup];
-                double flops = 0, wbytes = 0;
-                for (int j = 0; j < nk && j < kMaxGroup; ++j) {
-                    const ConvLayer& l1 = st.c1[j][m];
-                    const ConvLayer& l2 = st.c2[j][m];
-                    pp[j] = PairProblem{cur[j], wb + l1.w16_off, wb + l2.w16_off, blob + l1.b_off, blob + l2.b_off,
-                                        (cur[j] == ws + w.y[j]) ? ws + w.xt[j] : ws + w.y[j], l1.k, l1.dil};
-                    flops += 2.0 * n_el * (l1.C_in * l1.k + l2.C_in * l2.k);
-                    wbytes += 2.0 * (double)(l1.ref_w_floats + l2.ref_w_floats) + 4.0 * (l1.C_out + l2.C_out);
-                }
-                PairLaunch pa = pair_launch(pp, nk, B, L_out, st.C, slope);
-                const bool want_xt = stop.stage == (int)i && stop.step == 2 * m;
-                bool same_k = true;
-                for (int j = 0; j < nk; ++j) same_k = same_k && st.c1[j][m].k == st.c2[j][m].k && st.c2[j][m].dil == 1;
-                // The stage's LAST pair: one block runs the three branches of its rows and stores only the MRF mean, as the
-                // operand of the layer that follows (bf16, activated) or -- last stage -- as the fp32 mean conv_post takes.
-                // Not when the caller asked for a state of this stage (forward_until returns branch tensors).  The fp32 mean
-                // of the last stage is twice a bf16 tensor: it goes into `up` + y[0], adjacent in the workspace and both
-                // free while the pair reads xt[j] (an odd number of pairs per ResBlock; otherwise conv_post reads three).
-                if (m == nd - 1 && stop.stage != (int)i && same_k && nk == 3) {
-                    const bool last_stage = i + 1 == h->stages.size();
-                    bool room = true;
-                    if (last_stage) {
-                        room = w.y[0] >= w.up && (w.y[0] - w.up) * 2 >= (size_t)n_el * 2 && (w.y[0] - w.up) <= (size_t)n_el + 128;
-                        for (int j = 0; j < nk; ++j) room = room && cur[j] == ws + w.xt[j];
-                        post::ConvPostLaunch probe; memset(&probe, 0, sizeof(probe));       // conv_post must take one fp32 input of this shape
-                        probe.B = B; probe.L = L_out; probe.C = st.C; probe.n_in = 1; probe.k = h->post.k;
-                        room = room && h->post.C_in == st.C && post::conv_post_rows_ok(probe, false);
-                    }
-                    if (room && pair_sum_applicable(pa, nk, last_stage)) {
-                        void* dst = last_stage ? (void*)(ws + w.up) : (void*)pa.p[0].y;
-                        TRY(prof.begin(2, (int)i, 2 * m + 1, flops, 2.0 * n_el * nk * 5 + wbytes));
-                        HIP_TRY(launch_pair_bf16_sum(pa, dst, last_stage, stream));
-                        TRY(prof.end());
-                        if (last_stage) mean32 = (const float*)dst; else mean16 = (const uint16_t*)dst;
-                        for (int j = 0; j < nk; ++j) cur[j] = nullptr;
-                        continue;
-                    }
-                }
-                if (!want_xt && same_k && pair_applicable(pa, nk)) {
-                    TRY(prof.begin(2, (int)i, 2 * m + 1, flops, 2.0 * n_el * nk * 5 + wbytes));
-                    HIP_TRY(launch_pair_bf16(pa, nk, stream));
-                    TRY(prof.end());
-                    for (int j = 0; j < nk; ++j) cur[j] = pa.p[j].y;
-                    if (stop.stage == (int)i && stop.step == 2 * m + 1) return report_stop();
-                    continue;
-                }
-            }
-            for (int half = 0; half < 2; ++half) {
-                Problem p[kMaxGroup];
-                double flops = 0, wbytes = 0;
-                for (int j = 0; j < nk; ++j) {
-                    const ConvLayer& l = half == 0 ? st.c1[j][m] : st.c2[j][m];
-                    // x entering this pair is cur[j]; conv1 writes the branch's other buffer, conv2 (own rows only:
-                    // in place is safe) writes back to cur[j], or to y[j] when cur[j] is the shared upsample output
-                    uint16_t* tmp = (cur[j] == ws + w.xt[j]) ? ws + w.y[j] : ws + w.xt[j];
-                    uint16_t* dst = (cur[j] == ws + w.up) ? ws + w.y[j] : const_cast<uint16_t*>(cur[j]);
-                    p[j] = half == 0 ? conv_problem(cur[j], wb + l.w16_off, blob + l.b_off, nullptr, tmp, l.k, l.dil)
-                                     : conv_problem(tmp, wb + l.w16_off, blob + l.b_off, cur[j], dst, l.k, l.dil);
-                    flops += 2.0 * n_el * l.C_in * l.k;
-                    wbytes += 2.0 * (double)l.ref_w_floats + 4.0 * l.C_out;
-                }
-                Launch a = conv_launch(p, nk, B, L_out, st.C, st.C, IN_ACT_LRELU, slope);
-                TRY(prof.begin(2, (int)i, 2 * m + half, flops, 2.0 * n_el * nk * (half == 0 ? 2 : 3) + wbytes));
+        c.L = L_out;
+        const MrfStagePlan plan = plan_mrf_stage_bf16(c, stop);
+        for (int n = 0; n < plan.n; ++n) {
+            const MrfStep& s = plan.s[n];
+            double flops, bytes;
+            if (s.kind == STEP_PAIR || s.kind == STEP_PAIR_SUM) {
+                PairLaunch pa = stage_pair_launch(c, s, flops, bytes);
+                TRY(prof.begin(2, c.i, 2 * s.m + 1, flops, bytes));      // the record carries the index of the pair's second step
+                if (s.kind == STEP_PAIR_SUM) HIP_TRY(launch_pair_bf16_sum(pa, c.buf(s.y, 0), s.mean == MEAN_F32_IN_UP, stream));
+                else                         HIP_TRY(launch_pair_bf16(pa, nk, stream));
+            } else {
+                Launch a = stage_conv_launch(c, s, flops, bytes);
+                TRY(prof.begin(2, c.i, 2 * s.m + s.half, flops, bytes));
                 HIP_TRY(launch_conv_bf16(a, nk, stream));
-                TRY(prof.end());
-                if (half == 1) for (int j = 0; j < nk; ++j) cur[j] = a.p[j].y;
-                if (stop.stage == (int)i && stop.step == 2 * m + half) {
-                    // after conv1 the flag says where xt is NOT: x is still in cur[], xt in the other buffer
-                    return report_stop();
-                }
+            }
+            TRY(prof.end());
+            if (stop.stage == c.i && stop.step == 2 * s.m + s.half) {
+                // where the running x lies now: conv1 left it where it was (and xt in the branch's other buffer)
+                if (until_flags) *until_flags = (s.kind == STEP_CONV1 ? s.x : s.y) == WS_XT ? IRIS_HIFIGAN_UNTIL_X_IN_XT : 0;
+                return prof.finish();
             }
         }
-        L = L_out;
+        prev = plan.out();
     }
 
     // ---- LeakyReLU + conv_post + tanh (hifigan_pretrained.py:139-141): bf16 in, fp32 waveform (or what `out` asks for) out ----
     {
         const ConvLayer& l = h->post;
+        const int L = c.L;
         TRY(prof.begin(3, -1, 0, 2.0 * fB * L * l.C_in * l.k,
                        2.0 * fB * L * l.C_in * nk + 4.0 * (fB * L + (double)l.ref_w_floats + 1)));
-        const int C = l.C_in;
-        post::ConvPostLaunch ar; memset(&ar, 0, sizeof(ar));
-        for (int j = 0; j < nk && j < 4; ++j) ar.x[j] = cur[j];
-        ar.n_in = nk; ar.inv_n = 1.0f / (float)nk;
-        ar.w = blob + l.w_off; ar.bias = blob + l.b_off; out.to_post(ar);
-        ar.B = B; ar.L = L; ar.C = C; ar.k = l.k; ar.slope = slope;
-        if (mean32) {
-            // the summing pair left the fp32 mean: conv_post as in the fp32 path (one fp32 input, LeakyReLU in fp32)
-            ar.x[0] = mean32; ar.n_in = 1;
+        auto fill = [&](auto& a) {        // the fields the two descriptors (conv_post.h, conv_mfma_bf16.h) share
+            memset(&a, 0, sizeof(a));
+            for (int j = 0; j < nk; ++j) a.x[j] = c.buf(prev.buf, j);
+            a.n_in = nk; a.inv_n = 1.0f / (float)nk;
+            a.w = blob + l.w_off; a.bias = blob + l.b_off; out.to_post(a);
+            a.B = B; a.L = L; a.C = l.C_in; a.k = l.k; a.slope = slope;
+        };
+        post::ConvPostLaunch ar; fill(ar);
+        if (prev.mean == MEAN_F32_IN_UP) {
+            // the summing pair left the fp32 mean in `up`: conv_post as in the fp32 path (one fp32 input, LeakyReLU in fp32)
+            ar.n_in = 1;
             if (!post::conv_post_rows_ok(ar, false)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "conv_post: shape not supported behind the summing pair");
             HIP_TRY(post::launch_conv_post_t<false>(ar, stream));
         } else if (post::conv_post_rows_ok(ar, true)) {
@@ -342,11 +382,7 @@ int bf16_forward(iris_hifigan_handle* h, const void* mel_dev, int B, int T, cons
             // the shapes this one cannot (other channel counts; a single item of 2^31 bytes or more)
             HIP_TRY(post::launch_conv_post_t<true>(ar, stream));
         } else {
-            PostLaunch a; memset(&a, 0, sizeof(a));
-            for (int j = 0; j < nk; ++j) a.x[j] = cur[j];
-            a.n_in = nk; a.inv_n = 1.0f / (float)nk;
-            a.w = blob + l.w_off; a.bias = blob + l.b_off; out.to_post(a);
-            a.B = B; a.L = L; a.C = C; a.k = l.k; a.slope = slope;
+            PostLaunch a; fill(a);
             HIP_TRY(launch_conv_post_bf16(a, stream));
         }
         TRY(prof.end());
@@ -375,6 +411,19 @@ int upload_pair_weights(PairWeights& d, PairProblem& p, const float* w1, const f
     HIP_TRY(d.b1.upload(b1, sizeof(float) * C));
     HIP_TRY(d.b2.upload(b2, sizeof(float) * C));
     p.w1 = d.w1.p; p.w2 = d.w2.p; p.b1 = d.b1.f32(); p.b2 = d.b2.f32();
+    return IRIS_HIFIGAN_OK;
+}
+
+// The per-branch argument checks of the two pair entry points, and their problems without weights.  y_dev: the branch
+// outputs; null for the summing pair, which has none.
+int pair_problems(PairProblem* p, int nz, const void* const* x_dev, const float* const* w1_host, const float* const* b1_host,
+                  const float* const* w2_host, const float* const* b2_host, void* const* y_dev, const int32_t* k, const int32_t* dil) {
+    for (int j = 0; j < nz; ++j) {
+        if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j] || (y_dev && !y_dev[j]))
+            return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
+        if (k[j] < 1 || !(k[j] & 1) || dil[j] < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad kernel size / dilation");
+        p[j] = PairProblem{(const uint16_t*)x_dev[j], nullptr, nullptr, nullptr, nullptr, y_dev ? (uint16_t*)y_dev[j] : nullptr, k[j], dil[j]};
+    }
     return IRIS_HIFIGAN_OK;
 }
 }  // namespace
@@ -416,12 +465,7 @@ int32_t iris_hifigan_op_mrf_pair_bf16(const void* const* x_dev, const float* con
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad mrf_pair shape");
     hipStream_t stream = (hipStream_t)stream_;
     PairProblem p[kMaxGroup];
-    for (int j = 0; j < n_branches; ++j) {
-        if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j] || !y_dev[j])
-            return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
-        if (k[j] < 1 || !(k[j] & 1) || dil[j] < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad kernel size / dilation");
-        p[j] = PairProblem{(const uint16_t*)x_dev[j], nullptr, nullptr, nullptr, nullptr, (uint16_t*)y_dev[j], k[j], dil[j]};
-    }
+    TRY(pair_problems(p, n_branches, x_dev, w1_host, b1_host, w2_host, b2_host, y_dev, k, dil));
     PairLaunch a = pair_launch(p, n_branches, B, L, C, slope);
     if (!pair_applicable(a, n_branches))
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the fused pair kernel takes C = 32, 64 or 128 and windows up to 64 KB");
@@ -444,13 +488,9 @@ int32_t iris_hifigan_op_mrf_pair_mean_bf16(const void* const* x_dev, const float
     const int nz = 3;
     hipStream_t stream = (hipStream_t)stream_;
     PairProblem p[kMaxGroup];
-    for (int j = 0; j < nz; ++j) {
-        if (!x_dev[j] || !w1_host[j] || !b1_host[j] || !w2_host[j] || !b2_host[j])
-            return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL branch argument");
-        if (k[j] < 1 || !(k[j] & 1) || dil[j] < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad kernel size / dilation");
+    TRY(pair_problems(p, nz, x_dev, w1_host, b1_host, w2_host, b2_host, nullptr, k, dil));
+    for (int j = 0; j < nz; ++j)
         if (x_dev[j] == mean_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "the mean must not overwrite an input");
-        p[j] = PairProblem{(const uint16_t*)x_dev[j], nullptr, nullptr, nullptr, nullptr, nullptr, k[j], dil[j]};
-    }
     PairLaunch a = pair_launch(p, nz, B, L, C, slope);
     if (!pair_sum_applicable(a, nz, mean_f32 != 0))
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the summing pair kernel takes C = 32 or 64, three branches and windows up to 64 KB");

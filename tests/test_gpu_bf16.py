@@ -314,6 +314,36 @@ def test_bf16_intermediates_match_restatement(engine, dev):
         assert np.abs(got["xt"][j] - want).max() <= 0.02 * np.abs(want).max() and (got["xt"][j] == want).mean() > 0.9, j
 
 
+def test_bf16_buffer_routing_at_every_stop(engine, dev):
+    """``forward_until`` at every (stage, step): where each step leaves the running x, xt and the upsample output.  A stop
+    after a conv1 (even step) leaves the x that entered the pair untouched, so -- once the engine has applied the flag's
+    swap -- it is bit for bit the x the previous pair's stop returned; nothing overwrites ``up`` while its stage is the one
+    asked for; no bf16 stop reports a mean in y[0]; and the last step's branch mean meets the restatement's ``mrf.{i}`` tap
+    within the bounds of test_bf16_intermediates_match_restatement."""
+    from iris._weights import seeded_mel
+    eng, sd = engine
+    cfg = eng.cfg
+    mel_np = seeded_mel(21, 2, 9, log_mel=True)
+    taps = {}
+    orc.generator_forward_bf16(orc.to_torch_folded(sd), mel_np, taps=taps)
+    mel = torch.from_numpy(mel_np).to(dev)
+    n_steps = 2 * len(cfg.resblock_dilation_sizes[0])
+    for i in range(cfg.num_upsamples):
+        stops = [eng.forward_until(mel, i, s, dtype="bf16") for s in range(n_steps)]
+        for s, got in enumerate(stops):
+            assert not got["mean_in_y0"], (i, s)
+            assert np.array_equal(got["up"], stops[0]["up"]), (i, s)
+        for m in range(1, n_steps // 2):
+            for j in range(cfg.num_kernels):
+                assert np.array_equal(stops[2 * m]["y"][j], stops[2 * m - 1]["y"][j]), (i, m, j)
+        y = stops[-1]["y"]
+        mrf = ((y[0] + y[1]) + y[2]) / np.float32(3)
+        want = taps[f"mrf.{i}"].numpy()
+        d = np.abs(mrf - want)
+        print(f"stage {i}: mean max {d.max():.3e} mean {d.mean():.3e} of max|want| {np.abs(want).max():.3e}")
+        assert d.max() <= 0.03 * np.abs(want).max() and d.mean() <= 2e-3 * np.abs(want).max(), (i, d.max(), d.mean())
+
+
 def test_bf16_is_deterministic_and_batch_independent(engine, dev):
     from iris._weights import seeded_mel
     eng, _ = engine
