@@ -494,10 +494,16 @@ int32_t iris_vae_decoder_forward_ragged(iris_vae_decoder_handle* h, const float*
 /* The decoder half of TextConditionedVAE.call(training=False) (vae.py:401-422): z_dev [B, T / 2^down_stages, latent_dim] is a
  * posterior latent (the mean that iris_vae_encoder_forward writes) and the flow runs FORWARDS -- couplings 0 .. n - 1,
  * y2 = x2 + t -- where iris_vae_decoder_forward runs it in reverse.  Everything else is iris_vae_decoder_forward: the same
- * plan, launches (iris_vae_decoder_launch_count), workspace, outputs, checks and errors.  Dense batches only. */
+ * plan, launches (iris_vae_decoder_launch_count), workspace, outputs, checks and errors. */
 int32_t iris_vae_decoder_forward_posterior(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_dev, int32_t B, int32_t T,
                                            float* mel_out_dev, float* residual_out_dev, void* workspace_dev,
                                            uint64_t workspace_bytes, void* stream);
+/* iris_vae_decoder_forward_posterior over a ragged batch: lengths_dev, its sanitising, what is read, what is written as 0.0f,
+ * the plan, the checks and the errors are those of iris_vae_decoder_forward_ragged; the flow runs forwards.  Item b is bit
+ * for bit iris_vae_decoder_forward_posterior of cond[b, :len_b] and z[b, :len_b >> down_stages] alone. */
+int32_t iris_vae_decoder_forward_posterior_ragged(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_dev, int32_t B,
+                                                  int32_t T, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
+                                                  void* workspace_dev, uint64_t workspace_bytes, void* stream);
 /* Host only: kernel launches of one forward that asks for the residual (one fewer without it):
  * 3 + 2 * down_stages + decoder_blocks + 2. */
 int32_t iris_vae_decoder_launch_count(const iris_vae_decoder_handle* h, int32_t B, int32_t T, int32_t* n);
@@ -540,6 +546,24 @@ int32_t iris_vae_encoder_workspace_bytes(const iris_vae_encoder_handle* h, int32
 int32_t iris_vae_encoder_forward(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
                                  float* mean_out_dev, float* logvar_out_dev, void* workspace_dev, uint64_t workspace_bytes,
                                  void* stream);
+/* Ragged batch: recorded utterances of different lengths encoded in one call (the posterior half of
+ * iris_vae_decoder_forward_ragged, and with the same semantics).  mel_dev [B, n_mels, T], cond_dev [B, T, cond_dim] and the
+ * outputs [B, T / 2^down_stages, latent_dim] as in the dense call; lengths_dev [B] int32 on the device (caller-owned): item
+ * b's frames at the full rate, sanitised on the device -- clamped to [0, T], then rounded down to a multiple of
+ * 2^down_stages -- giving len_b.
+ * Item b is computed exactly as the dense call on mel[b, :, :len_b] and cond[b, :len_b] alone would compute it, bit for
+ * bit: at every level the 'same' padding ends at the item's own length.  mel[b, :, len_b:] and cond[b, len_b:, :] are
+ * never read, so they may hold anything, NaN included; workspace rows past an item's length are neither written nor read
+ * (the taps below are undefined there).  mean[b, len_b >> down_stages:, :] and logvar[b, len_b >> down_stages:, :] are
+ * written as 0.0f: such a row adds exactly 0 to the KL sum of iris_vae_losses.
+ * The host never reads the lengths: launches, grids and workspace are the dense call's for (B, T), and the launch count
+ * and workspace queries above and below hold for both calls.  Asynchronous on `stream`, allocates nothing, safe inside a
+ * stream capture.  lengths_dev == NULL (B, T > 0) returns IRIS_HIFIGAN_INVALID_ARGUMENT; shape and workspace errors are the
+ * dense call's.  No failing call launches.  (Named outside the iris_vae_encoder_ family, whose seven functions are the
+ * dense stage; it takes that stage's handle.) */
+int32_t iris_vae_posterior_encode_ragged(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
+                                        const int32_t* lengths_dev, float* mean_out_dev, float* logvar_out_dev,
+                                        void* workspace_dev, uint64_t workspace_bytes, void* stream);
 /* Host only: kernel launches of one forward (a dry run of the forward's own code). */
 int32_t iris_vae_encoder_launch_count(const iris_vae_encoder_handle* h, int32_t B, int32_t T, int32_t* n);
 /* Host only, for tests: where a forward of (B, T) leaves an intermediate in its workspace (valid until the next forward on
@@ -549,6 +573,30 @@ int32_t iris_vae_encoder_launch_count(const iris_vae_encoder_handle* h, int32_t 
 #define IRIS_VAE_ENC_TAP_LAT_H 2   /* downsample(h) */
 int32_t iris_vae_encoder_tap(const iris_vae_encoder_handle* h, int32_t B, int32_t T, int32_t which, uint64_t* byte_offset,
                              uint64_t* floats);
+
+/* ---- Masked VAE losses of a reconstruction (csrc/vae_losses.h) -----------------------------------------------------
+ * TextConditionedVAE.compute_recon_l1 and compute_kl (src/iris/vae.py:424-446) as scripts/train_vae.py:94-103 calls them,
+ * reduced on the device: target_dev and recon_dev [B, n_mels, T] (channels-first), mean_dev and logvar_dev
+ * [B, T / 2^down_stages, latent_dim], lengths_dev [B] int32 on the device or NULL.  out_dev holds 2 + 2B floats:
+ *   out[0]          the reconstruction L1,  sum_b sum_{t < len_b} |target - recon|  /  (sum_b len_b * n_mels + 1e-6)
+ *   out[1]          the KL,  sum_b sum -0.5 (1 + logvar - mean^2 - exp(logvar)) over latent rows < len_b >> down_stages and
+ *                   every channel  /  (sum_b (len_b >> down_stages) + 1e-8)  -- rows, not rows x channels: the reference's own
+ *   out[2 + b]      item b's L1 sum (the numerator's part);  out[2 + B + b]  item b's KL sum.
+ * len_b is lengths_dev[b] sanitised as the ragged forwards sanitise it (clamped to [0, T], rounded down to a multiple of
+ * 2^down_stages); nothing at or past an item's length is read, in any of the four tensors.  lengths_dev == NULL: both are
+ * the plain means over all elements (ops.mean), and the item sums cover whole items.
+ * Terms are computed in fp32 and added in fp64 in a fixed order (fixed tiles counted from each item's row 0, a fixed tree
+ * inside a tile, tiles in order, items in order; no floating-point atomics): two calls give the same bits, and item b's
+ * two sums are bit for bit those of the call on its own rows alone, whatever T it is padded to.  An all-empty batch gives
+ * 0 / (0 + eps) = 0.  Two launches (one when B == 0 or T == 0), asynchronous on `stream`, on the current device; allocates
+ * nothing.  workspace_dev: iris_vae_losses_workspace_bytes bytes, aligned to 8.
+ * A NULL pointer, a negative size and a T that is not a multiple of 2^down_stages return IRIS_HIFIGAN_INVALID_ARGUMENT,
+ * B > 65535 and down_stages > 8 IRIS_HIFIGAN_UNSUPPORTED, a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call
+ * launches. */
+int32_t iris_vae_losses_workspace_bytes(int32_t B, int32_t n_mels, int32_t T, int32_t latent_dim, int32_t down_stages, uint64_t* bytes);
+int32_t iris_vae_losses(const float* target_dev, const float* recon_dev, const float* mean_dev, const float* logvar_dev, int32_t B,
+                        int32_t n_mels, int32_t T, int32_t latent_dim, int32_t down_stages, const int32_t* lengths_dev /* or NULL */,
+                        float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
 /* ---- Phoneme encoder, duration head and length regulator in front of the VAE decoder (csrc/text_encoder.h) ----
  * The text side of the reference's scripts/synthesize.py:93-122: phoneme ids [B, P] -> encoder output [B, P, embed_dim]

@@ -92,7 +92,7 @@ float* vae_dec_out(float* ws, const VaeWs& w, int i) { return ws + ((i & 1) ? w.
 // Queues the launches of one forward (or, in a dry run, counts them).  `lengths` (device, or nullptr for the dense forward)
 // selects the ragged kernels: the same launches over the same grids and buffers, each bounded by the items' own rows at
 // its level -- sh_in / sh_out count the halvings of the launch's input and output below the full rate.
-// `posterior`: z is a posterior latent and the flow runs forwards (TextConditionedVAE.call, vae.py:401); dense only.
+// `posterior`: z is a posterior latent and the flow runs forwards (TextConditionedVAE.call, vae.py:401).
 int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, int B, int T, const int32_t* lengths, float* mel,
                 float* residual, float* ws, hipStream_t stream, bool posterior = false) {
     const iris_vae_decoder_config& c = h->cfg;
@@ -282,6 +282,13 @@ int32_t iris_vae_decoder_forward_posterior(iris_vae_decoder_handle* h, const flo
                                            float* mel_out_dev, float* residual_out_dev, void* workspace_dev,
                                            uint64_t workspace_bytes, void* stream_) {
     return vae_forward_checked(h, cond_dev, z_dev, B, T, false, nullptr, mel_out_dev, residual_out_dev, workspace_dev,
+                               workspace_bytes, stream_, true);
+}
+
+int32_t iris_vae_decoder_forward_posterior_ragged(iris_vae_decoder_handle* h, const float* cond_dev, const float* z_dev, int32_t B,
+                                                  int32_t T, const int32_t* lengths_dev, float* mel_out_dev, float* residual_out_dev,
+                                                  void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
+    return vae_forward_checked(h, cond_dev, z_dev, B, T, true, lengths_dev, mel_out_dev, residual_out_dev, workspace_dev,
                                workspace_bytes, stream_, true);
 }
 

@@ -9,6 +9,13 @@
 //   3 .. N+2   one fused WaveNet block each (conv -> GELU -> FiLM rows of launch 2 -> LDS -> res_proj -> + h)
 //   next S     downsample.blocks[s] on h: k5 stride 2 'same' + GELU -- the weights the conditioning goes through in the decoder
 //   last       latent_mean_proj | latent_logvar_proj as one GEMM of 2 * latent_dim columns, stored as two tensors (kGemmSplitOut)
+//
+// iris_vae_posterior_encode_ragged runs the same launches over the same grids and buffers with the RAGGED instantiations
+// ("Ragged form", vae_decoder.h): every launch is bounded by its items' own rows at its level, and the last one stores
+// mean | logvar rows past an item's latent rows as 0.0f.
+//
+// The iris_vae_losses* entry points (csrc/vae_losses.h) are here too: the masked reconstruction L1 and KL of a
+// reconstruction, reduced on the device from the tensors the two posterior forwards leave there.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,6 +24,7 @@
 
 #include "stage_host.h"
 #include "vae_decoder.h"
+#include "vae_losses.h"
 
 using namespace iris;
 
@@ -97,32 +105,35 @@ int enc_check_shape(const iris_vae_encoder_handle* h, int32_t B, int32_t T) {
     return IRIS_HIFIGAN_OK;
 }
 
-// Queues the launches of one forward (or, in a dry run, counts them).
-int enc_forward(iris_vae_encoder_handle* h, const float* mel, const float* cond, int B, int T, float* mean, float* logvar, float* ws,
-                hipStream_t stream) {
+// Queues the launches of one forward (or, in a dry run, counts them).  `lengths` (device, or nullptr for the dense forward)
+// selects the ragged kernels, as in vae_forward (iris_vae_decoder.hip): sh_in / sh_out count the halvings of a launch's input
+// and output below the full rate.
+int enc_forward(iris_vae_encoder_handle* h, const float* mel, const float* cond, int B, int T, const int32_t* lengths, float* mean,
+                float* logvar, float* ws, hipStream_t stream) {
     const iris_vae_encoder_config& c = h->cfg;
     const int C = c.model_channels, S = c.down_stages, Tq = T >> S;
     const EncWs w = enc_ws(h, B, T);
     const float* blob = h->blob;
-    auto gemm = [&](const float* x, const PackedGemm& l, float* y, int L_in, int L_out) {
+    auto gemm = [&](const float* x, const PackedGemm& l, float* y, int L_in, int L_out, int sh_in, int sh_out) {
         vae::GemmLaunch a; memset(&a, 0, sizeof(a));
+        a.lengths = lengths; a.len_T = T; a.len_shift = S; a.sh_in = sh_in; a.sh_out = sh_out;
         a.x = x; a.wp = (const f32x4*)(blob + l.w_off); a.bias = blob + l.b_off; a.y = y;
         a.L_in = L_in; a.L_out = L_out; a.C_in = l.C_in; a.C_out = l.C_out;
         a.ks = l.k; a.dil = 1; a.stride = 1; a.pad_left = (l.k - 1) / 2;
         return a;
     };
     {   // h = in_proj(mels^T): the transpose is the staging loop's                           vae.py:382-385
-        vae::GemmLaunch a = gemm(mel, h->in_proj, ws + w.h0, T, T);
+        vae::GemmLaunch a = gemm(mel, h->in_proj, ws + w.h0, T, T, 0, 0);
         HIP_TRY(vae::launch_gemm(a, B, false, stream, vae::kGemmMelIn));
     }
     if (c.num_wavenet_blocks > 0) {   // FiLM rows of every block, from the full-rate conditioning         vae.py:21-29
-        vae::GemmLaunch a = gemm(cond, h->film_gemm, ws + w.film, T, T);
+        vae::GemmLaunch a = gemm(cond, h->film_gemm, ws + w.film, T, T, 0, 0);
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
     const float* x = ws + w.h0;
     for (int i = 0; i < c.num_wavenet_blocks; ++i) {                                         // vae.py:57-67, 388-389
         float* y = ws + ((i & 1) ? w.hb : w.ha);
-        vae::GemmLaunch a = gemm(x, h->conv[i], y, T, T);
+        vae::GemmLaunch a = gemm(x, h->conv[i], y, T, T, 0, 0);
         a.dil = 1 << (i % 4); a.pad_left = a.dil * (a.ks - 1) / 2; a.gelu = 1;
         a.film = ws + w.film; a.ld_film = h->film_cols; a.gamma_off = i * 2 * C; a.beta_off = i * 2 * C + C;
         a.wp2 = (const f32x4*)(blob + h->res[i].w_off); a.bias2 = blob + h->res[i].b_off; a.res = x;
@@ -131,14 +142,15 @@ int enc_forward(iris_vae_encoder_handle* h, const float* mel, const float* cond,
     }
     for (int s = 0; s < S; ++s) {                                                            // lat_h = downsample(h), vae.py:393
         float* y = ws + w.d[s & 1];
-        vae::GemmLaunch a = gemm(x, h->down[s], y, T >> s, T >> (s + 1));
+        vae::GemmLaunch a = gemm(x, h->down[s], y, T >> s, T >> (s + 1), s, s + 1);
         a.stride = 2; a.pad_left = 1; a.gelu = 1;
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
         x = y;
     }
     {   // mean | logvar = latent_mean_proj(lat_h) | latent_logvar_proj(lat_h)                vae.py:396-397
-        vae::GemmLaunch a = gemm(x, h->heads, mean, Tq, Tq);
+        vae::GemmLaunch a = gemm(x, h->heads, mean, Tq, Tq, S, S);
         a.y2 = logvar; a.split = c.latent_dim;
+        a.zero_tail = 1;                                                                    // ragged: mean | logvar [b, len_b >> S:] = 0
         HIP_TRY(vae::launch_gemm(a, B, false, stream, vae::kGemmSplitOut));
     }
     return IRIS_HIFIGAN_OK;
@@ -224,17 +236,73 @@ int32_t iris_vae_encoder_tap(const iris_vae_encoder_handle* h, int32_t B, int32_
     return IRIS_HIFIGAN_OK;
 }
 
-int32_t iris_vae_encoder_forward(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
-                                 float* mean_out_dev, float* logvar_out_dev, void* workspace_dev, uint64_t workspace_bytes,
-                                 void* stream_) {
+// The dense and the ragged entry point: the same checks in the same order, then the same plan.
+static int32_t enc_forward_checked(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
+                                   bool ragged, const int32_t* lengths_dev, float* mean_out_dev, float* logvar_out_dev,
+                                   void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
     IRIS_ABI_BEGIN
     TRY(enc_check_shape(h, B, T));
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     if (!mel_dev || !cond_dev || !mean_out_dev || !logvar_out_dev || !workspace_dev)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (ragged && !lengths_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lengths_dev is NULL");
     ForwardScope scope(*h, workspace_bytes, enc_ws(h, B, T).total);
     TRY(scope.rc);
-    return enc_forward(h, mel_dev, cond_dev, B, T, mean_out_dev, logvar_out_dev, (float*)workspace_dev, (hipStream_t)stream_);
+    return enc_forward(h, mel_dev, cond_dev, B, T, ragged ? lengths_dev : nullptr, mean_out_dev, logvar_out_dev,
+                       (float*)workspace_dev, (hipStream_t)stream_);
+    IRIS_ABI_END
+}
+
+int32_t iris_vae_encoder_forward(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
+                                 float* mean_out_dev, float* logvar_out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                 void* stream_) {
+    return enc_forward_checked(h, mel_dev, cond_dev, B, T, false, nullptr, mean_out_dev, logvar_out_dev, workspace_dev,
+                               workspace_bytes, stream_);
+}
+
+int32_t iris_vae_posterior_encode_ragged(iris_vae_encoder_handle* h, const float* mel_dev, const float* cond_dev, int32_t B, int32_t T,
+                                        const int32_t* lengths_dev, float* mean_out_dev, float* logvar_out_dev, void* workspace_dev,
+                                        uint64_t workspace_bytes, void* stream_) {
+    return enc_forward_checked(h, mel_dev, cond_dev, B, T, true, lengths_dev, mean_out_dev, logvar_out_dev, workspace_dev,
+                               workspace_bytes, stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Masked reconstruction L1 and KL of a reconstruction (csrc/vae_losses.h)
+// ------------------------------------------------------------------------------------------------
+static int losses_check_shape(int32_t B, int32_t n_mels, int32_t T, int32_t latent_dim, int32_t down_stages) {
+    if (B < 0 || T < 0 || n_mels < 1 || latent_dim < 1 || down_stages < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad loss shape");
+    if (down_stages > 8) return fail(IRIS_HIFIGAN_UNSUPPORTED, "down_stages <= 8");
+    if (T & ((1 << down_stages) - 1))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "T = %d is not a multiple of 2^down_stages = %d", T, 1 << down_stages);
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    if ((uint64_t)B * T * (uint64_t)(n_mels > latent_dim ? n_mels : latent_dim) > 0x7fffffffull * 64)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "B * T too large");
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_losses_workspace_bytes(int32_t B, int32_t n_mels, int32_t T, int32_t latent_dim, int32_t down_stages, uint64_t* bytes) {
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    TRY(losses_check_shape(B, n_mels, T, latent_dim, down_stages));
+    *bytes = vae::loss_workspace_doubles(B, T, down_stages, latent_dim) * sizeof(double);
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_vae_losses(const float* target_dev, const float* recon_dev, const float* mean_dev, const float* logvar_dev, int32_t B,
+                        int32_t n_mels, int32_t T, int32_t latent_dim, int32_t down_stages, const int32_t* lengths_dev,
+                        float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(losses_check_shape(B, n_mels, T, latent_dim, down_stages));
+    const uint64_t need = vae::loss_workspace_doubles(B, T, down_stages, latent_dim) * sizeof(double);
+    if (!out_dev || (need && !workspace_dev) || (B > 0 && T > 0 && (!target_dev || !recon_dev || !mean_dev || !logvar_dev)))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if ((uintptr_t)workspace_dev & 7) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "workspace_dev must be aligned to 8 bytes");
+    TRY(ForwardScope::check_workspace(workspace_bytes, need));
+    vae::LossLaunch a; memset(&a, 0, sizeof(a));
+    a.target = target_dev; a.recon = recon_dev; a.mean = mean_dev; a.logvar = logvar_dev; a.lengths = lengths_dev; a.out = out_dev;
+    a.B = B; a.n_mels = n_mels; a.T = T; a.latent = latent_dim; a.S = down_stages;
+    HIP_TRY(vae::launch_losses(a, (double*)workspace_dev, (hipStream_t)stream_));
+    return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 
@@ -245,7 +313,7 @@ int32_t iris_vae_encoder_launch_count(const iris_vae_encoder_handle* h, int32_t 
     *n = 0;
     if (B == 0 || T == 0) return IRIS_HIFIGAN_OK;
     return count_launches([&](float* fake) {
-        return enc_forward(const_cast<iris_vae_encoder_handle*>(h), fake, fake, B, T, fake, fake, fake, nullptr); }, n);
+        return enc_forward(const_cast<iris_vae_encoder_handle*>(h), fake, fake, B, T, nullptr, fake, fake, fake, nullptr); }, n);
     IRIS_ABI_END
 }
 

@@ -35,6 +35,11 @@
 // therefore runs the dense form's loads, MFMAs and FMAs in the dense form's order: bit for bit the batch-of-one result.
 // A block whose rows all lie past its item's length returns before its first barrier; the two output launches store 0.0f
 // there instead (zero_tail).  The dense instantiations contain none of this.
+//
+// The posterior side is ragged in the same way (iris_vae_posterior_encode_ragged, iris_vae_decoder_forward_posterior_ragged):
+// the kGemmMelIn staging loop is bounded by the item's frames, the kGemmSplitOut launch stores mean | logvar rows past the
+// item's latent rows as 0.0f (a padded latent row then adds exactly 0 to the KL sum of vae_losses.h), and the FORWARD flow
+// takes the RAGGED bound like the reverse one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,12 +96,21 @@ __device__ __forceinline__ int item_frames(const int32_t* __restrict__ lengths, 
     return (len >> S) << S;
 }
 
-// zero_tail: row t of item b (t < L_out, past the item's rows) of this wave's C_out tile as 0.0f, in y's layout
+// zero_tail: row t of item b (t < L_out, past the item's rows) of this wave's C_out tile as 0.0f, in y's layout (FORM ==
+// kGemmSplitOut: in the layout of the y | y2 pair)
+template <int FORM>
 __device__ __forceinline__ void store_zero_row(const GemmLaunch& a, int b, int ct, int t, int hi) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int co = ct * 32 + 8 * g + 4 * hi;
-        if (a.y_channels_first) {
+        if constexpr (FORM == kGemmSplitOut) {
+            if (co < a.C_out) {                            // split % 4 == 0: the group lies on one side of it
+                const size_t row = (size_t)b * a.L_out + t;
+                const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+                float* dst = co < a.split ? a.y + row * a.split + co : a.y2 + row * (a.C_out - a.split) + (co - a.split);
+                *reinterpret_cast<f32x4*>(dst) = zero;
+            }
+        } else if (a.y_channels_first) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (co + e < a.C_out) a.y[((size_t)b * a.C_out + co + e) * a.L_out + t] = 0.f;
@@ -136,7 +150,7 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
         Lb_in = len >> a.sh_in;
         Lb_out = len >> a.sh_out;
         if (i0 >= Lb_out) {                                // block-uniform, before the first barrier
-            if (!FUSED && a.zero_tail && active && i0 + lo < a.L_out) store_zero_row(a, b, ct, i0 + lo, hi);
+            if (!FUSED && a.zero_tail && active && i0 + lo < a.L_out) store_zero_row<FORM>(a, b, ct, i0 + lo, hi);
             return;
         }
     }
@@ -278,7 +292,7 @@ __global__ void __launch_bounds__(64 * kGemmMaxWaves) vae_gemm_kernel(const Gemm
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (RAGGED) {
-            if (a.zero_tail && active && t >= Lb_out && t < a.L_out) store_zero_row(a, b, ct, t, hi);
+            if (a.zero_tail && active && t >= Lb_out && t < a.L_out) store_zero_row<FORM>(a, b, ct, t, hi);
         }
     }
 }
@@ -399,13 +413,17 @@ inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stre
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     dim3 grid((unsigned)((a.L_out + kGemmRows - 1) / kGemmRows), (unsigned)((a.n_ct + nw - 1) / nw), (unsigned)B);
     dim3 block((unsigned)(64 * nw));
-    if (form != kGemmPlain) {                              // dense, unfused forms of the posterior encoder
-        if (fused || a.lengths || a.up || a.y_channels_first) return hipErrorInvalidValue;
+    if (form != kGemmPlain) {                              // unfused forms of the posterior encoder
+        if (fused || a.up || a.y_channels_first) return hipErrorInvalidValue;
         if (form == kGemmMelIn) {
             if (a.ks != 1 || a.stride != 1 || a.pad_left != 0) return hipErrorInvalidValue;
+            if (a.lengths)
+                return launch_kernel_named("vae_gemm_kernel_ragged<mel_in>", vae_gemm_kernel<false, true, kGemmMelIn>, grid, block, lds_bytes, stream, a);
             return launch_kernel_named("vae_gemm_kernel<mel_in>", vae_gemm_kernel<false, false, kGemmMelIn>, grid, block, lds_bytes, stream, a);
         }
         if (form != kGemmSplitOut || !a.y2 || a.split <= 0 || a.split >= a.C_out || (a.split & 3)) return hipErrorInvalidValue;
+        if (a.lengths)
+            return launch_kernel_named("vae_gemm_kernel_ragged<split_out>", vae_gemm_kernel<false, true, kGemmSplitOut>, grid, block, lds_bytes, stream, a);
         return launch_kernel_named("vae_gemm_kernel<split_out>", vae_gemm_kernel<false, false, kGemmSplitOut>, grid, block, lds_bytes, stream, a);
     }
     if (a.lengths) {
@@ -418,8 +436,9 @@ inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stre
 
 inline hipError_t launch_flow(const FlowLaunch& a, int B, hipStream_t stream, bool forward = false) {
     dim3 grid((unsigned)((a.Tq + kFlowRows - 1) / kFlowRows), (unsigned)B), block(256);
-    if (forward) {                                         // the posterior decode is dense
-        if (a.lengths) return hipErrorInvalidValue;
+    if (forward) {
+        if (a.lengths)
+            return launch_kernel_named("vae_flow_kernel_ragged<forward>", vae_flow_kernel<true, true>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
         return launch_kernel_named("vae_flow_kernel<forward>", vae_flow_kernel<false, true>, grid, block, flow_lds_bytes(a.latent, a.FH), stream, a);
     }
     if (a.lengths)

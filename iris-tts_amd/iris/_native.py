@@ -193,6 +193,7 @@ VAE_SYMBOLS = {
     "iris_vae_decoder_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_forward_ragged": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_forward_posterior": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_vae_decoder_forward_posterior_ragged": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "iris_vae_decoder_launch_count": (_i32, [_vp, _i32, _i32, _ip]),
     "iris_vae_decoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
 }
@@ -218,6 +219,17 @@ VAE_ENCODER_SYMBOLS = {
     "iris_vae_encoder_tap": (_i32, [_vp, _i32, _i32, _i32, _u64p, _u64p]),
 }
 
+# the ragged forward of the posterior encoder (iris.vae: encode_device(lengths=)): bound by load() like SYMBOLS.  It takes an
+# iris_vae_encoder handle but is named outside the iris_vae_encoder_* family, which keeps its seven functions.
+VAE_POSTERIOR_SYMBOLS = {
+    "iris_vae_posterior_encode_ragged": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
+# the masked VAE losses (iris.vae.vae_losses): bound by load() like SYMBOLS
+VAE_LOSSES_SYMBOLS = {
+    "iris_vae_losses_workspace_bytes": (_i32, [_i32, _i32, _i32, _i32, _i32, _u64p]),
+    "iris_vae_losses": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+}
 
 
 class PhonemeEncoderConfig(ctypes.Structure):
@@ -278,7 +290,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **TEXT_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

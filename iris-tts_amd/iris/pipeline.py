@@ -128,9 +128,18 @@ class MelToWavePipeline:
         """Copy-synthesis: a recorded mel ``[B, n_mels, T]`` and its frame conditioning ``[B, T, cond_dim]`` -> what ``infer``
         returns for the VAE's reconstruction of it (``iris.vae.reconstruct``: posterior encoder, forward flow, decoder), all
         on one stream -- what the acoustic model loses, heard apart from what the text side loses.  ``**kw`` goes to
-        ``infer`` (``pcm16``, ``normalize``, ``resampler``)."""
+        ``infer`` (``pcm16``, ``normalize``, ``resampler``).
+
+        A sequence of mels ``[n_mels, T_i]`` with a sequence of conditionings ``[T_i, cond_dim]``: utterances of different
+        lengths, packed and reconstructed in ONE ragged ``reconstruct(..., lengths=)``, whose mel then goes on the way
+        ``infer_from_phonemes`` hands a batch on -- ``infer_batch`` over slices of it, one ragged PostNet pass and one ragged
+        vocoder forward.  The result is a list, item i bit for bit ``resynthesize(mel[i][None], frame_cond[i][None])[0]``.
+        Every ``T_i`` must be a multiple of ``acoustic.downsample_factor`` (``ValueError``; nothing is padded silently).  A
+        posterior that is a plain callable gets the items one by one instead."""
         if self.posterior is None:
             raise ValueError("resynthesize needs a posterior encoder: construct the pipeline with posterior=VAEPosteriorEncoder(...)")
+        if isinstance(mel, (list, tuple)):
+            return self._resynthesize_batch(list(mel), list(frame_cond), **kw)
         if hasattr(self.posterior, "encode_device"):
             if self.acoustic is None:
                 raise ValueError("resynthesize needs the decoder too: construct the pipeline with acoustic=TextConditionedVAE(...)")
@@ -142,6 +151,37 @@ class MelToWavePipeline:
         else:
             recon = self.posterior(mel, frame_cond)[0]
         return self.infer(recon, **kw)
+
+    def _resynthesize_batch(self, mels: list, conds: list, **kw) -> List[torch.Tensor]:
+        """``resynthesize`` of a list: shapes are checked on the host, then one ragged ``reconstruct`` and ``infer_batch``."""
+        if len(mels) != len(conds):
+            raise ValueError(f"{len(mels)} mels but {len(conds)} conditionings")
+        if not mels:
+            return []
+        ragged = hasattr(self.posterior, "encode_device")
+        if ragged and self.acoustic is None:
+            raise ValueError("resynthesize needs the decoder too: construct the pipeline with acoustic=TextConditionedVAE(...)")
+        factor = int(getattr(self.acoustic, "downsample_factor", 1))
+        conds = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c, dtype=np.float32)))
+                 for c in conds]
+        for i, (m, c) in enumerate(zip(mels, conds)):
+            if len(m.shape) != 2 or c.dim() != 2 or c.shape[0] != m.shape[1] or c.shape[1] != conds[0].shape[1]:
+                raise ValueError(f"item {i}: expected a mel [n_mels, T] and a conditioning [T, cond_dim], got "
+                                 f"{tuple(m.shape)} and {tuple(c.shape)}")
+            if m.shape[1] % factor:
+                raise ValueError(f"item {i}: T = {m.shape[1]} is not a multiple of 2^down_stages = {factor}: pad the mel and "
+                                 "the conditioning first; nothing is padded silently")
+        if not ragged:
+            recons = [self.posterior(self._to_device(torch.as_tensor(m)[None]), c[None])[0][0] for m, c in zip(mels, conds)]
+            return self.infer_batch(recons, **kw)
+        from .vae import reconstruct
+        padded, lengths = pack_mels(mels)
+        padded = self._to_device(padded)
+        cond = torch.zeros((len(conds), padded.shape[2], conds[0].shape[1]), dtype=torch.float32, device=padded.device)
+        for i, c in enumerate(conds):
+            cond[i, :c.shape[0]] = c.to(device=cond.device, dtype=torch.float32)
+        recon = reconstruct(self.posterior, self.acoustic, padded, cond, lengths=lengths)[0]
+        return self.infer_batch([recon[i, :, :int(n)] for i, n in enumerate(lengths)], **kw)
 
     def infer_from_phonemes(self, ids, lengths=None, durations=None, z_prior=None, **kw):
         """Phoneme ids ``[B, P]`` -> ``(what infer returns, frames_per_item)``: phoneme encoder, duration head and length

@@ -7,7 +7,9 @@ flow_layers=4, flow_hidden=64, dropout=0.1, name=None)`` (:263-351) and ``genera
 the PostNet.  ``TextConditionedVAE`` holds the decoder half only: its ``__call__`` raises, and encoder-side keys in a
 weight file are ignored by it.  The encoder half (``in_proj``, ``enc_blocks``, ``latent_*_proj``) is
 ``VAEPosteriorEncoder``, and ``reconstruct(encoder, vae, mels, frame_text_cond)`` is the reference's
-``call(training=False)`` (:366-422) over the two: posterior statistics, forward flow, decoded reconstruction.
+``call(training=False)`` (:366-422) over the two: posterior statistics, forward flow, decoded reconstruction -- with
+``lengths=`` over a ragged batch of recorded utterances in one pass, and with ``losses=True`` followed by ``vae_losses``,
+the masked ``compute_recon_l1`` / ``compute_kl`` (:424-446) reduced on the device.
 
     h = in_proj(mels^T)                                 # the mel arrives channels-first [B, n_mels, T]           :382-385
     for i, block in enumerate(enc_blocks):              # WaveNetResBlock, dilation 2^(i % 4), FiLM on frame_cond :388-389
@@ -57,6 +59,35 @@ import torch
 
 from . import _native
 from ._native_model import _NativeModel, _ptr, _stream
+
+
+def check_lengths(lengths, B: int, T: int, factor: int):
+    """``lengths`` of a ragged call -> an int32 device tensor, passed through unread, or a validated int32 host array.
+    Host lengths are checked here, before any device work; a device tensor is sanitised by the kernels instead."""
+    if isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu":
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError(f"device lengths must be an int32 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        return lengths
+    arr = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
+    if arr.ndim != 1 or arr.shape[0] != B:
+        raise ValueError(f"lengths must hold {B} frame counts (one per item), got shape {tuple(arr.shape)}")
+    if arr.size and not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"lengths must be integers, got {arr.dtype}")
+    arr = arr.astype(np.int64)
+    for b, n in enumerate(arr.tolist()):
+        if not 0 <= n <= T:
+            raise ValueError(f"lengths[{b}] = {n} is outside [0, T = {T}]")
+        if n % factor:
+            raise ValueError(f"lengths[{b}] = {n} is not a multiple of 2^down_stages = {factor}: pad the "
+                             "item first; nothing is padded silently")
+    return arr.astype(np.int32)
+
+
+def _lengths_on(lengths, device) -> torch.Tensor:
+    """What ``check_lengths`` returned, as a contiguous int32 tensor on ``device``."""
+    if not isinstance(lengths, torch.Tensor):
+        lengths = torch.from_numpy(lengths)
+    return lengths.to(device).contiguous()
 
 
 class TextConditionedVAE(_NativeModel):
@@ -169,25 +200,8 @@ class TextConditionedVAE(_NativeModel):
         return B, T
 
     def _check_lengths(self, lengths, B: int, T: int):
-        """``lengths`` of a ragged call -> an int32 device tensor, passed through unread, or a validated int32 host array.
-        Host lengths are checked here, before any device work; a device tensor is sanitised by the kernels instead."""
-        if isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu":
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
-                raise ValueError(f"device lengths must be an int32 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
-            return lengths
-        arr = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
-        if arr.ndim != 1 or arr.shape[0] != B:
-            raise ValueError(f"lengths must hold {B} frame counts (one per item), got shape {tuple(arr.shape)}")
-        if arr.size and not np.issubdtype(arr.dtype, np.integer):
-            raise ValueError(f"lengths must be integers, got {arr.dtype}")
-        arr = arr.astype(np.int64)
-        for b, n in enumerate(arr.tolist()):
-            if not 0 <= n <= T:
-                raise ValueError(f"lengths[{b}] = {n} is outside [0, T = {T}]")
-            if n % self.downsample_factor:
-                raise ValueError(f"lengths[{b}] = {n} is not a multiple of 2^down_stages = {self.downsample_factor}: pad the "
-                                 "item's conditioning first; nothing is padded silently")
-        return arr.astype(np.int32)
+        """``check_lengths`` with this model's ``2^down_stages``."""
+        return check_lengths(lengths, B, T, self.downsample_factor)
 
     def launch_count(self, B: int, T: int) -> int:
         """Kernel launches of one ``generate_device(..., want_residual=True)`` (one fewer without the residual)."""
@@ -230,9 +244,7 @@ class TextConditionedVAE(_NativeModel):
         if lengths is None:
             _native.check("iris_vae_decoder_forward", lib.iris_vae_decoder_forward(self._handle, _ptr(cond), _ptr(z_prior), B, T, *out))
             return mel, residual
-        if not isinstance(lengths, torch.Tensor):
-            lengths = torch.from_numpy(lengths)
-        lengths = lengths.to(self._device).contiguous()
+        lengths = _lengths_on(lengths, self._device)
         _native.check("iris_vae_decoder_forward_ragged", lib.iris_vae_decoder_forward_ragged(
             self._handle, _ptr(cond), _ptr(z_prior), B, T, _ptr(lengths), *out))
         return mel, residual
@@ -251,11 +263,14 @@ class TextConditionedVAE(_NativeModel):
         mel, residual = self.generate_device(torch.from_numpy(cond).to(self._device), z, True, generator, lengths)
         return mel.cpu().numpy(), residual.cpu().numpy()
 
-    def decode_posterior_device(self, cond: torch.Tensor, z: torch.Tensor, want_residual: bool = True):
+    def decode_posterior_device(self, cond: torch.Tensor, z: torch.Tensor, want_residual: bool = True, lengths=None):
         """The decoder half of the reference's ``call(training=False)`` (vae.py:401-422): ``z [B, T / 2^S, latent_dim]`` is a
         posterior latent (``VAEPosteriorEncoder.encode_device``'s mean) and the flow runs forwards; shapes, outputs and
-        launches are ``generate_device``'s (``iris_vae_decoder_forward_posterior``)."""
+        launches are ``generate_device``'s (``iris_vae_decoder_forward_posterior``), and so is ``lengths``
+        (``iris_vae_decoder_forward_posterior_ragged``)."""
         B, T = self._check_cond(tuple(cond.shape))
+        if lengths is not None:
+            lengths = self._check_lengths(lengths, B, T)
         Tq = T // self.downsample_factor
         if tuple(z.shape) != (B, Tq, self.latent_dim):
             raise ValueError(f"expected z [{B}, {Tq}, {self.latent_dim}], got {tuple(z.shape)}")
@@ -267,9 +282,14 @@ class TextConditionedVAE(_NativeModel):
         if B == 0 or T == 0:
             return mel, residual
         ws = self._ws(B, T)
-        _native.check("iris_vae_decoder_forward_posterior", lib.iris_vae_decoder_forward_posterior(
-            self._handle, _ptr(cond), _ptr(z), B, T, _ptr(mel), _ptr(residual), _ptr(ws), ctypes.c_uint64(ws.numel()),
-            _stream(self._device)))
+        out = (_ptr(mel), _ptr(residual), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device))
+        if lengths is None:
+            _native.check("iris_vae_decoder_forward_posterior", lib.iris_vae_decoder_forward_posterior(
+                self._handle, _ptr(cond), _ptr(z), B, T, *out))
+            return mel, residual
+        lengths = _lengths_on(lengths, self._device)
+        _native.check("iris_vae_decoder_forward_posterior_ragged", lib.iris_vae_decoder_forward_posterior_ragged(
+            self._handle, _ptr(cond), _ptr(z), B, T, _ptr(lengths), *out))
         return mel, residual
 
     def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:
@@ -296,6 +316,9 @@ class VAEPosteriorEncoder(_NativeModel):
     ``latent_mean_proj.*``, ``latent_logvar_proj.*``.  One full-checkpoint ``.npz`` loads into both classes."""
 
     _abi_name = "vae_encoder"
+
+    #: ``encode`` / ``encode_device`` take ``lengths=`` (a ragged batch in one forward)
+    takes_lengths = True
 
     def __init__(self, n_mels: int, cond_dim: int, model_channels: int = 192, latent_dim: int = 16,
                  num_wavenet_blocks: int = 8, wavenet_kernel_size: int = 5, down_stages: int = 2,
@@ -380,10 +403,18 @@ class VAEPosteriorEncoder(_NativeModel):
         _native.check("iris_vae_encoder_launch_count", lib.iris_vae_encoder_launch_count(self._handle, B, T, ctypes.byref(n)))
         return int(n.value)
 
-    def encode_device(self, mel: torch.Tensor, cond: torch.Tensor):
+    def encode_device(self, mel: torch.Tensor, cond: torch.Tensor, lengths=None):
         """``mel [B, n_mels, T]`` (channels-first, read as it lies), ``cond [B, T, cond_dim]`` (fp32 device tensors) ->
-        ``(mean, logvar)``, ``[B, T / 2^S, latent_dim]`` each, asynchronous on the current stream.  Neither input is written."""
+        ``(mean, logvar)``, ``[B, T / 2^S, latent_dim]`` each, asynchronous on the current stream.  Neither input is written.
+
+        ``lengths`` (``B`` frame counts, under ``TextConditionedVAE.generate_device``'s rules: a validated host sequence, or
+        an int32 device tensor the host never reads) makes the batch ragged in ONE forward
+        (``iris_vae_posterior_encode_ragged``): item b is bit for bit the batch-of-one call on ``mel[b:b+1, :, :lengths[b]]``
+        and ``cond[b:b+1, :lengths[b]]``, frames past an item's length are never read, and ``mean`` / ``logvar`` rows from
+        ``lengths[b] / 2^S`` on are 0."""
         B, T = self._check_inputs(tuple(mel.shape), tuple(cond.shape))
+        if lengths is not None:
+            lengths = check_lengths(lengths, B, T, self.downsample_factor)
         lib = self._ensure()
         mel = mel.to(device=self._device, dtype=torch.float32).contiguous()
         cond = cond.to(device=self._device, dtype=torch.float32).contiguous()
@@ -393,20 +424,27 @@ class VAEPosteriorEncoder(_NativeModel):
         if B == 0 or T == 0:
             return mean, logvar
         ws = self._ws(B, T)
-        _native.check("iris_vae_encoder_forward", lib.iris_vae_encoder_forward(
-            self._handle, _ptr(mel), _ptr(cond), B, T, _ptr(mean), _ptr(logvar), _ptr(ws), ctypes.c_uint64(ws.numel()),
-            _stream(self._device)))
+        out = (_ptr(mean), _ptr(logvar), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device))
+        if lengths is None:
+            _native.check("iris_vae_encoder_forward", lib.iris_vae_encoder_forward(self._handle, _ptr(mel), _ptr(cond), B, T, *out))
+            return mean, logvar
+        lengths = _lengths_on(lengths, self._device)
+        _native.check("iris_vae_posterior_encode_ragged", lib.iris_vae_posterior_encode_ragged(
+            self._handle, _ptr(mel), _ptr(cond), B, T, _ptr(lengths), *out))
         return mean, logvar
 
-    def encode(self, mels, frame_text_cond):
-        """numpy in -> numpy out, device tensors in -> device tensors out."""
+    def encode(self, mels, frame_text_cond, lengths=None):
+        """numpy in -> numpy out, device tensors in -> device tensors out.  ``lengths``: a ragged batch, as in
+        ``encode_device``."""
         if isinstance(mels, torch.Tensor):
-            return self.encode_device(mels, frame_text_cond)
+            return self.encode_device(mels, frame_text_cond, lengths)
         mels = np.ascontiguousarray(np.asarray(mels, dtype=np.float32))
         cond = np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32))
-        self._check_inputs(mels.shape, cond.shape)
+        B, T = self._check_inputs(mels.shape, cond.shape)
+        if lengths is not None:
+            lengths = check_lengths(lengths, B, T, self.downsample_factor)
         self._ensure()
-        mean, logvar = self.encode_device(torch.from_numpy(mels).to(self._device), torch.from_numpy(cond).to(self._device))
+        mean, logvar = self.encode_device(torch.from_numpy(mels).to(self._device), torch.from_numpy(cond).to(self._device), lengths)
         return mean.cpu().numpy(), logvar.cpu().numpy()
 
     def _read_tap(self, which: int, B: int, T: int) -> torch.Tensor:
@@ -435,22 +473,96 @@ def check_pair(encoder: VAEPosteriorEncoder, vae: TextConditionedVAE) -> None:
                                  "load both halves from the same checkpoint")
 
 
-def reconstruct(encoder: VAEPosteriorEncoder, vae: TextConditionedVAE, mels, frame_text_cond):
+_losses_ws = {}                                         # device -> the loss reduction's workspace, grown on demand
+
+
+def vae_losses(target, recon, mean, logvar, down_stages: int, lengths=None):
+    """The reference's ``compute_recon_l1(target, recon, mask)`` and ``compute_kl(mean, logvar, mask[:, ::2^S])``
+    (vae.py:424-446, scripts/train_vae.py:94-103) with the mask given as ``lengths`` -> ``(recon_l1, kl, per_item_l1_sum
+    [B], per_item_kl_sum [B])``.  ``target`` / ``recon`` ``[B, n_mels, T]``, ``mean`` / ``logvar`` ``[B, T / 2^S, latent]``.
+
+    ``recon_l1 = sum |target - recon| over t < lengths[b]  /  (sum(lengths) * n_mels + 1e-6)`` and ``kl = sum -0.5 (1 + logvar -
+    mean^2 - exp(logvar)) over latent rows < lengths[b] / 2^S  /  (sum(lengths / 2^S) + 1e-8)`` -- rows, not rows x channels, as
+    the reference has it; ``lengths=None`` gives the plain means.  ``lengths`` follows ``generate_device``'s rules; nothing
+    past an item's length is read.  One reduction on the device (``iris_vae_losses``): fp32 terms, fp64 sums in a fixed
+    order, so two calls agree bit for bit and an item's sums do not depend on the batch around it.
+
+    Device tensors in -> device tensors out (``recon_l1`` and ``kl`` 0-d), asynchronous on the current stream, nothing is
+    synchronised; numpy in -> two floats and two numpy arrays."""
+    on_host = not isinstance(target, torch.Tensor)
+    if on_host:
+        target, recon, mean, logvar = (torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
+                                       for a in (target, recon, mean, logvar))
+    if target.dim() != 3 or tuple(recon.shape) != tuple(target.shape):
+        raise ValueError(f"expected target and recon [B, n_mels, T], got {tuple(target.shape)} and {tuple(recon.shape)}")
+    B, n_mels, T = (int(v) for v in target.shape)
+    factor = 2 ** int(down_stages)
+    if T % factor:
+        raise ValueError(f"T = {T} is not a multiple of 2^down_stages = {factor}")
+    if mean.dim() != 3 or tuple(mean.shape[:2]) != (B, T // factor) or tuple(logvar.shape) != tuple(mean.shape):
+        raise ValueError(f"expected mean and logvar [{B}, {T // factor}, latent], got {tuple(mean.shape)} and {tuple(logvar.shape)}")
+    latent = int(mean.shape[2])
+    if lengths is not None:
+        lengths = check_lengths(lengths, B, T, factor)
+    lib = _native.load()
+    if on_host:
+        from ._engine import require_gpu
+        device = require_gpu()
+    else:
+        device = target.device
+        if device.type != "cuda":
+            raise ValueError("vae_losses reduces on the device: pass device tensors, or numpy arrays")
+    target, recon, mean, logvar = (a.to(device=device, dtype=torch.float32).contiguous() for a in (target, recon, mean, logvar))
+    if lengths is not None:
+        lengths = _lengths_on(lengths, device)
+    need = ctypes.c_uint64()
+    _native.check("iris_vae_losses_workspace_bytes",
+                  lib.iris_vae_losses_workspace_bytes(B, n_mels, T, latent, int(down_stages), ctypes.byref(need)))
+    ws = _losses_ws.get(device)
+    if ws is None or ws.numel() < need.value:
+        ws = _losses_ws[device] = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=device)
+    out = torch.empty(2 + 2 * B, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _native.check("iris_vae_losses", lib.iris_vae_losses(
+            _ptr(target), _ptr(recon), _ptr(mean), _ptr(logvar), B, n_mels, T, latent, int(down_stages), _ptr(lengths), _ptr(out),
+            _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(device)))
+    result = (out[0], out[1], out[2:2 + B], out[2 + B:])
+    if on_host:
+        host = out.cpu().numpy()
+        return float(host[0]), float(host[1]), host[2:2 + B].copy(), host[2 + B:].copy()
+    return result
+
+
+def reconstruct(encoder: VAEPosteriorEncoder, vae: TextConditionedVAE, mels, frame_text_cond, lengths=None, losses: bool = False):
     """The reference's ``TextConditionedVAE.call(mels, frame_text_cond, training=False)`` (vae.py:366-422) ->
     ``(recon [B, n_mels, T], (mean, logvar), residual [B, T, cond_dim])``: ``encode_device`` then
     ``decode_posterior_device(cond, mean)`` on the current stream, nothing returning to the host in between.  numpy in ->
-    numpy out, device tensors in -> device tensors out."""
+    numpy out, device tensors in -> device tensors out.
+
+    ``lengths`` (``generate_device``'s rules): the batch is ragged and both calls are the ragged ones, on one stream -- item b
+    is bit for bit the call on its own ``lengths[b]`` frames, and everything past them is 0 in all four outputs.
+    ``losses=True`` appends ``vae_losses(mels, recon, mean, logvar, down_stages, lengths)`` -- ``(recon_l1, kl,
+    per_item_l1_sum, per_item_kl_sum)`` -- to the returned tuple."""
     check_pair(encoder, vae)
     on_host = not isinstance(mels, torch.Tensor)
     if on_host:
         mels = torch.from_numpy(np.ascontiguousarray(np.asarray(mels, dtype=np.float32)))
         frame_text_cond = torch.from_numpy(np.ascontiguousarray(np.asarray(frame_text_cond, dtype=np.float32)))
-    encoder._check_inputs(tuple(mels.shape), tuple(frame_text_cond.shape))
+    B, T = encoder._check_inputs(tuple(mels.shape), tuple(frame_text_cond.shape))
+    if lengths is not None:
+        lengths = check_lengths(lengths, B, T, encoder.downsample_factor)
     if on_host:
         encoder._ensure()
         mels, frame_text_cond = mels.to(encoder._device), frame_text_cond.to(encoder._device)
-    mean, logvar = encoder.encode_device(mels, frame_text_cond)
-    recon, residual = vae.decode_posterior_device(frame_text_cond, mean)
+    if lengths is not None:
+        encoder._ensure()
+        lengths = _lengths_on(lengths, encoder._device)                               # one upload for both calls and the losses
+    mean, logvar = encoder.encode_device(mels, frame_text_cond, lengths)
+    recon, residual = vae.decode_posterior_device(frame_text_cond, mean, lengths=lengths)
+    loss = vae_losses(mels.to(recon.device), recon, mean, logvar, encoder.down_stages, lengths) if losses else None
     if on_host:
-        return recon.cpu().numpy(), (mean.cpu().numpy(), logvar.cpu().numpy()), residual.cpu().numpy()
-    return recon, (mean, logvar), residual
+        recon, mean, logvar, residual = (t.cpu().numpy() for t in (recon, mean, logvar, residual))
+        if losses:
+            loss = (float(loss[0]), float(loss[1]), loss[2].cpu().numpy(), loss[3].cpu().numpy())
+    out = (recon, (mean, logvar), residual)
+    return out + (loss,) if losses else out

@@ -4,10 +4,17 @@
 same weights) on the same GPU.
 
     python tools/vae_posterior_bench.py [--shapes 1x1024 8x1024] [--iters 100] [--rounds 5] [--out profiles/vae_posterior_bench.json]
+    python tools/vae_posterior_bench.py --ragged [--iters 100] [--rounds 5] [--out profiles/vae_posterior_ragged_bench.json]
 
 Device events around `iters` back-to-back calls, after a warm-up of every shape; the implementations alternate in every
 round and the median round is reported with the spread.  Outputs are compared at the timed shape before timing.  Needs a
 GPU: there is no CPU fallback and no number without one.
+
+--ragged times a validation pass over a batch of 8 recorded utterances of 128, 256, ..., 1024 frames three ways, alternating
+in every round: ONE ragged reconstruct(..., lengths=, losses=True), eight batch-of-one reconstruct(..., losses=True) calls at
+the items' own lengths (what a host loop over the items costs), and the dense 8 x 1024 reconstruct(..., losses=True) (what the
+ragged call's launches cost when every block has work; its numbers are not the items').  Before timing, every item of the
+ragged call is compared with its batch-of-one call bit for bit, the loss sums included.
 """
 from __future__ import annotations
 
@@ -88,22 +95,77 @@ def rel(a, b):
     return float((a - b).abs().max()) / max(1.0, float(b.abs().max()))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", default=["1x1024", "8x1024"])
-    ap.add_argument("--iters", type=int, default=100)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None, help="default: profiles/vae_posterior_bench.json")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("vae_posterior_bench needs a HIP device: nothing is measured without one")
-    dev = torch.device("cuda", 0)
+def make_models():
     vae = TextConditionedVAE(80, 256, seed=1)
     randomise(vae, 101)
     enc = VAEPosteriorEncoder(80, 256, seed=2)
     w = randomise(enc, 303, scale=0.5)                    # half-size kernels: 8 residual blocks at gamma ~ 1 stay O(10)
     w.update({k: v for k, v in vae.weights.items() if k.startswith("downsample.blocks.")})
     enc.set_weights_dict(w)
+    return enc, vae
+
+
+def ragged_main(args, dev):
+    enc, vae = make_models()
+    lengths = [128 * (i + 1) for i in range(8)]
+    B, T, f = len(lengths), max(lengths), vae.downsample_factor
+    g = torch.Generator(device="cpu").manual_seed(B * 1000 + T)
+    mel = torch.randn(B, vae.n_mels, T, generator=g).to(dev)
+    cond = torch.randn(B, T, vae.cond_dim, generator=g).to(dev)
+    lengths_dev = torch.tensor(lengths, dtype=torch.int32, device=dev)
+    items = [(mel[b:b + 1, :, :n].contiguous(), cond[b:b + 1, :n].contiguous()) for b, n in enumerate(lengths)]
+    ragged = lambda: reconstruct(enc, vae, mel, cond, lengths=lengths_dev, losses=True)
+
+    def loop():
+        return [reconstruct(enc, vae, m, c, losses=True) for m, c in items]
+    dense = lambda: reconstruct(enc, vae, mel, cond, losses=True)
+    with torch.no_grad():
+        (recon, (mean, logvar), res, loss), singles = ragged(), loop()
+        for b, n in enumerate(lengths):
+            r1, (m1, l1), s1, loss1 = singles[b]
+            same = (torch.equal(recon[b, :, :n], r1[0]) and torch.equal(res[b, :n], s1[0]) and torch.equal(mean[b, :n // f], m1[0])
+                    and torch.equal(logvar[b, :n // f], l1[0]) and torch.equal(loss[2][b], loss1[2][0]) and torch.equal(loss[3][b], loss1[3][0]))
+            if not same:
+                raise SystemExit(f"item {b}: the ragged call differs from its batch-of-one call")
+            if recon[b, :, n:].any() or res[b, n:].any() or mean[b, n // f:].any() or logvar[b, n // f:].any():
+                raise SystemExit(f"item {b}: rows past its length are not 0")
+        for _ in range(20):
+            ragged(); loop(); dense()
+        rounds = [(time_ms(ragged, args.iters, dev), time_ms(loop, args.iters, dev), time_ms(dense, args.iters, dev))
+                  for _ in range(args.rounds)]
+    r = np.array(rounds)
+    med = np.median(r, axis=0)
+    keys = ("ragged_ms", "loop_of_8_ms", "dense_8x1024_ms")
+    rec = {"lengths": lengths, "T": T, "recon_l1": float(loss[0]), "kl": float(loss[1])}
+    for i, k in enumerate(keys):
+        rec[k] = float(med[i])
+        rec[k + "_min_max"] = [float(r[:, i].min()), float(r[:, i].max())]
+    per_call = lambda Bn, Tn: enc.launch_count(Bn, Tn) + vae.launch_count(Bn, Tn) + 2     # + the two launches of the losses
+    rec.update({"ratio_loop_over_ragged": float(med[1] / med[0]), "ratio_ragged_over_dense": float(med[0] / med[2]),
+                "launches_ragged": per_call(B, T), "launches_loop": sum(per_call(1, n) for n in lengths),
+                "items_bit_for_bit_their_batch_of_one_calls": True, "iters": args.iters, "rounds": args.rounds,
+                "timing": "device events around `iters` back-to-back calls (launch gaps included), median of rounds; "
+                          "the three ways alternate in every round; lengths are a device tensor made once"})
+    print(json.dumps(rec), flush=True)
+    out = Path(args.out or REPO / "profiles" / "vae_posterior_ragged_bench.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps({"gpu": torch.cuda.get_device_name(dev), "results": [rec]}, indent=1) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ragged", action="store_true", help="time the ragged batch of 8 against the loop and the dense call")
+    ap.add_argument("--shapes", nargs="+", default=["1x1024", "8x1024"])
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None, help="default: profiles/vae_posterior_bench.json (vae_posterior_ragged_bench.json with --ragged)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("vae_posterior_bench needs a HIP device: nothing is measured without one")
+    dev = torch.device("cuda", 0)
+    if args.ragged:
+        return ragged_main(args, dev)
+    enc, vae = make_models()
     graph = TorchPosterior(enc, vae, dev)
     results = []
     for shape in args.shapes:
