@@ -667,6 +667,49 @@ int32_t iris_length_scan(const int32_t* frames_dev, const int32_t* lengths_dev, 
 int32_t iris_length_regulate(const float* enc_out_dev, const int32_t* offsets_dev, const int32_t* totals_dev, int32_t B, int32_t P,
                              int32_t E, int32_t T_pad, float* cond_dev, void* stream);
 
+/* ---- Mel front-end: waveform to log-mel in front of the posterior encoder (csrc/mel_frontend.h) --------------------
+ * The reference's compute_mel_spectrogram (src/iris/data.py:25-67): librosa 0.11's melspectrogram(power=1.0) and
+ * log(max(mel, 1e-5)).  audio [B, L] -> mel [B, n_mels, T], T = 1 + L / hop_length, channels-first as every consumer reads it.
+ *   frame t covers samples [t * hop - n_fft / 2, t * hop + n_fft / 2) of its item, 0 outside the item (center=True,
+ *   pad_mode="constant"); periodic Hann of win_length centred in n_fft; magnitudes of bins 0 .. n_fft / 2; Slaney mel scale
+ *   and area normalisation (htk=False, norm="slaney"); fmax <= 0 means sample_rate / 2.
+ * Samples are fp32, or int16 taken as x * (1.0f / 32768) (what a 16-bit WAV reads as): bit for bit the fp32 call on those.
+ * One launch; magnitudes stay in LDS.  hop_length that does not divide n_fft or is no multiple of 4, win_length > n_fft,
+ * n_fft > 4096, and a config whose sample window and magnitude tile exceed 160 KB of LDS return IRIS_HIFIGAN_UNSUPPORTED
+ * (from every function below that takes the config; create reports it before it touches the device); a NULL pointer, a
+ * negative shape and an unknown sample format IRIS_HIFIGAN_INVALID_ARGUMENT; a short workspace
+ * IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches.  audio_dev may be NULL when L == 0 (every item is one frame
+ * of zeros). */
+typedef struct iris_mel_frontend_config {
+    int32_t sample_rate, n_fft, hop_length, win_length, n_mels, reserved;
+    double fmin, fmax;
+} iris_mel_frontend_config;
+typedef struct iris_mel_frontend_handle iris_mel_frontend_handle;
+#define IRIS_MEL_SAMPLES_F32 0
+#define IRIS_MEL_SAMPLES_I16 1
+
+/* Host only (no device is needed).  design: *n_bins = n_fft / 2 + 1 and, where the pointers are not NULL, the fp32 tables
+ * the handle uploads -- dft_host [2][n_bins][n_fft]: w[n] cos(2 pi k n / n_fft), then w[n] sin(2 pi k n / n_fft), evaluated in
+ * double with the angle reduced by (k n) mod n_fft and rounded once; fb_host [n_mels][n_bins].  launch_count: a dry run of the
+ * forward's own code. */
+int32_t iris_mel_frontend_design(const iris_mel_frontend_config* cfg, int32_t* n_bins, float* dft_host, uint64_t dft_floats,
+                                 float* fb_host, uint64_t fb_floats);
+int32_t iris_mel_frontend_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, uint64_t* bytes);
+int32_t iris_mel_frontend_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, int32_t* n);
+/* create: on the current device, which becomes the handle's.  The forwards are asynchronous on `stream`, allocate and copy
+ * nothing, and are safe inside a stream capture. */
+int32_t iris_mel_frontend_create(const iris_mel_frontend_config* cfg, iris_mel_frontend_handle** out);
+int32_t iris_mel_frontend_destroy(iris_mel_frontend_handle* h);
+int32_t iris_mel_frontend_forward(iris_mel_frontend_handle* h, const void* audio_dev, int32_t sample_format, int32_t B, int32_t L,
+                                  float* mel_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+/* Ragged: n_samples_dev [B] int32 on the device, clamped to [0, L] and never read by the host; samples at or past an item's
+ * count read as 0 and are not fetched.  max_frames_dev [B] (or NULL) caps an item's frames: item b has
+ * min(1 + n_b / hop_length, max(max_frames[b], 0)) frames, counted from its own sample 0, which go to frames_out_dev [B];
+ * mel[b, :, frames_b:] is stored as 0.0f.  Item b is bit for bit its batch-of-one dense call. */
+int32_t iris_mel_frontend_forward_ragged(iris_mel_frontend_handle* h, const void* audio_dev, int32_t sample_format, int32_t B, int32_t L,
+                                         const int32_t* n_samples_dev, const int32_t* max_frames_dev /* or NULL */, float* mel_out_dev,
+                                         int32_t* frames_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,29 @@ TEXT_SYMBOLS = {
     "iris_length_regulate": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
+
+
+class MelFrontendConfig(ctypes.Structure):
+    """``iris_mel_frontend_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "n_fft", "hop_length", "win_length", "n_mels", "reserved")] + [
+        ("fmin", ctypes.c_double), ("fmax", ctypes.c_double)]
+
+
+MEL_SAMPLES_F32, MEL_SAMPLES_I16 = 0, 1
+
+# the mel front-end (iris.mel): bound by load() like SYMBOLS
+_mfc = _c.POINTER(MelFrontendConfig)
+MEL_SYMBOLS = {
+    "iris_mel_frontend_design": (_i32, [_mfc, _ip, _fp, _u64, _fp, _u64]),
+    "iris_mel_frontend_workspace_bytes": (_i32, [_mfc, _i32, _i32, _u64p]),
+    "iris_mel_frontend_launch_count": (_i32, [_mfc, _i32, _i32, _ip]),
+    "iris_mel_frontend_create": (_i32, [_mfc, _c.POINTER(_vp)]),
+    "iris_mel_frontend_destroy": (_i32, [_vp]),
+    "iris_mel_frontend_forward": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _u64, _vp]),
+    "iris_mel_frontend_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -290,7 +313,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

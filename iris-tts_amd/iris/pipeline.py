@@ -30,15 +30,17 @@ class MelToWavePipeline:
     ``(frame_cond, z_prior) -> (device mel [B, n_mels, T], ...)``) for ``infer_from_cond``, or None.  ``text``: a pair
     ``(iris.encoder.PhonemeEncoder, iris.encoder.DurationPredictor)`` for ``infer_from_phonemes``, or None.  ``posterior``:
     an ``iris.vae.VAEPosteriorEncoder`` (or any callable ``(mel, frame_cond) -> (device recon [B, n_mels, T], ...)``) for
-    ``resynthesize``, or None."""
+    ``resynthesize``, or None.  ``frontend``: an ``iris.mel.MelFrontend`` (or any callable ``(audio [B, L], lengths=,
+    max_frames=) -> (device mel [B, n_mels, T], frames [B])``) for ``mel_from_audio`` and ``resynthesize_from_audio``, or None."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
-                 group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None):
+                 group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None):
         self.postnet = postnet
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
+        self.frontend = frontend
         self.device = device
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
@@ -182,6 +184,82 @@ class MelToWavePipeline:
             cond[i, :c.shape[0]] = c.to(device=cond.device, dtype=torch.float32)
         recon = reconstruct(self.posterior, self.acoustic, padded, cond, lengths=lengths)[0]
         return self.infer_batch([recon[i, :, :int(n)] for i, n in enumerate(lengths)], **kw)
+
+    def _frontend_fn(self) -> Callable:
+        if self.frontend is None:
+            raise ValueError("this call needs a mel front-end: construct the pipeline with frontend=MelFrontend(...)")
+        return getattr(self.frontend, "forward_device", self.frontend)
+
+    @staticmethod
+    def _audio_rows(audio):
+        """One waveform ``[n]`` or a batch ``[B, L]`` (numpy or tensor, float or int16) -> ``[B, L]``."""
+        if not isinstance(audio, torch.Tensor):
+            audio = np.asarray(audio)
+            audio = torch.from_numpy(np.ascontiguousarray(audio if audio.dtype == np.int16 else audio.astype(np.float32, copy=False)))
+        if audio.dim() == 1:
+            audio = audio[None]
+        if audio.dim() != 2:
+            raise ValueError(f"expected audio [n] or [B, L], got shape {tuple(audio.shape)}")
+        return audio
+
+    def mel_from_audio(self, audio) -> torch.Tensor:
+        """A waveform ``[n]`` or a batch ``[B, L]`` (float32 or int16, host or device) -> its device log-mel
+        ``[B, n_mels, 1 + L // hop]`` (``iris.mel.MelFrontend.forward_device``: the reference's ``compute_mel_spectrogram``)."""
+        return self._frontend_fn()(self._audio_rows(audio))[0]
+
+    def resynthesize_from_audio(self, audio, frame_cond, **kw):
+        """``resynthesize`` from the recording itself: ``audio [n]`` (float32 or int16) and its frame conditioning
+        ``[T, cond_dim]`` (or ``[1, T, cond_dim]``).  The mel is the front-end's, cut at the conditioning's ``T`` frames as the
+        reference's dataset trims it to the duration total (``datasets.py:621-624``), and goes to ``resynthesize``.  The
+        audio must have at least ``T`` frames (``1 + n // hop >= T``) and ``T`` must be a multiple of
+        ``acoustic.downsample_factor`` (``ValueError``; nothing is padded silently).
+
+        Lists of waveforms and conditionings: ONE ragged front-end call over the padded batch (``lengths`` = the items'
+        samples, ``max_frames`` = their ``T_i``), then the list form of ``resynthesize`` -- one ragged ``reconstruct`` and
+        ``infer_batch``.  The result is a list."""
+        fe = self._frontend_fn()
+        hop = int(getattr(self.frontend, "hop_length", self.streamer.hop_length))
+        factor = int(getattr(self.acoustic, "downsample_factor", 1))
+
+        def check(i, n, T):
+            if 1 + n // hop < T:
+                raise ValueError(f"item {i}: {n} samples give {1 + n // hop} frames, the conditioning has {T}")
+            if T % factor:
+                raise ValueError(f"item {i}: T = {T} is not a multiple of 2^down_stages = {factor}: pad the conditioning "
+                                 "first; nothing is padded silently")
+
+        if isinstance(audio, (list, tuple)):
+            audios, conds = list(audio), list(frame_cond)
+            if len(audios) != len(conds):
+                raise ValueError(f"{len(audios)} waveforms but {len(conds)} conditionings")
+            if not audios:
+                return []
+            rows = [self._audio_rows(a) for a in audios]
+            for i, (a, c) in enumerate(zip(rows, conds)):
+                if a.shape[0] != 1 or len(c.shape) != 2 or a.dtype != rows[0].dtype:
+                    raise ValueError(f"item {i}: expected a waveform [n] of one sample type and a conditioning [T, cond_dim], got "
+                                     f"{a.dtype} {tuple(a.shape)} and {tuple(c.shape)}")
+                check(i, int(a.shape[1]), int(c.shape[0]))
+            counts = [int(a.shape[1]) for a in rows]
+            caps = [int(c.shape[0]) for c in conds]
+            packed = torch.zeros((len(rows), max(counts)), dtype=rows[0].dtype, device=rows[0].device)
+            for i, a in enumerate(rows):
+                packed[i, :counts[i]] = a[0].to(packed.device)
+            mel = fe(packed, lengths=counts, max_frames=caps)[0]
+            return self.resynthesize([mel[i, :, :t] for i, t in enumerate(caps)], conds, **kw)
+        rows = self._audio_rows(audio)
+        if rows.shape[0] != 1:
+            raise ValueError("resynthesize_from_audio takes one waveform [n], or lists of waveforms and conditionings")
+        if not isinstance(frame_cond, torch.Tensor):
+            frame_cond = torch.from_numpy(np.ascontiguousarray(np.asarray(frame_cond, dtype=np.float32)))
+        if frame_cond.dim() == 2:
+            frame_cond = frame_cond[None]
+        if frame_cond.dim() != 3 or frame_cond.shape[0] != 1:
+            raise ValueError(f"expected a conditioning [T, cond_dim], got shape {tuple(frame_cond.shape)}")
+        T = int(frame_cond.shape[1])
+        check(0, int(rows.shape[1]), T)
+        mel = fe(rows, max_frames=[T])[0]
+        return self.resynthesize(mel[:, :, :T].contiguous(), frame_cond, **kw)
 
     def infer_from_phonemes(self, ids, lengths=None, durations=None, z_prior=None, **kw):
         """Phoneme ids ``[B, P]`` -> ``(what infer returns, frames_per_item)``: phoneme encoder, duration head and length
