@@ -710,6 +710,53 @@ int32_t iris_mel_frontend_forward_ragged(iris_mel_frontend_handle* h, const void
                                          const int32_t* n_samples_dev, const int32_t* max_frames_dev /* or NULL */, float* mel_out_dev,
                                          int32_t* frames_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- Griffin-Lim vocoder: log-mel to waveform without trained weights (csrc/griffin_lim.h) -------------------------
+ * The reference's --use_griffin_lim path (scripts/synthesize.py:174-194): m = exp(clip(logmel, -11.513, 2.0)), librosa 0.11's
+ * mel_to_stft(power=1.0) and griffinlim(n_iter, hop_length, win_length), in fp32.  logmel [B, n_mels, T] -> waveform
+ * [B, hop_length * (T - 1)].  Window, frames and filterbank fb [n_mels][n_bins] are the mel front-end's, and so are the config
+ * rules (the first eight fields are its fields).
+ *   inversion  x0 = max(P m, 0) with P = pinv(fb) [n_bins][n_mels] from the caller (float64, rounded once), then nnls_iters
+ *              projected-gradient steps x <- max(x - nnls_step * fb^T (fb x - m), 0); nnls_step = 1 / lambda_max(fb fb^T) keeps
+ *              ||fb x - m|| from growing.  S = x.
+ *   phase      c = S * (cos phi0, sin phi0); n_iter times: y = istft(c), r = stft(y), a = r - momentum / (1 + momentum) * r_prev
+ *              (r_prev = 0 in the first pass), c = S * a / (|a| + FLT_MIN); then out = istft(c).
+ *   stft       frame t covers samples [t * hop - n_fft / 2, t * hop + n_fft / 2) of y, 0 outside (the front-end's frames).
+ *   istft      w[n] * irfft(c[:, t])[n] overlap-added, divided by the window-sum-square where that exceeds FLT_MIN, n_fft / 2
+ *              samples trimmed at each end; the imaginary parts of bins 0 and n_fft / 2 are ignored.
+ * phase0_dev: fp32 [B][T][n_bins][2], frame-major -- cos(phi0[b, k, t]) then sin(phi0[b, k, t]) at ((b * T + t) * n_bins + k) * 2;
+ * 8-byte aligned.  2 * n_iter + 2 launches, no atomics: two runs agree bit for bit, and item b is its batch-of-one call.
+ * After a forward the workspace starts with S as fp32 [B][T][Ks], Ks = n_bins rounded up to a multiple of 4.
+ * The front-end's unsupported configs, an n_fft that is no multiple of 32, and an inversion tile (32 frames of n_mels and n_bins
+ * floats) or a frame window of the transforms (31 + n_fft / hop_length frames of 260 floats: n_fft / hop_length >= 128) above
+ * 160 KB of LDS return
+ * IRIS_HIFIGAN_UNSUPPORTED (from every function below that takes the config; create reports it before it touches the device);
+ * T < 2, a NULL pointer, a negative count, momentum outside [0, 1), a non-positive nnls_step and a wrong pinv size
+ * IRIS_HIFIGAN_INVALID_ARGUMENT; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches. */
+typedef struct iris_griffin_lim_config {
+    int32_t sample_rate, n_fft, hop_length, win_length, n_mels, n_iter;
+    double fmin, fmax;
+    int32_t nnls_iters, reserved;
+    double momentum, nnls_step;
+} iris_griffin_lim_config;
+typedef struct iris_griffin_lim_handle iris_griffin_lim_handle;
+
+/* Host only (no device is needed).  design: *n_bins and, where the pointers are not NULL, the fp32 tables the handle uploads --
+ * dft_host as iris_mel_frontend_design gives it; idft_host [2][n_bins][n_fft]: w[n] f_k cos(2 pi k n / n_fft) / n_fft, then
+ * -w[n] f_k sin(2 pi k n / n_fft) / n_fft (f_k = 1 for k = 0 and n_fft / 2, else 2; those two bins' sine rows are 0), in double
+ * with the angle reduced by (k n) mod n_fft, rounded once; fb_host [n_mels][n_bins]; wsq_host [n_fft]: w[n]^2.
+ * launch_count: a dry run of the forward's own code. */
+int32_t iris_griffin_lim_design(const iris_griffin_lim_config* cfg, int32_t* n_bins, float* dft_host, uint64_t dft_floats,
+                                float* idft_host, uint64_t idft_floats, float* fb_host, uint64_t fb_floats, float* wsq_host,
+                                uint64_t wsq_floats);
+int32_t iris_griffin_lim_workspace_bytes(const iris_griffin_lim_config* cfg, int32_t B, int32_t T, uint64_t* bytes);
+int32_t iris_griffin_lim_launch_count(const iris_griffin_lim_config* cfg, int32_t B, int32_t T, int32_t* n);
+/* create: on the current device, which becomes the handle's; pinv_host [n_bins][n_mels].  The forward is asynchronous on
+ * `stream`, allocates and copies nothing, and is safe inside a stream capture. */
+int32_t iris_griffin_lim_create(const iris_griffin_lim_config* cfg, const float* pinv_host, uint64_t n_pinv, iris_griffin_lim_handle** out);
+int32_t iris_griffin_lim_destroy(iris_griffin_lim_handle* h);
+int32_t iris_griffin_lim_forward(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, int32_t B, int32_t T,
+                                 float* wav_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,400 @@
+// griffin_lim.h -- log-mel to waveform on the device without a trained vocoder (iris_griffin_lim_*): the reference's
+// --use_griffin_lim path (scripts/synthesize.py:174-194), i.e. exp(clip(logmel, -11.513, 2)), librosa 0.11's
+// mel_to_stft(power=1.0) and griffinlim(n_iter, hop_length, win_length), fp32.  Window, frames and filterbank are the mel
+// front-end's (mel_frontend.h).  N = n_fft, H = hop, K = N / 2 + 1 bins, T frames, Ly = H (T - 1) samples.
+//
+//   invert   m = exp(clip(logmel)) (exp in double, rounded once);  x0 = max(P m, 0), P = pinv(fb) from the caller;
+//            nnls_iters steps  x <- max(x - s fb^T (fb x - m), 0),  s = 1 / lambda_max(fb fb^T) from the caller;  S = x
+//   phase    c0 = S (cos phi0, sin phi0);  n_iter times:  y = istft(c);  r = stft(y);  a = r - alpha r_prev (alpha =
+//            momentum / (1 + momentum); r_prev = 0 in the first pass);  c = S a / (|a| + FLT_MIN);  then out = istft(c)
+//   stft     the front-end's frames: frame t covers samples [t H - N / 2, t H + N / 2) of y, 0 outside
+//   istft    w[n] irfft(c[:, t])[n] overlap-added, divided by the window-sum-square where that exceeds FLT_MIN, N / 2
+//            samples trimmed at each end; Im of bins 0 and N / 2 is ignored
+//
+// Buffers (fp32, frame-major so that a block stages 32 frames as 32 LDS rows):
+//   S [B][T][Ks]   Ks = K rounded up to 4
+//   c, r [B][T][Qp] interleaved complex: column 2 k is Re, 2 k + 1 is Im of bin k; Q = N + 2 columns, Qp = Q rounded up to 8
+//                  (columns from Q on are never written and read as 0)
+//   y [B][Ly]
+//
+// gl_invert_kernel: ONE launch.  A block owns 32 frames; m (32 x n_mels), the residual and x (32 x K) stay in LDS and the
+// three products run on the MFMA loop of gemm_tile_f32.h against P, fb and fb^T in fragment order.  It stores S and c0.
+//
+// gl_istft_kernel: gather form, no atomics.  View the zero-padded signal as rows of H samples: row j is the sum over taps
+// kap < N / H of frame j - kap's samples [kap H, (kap + 1) H) -- an N / H tap, C_in = Q implicit-GEMM convolution over frames
+// against the windowed inverse-DFT table [Q][N], with the taps in reverse order.  A block owns 32 rows and a wave one 32-wide
+// tile of a row's H columns (grid.z counts groups of 8 tiles); the Q columns are staged in slices of 256 (the text stage's
+// precedent), 31 + N / H frames at a time.  The epilogue sums w^2 over the frames that exist (at most N / H terms, ascending
+// tap), divides and stores the samples that survive the trim.
+//
+// gl_stft_update_kernel: the front-end's DFT convolution (same packed table, same column order: Re and Im of a bin in one
+// lane) with the phase update as its epilogue; it stores the new c and keeps r for the next pass.  grid.z counts groups of 8
+// column tiles, so a wave runs one tile.
+//
+// Summation: the MFMA adds a chain's terms one after the other, and a chain of n_fft / hop * (n_fft + 2) = 4104 terms (the
+// inverse STFT at the defaults) loses more than the blocked sums of a host BLAS.  Both transforms therefore run short chains
+// and add the partial sums: one per tap and 64 columns (inverse) or 64 samples (forward).  The normalisation a / |a| amplifies
+// what is left where |a| is small.
+#pragma once
+#include <float.h>
+
+#include "mel_frontend.h"
+
+namespace iris {
+namespace gl {
+
+constexpr int kRows = 32;            // frames (invert, stft) or output rows (istft) of a block
+constexpr int kWaves = 8;
+constexpr int kSlice = 256;          // columns of c staged at a time by the istft
+constexpr double kLogLo = -11.513, kLogHi = 2.0;
+
+struct Design {
+    mel::Design m;
+    int n_iter = 0, nnls_iters = 0;
+    double momentum = 0.0, nnls_step = 0.0;
+    int bins() const { return m.bins(); }
+    int ks() const { return (bins() + 3) & ~3; }
+    int q() const { return m.n_fft + 2; }
+    int qp() const { return (q() + 7) & ~7; }
+    int hop_tiles() const { return (m.hop + 31) / 32; }
+    int first_row() const { return (m.n_fft / 2) / m.hop; }                  // the padded row that holds output sample 0
+    static int row_floats(int C) { return ((C + 7) & ~7) + 4; }
+    size_t invert_lds_bytes() const { return (size_t)kRows * (2 * row_floats(m.n_mels) + row_floats(bins())) * sizeof(float); }
+    size_t istft_lds_bytes() const { return (size_t)(kRows - 1 + m.taps()) * (kSlice + 4) * sizeof(float); }
+    size_t stft_lds_bytes() const { return (size_t)m.window_rows() * (m.hop8() + 4) * sizeof(float); }
+};
+
+// idft [2][bins][n_fft]: w[n] f_k cos(2 pi k n / N) / N, then -w[n] f_k sin(2 pi k n / N) / N, with f_k = 1 for k = 0 and
+// N / 2 and 2 otherwise -- w[n] irfft(c)[n] = sum_k Re c_k idft[0][k][n] + Im c_k idft[1][k][n].  In double, angle reduced
+// by (k n) mod N, rounded once.
+inline void fill_idft(const mel::Design& d, float* idft) {
+    const double two_pi = 6.283185307179586476925286766559;
+    const int N = d.n_fft, nb = d.bins();
+    std::vector<double> w, c(N), s(N);
+    mel::fill_window(d, w);
+    for (int j = 0; j < N; ++j) { c[j] = cos(two_pi * j / N); s[j] = sin(two_pi * j / N); }
+    s[0] = 0.0;
+    if (!(N & 1)) s[N / 2] = 0.0;
+    for (int k = 0; k < nb; ++k) {
+        const bool edge = k == 0 || 2 * k == N;
+        const double f = (edge ? 1.0 : 2.0) / N;
+        for (int n = 0; n < N; ++n) {
+            const int j = (int)(((long long)k * n) % N);
+            idft[(size_t)k * N + n] = (float)(w[n] * f * c[j]);
+            idft[((size_t)nb + k) * N + n] = edge ? 0.f : (float)(-(w[n] * f * s[j]));
+        }
+    }
+}
+
+// wsq [n_fft]: w[n]^2 in double, rounded once
+inline void fill_wsq(const mel::Design& d, float* wsq) {
+    std::vector<double> w;
+    mel::fill_window(d, w);
+    for (int n = 0; n < d.n_fft; ++n) wsq[n] = (float)(w[n] * w[n]);
+}
+
+// The inverse table as the [C_out = 32 * hop_tiles][C_in = Q][k = taps] Conv1d weight of the gather: tap kk multiplies frame
+// j - (taps - 1 - kk), whose samples [(taps - 1 - kk) H, ...) land in row j.
+inline void conv_weight_from_idft(const Design& d, const float* idft, std::vector<float>& w) {
+    const int N = d.m.n_fft, H = d.m.hop, K = d.m.taps(), nb = d.bins(), Q = d.q(), C_out = 32 * d.hop_tiles();
+    w.assign((size_t)C_out * Q * K, 0.f);
+    for (int co = 0; co < H; ++co)
+        for (int q = 0; q < Q; ++q) {
+            const float* row = idft + ((size_t)(q & 1 ? nb : 0) + (q >> 1)) * N;
+            for (int kk = 0; kk < K; ++kk) w[((size_t)co * Q + q) * K + kk] = row[(K - 1 - kk) * H + co];
+        }
+}
+
+}  // namespace gl
+}  // namespace iris
+
+#ifdef __HIPCC__
+namespace iris {
+namespace gl {
+
+struct InvertLaunch {
+    const float* logmel;      // [B, n_mels, T]
+    const float* phase0;      // [B, T, bins, 2]: cos, sin
+    const f32x4* wp;          // packed P: C_in n_mels, C_out bins
+    const f32x4* wfb;         // packed fb: C_in bins, C_out n_mels
+    const f32x4* wfbt;        // packed fb^T: C_in n_mels, C_out bins
+    float* S;                 // [B, T, Ks]
+    float* c;                 // [B, T, Qp]
+    int T, n_mels, bins, Ks, Qp, nnls_iters;
+    float step;
+    int GpM, nctK, GpK, nctM;
+};
+
+__global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, nthr = 64 * kWaves;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lo = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y, i0 = blockIdx.x * kRows;
+    const int Mp = (a.n_mels + 7) & ~7, SM = Mp + 4, Kb = (a.bins + 7) & ~7, SX = Kb + 4;
+    float* m = lds;                       // [32][SM]  exp(clip(logmel)); columns from n_mels on are 0
+    float* res = m + kRows * SM;          // [32][SM]  fb x - m
+    float* x = res + kRows * SM;          // [32][SX]  the solution; columns from bins on are 0
+
+    for (int idx = tid; idx < kRows * Mp; idx += nthr) {             // consecutive threads: consecutive frames of one channel
+        const int ch = idx / kRows, r = idx - ch * kRows, t = i0 + r;
+        float v = 0.f;
+        if (ch < a.n_mels && t < a.T) {
+            double l = (double)a.logmel[((size_t)b * a.n_mels + ch) * a.T + t];
+            l = l < kLogLo ? kLogLo : (l > kLogHi ? kLogHi : l);
+            v = (float)exp(l);                                       // in double, rounded once (as the front-end takes its log)
+        }
+        m[r * SM + ch] = v;
+        res[r * SM + ch] = 0.f;
+    }
+    for (int idx = tid; idx < kRows * (Kb - a.bins); idx += nthr) {
+        const int r = idx / (Kb - a.bins), cc = idx - r * (Kb - a.bins);
+        x[r * SX + a.bins + cc] = 0.f;
+    }
+    __syncthreads();
+
+    for (int ct = wave; ct < a.nctK; ct += kWaves) {                 // x0 = max(P m, 0)
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        mma_loop(acc, m + lo * SM + 4 * hi, 0, a.wp + (size_t)ct * 64 + lane, (size_t)a.nctK * 64, a.GpM, 1, Mp >> 3);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int bin = ct * 32 + 8 * g + 4 * hi + e;
+                if (bin < a.bins) x[lo * SX + bin] = fmaxf(acc[4 * g + e], 0.f);
+            }
+    }
+    __syncthreads();
+
+    for (int it = 0; it < a.nnls_iters; ++it) {
+        for (int ct = wave; ct < a.nctM; ct += kWaves) {             // res = fb x - m
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            mma_loop(acc, x + lo * SX + 4 * hi, 0, a.wfb + (size_t)ct * 64 + lane, (size_t)a.nctM * 64, a.GpK, 1, Kb >> 3);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int ch = ct * 32 + 8 * g + 4 * hi + e;
+                    if (ch < a.n_mels) res[lo * SM + ch] = acc[4 * g + e] - m[lo * SM + ch];
+                }
+        }
+        __syncthreads();
+        for (int ct = wave; ct < a.nctK; ct += kWaves) {             // x = max(x - s fb^T res, 0)
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            mma_loop(acc, res + lo * SM + 4 * hi, 0, a.wfbt + (size_t)ct * 64 + lane, (size_t)a.nctK * 64, a.GpM, 1, Mp >> 3);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int bin = ct * 32 + 8 * g + 4 * hi + e;
+                    if (bin < a.bins) x[lo * SX + bin] = fmaxf(x[lo * SX + bin] - a.step * acc[4 * g + e], 0.f);
+                }
+        }
+        __syncthreads();
+    }
+
+    for (int idx = tid; idx < kRows * a.bins; idx += nthr) {         // S and c0 = S (cos, sin)
+        const int r = idx / a.bins, k = idx - r * a.bins, t = i0 + r;
+        if (t >= a.T) break;
+        const size_t row = (size_t)b * a.T + t;
+        const float s = x[r * SX + k];
+        const float2 ph = reinterpret_cast<const float2*>(a.phase0)[row * a.bins + k];
+        a.S[row * a.Ks + k] = s;
+        reinterpret_cast<float2*>(a.c)[(row * a.Qp >> 1) + k] = make_float2(s * ph.x, s * ph.y);
+    }
+}
+
+struct IstftLaunch {
+    const float* c;           // [B, T, Qp]
+    const f32x4* widft;       // packed inverse table: `taps` taps, Gp groups, n_ct column tiles
+    const float* wsq;         // [n_fft]
+    float* y;                 // [B, Ly]
+    int T, Ly, hop, taps, n_fft, Q, Qp, Gp, n_ct, first_row;
+};
+
+__global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, nthr = 64 * kWaves;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lo = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y;
+    const int j0 = a.first_row + blockIdx.x * kRows;         // the block's first padded row
+    const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
+    const int R = kRows - 1 + a.taps, S = kSlice + 4;
+    const int t0 = j0 - (a.taps - 1);                        // LDS row r holds frame t0 + r
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    for (int q0 = 0; q0 < a.Qp; q0 += kSlice) {
+        const int width = a.Qp - q0 < kSlice ? a.Qp - q0 : kSlice;          // a multiple of 8
+        for (int idx = tid; idx < R * (kSlice / 4); idx += nthr) {
+            const int r = idx / (kSlice / 4), q = q0 + 4 * (idx - r * (kSlice / 4)), t = t0 + r;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (t >= 0 && t < a.T && q < a.Qp) {
+                v = *reinterpret_cast<const f32x4*>(a.c + ((size_t)b * a.T + t) * a.Qp + q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = q + e < a.Q ? v[e] : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(lds + r * S + (q - q0)) = v;
+        }
+        __syncthreads();
+        if (ct < a.n_ct)
+            for (int kk = 0; kk < a.taps; ++kk)              // one chain per tap and 64 columns (see "Summation" above)
+                for (int g0 = 0; g0 < width >> 3; g0 += 8) {
+                    f32x16 part;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) part[r] = 0.f;
+                    mma_loop(part, lds + (lo + kk) * S + 4 * hi + 8 * g0, 0,
+                             a.widft + ((size_t)kk * a.Gp + (q0 >> 3) + g0) * a.n_ct * 64 + (size_t)ct * 64 + lane, (size_t)a.n_ct * 64, a.Gp, 1,
+                             (width >> 3) - g0 < 8 ? (width >> 3) - g0 : 8);
+                    acc += part;
+                }
+        __syncthreads();
+    }
+    if (ct >= a.n_ct) return;
+
+    // D[col][row]: lane & 31 = row, registers 4g .. 4g + 3 = columns 8g + 4 (lane >> 5) + {0..3}
+    const int j = j0 + lo, half = a.n_fft >> 1;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int col = ct * 32 + 8 * g + 4 * hi + e;
+            const long long s = (long long)j * a.hop + col - half;
+            if (col >= a.hop || s < 0 || s >= a.Ly) continue;
+            float wss = 0.f;
+            for (int kap = 0; kap < a.taps; ++kap) {
+                const int t = j - kap;
+                if (t >= 0 && t < a.T) wss += a.wsq[kap * a.hop + col];
+            }
+            const float v = acc[4 * g + e];
+            a.y[(size_t)b * a.Ly + (size_t)s] = wss > FLT_MIN ? v / wss : v;
+        }
+}
+
+struct StftLaunch {
+    const float* y;           // [B, Ly]
+    const f32x4* wdft;        // the front-end's packed windowed DFT
+    const float* S;           // [B, T, Ks]
+    float* c;                 // [B, T, Qp] out
+    float* r;                 // [B, T, Qp] r_prev in (unless first), r out
+    int Ly, T, hop, taps, n_fft, Ks, Qp, Gp, n_ct, first;
+    float alpha;
+};
+
+__device__ __forceinline__ void phase_update(float re, float im, float pr, float pi, float alpha, float s, float& cre, float& cim) {
+    const float ar = re - alpha * pr, ai = im - alpha * pi;
+    const float den = sqrtf(ar * ar + ai * ai) + FLT_MIN;
+    cre = s * ar / den;
+    cim = s * ai / den;
+}
+
+__global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, nthr = 64 * kWaves;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lo = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y, i0 = blockIdx.x * kRows;
+    const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
+    const int H = a.hop, Cp = (H + 7) & ~7, S = Cp + 4, R = kRows - 1 + a.taps, half = a.n_fft >> 1;
+
+    {   // the front-end's window: row r, column c is sample i0 * hop - n_fft / 2 + r * hop + c; 0 outside [0, Ly)
+        const long long s0 = (long long)i0 * H - half;
+        const size_t item = (size_t)b * a.Ly;
+        for (int idx = tid; idx < R * Cp; idx += nthr) {
+            const int r = idx / Cp, c = idx - r * Cp;
+            const long long s = s0 + (long long)r * H + c;
+            lds[r * S + c] = (c < H && s >= 0 && s < a.Ly) ? a.y[item + (size_t)s] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int t = i0 + lo;
+    if (ct >= a.n_ct) return;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int kk = 0; kk < a.taps; ++kk)                      // one chain per tap and 64 samples (see "Summation" above)
+        for (int g0 = 0; g0 < Cp >> 3; g0 += 8) {
+            f32x16 part;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) part[r] = 0.f;
+            mma_loop(part, lds + (lo + kk) * S + 4 * hi + 8 * g0, 0, a.wdft + ((size_t)kk * a.Gp + g0) * a.n_ct * 64 + (size_t)ct * 64 + lane,
+                     (size_t)a.n_ct * 64, a.Gp, 1, (Cp >> 3) - g0 < 8 ? (Cp >> 3) - g0 : 8);
+            acc += part;
+        }
+    if (t >= a.T) return;
+
+    // registers 4g + e: g < 2 Re, g >= 2 Im of bin 16 ct + 8 g + 4 (lane >> 5) + e; the Im column of bin 0 is Re of bin n_fft / 2
+    const size_t row = (size_t)b * a.T + t;
+    float* crow = a.c + row * a.Qp;
+    float* rrow = a.r + row * a.Qp;
+    const float* srow = a.S + row * a.Ks;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int bin0 = 16 * ct + 8 * g + 4 * hi;           // 4 bins, 8 consecutive floats of c and r
+        if (bin0 >= half) continue;
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(srow + bin0);
+        f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = p0;
+        if (!a.first) {
+            p0 = *reinterpret_cast<const f32x4*>(rrow + 2 * bin0);
+            p1 = *reinterpret_cast<const f32x4*>(rrow + 2 * bin0 + 4);
+        }
+        const float prev[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
+        float cn[8], rn[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float re = acc[4 * g + e];
+            float im = -acc[4 * (g + 2) + e];                 // the table holds +sin: the sum is minus the imaginary part
+            if (bin0 + e == 0) {                              // one lane of tile 0: bins 0 and n_fft / 2 are real
+                const float nyq = acc[4 * (g + 2) + e], pn = a.first ? 0.f : rrow[2 * half];
+                float cre, unused;
+                phase_update(nyq, 0.f, pn, 0.f, a.alpha, srow[half], cre, unused);
+                rrow[2 * half] = nyq; rrow[2 * half + 1] = 0.f;
+                crow[2 * half] = cre; crow[2 * half + 1] = 0.f;
+                im = 0.f;
+            }
+            rn[2 * e] = re; rn[2 * e + 1] = im;
+            phase_update(re, im, prev[2 * e], bin0 + e == 0 ? 0.f : prev[2 * e + 1], a.alpha, sv[e], cn[2 * e], cn[2 * e + 1]);
+        }
+        *reinterpret_cast<f32x4*>(rrow + 2 * bin0) = f32x4{rn[0], rn[1], rn[2], rn[3]};
+        *reinterpret_cast<f32x4*>(rrow + 2 * bin0 + 4) = f32x4{rn[4], rn[5], rn[6], rn[7]};
+        *reinterpret_cast<f32x4*>(crow + 2 * bin0) = f32x4{cn[0], cn[1], cn[2], cn[3]};
+        *reinterpret_cast<f32x4*>(crow + 2 * bin0 + 4) = f32x4{cn[4], cn[5], cn[6], cn[7]};
+    }
+}
+
+inline hipError_t launch_invert(InvertLaunch& a, const Design& d, int B, hipStream_t stream) {
+    a.n_mels = d.m.n_mels; a.bins = d.bins(); a.Ks = d.ks(); a.Qp = d.qp(); a.nnls_iters = d.nnls_iters; a.step = (float)d.nnls_step;
+    a.GpM = packed_groups(d.m.n_mels); a.nctK = packed_cotiles(d.bins());
+    a.GpK = packed_groups(d.bins()); a.nctM = packed_cotiles(d.m.n_mels);
+    const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B), block(64 * kWaves);
+    return launch_kernel_named("gl_invert_kernel", gl_invert_kernel, grid, block, d.invert_lds_bytes(), stream, a);
+}
+
+inline hipError_t launch_istft(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
+    a.Ly = d.m.hop * (a.T - 1); a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Q = d.q(); a.Qp = d.qp();
+    a.Gp = packed_groups(d.q()); a.n_ct = d.hop_tiles(); a.first_row = d.first_row();
+    const long long last = ((long long)d.m.n_fft / 2 + a.Ly - 1) / d.m.hop;             // the padded row of the last sample
+    const int rows = (int)(last - a.first_row + 1);
+    const dim3 grid((unsigned)((rows + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
+    return launch_kernel_named("gl_istft_kernel", gl_istft_kernel, grid, block, d.istft_lds_bytes(), stream, a);
+}
+
+inline hipError_t launch_stft_update(StftLaunch& a, const Design& d, int B, hipStream_t stream) {
+    a.Ly = d.m.hop * (a.T - 1); a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Ks = d.ks(); a.Qp = d.qp();
+    a.Gp = packed_groups(d.m.hop); a.n_ct = d.m.dft_tiles();
+    a.alpha = (float)(d.momentum / (1.0 + d.momentum));
+    const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
+    return launch_kernel_named("gl_stft_update_kernel", gl_stft_update_kernel, grid, block, d.stft_lds_bytes(), stream, a);
+}
+
+}  // namespace gl
+}  // namespace iris
+#endif

@@ -1,0 +1,209 @@
+// iris_griffin_lim.hip -- the iris_griffin_lim_* entry points of include/iris_hifigan.h: log-mel [B, n_mels, T] to a waveform
+// [B, hop (T - 1)] by mel inversion and Griffin-Lim phase retrieval (csrc/griffin_lim.h), the reference's --use_griffin_lim
+// path (scripts/synthesize.py:174-194).  2 * n_iter + 2 launches: the inversion, n_iter times (inverse STFT, STFT with the phase
+// update), and the last inverse STFT.  The handle owns the packed tables: P = pinv(fb) from the caller, fb both ways round, the
+// front-end's windowed DFT and the windowed inverse DFT, and w^2.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include <new>
+#include <vector>
+
+#include "stage_host.h"
+#include "griffin_lim.h"
+
+using namespace iris;
+
+struct iris_griffin_lim_handle : StageHandle {
+    gl::Design d;
+    PackedGemm p, fb, fbt, dft, idft;
+    size_t wsq_off = 0;
+};
+
+// the layout iris._native.GriffinLimConfig restates (tests/test_griffin_lim.py holds the two together)
+static_assert(sizeof(iris_griffin_lim_config) == 64 && offsetof(iris_griffin_lim_config, n_iter) == 20 &&
+              offsetof(iris_griffin_lim_config, fmin) == 24 && offsetof(iris_griffin_lim_config, nnls_iters) == 40 &&
+              offsetof(iris_griffin_lim_config, momentum) == 48 && offsetof(iris_griffin_lim_config, nnls_step) == 56,
+              "iris_griffin_lim_config layout");
+
+namespace {
+
+int gl_validate(const iris_griffin_lim_config* c, gl::Design* d) {
+    if (!c) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "config is NULL");
+    const iris_mel_frontend_config mc = {c->sample_rate, c->n_fft, c->hop_length, c->win_length, c->n_mels, 0, c->fmin, c->fmax};
+    TRY(mel_validate(&mc, &d->m));
+    if (c->n_iter < 0 || c->nnls_iters < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "n_iter and nnls_iters must not be negative");
+    if (!(c->momentum >= 0.0) || !(c->momentum < 1.0))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "0 <= momentum < 1 is required, got %g", c->momentum);
+    if (!(c->nnls_step > 0.0) || !isfinite(c->nnls_step))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "nnls_step must be positive and finite, got %g", c->nnls_step);
+    if (c->n_fft % 32) return fail(IRIS_HIFIGAN_UNSUPPORTED, "n_fft %d is not a multiple of 32 (bins come in tiles of 16)", c->n_fft);
+    d->n_iter = c->n_iter; d->nnls_iters = c->nnls_iters; d->momentum = c->momentum; d->nnls_step = c->nnls_step;
+    if (d->invert_lds_bytes() > mel::kMaxLdsBytes)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "the mel inversion of n_mels %d, n_fft %d needs %llu bytes of LDS, more than %llu", c->n_mels,
+                    c->n_fft, (unsigned long long)d->invert_lds_bytes(), (unsigned long long)mel::kMaxLdsBytes);
+    const size_t transform = d->istft_lds_bytes() > d->stft_lds_bytes() ? d->istft_lds_bytes() : d->stft_lds_bytes();
+    if (transform > mel::kMaxLdsBytes)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "the frame window of n_fft %d, hop_length %d (31 + %d frames) needs %llu bytes of LDS, more than "
+                    "%llu: no form that slices the frames is built", c->n_fft, c->hop_length, d->m.taps(), (unsigned long long)transform,
+                    (unsigned long long)mel::kMaxLdsBytes);
+    return IRIS_HIFIGAN_OK;
+}
+
+int gl_check_shape(int32_t B, int32_t T) {
+    if (B < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative batch");
+    if (T < 2) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "T = %d: Griffin-Lim needs at least 2 frames (the output has hop (T - 1) samples)", T);
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    return IRIS_HIFIGAN_OK;
+}
+
+// S first (tests read it there), then c, r and the waveform between the passes.
+struct GlWorkspace {
+    size_t S, c, r, y, floats;
+    GlWorkspace(const gl::Design& d, int B, int T) {
+        WsTaker ws;
+        const size_t frames = (size_t)B * T;
+        S = ws.take(frames * d.ks());
+        c = ws.take(frames * d.qp());
+        r = ws.take(frames * d.qp());
+        y = ws.take((size_t)B * d.m.hop * (T - 1));
+        floats = ws.off;
+    }
+};
+
+struct GlTables { const float *p, *fb, *fbt, *dft, *idft, *wsq; };
+
+// Queues the forward's launches (or, in a dry run, counts them).
+int gl_forward(const gl::Design& d, const GlTables& tb, const float* logmel, const float* phase0, int B, int T, float* wav_out,
+               float* ws, hipStream_t stream) {
+    const GlWorkspace lay(d, B, T);
+    gl::InvertLaunch inv; memset(&inv, 0, sizeof(inv));
+    inv.logmel = logmel; inv.phase0 = phase0; inv.T = T;
+    inv.wp = (const f32x4*)tb.p; inv.wfb = (const f32x4*)tb.fb; inv.wfbt = (const f32x4*)tb.fbt;
+    inv.S = ws + lay.S; inv.c = ws + lay.c;
+    HIP_TRY(gl::launch_invert(inv, d, B, stream));
+    gl::IstftLaunch is; memset(&is, 0, sizeof(is));
+    is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.T = T;
+    gl::StftLaunch st; memset(&st, 0, sizeof(st));
+    st.wdft = (const f32x4*)tb.dft; st.S = ws + lay.S; st.c = ws + lay.c; st.r = ws + lay.r; st.y = ws + lay.y; st.T = T;
+    for (int it = 0; it < d.n_iter; ++it) {
+        is.y = ws + lay.y;
+        HIP_TRY(gl::launch_istft(is, d, B, stream));
+        st.first = it == 0;
+        HIP_TRY(gl::launch_stft_update(st, d, B, stream));
+    }
+    is.y = wav_out;
+    HIP_TRY(gl::launch_istft(is, d, B, stream));
+    return IRIS_HIFIGAN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t iris_griffin_lim_design(const iris_griffin_lim_config* cfg, int32_t* n_bins, float* dft_host, uint64_t dft_floats,
+                                float* idft_host, uint64_t idft_floats, float* fb_host, uint64_t fb_floats, float* wsq_host,
+                                uint64_t wsq_floats) {
+    IRIS_ABI_BEGIN
+    gl::Design d;
+    TRY(gl_validate(cfg, &d));
+    if (n_bins) *n_bins = d.bins();
+    const uint64_t table = (uint64_t)2 * d.bins() * d.m.n_fft;
+    if ((dft_host && dft_floats < table) || (idft_host && idft_floats < table) || (fb_host && fb_floats < (uint64_t)d.m.n_mels * d.bins()) ||
+        (wsq_host && wsq_floats < (uint64_t)d.m.n_fft))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "a table does not fit its array: the DFT tables have %llu floats each, the filterbank "
+                    "%llu, the squared window %d", (unsigned long long)table, (unsigned long long)d.m.n_mels * d.bins(), d.m.n_fft);
+    if (dft_host) mel::fill_dft(d.m, dft_host);
+    if (idft_host) gl::fill_idft(d.m, idft_host);
+    if (fb_host) mel::fill_filterbank(d.m, fb_host);
+    if (wsq_host) gl::fill_wsq(d.m, wsq_host);
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_create(const iris_griffin_lim_config* cfg, const float* pinv_host, uint64_t n_pinv, iris_griffin_lim_handle** out) {
+    IRIS_ABI_BEGIN
+    if (!out || !pinv_host) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(gl_validate(cfg, &d));
+    const int nb = d.bins(), M = d.m.n_mels, N = d.m.n_fft;
+    if (n_pinv != (uint64_t)nb * M)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "pinv(fb) [n_bins][n_mels] has %llu values, got %llu", (unsigned long long)nb * M,
+                    (unsigned long long)n_pinv);
+    std::unique_ptr<iris_griffin_lim_handle> h(new (std::nothrow) iris_griffin_lim_handle);
+    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    h->d = d;
+    std::vector<float> dft((size_t)2 * nb * N), idft((size_t)2 * nb * N), fbank((size_t)M * nb), fbt((size_t)nb * M), w;
+    mel::fill_dft(d.m, dft.data());
+    gl::fill_idft(d.m, idft.data());
+    mel::fill_filterbank(d.m, fbank.data());
+    for (int i = 0; i < M; ++i)
+        for (int k = 0; k < nb; ++k) fbt[(size_t)k * M + i] = fbank[(size_t)i * nb + k];
+    int widest = 32 * d.m.dft_tiles();
+    for (int v : {32 * d.hop_tiles(), M, nb}) widest = v > widest ? v : widest;
+    const std::vector<float> no_bias(widest, 0.f);                           // no GEMM here has one
+    BlobBuilder bb(nullptr);
+    bb.dense(h->p, pinv_host, no_bias.data(), M, nb, 1);
+    bb.dense(h->fb, fbank.data(), no_bias.data(), nb, M, 1);
+    bb.dense(h->fbt, fbt.data(), no_bias.data(), M, nb, 1);
+    mel::conv_weight_from_dft(d.m, dft.data(), w);
+    bb.dense(h->dft, w.data(), no_bias.data(), d.m.hop, 32 * d.m.dft_tiles(), d.m.taps());
+    gl::conv_weight_from_idft(d, idft.data(), w);
+    bb.dense(h->idft, w.data(), no_bias.data(), d.q(), 32 * d.hop_tiles(), d.m.taps());
+    h->wsq_off = bb.reserve(N);
+    gl::fill_wsq(d.m, bb.host.data() + h->wsq_off);
+    TRY(upload(bb.host, h.get(), "Griffin-Lim"));
+    *out = h.release();
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_destroy(iris_griffin_lim_handle* h) {
+    delete h;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_griffin_lim_workspace_bytes(const iris_griffin_lim_config* cfg, int32_t B, int32_t T, uint64_t* bytes) {
+    IRIS_ABI_BEGIN
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(gl_validate(cfg, &d));
+    TRY(gl_check_shape(B, T));
+    *bytes = (uint64_t)GlWorkspace(d, B, T).floats * sizeof(float);
+    if (*bytes < 256) *bytes = 256;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_launch_count(const iris_griffin_lim_config* cfg, int32_t B, int32_t T, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(gl_validate(cfg, &d));
+    TRY(gl_check_shape(B, T));
+    *n = 0;
+    if (B == 0) return IRIS_HIFIGAN_OK;
+    return count_launches([&](float* fake) {
+        const GlTables tb = {fake, fake, fake, fake, fake, fake};
+        return gl_forward(d, tb, fake, fake, B, T, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_forward(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, int32_t B, int32_t T,
+                                 float* wav_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(gl_check_shape(B, T));
+    if (B == 0) return IRIS_HIFIGAN_OK;
+    if (!logmel_dev || !phase0_dev || !wav_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    ForwardScope scope(*h, workspace_bytes, GlWorkspace(h->d, B, T).floats);
+    TRY(scope.rc);
+    const GlTables tb = {h->blob + h->p.w_off, h->blob + h->fb.w_off, h->blob + h->fbt.w_off, h->blob + h->dft.w_off,
+                         h->blob + h->idft.w_off, h->blob + h->wsq_off};
+    return gl_forward(h->d, tb, logmel_dev, phase0_dev, B, T, wav_out_dev, (float*)workspace_dev, (hipStream_t)stream);
+    IRIS_ABI_END
+}
+
+}  // extern "C"

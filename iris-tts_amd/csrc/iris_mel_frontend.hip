@@ -18,8 +18,9 @@ struct iris_mel_frontend_handle : StageHandle {
     PackedGemm dft, fb;
 };
 
-namespace {
+namespace iris {
 
+// declared in mel_frontend.h: iris_griffin_lim.hip holds its config to the same rules
 int mel_validate(const iris_mel_frontend_config* c, mel::Design* d) {
     if (!c) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "config is NULL");
     if (c->sample_rate < 1 || c->n_fft < 2 || c->hop_length < 1 || c->win_length < 1 || c->n_mels < 1)
@@ -42,6 +43,10 @@ int mel_validate(const iris_mel_frontend_config* c, mel::Design* d) {
                     (unsigned long long)d->lds_bytes(), (unsigned long long)mel::kMaxLdsBytes);
     return IRIS_HIFIGAN_OK;
 }
+
+}  // namespace iris
+
+namespace {
 
 int mel_check_shape(int32_t B, int32_t L) {
     if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");

@@ -42,6 +42,8 @@
 
 #include "packed_conv_f32.h"
 
+struct iris_mel_frontend_config;
+
 namespace iris {
 namespace mel {
 
@@ -133,6 +135,10 @@ inline void conv_weight_from_dft(const Design& d, const float* dft, std::vector<
 }
 
 }  // namespace mel
+
+// Checks a config and fills the design (iris_mel_frontend.hip): IRIS_HIFIGAN_OK, or the status of the rule it breaks.
+int mel_validate(const ::iris_mel_frontend_config* c, mel::Design* d);
+
 }  // namespace iris
 
 #ifdef __HIPCC__

@@ -288,6 +288,26 @@ MEL_SYMBOLS = {
     "iris_mel_frontend_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
+
+class GriffinLimConfig(ctypes.Structure):
+    """``iris_griffin_lim_config``"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "n_fft", "hop_length", "win_length", "n_mels", "n_iter")] + [
+        ("fmin", ctypes.c_double), ("fmax", ctypes.c_double), ("nnls_iters", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("momentum", ctypes.c_double), ("nnls_step", ctypes.c_double)]
+
+
+# the Griffin-Lim vocoder (iris.griffin_lim): bound by load() like SYMBOLS
+_glc = _c.POINTER(GriffinLimConfig)
+GRIFFIN_LIM_SYMBOLS = {
+    "iris_griffin_lim_design": (_i32, [_glc, _ip, _fp, _u64, _fp, _u64, _fp, _u64, _fp, _u64]),
+    "iris_griffin_lim_workspace_bytes": (_i32, [_glc, _i32, _i32, _u64p]),
+    "iris_griffin_lim_launch_count": (_i32, [_glc, _i32, _i32, _ip]),
+    "iris_griffin_lim_create": (_i32, [_glc, _fp, _u64, _c.POINTER(_vp)]),
+    "iris_griffin_lim_destroy": (_i32, [_vp]),
+    "iris_griffin_lim_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -313,7 +333,8 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS}.items():
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
+                                      **GRIFFIN_LIM_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -31,7 +31,12 @@ class MelToWavePipeline:
     ``(iris.encoder.PhonemeEncoder, iris.encoder.DurationPredictor)`` for ``infer_from_phonemes``, or None.  ``posterior``:
     an ``iris.vae.VAEPosteriorEncoder`` (or any callable ``(mel, frame_cond) -> (device recon [B, n_mels, T], ...)``) for
     ``resynthesize``, or None.  ``frontend``: an ``iris.mel.MelFrontend`` (or any callable ``(audio [B, L], lengths=,
-    max_frames=) -> (device mel [B, n_mels, T], frames [B])``) for ``mel_from_audio`` and ``resynthesize_from_audio``, or None."""
+    max_frames=) -> (device mel [B, n_mels, T], frames [B])``) for ``mel_from_audio`` and ``resynthesize_from_audio``, or None.
+
+    ``vocode`` may also be an ``iris.griffin_lim.GriffinLim`` (any object with ``whole_utterance = True`` and a
+    ``forward_device``): text to waveform with no trained vocoder.  Such a vocoder takes the whole mel in one call -- every
+    sample depends on every frame, so nothing is chunked and ``stream`` / ``session`` are refused -- and decides the length of
+    its output itself (``hop * (T - 1)`` samples); a batch of unequal lengths raises ``NotImplementedError``."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -45,6 +50,9 @@ class MelToWavePipeline:
         if config is None:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
         self.config = config
+        self._whole = vocode if getattr(vocode, "whole_utterance", False) else None
+        if self._whole is not None and hop_length is None:
+            hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
                                          halo_frames=halo_frames, group_chunks=group_chunks, config=config)
 
@@ -70,7 +78,20 @@ class MelToWavePipeline:
 
     def stream(self, mel) -> Iterator[torch.Tensor]:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``."""
+        if self._whole is not None:
+            raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         yield from self.streamer.stream(self.refine(mel))
+
+    def _vocode_whole(self, mel: torch.Tensor, pcm16: bool, normalize: bool, resampler):
+        """One call of a whole-utterance vocoder, then the stand-alone output stages on its waveform, whose length is the
+        tensor's own: ``Resampler.forward``, or ``synthesis_output.pcm16_on_device`` (``(pcm, peaks)`` with ``normalize``)."""
+        wav = self._whole.forward_device(mel)
+        if resampler is not None:
+            return resampler.forward(wav, pcm16=pcm16, normalize=normalize)
+        if not pcm16:
+            return wav
+        from .synthesis_output import pcm16_on_device
+        return pcm16_on_device(wav, normalize=normalize)
 
     def _pcm16_fn(self) -> Callable:
         fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_pcm16", None)
@@ -97,6 +118,8 @@ class MelToWavePipeline:
         result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
+        if self._whole is not None:
+            return self._vocode_whole(self.refine(mel), pcm16, normalize, resampler)
         if resampler is not None:
             fwd = self._resampled_fn()
             if pcm16:
@@ -265,7 +288,8 @@ class MelToWavePipeline:
         """Phoneme ids ``[B, P]`` -> ``(what infer returns, frames_per_item)``: phoneme encoder, duration head and length
         regulator (``iris.encoder.frame_conditioning``, reference scripts/synthesize.py:93-122), then ``infer_from_cond``.
         The conditioning is padded to ``acoustic.downsample_factor`` frames, as the reference pads it, and so is the audio:
-        item i has ``hop * ceil(frames_per_item[i] / factor) * factor`` samples.  ``durations`` (integer ``[B, P]``)
+        item i has ``hop * T_i`` samples with ``T_i = ceil(frames_per_item[i] / factor) * factor`` (``hop * (T_i - 1)`` from a
+        whole-utterance vocoder, ``iris.griffin_lim``).  ``durations`` (integer ``[B, P]``)
         replaces the duration head's prediction.
 
         ``B == 1``: one chain on one stream; the only read-back is the frame total.  ``B > 1``: every stage runs ONCE over
@@ -330,9 +354,15 @@ class MelToWavePipeline:
         if not mels:
             return []
         padded, lengths = pack_mels(mels)
+        if self._whole is not None and len(set(int(n) for n in lengths)) > 1:
+            raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) takes items of one length: an item's last frames "
+                                      "change its own STFT, and no ragged form is built; call infer once per length")
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
+        if self._whole is not None:
+            out = self._vocode_whole(padded, pcm16, normalize, resampler)
+            return list((out[0] if normalize else out).unbind(0))
         if resampler is not None:
             wav = self._resampled_fn()(padded, resampler, lengths=lengths, pcm16=pcm16, normalize=normalize)
             wav = wav[0] if normalize else wav
@@ -348,6 +378,8 @@ class MelToWavePipeline:
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
         """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
         PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own."""
+        if self._whole is not None:
+            raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         return PipelineSession(self, postnet_halo_frames)
 
 

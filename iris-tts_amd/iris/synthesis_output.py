@@ -80,6 +80,33 @@ def pcm16_from_float(audio, normalize: bool = False, peak_target: float = 0.95) 
     return np.round(np.clip(w, np.float32(-1.0), np.float32(1.0)) * np.float32(32767.0)).astype("<i2")
 
 
+def pcm16_on_device(wav, normalize: bool = False, peak_target: float = 0.95):
+    """The device output stage on a waveform that already exists (``iris_hifigan_op_pcm16``, csrc/pcm_out.h): an fp32 device
+    tensor ``[B, L]`` -> int16 ``[B, L]``, bit for bit ``pcm16_from_float(wav)``; with ``normalize`` every item is scaled to
+    ``peak_target`` at its own peak first and ``(pcm, peaks)`` is returned, ``peaks`` the fp32 tensor ``[B]`` of the items'
+    max |w|.  Asynchronous on the current stream.  For vocoders without an output stage of their own (``iris.griffin_lim``)."""
+    import ctypes
+
+    import torch
+
+    from . import _native
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_cuda:
+        raise ValueError(f"expected an fp32 device waveform [B, L], got {wav.dtype} {tuple(wav.shape)} on {wav.device}")
+    if normalize:
+        _check_peak_target(peak_target)
+    wav = wav.contiguous()
+    B, L = int(wav.shape[0]), int(wav.shape[1])
+    pcm = torch.empty((B, L), dtype=torch.int16, device=wav.device)
+    peaks = torch.zeros((B,), dtype=torch.float32, device=wav.device) if normalize else None
+    if B and L:
+        with torch.cuda.device(wav.device):
+            _native.check("iris_hifigan_op_pcm16", _native.load().iris_hifigan_op_pcm16(
+                ctypes.c_void_p(wav.data_ptr()), None, 1, ctypes.c_void_p(pcm.data_ptr()),
+                ctypes.c_void_p(None if peaks is None else peaks.data_ptr()), B, L, int(bool(normalize)),
+                ctypes.c_float(float(peak_target)), ctypes.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)))
+    return (pcm, peaks) if normalize else pcm
+
+
 RESAMPLE_TO_RANGE = (4000, 192000)     # what the device resampler admits (include/iris_hifigan.h)
 
 
