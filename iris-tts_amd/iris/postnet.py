@@ -120,6 +120,28 @@ class PostNet(_NativeModel):
             self._handle, _ptr(mel), B, T, _ptr(out), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device)))
         return out
 
+    def _workspace_layout(self, B: int, T: int):
+        """Test-only: ``postnet_ws`` (csrc/iris_hifigan.hip) restated: float offsets of hid[0], hid[1] ([B, T, channels]
+        each) and res ([B, T, n_mels]) and the total, every buffer starting on a 256-byte boundary (64 floats)."""
+        offs, off = [], 0
+        for n in (B * T * self.channels, B * T * self.channels, B * T * self.n_mels):
+            offs.append(off)
+            off += (n + 63) & ~63
+        return offs[0], offs[1], offs[2], off
+
+    def _read_layers(self, B: int, T: int):
+        """Test-only: the layer outputs the last ``forward_device`` of shape (B, T) left in the workspace, as
+        ({layer index: [B, T, C] copy}, bytes of the layout).  Layer i wrote hid[i & 1] and the last layer res, so what
+        survives is every layer of a 2- or 3-layer net and the layers L-3, L-2 and L-1 (res) of a deeper one."""
+        h0, h1, res, total = self._workspace_layout(B, T)
+        ws = self._workspace.view(torch.float32)
+        L = self.num_layers
+        out = {L - 1: ws[res:res + B * T * self.n_mels].clone().view(B, T, self.n_mels)}
+        for i in range(max(0, L - 3), L - 1):
+            off = h1 if i & 1 else h0
+            out[i] = ws[off:off + B * T * self.channels].clone().view(B, T, self.channels)
+        return out, 4 * total
+
     def __call__(self, mels_bt_f, training: bool = False) -> np.ndarray:
         """[B, n_mels, T] -> [B, n_mels, T] (input + residual), reference postnet.py:48-67."""
         if training:

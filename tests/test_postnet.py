@@ -1,5 +1,10 @@
 """PostNet on device against the numpy restatement of the reference's
-Keras model (oracle/postnet_oracle.py).  Parity unpinned by the reference (Keras-only, no vectors)."""
+Keras model (oracle/postnet_oracle.py).  Parity unpinned by the reference (Keras-only, no vectors).
+
+The end-to-end bar is ``min(2e-5, 4 * e32)`` relative to max(1, max |want|), e32 being the restatement's own fp32 error on
+exactly the case's inputs (oracle/postnet_oracle.e32).  Measured (e32 on the CPU, err on an MI355X): 2x333 e32 3.64e-07 err
+1.15e-06; 1x1000 e32 3.71e-07 err 9.46e-07; 3x17 e32 8.53e-08 err 1.20e-07; 1x1 e32 6.88e-08 err 1.69e-07.  Launch by launch
+the PostNet is held to its fmaf chain in tests/test_gpu_postnet_chain.py."""
 import numpy as np
 import pytest
 import torch
@@ -64,7 +69,12 @@ def test_postnet_matches_oracle_gpu(n_mels, layers, ch, k, B, T):
     got = pn(mel)
     want = porc.postnet_forward_np(pn.weights, mel, layers)
     assert got.shape == mel.shape and got.dtype == np.float32
-    assert np.abs(got - want).max() <= 2e-5 * max(1.0, np.abs(want).max())
+    # the bar: 4 x the reference's own fp32 error on exactly these inputs (the numpy restatement in fp32 against itself in
+    # fp64), and never above the fixed 2e-5 it replaces
+    e32 = porc.e32(pn.weights, mel, layers)
+    err = np.abs(got - want).max() / max(1.0, np.abs(want).max())
+    print(f"postnet {n_mels}/{layers}/{ch}/k{k} {B}x{T}: err {err:.3e} e32 {e32:.3e} bar {min(2e-5, 4 * e32):.3e}")
+    assert err <= min(2e-5, 4 * e32), (err, e32)
     # device tensor in -> device tensor out, and it chains straight into the vocoder's input layout
     dev_out = pn(torch.from_numpy(mel).cuda())
     assert dev_out.is_cuda and np.array_equal(dev_out.cpu().numpy(), got)

@@ -147,9 +147,13 @@ def test_ragged_postnet_against_oracle(postnet):
     mel = seeded_mel(1003, 3, 120, log_mel=True)
     got = postnet.forward_device(torch.from_numpy(mel).cuda(), lengths=lengths).cpu().numpy()
     for b, n in enumerate(lengths):
-        want = porc.postnet_forward_np(postnet.weights, np.ascontiguousarray(mel[b:b + 1, :, :n]), 3)[0]
-        # the bar tests/test_postnet.py sets for the plain forward
-        assert np.abs(got[b, :, :n] - want).max() <= 2e-5 * max(1.0, np.abs(want).max())
+        item = np.ascontiguousarray(mel[b:b + 1, :, :n])
+        want = porc.postnet_forward_np(postnet.weights, item, 3)[0]
+        # the bar tests/test_postnet.py sets for the plain forward: 4 x the reference's own fp32 error on this item, at most 2e-5
+        e32 = porc.e32(postnet.weights, item, 3)
+        err = np.abs(got[b, :, :n] - want).max() / max(1.0, np.abs(want).max())
+        print(f"ragged postnet item {b} ({n} frames): err {err:.3e} e32 {e32:.3e} bar {min(2e-5, 4 * e32):.3e}")
+        assert err <= min(2e-5, 4 * e32), (err, e32)
         assert not got[b, :, n:].any()
 
 
