@@ -119,8 +119,9 @@ int vae_forward(iris_vae_decoder_handle* h, const float* cond, const float* z, i
         a.stride = 2; a.pad_left = 1; a.gelu = 1;
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }
-    // every Dense(lat_cond) of the decoder at once: FiLM rows of each block, cond_proj of each coupling
-    {
+    // every Dense(lat_cond) of the decoder at once: FiLM rows of each block, cond_proj of each coupling.  No block and no
+    // coupling: no column, no launch (the flow reads no `cond` column when n_flow == 0).
+    if (h->film_cols > 0) {
         vae::GemmLaunch a = gemm(ws + w.latcond, h->cond_gemm, ws + w.film, Tq, Tq, S, S);
         HIP_TRY(vae::launch_gemm(a, B, false, stream));
     }

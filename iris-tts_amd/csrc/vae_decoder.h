@@ -404,6 +404,7 @@ __global__ void __launch_bounds__(256) vae_flow_kernel(const FlowLaunch a) {
 #ifndef IRIS_KERNELS_ONLY
 // Fills Gp / n_ct and launches.  FUSED launches need every C_out tile in one block (C_out <= 32 * kGemmMaxWaves).
 inline hipError_t launch_gemm(GemmLaunch& a, int B, bool fused, hipStream_t stream, int form = kGemmPlain) {
+    if (a.C_in < 1 || a.C_out < 1) return hipErrorInvalidValue;   // no C_out tile: no wave, and the grid below divides by the waves
     a.Gp = packed_groups(a.C_in);
     a.n_ct = packed_cotiles(a.C_out);
     a.Gp2 = packed_groups(a.C_out);

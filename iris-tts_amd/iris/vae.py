@@ -90,6 +90,20 @@ def _lengths_on(lengths, device) -> torch.Tensor:
     return lengths.to(device).contiguous()
 
 
+def _take_buffers(sizes):
+    """``WsTaker`` (csrc/stage_host.h): the buffers one behind the other, each rounded up to 64 floats."""
+    layout, off = {}, 0
+    for name, n in sizes:
+        layout[name] = (off, n)
+        off += (n + 63) & ~63
+    return layout, off
+
+
+def _read_buffers(model, layout, total):
+    ws = model._workspace.view(torch.float32)
+    return {name: ws[off:off + n].clone() for name, (off, n) in layout.items()}, 4 * total
+
+
 class TextConditionedVAE(_NativeModel):
     _abi_name = "vae_decoder"
 
@@ -301,6 +315,22 @@ class TextConditionedVAE(_NativeModel):
         raw = self._workspace[off.value:off.value + 4 * n.value].clone()
         return raw.view(torch.float32).view(B, T // self.downsample_factor, self.model_channels)
 
+    def _workspace_layout(self, B: int, T: int):
+        """Test-only: ``vae_ws`` (csrc/iris_vae_decoder.hip) restated -- ``({buffer: (float offset, floats)}, total floats)``
+        in the struct's order: p, q (frames x C), latcond (latent rows x C), film (latent rows x film_cols), d0, da, db
+        (latent rows x C).  Needs no device."""
+        C, frames = self.model_channels, B * T
+        lat = frames >> self.down_stages
+        hp = (self.latent_dim // 2 + 3) & ~3
+        film_cols = self.decoder_blocks * 2 * C + self.flow_layers * hp
+        return _take_buffers((("p", frames * C), ("q", frames * C), ("latcond", lat * C), ("film", lat * film_cols),
+                              ("d0", lat * C), ("da", lat * C), ("db", lat * C)))
+
+    def _read_buffers(self, B: int, T: int):
+        """Test-only: every workspace buffer as the last forward of shape (B, T) left it -- ``({buffer: flat fp32 copy},
+        bytes of the layout)``.  Which launch wrote a buffer last is the reader's to know (``vae_forward``)."""
+        return _read_buffers(self, *self._workspace_layout(B, T))
+
     def __call__(self, mels_bt_f=None, frame_text_cond=None, training: bool = False):
         raise NotImplementedError("the MI355X build holds the inference half only (generate()): the encoder of "
                                   "TextConditionedVAE.call() and training are not built")
@@ -455,6 +485,18 @@ class VAEPosteriorEncoder(_NativeModel):
         _native.check("iris_vae_encoder_tap", lib.iris_vae_encoder_tap(self._handle, B, T, which, ctypes.byref(off), ctypes.byref(n)))
         raw = self._workspace[off.value:off.value + 4 * n.value].clone()
         return raw.view(torch.float32).view(B, -1, self.model_channels)
+
+    def _workspace_layout(self, B: int, T: int):
+        """Test-only: ``enc_ws`` (csrc/iris_vae_encoder.hip) restated, as ``TextConditionedVAE._workspace_layout``: film
+        (frames x N * 2C), h0, ha, hb (frames x C), d0 (frames / 2 x C), d1 (frames / 4 x C)."""
+        C, frames = self.model_channels, B * T
+        return _take_buffers((("film", frames * self.num_wavenet_blocks * 2 * C), ("h0", frames * C), ("ha", frames * C),
+                              ("hb", frames * C), ("d0", (frames >> 1) * C), ("d1", (frames >> 2) * C)))
+
+    def _read_buffers(self, B: int, T: int):
+        """Test-only: every workspace buffer as the last ``encode_device`` of shape (B, T) left it (``enc_forward``) --
+        ``({buffer: flat fp32 copy}, bytes of the layout)``."""
+        return _read_buffers(self, *self._workspace_layout(B, T))
 
 
 _SHARED_SIZES = ("n_mels", "cond_dim", "model_channels", "latent_dim", "down_stages")
