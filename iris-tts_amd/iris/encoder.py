@@ -54,6 +54,7 @@ import torch
 from . import _native
 from ._engine import require_gpu
 from ._native_model import _NativeModel, _ptr, _stream
+from .vae import _read_buffers, _take_buffers
 
 DEFAULT_MAX_FRAMES = 65536          # frames of one utterance batch item that frame_conditioning accepts by default
 
@@ -242,6 +243,18 @@ class PhonemeEncoder(_TextModel):
         """Test-only: the output of block 0 the last ``forward_device`` of shape (B, P) left in the workspace (a copy)."""
         return self._read_tap(B, P, self.embed_dim)
 
+    def _workspace_layout(self, B: int, P: int):
+        """Test-only: ``enc_ws`` (csrc/iris_text_encoder.hip) restated -- ``({buffer: (float offset, floats)}, total floats)``
+        in the struct's order: x0, x1, t0 (rows x E), qkv (rows x 3E), attn (rows x E), ffn (rows x ffn_dim).  Needs no device."""
+        rows, E = B * P, self.embed_dim
+        return _take_buffers((("x0", rows * E), ("x1", rows * E), ("t0", rows * E), ("qkv", rows * 3 * E), ("attn", rows * E),
+                              ("ffn", rows * self.ffn_dim)))
+
+    def _read_buffers(self, B: int, P: int):
+        """Test-only: every workspace buffer as the last ``forward_device`` of shape (B, P) left it -- ``({buffer: flat fp32
+        copy}, bytes of the layout)``.  Which launch wrote a buffer last is the reader's to know (``enc_forward``)."""
+        return _read_buffers(self, *self._workspace_layout(B, P))
+
 
 class DurationPredictor(_TextModel):
     """``in_dim``: channels of the encoder output (Keras builds the first conv lazily; ``hidden_dim`` when omitted, as in the
@@ -336,6 +349,16 @@ class DurationPredictor(_TextModel):
     def _read_layer0(self, B: int, P: int) -> torch.Tensor:
         """Test-only: the output of the first layer the last ``forward_device`` of shape (B, P) left in the workspace."""
         return self._read_tap(B, P, self.hidden_dim)
+
+    def _workspace_layout(self, B: int, P: int):
+        """Test-only: ``dur_ws`` restated, as ``PhonemeEncoder._workspace_layout``: d0, d1, d2 (rows x hidden_dim); layer 0
+        writes d0, the later layers alternate d2, d1."""
+        n = B * P * self.hidden_dim
+        return _take_buffers((("d0", n), ("d1", n), ("d2", n)))
+
+    def _read_buffers(self, B: int, P: int):
+        """Test-only, as ``PhonemeEncoder._read_buffers`` (``dur_forward``)."""
+        return _read_buffers(self, *self._workspace_layout(B, P))
 
 
 def create_encoder(vocab_size: int, embed_dim: int = 256, num_blocks: int = 4, num_heads: int = 4, **kwargs) -> PhonemeEncoder:
