@@ -756,6 +756,21 @@ int32_t iris_griffin_lim_create(const iris_griffin_lim_config* cfg, const float*
 int32_t iris_griffin_lim_destroy(iris_griffin_lim_handle* h);
 int32_t iris_griffin_lim_forward(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, int32_t B, int32_t T,
                                  float* wav_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+/* The ragged forward: lengths_dev [B] (device, or NULL: every item has T frames) holds the items' frame counts.  Item b has
+ * T_b = min(max(lengths[b], 0), T) frames, 0 if that is below 2 (an empty item); its samples wav[b, :hop_length * (T_b - 1)] are
+ * bit for bit its batch-of-one dense call on logmel[b, :, :T_b] and its phase rows, and wav[b, hop_length * (T_b - 1):] is stored
+ * as 0.0f.  Nothing of logmel, phase0 or the workspace at frames t >= T_b is read or written.  The lengths are never read by the
+ * host: a captured graph follows new contents of lengths_dev.  Strides, the workspace and the launch count are the dense call's.
+ * phase0_dev may be NULL: the start phase is then drawn on the device -- Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ * and counter (k >> 2, t, item0 + b, 0), output word k & 3 for bin k of frame t of item b; u = (x >> 8) * 2^-24, angle =
+ * 6.2831855f * u in fp32, phase = (cosf, sinf) of it -- and depends on no batch position but item0 + b (item0 >= 0).  seed and
+ * item0 are ignored otherwise.  draw_phase stores the same draw as the packed phase_out_dev [B][T][n_bins][2] (one launch).
+ * Status rules as for iris_griffin_lim_forward, checked before anything is launched. */
+int32_t iris_griffin_lim_forward_ragged(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, uint64_t seed,
+                                        int32_t item0, int32_t B, int32_t T, const int32_t* lengths_dev, float* wav_out_dev,
+                                        void* workspace_dev, uint64_t workspace_bytes, void* stream);
+int32_t iris_griffin_lim_draw_phase(iris_griffin_lim_handle* h, uint64_t seed, int32_t item0, int32_t B, int32_t T, float* phase_out_dev,
+                                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,18 @@
 // lane) with the phase update as its epilogue; it stores the new c and keeps r for the next pass.  grid.z counts groups of 8
 // column tiles, so a wave runs one tile.
 //
+// Ragged batches: each kernel takes `lengths` (a device pointer to [B] frame counts, or NULL: every item has T frames).  A
+// block reads T_b = min(max(lengths[b], 0), T), 0 if that is below 2, and Ly_b = H (T_b - 1), and bounds its loads, its
+// window-sum-square terms and its stores by them; strides stay T and H (T - 1), and the tiling (i0 = 32 blockIdx.x,
+// j0 = first_row + 32 blockIdx.x) does not depend on T, so every chain of item b has the terms and the order of its
+// batch-of-one call at T = T_b.  A block past its item returns before its first barrier.  Nothing at t >= T_b is read or
+// written, except that the last inverse transform (zero_tail) stores 0.f to wav[b, Ly_b:].
+//
+// Start phase: with phase0 == NULL the inversion draws it in its epilogue -- Philox4x32-10, key (seed & 0xffffffff, seed >> 32),
+// counter (k >> 2, t, stream, 0) with output word k & 3 for bin k of frame t; u = (x >> 8) 2^-24, angle = 6.2831855f * u (one
+// fp32 product), phase = (cosf, sinf) of it.  A counter-based draw depends on no grid shape or batch position: item b of a call
+// uses stream item0 + b.  gl_draw_phase_kernel stores the same numbers as a packed [B][T][bins][2] tensor.
+//
 // Summation: the MFMA adds a chain's terms one after the other, and a chain of n_fft / hop * (n_fft + 2) = 4104 terms (the
 // inverse STFT at the defaults) loses more than the blocked sums of a host BLAS.  Both transforms therefore run short chains
 // and add the partial sums: one per tap and 64 columns (inverse) or 64 samples (forward).  The normalisation a / |a| amplifies
@@ -112,9 +124,65 @@ inline void conv_weight_from_idft(const Design& d, const float* idft, std::vecto
 namespace iris {
 namespace gl {
 
+// T_b of item b: `lengths` sanitised as the header says; NULL: T.
+__device__ __forceinline__ int item_frames(const int* lengths, int b, int T) {
+    if (!lengths) return T;
+    int n = lengths[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+    return n < 2 ? 0 : n;
+}
+
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped by the Weyl constants between them.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// The start phase of bins 4 k4 .. 4 k4 + 3 of frame t of item stream `stream`: (cos, sin) per bin.
+__device__ __forceinline__ void draw_phase4(uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, int t, int k4, float2 (&ph)[4]) {
+    uint32_t c[4] = {(uint32_t)k4, (uint32_t)t, stream, 0u};
+    philox4x32_10(c, seed_lo, seed_hi);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float u = (float)(c[e] >> 8) * 0x1p-24f;
+        const float ang = 6.2831855f * u;
+        ph[e] = make_float2(cosf(ang), sinf(ang));
+    }
+}
+
+struct DrawLaunch {
+    float* phase;             // [B, T, bins, 2] out
+    int T, bins;
+    uint32_t seed_lo, seed_hi, item0;
+};
+
+__global__ void __launch_bounds__(256) gl_draw_phase_kernel(const DrawLaunch a) {
+    const int b = blockIdx.y, i0 = blockIdx.x * kRows, groups = (a.bins + 3) >> 2;
+    for (int idx = threadIdx.x; idx < kRows * groups; idx += 256) {
+        const int r = idx / groups, k4 = idx - r * groups, t = i0 + r;
+        if (t >= a.T) break;
+        float2 ph[4];
+        draw_phase4(a.seed_lo, a.seed_hi, a.item0 + (uint32_t)b, t, k4, ph);
+        float2* row = reinterpret_cast<float2*>(a.phase) + ((size_t)b * a.T + t) * a.bins;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (4 * k4 + e < a.bins) row[4 * k4 + e] = ph[e];
+    }
+}
+
 struct InvertLaunch {
     const float* logmel;      // [B, n_mels, T]
-    const float* phase0;      // [B, T, bins, 2]: cos, sin
+    const float* phase0;      // [B, T, bins, 2]: cos, sin; NULL: drawn here from (seed, item0 + b)
+    const int* lengths;       // [B] or NULL
     const f32x4* wp;          // packed P: C_in n_mels, C_out bins
     const f32x4* wfb;         // packed fb: C_in bins, C_out n_mels
     const f32x4* wfbt;        // packed fb^T: C_in n_mels, C_out bins
@@ -123,6 +191,7 @@ struct InvertLaunch {
     int T, n_mels, bins, Ks, Qp, nnls_iters;
     float step;
     int GpM, nctK, GpK, nctM;
+    uint32_t seed_lo, seed_hi, item0;
 };
 
 __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaunch a) {
@@ -135,11 +204,13 @@ __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaun
     float* m = lds;                       // [32][SM]  exp(clip(logmel)); columns from n_mels on are 0
     float* res = m + kRows * SM;          // [32][SM]  fb x - m
     float* x = res + kRows * SM;          // [32][SX]  the solution; columns from bins on are 0
+    const int Tb = item_frames(a.lengths, b, a.T);
+    if (i0 >= Tb) return;                 // block-uniform: all 32 frames lie past the item
 
     for (int idx = tid; idx < kRows * Mp; idx += nthr) {             // consecutive threads: consecutive frames of one channel
         const int ch = idx / kRows, r = idx - ch * kRows, t = i0 + r;
         float v = 0.f;
-        if (ch < a.n_mels && t < a.T) {
+        if (ch < a.n_mels && t < Tb) {
             double l = (double)a.logmel[((size_t)b * a.n_mels + ch) * a.T + t];
             l = l < kLogLo ? kLogLo : (l > kLogHi ? kLogHi : l);
             v = (float)exp(l);                                       // in double, rounded once (as the front-end takes its log)
@@ -199,9 +270,28 @@ __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaun
         __syncthreads();
     }
 
+    if (!a.phase0) {                                                 // S and c0 from the drawn phase, four bins at a time
+        const int groups = (a.bins + 3) >> 2;
+        for (int idx = tid; idx < kRows * groups; idx += nthr) {
+            const int r = idx / groups, k4 = idx - r * groups, t = i0 + r;
+            if (t >= Tb) break;
+            const size_t row = (size_t)b * a.T + t;
+            float2 ph[4];
+            draw_phase4(a.seed_lo, a.seed_hi, a.item0 + (uint32_t)b, t, k4, ph);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = 4 * k4 + e;
+                if (k >= a.bins) break;
+                const float s = x[r * SX + k];
+                a.S[row * a.Ks + k] = s;
+                reinterpret_cast<float2*>(a.c)[(row * a.Qp >> 1) + k] = make_float2(s * ph[e].x, s * ph[e].y);
+            }
+        }
+        return;
+    }
     for (int idx = tid; idx < kRows * a.bins; idx += nthr) {         // S and c0 = S (cos, sin)
         const int r = idx / a.bins, k = idx - r * a.bins, t = i0 + r;
-        if (t >= a.T) break;
+        if (t >= Tb) break;
         const size_t row = (size_t)b * a.T + t;
         const float s = x[r * SX + k];
         const float2 ph = reinterpret_cast<const float2*>(a.phase0)[row * a.bins + k];
@@ -215,7 +305,9 @@ struct IstftLaunch {
     const f32x4* widft;       // packed inverse table: `taps` taps, Gp groups, n_ct column tiles
     const float* wsq;         // [n_fft]
     float* y;                 // [B, Ly]
+    const int* lengths;       // [B] or NULL
     int T, Ly, hop, taps, n_fft, Q, Qp, Gp, n_ct, first_row;
+    int zero_tail;            // the last transform of a ragged forward: y[b, Ly_b:] = 0
 };
 
 __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
@@ -228,6 +320,22 @@ __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch
     const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
     const int R = kRows - 1 + a.taps, S = kSlice + 4;
     const int t0 = j0 - (a.taps - 1);                        // LDS row r holds frame t0 + r
+    const int Tb = item_frames(a.lengths, b, a.T);
+    const int Lyb = Tb ? a.hop * (Tb - 1) : 0;               // a.Ly of a dense call
+    const long long s_first = (long long)j0 * a.hop - (a.n_fft >> 1);     // the block's first sample; negative ones are trimmed
+    if (Lyb <= (s_first > 0 ? s_first : 0)) {                // block-uniform: every row lies past the item
+        if (a.zero_tail && ct < a.n_ct) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int col = ct * 32 + 8 * g + 4 * hi + e;
+                    const long long s = s_first + (long long)lo * a.hop + col;
+                    if (col < a.hop && s >= 0 && s < a.Ly) a.y[(size_t)b * a.Ly + (size_t)s] = 0.f;
+                }
+        }
+        return;
+    }
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -237,7 +345,7 @@ __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch
         for (int idx = tid; idx < R * (kSlice / 4); idx += nthr) {
             const int r = idx / (kSlice / 4), q = q0 + 4 * (idx - r * (kSlice / 4)), t = t0 + r;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (t >= 0 && t < a.T && q < a.Qp) {
+            if (t >= 0 && t < Tb && q < a.Qp) {
                 v = *reinterpret_cast<const f32x4*>(a.c + ((size_t)b * a.T + t) * a.Qp + q);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = q + e < a.Q ? v[e] : 0.f;
@@ -269,10 +377,14 @@ __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch
             const int col = ct * 32 + 8 * g + 4 * hi + e;
             const long long s = (long long)j * a.hop + col - half;
             if (col >= a.hop || s < 0 || s >= a.Ly) continue;
+            if (s >= Lyb) {
+                if (a.zero_tail) a.y[(size_t)b * a.Ly + (size_t)s] = 0.f;
+                continue;
+            }
             float wss = 0.f;
             for (int kap = 0; kap < a.taps; ++kap) {
                 const int t = j - kap;
-                if (t >= 0 && t < a.T) wss += a.wsq[kap * a.hop + col];
+                if (t >= 0 && t < Tb) wss += a.wsq[kap * a.hop + col];
             }
             const float v = acc[4 * g + e];
             a.y[(size_t)b * a.Ly + (size_t)s] = wss > FLT_MIN ? v / wss : v;
@@ -285,6 +397,7 @@ struct StftLaunch {
     const float* S;           // [B, T, Ks]
     float* c;                 // [B, T, Qp] out
     float* r;                 // [B, T, Qp] r_prev in (unless first), r out
+    const int* lengths;       // [B] or NULL
     int Ly, T, hop, taps, n_fft, Ks, Qp, Gp, n_ct, first;
     float alpha;
 };
@@ -304,6 +417,9 @@ __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftL
     const int b = blockIdx.y, i0 = blockIdx.x * kRows;
     const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
     const int H = a.hop, Cp = (H + 7) & ~7, S = Cp + 4, R = kRows - 1 + a.taps, half = a.n_fft >> 1;
+    const int Tb = item_frames(a.lengths, b, a.T);
+    if (i0 >= Tb) return;                                    // block-uniform: all 32 frames lie past the item
+    const int Lyb = H * (Tb - 1);                            // a.Ly of a dense call
 
     {   // the front-end's window: row r, column c is sample i0 * hop - n_fft / 2 + r * hop + c; 0 outside [0, Ly)
         const long long s0 = (long long)i0 * H - half;
@@ -311,7 +427,7 @@ __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftL
         for (int idx = tid; idx < R * Cp; idx += nthr) {
             const int r = idx / Cp, c = idx - r * Cp;
             const long long s = s0 + (long long)r * H + c;
-            lds[r * S + c] = (c < H && s >= 0 && s < a.Ly) ? a.y[item + (size_t)s] : 0.f;
+            lds[r * S + c] = (c < H && s >= 0 && s < Lyb) ? a.y[item + (size_t)s] : 0.f;
         }
     }
     __syncthreads();
@@ -329,7 +445,7 @@ __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftL
                      (size_t)a.n_ct * 64, a.Gp, 1, (Cp >> 3) - g0 < 8 ? (Cp >> 3) - g0 : 8);
             acc += part;
         }
-    if (t >= a.T) return;
+    if (t >= Tb) return;
 
     // registers 4g + e: g < 2 Re, g >= 2 Im of bin 16 ct + 8 g + 4 (lane >> 5) + e; the Im column of bin 0 is Re of bin n_fft / 2
     const size_t row = (size_t)b * a.T + t;
@@ -376,6 +492,11 @@ inline hipError_t launch_invert(InvertLaunch& a, const Design& d, int B, hipStre
     a.GpK = packed_groups(d.bins()); a.nctM = packed_cotiles(d.m.n_mels);
     const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B), block(64 * kWaves);
     return launch_kernel_named("gl_invert_kernel", gl_invert_kernel, grid, block, d.invert_lds_bytes(), stream, a);
+}
+
+inline hipError_t launch_draw_phase(const DrawLaunch& a, int B, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B), block(256);
+    return launch_kernel_named("gl_draw_phase_kernel", gl_draw_phase_kernel, grid, block, 0, stream, a);
 }
 
 inline hipError_t launch_istft(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {

@@ -1,6 +1,7 @@
 // iris_griffin_lim.hip -- the iris_griffin_lim_* entry points of include/iris_hifigan.h: log-mel [B, n_mels, T] to a waveform
 // [B, hop (T - 1)] by mel inversion and Griffin-Lim phase retrieval (csrc/griffin_lim.h), the reference's --use_griffin_lim
-// path (scripts/synthesize.py:174-194).  2 * n_iter + 2 launches: the inversion, n_iter times (inverse STFT, STFT with the phase
+// path (scripts/synthesize.py:174-194); iris_griffin_lim_forward_ragged adds per-item frame counts and a start phase drawn on
+// the device, through the same host routine.  2 * n_iter + 2 launches: the inversion, n_iter times (inverse STFT, STFT with the phase
 // update), and the last inverse STFT.  The handle owns the packed tables: P = pinv(fb) from the caller, fb both ways round, the
 // front-end's windowed DFT and the windowed inverse DFT, and w^2.
 #include <hip/hip_runtime.h>
@@ -75,28 +76,47 @@ struct GlWorkspace {
 
 struct GlTables { const float *p, *fb, *fbt, *dft, *idft, *wsq; };
 
-// Queues the forward's launches (or, in a dry run, counts them).
-int gl_forward(const gl::Design& d, const GlTables& tb, const float* logmel, const float* phase0, int B, int T, float* wav_out,
-               float* ws, hipStream_t stream) {
+// Queues the forward's launches (or, in a dry run, counts them).  `lengths` (device, or NULL: dense) is handed to every launch
+// and never read here; `seed` and `item0` matter when `phase0` is NULL.
+int gl_forward(const gl::Design& d, const GlTables& tb, const float* logmel, const float* phase0, uint64_t seed, int32_t item0,
+               int B, int T, const int32_t* lengths, float* wav_out, float* ws, hipStream_t stream) {
     const GlWorkspace lay(d, B, T);
     gl::InvertLaunch inv; memset(&inv, 0, sizeof(inv));
-    inv.logmel = logmel; inv.phase0 = phase0; inv.T = T;
+    inv.logmel = logmel; inv.phase0 = phase0; inv.lengths = lengths; inv.T = T;
+    inv.seed_lo = (uint32_t)seed; inv.seed_hi = (uint32_t)(seed >> 32); inv.item0 = (uint32_t)item0;
     inv.wp = (const f32x4*)tb.p; inv.wfb = (const f32x4*)tb.fb; inv.wfbt = (const f32x4*)tb.fbt;
     inv.S = ws + lay.S; inv.c = ws + lay.c;
     HIP_TRY(gl::launch_invert(inv, d, B, stream));
     gl::IstftLaunch is; memset(&is, 0, sizeof(is));
-    is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.T = T;
+    is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.lengths = lengths; is.T = T;
     gl::StftLaunch st; memset(&st, 0, sizeof(st));
     st.wdft = (const f32x4*)tb.dft; st.S = ws + lay.S; st.c = ws + lay.c; st.r = ws + lay.r; st.y = ws + lay.y; st.T = T;
+    st.lengths = lengths;
     for (int it = 0; it < d.n_iter; ++it) {
         is.y = ws + lay.y;
         HIP_TRY(gl::launch_istft(is, d, B, stream));
         st.first = it == 0;
         HIP_TRY(gl::launch_stft_update(st, d, B, stream));
     }
-    is.y = wav_out;
+    is.y = wav_out; is.zero_tail = lengths != nullptr;
     HIP_TRY(gl::launch_istft(is, d, B, stream));
     return IRIS_HIFIGAN_OK;
+}
+
+// What both forwards check, in one order, before anything is launched.
+int gl_forward_checked(iris_griffin_lim_handle* h, const float* logmel, const float* phase0, bool need_phase, uint64_t seed,
+                       int32_t item0, int32_t B, int32_t T, const int32_t* lengths, float* wav_out, void* workspace,
+                       uint64_t workspace_bytes, void* stream) {
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(gl_check_shape(B, T));
+    if (item0 < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative item0");
+    if (B == 0) return IRIS_HIFIGAN_OK;
+    if (!logmel || (need_phase && !phase0) || !wav_out || !workspace) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    ForwardScope scope(*h, workspace_bytes, GlWorkspace(h->d, B, T).floats);
+    TRY(scope.rc);
+    const GlTables tb = {h->blob + h->p.w_off, h->blob + h->fb.w_off, h->blob + h->fbt.w_off, h->blob + h->dft.w_off,
+                         h->blob + h->idft.w_off, h->blob + h->wsq_off};
+    return gl_forward(h->d, tb, logmel, phase0, seed, item0, B, T, lengths, wav_out, (float*)workspace, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -187,22 +207,41 @@ int32_t iris_griffin_lim_launch_count(const iris_griffin_lim_config* cfg, int32_
     if (B == 0) return IRIS_HIFIGAN_OK;
     return count_launches([&](float* fake) {
         const GlTables tb = {fake, fake, fake, fake, fake, fake};
-        return gl_forward(d, tb, fake, fake, B, T, fake, fake, nullptr); }, n);
+        return gl_forward(d, tb, fake, fake, 0, 0, B, T, nullptr, fake, fake, nullptr); }, n);
     IRIS_ABI_END
 }
 
 int32_t iris_griffin_lim_forward(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, int32_t B, int32_t T,
                                  float* wav_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
     IRIS_ABI_BEGIN
+    return gl_forward_checked(h, logmel_dev, phase0_dev, true, 0, 0, B, T, nullptr, wav_out_dev, workspace_dev, workspace_bytes, stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_forward_ragged(iris_griffin_lim_handle* h, const float* logmel_dev, const float* phase0_dev, uint64_t seed,
+                                        int32_t item0, int32_t B, int32_t T, const int32_t* lengths_dev, float* wav_out_dev,
+                                        void* workspace_dev, uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    return gl_forward_checked(h, logmel_dev, phase0_dev, false, seed, item0, B, T, lengths_dev, wav_out_dev, workspace_dev,
+                              workspace_bytes, stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_griffin_lim_draw_phase(iris_griffin_lim_handle* h, uint64_t seed, int32_t item0, int32_t B, int32_t T, float* phase_out_dev,
+                                    void* stream) {
+    IRIS_ABI_BEGIN
     if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
     TRY(gl_check_shape(B, T));
+    if (item0 < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative item0");
     if (B == 0) return IRIS_HIFIGAN_OK;
-    if (!logmel_dev || !phase0_dev || !wav_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    ForwardScope scope(*h, workspace_bytes, GlWorkspace(h->d, B, T).floats);
-    TRY(scope.rc);
-    const GlTables tb = {h->blob + h->p.w_off, h->blob + h->fb.w_off, h->blob + h->fbt.w_off, h->blob + h->dft.w_off,
-                         h->blob + h->idft.w_off, h->blob + h->wsq_off};
-    return gl_forward(h->d, tb, logmel_dev, phase0_dev, B, T, wav_out_dev, (float*)workspace_dev, (hipStream_t)stream);
+    if (!phase_out_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    DeviceGuard guard(h->device, true);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    gl::DrawLaunch a; memset(&a, 0, sizeof(a));
+    a.phase = phase_out_dev; a.T = T; a.bins = h->d.bins();
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.item0 = (uint32_t)item0;
+    HIP_TRY(gl::launch_draw_phase(a, B, (hipStream_t)stream));
+    return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
 

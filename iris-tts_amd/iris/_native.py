@@ -306,6 +306,8 @@ GRIFFIN_LIM_SYMBOLS = {
     "iris_griffin_lim_create": (_i32, [_glc, _fp, _u64, _c.POINTER(_vp)]),
     "iris_griffin_lim_destroy": (_i32, [_vp]),
     "iris_griffin_lim_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _u64, _vp]),
+    "iris_griffin_lim_forward_ragged": (_i32, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_griffin_lim_draw_phase": (_i32, [_vp, _u64, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

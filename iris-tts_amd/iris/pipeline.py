@@ -36,7 +36,9 @@ class MelToWavePipeline:
     ``vocode`` may also be an ``iris.griffin_lim.GriffinLim`` (any object with ``whole_utterance = True`` and a
     ``forward_device``): text to waveform with no trained vocoder.  Such a vocoder takes the whole mel in one call -- every
     sample depends on every frame, so nothing is chunked and ``stream`` / ``session`` are refused -- and decides the length of
-    its output itself (``hop * (T - 1)`` samples); a batch of unequal lengths raises ``NotImplementedError``."""
+    its output itself (``hop * (T - 1)`` samples).  A batch of unequal lengths goes through ONE ragged call when the vocoder
+    says ``takes_lengths`` (``GriffinLim(..., ragged=True)``: ``forward_device(mel, lengths=)``, item i bit for bit its own
+    ``infer``); one that does not raises ``NotImplementedError``."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -92,6 +94,26 @@ class MelToWavePipeline:
             return wav
         from .synthesis_output import pcm16_on_device
         return pcm16_on_device(wav, normalize=normalize)
+
+    def _vocode_whole_ragged(self, padded: torch.Tensor, lengths, pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
+        """A batch through a whole-utterance vocoder that takes ``lengths``: ONE ``forward_device(padded, lengths=)``, whose
+        rows are 0 past ``hop * (T_i - 1)`` -- so an item's peak is its own -- then the output stage over the whole batch
+        and a list cut at each item's own count.  An item of one frame is refused by the vocoder, as ``infer`` refuses it."""
+        hop = self.streamer.hop_length
+        frames = [int(t) for t in lengths]
+        rows = [max(t - 1, 0) for t in frames]
+        samples = [hop * r for r in rows]
+        wav = self._whole.forward_device(padded, lengths=frames)
+        if resampler is not None:
+            out = resampler.forward(wav, lengths=rows, row_scale=hop, pcm16=pcm16, normalize=normalize)
+            samples = [resampler.out_range(0, n)[1] for n in samples]
+        elif pcm16:
+            from .synthesis_output import pcm16_on_device
+            out = pcm16_on_device(wav, normalize=normalize)
+        else:
+            out = wav
+        out = out[0] if normalize else out
+        return [out[i, :n] for i, n in enumerate(samples)]
 
     def _pcm16_fn(self) -> Callable:
         fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_pcm16", None)
@@ -347,19 +369,23 @@ class MelToWavePipeline:
         ``lengths``; a vocoder dtype without a ragged forward (bf16, f32s) fails as ``engine.forward(lengths=...)`` does.
         ``pcm16=True``: int16 waveforms from ``GeneratorEngine.forward_pcm16``; with ``normalize=True`` each is scaled to
         0.95 at its own peak first.  ``resampler``: every waveform at its rate (``GeneratorEngine.forward_resampled`` with the
-        same lengths: item i has ``resampler.out_range(0, hop * T_i)[1]`` samples, bit for bit its one-item conversion)."""
+        same lengths: item i has ``resampler.out_range(0, hop * T_i)[1]`` samples, bit for bit its one-item conversion).
+        A whole-utterance vocoder with ``takes_lengths`` (``_vocode_whole_ragged``): ``hop * (T_i - 1)`` samples per item."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
         mels = list(mels)
         if not mels:
             return []
         padded, lengths = pack_mels(mels)
-        if self._whole is not None and len(set(int(n) for n in lengths)) > 1:
+        ragged_whole = self._whole is not None and getattr(self._whole, "takes_lengths", False)
+        if self._whole is not None and not ragged_whole and len(set(int(n) for n in lengths)) > 1:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) takes items of one length: an item's last frames "
                                       "change its own STFT, and no ragged form is built; call infer once per length")
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
+        if ragged_whole:
+            return self._vocode_whole_ragged(padded, lengths, pcm16, normalize, resampler)
         if self._whole is not None:
             out = self._vocode_whole(padded, pcm16, normalize, resampler)
             return list((out[0] if normalize else out).unbind(0))
