@@ -293,6 +293,25 @@ class GriffinLim(_NativeModel):
         s = self._workspace[:B * T * ks * 4].view(torch.float32).view(B, T, ks)
         return s[:, :, :self.n_bins].transpose(1, 2).contiguous()
 
+    def _workspace_layout(self, B: int, T: int):
+        """``({buffer: (offset, shape)}, floats)``: ``GlWorkspace`` (csrc/iris_griffin_lim.hip) restated -- S, c, r and the
+        in-loop waveform y in ``WsTaker`` order, each rounded up to 64 floats.  Host only."""
+        ks, qp = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8
+        layout, off = {}, 0
+        for name, shape in (("S", (B, T, ks)), ("c", (B, T, qp)), ("r", (B, T, qp)), ("y", (B, self.hop_length * (T - 1)))):
+            layout[name] = (off, shape)
+            off += (int(np.prod(shape)) + 63) // 64 * 64
+        return layout, off
+
+    def _read_buffers(self, B: int, T: int) -> dict:
+        """Test-only: the views ``S [B, T, Ks]``, ``c [B, T, Qp]``, ``r [B, T, Qp]`` and ``y [B, hop (T - 1)]`` of the workspace
+        as the last ``forward_device`` of shape (B, T) left it.  Which launch wrote a buffer last is the reader's to know
+        (``gl_forward``): S the inversion, c and r the last update (c0 the inversion when ``n_iter`` is 0; r nothing then), y
+        the last in-loop inverse transform."""
+        layout, _ = self._workspace_layout(B, T)
+        ws = self._workspace.view(torch.float32)
+        return {name: ws[off:off + int(np.prod(shape))].view(shape) for name, (off, shape) in layout.items()}
+
     def __call__(self, mel, phase0=None, seed: int = 1337) -> np.ndarray:
         """``[n_mels, T]`` -> ``[samples]``; ``[B, n_mels, T]`` -> ``[B, samples]``, on the host (as ``HiFiGANVocoder.infer``)."""
         mel = mel.detach().cpu().numpy() if isinstance(mel, torch.Tensor) else np.asarray(mel, dtype=np.float32)

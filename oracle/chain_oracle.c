@@ -206,6 +206,12 @@ int chain_conv_transpose1d(const float *x, const float *w, const float *b, float
     return run(&j, run_conv);
 }
 
+/* out[i] = fmaf(a[i], b[i], c[i]): one correctly rounded multiply-add per element, for the restatement of an epilogue whose
+ * source leaves a * b + c open to contraction (oracle/dsp_chain_cases.py tries the fused and the plain form). */
+void chain_fmaf(const float *a, const float *b, const float *c, float *out, long long n) {
+    for (long long i = 0; i < n; ++i) out[i] = fmaf(a[i], b[i], c[i]);
+}
+
 /* conv_post before tanh: bias first, taps ascending, channels ascending.  w [k][Ci]; out [B][n_rows]. */
 int chain_conv_post_preact(const float *x, const float *w, const float *b, float *out, int B, int L, int Ci, int k,
                            const int32_t *rows, int n_rows) {

@@ -32,6 +32,8 @@ def load():
         lib.chain_conv_transpose1d.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, i]
         lib.chain_conv_post_preact.restype = i
         lib.chain_conv_post_preact.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, i]
+        lib.chain_fmaf.restype = None
+        lib.chain_fmaf.argtypes = [vp, vp, vp, vp, ctypes.c_longlong]
         lib.chain_set_portable.argtypes = [i]
         lib.chain_uses_fma_unit.restype = i
         _lib = lib
@@ -123,6 +125,15 @@ def chain_conv_post_preact(x, w, b, rows):
     out = np.empty((B, idx.size), dtype=np.float32)
     _check(load().chain_conv_post_preact(xc.ctypes.data, wc.ctypes.data, bc.ctypes.data, out.ctypes.data, B, L, C, k,
                                          idx.ctypes.data, idx.size), "chain_conv_post_preact")
+    return out
+
+
+def fmaf32(a, b, c):
+    """``fmaf(a, b, c)`` element by element in fp32 (broadcast first): ONE rounding, where numpy's ``a * b + c`` has two."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32), np.asarray(c, dtype=np.float32))
+    a, b, c = _f32(a), _f32(b), _f32(c)
+    out = np.empty(a.shape, dtype=np.float32)
+    load().chain_fmaf(a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data, out.size)
     return out
 
 

@@ -1,0 +1,546 @@
+"""The mel front-end (csrc/mel_frontend.h) and the Griffin-Lim vocoder (csrc/griffin_lim.h), launch by launch, each on its
+OWN input.  TEST INFRASTRUCTURE ONLY, like the rest of ``oracle/``.
+
+Both stages run ``mma_loop`` of csrc/gemm_tile_f32.h: taps ascending, groups of 8 channels ascending, the channels 0, 4, 1, 5,
+2, 6, 3, 7 of a group -- ``chain_oracle.chain_conv1d`` with ONE chunk.  The transforms are valid convolutions with an even
+number of taps, so ``chain`` below hands the oracle a k = 1 convolution over the taps laid side by side (each padded to a
+multiple of 8 channels with zero samples AND zero weights: ``fmaf(0, 0, acc) == acc`` by value), which walks the same terms in
+the same order.  Conv weights are built here from ``design()``'s ``dft`` / ``idft`` tables exactly as ``conv_weight_from_dft``
+/ ``conv_weight_from_idft`` build them; nothing is read back from the device.  Comparisons are ``np.array_equal``: -0 == +0.
+
+Restatements, per item (the caller loops over the batch), every one taking the launch's own input:
+
+    ``mel_launch``     mel_kernel, all four forms: stage (0 outside [0, n_b), int16 times 1.0f / 32768), one chain of
+                       taps * hop8 terms per column, |re| for bin 0, |Im column of bin 0| for bin n_fft / 2, sqrtf(re re + im im)
+                       otherwise, the filterbank chain over bins8 columns, (float) log((double) max(acc, 1e-5f)); frames past
+                       the item's count are 0.0f.
+    ``invert_launch``  gl_invert_kernel: m = (float) exp(clip(l)) in double, x0 = max(chain(P, m), 0), nnls_iters times
+                       res = chain(fb, x) - m and x = max(x - step chain(fb^T, res), 0); S = x, c0 = (S cos, S sin).
+    ``istft_launch``   gl_istft_kernel: for each 256-column slice of c (columns from Q on read as 0), each tap ascending, each run
+                       of 64 columns a partial chain from 0, ``acc = acc + part`` in that nesting; wss = the sum of
+                       wsq[kap hop + col] over taps ascending whose frame exists; v / wss where wss > FLT_MIN; the trim; with
+                       ``zero_tail`` exact zeros from Ly_b to Ly.
+    ``update_launch``  gl_stft_update_kernel: the front-end's window of y bounded by Ly_b, a partial chain per tap and run of 64
+                       samples added as above, Re = acc, Im = -acc of the sine column, bins 0 and n_fft / 2 real (the Nyquist
+                       value from the Im column of bin 0 with its own r_prev at 2 half), ``phase_update`` as written.
+
+What survives a forward (``gl_forward`` in csrc/iris_griffin_lim.hip): S, the last c, the last r, the last in-loop y and the
+output.  r_prev is overwritten in place and c by every update.  So the same inputs run at ``n_iter`` = 0, 1 and 2, and what
+one forward destroyed is taken from the forward before it (reruns are bit-equal: test_determinism_and_batch_independence, and
+the chain shows it too -- the r1 judged in run 1 is the r_prev that reproduces run 2):
+
+    run 0   invert (logmel, phase -> S, c0);  final istft (c0 -> out0)
+    run 1   in-loop istft (c0 of run 0 -> y0);  update, first (y0, S -> r1, c1);  final istft (c1 -> out1)
+    run 2   in-loop istft (c1 of run 1 -> y1);  update, momentum (y1, S, r1 of run 1 -> r2, c2);  final istft (c2 -> out2)
+
+and once more for ``n_iter`` = 31 and 32 on ``small``: a late-loop state.  (The in-loop transform of run 2's FIRST pass is
+overwritten by its second, so the in-loop form is judged twice per two-pass forward, not three times.)
+
+Claims -- derived, none measured against the device:
+
+* Bit for bit wherever the source fixes every rounding: the chains and the additions of the partial sums, fmaxf, acc - m, wss,
+  the products s ph, (s ar) / den, sqrtf, the stored zeros.  fp32 division and sqrtf are IEEE-rounded under the project's
+  flags (csrc/Makefile passes no fast-math option and hipcc keeps both correctly rounded by default).
+* Four sites where the source leaves FMA contraction open: ``re re + im im`` (mel_kernel), ``x - step acc`` (NNLS),
+  ``re - alpha pr`` and ``ar ar + ai ai`` (phase_update).  A restatement takes the rounding of each as a parameter -- 0 plain,
+  1 fused on the first product, 2 fused on the second where there are two -- and the claim is that ONE assignment per kernel
+  reproduces every element of every case, seed and form of a session (``Session.judge`` keeps the assignments that survive
+  and fails when none is left).
+* exp / log in double, rounded once: the device's libm and numpy's may differ by a double ulp.  An element is *decided* when
+  numpy's float64 result lies further than 2^-40 (relative) from the nearest fp32 rounding midpoint; then both round alike.  A
+  frame with an undecided element leaves the exact claim of its launch and is held to 1 fp32 ulp at the exp / log and to
+  4 e32 downstream (S of the inversion; e32 as tests/griffin_lim_cases.py measures it).  At most 1 % of a case's frames may;
+  tests/test_oracle_dsp_chain.py shows that the inputs here leave out none.  An exact-zero frame gives (float) log(1e-5f).
+* c0 of a ``phase0="device"`` forward is S times what ``draw_phase`` stores for the same seed and stream, bit for bit.
+
+``MUTATIONS`` are wrong restatements; tests/test_oracle_dsp_chain.py shows each fails against the right one.
+"""
+import numpy as np
+
+from oracle import chain_oracle as co
+
+FLT_MIN = np.float32(np.finfo(np.float32).tiny)
+LOG_LO, LOG_HI = -11.513, 2.0
+CLIP = np.float32(1e-5)
+LOG_CLIP = np.float32(np.log(np.float64(CLIP)))
+K_ROWS, K_SLICE, K_WAVES, RUN = 32, 256, 8, 64
+DECIDED = 2.0 ** -40
+MOMENTUM, NNLS_ITERS = 0.99, 32
+
+# ---- cases ---------------------------------------------------------------------------------------------------------------------
+# default   five 256-column slices, the last 8 wide; grid.z = 4 in the update; B 2, T 33 crosses a block
+# small     win < n_fft; 9 groups = 8 + 1 in one slice; T 3 (fewer frames than taps) and T 70
+# two_tap   two taps
+# odd_hop   hop % 8 != 0 (Cp = 16 > H), n_mels < 8 (Mp padding), Ks = 52 != 49 bins
+# wide_hop  16 column tiles: blockIdx.z = 1 in gl_istft_kernel
+GL_CONFIGS = {
+    "default": dict(sample_rate=22050, n_fft=1024, hop_length=256, win_length=1024, n_mels=80, fmin=0.0, fmax=8000.0),
+    "small": dict(sample_rate=8000, n_fft=64, hop_length=16, win_length=48, n_mels=12, fmin=0.0, fmax=None),
+    "two_tap": dict(sample_rate=16000, n_fft=256, hop_length=128, win_length=256, n_mels=20, fmin=0.0, fmax=None),
+    "odd_hop": dict(sample_rate=8000, n_fft=96, hop_length=12, win_length=80, n_mels=6, fmin=0.0, fmax=None),
+    "wide_hop": dict(sample_rate=22050, n_fft=1024, hop_length=512, win_length=1024, n_mels=12, fmin=0.0, fmax=8000.0),
+}
+GL_CASES = (("default", 2, 33), ("small", 1, 3), ("small", 1, 70), ("two_tap", 1, 34), ("odd_hop", 1, 3), ("odd_hop", 1, 35),
+            ("wide_hop", 1, 3), ("wide_hop", 1, 34))
+GL_SEEDS = (1337, 7)                              # start-phase seeds of a dense case
+GL_LATE = ("small", 1, 70)                        # the case of the n_iter = 31 / 32 pair
+# (config, T, lengths): the full T, 0, 1 (sanitised to 0), inside a block, on a block edge
+GL_RAGGED = (("small", 70, (70, 0, 1, 33, 64)), ("odd_hop", 35, (35, 0, 1, 20, 32)))
+MEL_CONFIGS = {
+    "default": GL_CONFIGS["default"],
+    "small": dict(sample_rate=16000, n_fft=256, hop_length=64, win_length=192, n_mels=20, fmin=50.0, fmax=None),
+    "odd_hop": GL_CONFIGS["odd_hop"],
+}
+# (config, B, L): 33 frames (two blocks); odd_hop at 3 and 35 frames
+MEL_CASES = (("default", 2, 8229), ("small", 1, 2085), ("odd_hop", 1, 31), ("odd_hop", 1, 413))
+MEL_SEEDS = (0, 1)
+# (config, L, n_samples): frames 33, 1, 1, 17, 32 (default) and 35, 1, 1, 17, 32 (odd_hop)
+MEL_RAGGED = (("default", 8229, (8229, 0, 1, 4096, 31 * 256 + 5)), ("odd_hop", 413, (413, 0, 1, 200, 31 * 12)))
+
+MUTATIONS = ("taps_descending", "istft_one_chain", "stft_one_chain", "mel_partial_sums", "istft_taps_outside_slices", "ascending",
+             "mel_no_nyquist", "idft_nyquist_2", "window_uncentred", "frames_shifted", "wss_past_end", "trim_short",
+             "alpha_momentum", "first_uses_rprev", "im_sign", "exp_f32", "log_f32", "clip_after_exp", "residual_sign")
+
+
+def case_id(case) -> str:
+    return f"{case[0]}-B{case[1]}-T{case[2]}"
+
+
+class Design:
+    """``mel::Design`` and ``gl::Design`` restated, with what the launch code derives from them."""
+
+    def __init__(self, cfg):
+        self.n_fft, self.hop, self.win, self.n_mels = cfg["n_fft"], cfg["hop_length"], cfg["win_length"], cfg["n_mels"]
+        N, H = self.n_fft, self.hop
+        self.taps, self.bins, self.half = N // H, N // 2 + 1, N // 2
+        self.cp, self.bins8, self.mp = (H + 7) & ~7, (self.bins + 7) & ~7, (self.n_mels + 7) & ~7
+        self.dft_tiles, self.hop_tiles = (self.half + 15) // 16, (H + 31) // 32
+        self.ks, self.q = (self.bins + 3) & ~3, N + 2
+        self.qp = (self.q + 7) & ~7
+        self.first_row = self.half // H
+        self.slices = [(q0, min(K_SLICE, self.qp - q0)) for q0 in range(0, self.qp, K_SLICE)]
+        self.istft_grid_z = (self.hop_tiles + K_WAVES - 1) // K_WAVES
+        self.update_grid_z = (self.dft_tiles + K_WAVES - 1) // K_WAVES
+
+    def dft_col(self, bins, im):
+        """The output column of ``conv_weight_from_dft`` that holds Re (im = 0) or the sine sum (im = 1) of ``bins``."""
+        bins = np.asarray(bins)
+        return 32 * (bins // 16) + 16 * im + bins % 16
+
+
+def tables_np(cfg, centred=True, nyquist_factor=1.0):
+    """``fill_dft``, ``fill_idft`` and ``fill_wsq`` in numpy's float64, for the mutations that change a table (the right
+    tables are ``design()``'s)."""
+    N, win = cfg["n_fft"], cfg["win_length"]
+    w = np.zeros(N)
+    lpad = (N - win) // 2 if centred else 0
+    w[lpad:lpad + win] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win) / win)
+    k, n = np.arange(N // 2 + 1)[:, None], np.arange(N)[None, :]
+    j = (k * n) % N
+    c, s = np.cos(2.0 * np.pi * j / N), np.where(2 * j % N == 0, 0.0, np.sin(2.0 * np.pi * j / N))
+    edge = (k == 0) | (2 * k == N)
+    f = np.where(edge, 1.0, 2.0) / N
+    f[-1] *= nyquist_factor
+    return {"dft": np.stack([w * c, w * s]).astype(np.float32),
+            "idft": np.stack([w * f * c, np.where(edge, 0.0, -(w * f * s))]).astype(np.float32), "wsq": (w * w).astype(np.float32)}
+
+
+def mutate_tables(tab, cfg, mut):
+    if mut == "window_uncentred":
+        return {**tab, **tables_np(cfg, centred=False)}
+    if mut == "idft_nyquist_2":
+        idft = tab["idft"].copy()
+        idft[0, -1] *= np.float32(2.0)
+        return {**tab, "idft": idft}
+    return tab
+
+
+# ---- inputs (tests/ is on sys.path in every test that comes here) -----------------------------------------------------------------
+_cache: dict = {}
+
+
+def gl_model(name, **kw):
+    from iris.griffin_lim import GriffinLim
+    return GriffinLim(**GL_CONFIGS[name], momentum=MOMENTUM, nnls_iters=NNLS_ITERS, **kw)
+
+
+def gl_tables(name):
+    """``design()``'s fp32 tables with ``P`` and ``step`` (host only), fetched once."""
+    if ("tab", name) not in _cache:
+        gl = gl_model(name)
+        t = gl.design()
+        t["P"], t["step"] = gl.inversion_tables()
+        _cache[("tab", name)] = t
+    return _cache[("tab", name)]
+
+
+def gl_logmel(case):
+    """``[B, n_mels, T]`` float32: ``griffin_lim_cases.logmel``'s recipe on this module's configs."""
+    if ("lm", case) not in _cache:
+        import griffin_lim_cases as GC
+        import mel_restatement as M
+        name, B, T = case
+        cfg = GL_CONFIGS[name]
+        _cache[("lm", case)] = np.stack([M.mel_np(GC.waveform(cfg["hop_length"] * (T - 1), cfg, seed=b), **cfg)
+                                         for b in range(B)]).astype(np.float32)
+    return _cache[("lm", case)]
+
+
+def gl_phase(case, seed):
+    """``phi0 [B, bins, T]`` float64, the draw of ``griffin_lim_cases.phase``."""
+    name, B, T = case
+    return 2.0 * np.pi * np.random.default_rng(seed).random((B, GL_CONFIGS[name]["n_fft"] // 2 + 1, T))
+
+
+def mel_tables(name):
+    if ("mtab", name) not in _cache:
+        from iris.mel import MelFrontend
+        dft, fb = MelFrontend(**MEL_CONFIGS[name]).design()
+        _cache[("mtab", name)] = {"dft": dft, "fb": fb}
+    return _cache[("mtab", name)]
+
+
+def mel_audio(name, B, L, seed):
+    """``[B, L]`` float32 of ``mel_cases.waveform`` (item b: seed + 10 b)."""
+    import mel_cases as MC
+    return np.stack([MC.waveform(L, MEL_CONFIGS[name], seed=seed + 10 * b) for b in range(B)])
+
+
+def to_int16(audio):
+    return np.round(np.asarray(audio, dtype=np.float64) * 32767.0).astype(np.int16)
+
+
+# ---- the chain -------------------------------------------------------------------------------------------------------------------
+def chain(x, w, mut=None):
+    """``x [n, C]``, ``w [C_out, C]``, C a multiple of 8 -> ``[n, C_out]``: per element ONE fmaf chain from 0 over the groups of 8
+    ascending, channels 0, 4, 1, 5, 2, 6, 3, 7 inside a group."""
+    n, C = x.shape
+    assert w.shape[1] == C and C % 8 == 0 and x.dtype == np.float32 and w.dtype == np.float32
+    if n == 0:
+        return np.zeros((0, w.shape[0]), np.float32)
+    y = co.chain_conv1d(x.T[None], w[:, :, None], np.zeros(w.shape[0], np.float32), 1, C, [(0, n)],
+                        variant=co.ASCENDING if mut == "ascending" else 0)
+    return np.ascontiguousarray(y[0].T)
+
+
+def pad_cols(a, C):
+    out = np.zeros(a.shape[:-1] + (C,), np.float32)
+    out[..., :a.shape[-1]] = a
+    return out
+
+
+def dft_conv_weight(d, dft):
+    """``conv_weight_from_dft``: ``[32 dft_tiles, hop, taps]``."""
+    w = np.zeros((32 * d.dft_tiles, d.hop, d.taps), np.float32)
+    for c in range(w.shape[0]):
+        j = c & 31
+        b, im = 16 * (c >> 5) + 8 * ((j >> 3) & 1) + (j & 7), j >> 4
+        if b >= d.half:
+            continue
+        row = dft[0, d.half] if (b == 0 and im) else dft[im, b]
+        w[c] = row.reshape(d.taps, d.hop).T
+    return w
+
+
+def idft_conv_weight(d, idft):
+    """``conv_weight_from_idft``: ``[32 hop_tiles, Q, taps]``; tap kk multiplies frame j - (taps - 1 - kk)."""
+    rows = np.empty((d.q, d.n_fft), np.float32)
+    rows[0::2], rows[1::2] = idft[0], idft[1]
+    w = np.zeros((32 * d.hop_tiles, d.q, d.taps), np.float32)
+    w[:d.hop] = rows.reshape(d.q, d.taps, d.hop)[:, ::-1, :].transpose(2, 0, 1)
+    return w
+
+
+def tap_weights(w, C):
+    """``[C_out, C_in, taps]`` -> ``[taps, C_out, C]`` with the channels padded to C by zeros."""
+    return np.ascontiguousarray(pad_cols(w.transpose(2, 0, 1), C))
+
+
+def stage_rows(x, n_b, d, T, mut=None):
+    """``[T, taps, hop8]``: row t, tap kk, column c is sample t hop - n_fft / 2 + kk hop + c; 0 for c >= hop and outside [0, n_b)."""
+    t, kk, c = np.arange(T)[:, None, None], np.arange(d.taps)[None, :, None], np.arange(d.cp)[None, None, :]
+    s = (t + kk + (1 if mut == "frames_shifted" else 0)) * d.hop + c - d.half
+    ok = (c < d.hop) & (s >= 0) & (s < n_b)
+    x = np.asarray(x, dtype=np.float32)
+    if x.size == 0:
+        x = np.zeros(1, np.float32)
+    return np.where(ok, x[np.clip(s, 0, x.size - 1)], np.float32(0))
+
+
+def transform_acc(rows, wt, partial, mut=None):
+    """The forward DFT of staged ``rows [T, taps, hop8]`` against ``wt [taps, C_out, hop8]``: ONE chain of taps * hop8 terms
+    (mel_kernel), or a partial chain per tap and run of 64 samples, added in that order (gl_stft_update_kernel)."""
+    T, K, Cp = rows.shape
+    order = range(K - 1, -1, -1) if mut == "taps_descending" else range(K)
+    if not partial:
+        return chain(np.concatenate([rows[:, kk] for kk in order], axis=1), np.concatenate([wt[kk] for kk in order], axis=1), mut)
+    acc = np.zeros((T, wt.shape[1]), np.float32)
+    for kk in order:
+        for g in range(0, Cp, RUN):
+            acc = acc + chain(np.ascontiguousarray(rows[:, kk, g:g + RUN]), np.ascontiguousarray(wt[kk][:, g:g + RUN]), mut)
+    return acc
+
+
+def sum_sq(a, b, mode):
+    """a a + b b: 0 both products rounded, 1 fmaf(a, a, fl(b b)), 2 fmaf(b, b, fl(a a))."""
+    if mode == 0:
+        return a * a + b * b
+    return co.fmaf32(a, a, b * b) if mode == 1 else co.fmaf32(b, b, a * a)
+
+
+def sub_prod(x, s, a, mode):
+    """x - s a: 0 the product rounded, 1 fmaf(-s, a, x)."""
+    return x - s * a if mode == 0 else co.fmaf32(-s, a, x)
+
+
+def decided(v64):
+    """Where the float64 value lies further than 2^-40 (relative) from the fp32 rounding midpoints around it."""
+    v64 = np.asarray(v64, dtype=np.float64)
+    f = v64.astype(np.float32)
+    out = np.ones(v64.shape, bool)
+    for side in (-np.inf, np.inf):
+        mid = 0.5 * (f.astype(np.float64) + np.nextafter(f, np.float32(side)).astype(np.float64))
+        out &= np.abs(v64 - mid) > DECIDED * np.abs(v64)
+    return out
+
+
+# ---- mel_kernel --------------------------------------------------------------------------------------------------------------------
+MEL_SITES = {"mag": 3}
+INVERT_SITES = {"nnls": 2}
+UPDATE_SITES = {"alpha": 2, "den": 3}
+
+
+def assignments(sites):
+    out = [{}]
+    for name, n in sites.items():
+        out = [{**a, name: v} for a in out for v in range(n)]
+    return out
+
+
+def mel_samples(audio):
+    """What the staging loads: fp32 as it is, int16 times ``1.0f / 32768``."""
+    audio = np.asarray(audio)
+    if audio.dtype == np.int16:
+        return audio.astype(np.float32) * (np.float32(1.0) / np.float32(32768))
+    assert audio.dtype == np.float32
+    return audio
+
+
+def mel_launch(audio, n_b, cap, cfg, tab, fma, mut=None):
+    """One item of mel_kernel: ``audio [L]`` fp32 or int16, ``n_b`` its own samples (L of a dense call), ``cap`` its
+    max_frames or None -> ``(mel [n_mels, T], frames, ok [T])``: ``ok`` marks the frames whose logarithms are all decided."""
+    d = Design(cfg)
+    tab = mutate_tables(tab, cfg, mut)
+    L = len(audio)
+    T = 1 + L // d.hop
+    n_b = min(max(int(n_b), 0), L)
+    Tb = 1 + n_b // d.hop
+    if cap is not None:
+        Tb = min(Tb, max(int(cap), 0))
+    out, ok = np.zeros((d.n_mels, T), np.float32), np.ones(T, bool)
+    if Tb == 0:
+        return out, Tb, ok
+    rows = stage_rows(mel_samples(audio), n_b, d, Tb, mut)
+    acc = transform_acc(rows, tap_weights(dft_conv_weight(d, tab["dft"]), d.cp), mut == "mel_partial_sums", mut)
+    b = np.arange(1, d.half)
+    mag = np.zeros((Tb, d.bins8), np.float32)
+    mag[:, 0] = np.abs(acc[:, d.dft_col(0, 0)])
+    mag[:, d.half] = 0 if mut == "mel_no_nyquist" else np.abs(acc[:, d.dft_col(0, 1)])
+    mag[:, 1:d.half] = np.sqrt(sum_sq(acc[:, d.dft_col(b, 0)], acc[:, d.dft_col(b, 1)], fma["mag"]))
+    m = np.maximum(chain(mag, pad_cols(tab["fb"], d.bins8), mut), CLIP)
+    lg = np.log(m) if mut == "log_f32" else np.log(m.astype(np.float64))
+    out[:, :Tb] = lg.astype(np.float32).T
+    ok[:Tb] = decided(lg).all(axis=1)
+    return out, Tb, ok
+
+
+# ---- gl_invert_kernel ------------------------------------------------------------------------------------------------------------
+def item_frames(n, T):
+    """``item_frames`` of csrc/griffin_lim.h (n None: a dense call)."""
+    if n is None:
+        return T
+    n = min(max(int(n), 0), T)
+    return 0 if n < 2 else n
+
+
+def invert_launch(logmel, phase, Tb, cfg, tab, nnls_iters, fma, mut=None):
+    """``logmel [n_mels, T]``, ``phase [T, bins, 2]`` (the packed cos / sin the launch was given, or what ``draw_phase``
+    stores) -> ``(S [Tb, bins], c0 [Tb, Q], ok [Tb], m [Tb, n_mels])``."""
+    d = Design(cfg)
+    lm = np.asarray(logmel, dtype=np.float32)[:, :Tb].T
+    if mut == "exp_f32":
+        e = np.exp(np.clip(lm, np.float32(LOG_LO), np.float32(LOG_HI)))
+    elif mut == "clip_after_exp":
+        e = np.clip(np.exp(lm.astype(np.float64)), LOG_LO, LOG_HI)
+    else:
+        e = np.exp(np.clip(lm.astype(np.float64), LOG_LO, LOG_HI))
+    ok = decided(e).all(axis=1)
+    m = pad_cols(e.astype(np.float32), d.mp)
+    P, fb, fbt = pad_cols(tab["P"], d.mp), pad_cols(tab["fb"], d.bins8), pad_cols(np.ascontiguousarray(tab["fb"].T), d.mp)
+    step, zero = np.float32(tab["step"]), np.float32(0)
+    x = np.maximum(chain(m, P, mut), zero)
+    for _ in range(nnls_iters):
+        acc = chain(pad_cols(x, d.bins8), fb, mut)
+        res = pad_cols(m[:, :d.n_mels] - acc if mut == "residual_sign" else acc - m[:, :d.n_mels], d.mp)
+        x = np.maximum(sub_prod(x, step, chain(res, fbt, mut), fma["nnls"]), zero)
+    c0 = np.empty((Tb, d.q), np.float32)
+    ph = np.asarray(phase, dtype=np.float32)[:Tb]
+    c0[:, 0::2], c0[:, 1::2] = x * ph[:, :, 0], x * ph[:, :, 1]
+    return x, c0, ok, m[:, :d.n_mels]
+
+
+# ---- gl_istft_kernel -------------------------------------------------------------------------------------------------------------
+def istft_launch(c, Tb, T, cfg, tab, zero_tail, mut=None):
+    """``c [T, Qp]`` (or ``[.., Q]``; rows from Tb on are never read) -> ``(y [Ly], written [Ly])``: what the launch stores and
+    where."""
+    d = Design(cfg)
+    tab = mutate_tables(tab, cfg, mut)
+    H, K = d.hop, d.taps
+    Ly, Lyb = H * (T - 1), (H * (Tb - 1) if Tb else 0)
+    y, written = np.zeros(Ly, np.float32), np.zeros(Ly, bool)
+    if zero_tail:
+        written[Lyb:] = True
+    if Lyb == 0:
+        return y, written
+    trim = d.half - H if mut == "trim_short" else d.half
+    j = np.arange(trim // H, (trim + Lyb - 1) // H + 1)                            # padded rows that hold a surviving sample
+    cz = np.zeros((Tb, d.qp), np.float32)
+    cz[:, :d.q] = np.asarray(c, dtype=np.float32)[:Tb, :d.q]
+    wt = tap_weights(idft_conv_weight(d, tab["idft"]), d.qp)[:, :H]               # [taps, hop, Qp]
+    shift = 1 if mut == "frames_shifted" else 0
+
+    def frames_of(kk):
+        t = j - (K - 1 - kk) + shift
+        ok = (t >= 0) & (t < Tb)
+        return np.where(ok[:, None], cz[np.clip(t, 0, Tb - 1)], np.float32(0))
+
+    taps = list(range(K - 1, -1, -1) if mut == "taps_descending" else range(K))
+    runs = [(q0 + g, min(RUN, q0 + width - (q0 + g))) for q0, width in d.slices for g in range(0, width, RUN)]
+    if mut == "istft_one_chain":
+        order = [(kk, q0, width) for q0, width in d.slices for kk in taps]
+        acc = chain(np.concatenate([frames_of(kk)[:, q0:q0 + n] for kk, q0, n in order], axis=1),
+                    np.concatenate([wt[kk][:, q0:q0 + n] for kk, q0, n in order], axis=1), mut)
+    else:
+        if mut == "istft_taps_outside_slices":
+            order = [(kk, q, n) for kk in taps for q, n in runs]
+        else:
+            order = [(kk, q, n) for q0, width in d.slices for kk in taps for q, n in runs if q0 <= q < q0 + width]
+        xs = {kk: frames_of(kk) for kk in taps}
+        acc = np.zeros((len(j), H), np.float32)
+        for kk, q, n in order:
+            acc = acc + chain(np.ascontiguousarray(xs[kk][:, q:q + n]), np.ascontiguousarray(wt[kk][:, q:q + n]), mut)
+    wss = np.zeros((len(j), H), np.float32)
+    for kap in range(K):
+        t = j - kap
+        ok = (t >= 0) if mut == "wss_past_end" else (t >= 0) & (t < Tb)
+        wss = wss + np.where(ok[:, None], tab["wsq"][kap * H:(kap + 1) * H][None, :], np.float32(0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.where(wss > FLT_MIN, acc / wss, acc)
+    s = j[:, None] * H + np.arange(H)[None, :] - trim
+    keep = (s >= 0) & (s < Lyb)
+    y[s[keep]] = v[keep]
+    written[s[keep]] = True
+    return y, written
+
+
+# ---- gl_stft_update_kernel -------------------------------------------------------------------------------------------------------
+def phase_update(re, im, pr, pi, alpha, s, fma):
+    ar, ai = sub_prod(re, alpha, pr, fma["alpha"]), sub_prod(im, alpha, pi, fma["alpha"])
+    den = np.sqrt(sum_sq(ar, ai, fma["den"])) + FLT_MIN
+    return s * ar / den, s * ai / den
+
+
+def update_acc(y, Tb, cfg, tab, mut=None):
+    """The transform of gl_stft_update_kernel alone (it does not depend on the contraction sites): ``[Tb, 32 dft_tiles]``."""
+    d = Design(cfg)
+    tab = mutate_tables(tab, cfg, mut)
+    rows = stage_rows(y, d.hop * (Tb - 1), d, Tb, mut)
+    return transform_acc(rows, tap_weights(dft_conv_weight(d, tab["dft"]), d.cp), mut != "stft_one_chain", mut)
+
+
+def update_launch(acc, S, r_prev, cfg, first, fma, mut=None, momentum=MOMENTUM):
+    """``acc`` of ``update_acc``, ``S [.., Ks]``, ``r_prev [.., Qp]`` (read unless ``first``) -> ``(r [Tb, Q], c [Tb, Q])``."""
+    d = Design(cfg)
+    Tb, half = acc.shape[0], d.half
+    alpha = np.float32(momentum if mut == "alpha_momentum" else momentum / (1.0 + momentum))
+    b = np.arange(half)
+    re, sine = acc[:, d.dft_col(b, 0)], acc[:, d.dft_col(b, 1)]
+    im = sine.copy() if mut == "im_sign" else -sine
+    im[:, 0] = 0
+    nyq = sine[:, 0]
+    if first and mut != "first_uses_rprev":
+        pr, pi, pn = np.zeros_like(re), np.zeros_like(re), np.zeros_like(nyq)
+    else:
+        rp = np.asarray(r_prev, dtype=np.float32)[:Tb]
+        pr, pi, pn = rp[:, 0:2 * half:2].copy(), rp[:, 1:2 * half:2].copy(), rp[:, 2 * half].copy()
+        pi[:, 0] = 0
+    S = np.asarray(S, dtype=np.float32)[:Tb]
+    r, c = np.zeros((Tb, d.q), np.float32), np.zeros((Tb, d.q), np.float32)
+    r[:, 0:2 * half:2], r[:, 1:2 * half:2], r[:, 2 * half] = re, im, nyq
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c[:, 0:2 * half:2], c[:, 1:2 * half:2] = phase_update(re, im, pr, pi, alpha, S[:, :half], fma)
+        c[:, 2 * half] = phase_update(nyq, np.zeros_like(nyq), pn, np.zeros_like(nyq), alpha, S[:, half], fma)[0]
+    return r, c
+
+
+# ---- a forward on the CPU (the restatements fed with their own outputs) -------------------------------------------------------------
+def forward_np(logmel, phase, cfg, tab, n_iter, fma, length=None, nnls_iters=NNLS_ITERS, mut=None):
+    """One item through ``gl_forward``: ``{"S", "c0", "wav": {n: out_n}, "r": [..], "c": [..], "y": [..]}`` for n <= n_iter."""
+    T = logmel.shape[1]
+    Tb = item_frames(length, T)
+    S, c, _, _ = invert_launch(logmel, phase, Tb, cfg, tab, nnls_iters, fma, mut)
+    out = {"S": S, "c0": c, "wav": {}, "r": [], "c": [c], "y": []}
+    r = None
+    for it in range(n_iter + 1):
+        out["wav"][it] = istft_launch(c, Tb, T, cfg, tab, length is not None, mut)[0]
+        if it == n_iter:
+            break
+        y = istft_launch(c, Tb, T, cfg, tab, False, mut)[0]
+        r, c = update_launch(update_acc(y, Tb, cfg, tab, mut), pad_cols(S, Design(cfg).ks), r, cfg, it == 0, fma, mut)
+        out["y"].append(y), out["r"].append(r), out["c"].append(c)
+    return out
+
+
+# ---- judging on the device's own tensors ---------------------------------------------------------------------------------------
+class Session:
+    """What a GPU test module keeps: per kernel the contraction assignments that still reproduce every element judged so far,
+    and per launch kind the counts the issue asks to print."""
+
+    def __init__(self):
+        self.alive = {"mel_kernel": assignments(MEL_SITES), "gl_invert_kernel": assignments(INVERT_SITES),
+                      "gl_stft_update_kernel": assignments(UPDATE_SITES)}
+        self.stats = {}
+
+    def count(self, kind, exact=0, undecided=0, frames=0, ratio=0.0):
+        s = self.stats.setdefault(kind, {"exact": 0, "undecided": 0, "frames": 0, "worst": 0.0})
+        s["exact"] += int(exact)
+        s["undecided"] += int(undecided)
+        s["frames"] += int(frames)
+        s["worst"] = max(s["worst"], float(ratio))
+
+    def judge(self, kernel, kind, where, restate, compare):
+        """``restate(fma)`` -> the restatement under one assignment; ``compare(restated)`` -> the number of elements that
+        differ from the device.  Keeps the assignments with no difference; fails, naming the launch, when none is left."""
+        left, seen = [], []
+        for fma in self.alive[kernel]:
+            bad = compare(restate(fma))
+            seen.append((fma, bad))
+            if bad == 0:
+                left.append(fma)
+        assert left, f"{kind} {where}: no single contraction assignment of {kernel} reproduces the device; differing elements per assignment: {seen}"
+        self.alive[kernel] = left
+        return left[0]
+
+    def report(self):
+        for kind, s in sorted(self.stats.items()):
+            print(f"{kind}: {s['exact']} elements exact, {s['undecided']} of {s['frames']} frames undecided, worst error / bar {s['worst']:.3f}")
+        for kernel, left in self.alive.items():
+            print(f"{kernel}: contraction assignment(s) that reproduce every element: {left}")
+
+
+def differing(got, want, mask=None):
+    """Elements of ``got`` that differ from ``want`` by value (NaN differs from everything), within ``mask``."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32, (got.shape, want.shape, got.dtype, want.dtype)
+    bad = ~(got == want)
+    return int(bad.sum() if mask is None else (bad & mask).sum())
