@@ -772,6 +772,47 @@ int32_t iris_griffin_lim_forward_ragged(iris_griffin_lim_handle* h, const float*
 int32_t iris_griffin_lim_draw_phase(iris_griffin_lim_handle* h, uint64_t seed, int32_t item0, int32_t B, int32_t T, float* phase_out_dev,
                                     void* stream);
 
+/* ---- Bias denoiser: spectral bias subtraction on the vocoder's waveform (csrc/denoiser.h) -----------------------------
+ * What HiFiGAN users run behind the vocoder: the magnitude spectrum of the vocoder's output for a silent mel (its constant
+ * hum, the "bias") is subtracted, times `strength`, from the magnitudes of an utterance; the phase is kept.  fp32, on the
+ * Griffin-Lim stage's transforms above (stft, istft: the mel front-end's window, frames and tables; sample_rate, n_mels,
+ * fmin and fmax of the config are checked by the front-end's rules and otherwise unused).  wav [B, L] -> out [B, L], L a
+ * multiple of hop_length (M = L / hop_length mel frames, T = M + 1 frames).  Per frame t and bin k of a = stft(wav):
+ *     mag = sqrtf(re re + im im);  g = fmaxf(fmaf(-strength, bias[k], mag), 0);  scale = mag > 0 ? g / mag : 0;
+ *     c = (scale re, scale im);  out = istft(c)
+ * Bins 0 and n_fft / 2 are real.  strength = 0 leaves c = stft(wav); a strength at or above max(mag / bias) gives out == 0.
+ * bias [n_bins] is finite and not negative (create checks bias_host; NULL: zeros).  set_bias copies n_bins floats from the
+ * device into the handle, asynchronously on `stream`: an estimate never visits the host.
+ * estimate_bias: wav [1, L] -> bias_out_dev [n_bins], the mean of mag[t, k] over the frames whose window lies wholly inside the
+ * signal, e <= t < T - e with e = ceil(n_fft / 2 / hop_length); fp32 terms summed in fp64 in ascending t, rounded once: the
+ * same bits on every run.  Its workspace is that of a forward of shape (1, L).
+ * forward: 2 launches (the STFT with the subtraction as its epilogue, the inverse STFT); estimate_bias: 2 launches (the STFT
+ * storing magnitudes, the mean).  No atomics: two runs agree bit for bit.  lengths_dev [B] (device, or NULL: dense) holds the
+ * items' MEL frames: item b has M_b = min(max(lengths[b], 0), M) frames; out[b, :hop_length * M_b] is bit for bit the
+ * batch-of-one dense call on wav[b, :hop_length * M_b], out[b, hop_length * M_b:] is stored as 0.0f, and nothing of wav at or
+ * past hop_length * M_b is read.  The lengths are never read by the host: a captured graph follows new contents.
+ * After a forward the workspace starts with c as fp32 [B][T][Qp] (column 2 k Re, 2 k + 1 Im of bin k; Qp = n_fft + 2 rounded
+ * up to 8; rows t > M_b and columns from n_fft + 2 on are not written), followed by the items' frame counts.
+ * L that is no multiple of hop_length, a negative shape, a negative or non-finite strength, a NULL pointer, out_dev
+ * overlapping wav_dev, and (estimate_bias) an L without an interior frame return IRIS_HIFIGAN_INVALID_ARGUMENT; the front-end's
+ * and the Griffin-Lim stage's unsupported configs and B > 65535 IRIS_HIFIGAN_UNSUPPORTED (from every function that takes the
+ * config; create reports it before it touches the device); a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing
+ * call launches.  B == 0 or L == 0: nothing to do, IRIS_HIFIGAN_OK. */
+typedef struct iris_denoiser_handle iris_denoiser_handle;
+/* Host only (no device is needed); the launch counts are dry runs of the forward's and the estimator's own code. */
+int32_t iris_denoiser_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, uint64_t* bytes);
+int32_t iris_denoiser_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, int32_t* n);
+int32_t iris_denoiser_estimate_launch_count(const iris_mel_frontend_config* cfg, int32_t L, int32_t* n);
+/* create: on the current device, which becomes the handle's.  The calls below it are asynchronous on `stream`, allocate
+ * nothing, and are safe inside a stream capture. */
+int32_t iris_denoiser_create(const iris_mel_frontend_config* cfg, const float* bias_host /* [n_bins] or NULL */, iris_denoiser_handle** out);
+int32_t iris_denoiser_destroy(iris_denoiser_handle* h);
+int32_t iris_denoiser_set_bias(iris_denoiser_handle* h, const float* bias_dev, void* stream);
+int32_t iris_denoiser_estimate_bias(iris_denoiser_handle* h, const float* wav_dev, int32_t L, float* bias_out_dev, void* workspace_dev,
+                                    uint64_t workspace_bytes, void* stream);
+int32_t iris_denoiser_forward(iris_denoiser_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev /* or NULL */,
+                              float strength, float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

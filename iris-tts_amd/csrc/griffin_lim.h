@@ -47,6 +47,9 @@
 // inverse STFT at the defaults) loses more than the blocked sums of a host BLAS.  Both transforms therefore run short chains
 // and add the partial sums: one per tap and 64 columns (inverse) or 64 samples (forward).  The normalisation a / |a| amplifies
 // what is left where |a| is small.
+//
+// The kernels have internal linkage: iris_denoiser.hip includes this header as well (it launches gl_istft_kernel), and each
+// translation unit carries its own copy.
 #pragma once
 #include <float.h>
 
@@ -165,7 +168,7 @@ struct DrawLaunch {
     uint32_t seed_lo, seed_hi, item0;
 };
 
-__global__ void __launch_bounds__(256) gl_draw_phase_kernel(const DrawLaunch a) {
+static __global__ void __launch_bounds__(256) gl_draw_phase_kernel(const DrawLaunch a) {
     const int b = blockIdx.y, i0 = blockIdx.x * kRows, groups = (a.bins + 3) >> 2;
     for (int idx = threadIdx.x; idx < kRows * groups; idx += 256) {
         const int r = idx / groups, k4 = idx - r * groups, t = i0 + r;
@@ -194,7 +197,7 @@ struct InvertLaunch {
     uint32_t seed_lo, seed_hi, item0;
 };
 
-__global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaunch a) {
+static __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const InvertLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = 64 * kWaves;
     const int lane = tid & 63, wave = tid >> 6;
@@ -310,7 +313,7 @@ struct IstftLaunch {
     int zero_tail;            // the last transform of a ragged forward: y[b, Ly_b:] = 0
 };
 
-__global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
+static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = 64 * kWaves;
     const int lane = tid & 63, wave = tid >> 6;
@@ -409,7 +412,7 @@ __device__ __forceinline__ void phase_update(float re, float im, float pr, float
     cim = s * ai / den;
 }
 
-__global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftLaunch a) {
+static __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(const StftLaunch a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, nthr = 64 * kWaves;
     const int lane = tid & 63, wave = tid >> 6;

@@ -1,0 +1,218 @@
+// iris_denoiser.hip -- the iris_denoiser_* entry points of include/iris_hifigan.h: spectral bias subtraction on a waveform
+// [B, L] (csrc/denoiser.h), the post-processing step HiFiGAN users run behind the vocoder.  A forward is 2 launches: the STFT
+// whose epilogue subtracts strength * bias from the magnitudes, and the Griffin-Lim stage's inverse STFT as it stands.  The
+// estimator is 2 launches: the same STFT storing magnitudes, and the fp64 mean over the interior frames.  The handle owns the
+// front-end's packed windowed DFT, the packed windowed inverse DFT, w^2 and the bias row.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include <new>
+#include <vector>
+
+#include "stage_host.h"
+#include "denoiser.h"
+
+using namespace iris;
+
+struct iris_denoiser_handle : StageHandle {
+    gl::Design d;
+    PackedGemm dft, idft;
+    size_t wsq_off = 0, bias_off = 0;
+};
+
+namespace {
+
+// The front-end's rules, then the Griffin-Lim stage's for its two transforms (iris_griffin_lim.hip: gl_validate).
+int dn_validate(const iris_mel_frontend_config* c, gl::Design* d) {
+    TRY(mel_validate(c, &d->m));
+    if (c->n_fft % 32) return fail(IRIS_HIFIGAN_UNSUPPORTED, "n_fft %d is not a multiple of 32 (bins come in tiles of 16)", c->n_fft);
+    const size_t transform = d->istft_lds_bytes() > d->stft_lds_bytes() ? d->istft_lds_bytes() : d->stft_lds_bytes();
+    if (transform > mel::kMaxLdsBytes)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "the frame window of n_fft %d, hop_length %d (31 + %d frames) needs %llu bytes of LDS, more than "
+                    "%llu: no form that slices the frames is built", c->n_fft, c->hop_length, d->m.taps(), (unsigned long long)transform,
+                    (unsigned long long)mel::kMaxLdsBytes);
+    return IRIS_HIFIGAN_OK;
+}
+
+int dn_check_shape(const gl::Design& d, int32_t B, int32_t L) {
+    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (L % d.m.hop) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "L = %d is not a multiple of hop_length %d (a vocoder emits hop_length samples per mel frame)", L, d.m.hop);
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    return IRIS_HIFIGAN_OK;
+}
+
+// c first (tests read it there; the estimator keeps its magnitudes [T][Ks] in the same place), then the items' frame counts.
+struct DnWorkspace {
+    size_t c, frames, floats;
+    DnWorkspace(const gl::Design& d, int B, int L) {
+        WsTaker ws;
+        c = ws.take((size_t)B * (L / d.m.hop + 1) * d.qp());
+        frames = ws.take((size_t)B);
+        floats = ws.off;
+    }
+};
+
+struct DnTables { const float *dft, *idft, *wsq, *bias; };
+
+// Queues the forward's two launches (or, in a dry run, counts them).  `lengths` (device, or NULL: dense) is never read here.
+int dn_forward(const gl::Design& d, const DnTables& tb, const float* wav, int B, int L, const int32_t* lengths, float strength,
+               float* out, float* ws, hipStream_t stream) {
+    const DnWorkspace lay(d, B, L);
+    const int T = L / d.m.hop + 1;
+    int32_t* frames = reinterpret_cast<int32_t*>(ws + lay.frames);
+    dn::StftLaunch st; memset(&st, 0, sizeof(st));
+    st.y = wav; st.wdft = (const f32x4*)tb.dft; st.bias = tb.bias; st.out = ws + lay.c; st.lengths = lengths; st.frames = frames;
+    st.T = T; st.strength = strength;
+    HIP_TRY(dn::launch_stft(st, d, B, false, stream));
+    gl::IstftLaunch is; memset(&is, 0, sizeof(is));
+    is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.lengths = frames; is.T = T; is.y = out; is.zero_tail = 1;
+    HIP_TRY(gl::launch_istft(is, d, B, stream));
+    return IRIS_HIFIGAN_OK;
+}
+
+// Queues the estimator's two launches (or counts them); the caller has checked that an interior frame exists.
+int dn_estimate(const gl::Design& d, const float* dft, const float* wav, int L, float* bias_out, float* ws, hipStream_t stream) {
+    const int T = L / d.m.hop + 1, edge = dn::edge_frames(d.m);
+    dn::StftLaunch st; memset(&st, 0, sizeof(st));
+    st.y = wav; st.wdft = (const f32x4*)dft; st.out = ws; st.T = T;
+    HIP_TRY(dn::launch_stft(st, d, 1, true, stream));
+    dn::ReduceLaunch rd; memset(&rd, 0, sizeof(rd));
+    rd.mag = ws; rd.bias = bias_out; rd.t_lo = edge; rd.t_hi = T - edge; rd.Ks = d.ks(); rd.bins = d.bins();
+    HIP_TRY(dn::launch_bias_reduce(rd, stream));
+    return IRIS_HIFIGAN_OK;
+}
+
+int dn_check_interior(const gl::Design& d, int32_t L) {
+    const int T = L / d.m.hop + 1, edge = dn::edge_frames(d.m);
+    if (T - edge <= edge)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "L = %d: no frame of n_fft %d, hop_length %d lies wholly inside the signal (at least %d samples are needed)",
+                    L, d.m.n_fft, d.m.hop, 2 * edge * d.m.hop);
+    return IRIS_HIFIGAN_OK;
+}
+
+bool overlap(const float* a, const float* b, size_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = n * sizeof(float);
+    return x < y + bytes && y < x + bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t iris_denoiser_create(const iris_mel_frontend_config* cfg, const float* bias_host, iris_denoiser_handle** out) {
+    IRIS_ABI_BEGIN
+    if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    const int nb = d.bins(), N = d.m.n_fft;
+    if (bias_host)
+        for (int k = 0; k < nb; ++k)
+            if (!(bias_host[k] >= 0.f) || !isfinite(bias_host[k]))
+                return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bias[%d] = %g: a magnitude spectrum is finite and not negative", k, (double)bias_host[k]);
+    std::unique_ptr<iris_denoiser_handle> h(new (std::nothrow) iris_denoiser_handle);
+    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    h->d = d;
+    std::vector<float> dft((size_t)2 * nb * N), idft((size_t)2 * nb * N), w;
+    mel::fill_dft(d.m, dft.data());
+    gl::fill_idft(d.m, idft.data());
+    const int widest = 32 * d.m.dft_tiles() > 32 * d.hop_tiles() ? 32 * d.m.dft_tiles() : 32 * d.hop_tiles();
+    const std::vector<float> no_bias(widest, 0.f);                           // neither GEMM has one
+    BlobBuilder bb(nullptr);
+    mel::conv_weight_from_dft(d.m, dft.data(), w);
+    bb.dense(h->dft, w.data(), no_bias.data(), d.m.hop, 32 * d.m.dft_tiles(), d.m.taps());
+    gl::conv_weight_from_idft(d, idft.data(), w);
+    bb.dense(h->idft, w.data(), no_bias.data(), d.q(), 32 * d.hop_tiles(), d.m.taps());
+    h->wsq_off = bb.reserve(N);
+    gl::fill_wsq(d.m, bb.host.data() + h->wsq_off);
+    h->bias_off = bb.reserve(d.ks());                                        // zeros behind the last bin
+    if (bias_host) memcpy(bb.host.data() + h->bias_off, bias_host, sizeof(float) * nb);
+    TRY(upload(bb.host, h.get(), "denoiser"));
+    *out = h.release();
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_destroy(iris_denoiser_handle* h) {
+    delete h;
+    return IRIS_HIFIGAN_OK;
+}
+
+int32_t iris_denoiser_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, uint64_t* bytes) {
+    IRIS_ABI_BEGIN
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    TRY(dn_check_shape(d, B, L));
+    *bytes = (uint64_t)DnWorkspace(d, B, L).floats * sizeof(float);
+    if (*bytes < 256) *bytes = 256;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    TRY(dn_check_shape(d, B, L));
+    *n = 0;
+    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
+    return count_launches([&](float* fake) {
+        const DnTables tb = {fake, fake, fake, fake};
+        return dn_forward(d, tb, fake, B, L, nullptr, 0.f, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_set_bias(iris_denoiser_handle* h, const float* bias_dev, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h || !bias_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(h->device, true);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    HIP_TRY(hipMemcpyAsync(h->blob + h->bias_off, bias_dev, sizeof(float) * h->d.bins(), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_estimate_bias(iris_denoiser_handle* h, const float* wav_dev, int32_t L, float* bias_out_dev, void* workspace_dev,
+                                    uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(dn_check_shape(h->d, 1, L));
+    TRY(dn_check_interior(h->d, L));
+    if (!wav_dev || !bias_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    ForwardScope scope(*h, workspace_bytes, DnWorkspace(h->d, 1, L).floats);
+    TRY(scope.rc);
+    return dn_estimate(h->d, h->blob + h->dft.w_off, wav_dev, L, bias_out_dev, (float*)workspace_dev, (hipStream_t)stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_estimate_launch_count(const iris_mel_frontend_config* cfg, int32_t L, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    TRY(dn_check_shape(d, 1, L));
+    TRY(dn_check_interior(d, L));
+    return count_launches([&](float* fake) { return dn_estimate(d, fake, fake, L, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_forward(iris_denoiser_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, float strength,
+                              float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(dn_check_shape(h->d, B, L));
+    if (!(strength >= 0.f) || !isfinite(strength)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "strength must be finite and not negative, got %g", (double)strength);
+    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
+    if (!wav_dev || !out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (overlap(wav_dev, out_dev, (size_t)B * L)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev aliases wav_dev");
+    ForwardScope scope(*h, workspace_bytes, DnWorkspace(h->d, B, L).floats);
+    TRY(scope.rc);
+    const DnTables tb = {h->blob + h->dft.w_off, h->blob + h->idft.w_off, h->blob + h->wsq_off, h->blob + h->bias_off};
+    return dn_forward(h->d, tb, wav_dev, B, L, lengths_dev, strength, out_dev, (float*)workspace_dev, (hipStream_t)stream);
+    IRIS_ABI_END
+}
+
+}  // extern "C"

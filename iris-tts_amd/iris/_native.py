@@ -310,6 +310,18 @@ GRIFFIN_LIM_SYMBOLS = {
     "iris_griffin_lim_draw_phase": (_i32, [_vp, _u64, _i32, _i32, _i32, _vp, _vp]),
 }
 
+# the bias denoiser (iris.denoiser): bound by load() like SYMBOLS; it takes the mel front-end's config
+DENOISER_SYMBOLS = {
+    "iris_denoiser_workspace_bytes": (_i32, [_mfc, _i32, _i32, _u64p]),
+    "iris_denoiser_launch_count": (_i32, [_mfc, _i32, _i32, _ip]),
+    "iris_denoiser_estimate_launch_count": (_i32, [_mfc, _i32, _ip]),
+    "iris_denoiser_create": (_i32, [_mfc, _fp, _c.POINTER(_vp)]),
+    "iris_denoiser_destroy": (_i32, [_vp]),
+    "iris_denoiser_set_bias": (_i32, [_vp, _vp, _vp]),
+    "iris_denoiser_estimate_bias": (_i32, [_vp, _vp, _i32, _vp, _vp, _u64, _vp]),
+    "iris_denoiser_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _f, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -336,7 +348,7 @@ def load() -> ctypes.CDLL:
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
-                                      **GRIFFIN_LIM_SYMBOLS}.items():
+                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

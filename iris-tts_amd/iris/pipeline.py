@@ -38,12 +38,21 @@ class MelToWavePipeline:
     sample depends on every frame, so nothing is chunked and ``stream`` / ``session`` are refused -- and decides the length of
     its output itself (``hop * (T - 1)`` samples).  A batch of unequal lengths goes through ONE ragged call when the vocoder
     says ``takes_lengths`` (``GriffinLim(..., ragged=True)``: ``forward_device(mel, lengths=)``, item i bit for bit its own
-    ``infer``); one that does not raises ``NotImplementedError``."""
+    ``infer``); one that does not raises ``NotImplementedError``.
+
+    ``denoiser``: an ``iris.denoiser.Denoiser`` (or any object with ``forward_device(wav [B, L], lengths=) -> [B, L]``), or
+    None.  With one, ``infer``, ``infer_batch`` and every ``infer_from_*`` / ``resynthesize*`` route take the vocoder's fp32
+    waveform through it -- in the ragged routes with the batch's lengths -- and run the output stage afterwards as
+    stand-alone launches: ``pcm16=`` / ``normalize=`` through ``synthesis_output.pcm16_on_device``, ``resampler=`` through
+    ``Resampler.forward``.  ``stream`` and ``session`` raise ``ValueError`` then: a chunk seam needs ``n_fft / 2`` samples of
+    context on either side, and a chunked denoiser is left for later.  With ``denoiser=None`` nothing changes."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
-                 group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None):
+                 group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None,
+                 denoiser=None):
         self.postnet = postnet
+        self.denoiser = denoiser
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
@@ -79,15 +88,26 @@ class MelToWavePipeline:
         return self._refine_fn()(mel)
 
     def stream(self, mel) -> Iterator[torch.Tensor]:
-        """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``."""
+        """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``.  Refused with a
+        denoiser (``ValueError``): its frames reach ``n_fft / 2`` samples across a chunk seam."""
+        self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         yield from self.streamer.stream(self.refine(mel))
 
+    def _refuse_chunked_denoiser(self) -> None:
+        if self.denoiser is not None:
+            raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
+                             "either side, and no chunked denoiser is built; use infer / infer_batch")
+
     def _vocode_whole(self, mel: torch.Tensor, pcm16: bool, normalize: bool, resampler):
-        """One call of a whole-utterance vocoder, then the stand-alone output stages on its waveform, whose length is the
-        tensor's own: ``Resampler.forward``, or ``synthesis_output.pcm16_on_device`` (``(pcm, peaks)`` with ``normalize``)."""
-        wav = self._whole.forward_device(mel)
+        """One call of a whole-utterance vocoder, then ``_output_stage`` on its waveform."""
+        return self._output_stage(self._whole.forward_device(mel), pcm16, normalize, resampler)
+
+    @staticmethod
+    def _output_stage(wav: torch.Tensor, pcm16: bool, normalize: bool, resampler):
+        """The stand-alone output stages on a waveform that exists, whose length is the tensor's own: ``Resampler.forward``, or
+        ``synthesis_output.pcm16_on_device`` (``(pcm, peaks)`` with ``normalize``)."""
         if resampler is not None:
             return resampler.forward(wav, pcm16=pcm16, normalize=normalize)
         if not pcm16:
@@ -99,11 +119,19 @@ class MelToWavePipeline:
         """A batch through a whole-utterance vocoder that takes ``lengths``: ONE ``forward_device(padded, lengths=)``, whose
         rows are 0 past ``hop * (T_i - 1)`` -- so an item's peak is its own -- then the output stage over the whole batch
         and a list cut at each item's own count.  An item of one frame is refused by the vocoder, as ``infer`` refuses it."""
-        hop = self.streamer.hop_length
         frames = [int(t) for t in lengths]
         rows = [max(t - 1, 0) for t in frames]
+        return self._ragged_output_stage(self._whole.forward_device(padded, lengths=frames), rows, pcm16, normalize, resampler)
+
+    def _denoise(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
+        """The vocoder's waveform through the denoiser (``lengths``: the items' mel frames, ``hop`` samples each)."""
+        wav = wav.float()
+        return self.denoiser.forward_device(wav) if lengths is None else self.denoiser.forward_device(wav, lengths=lengths)
+
+    def _ragged_output_stage(self, wav: torch.Tensor, rows: Sequence[int], pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
+        """The output stage over a batch whose item i owns ``hop * rows[i]`` samples and is 0 behind them, cut per item."""
+        hop = self.streamer.hop_length
         samples = [hop * r for r in rows]
-        wav = self._whole.forward_device(padded, lengths=frames)
         if resampler is not None:
             out = resampler.forward(wav, lengths=rows, row_scale=hop, pcm16=pcm16, normalize=normalize)
             samples = [resampler.out_range(0, n)[1] for n in samples]
@@ -140,6 +168,10 @@ class MelToWavePipeline:
         result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
+        if self.denoiser is not None:
+            mel = self.refine(mel)
+            wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
+            return self._output_stage(self._denoise(wav), pcm16, normalize, resampler)
         if self._whole is not None:
             return self._vocode_whole(self.refine(mel), pcm16, normalize, resampler)
         if resampler is not None:
@@ -384,6 +416,18 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
+        if self.denoiser is not None:
+            frames = [int(t) for t in lengths]
+            if ragged_whole:
+                rows = [max(t - 1, 0) for t in frames]
+                wav = self._whole.forward_device(padded, lengths=frames)
+            elif self._whole is not None:
+                rows = [max(frames[0] - 1, 0)] * len(frames)
+                wav = self._whole.forward_device(padded)
+            else:
+                rows = frames
+                wav = self.streamer.forward(padded, lengths=lengths)
+            return self._ragged_output_stage(self._denoise(wav, rows), rows, pcm16, normalize, resampler)
         if ragged_whole:
             return self._vocode_whole_ragged(padded, lengths, pcm16, normalize, resampler)
         if self._whole is not None:
@@ -403,7 +447,9 @@ class MelToWavePipeline:
 
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
         """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
-        PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own."""
+        PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own.
+        Refused with a denoiser (``ValueError``), as ``stream`` is."""
+        self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         return PipelineSession(self, postnet_halo_frames)
