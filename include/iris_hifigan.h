@@ -813,6 +813,28 @@ int32_t iris_denoiser_estimate_bias(iris_denoiser_handle* h, const float* wav_de
 int32_t iris_denoiser_forward(iris_denoiser_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev /* or NULL */,
                               float strength, float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* Windows: the forward on samples [origin, origin + Lw) of an utterance, for a caller that receives the waveform piece by piece.
+ * origin = hop_length m0 and Lw = hop_length Mw; `final` (0 or not) says that origin + Lw is the utterance's end.  Frame t covers
+ * samples [t hop_length - n_fft / 2, t hop_length + n_fft / 2) and exists when t >= 0 and, only if final, t <= m0 + Mw.  A frame
+ * is computable in the window when every sample of its span that lies inside the utterance lies inside the window; sample s,
+ * the sum over the n_fft / hop_length frames that end at floor((s + n_fft / 2) / hop_length), is final in the window when each
+ * of those frames is computable or does not exist.  The final samples of a window are one range:
+ *     window_range -> out_lo (an index into the utterance) and out_count (0: none; out_lo is then origin).
+ * An interior window loses (n_fft / hop_length - 1) hop_length samples on either side: 768 at 1024 / 256, 128 at 256 / 128.
+ * forward_window: wav_dev [B, Lw] -> out_dev [B, out_count], each sample bit for bit that of iris_denoiser_forward on the whole
+ * utterance: a frame's sums depend on its own n_fft samples and a sample's on its own frames, in a fixed order, whichever
+ * window they are computed in.  Dense only; stateless; 2 launches, none when B == 0 or out_count == 0 (IRIS_HIFIGAN_OK).  The
+ * workspace is that of a forward of shape (B, Lw).  An origin or Lw that is negative or no multiple of hop_length returns
+ * IRIS_HIFIGAN_INVALID_ARGUMENT, an origin above 2^60 IRIS_HIFIGAN_UNSUPPORTED; the other refusals are the forward's. */
+int32_t iris_denoiser_window_range(const iris_mel_frontend_config* cfg, int64_t origin, int32_t Lw, int32_t final, int64_t* out_lo,
+                                   int64_t* out_count);
+int32_t iris_denoiser_window_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, uint64_t* bytes);
+int32_t iris_denoiser_window_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, int64_t origin, int32_t final,
+                                          int32_t* n);
+int32_t iris_denoiser_forward_window(iris_denoiser_handle* h, const float* wav_dev /* [B, Lw] */, int32_t B, int32_t Lw, int64_t origin,
+                                     int32_t final, float strength, float* out_dev /* [B, out_count] */, void* workspace_dev,
+                                     uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

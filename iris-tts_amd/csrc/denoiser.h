@@ -14,7 +14,7 @@
 //
 // dn_stft_kernel: tiling, LDS staging and summation are gl_stft_update_kernel's -- a block owns 32 frames and stages their
 // 31 + taps rows of H samples, a wave runs one 32-column tile that pairs Re and Im of 16 bins in one lane, one chain per tap
-// and 64 samples with the partial sums added -- restated here so that griffin_lim.h stays as it is.  The epilogue is the
+// and 64 samples with the partial sums added -- restated here, not templated into griffin_lim.h.  The epilogue is the
 // template parameter: SUBTRACT stores c [B][T][Qp] (interleaved complex, the inverse kernel's input), MAGNITUDE stores
 // mag [B][T][Ks] for the estimator.  A lane holds 16 accumulators and, per group of 4 bins, 4 bias values.
 //
@@ -22,6 +22,17 @@
 // T_b = M_b + 1 (0 if M_b == 0) and L_b = H M_b, bounds its loads and stores by them and writes T_b to frames[b], which the
 // inverse kernel then reads as its `lengths`.  Strides stay those of (B, T) and the tiling does not depend on T, so every
 // chain of item b has the terms and the order of its batch-of-one call at M = M_b.  Nothing at t >= T_b is read or written.
+//
+// Windows (iris_denoiser_forward_window): a dense call on samples [o, o + Lw) of an utterance, o = H m0, Lw = H Mw, `final`
+// when o + Lw is the utterance's end.  Frame t exists when t >= 0 and, if final, t <= m0 + Mw; it is computable when every
+// sample of its span inside the utterance lies inside the window; a sample is final when each of its `taps` frames is
+// computable or does not exist.  `Window` below is that rule in closed form, the only place it is written down.  A frame's
+// chain depends on its own n_fft samples alone and a row's on its own `taps` frames alone, not on the block or lane either
+// falls into, so both launches run in coordinates that start at the window's first computable frame f_lo: the STFT reads its
+// samples `y_org` = H f_lo - o into the window (StftLaunch::y_org) and stores c [B, frames, Qp]; the inverse transform sees
+// c as a whole utterance's -- a final sample's frames outside [f_lo, f_hi) do not exist, so "staged as 0, no w^2 term" is
+// the one-shot's own treatment of them -- and stores the samples from `s_org` = out_lo - H f_lo on (IstftLaunch::s_org).
+// With both origins 0 and L = H (T - 1) the launches are the whole-utterance ones.
 #pragma once
 #include "griffin_lim.h"
 
@@ -35,6 +46,25 @@ constexpr int kReduceThreads = 256;
 // frames on either side whose window leaves the signal
 inline int edge_frames(const mel::Design& d) { return (d.n_fft / 2 + d.hop - 1) / d.hop; }
 
+// The finality rule of "Windows" above for the window [H m0, H (m0 + Mw)): frames [f_lo, f_hi) are computable (f_lo is
+// clamped to f_hi when there is none) and samples [out_lo, out_lo + out_count) are final.  Frames before f_lo exist unless
+// m0 == 0, frames from f_hi on exist unless `final`, so a row j = floor((s + n_fft / 2) / H) is final when
+// j - taps + 1 >= f_lo (or m0 == 0) and j < f_hi (or final).
+struct Window {
+    long long f_lo, f_hi, out_lo, out_count;
+    Window(const mel::Design& d, long long m0, long long Mw, bool final) {
+        const long long H = d.hop, half = d.n_fft / 2, e = edge_frames(d), o = H * m0, end = o + H * Mw;
+        f_lo = m0 ? m0 + e : 0;
+        f_hi = final ? m0 + Mw + 1 : m0 + Mw - e + 1;
+        if (f_hi < f_lo) f_hi = f_lo;
+        long long lo = o, hi = end;
+        if (m0 && (f_lo + d.taps() - 1) * H - half > lo) lo = (f_lo + d.taps() - 1) * H - half;
+        if (!final && f_hi * H - half < hi) hi = f_hi * H - half;
+        out_count = f_hi > f_lo && hi > lo ? hi - lo : 0;
+        out_lo = out_count ? lo : o;
+    }
+};
+
 }  // namespace dn
 }  // namespace iris
 
@@ -45,13 +75,14 @@ namespace dn {
 enum Epilogue { SUBTRACT = 0, MAGNITUDE = 1 };
 
 struct StftLaunch {
-    const float* y;           // [B, L]
+    const float* y;           // [B, L]; frame 0 is centred on sample y_org
     const f32x4* wdft;        // the front-end's packed windowed DFT
     const float* bias;        // [Ks] (SUBTRACT)
     float* out;               // SUBTRACT: c [B, T, Qp]; MAGNITUDE: mag [B, T, Ks]
     const int* lengths;       // [B] mel frames, or NULL
     int* frames;              // [B] out: T_b (SUBTRACT)
     int L, T, hop, taps, n_fft, Ks, Qp, Gp, n_ct;
+    int y_org;                // a window: H f_lo - o ("Windows" above); 0 for a whole utterance, where L = H (T - 1)
     float strength;
 };
 
@@ -79,10 +110,10 @@ __global__ void __launch_bounds__(64 * kWaves) dn_stft_kernel(const StftLaunch a
     }
     if (EPI == SUBTRACT && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) a.frames[b] = Tb;
     if (i0 >= Tb) return;                                    // block-uniform: all 32 frames lie past the item
-    const int Lb = H * (Tb - 1);                             // a.L of a dense call
+    const int Lb = a.lengths ? H * (Tb - 1) : a.L;           // H (T - 1) of a dense whole utterance as well
 
-    {   // the front-end's window: row r, column c is sample i0 * hop - n_fft / 2 + r * hop + c; 0 outside [0, Lb)
-        const long long s0 = (long long)i0 * H - half;
+    {   // the front-end's window: row r, column c is sample y_org + i0 * hop - n_fft / 2 + r * hop + c; 0 outside [0, Lb)
+        const long long s0 = (long long)a.y_org + (long long)i0 * H - half;
         const size_t item = (size_t)b * a.L;
         for (int idx = tid; idx < R * Cp; idx += nthr) {
             const int r = idx / Cp, c = idx - r * Cp;
@@ -164,8 +195,9 @@ __global__ void __launch_bounds__(kReduceThreads) dn_bias_reduce_kernel(const Re
     a.bias[k] = (float)(sum / (double)(a.t_hi - a.t_lo));
 }
 
+// The caller sets y, L, T and y_org (a whole utterance: L = hop * (T - 1), y_org = 0).
 inline hipError_t launch_stft(StftLaunch& a, const gl::Design& d, int B, bool magnitude_only, hipStream_t stream) {
-    a.L = d.m.hop * (a.T - 1); a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Ks = d.ks(); a.Qp = d.qp();
+    a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Ks = d.ks(); a.Qp = d.qp();
     a.Gp = packed_groups(d.m.hop); a.n_ct = d.m.dft_tiles();
     const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
     if (magnitude_only) return launch_kernel_named("dn_stft_kernel<magnitude>", dn_stft_kernel<MAGNITUDE>, grid, block, d.stft_lds_bytes(), stream, a);

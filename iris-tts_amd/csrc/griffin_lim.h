@@ -307,10 +307,11 @@ struct IstftLaunch {
     const float* c;           // [B, T, Qp]
     const f32x4* widft;       // packed inverse table: `taps` taps, Gp groups, n_ct column tiles
     const float* wsq;         // [n_fft]
-    float* y;                 // [B, Ly]
+    float* y;                 // [B, Ly]: samples [s_org, s_org + Ly)
     const int* lengths;       // [B] or NULL
     int T, Ly, hop, taps, n_fft, Q, Qp, Gp, n_ct, first_row;
     int zero_tail;            // the last transform of a ragged forward: y[b, Ly_b:] = 0
+    int s_org;                // 0, and Ly = hop * (T - 1), unless a slice of the samples is stored (launch_istft_slice)
 };
 
 static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
@@ -324,7 +325,7 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const Istf
     const int R = kRows - 1 + a.taps, S = kSlice + 4;
     const int t0 = j0 - (a.taps - 1);                        // LDS row r holds frame t0 + r
     const int Tb = item_frames(a.lengths, b, a.T);
-    const int Lyb = Tb ? a.hop * (Tb - 1) : 0;               // a.Ly of a dense call
+    const int Lyb = a.lengths ? (Tb ? a.hop * (Tb - 1) : 0) : a.s_org + a.Ly;            // dense: the end of what is stored, hop * (T - 1)
     const long long s_first = (long long)j0 * a.hop - (a.n_fft >> 1);     // the block's first sample; negative ones are trimmed
     if (Lyb <= (s_first > 0 ? s_first : 0)) {                // block-uniform: every row lies past the item
         if (a.zero_tail && ct < a.n_ct) {
@@ -333,7 +334,7 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const Istf
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int col = ct * 32 + 8 * g + 4 * hi + e;
-                    const long long s = s_first + (long long)lo * a.hop + col;
+                    const long long s = s_first + (long long)lo * a.hop + col - a.s_org;
                     if (col < a.hop && s >= 0 && s < a.Ly) a.y[(size_t)b * a.Ly + (size_t)s] = 0.f;
                 }
         }
@@ -378,10 +379,10 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const Istf
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int col = ct * 32 + 8 * g + 4 * hi + e;
-            const long long s = (long long)j * a.hop + col - half;
-            if (col >= a.hop || s < 0 || s >= a.Ly) continue;
+            const long long s = (long long)j * a.hop + col - half, so = s - a.s_org;
+            if (col >= a.hop || so < 0 || so >= a.Ly) continue;
             if (s >= Lyb) {
-                if (a.zero_tail) a.y[(size_t)b * a.Ly + (size_t)s] = 0.f;
+                if (a.zero_tail) a.y[(size_t)b * a.Ly + (size_t)so] = 0.f;
                 continue;
             }
             float wss = 0.f;
@@ -390,7 +391,7 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const Istf
                 if (t >= 0 && t < Tb) wss += a.wsq[kap * a.hop + col];
             }
             const float v = acc[4 * g + e];
-            a.y[(size_t)b * a.Ly + (size_t)s] = wss > FLT_MIN ? v / wss : v;
+            a.y[(size_t)b * a.Ly + (size_t)so] = wss > FLT_MIN ? v / wss : v;
         }
 }
 
@@ -502,13 +503,20 @@ inline hipError_t launch_draw_phase(const DrawLaunch& a, int B, hipStream_t stre
     return launch_kernel_named("gl_draw_phase_kernel", gl_draw_phase_kernel, grid, block, 0, stream, a);
 }
 
-inline hipError_t launch_istft(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
-    a.Ly = d.m.hop * (a.T - 1); a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Q = d.q(); a.Qp = d.qp();
-    a.Gp = packed_groups(d.q()); a.n_ct = d.hop_tiles(); a.first_row = d.first_row();
-    const long long last = ((long long)d.m.n_fft / 2 + a.Ly - 1) / d.m.hop;             // the padded row of the last sample
+// Stores samples [s_org, s_org + Ly) of istft(c [B, T, Qp]) into y [B, Ly]; the caller has set both (Ly > 0, s_org >= 0).
+inline hipError_t launch_istft_slice(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
+    a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Q = d.q(); a.Qp = d.qp();
+    a.Gp = packed_groups(d.q()); a.n_ct = d.hop_tiles();
+    a.first_row = (int)(((long long)d.m.n_fft / 2 + a.s_org) / d.m.hop);                 // the padded row of the first sample
+    const long long last = ((long long)d.m.n_fft / 2 + a.s_org + a.Ly - 1) / d.m.hop;   // and of the last
     const int rows = (int)(last - a.first_row + 1);
     const dim3 grid((unsigned)((rows + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
     return launch_kernel_named("gl_istft_kernel", gl_istft_kernel, grid, block, d.istft_lds_bytes(), stream, a);
+}
+
+inline hipError_t launch_istft(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
+    a.Ly = d.m.hop * (a.T - 1); a.s_org = 0;                                             // first_row = d.first_row()
+    return launch_istft_slice(a, d, B, stream);
 }
 
 inline hipError_t launch_stft_update(StftLaunch& a, const Design& d, int B, hipStream_t stream) {

@@ -3,6 +3,8 @@
 // whose epilogue subtracts strength * bias from the magnitudes, and the Griffin-Lim stage's inverse STFT as it stands.  The
 // estimator is 2 launches: the same STFT storing magnitudes, and the fp64 mean over the interior frames.  The handle owns the
 // front-end's packed windowed DFT, the packed windowed inverse DFT, w^2 and the bias row.
+// forward_window is the same two launches on a window of an utterance, storing the samples that the window settles
+// (dn::Window in csrc/denoiser.h): a session that pushes consecutive windows reproduces the whole-utterance forward bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -64,7 +66,7 @@ int dn_forward(const gl::Design& d, const DnTables& tb, const float* wav, int B,
     int32_t* frames = reinterpret_cast<int32_t*>(ws + lay.frames);
     dn::StftLaunch st; memset(&st, 0, sizeof(st));
     st.y = wav; st.wdft = (const f32x4*)tb.dft; st.bias = tb.bias; st.out = ws + lay.c; st.lengths = lengths; st.frames = frames;
-    st.T = T; st.strength = strength;
+    st.L = L; st.T = T; st.strength = strength;
     HIP_TRY(dn::launch_stft(st, d, B, false, stream));
     gl::IstftLaunch is; memset(&is, 0, sizeof(is));
     is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.lengths = frames; is.T = T; is.y = out; is.zero_tail = 1;
@@ -72,11 +74,36 @@ int dn_forward(const gl::Design& d, const DnTables& tb, const float* wav, int B,
     return IRIS_HIFIGAN_OK;
 }
 
+// The window's two launches (or their count): the computable frames [f_lo, f_hi) of wav [B, Lw] into c [B, f_hi - f_lo, Qp], then
+// the final samples of its inverse transform into out [B, out_count].  The caller has checked that out_count > 0.
+int dn_forward_window(const gl::Design& d, const DnTables& tb, const float* wav, int B, int Lw, const dn::Window& w, long long origin,
+                      float strength, float* out, float* ws, hipStream_t stream) {
+    const DnWorkspace lay(d, B, Lw);                                         // f_hi - f_lo <= Lw / hop + 1
+    const int frames = (int)(w.f_hi - w.f_lo);
+    dn::StftLaunch st; memset(&st, 0, sizeof(st));
+    st.y = wav; st.wdft = (const f32x4*)tb.dft; st.bias = tb.bias; st.out = ws + lay.c; st.frames = reinterpret_cast<int32_t*>(ws + lay.frames);
+    st.L = Lw; st.T = frames; st.y_org = (int)(w.f_lo * d.m.hop - origin); st.strength = strength;
+    HIP_TRY(dn::launch_stft(st, d, B, false, stream));
+    gl::IstftLaunch is; memset(&is, 0, sizeof(is));
+    is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.T = frames; is.y = out;
+    is.Ly = (int)w.out_count; is.s_org = (int)(w.out_lo - w.f_lo * d.m.hop);
+    HIP_TRY(gl::launch_istft_slice(is, d, B, stream));
+    return IRIS_HIFIGAN_OK;
+}
+
+int dn_check_window(const gl::Design& d, int32_t B, int32_t Lw, int64_t origin) {
+    TRY(dn_check_shape(d, B, Lw));
+    if (origin < 0 || origin % d.m.hop)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin = %lld is not a multiple of hop_length %d at or above 0", (long long)origin, d.m.hop);
+    if (origin > ((int64_t)1 << 60)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "origin = %lld exceeds 2^60", (long long)origin);
+    return IRIS_HIFIGAN_OK;
+}
+
 // Queues the estimator's two launches (or counts them); the caller has checked that an interior frame exists.
 int dn_estimate(const gl::Design& d, const float* dft, const float* wav, int L, float* bias_out, float* ws, hipStream_t stream) {
     const int T = L / d.m.hop + 1, edge = dn::edge_frames(d.m);
     dn::StftLaunch st; memset(&st, 0, sizeof(st));
-    st.y = wav; st.wdft = (const f32x4*)dft; st.out = ws; st.T = T;
+    st.y = wav; st.wdft = (const f32x4*)dft; st.out = ws; st.L = L; st.T = T;
     HIP_TRY(dn::launch_stft(st, d, 1, true, stream));
     dn::ReduceLaunch rd; memset(&rd, 0, sizeof(rd));
     rd.mag = ws; rd.bias = bias_out; rd.t_lo = edge; rd.t_hi = T - edge; rd.Ks = d.ks(); rd.bins = d.bins();
@@ -92,9 +119,9 @@ int dn_check_interior(const gl::Design& d, int32_t L) {
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, const float* b, size_t n) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = n * sizeof(float);
-    return x < y + bytes && y < x + bytes;
+bool overlap(const float* a, size_t na, const float* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
 }
 
 }  // namespace
@@ -207,11 +234,60 @@ int32_t iris_denoiser_forward(iris_denoiser_handle* h, const float* wav_dev, int
     if (!(strength >= 0.f) || !isfinite(strength)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "strength must be finite and not negative, got %g", (double)strength);
     if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
     if (!wav_dev || !out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    if (overlap(wav_dev, out_dev, (size_t)B * L)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev aliases wav_dev");
+    if (overlap(wav_dev, (size_t)B * L, out_dev, (size_t)B * L)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev aliases wav_dev");
     ForwardScope scope(*h, workspace_bytes, DnWorkspace(h->d, B, L).floats);
     TRY(scope.rc);
     const DnTables tb = {h->blob + h->dft.w_off, h->blob + h->idft.w_off, h->blob + h->wsq_off, h->blob + h->bias_off};
     return dn_forward(h->d, tb, wav_dev, B, L, lengths_dev, strength, out_dev, (float*)workspace_dev, (hipStream_t)stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_window_range(const iris_mel_frontend_config* cfg, int64_t origin, int32_t Lw, int32_t final, int64_t* out_lo,
+                                   int64_t* out_count) {
+    IRIS_ABI_BEGIN
+    if (!out_lo || !out_count) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    TRY(dn_check_window(d, 1, Lw, origin));
+    const dn::Window w(d.m, origin / d.m.hop, Lw / d.m.hop, final != 0);
+    *out_lo = w.out_lo; *out_count = w.out_count;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_window_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, uint64_t* bytes) {
+    return iris_denoiser_workspace_bytes(cfg, B, Lw, bytes);                 // c of at most Lw / hop + 1 frames, and the frame counts
+}
+
+int32_t iris_denoiser_window_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, int64_t origin, int32_t final, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    gl::Design d;
+    TRY(dn_validate(cfg, &d));
+    TRY(dn_check_window(d, B, Lw, origin));
+    const dn::Window w(d.m, origin / d.m.hop, Lw / d.m.hop, final != 0);
+    *n = 0;
+    if (B == 0 || w.out_count == 0) return IRIS_HIFIGAN_OK;
+    return count_launches([&](float* fake) {
+        const DnTables tb = {fake, fake, fake, fake};
+        return dn_forward_window(d, tb, fake, B, Lw, w, origin, 0.f, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_denoiser_forward_window(iris_denoiser_handle* h, const float* wav_dev, int32_t B, int32_t Lw, int64_t origin, int32_t final,
+                                     float strength, float* out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(dn_check_window(h->d, B, Lw, origin));
+    if (!(strength >= 0.f) || !isfinite(strength)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "strength must be finite and not negative, got %g", (double)strength);
+    const dn::Window w(h->d.m, origin / h->d.m.hop, Lw / h->d.m.hop, final != 0);
+    if (B == 0 || w.out_count == 0) return IRIS_HIFIGAN_OK;
+    if (!wav_dev || !out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (overlap(wav_dev, (size_t)B * Lw, out_dev, (size_t)B * w.out_count)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev aliases wav_dev");
+    ForwardScope scope(*h, workspace_bytes, DnWorkspace(h->d, B, Lw).floats);
+    TRY(scope.rc);
+    const DnTables tb = {h->blob + h->dft.w_off, h->blob + h->idft.w_off, h->blob + h->wsq_off, h->blob + h->bias_off};
+    return dn_forward_window(h->d, tb, wav_dev, B, Lw, w, origin, strength, out_dev, (float*)workspace_dev, (hipStream_t)stream);
     IRIS_ABI_END
 }
 

@@ -320,6 +320,10 @@ DENOISER_SYMBOLS = {
     "iris_denoiser_set_bias": (_i32, [_vp, _vp, _vp]),
     "iris_denoiser_estimate_bias": (_i32, [_vp, _vp, _i32, _vp, _vp, _u64, _vp]),
     "iris_denoiser_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _f, _vp, _vp, _u64, _vp]),
+    "iris_denoiser_window_range": (_i32, [_mfc, _i64, _i32, _i32, _i64p, _i64p]),
+    "iris_denoiser_window_workspace_bytes": (_i32, [_mfc, _i32, _i32, _u64p]),
+    "iris_denoiser_window_launch_count": (_i32, [_mfc, _i32, _i32, _i64, _i32, _ip]),
+    "iris_denoiser_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _f, _vp, _vp, _u64, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -44,8 +44,19 @@ class MelToWavePipeline:
     None.  With one, ``infer``, ``infer_batch`` and every ``infer_from_*`` / ``resynthesize*`` route take the vocoder's fp32
     waveform through it -- in the ragged routes with the batch's lengths -- and run the output stage afterwards as
     stand-alone launches: ``pcm16=`` / ``normalize=`` through ``synthesis_output.pcm16_on_device``, ``resampler=`` through
-    ``Resampler.forward``.  ``stream`` and ``session`` raise ``ValueError`` then: a chunk seam needs ``n_fft / 2`` samples of
-    context on either side, and a chunked denoiser is left for later.  With ``denoiser=None`` nothing changes."""
+    ``Resampler.forward``.  ``stream`` and ``session`` raise ``ValueError`` for a plain ``Denoiser``: a chunk seam needs the
+    frames on either side of it.  With ``denoiser=None`` nothing changes.
+
+    ``denoiser=dn.chunked()`` (an ``iris.denoiser.ChunkedDenoiser``, or any object with ``chunked_sessions = True``, a
+    ``forward_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: every fp32 chunk the
+    vocoder emits is pushed into ONE ``DenoiserSession``, what becomes final is yielded (empty pieces are skipped) and the
+    end of the utterance drains it.  The concatenation equals ``infer(mel)`` bit for bit -- the session's seams are exact --
+    but the pieces are no longer all ``[B, hop * chunk]``: the first is short by the denoiser's right-hand halo
+    (``n_fft / hop - 1`` frames: 3 at 1024 / 256) and the last carries it.  Added latency: a sample leaves that halo after
+    its chunk does, on top of ``hv + hp`` -- a chunk shorter than the halo yields nothing until a later chunk covers it.
+    ``infer``, ``infer_batch`` and the ragged routes go through ``forward_device`` as before.  Such a denoiser needs fp32: a
+    pipeline built on ``forward_pcm16`` refuses it (``ValueError``), and so does a stream handed an integer chunk; a
+    whole-utterance vocoder stays refused."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -62,6 +73,10 @@ class MelToWavePipeline:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
         self.config = config
         self._whole = vocode if getattr(vocode, "whole_utterance", False) else None
+        self._chunked_denoiser = bool(getattr(denoiser, "chunked_sessions", False))
+        if self._chunked_denoiser and getattr(vocode, "__name__", "") == "forward_pcm16":
+            raise ValueError("a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+                             "forward_pcm16 (no chunked PCM stage runs behind the denoiser)")
         if self._whole is not None and hop_length is None:
             hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
@@ -89,14 +104,31 @@ class MelToWavePipeline:
 
     def stream(self, mel) -> Iterator[torch.Tensor]:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``.  Refused with a
-        denoiser (``ValueError``): its frames reach ``n_fft / 2`` samples across a chunk seam."""
+        plain denoiser (``ValueError``): its frames reach ``n_fft / 2`` samples across a chunk seam.  With a chunked one the
+        pieces are the ``DenoiserSession``'s: the first short by its halo, the last carrying it, none empty."""
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
-        yield from self.streamer.stream(self.refine(mel))
+        if not self._chunked_denoiser:
+            yield from self.streamer.stream(self.refine(mel))
+            return
+        session = self.denoiser.open_session()
+        for chunk in self.streamer.stream(self.refine(mel)):
+            piece = session.push(self._denoiser_input(chunk))
+            if piece.shape[1]:
+                yield piece
+        piece = session.flush()
+        if piece.shape[1]:
+            yield piece
+
+    @staticmethod
+    def _denoiser_input(chunk: torch.Tensor) -> torch.Tensor:
+        if not chunk.is_floating_point():
+            raise ValueError(f"a chunked denoiser takes fp32 chunks, the vocoder returned {chunk.dtype}")
+        return chunk.float()
 
     def _refuse_chunked_denoiser(self) -> None:
-        if self.denoiser is not None:
+        if self.denoiser is not None and not self._chunked_denoiser:
             raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
                              "either side, and no chunked denoiser is built; use infer / infer_batch")
 
@@ -448,7 +480,8 @@ class MelToWavePipeline:
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
         """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
         PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own.
-        Refused with a denoiser (``ValueError``), as ``stream`` is."""
+        Refused with a plain denoiser (``ValueError``), as ``stream`` is; with a chunked one the session's pieces are the
+        denoiser session's."""
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
@@ -474,7 +507,11 @@ class PipelineSession:
     not yet refined with their left-hand context, refined ones not yet emitted with theirs) plus the piece just pushed.
 
     A pipeline built on ``engine.forward_pcm16`` yields int16 chunks.  No peak normalisation here: it needs the peak of an
-    utterance that has not ended yet."""
+    utterance that has not ended yet.
+
+    With a chunked denoiser (``MelToWavePipeline(denoiser=dn.chunked())``) every chunk goes through one ``DenoiserSession``
+    on its way out: ``push`` and ``flush`` return its non-empty pieces -- the first short by the denoiser's halo, ``flush``
+    returning it -- and a chunk leaves that many samples later."""
 
     def __init__(self, pipeline: MelToWavePipeline, postnet_halo_frames: Optional[int] = None):
         sv = pipeline.streamer
@@ -509,6 +546,7 @@ class PipelineSession:
         self._refined = 0             # first raw frame not yet refined (== frames pushed into the inner session)
         self._lead = None             # (B, n_mels) of the utterance
         self._closed = False
+        self._denoise = pipeline.denoiser.open_session() if pipeline._chunked_denoiser else None
 
     @property
     def frames_received(self) -> int:
@@ -539,7 +577,16 @@ class PipelineSession:
         keep_from = max(0, stop - hp)                             # the next window's left-hand context
         self._raw = [buf[:, :, keep_from - self._base:]]
         self._base = keep_from
-        return self._inner.push(piece)
+        return self._denoised(self._inner.push(piece))
+
+    def _denoised(self, chunks: List, final: bool = False) -> List:
+        """The vocoder's chunks through the denoiser session (if there is one); empty pieces are dropped."""
+        if self._denoise is None:
+            return chunks
+        pieces = [self._denoise.push(MelToWavePipeline._denoiser_input(c)) for c in chunks]
+        if final:
+            pieces.append(self._denoise.flush())
+        return [p for p in pieces if p.shape[1]]
 
     def push(self, mel_piece) -> List[torch.Tensor]:
         """Appends the raw ``mel_piece [B, n_mels, t]`` (t >= 0, host or device) and returns the waveform chunks
@@ -565,7 +612,7 @@ class PipelineSession:
         if self._closed:
             return []
         out = self._advance(final=True)
-        out += self._inner.flush()
+        out += self._denoised(self._inner.flush(), final=True)
         self._closed = True
         self._raw = []
         return out

@@ -4,12 +4,18 @@ torch.stft -> subtract -> torch.istft on the same GPU, and, host-inclusive, agai
 copy the waveform out and run the loop in numpy.
 
     python tools/denoiser_bench.py [--iters 10] [--rounds 5] [--out profiles/denoiser_bench.json]
+    python tools/denoiser_bench.py --chunked 256          # a DenoiserSession in 256-frame pushes against the whole-utterance call
 
 Two shapes at the defaults (n_fft 1024, hop 256): 1 x 1000 and 32 x 500 mel frames of vocoder output.  Device events around
 `iters` back-to-back calls, after a warm-up; the implementations alternate in every round and the median round is reported
 with the spread.  The host-inclusive figures are a host clock from a device waveform until the denoised waveform is on the host
 (device stage) or from the same device waveform through copy-out and numpy's rfft / irfft (host loop, fewer rounds: it is
 slow).  Before timing, the two device results are compared.  Needs a GPU: there is no CPU fallback and no number without one.
+
+--chunked CHUNK_FRAMES: 1 x 1000 frames only.  One session (``Denoiser.open_session``: pushes of CHUNK_FRAMES frames, then
+``flush``) against ``forward_device`` of the same waveform in the same process, after checking that the two agree bit for bit.
+Device events around `iters` whole sessions, the two alternating in every round; reported are the session's total, the total
+divided by its windows (the per-push time) and the ratio total / whole with the spread over the rounds.
 """
 from __future__ import annotations
 
@@ -70,17 +76,62 @@ def _summary(name: str, samples) -> dict:
     return {f"{name}_ms": float(np.median(samples)), f"{name}_ms_min_max": [float(min(samples)), float(max(samples))]}
 
 
+def chunked_main(args, dev):
+    dn = Denoiser(strength=args.strength, device=dev)
+    M, hop = 1000, dn.hop_length
+    rng = np.random.default_rng(M)
+    wav = torch.from_numpy((0.1 * rng.standard_normal((1, hop * M))).astype(np.float32)).to(dev)
+    hum = torch.from_numpy((0.01 * rng.standard_normal((1, hop * 88))).astype(np.float32)).to(dev)
+    dn.set_bias(dn.estimate_bias(hum))
+    step = hop * args.chunked
+    pieces = [wav[:, at:at + step].contiguous() for at in range(0, wav.shape[1], step)]
+
+    def session():
+        s = dn.open_session()
+        out = [s.push(p) for p in pieces]
+        out.append(s.flush())
+        return out
+
+    whole = lambda: dn.forward_device(wav)
+    got = session()
+    if not torch.equal(torch.cat(got, dim=1), whole()):
+        sys.exit("the chunked session differs from the whole-utterance forward")
+    windows = sum(1 for p in got if p.shape[1])
+    for fn in (whole, session):
+        time_ms(fn, 2, dev)
+    a, b_ = [], []
+    for _ in range(args.rounds):
+        a.append(time_ms(whole, args.iters, dev))
+        b_.append(time_ms(session, args.iters, dev))
+    halo = dn.open_session().halo
+    rec = {"shape": f"1x{M}", "chunk_frames": args.chunked, "pushes": len(pieces), "windows": windows, "halo_samples": list(halo),
+           "iters": args.iters, "rounds": args.rounds, **_summary("whole", a), **_summary("chunked_total", b_),
+           "per_push_ms": float(np.median(b_) / windows), "ratio_total_over_whole": float(np.median(b_) / np.median(a)),
+           "ratio_min_max": [float(min(b_) / max(a)), float(max(b_) / min(a))], "bit_identical": True}
+    print(json.dumps(rec))
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        out = {"tool": "tools/denoiser_bench.py --chunked", "gpu": torch.cuda.get_device_name(dev), "config": dn.get_config(), "results": [rec]}
+        Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--host-rounds", type=int, default=3, help="rounds of the host-inclusive comparison (numpy is slow)")
     ap.add_argument("--strength", type=float, default=0.1)
+    ap.add_argument("--chunked", type=int, default=0, metavar="CHUNK_FRAMES",
+                    help="time a DenoiserSession in pushes of CHUNK_FRAMES frames against the whole-utterance call (1 x 1000 frames)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.chunked < 0:
+        ap.error("--chunked takes a positive frame count")
     if not torch.cuda.is_available():
         sys.exit("denoiser_bench needs a GPU")
     dev = torch.device("cuda", 0)
+    if args.chunked:
+        return chunked_main(args, dev)
     dn = Denoiser(strength=args.strength, device=dev)
     results = []
     for B, M in ((1, 1000), (32, 500)):
