@@ -1,124 +1,48 @@
 // griffin_lim.h -- log-mel to waveform on the device without a trained vocoder (iris_griffin_lim_*): the reference's
 // --use_griffin_lim path (scripts/synthesize.py:174-194), i.e. exp(clip(logmel, -11.513, 2)), librosa 0.11's
-// mel_to_stft(power=1.0) and griffinlim(n_iter, hop_length, win_length), fp32.  Window, frames and filterbank are the mel
-// front-end's (mel_frontend.h).  N = n_fft, H = hop, K = N / 2 + 1 bins, T frames, Ly = H (T - 1) samples.
+// mel_to_stft(power=1.0) and griffinlim(n_iter, hop_length, win_length), fp32.  The filterbank is the mel front-end's
+// (mel_frontend.h); window, frames, both transforms, their buffers (S, c, r, y), their summation and the ragged rule
+// (`lengths` holds frame counts: extra = 0) are stft_f32.h's.  N = n_fft, H = hop, K = N / 2 + 1 bins, T frames,
+// Ly = H (T - 1) samples.
 //
 //   invert   m = exp(clip(logmel)) (exp in double, rounded once);  x0 = max(P m, 0), P = pinv(fb) from the caller;
 //            nnls_iters steps  x <- max(x - s fb^T (fb x - m), 0),  s = 1 / lambda_max(fb fb^T) from the caller;  S = x
 //   phase    c0 = S (cos phi0, sin phi0);  n_iter times:  y = istft(c);  r = stft(y);  a = r - alpha r_prev (alpha =
 //            momentum / (1 + momentum); r_prev = 0 in the first pass);  c = S a / (|a| + FLT_MIN);  then out = istft(c)
-//   stft     the front-end's frames: frame t covers samples [t H - N / 2, t H + N / 2) of y, 0 outside
-//   istft    w[n] irfft(c[:, t])[n] overlap-added, divided by the window-sum-square where that exceeds FLT_MIN, N / 2
-//            samples trimmed at each end; Im of bins 0 and N / 2 is ignored
-//
-// Buffers (fp32, frame-major so that a block stages 32 frames as 32 LDS rows):
-//   S [B][T][Ks]   Ks = K rounded up to 4
-//   c, r [B][T][Qp] interleaved complex: column 2 k is Re, 2 k + 1 is Im of bin k; Q = N + 2 columns, Qp = Q rounded up to 8
-//                  (columns from Q on are never written and read as 0)
-//   y [B][Ly]
+//            (in a ragged forward with zero_tail set: wav[b, Ly_b:] = 0.f)
 //
 // gl_invert_kernel: ONE launch.  A block owns 32 frames; m (32 x n_mels), the residual and x (32 x K) stay in LDS and the
-// three products run on the MFMA loop of gemm_tile_f32.h against P, fb and fb^T in fragment order.  It stores S and c0.
+// three products run on the MFMA loop of gemm_tile_f32.h against P, fb and fb^T in fragment order.  It stores S and c0 and
+// bounds item b by stft::item_frames (extra = 0) like the transforms.
 //
-// gl_istft_kernel: gather form, no atomics.  View the zero-padded signal as rows of H samples: row j is the sum over taps
-// kap < N / H of frame j - kap's samples [kap H, (kap + 1) H) -- an N / H tap, C_in = Q implicit-GEMM convolution over frames
-// against the windowed inverse-DFT table [Q][N], with the taps in reverse order.  A block owns 32 rows and a wave one 32-wide
-// tile of a row's H columns (grid.z counts groups of 8 tiles); the Q columns are staged in slices of 256 (the text stage's
-// precedent), 31 + N / H frames at a time.  The epilogue sums w^2 over the frames that exist (at most N / H terms, ascending
-// tap), divides and stores the samples that survive the trim.
-//
-// gl_stft_update_kernel: the front-end's DFT convolution (same packed table, same column order: Re and Im of a bin in one
-// lane) with the phase update as its epilogue; it stores the new c and keeps r for the next pass.  grid.z counts groups of 8
-// column tiles, so a wave runs one tile.
-//
-// Ragged batches: each kernel takes `lengths` (a device pointer to [B] frame counts, or NULL: every item has T frames).  A
-// block reads T_b = min(max(lengths[b], 0), T), 0 if that is below 2, and Ly_b = H (T_b - 1), and bounds its loads, its
-// window-sum-square terms and its stores by them; strides stay T and H (T - 1), and the tiling (i0 = 32 blockIdx.x,
-// j0 = first_row + 32 blockIdx.x) does not depend on T, so every chain of item b has the terms and the order of its
-// batch-of-one call at T = T_b.  A block past its item returns before its first barrier.  Nothing at t >= T_b is read or
-// written, except that the last inverse transform (zero_tail) stores 0.f to wav[b, Ly_b:].
+// gl_stft_update_kernel: the forward transform of stft_f32.h (same packed table, same column order, same staging, chain loop
+// and decode as stft::stft_kernel) written out with the phase update as its epilogue; it stores the new c and keeps r for the
+// next pass.  It is not an instantiation of stft::stft_kernel: with the update as a policy the compiler schedules the epilogue
+// differently and a 60-pass forward measured 0.3 % slower (profiles/dsp_stft_refactor.md), so a change to the transform's
+// body is made in both.  The normalisation a / |a| amplifies what the transform's summation leaves where |a| is small.
 //
 // Start phase: with phase0 == NULL the inversion draws it in its epilogue -- Philox4x32-10, key (seed & 0xffffffff, seed >> 32),
 // counter (k >> 2, t, stream, 0) with output word k & 3 for bin k of frame t; u = (x >> 8) 2^-24, angle = 6.2831855f * u (one
 // fp32 product), phase = (cosf, sinf) of it.  A counter-based draw depends on no grid shape or batch position: item b of a call
 // uses stream item0 + b.  gl_draw_phase_kernel stores the same numbers as a packed [B][T][bins][2] tensor.
 //
-// Summation: the MFMA adds a chain's terms one after the other, and a chain of n_fft / hop * (n_fft + 2) = 4104 terms (the
-// inverse STFT at the defaults) loses more than the blocked sums of a host BLAS.  Both transforms therefore run short chains
-// and add the partial sums: one per tap and 64 columns (inverse) or 64 samples (forward).  The normalisation a / |a| amplifies
-// what is left where |a| is small.
-//
-// The kernels have internal linkage: iris_denoiser.hip includes this header as well (it launches gl_istft_kernel), and each
-// translation unit carries its own copy.
+// The kernels have internal linkage, like stft::gl_istft_kernel.
 #pragma once
-#include <float.h>
-
 #include "mel_frontend.h"
 
 namespace iris {
 namespace gl {
 
-constexpr int kRows = 32;            // frames (invert, stft) or output rows (istft) of a block
-constexpr int kWaves = 8;
-constexpr int kSlice = 256;          // columns of c staged at a time by the istft
+constexpr int kRows = stft::kRows;   // frames of a block
+constexpr int kWaves = stft::kWaves;
 constexpr double kLogLo = -11.513, kLogHi = 2.0;
 
-struct Design {
-    mel::Design m;
+struct Design : mel::Design {
     int n_iter = 0, nnls_iters = 0;
     double momentum = 0.0, nnls_step = 0.0;
-    int bins() const { return m.bins(); }
-    int ks() const { return (bins() + 3) & ~3; }
-    int q() const { return m.n_fft + 2; }
-    int qp() const { return (q() + 7) & ~7; }
-    int hop_tiles() const { return (m.hop + 31) / 32; }
-    int first_row() const { return (m.n_fft / 2) / m.hop; }                  // the padded row that holds output sample 0
     static int row_floats(int C) { return ((C + 7) & ~7) + 4; }
-    size_t invert_lds_bytes() const { return (size_t)kRows * (2 * row_floats(m.n_mels) + row_floats(bins())) * sizeof(float); }
-    size_t istft_lds_bytes() const { return (size_t)(kRows - 1 + m.taps()) * (kSlice + 4) * sizeof(float); }
-    size_t stft_lds_bytes() const { return (size_t)m.window_rows() * (m.hop8() + 4) * sizeof(float); }
+    size_t invert_lds_bytes() const { return (size_t)kRows * (2 * row_floats(n_mels) + row_floats(bins())) * sizeof(float); }
 };
-
-// idft [2][bins][n_fft]: w[n] f_k cos(2 pi k n / N) / N, then -w[n] f_k sin(2 pi k n / N) / N, with f_k = 1 for k = 0 and
-// N / 2 and 2 otherwise -- w[n] irfft(c)[n] = sum_k Re c_k idft[0][k][n] + Im c_k idft[1][k][n].  In double, angle reduced
-// by (k n) mod N, rounded once.
-inline void fill_idft(const mel::Design& d, float* idft) {
-    const double two_pi = 6.283185307179586476925286766559;
-    const int N = d.n_fft, nb = d.bins();
-    std::vector<double> w, c(N), s(N);
-    mel::fill_window(d, w);
-    for (int j = 0; j < N; ++j) { c[j] = cos(two_pi * j / N); s[j] = sin(two_pi * j / N); }
-    s[0] = 0.0;
-    if (!(N & 1)) s[N / 2] = 0.0;
-    for (int k = 0; k < nb; ++k) {
-        const bool edge = k == 0 || 2 * k == N;
-        const double f = (edge ? 1.0 : 2.0) / N;
-        for (int n = 0; n < N; ++n) {
-            const int j = (int)(((long long)k * n) % N);
-            idft[(size_t)k * N + n] = (float)(w[n] * f * c[j]);
-            idft[((size_t)nb + k) * N + n] = edge ? 0.f : (float)(-(w[n] * f * s[j]));
-        }
-    }
-}
-
-// wsq [n_fft]: w[n]^2 in double, rounded once
-inline void fill_wsq(const mel::Design& d, float* wsq) {
-    std::vector<double> w;
-    mel::fill_window(d, w);
-    for (int n = 0; n < d.n_fft; ++n) wsq[n] = (float)(w[n] * w[n]);
-}
-
-// The inverse table as the [C_out = 32 * hop_tiles][C_in = Q][k = taps] Conv1d weight of the gather: tap kk multiplies frame
-// j - (taps - 1 - kk), whose samples [(taps - 1 - kk) H, ...) land in row j.
-inline void conv_weight_from_idft(const Design& d, const float* idft, std::vector<float>& w) {
-    const int N = d.m.n_fft, H = d.m.hop, K = d.m.taps(), nb = d.bins(), Q = d.q(), C_out = 32 * d.hop_tiles();
-    w.assign((size_t)C_out * Q * K, 0.f);
-    for (int co = 0; co < H; ++co)
-        for (int q = 0; q < Q; ++q) {
-            const float* row = idft + ((size_t)(q & 1 ? nb : 0) + (q >> 1)) * N;
-            for (int kk = 0; kk < K; ++kk) w[((size_t)co * Q + q) * K + kk] = row[(K - 1 - kk) * H + co];
-        }
-}
 
 }  // namespace gl
 }  // namespace iris
@@ -126,14 +50,6 @@ inline void conv_weight_from_idft(const Design& d, const float* idft, std::vecto
 #ifdef __HIPCC__
 namespace iris {
 namespace gl {
-
-// T_b of item b: `lengths` sanitised as the header says; NULL: T.
-__device__ __forceinline__ int item_frames(const int* lengths, int b, int T) {
-    if (!lengths) return T;
-    int n = lengths[b];
-    n = n < 0 ? 0 : (n > T ? T : n);
-    return n < 2 ? 0 : n;
-}
 
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
@@ -207,7 +123,7 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const Inv
     float* m = lds;                       // [32][SM]  exp(clip(logmel)); columns from n_mels on are 0
     float* res = m + kRows * SM;          // [32][SM]  fb x - m
     float* x = res + kRows * SM;          // [32][SX]  the solution; columns from bins on are 0
-    const int Tb = item_frames(a.lengths, b, a.T);
+    const int Tb = stft::item_frames(a.lengths, b, a.T, 0);
     if (i0 >= Tb) return;                 // block-uniform: all 32 frames lie past the item
 
     for (int idx = tid; idx < kRows * Mp; idx += nthr) {             // consecutive threads: consecutive frames of one channel
@@ -303,98 +219,6 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_invert_kernel(const Inv
     }
 }
 
-struct IstftLaunch {
-    const float* c;           // [B, T, Qp]
-    const f32x4* widft;       // packed inverse table: `taps` taps, Gp groups, n_ct column tiles
-    const float* wsq;         // [n_fft]
-    float* y;                 // [B, Ly]: samples [s_org, s_org + Ly)
-    const int* lengths;       // [B] or NULL
-    int T, Ly, hop, taps, n_fft, Q, Qp, Gp, n_ct, first_row;
-    int zero_tail;            // the last transform of a ragged forward: y[b, Ly_b:] = 0
-    int s_org;                // 0, and Ly = hop * (T - 1), unless a slice of the samples is stored (launch_istft_slice)
-};
-
-static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const IstftLaunch a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, nthr = 64 * kWaves;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int lo = lane & 31, hi = lane >> 5;
-    const int b = blockIdx.y;
-    const int j0 = a.first_row + blockIdx.x * kRows;         // the block's first padded row
-    const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
-    const int R = kRows - 1 + a.taps, S = kSlice + 4;
-    const int t0 = j0 - (a.taps - 1);                        // LDS row r holds frame t0 + r
-    const int Tb = item_frames(a.lengths, b, a.T);
-    const int Lyb = a.lengths ? (Tb ? a.hop * (Tb - 1) : 0) : a.s_org + a.Ly;            // dense: the end of what is stored, hop * (T - 1)
-    const long long s_first = (long long)j0 * a.hop - (a.n_fft >> 1);     // the block's first sample; negative ones are trimmed
-    if (Lyb <= (s_first > 0 ? s_first : 0)) {                // block-uniform: every row lies past the item
-        if (a.zero_tail && ct < a.n_ct) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int col = ct * 32 + 8 * g + 4 * hi + e;
-                    const long long s = s_first + (long long)lo * a.hop + col - a.s_org;
-                    if (col < a.hop && s >= 0 && s < a.Ly) a.y[(size_t)b * a.Ly + (size_t)s] = 0.f;
-                }
-        }
-        return;
-    }
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    for (int q0 = 0; q0 < a.Qp; q0 += kSlice) {
-        const int width = a.Qp - q0 < kSlice ? a.Qp - q0 : kSlice;          // a multiple of 8
-        for (int idx = tid; idx < R * (kSlice / 4); idx += nthr) {
-            const int r = idx / (kSlice / 4), q = q0 + 4 * (idx - r * (kSlice / 4)), t = t0 + r;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (t >= 0 && t < Tb && q < a.Qp) {
-                v = *reinterpret_cast<const f32x4*>(a.c + ((size_t)b * a.T + t) * a.Qp + q);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = q + e < a.Q ? v[e] : 0.f;
-            }
-            *reinterpret_cast<f32x4*>(lds + r * S + (q - q0)) = v;
-        }
-        __syncthreads();
-        if (ct < a.n_ct)
-            for (int kk = 0; kk < a.taps; ++kk)              // one chain per tap and 64 columns (see "Summation" above)
-                for (int g0 = 0; g0 < width >> 3; g0 += 8) {
-                    f32x16 part;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) part[r] = 0.f;
-                    mma_loop(part, lds + (lo + kk) * S + 4 * hi + 8 * g0, 0,
-                             a.widft + ((size_t)kk * a.Gp + (q0 >> 3) + g0) * a.n_ct * 64 + (size_t)ct * 64 + lane, (size_t)a.n_ct * 64, a.Gp, 1,
-                             (width >> 3) - g0 < 8 ? (width >> 3) - g0 : 8);
-                    acc += part;
-                }
-        __syncthreads();
-    }
-    if (ct >= a.n_ct) return;
-
-    // D[col][row]: lane & 31 = row, registers 4g .. 4g + 3 = columns 8g + 4 (lane >> 5) + {0..3}
-    const int j = j0 + lo, half = a.n_fft >> 1;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int col = ct * 32 + 8 * g + 4 * hi + e;
-            const long long s = (long long)j * a.hop + col - half, so = s - a.s_org;
-            if (col >= a.hop || so < 0 || so >= a.Ly) continue;
-            if (s >= Lyb) {
-                if (a.zero_tail) a.y[(size_t)b * a.Ly + (size_t)so] = 0.f;
-                continue;
-            }
-            float wss = 0.f;
-            for (int kap = 0; kap < a.taps; ++kap) {
-                const int t = j - kap;
-                if (t >= 0 && t < Tb) wss += a.wsq[kap * a.hop + col];
-            }
-            const float v = acc[4 * g + e];
-            a.y[(size_t)b * a.Ly + (size_t)so] = wss > FLT_MIN ? v / wss : v;
-        }
-}
-
 struct StftLaunch {
     const float* y;           // [B, Ly]
     const f32x4* wdft;        // the front-end's packed windowed DFT
@@ -421,7 +245,7 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(cons
     const int b = blockIdx.y, i0 = blockIdx.x * kRows;
     const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
     const int H = a.hop, Cp = (H + 7) & ~7, S = Cp + 4, R = kRows - 1 + a.taps, half = a.n_fft >> 1;
-    const int Tb = item_frames(a.lengths, b, a.T);
+    const int Tb = stft::item_frames(a.lengths, b, a.T, 0);
     if (i0 >= Tb) return;                                    // block-uniform: all 32 frames lie past the item
     const int Lyb = H * (Tb - 1);                            // a.Ly of a dense call
 
@@ -491,9 +315,9 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_stft_update_kernel(cons
 }
 
 inline hipError_t launch_invert(InvertLaunch& a, const Design& d, int B, hipStream_t stream) {
-    a.n_mels = d.m.n_mels; a.bins = d.bins(); a.Ks = d.ks(); a.Qp = d.qp(); a.nnls_iters = d.nnls_iters; a.step = (float)d.nnls_step;
-    a.GpM = packed_groups(d.m.n_mels); a.nctK = packed_cotiles(d.bins());
-    a.GpK = packed_groups(d.bins()); a.nctM = packed_cotiles(d.m.n_mels);
+    a.n_mels = d.n_mels; a.bins = d.bins(); a.Ks = d.ks(); a.Qp = d.qp(); a.nnls_iters = d.nnls_iters; a.step = (float)d.nnls_step;
+    a.GpM = packed_groups(d.n_mels); a.nctK = packed_cotiles(d.bins());
+    a.GpK = packed_groups(d.bins()); a.nctM = packed_cotiles(d.n_mels);
     const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B), block(64 * kWaves);
     return launch_kernel_named("gl_invert_kernel", gl_invert_kernel, grid, block, d.invert_lds_bytes(), stream, a);
 }
@@ -503,25 +327,9 @@ inline hipError_t launch_draw_phase(const DrawLaunch& a, int B, hipStream_t stre
     return launch_kernel_named("gl_draw_phase_kernel", gl_draw_phase_kernel, grid, block, 0, stream, a);
 }
 
-// Stores samples [s_org, s_org + Ly) of istft(c [B, T, Qp]) into y [B, Ly]; the caller has set both (Ly > 0, s_org >= 0).
-inline hipError_t launch_istft_slice(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
-    a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Q = d.q(); a.Qp = d.qp();
-    a.Gp = packed_groups(d.q()); a.n_ct = d.hop_tiles();
-    a.first_row = (int)(((long long)d.m.n_fft / 2 + a.s_org) / d.m.hop);                 // the padded row of the first sample
-    const long long last = ((long long)d.m.n_fft / 2 + a.s_org + a.Ly - 1) / d.m.hop;   // and of the last
-    const int rows = (int)(last - a.first_row + 1);
-    const dim3 grid((unsigned)((rows + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
-    return launch_kernel_named("gl_istft_kernel", gl_istft_kernel, grid, block, d.istft_lds_bytes(), stream, a);
-}
-
-inline hipError_t launch_istft(IstftLaunch& a, const Design& d, int B, hipStream_t stream) {
-    a.Ly = d.m.hop * (a.T - 1); a.s_org = 0;                                             // first_row = d.first_row()
-    return launch_istft_slice(a, d, B, stream);
-}
-
 inline hipError_t launch_stft_update(StftLaunch& a, const Design& d, int B, hipStream_t stream) {
-    a.Ly = d.m.hop * (a.T - 1); a.hop = d.m.hop; a.taps = d.m.taps(); a.n_fft = d.m.n_fft; a.Ks = d.ks(); a.Qp = d.qp();
-    a.Gp = packed_groups(d.m.hop); a.n_ct = d.m.dft_tiles();
+    a.Ly = d.hop * (a.T - 1); a.hop = d.hop; a.taps = d.taps(); a.n_fft = d.n_fft; a.Ks = d.ks(); a.Qp = d.qp();
+    a.Gp = packed_groups(d.hop); a.n_ct = d.dft_tiles();
     a.alpha = (float)(d.momentum / (1.0 + d.momentum));
     const dim3 grid((unsigned)((a.T + kRows - 1) / kRows), (unsigned)B, (unsigned)((a.n_ct + kWaves - 1) / kWaves)), block(64 * kWaves);
     return launch_kernel_named("gl_stft_update_kernel", gl_stft_update_kernel, grid, block, d.stft_lds_bytes(), stream, a);

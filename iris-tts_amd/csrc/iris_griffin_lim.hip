@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 
+#define IRIS_MEL_NO_KERNEL               // this stage takes the front-end's design and filterbank, not mel_kernel
 #include "stage_host.h"
 #include "griffin_lim.h"
 
@@ -19,8 +20,8 @@ using namespace iris;
 
 struct iris_griffin_lim_handle : StageHandle {
     gl::Design d;
-    PackedGemm p, fb, fbt, dft, idft;
-    size_t wsq_off = 0;
+    PackedGemm p, fb, fbt;
+    stft::Tables t;
 };
 
 // the layout iris._native.GriffinLimConfig restates (tests/test_griffin_lim.py holds the two together)
@@ -34,30 +35,24 @@ namespace {
 int gl_validate(const iris_griffin_lim_config* c, gl::Design* d) {
     if (!c) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "config is NULL");
     const iris_mel_frontend_config mc = {c->sample_rate, c->n_fft, c->hop_length, c->win_length, c->n_mels, 0, c->fmin, c->fmax};
-    TRY(mel_validate(&mc, &d->m));
+    TRY(mel_validate(&mc, d));
     if (c->n_iter < 0 || c->nnls_iters < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "n_iter and nnls_iters must not be negative");
     if (!(c->momentum >= 0.0) || !(c->momentum < 1.0))
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "0 <= momentum < 1 is required, got %g", c->momentum);
     if (!(c->nnls_step > 0.0) || !isfinite(c->nnls_step))
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "nnls_step must be positive and finite, got %g", c->nnls_step);
-    if (c->n_fft % 32) return fail(IRIS_HIFIGAN_UNSUPPORTED, "n_fft %d is not a multiple of 32 (bins come in tiles of 16)", c->n_fft);
+    TRY(stft::validate_bin_tiles(*d));
     d->n_iter = c->n_iter; d->nnls_iters = c->nnls_iters; d->momentum = c->momentum; d->nnls_step = c->nnls_step;
-    if (d->invert_lds_bytes() > mel::kMaxLdsBytes)
+    if (d->invert_lds_bytes() > stft::kMaxLdsBytes)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the mel inversion of n_mels %d, n_fft %d needs %llu bytes of LDS, more than %llu", c->n_mels,
-                    c->n_fft, (unsigned long long)d->invert_lds_bytes(), (unsigned long long)mel::kMaxLdsBytes);
-    const size_t transform = d->istft_lds_bytes() > d->stft_lds_bytes() ? d->istft_lds_bytes() : d->stft_lds_bytes();
-    if (transform > mel::kMaxLdsBytes)
-        return fail(IRIS_HIFIGAN_UNSUPPORTED, "the frame window of n_fft %d, hop_length %d (31 + %d frames) needs %llu bytes of LDS, more than "
-                    "%llu: no form that slices the frames is built", c->n_fft, c->hop_length, d->m.taps(), (unsigned long long)transform,
-                    (unsigned long long)mel::kMaxLdsBytes);
-    return IRIS_HIFIGAN_OK;
+                    c->n_fft, (unsigned long long)d->invert_lds_bytes(), (unsigned long long)stft::kMaxLdsBytes);
+    return stft::validate_frame_window(*d);
 }
 
 int gl_check_shape(int32_t B, int32_t T) {
     if (B < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative batch");
     if (T < 2) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "T = %d: Griffin-Lim needs at least 2 frames (the output has hop (T - 1) samples)", T);
-    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
-    return IRIS_HIFIGAN_OK;
+    return check_batch(B);
 }
 
 // S first (tests read it there), then c, r and the waveform between the passes.
@@ -69,7 +64,7 @@ struct GlWorkspace {
         S = ws.take(frames * d.ks());
         c = ws.take(frames * d.qp());
         r = ws.take(frames * d.qp());
-        y = ws.take((size_t)B * d.m.hop * (T - 1));
+        y = ws.take((size_t)B * d.hop * (T - 1));
         floats = ws.off;
     }
 };
@@ -87,19 +82,19 @@ int gl_forward(const gl::Design& d, const GlTables& tb, const float* logmel, con
     inv.wp = (const f32x4*)tb.p; inv.wfb = (const f32x4*)tb.fb; inv.wfbt = (const f32x4*)tb.fbt;
     inv.S = ws + lay.S; inv.c = ws + lay.c;
     HIP_TRY(gl::launch_invert(inv, d, B, stream));
-    gl::IstftLaunch is; memset(&is, 0, sizeof(is));
+    stft::IstftLaunch is; memset(&is, 0, sizeof(is));
     is.c = ws + lay.c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.lengths = lengths; is.T = T;
     gl::StftLaunch st; memset(&st, 0, sizeof(st));
     st.wdft = (const f32x4*)tb.dft; st.S = ws + lay.S; st.c = ws + lay.c; st.r = ws + lay.r; st.y = ws + lay.y; st.T = T;
     st.lengths = lengths;
     for (int it = 0; it < d.n_iter; ++it) {
         is.y = ws + lay.y;
-        HIP_TRY(gl::launch_istft(is, d, B, stream));
+        HIP_TRY(stft::launch_istft(is, d, B, stream));
         st.first = it == 0;
         HIP_TRY(gl::launch_stft_update(st, d, B, stream));
     }
     is.y = wav_out; is.zero_tail = lengths != nullptr;
-    HIP_TRY(gl::launch_istft(is, d, B, stream));
+    HIP_TRY(stft::launch_istft(is, d, B, stream));
     return IRIS_HIFIGAN_OK;
 }
 
@@ -114,8 +109,8 @@ int gl_forward_checked(iris_griffin_lim_handle* h, const float* logmel, const fl
     if (!logmel || (need_phase && !phase0) || !wav_out || !workspace) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
     ForwardScope scope(*h, workspace_bytes, GlWorkspace(h->d, B, T).floats);
     TRY(scope.rc);
-    const GlTables tb = {h->blob + h->p.w_off, h->blob + h->fb.w_off, h->blob + h->fbt.w_off, h->blob + h->dft.w_off,
-                         h->blob + h->idft.w_off, h->blob + h->wsq_off};
+    const GlTables tb = {h->blob + h->p.w_off, h->blob + h->fb.w_off, h->blob + h->fbt.w_off, h->blob + h->t.dft.w_off,
+                         h->blob + h->t.idft.w_off, h->blob + h->t.wsq_off};
     return gl_forward(h->d, tb, logmel, phase0, seed, item0, B, T, lengths, wav_out, (float*)workspace, (hipStream_t)stream);
 }
 
@@ -130,15 +125,15 @@ int32_t iris_griffin_lim_design(const iris_griffin_lim_config* cfg, int32_t* n_b
     gl::Design d;
     TRY(gl_validate(cfg, &d));
     if (n_bins) *n_bins = d.bins();
-    const uint64_t table = (uint64_t)2 * d.bins() * d.m.n_fft;
-    if ((dft_host && dft_floats < table) || (idft_host && idft_floats < table) || (fb_host && fb_floats < (uint64_t)d.m.n_mels * d.bins()) ||
-        (wsq_host && wsq_floats < (uint64_t)d.m.n_fft))
+    const uint64_t table = (uint64_t)2 * d.bins() * d.n_fft;
+    if ((dft_host && dft_floats < table) || (idft_host && idft_floats < table) || (fb_host && fb_floats < (uint64_t)d.n_mels * d.bins()) ||
+        (wsq_host && wsq_floats < (uint64_t)d.n_fft))
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "a table does not fit its array: the DFT tables have %llu floats each, the filterbank "
-                    "%llu, the squared window %d", (unsigned long long)table, (unsigned long long)d.m.n_mels * d.bins(), d.m.n_fft);
-    if (dft_host) mel::fill_dft(d.m, dft_host);
-    if (idft_host) gl::fill_idft(d.m, idft_host);
-    if (fb_host) mel::fill_filterbank(d.m, fb_host);
-    if (wsq_host) gl::fill_wsq(d.m, wsq_host);
+                    "%llu, the squared window %d", (unsigned long long)table, (unsigned long long)d.n_mels * d.bins(), d.n_fft);
+    if (dft_host) stft::fill_dft(d, dft_host);
+    if (idft_host) stft::fill_idft(d, idft_host);
+    if (fb_host) mel::fill_filterbank(d, fb_host);
+    if (wsq_host) stft::fill_wsq(d, wsq_host);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -148,32 +143,23 @@ int32_t iris_griffin_lim_create(const iris_griffin_lim_config* cfg, const float*
     if (!out || !pinv_host) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     gl::Design d;
     TRY(gl_validate(cfg, &d));
-    const int nb = d.bins(), M = d.m.n_mels, N = d.m.n_fft;
+    const int nb = d.bins(), M = d.n_mels;
     if (n_pinv != (uint64_t)nb * M)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "pinv(fb) [n_bins][n_mels] has %llu values, got %llu", (unsigned long long)nb * M,
                     (unsigned long long)n_pinv);
     std::unique_ptr<iris_griffin_lim_handle> h(new (std::nothrow) iris_griffin_lim_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->d = d;
-    std::vector<float> dft((size_t)2 * nb * N), idft((size_t)2 * nb * N), fbank((size_t)M * nb), fbt((size_t)nb * M), w;
-    mel::fill_dft(d.m, dft.data());
-    gl::fill_idft(d.m, idft.data());
-    mel::fill_filterbank(d.m, fbank.data());
+    std::vector<float> fbank((size_t)M * nb), fbt((size_t)nb * M);
+    mel::fill_filterbank(d, fbank.data());
     for (int i = 0; i < M; ++i)
         for (int k = 0; k < nb; ++k) fbt[(size_t)k * M + i] = fbank[(size_t)i * nb + k];
-    int widest = 32 * d.m.dft_tiles();
-    for (int v : {32 * d.hop_tiles(), M, nb}) widest = v > widest ? v : widest;
-    const std::vector<float> no_bias(widest, 0.f);                           // no GEMM here has one
+    const std::vector<float> no_bias(M > nb ? M : nb, 0.f);                  // no GEMM here has one
     BlobBuilder bb(nullptr);
     bb.dense(h->p, pinv_host, no_bias.data(), M, nb, 1);
     bb.dense(h->fb, fbank.data(), no_bias.data(), nb, M, 1);
     bb.dense(h->fbt, fbt.data(), no_bias.data(), M, nb, 1);
-    mel::conv_weight_from_dft(d.m, dft.data(), w);
-    bb.dense(h->dft, w.data(), no_bias.data(), d.m.hop, 32 * d.m.dft_tiles(), d.m.taps());
-    gl::conv_weight_from_idft(d, idft.data(), w);
-    bb.dense(h->idft, w.data(), no_bias.data(), d.q(), 32 * d.hop_tiles(), d.m.taps());
-    h->wsq_off = bb.reserve(N);
-    gl::fill_wsq(d.m, bb.host.data() + h->wsq_off);
+    stft::pack_tables(bb, d, true, h->t);
     TRY(upload(bb.host, h.get(), "Griffin-Lim"));
     *out = h.release();
     return IRIS_HIFIGAN_OK;

@@ -8,6 +8,7 @@
 #include <new>
 #include <vector>
 
+#define IRIS_STFT_NO_INVERSE             // this stage launches no inverse transform
 #include "stage_host.h"
 #include "mel_frontend.h"
 
@@ -15,7 +16,8 @@ using namespace iris;
 
 struct iris_mel_frontend_handle : StageHandle {
     mel::Design d;
-    PackedGemm dft, fb;
+    stft::Tables t;
+    PackedGemm fb;
 };
 
 namespace iris {
@@ -37,10 +39,10 @@ int mel_validate(const iris_mel_frontend_config* c, mel::Design* d) {
     if (c->n_mels > 1024) return fail(IRIS_HIFIGAN_UNSUPPORTED, "n_mels %d exceeds 1024", c->n_mels);
     d->sample_rate = c->sample_rate; d->n_fft = c->n_fft; d->hop = c->hop_length; d->win = c->win_length; d->n_mels = c->n_mels;
     d->fmin = c->fmin; d->fmax = fmax;
-    if (d->lds_bytes() > mel::kMaxLdsBytes)
+    if (d->lds_bytes() > stft::kMaxLdsBytes)
         return fail(IRIS_HIFIGAN_UNSUPPORTED, "the sample window and the magnitude tile of n_fft %d, hop_length %d need %llu bytes of LDS, "
                     "more than %llu: the single-launch form does not fit and no two-launch form is built", c->n_fft, c->hop_length,
-                    (unsigned long long)d->lds_bytes(), (unsigned long long)mel::kMaxLdsBytes);
+                    (unsigned long long)d->lds_bytes(), (unsigned long long)stft::kMaxLdsBytes);
     return IRIS_HIFIGAN_OK;
 }
 
@@ -50,8 +52,7 @@ namespace {
 
 int mel_check_shape(int32_t B, int32_t L) {
     if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
-    return IRIS_HIFIGAN_OK;
+    return check_batch(B);
 }
 
 // The single launch keeps nothing in HBM between its two GEMMs; a forward still takes a workspace like every stage, of the
@@ -83,7 +84,7 @@ int32_t mel_forward_checked(iris_mel_frontend_handle* h, const void* audio_dev, 
     if (ragged && (!n_samples_dev || !frames_out_dev)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "n_samples_dev or frames_out_dev is NULL");
     ForwardScope scope(*h, workspace_bytes, kWorkspaceBytes / sizeof(float));
     TRY(scope.rc);
-    return mel_forward(h->d, h->blob, h->dft, h->fb, audio_dev, sample_format == IRIS_MEL_SAMPLES_I16, B, L,
+    return mel_forward(h->d, h->blob, h->t.dft, h->fb, audio_dev, sample_format == IRIS_MEL_SAMPLES_I16, B, L,
                        ragged ? n_samples_dev : nullptr, ragged ? max_frames_dev : nullptr, mel_out_dev, frames_out_dev, (hipStream_t)stream_);
     IRIS_ABI_END
 }
@@ -102,7 +103,7 @@ int32_t iris_mel_frontend_design(const iris_mel_frontend_config* cfg, int32_t* n
         const uint64_t need = (uint64_t)2 * d.bins() * d.n_fft;
         if (dft_floats < need) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "the DFT table has %llu floats, dft_host holds %llu",
                                            (unsigned long long)need, (unsigned long long)dft_floats);
-        mel::fill_dft(d, dft_host);
+        stft::fill_dft(d, dft_host);
     }
     if (fb_host) {
         const uint64_t need = (uint64_t)d.n_mels * d.bins();
@@ -122,13 +123,11 @@ int32_t iris_mel_frontend_create(const iris_mel_frontend_config* cfg, iris_mel_f
     std::unique_ptr<iris_mel_frontend_handle> h(new (std::nothrow) iris_mel_frontend_handle);
     if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
     h->d = d;
-    std::vector<float> dft((size_t)2 * d.bins() * d.n_fft), fbank((size_t)d.n_mels * d.bins()), w;
-    mel::fill_dft(d, dft.data());
+    std::vector<float> fbank((size_t)d.n_mels * d.bins());
     mel::fill_filterbank(d, fbank.data());
-    mel::conv_weight_from_dft(d, dft.data(), w);
-    const std::vector<float> no_bias(32 * d.dft_tiles() > d.n_mels ? 32 * d.dft_tiles() : d.n_mels, 0.f);     // neither GEMM has one
+    const std::vector<float> no_bias(d.n_mels, 0.f);
     BlobBuilder bb(nullptr);
-    bb.dense(h->dft, w.data(), no_bias.data(), d.hop, 32 * d.dft_tiles(), d.taps());
+    stft::pack_tables(bb, d, false, h->t);
     bb.dense(h->fb, fbank.data(), no_bias.data(), d.bins(), d.n_mels, 1);
     TRY(upload(bb.host, h.get(), "mel front-end"));
     *out = h.release();

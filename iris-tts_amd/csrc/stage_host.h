@@ -1,5 +1,5 @@
 // stage_host.h -- the host scaffold of the stages around the vocoder: the PostNet (iris_hifigan.hip), the VAE decoder
-// (iris_vae_decoder.hip) and the text stage (iris_text_encoder.hip).  Each of them packs a weight blob, uploads it, lays
+// (iris_vae_decoder.hip), the text stage (iris_text_encoder.hip) and the DSP stages (stft_f32.h).  Each of them packs a weight blob, uploads it, lays
 // out a workspace, checks it in front of a forward and counts its launches in a dry run; that is written here once.
 // The vocoder's own create and forward (iris_hifigan.hip, generator_internal.h) do not use it.  Not installed.
 #pragma once
@@ -78,6 +78,12 @@ struct ForwardScope {
         return fail(IRIS_HIFIGAN_WORKSPACE_TOO_SMALL, "workspace has %llu bytes, need %llu", (unsigned long long)have, (unsigned long long)need);
     }
 };
+
+// A stage whose grid.y is the batch takes at most 65535 items.
+inline int check_batch(int32_t B) {
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    return IRIS_HIFIGAN_OK;
+}
 
 // Counts the launches of `run` instead of issuing them: the forward's own code in a dry run.  `run` gets a pointer to pass
 // wherever the forward wants device memory (no pointer is dereferenced).

@@ -356,7 +356,7 @@ def mel_launch(audio, n_b, cap, cfg, tab, fma, mut=None):
 
 # ---- gl_invert_kernel ------------------------------------------------------------------------------------------------------------
 def item_frames(n, T):
-    """``item_frames`` of csrc/griffin_lim.h (n None: a dense call)."""
+    """``stft::item_frames`` of csrc/stft_f32.h at ``extra`` = 0 (n None: a dense call)."""
     if n is None:
         return T
     n = min(max(int(n), 0), T)
