@@ -116,6 +116,26 @@ class Denoiser(_NativeModel):
         off, shape = self._workspace_layout(B, L)[0]["c"]
         return self._workspace.view(torch.float32)[off:off + int(np.prod(shape))].view(shape)
 
+    def _read_frames(self, B: int, L: int) -> torch.Tensor:
+        """Test-only: the view ``frames [B]`` (int32) of the workspace, the items' T_b as the last ``forward_device`` of shape
+        (B, L) stored them (a ``forward_window`` of shape (B, Lw) stores its frame count there)."""
+        off, shape = self._workspace_layout(B, L)[0]["frames"]
+        return self._workspace.view(torch.int32)[off:off + int(np.prod(shape))].view(shape)
+
+    def _read_mag(self, L: int) -> torch.Tensor:
+        """Test-only: the view ``mag [T, Ks]`` of the workspace as the last ``estimate_bias`` of ``L`` samples left it: the
+        estimator keeps its magnitudes where a forward keeps c, at offset 0, in rows of ``Ks`` = the bins rounded up to 4."""
+        off = self._workspace_layout(1, L)[0]["c"][0]
+        T, ks = L // self.hop_length + 1, (self.n_bins + 3) // 4 * 4
+        return self._workspace.view(torch.float32)[off:off + T * ks].view(T, ks)
+
+    def _read_window_c(self, B: int, Lw: int, frames: int) -> torch.Tensor:
+        """Test-only: the view ``c [B, frames, Qp]`` as the last ``forward_window`` of shape (B, Lw) left it -- in the window's
+        own coordinates, ``frames`` = f_hi - f_lo rows per item (not the ``Lw / hop + 1`` the buffer has room for)."""
+        off, (_, T, qp) = self._workspace_layout(B, Lw)[0]["c"]
+        assert 0 <= frames <= T
+        return self._workspace.view(torch.float32)[off:off + B * frames * qp].view(B, frames, qp)
+
     # -- the native handle -------------------------------------------------------------------
     def _upload_blob(self) -> np.ndarray:
         return np.zeros(0, dtype=np.float32) if self._bias_host is None else self._bias_host

@@ -53,7 +53,28 @@ Claims -- derived, none measured against the device:
   tests/test_oracle_dsp_chain.py shows that the inputs here leave out none.  An exact-zero frame gives (float) log(1e-5f).
 * c0 of a ``phase0="device"`` forward is S times what ``draw_phase`` stores for the same seed and stream, bit for bit.
 
-``MUTATIONS`` are wrong restatements; tests/test_oracle_dsp_chain.py shows each fails against the right one.
+The bias denoiser (csrc/denoiser.h, ``iris_denoiser_*``) runs the same two transforms, so its launches are judged with the same
+parts and these beside them:
+
+    ``window_acc``        the transform of stft_kernel for a dense call whose frame 0 is centred on sample y_org of its input
+                          (StftLaunch::y_org); at y_org = 0 it is ``update_acc``.
+    ``subtract_launch``   Subtract::bins4 / nyquist: im = -sine with Im of bin 0 as 0.f, mag = sqrtf(re re + im im),
+                          g = fmaxf(fmaf(-strength, bias, mag), 0), scale = g / mag where mag > 0 and 0 otherwise,
+                          c = (scale re, scale im); the Nyquist bin from the sine column of bin 0, with bias[n_fft / 2] and
+                          magnitude(nyq, 0), and 0.f behind it.
+    ``magnitude_launch``  Magnitude::bins4 / nyquist: the same magnitudes, stored.
+    ``bias_reduce``       dn_bias_reduce_kernel: float64 sum in ascending t, float64 quotient, one rounding.
+    ``dn_window``         dn::Window.  The window's inverse transform is ``window_slice``: a slice of ``istft_launch``.
+
+Claims: ``fmaf(-strength, bias, mag)`` is written as an FMA, ``g / mag``, sqrtf and the products scale re, scale im are
+IEEE-rounded, and ``re re + im im`` is the one open contraction site -- of each of the two instantiations of dn_stft_kernel on
+its own (``DN_SITES``; they are judged separately).  The exact claim covers every stored element, subnormal squares included;
+a device test may leave out only elements whose float64 re^2 + im^2 is below ``DN_TINY`` = 2^-125, only where the device
+disagrees, at most ``DN_TINY_SHARE`` of a call's stored elements and none of a silence case
+(tests/test_oracle_denoiser_chain.py bounds their share on the CPU).
+
+``MUTATIONS`` are wrong restatements; tests/test_oracle_dsp_chain.py and tests/test_oracle_denoiser_chain.py show that each
+fails against the right one.
 """
 import numpy as np
 
@@ -99,7 +120,29 @@ MEL_RAGGED = (("default", 8229, (8229, 0, 1, 4096, 31 * 256 + 5)), ("odd_hop", 4
 
 MUTATIONS = ("taps_descending", "istft_one_chain", "stft_one_chain", "mel_partial_sums", "istft_taps_outside_slices", "ascending",
              "mel_no_nyquist", "idft_nyquist_2", "window_uncentred", "frames_shifted", "wss_past_end", "trim_short",
-             "alpha_momentum", "first_uses_rprev", "im_sign", "exp_f32", "log_f32", "clip_after_exp", "residual_sign")
+             "alpha_momentum", "first_uses_rprev", "im_sign", "exp_f32", "log_f32", "clip_after_exp", "residual_sign",
+             # the bias denoiser
+             "dn_fma_unfused", "dn_scale_unguarded", "dn_divide_last", "dn_im_sign", "dn_nyquist_bias0", "dn_nyquist_im_kept",
+             "dn_bias_sum_f32", "dn_bias_pairwise", "dn_interior_wide", "dn_mean_over_all_frames", "dn_frames_extra0",
+             "dn_window_origin_shift")
+
+# ---- the bias denoiser's cases (csrc/denoiser.h) ------------------------------------------------------------------------------------
+# (config, B, M): M mel frames, L = hop M samples, T = M + 1 frames
+# default   33 frames: two 32-frame blocks, grid.z = 4 in the forward transform, five inverse slices
+# small     fewer frames than taps (M 2); three blocks (M 69)
+# odd_hop   Cp = 16 > hop, Ks = 52 against 49 bins: the f32x4 bias load and the magnitude rows of Ks
+# wide_hop  two taps, 16 column tiles: blockIdx.z = 1 in the inverse kernel
+DN_CASES = (("default", 2, 32), ("small", 1, 2), ("small", 1, 69), ("two_tap", 1, 33), ("odd_hop", 1, 2), ("odd_hop", 1, 34),
+            ("wide_hop", 1, 2), ("wide_hop", 1, 33))
+# (config, M, lengths in mel frames): the full M, 0, 1, inside a block, T_b on a block edge, one past it
+DN_RAGGED = (("small", 69, (69, 0, 1, 31, 32, 33)), ("odd_hop", 34, (34, 0, 1, 20, 31)))
+# (config, M, m0, Mw, final), each at B = 2: a first, an interior and a last window, and the window that is the whole utterance
+DN_WINDOWS = (("default", 39, 0, 20, False), ("default", 39, 5, 20, False), ("default", 39, 19, 20, True), ("default", 39, 0, 39, True),
+              ("odd_hop", 34, 6, 20, False), ("odd_hop", 34, 14, 20, True), ("two_tap", 33, 4, 20, False), ("two_tap", 33, 13, 20, True))
+DN_STRENGTH = 1.0                                 # with denoiser_cases.bias: both branches of the clamp live
+DN_STRENGTHS = (DN_STRENGTH, 0.1, 0.0)            # 0.1 is the library's default
+DN_TINY = 2.0 ** -125                             # float64 re^2 + im^2 below this: the only elements a device test may leave out
+DN_TINY_SHARE = 1e-3                              # and at most this share of a case's stored elements
 
 
 def case_id(case) -> str:
@@ -256,10 +299,11 @@ def tap_weights(w, C):
     return np.ascontiguousarray(pad_cols(w.transpose(2, 0, 1), C))
 
 
-def stage_rows(x, n_b, d, T, mut=None):
-    """``[T, taps, hop8]``: row t, tap kk, column c is sample t hop - n_fft / 2 + kk hop + c; 0 for c >= hop and outside [0, n_b)."""
+def stage_rows(x, n_b, d, T, mut=None, org=0):
+    """``[T, taps, hop8]``: row t, tap kk, column c is sample org + t hop - n_fft / 2 + kk hop + c; 0 for c >= hop and outside
+    [0, n_b).  ``org``: StftLaunch::y_org, 0 for a whole utterance."""
     t, kk, c = np.arange(T)[:, None, None], np.arange(d.taps)[None, :, None], np.arange(d.cp)[None, None, :]
-    s = (t + kk + (1 if mut == "frames_shifted" else 0)) * d.hop + c - d.half
+    s = (t + kk + (1 if mut == "frames_shifted" else 0)) * d.hop + c - d.half + int(org)
     ok = (c < d.hop) & (s >= 0) & (s < n_b)
     x = np.asarray(x, dtype=np.float32)
     if x.size == 0:
@@ -308,6 +352,7 @@ def decided(v64):
 MEL_SITES = {"mag": 3}
 INVERT_SITES = {"nnls": 2}
 UPDATE_SITES = {"alpha": 2, "den": 3}
+DN_SITES = {"mag": 3}                             # per instantiation of dn_stft_kernel: the compiler may contract each its own way
 
 
 def assignments(sites):
@@ -483,6 +528,212 @@ def update_launch(acc, S, r_prev, cfg, first, fma, mut=None, momentum=MOMENTUM):
     return r, c
 
 
+# ---- the bias denoiser: dn_stft_kernel<subtract | magnitude>, dn_bias_reduce_kernel, dn::Window ------------------------------------
+def dn_waveform_item(n, cfg, seed):
+    """``[n]`` float32, the seeded waveform of a denoiser case (tests/denoiser_cases.py describes it): two tones at 1 % and 9 %
+    of the sample rate, amplitudes 0.7 and 0.1, white noise at 1e-3."""
+    rng = np.random.default_rng(4700 + 13 * n + seed)
+    t = np.arange(n, dtype=np.float64) / cfg["sample_rate"]
+    x = 1e-3 * rng.standard_normal(n)
+    for f, a in ((0.01 * cfg["sample_rate"], 0.7), (0.09 * cfg["sample_rate"], 0.1)):
+        x += a * np.sin(2.0 * np.pi * f * t + rng.uniform(0.0, 2.0 * np.pi))
+    return x.astype(np.float32)
+
+
+def dn_wave(name, B, M, seed=0):
+    """``[B, hop M]`` float32, the caller's own copy: item b is ``dn_waveform_item(hop M, cfg, seed + b)``."""
+    if ("dnwav", name, B, M, seed) not in _cache:
+        cfg = GL_CONFIGS[name]
+        _cache[("dnwav", name, B, M, seed)] = np.stack([dn_waveform_item(cfg["hop_length"] * M, cfg, seed + b) for b in range(B)])
+    return _cache[("dnwav", name, B, M, seed)].copy()
+
+
+def dn_case_m(name):
+    """The largest M of a config in ``DN_CASES``: the shape of its silence case."""
+    return max(M for n, _, M in DN_CASES if n == name)
+
+
+def dn_silence(name):
+    """``[2, hop M]``: item 0 is digital silence; item 1 has its middle 2 n_fft samples at 0.0f -- whole frames with mag == 0
+    beside live ones, and frames that are partly silent."""
+    cfg = GL_CONFIGS[name]
+    w = dn_wave(name, 2, dn_case_m(name), seed=20)
+    w[0] = 0
+    mid = w.shape[1] // 2
+    w[1, mid - cfg["n_fft"]:mid + cfg["n_fft"]] = 0
+    return w
+
+
+def dn_forced_bias(bias):
+    """``bias`` with every fourth entry from 0 forced to exactly 0.0 (scale == 1; bins 0 and n_fft / 2 are among them) and
+    every fourth from 2 to 1e30 (scale == 0), the odd ones left as they are."""
+    out = np.array(bias, dtype=np.float32)
+    out[0::4], out[2::4] = 0.0, 1e30
+    return out
+
+
+def dn_item_frames(m, T, mut=None):
+    """``stft::item_frames`` at ``extra`` = 1 -- ``m`` is an item's MEL frames (None: a dense call) -> its T_b."""
+    if m is None:
+        return T
+    extra = 0 if mut == "dn_frames_extra0" else 1
+    n = min(max(int(m), 0), T - extra) + extra
+    return 0 if n < 2 else n
+
+
+def window_acc(y, y_org, frames, cfg, tab, mut=None):
+    """The transform of ``stft_kernel`` for a dense call whose frame 0 is centred on sample ``y_org`` of ``y [Lw]``:
+    ``[frames, 32 dft_tiles]``.  Samples outside [0, Lw) read as 0.  With ``y_org`` = 0 and Lw = hop (frames - 1) it is
+    ``update_acc``; a ragged item is the dense call on its own ``y[:L_b]``."""
+    d = Design(cfg)
+    tab = mutate_tables(tab, cfg, mut)
+    y = np.asarray(y, dtype=np.float32)
+    org = int(y_org) + (d.hop if mut == "dn_window_origin_shift" else 0)
+    rows = stage_rows(y, len(y), d, frames, mut, org)
+    return transform_acc(rows, tap_weights(dft_conv_weight(d, tab["dft"]), d.cp), True, mut)
+
+
+def dn_parts(acc, d, mut=None):
+    """``(re, im, nyq)`` as ``decode_bins`` hands them to a policy: im = -sine, Im of bin 0 as 0.f, nyq from the sine column of bin 0."""
+    b = np.arange(d.half)
+    re, sine = acc[:, d.dft_col(b, 0)], acc[:, d.dft_col(b, 1)]
+    im = sine.copy() if mut == "dn_im_sign" else -sine
+    im[:, 0] = 0
+    return re, im, sine[:, 0].copy()
+
+
+def subtract_scale(re, im, bias, strength, fma, mut=None):
+    """``(scale, g, mag)`` of ``dn::subtract_scale(dn::magnitude(re, im), bias, strength)``."""
+    zero, s = np.float32(0), np.float32(strength)
+    mag = np.sqrt(sum_sq(re, im, fma["mag"]))
+    g = np.maximum(mag - s * bias if mut == "dn_fma_unfused" else co.fmaf32(-s, bias, mag), zero)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scale = g / mag if mut == "dn_scale_unguarded" else np.where(mag > 0, g / mag, zero)
+    return scale.astype(np.float32), g, mag
+
+
+def subtract_launch(acc, bias, strength, cfg, fma, mut=None):
+    """``acc`` of ``window_acc`` -> ``c [Tb, Q]`` exactly as ``Subtract::bins4`` and ``Subtract::nyquist`` write it."""
+    d = Design(cfg)
+    half = d.half
+    bias = np.asarray(bias, dtype=np.float32)
+    assert bias.shape == (d.bins,)
+    re, im, nyq = dn_parts(acc, d, mut)
+    c = np.zeros((acc.shape[0], d.q), np.float32)
+    scale, g, mag = subtract_scale(re, im, bias[None, :half], strength, fma, mut)
+    if mut == "dn_divide_last":
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c[:, 0:2 * half:2], c[:, 1:2 * half:2] = np.where(mag > 0, g * re / mag, 0), np.where(mag > 0, g * im / mag, 0)
+    else:
+        c[:, 0:2 * half:2], c[:, 1:2 * half:2] = scale * re, scale * im
+    c[:, 2 * half] = subtract_scale(nyq, np.zeros_like(nyq), bias[0 if mut == "dn_nyquist_bias0" else half], strength, fma, mut)[0] * nyq
+    if mut == "dn_nyquist_im_kept":                              # the sine column that carried the value, scaled like an Im
+        c[:, 2 * half + 1] = -c[:, 2 * half]
+    return c
+
+
+def magnitude_launch(acc, cfg, fma):
+    """``acc`` of ``window_acc`` -> ``mag [Tb, bins]`` as ``Magnitude::bins4`` and ``Magnitude::nyquist`` write it."""
+    d = Design(cfg)
+    re, im, nyq = dn_parts(acc, d)
+    mag = np.empty((acc.shape[0], d.bins), np.float32)
+    mag[:, :d.half] = np.sqrt(sum_sq(re, im, fma["mag"]))
+    mag[:, d.half] = np.sqrt(sum_sq(nyq, np.zeros_like(nyq), fma["mag"]))
+    return mag
+
+
+def dn_tiny(acc, cfg):
+    """``[Tb, Q]`` bool: the elements of c whose float64 re^2 + im^2 lies below ``DN_TINY`` -- where fp32 squares go subnormal."""
+    d = Design(cfg)
+    re, im, nyq = (v.astype(np.float64) for v in dn_parts(acc, d))
+    tiny = np.zeros((acc.shape[0], d.q), bool)
+    t = re * re + im * im < DN_TINY
+    tiny[:, 0:2 * d.half:2], tiny[:, 1:2 * d.half:2], tiny[:, 2 * d.half] = t, t, nyq * nyq < DN_TINY
+    return tiny
+
+
+def dn_interior(cfg, T, mut=None):
+    """``(t_lo, t_hi)`` of ``dn_estimate``: the frames whose window lies wholly inside the signal, e = ceil(n_fft / 2 / hop)."""
+    d = Design(cfg)
+    edge = (d.half + d.hop - 1) // d.hop
+    if mut == "dn_mean_over_all_frames":
+        return 0, T
+    if mut == "dn_interior_wide":
+        edge -= 1
+    return edge, T - edge
+
+
+def _pairwise(x):
+    return x[0] if len(x) == 1 else _pairwise(x[:len(x) // 2]) + _pairwise(x[len(x) // 2:])
+
+
+def bias_reduce(mag, t_lo, t_hi, mut=None):
+    """dn_bias_reduce_kernel: the fp32 terms summed in float64 strictly in ascending t, divided by the count in float64, rounded
+    to fp32 once.  ``dn_bias_pairwise`` is the tree order with fp32 partial sums: in float64 the order of at most a few
+    hundred fp32 terms moves the sum by 2^-53 relative, 2^-29 of the distance between two fp32 values, and no case can show it."""
+    m = np.asarray(mag, dtype=np.float32)[t_lo:t_hi]
+    assert t_hi > t_lo and m.shape[0] == t_hi - t_lo
+    if mut == "dn_bias_sum_f32":
+        total = np.add.accumulate(m, axis=0, dtype=np.float32)[-1]
+        return (total / np.float32(t_hi - t_lo)).astype(np.float32)
+    if mut == "dn_bias_pairwise":
+        return (_pairwise(m).astype(np.float64) / np.float64(t_hi - t_lo)).astype(np.float32)
+    total = np.zeros(m.shape[1], np.float64)
+    for t in range(m.shape[0]):
+        total = total + m[t].astype(np.float64)
+    return (total / np.float64(t_hi - t_lo)).astype(np.float32)
+
+
+def dn_window(cfg, m0, Mw, final, mut=None):
+    """``dn::Window`` restated: ``(f_lo, f_hi, out_lo, out_count)`` of the window [hop m0, hop (m0 + Mw))."""
+    d = Design(cfg)
+    H, half, e = d.hop, d.half, (d.half + d.hop - 1) // d.hop
+    o, end = H * m0, H * (m0 + Mw)
+    f_lo = m0 + e if m0 else 0
+    f_hi = max(m0 + Mw + 1 if final else m0 + Mw - e + 1, f_lo)
+    lo = max(o, (f_lo + d.taps - 1) * H - half) if m0 else o
+    hi = end if final else min(end, f_hi * H - half)
+    count = hi - lo if f_hi > f_lo and hi > lo else 0
+    return f_lo, f_hi, (lo if count else o), count
+
+
+def window_slice(c, frames, s_org, Ly, cfg, tab, mut=None):
+    """``launch_istft_slice`` on ``c [frames, Qp]``: samples [s_org, s_org + Ly) of the dense inverse transform of c taken as a
+    whole utterance's, so no new restatement is needed.  The kernel bounds a dense slice by s_org + Ly where ``istft_launch``
+    bounds by hop (frames - 1), and s_org + Ly <= hop (frames - 1) in both cases of ``dn::Window``: a final window ends at
+    sample hop (m0 + Mw) = hop (f_hi - 1), so out_lo + out_count - hop f_lo = hop (frames - 1); an interior one at or before
+    hop f_hi - n_fft / 2, and n_fft / 2 >= hop.  Frames outside [f_lo, f_hi) "do not exist": t < 0 or t >= frames in the
+    window's coordinates, which is the rule for the staged zeros and the w^2 terms that ``istft_launch`` already restates.  A
+    row's chain does not depend on the block it falls into, so the other ``first_row`` of a slice changes no bit."""
+    d = Design(cfg)
+    assert 0 <= s_org and Ly > 0 and s_org + Ly <= d.hop * (frames - 1), (s_org, Ly, frames)
+    y, written = istft_launch(c, frames, frames, cfg, tab, False, mut)
+    assert written[s_org:s_org + Ly].all()
+    return y[s_org:s_org + Ly]
+
+
+def dn_forward_np(wav, m, bias, strength, cfg, tab, fma, mut=None):
+    """One item through ``dn_forward``: ``wav [L]``, ``m`` its mel frames or None -> ``{"frames", "acc", "c", "out"}``."""
+    d = Design(cfg)
+    T = len(wav) // d.hop + 1
+    Tb = dn_item_frames(m, T, mut)
+    out = {"frames": Tb, "acc": None, "c": np.zeros((0, d.q), np.float32)}
+    if Tb:
+        out["acc"] = window_acc(np.asarray(wav)[:d.hop * (Tb - 1)], 0, Tb, cfg, tab, mut)
+        out["c"] = subtract_launch(out["acc"], bias, strength, cfg, fma, mut)
+    out["out"], written = istft_launch(out["c"], Tb, T, cfg, tab, True, mut)
+    assert written.all()
+    return out
+
+
+def dn_estimate_np(wav, cfg, tab, fma, mut=None):
+    """``dn_estimate`` on ``wav [L]`` -> ``(mag [T, bins], bias [bins])``."""
+    d = Design(cfg)
+    T = len(wav) // d.hop + 1
+    mag = magnitude_launch(window_acc(wav, 0, T, cfg, tab, mut), cfg, fma)
+    return mag, bias_reduce(mag, *dn_interior(cfg, T, mut), mut)
+
+
 # ---- a forward on the CPU (the restatements fed with their own outputs) -------------------------------------------------------------
 def forward_np(logmel, phase, cfg, tab, n_iter, fma, length=None, nnls_iters=NNLS_ITERS, mut=None):
     """One item through ``gl_forward``: ``{"S", "c0", "wav": {n: out_n}, "r": [..], "c": [..], "y": [..]}`` for n <= n_iter."""
@@ -508,8 +759,9 @@ class Session:
 
     def __init__(self):
         self.alive = {"mel_kernel": assignments(MEL_SITES), "gl_invert_kernel": assignments(INVERT_SITES),
-                      "gl_stft_update_kernel": assignments(UPDATE_SITES)}
-        self.stats = {}
+                      "gl_stft_update_kernel": assignments(UPDATE_SITES),
+                      "dn_stft_kernel<subtract>": assignments(DN_SITES), "dn_stft_kernel<magnitude>": assignments(DN_SITES)}
+        self.stats, self.judged = {}, set()
 
     def count(self, kind, exact=0, undecided=0, frames=0, ratio=0.0):
         s = self.stats.setdefault(kind, {"exact": 0, "undecided": 0, "frames": 0, "worst": 0.0})
@@ -522,6 +774,7 @@ class Session:
         """``restate(fma)`` -> the restatement under one assignment; ``compare(restated)`` -> the number of elements that
         differ from the device.  Keeps the assignments with no difference; fails, naming the launch, when none is left."""
         left, seen = [], []
+        self.judged.add(kernel)
         for fma in self.alive[kernel]:
             bad = compare(restate(fma))
             seen.append((fma, bad))
@@ -535,6 +788,8 @@ class Session:
         for kind, s in sorted(self.stats.items()):
             print(f"{kind}: {s['exact']} elements exact, {s['undecided']} of {s['frames']} frames undecided, worst error / bar {s['worst']:.3f}")
         for kernel, left in self.alive.items():
+            if kernel not in self.judged:                       # another module's kernels
+                continue
             print(f"{kernel}: contraction assignment(s) that reproduce every element: {left}")
 
 

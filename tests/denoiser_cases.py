@@ -10,10 +10,14 @@ from __future__ import annotations
 
 import numpy as np
 
+from oracle import dsp_chain_cases as O
+
 import denoiser_restatement as D
 import griffin_lim_cases as GC
 
-CONFIGS = GC.CONFIGS                      # default 1024 / 256 / 1024, small 64 / 16 / 48, two_tap 256 / 128 / 256
+# default 1024 / 256 / 1024, small 64 / 16 / 48, two_tap 256 / 128 / 256 (griffin_lim_cases's), and for the chain tests
+# (tests/test_gpu_denoiser_chain.py) odd_hop 96 / 12 / 80 and wide_hop 1024 / 512 / 1024
+CONFIGS = {**GC.CONFIGS, **{name: O.GL_CONFIGS[name] for name in ("odd_hop", "wide_hop")}}
 
 # (config, B, M): one frame past a 32-frame block edge; 40 frames; fewer frames than taps; three blocks; two taps
 CASES = (("default", 2, 32), ("default", 2, 39), ("small", 1, 2), ("small", 1, 69), ("two_tap", 1, 33))
@@ -30,13 +34,7 @@ def stft_args(name: str):
     return cfg["n_fft"], cfg["hop_length"], cfg["win_length"]
 
 
-def waveform_item(n: int, cfg: dict, seed: int) -> np.ndarray:
-    rng = np.random.default_rng(4700 + 13 * n + seed)
-    t = np.arange(n, dtype=np.float64) / cfg["sample_rate"]
-    x = 1e-3 * rng.standard_normal(n)
-    for f, a in ((0.01 * cfg["sample_rate"], 0.7), (0.09 * cfg["sample_rate"], 0.1)):
-        x += a * np.sin(2.0 * np.pi * f * t + rng.uniform(0.0, 2.0 * np.pi))
-    return x.astype(np.float32)
+waveform_item = O.dn_waveform_item        # (n, cfg, seed): the recipe lives beside the chain oracle's cases, which draw on it too
 
 
 _cache: dict = {}
@@ -69,7 +67,12 @@ def bias(case) -> np.ndarray:
 
 def tables(name: str) -> dict:
     """The library's fp32 tables (``dft``, ``idft``, ``wsq``) of config `name`: the Griffin-Lim stage's, host only."""
-    return GC.tables(name)
+    return GC.tables(name) if name in GC.CONFIGS else O.gl_tables(name)
+
+
+def config_bias(name: str) -> np.ndarray:
+    """The bias of the largest chain case (``O.DN_CASES``) of config `name`: what that config's ragged, window and silence cases use."""
+    return bias(next(c for c in O.DN_CASES if c[0] == name and c[2] == O.dn_case_m(name)))
 
 
 def restated(case, strength: float = STRENGTH, f32: bool = False) -> np.ndarray:
