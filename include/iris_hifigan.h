@@ -835,6 +835,50 @@ int32_t iris_denoiser_forward_window(iris_denoiser_handle* h, const float* wav_d
                                      int32_t final, float strength, float* out_dev /* [B, out_count] */, void* workspace_dev,
                                      uint64_t workspace_bytes, void* stream);
 
+/* ---- Time stretch: a phase vocoder between the two transforms above (csrc/time_stretch.h) -------------------------------
+ * Tempo without pitch: librosa.effects.time_stretch(y, rate=, n_fft=, hop_length=, win_length=) on the stage's own frame rules
+ * (center=True, zero padding, periodic Hann centred in n_fft), fp32.  Only n_fft, hop_length and win_length of the config are
+ * read: n_fft <= 4096, hop_length divides n_fft and is a multiple of 4, win_length <= n_fft, and the Griffin-Lim stage's
+ * limits on the transforms (2048 / 512, librosa's defaults for this effect, is inside them).  wav [B, L], L a multiple of
+ * hop_length, has T = L / hop_length + 1 frames c = stft(wav); rate is an argument of the forward, in [0.25, 4]:
+ *     T_out = ceil(T / rate);  step_t = t rate;  i = floor(step_t);  alpha = (float)(step_t - i)        (double; a column >= T is 0)
+ *     mag[t,k] = fmaf(alpha, |c[i+1,k]|, (1 - alpha) |c[i,k]|)
+ *     dphi = turns(c[i+1,k]) - turns(c[i,k]) - adv_k;  dphi -= rintf(dphi);  adv_k = ((k hop_length) mod n_fft) / n_fft
+ *     acc[0,k] = turns(c[0,k]);  acc[t+1,k] = acc[t,k] + adv_k + dphi;  out_c[t,k] = mag[t,k] (cos, sin)(2 pi acc[t,k])
+ *     n_out = rint(L / rate) (double, half to even);  out = istft(out_c, length = n_out)
+ * acc is a uint32 of 2^-32 turns: it wraps where an fp32 sum of radians would lose the phase, and its sum is associative, so
+ * two runs agree bit for bit whatever order the scan takes.  istft(length=): samples below min(n_out, hop_length (T_out - 1) +
+ * n_fft / 2) are the overlap-add value over the window-sum-square of the frames that exist, the rest are 0.0f.
+ * out_samples: T_out and n_out of one item of L samples, on the host, by the lines the device runs.
+ * forward: wav_dev [B, L] -> out_dev [B, n_out], 4 launches (the STFT, the vocoder's step, its scan, the inverse STFT).
+ * forward_ragged: lengths_dev [B] (device, or NULL: dense) holds the items' MEL frames as for the denoiser: M_b =
+ * min(max(lengths[b], 0), L / hop_length), L_b = hop_length M_b, T_b = M_b + 1 (an item with M_b == 0 is empty).  Item b's
+ * n_out_b = rint(L_b / rate) samples are bit for bit its batch-of-one call on wav[b, :L_b], out[b, n_out_b:] is stored as 0.0f,
+ * nothing of wav past L_b is read, and counts_out_dev [B] (or NULL) receives n_out_b: the next stage's lengths.  Row strides
+ * are n_out of the whole L.  The host never reads the lengths.
+ * After a forward the workspace holds, each starting on 256 bytes: c [B][T][Qp], mag [B][T_out][Ks] (fp32), inc and acc
+ * [B][T_out][Ks] (uint32), out_c [B][T_out][Qp], then T_b, T_out_b and n_out_b [B] (int32).  Ks = n_fft / 2 + 1 rounded up to 4,
+ * Qp = n_fft + 2 rounded up to 8.
+ * A rate outside [0.25, 4] or not finite, L no multiple of hop_length, a negative shape, a NULL pointer and out_dev overlapping
+ * wav_dev return IRIS_HIFIGAN_INVALID_ARGUMENT; an unsupported config, B > 65535 and a shape whose buffers pass 2^31 elements
+ * IRIS_HIFIGAN_UNSUPPORTED; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches.  B == 0 or L == 0:
+ * nothing to do, IRIS_HIFIGAN_OK. */
+typedef struct iris_time_stretch_handle iris_time_stretch_handle;
+/* Host only (no device is needed); the launch count is a dry run of the forward's own code. */
+int32_t iris_time_stretch_out_samples(const iris_mel_frontend_config* cfg, int32_t L, double rate, int32_t* frames_out, int32_t* samples_out);
+int32_t iris_time_stretch_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, double rate, uint64_t* bytes);
+int32_t iris_time_stretch_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t L, double rate, int32_t* n);
+/* create: on the current device, which becomes the handle's.  The forwards are asynchronous on `stream`, allocate nothing,
+ * and are safe inside a stream capture. */
+int32_t iris_time_stretch_create(const iris_mel_frontend_config* cfg, iris_time_stretch_handle** out);
+int32_t iris_time_stretch_destroy(iris_time_stretch_handle* h);
+int32_t iris_time_stretch_forward(iris_time_stretch_handle* h, const float* wav_dev, int32_t B, int32_t L, double rate, float* out_dev,
+                                  void* workspace_dev, uint64_t workspace_bytes, void* stream);
+int32_t iris_time_stretch_forward_ragged(iris_time_stretch_handle* h, const float* wav_dev, int32_t B, int32_t L,
+                                         const int32_t* lengths_dev /* or NULL */, double rate, float* out_dev,
+                                         int32_t* counts_out_dev /* [B] or NULL */, void* workspace_dev, uint64_t workspace_bytes,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

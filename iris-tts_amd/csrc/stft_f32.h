@@ -53,7 +53,9 @@
 // the stores; strides stay T and L, and the tiling (i0 = 32 blockIdx.x, j0 = first_row + 32 blockIdx.x) does not depend on T,
 // so every chain of item b has the terms and the order of its batch-of-one call at T = T_b.  A block past its item returns
 // before its first barrier.  Nothing at t >= T_b is read or written, except that an inverse transform with zero_tail set
-// stores 0.f to y[b, L_b:].
+// stores 0.f to y[b, L_b:].  The time stretch (time_stretch.h) sets IstftLaunch::sample_counts beside `lengths`: item b then owns
+// sample_counts[b] samples instead of H (T_b - 1) and lengths[b] frames as they stand (one frame is an item), which is
+// istft(c, length=); samples past H (T_b - 1) + N / 2 have no frame and come out as 0.  NULL in every other launch.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -322,6 +324,8 @@ struct IstftLaunch {
     const float* wsq;         // [n_fft]
     float* y;                 // [B, Ly]: samples [s_org, s_org + Ly)
     const int* lengths;       // [B] frame counts, or NULL
+    const int* sample_counts; // [B] or NULL (every launch but the time stretch's): item b owns samples [0, sample_counts[b]) and
+                              // lengths[b] frames, one frame included -- istft(c, length=) on a ragged batch (time_stretch.h)
     int T, Ly, hop, taps, n_fft, Q, Qp, Gp, n_ct, first_row;
     int zero_tail;            // the last transform of a ragged forward: y[b, Ly_b:] = 0
     int s_org;                // 0, and Ly = hop * (T - 1), unless a slice of the samples is stored (launch_istft_slice)
@@ -337,8 +341,14 @@ static __global__ void __launch_bounds__(64 * kWaves) gl_istft_kernel(const Istf
     const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
     const int R = kRows - 1 + a.taps, S = kSlice + 4;
     const int t0 = j0 - (a.taps - 1);                        // LDS row r holds frame t0 + r
-    const int Tb = item_frames(a.lengths, b, a.T, 0);
-    const int Lyb = a.lengths ? (Tb ? a.hop * (Tb - 1) : 0) : a.s_org + a.Ly;            // dense: the end of what is stored, hop * (T - 1)
+    int Tb, Lyb;
+    if (a.sample_counts) {
+        Tb = a.lengths[b] < 0 ? 0 : (a.lengths[b] > a.T ? a.T : a.lengths[b]);
+        Lyb = a.sample_counts[b] < 0 ? 0 : (a.sample_counts[b] > a.s_org + a.Ly ? a.s_org + a.Ly : a.sample_counts[b]);
+    } else {
+        Tb = item_frames(a.lengths, b, a.T, 0);
+        Lyb = a.lengths ? (Tb ? a.hop * (Tb - 1) : 0) : a.s_org + a.Ly;                  // dense: the end of what is stored, hop * (T - 1)
+    }
     const long long s_first = (long long)j0 * a.hop - (a.n_fft >> 1);     // the block's first sample; negative ones are trimmed
     if (Lyb <= (s_first > 0 ? s_first : 0)) {                // block-uniform: every row lies past the item
         if (a.zero_tail && ct < a.n_ct) {

@@ -326,6 +326,17 @@ DENOISER_SYMBOLS = {
     "iris_denoiser_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _f, _vp, _vp, _u64, _vp]),
 }
 
+# the time stretch (iris.time_stretch): bound by load() like SYMBOLS; it takes the mel front-end's config and a double rate
+TIME_STRETCH_SYMBOLS = {
+    "iris_time_stretch_out_samples": (_i32, [_mfc, _i32, _d, _ip, _ip]),
+    "iris_time_stretch_workspace_bytes": (_i32, [_mfc, _i32, _i32, _d, _u64p]),
+    "iris_time_stretch_launch_count": (_i32, [_mfc, _i32, _i32, _d, _ip]),
+    "iris_time_stretch_create": (_i32, [_mfc, _c.POINTER(_vp)]),
+    "iris_time_stretch_destroy": (_i32, [_vp]),
+    "iris_time_stretch_forward": (_i32, [_vp, _vp, _i32, _i32, _d, _vp, _vp, _u64, _vp]),
+    "iris_time_stretch_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _d, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -352,7 +363,7 @@ def load() -> ctypes.CDLL:
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
-                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS}.items():
+                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -56,14 +56,24 @@ class MelToWavePipeline:
     its chunk does, on top of ``hv + hp`` -- a chunk shorter than the halo yields nothing until a later chunk covers it.
     ``infer``, ``infer_batch`` and the ragged routes go through ``forward_device`` as before.  Such a denoiser needs fp32: a
     pipeline built on ``forward_pcm16`` refuses it (``ValueError``), and so does a stream handed an integer chunk; a
-    whole-utterance vocoder stays refused."""
+    whole-utterance vocoder stays refused.
+
+    ``stretch``: what ``iris.time_stretch.TimeStretch.at(rate)`` returns (or any object with ``hop_length``, ``out_samples(L)``
+    and ``forward_device(wav [B, L], lengths=) -> (out [B, n_out], counts [B])``), or None.  With one, ``infer``, ``infer_batch``
+    and every ``infer_from_*`` / ``resynthesize*`` route take the fp32 waveform -- the denoiser's, where there is one --
+    through the phase vocoder and run the output stage afterwards as stand-alone launches, as for a denoiser; an item then
+    has ``out_samples(hop * T_i)`` samples, and the ragged routes hand the stretch's ``counts`` on as sample lengths
+    (``row_scale=1``).  The waveform must be whole frames of the stretch's own ``hop_length`` (``ValueError`` otherwise).
+    ``stream`` and ``session`` raise ``ValueError``: the phase accumulator is a running state and no chunked form is built.
+    With ``stretch=None`` nothing changes."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
                  group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None,
-                 denoiser=None):
+                 denoiser=None, stretch=None):
         self.postnet = postnet
         self.denoiser = denoiser
+        self.stretch = stretch
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
@@ -128,6 +138,9 @@ class MelToWavePipeline:
         return chunk.float()
 
     def _refuse_chunked_denoiser(self) -> None:
+        if self.stretch is not None:
+            raise ValueError("a pipeline with a time stretch cannot be streamed: the phase accumulator runs through the whole "
+                             "utterance, and no chunked stretch is built; use infer / infer_batch")
         if self.denoiser is not None and not self._chunked_denoiser:
             raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
                              "either side, and no chunked denoiser is built; use infer / infer_batch")
@@ -160,10 +173,26 @@ class MelToWavePipeline:
         wav = wav.float()
         return self.denoiser.forward_device(wav) if lengths is None else self.denoiser.forward_device(wav, lengths=lengths)
 
-    def _ragged_output_stage(self, wav: torch.Tensor, rows: Sequence[int], pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
-        """The output stage over a batch whose item i owns ``hop * rows[i]`` samples and is 0 behind them, cut per item."""
-        hop = self.streamer.hop_length
-        samples = [hop * r for r in rows]
+    def _stretch_ragged(self, wav: torch.Tensor, rows: Sequence[int], pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
+        """A batch whose item i owns ``hop * rows[i]`` samples through ONE ragged stretch, then the output stage with the
+        stretch's ``counts`` as sample lengths.  The host knows the counts from ``out_samples``: nothing synchronises."""
+        hop, sh = self.streamer.hop_length, int(self.stretch.hop_length)
+        for i, r in enumerate(rows):
+            if hop * r % sh:
+                raise ValueError(f"item {i}: {hop * r} samples are not whole frames of the stretch's hop_length = {sh}; nothing is padded silently")
+        if wav.shape[1] % sh:                                        # the padded row itself; its tail belongs to no item
+            wav = torch.nn.functional.pad(wav, (0, sh - wav.shape[1] % sh))
+        out, counts = self.stretch.forward_device(wav, lengths=[hop * r // sh for r in rows])
+        return self._ragged_output_stage(out, counts, pcm16, normalize, resampler, hop=1,
+                                         samples=[self.stretch.out_samples(hop * r) for r in rows])
+
+    def _ragged_output_stage(self, wav: torch.Tensor, rows, pcm16: bool, normalize: bool, resampler, hop: Optional[int] = None,
+                             samples: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """The output stage over a batch whose item i owns ``hop * rows[i]`` samples and is 0 behind them, cut per item.
+        ``hop``: the vocoder's, unless the caller's rows are in another unit; ``samples``: the items' counts on the host where
+        ``rows`` is a device tensor."""
+        hop = self.streamer.hop_length if hop is None else hop
+        samples = [hop * r for r in rows] if samples is None else list(samples)
         if resampler is not None:
             out = resampler.forward(wav, lengths=rows, row_scale=hop, pcm16=pcm16, normalize=normalize)
             samples = [resampler.out_range(0, n)[1] for n in samples]
@@ -200,10 +229,14 @@ class MelToWavePipeline:
         result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
-        if self.denoiser is not None:
+        if self.denoiser is not None or self.stretch is not None:
             mel = self.refine(mel)
             wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
-            return self._output_stage(self._denoise(wav), pcm16, normalize, resampler)
+            if self.denoiser is not None:
+                wav = self._denoise(wav)
+            if self.stretch is not None:
+                wav = self.stretch.forward_device(wav.float())[0]
+            return self._output_stage(wav, pcm16, normalize, resampler)
         if self._whole is not None:
             return self._vocode_whole(self.refine(mel), pcm16, normalize, resampler)
         if resampler is not None:
@@ -448,7 +481,7 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        if self.denoiser is not None:
+        if self.denoiser is not None or self.stretch is not None:
             frames = [int(t) for t in lengths]
             if ragged_whole:
                 rows = [max(t - 1, 0) for t in frames]
@@ -459,7 +492,11 @@ class MelToWavePipeline:
             else:
                 rows = frames
                 wav = self.streamer.forward(padded, lengths=lengths)
-            return self._ragged_output_stage(self._denoise(wav, rows), rows, pcm16, normalize, resampler)
+            if self.denoiser is not None:
+                wav = self._denoise(wav, rows)
+            if self.stretch is not None:
+                return self._stretch_ragged(wav.float(), rows, pcm16, normalize, resampler)
+            return self._ragged_output_stage(wav, rows, pcm16, normalize, resampler)
         if ragged_whole:
             return self._vocode_whole_ragged(padded, lengths, pcm16, normalize, resampler)
         if self._whole is not None:

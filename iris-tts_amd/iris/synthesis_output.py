@@ -117,6 +117,50 @@ def check_resample_to(hz) -> int:
     return int(hz)
 
 
+TEMPO_RANGE = (0.25, 4.0)              # what the device time stretch admits (include/iris_hifigan.h)
+PITCH_STEPS_RANGE = (-12.0, 12.0)       # semitones: the stretch behind a shift stays inside TEMPO_RANGE with room to spare
+
+
+def check_tempo(rate) -> float:
+    """``--tempo``: a finite rate inside ``TEMPO_RANGE`` (above 1 is faster)."""
+    r = float(rate)
+    if not TEMPO_RANGE[0] <= r <= TEMPO_RANGE[1]:             # False for NaN too
+        raise ValueError(f"tempo must be a rate in [{TEMPO_RANGE[0]}, {TEMPO_RANGE[1]}], got {rate}")
+    return r
+
+
+def check_pitch_steps(n_steps) -> float:
+    """``--pitch_steps``: semitones inside ``PITCH_STEPS_RANGE`` (fractions are fine)."""
+    n = float(n_steps)
+    if not PITCH_STEPS_RANGE[0] <= n <= PITCH_STEPS_RANGE[1]:
+        raise ValueError(f"pitch_steps must lie in [{PITCH_STEPS_RANGE[0]:g}, {PITCH_STEPS_RANGE[1]:g}] semitones, got {n_steps}")
+    return n
+
+
+def tempo_and_pitch(audio: np.ndarray, tempo: Optional[float] = None, pitch_steps: Optional[float] = None, n_fft: int = 1024,
+                    hop_length: int = 256) -> np.ndarray:
+    """A float waveform ``[n]`` through the device phase vocoder (``iris.time_stretch``): first the pitch, at its own length,
+    then the tempo, to ``round(n / tempo)`` samples.  The stretch takes whole frames, so the waveform is zero-padded to a
+    multiple of ``hop_length`` on the way in and the result is cut to the length ``n`` asks for."""
+    import torch
+
+    from .time_stretch import TimeStretch, pitch_shift_device
+    audio = to_mono_float32(audio)
+    n = len(audio)
+    if n == 0 or (tempo is None and pitch_steps is None):
+        return audio
+    ts = TimeStretch(n_fft, hop_length)
+    wav = torch.from_numpy(np.pad(audio, (0, -n % hop_length))[None])
+    if pitch_steps is not None:
+        wav = pitch_shift_device(ts, wav, check_pitch_steps(pitch_steps))
+        wav[:, n:] = 0
+    if tempo is not None:
+        out = ts.forward_device(wav, check_tempo(tempo))[0][0, :int(round(n / float(tempo)))]
+    else:
+        out = wav[0, :n]
+    return out.cpu().numpy()
+
+
 def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 22050) -> Path:
     """Writes a mono WAV.  Float samples: ``soundfile`` is used when importable (the reference's writer,
     ``synthesize.py:211-213``); otherwise the standard-library ``wave`` module writes 16-bit PCM
@@ -160,7 +204,7 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
                   sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None,
-                  resample_to: Optional[int] = None) -> np.ndarray:
+                  resample_to: Optional[int] = None, tempo: Optional[float] = None, pitch_steps: Optional[float] = None) -> np.ndarray:
     """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
     int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
     ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
@@ -168,8 +212,16 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
     normalised on the host (``pcm16_from_float``).
     ``resample_to``: the entry is called with ``sample_rate_out=`` (``infer_hifigan`` / ``infer_hifigan_pcm16`` then convert
     the generator's 22 050 Hz on the GPU, ``iris.resample``) and the WAV header carries that rate; ``sample_rate`` keeps
-    labelling only, as in the reference."""
+    labelling only, as in the reference.
+    ``tempo`` / ``pitch_steps``: the entry's float waveform goes through ``tempo_and_pitch`` (the device phase vocoder) before
+    it is normalised and written; an entry that returns 16-bit PCM is refused (``ValueError``), the stage takes fp32."""
+    if tempo is not None:
+        check_tempo(tempo)
+    if pitch_steps is not None:
+        check_pitch_steps(pitch_steps)
     fn = resolve_vocoder_entry(vocoder_entry)
+    if (tempo is not None or pitch_steps is not None) and getattr(fn, "returns_pcm16", False):
+        raise ValueError("tempo / pitch_steps take the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
     if normalize_peak is not None:
@@ -190,6 +242,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
             raise ValueError(f"expected a single waveform after squeeze, got shape {audio.shape}")
     else:
         audio = to_mono_float32(audio)
+        if tempo is not None or pitch_steps is not None:
+            audio = tempo_and_pitch(audio, tempo, pitch_steps, hop_length=hop_length)
         if normalize_peak is not None:
             audio = pcm16_from_float(audio, normalize=True, peak_target=normalize_peak)
     logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / wav_rate:.2f}s")
@@ -212,6 +266,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--resample_to", type=int, default=None, metavar="HZ",
                         help="convert the generator's 22050 Hz waveform to HZ on the GPU (8000, 16000, 44100, 48000, ...); the "
                              "WAV header then carries HZ (--sample_rate keeps labelling only)")
+    parser.add_argument("--tempo", type=float, default=None, metavar="RATE",
+                        help="play RATE times as fast at the same pitch (0.25 .. 4; the device phase vocoder, iris.time_stretch)")
+    parser.add_argument("--pitch_steps", type=float, default=None, metavar="N",
+                        help="shift the pitch by N semitones at the same length (-12 .. 12, fractions allowed)")
     return parser
 
 
@@ -225,12 +283,20 @@ def main(argv: Optional[list] = None) -> int:
             check_resample_to(args.resample_to)
         except ValueError as exc:
             parser.error(f"--{exc}")
+    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps)):
+        if getattr(args, name) is not None:
+            try:
+                check(getattr(args, name))
+            except ValueError as exc:
+                parser.error(f"--{exc}")
+            if args.pcm16:
+                parser.error(f"--{name} takes the float waveform: it does not go with --pcm16")
     if args.pcm16 and args.vocoder_entry == DEFAULT_VOCODER_ENTRY:
         args.vocoder_entry = PCM16_VOCODER_ENTRY
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
     vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak,
-                  args.resample_to)
+                  args.resample_to, args.tempo, args.pitch_steps)
     return 0
 
 
