@@ -73,8 +73,54 @@ a device test may leave out only elements whose float64 re^2 + im^2 is below ``D
 disagrees, at most ``DN_TINY_SHARE`` of a call's stored elements and none of a silence case
 (tests/test_oracle_denoiser_chain.py bounds their share on the CPU).
 
-``MUTATIONS`` are wrong restatements; tests/test_oracle_dsp_chain.py and tests/test_oracle_denoiser_chain.py show that each
-fails against the right one.
+The time stretch (csrc/time_stretch.h, ``iris_time_stretch_*``) is four launches, judged with these:
+
+    ``ts_counts``         Spectrum::item: T_b = item_frames at extra = 1, T_out_b = ceil(T_b / rate) and n_out_b = rint(hop (T_b - 1)
+                          / rate) of float64 quotients (half to even); T_b = 0 gives 0, 0.
+    ``spectrum_launch``   Spectrum::bins4: ``window_acc`` at y_org = 0 stored as it is -- Re and Im = -sine interleaved, Im of bin 0
+                          as 0.f, column n_fft the Nyquist value from the sine column of bin 0 with 0.f behind it.  Exact.
+    ``step_launch``       ts_step_kernel.  alpha = (float)(t rate - floor(t rate)) with the product in double; a row i >= T_b and a
+                          row i + 1 >= T_b read as 0; mag = fmaf(alpha, sqrtf(re1 re1 + im1 im1), (1 - alpha) sqrtf(re0 re0 + im0 im0))
+                          with every product and sum rounded on its own (``#pragma clang fp contract(off)``): EXACT, with no
+                          contraction search -- the fused forms are mutations.  Padding bins hold +0 and 0u.  inc: see below.
+    ``scan_launch``       ts_scan_kernel.  acc is the exclusive scan of the launch's own inc from its own acc[0], modulo 2^32, in
+                          the block's two-level form (``time_stretch_restatement.scan_fixed``): exact.  out_c on the launch's own
+                          mag and acc: x = 2 (float)(int32) acc 2^-32 is exact, so the wanted value is mag (cospi x, sinpi x) in
+                          float64; columns 2 K .. Qp hold the padding bins' 0 (1, 0).
+    ``istft_launch``      with ``sample_count``: the ``sample_counts`` branch of gl_istft_kernel -- T_b = lengths[b] clamped to
+                          [0, T] with no item_frames rule, Ly_b = sample_count clamped to [0, Ly], samples at or past Ly_b stored
+                          as 0.f, wss over the frames that exist; samples past hop (T_b - 1) + n_fft / 2 have no frame: their
+                          chains and wss are 0 and so are they.  Exact.
+
+Derived bars of the time stretch (u32(v) = the distance from fp32(|v|) to the next fp32 value, 0 at v = 0; every term from the
+float64 values, none from the device's; first order):
+
+* ``TS_ATAN2_ULP`` = 4: HIP's table of math-function errors is not at hand where this was written, so atan2f is allowed the
+  4 ulp that tests/test_gpu_time_stretch.py already grants it.  ``TS_SINCOSPI_ULP`` = 2: twice one ulp, the allowance
+  oracle/text_chain_cases.py makes for expf and log1pf (HIP documents one ulp for those; the same is assumed of sincospif).
+* turns(c) = atan2f(im, re) * fl32(1 / (2 pi)): with theta = atan2(im, re) in float64 and c32 the fp32 constant,
+      e_turn(theta) = TS_ATAN2_ULP u32(theta) / (2 pi) + |theta| |c32 - 1 / (2 pi)| + u32(theta c32) / 2       [turns]
+  -- the function's error, the constant's own, the product's rounding.
+* inc, in units of 2^-32 turn, compared as a wrapped signed difference modulo 2^32.  Wanted: adv_fixed_k + 2^32 (tau1 - tau0 -
+  adv32_k) in float64, tau = theta / (2 pi), adv32 = the fp32 quotient (float) r / (float) n_fft the header names.  Bar:
+      2^32 (e_turn(theta1) + e_turn(theta0) + u32(tau1 - tau0) / 2 + u32(tau1 - tau0 - adv32) / 2) + 1 / 2
+  -- two angles, the two fp32 subtractions, llrintf.  ``wrap`` adds nothing: x - rintf(x) is exact for |x| <= 2 (the result is
+  a multiple of ulp(x) no larger than 1 / 2), the product by 2^32 is exact, and fixed(x) == fixed(wrap(x)) modulo 2^32, so the
+  comparison is continuous across the rintf and a restatement without ``wrap`` is the SAME restatement (shown on the CPU; it is
+  not a mutation).  Where both angles are exactly 0 (atan2f(0, x >= 0) = 0: digital silence, bins 0 and n_fft / 2 with Re > 0)
+  nothing rounds -- 0 - 0, 0 - adv32 and 2^32 adv32 (adv32 >= 2^-9 or 0) are exact -- and the bar is 0.  That is where a one-unit
+  error of advance_fixed shows; it can only at a config whose n_fft / hop is no power of two (``three_tap``): (k hop mod n_fft)
+  / n_fft = (k mod taps) / taps is dyadic otherwise, at odd_hop too, and both of the header's forms of the advance are exact.
+* acc[0]: wanted 2^32 tau(c[0, k]), bar 2^32 e_turn(theta) + 1 / 2, 0 where theta is 0; padding bins hold 0u.
+* out_c: |got - mag trig| <= TS_SINCOSPI_ULP |mag| u32(trig) + u32(mag trig) / 2 + 2^-126 per element, trig = cospi x or sinpi x.
+  For digital silence (mag == 0) that is 2^-126 against a wanted 0: 0 by value.
+tests/test_oracle_time_stretch_chain.py asserts that the largest inc / acc[0] bar stays below 2^19 units -- half the smallest
+nonzero difference between two bins' advances, 2^32 / n_fft with n_fft <= 4096 -- and the out_c bar below
+(TS_SINCOSPI_ULP + 1) 2^-23 |mag| + 2^-126.  The exact claim on mag covers subnormal squares; a device test may leave out only
+elements whose float64 re^2 + im^2 of either source row is below ``DN_TINY``, by the denoiser's rule.
+
+``MUTATIONS`` are wrong restatements; tests/test_oracle_dsp_chain.py, tests/test_oracle_denoiser_chain.py and
+tests/test_oracle_time_stretch_chain.py show that each fails against the right one.
 """
 import numpy as np
 
@@ -124,7 +170,11 @@ MUTATIONS = ("taps_descending", "istft_one_chain", "stft_one_chain", "mel_partia
              # the bias denoiser
              "dn_fma_unfused", "dn_scale_unguarded", "dn_divide_last", "dn_im_sign", "dn_nyquist_bias0", "dn_nyquist_im_kept",
              "dn_bias_sum_f32", "dn_bias_pairwise", "dn_interior_wide", "dn_mean_over_all_frames", "dn_frames_extra0",
-             "dn_window_origin_shift")
+             "dn_window_origin_shift",
+             # the time stretch
+             "ts_alpha_f32", "ts_lerp_fma_swapped", "ts_mag_fma_re", "ts_mag_fma_im", "ts_adv_no_modulo", "ts_adv_fixed_rounded",
+             "ts_fixed_truncated", "ts_scan_inclusive", "ts_start_phase_0", "ts_unfixed_u32", "ts_sin_cos_swapped", "ts_row_past_end_kept",
+             "ts_nyquist_im_kept", "ts_n_out_truncated", "ts_n_out_half_up", "ts_tail_dropped", "ts_istft_item_rule", "ts_sample_count_ignored")
 
 # ---- the bias denoiser's cases (csrc/denoiser.h) ------------------------------------------------------------------------------------
 # (config, B, M): M mel frames, L = hop M samples, T = M + 1 frames
@@ -143,6 +193,48 @@ DN_STRENGTH = 1.0                                 # with denoiser_cases.bias: bo
 DN_STRENGTHS = (DN_STRENGTH, 0.1, 0.0)            # 0.1 is the library's default
 DN_TINY = 2.0 ** -125                             # float64 re^2 + im^2 below this: the only elements a device test may leave out
 DN_TINY_SHARE = 1e-3                              # and at most this share of a case's stored elements
+
+# ---- the time stretch's cases (csrc/time_stretch.h) ----------------------------------------------------------------------------------
+# (config, B, M, rate): T = M + 1 frames, T_out = ceil(T / rate).  ts_step_kernel's 256-thread blocks hold 256 / G frames, G = Ks / 4
+# (9 at small, 13 at odd_hop, 33 at two_tap, 129 at default and wide_hop) -- never a whole number, so a block straddles a frame
+# boundary as soon as there is more than one; every config's last scan block has fewer than 32 live lanes (Ks % 32 is 4 or 20).
+# three_tap  n_fft / hop = 3 is no power of two: the advance (k mod 3) / 3 is an inexact fp32 quotient and advance_fixed a truncation.
+#            (odd_hop's n_fft is no power of two either, but its advance (k mod 8) / 8 is dyadic: both forms are exact there.)
+TS_CONFIGS = {**GL_CONFIGS, "three_tap": dict(sample_rate=8000, n_fft=96, hop_length=32, win_length=80, n_mels=6, fmin=0.0, fmax=None)}
+TS_SEMITONE_DOWN = 2.0 ** (-1.0 / 12.0)
+TS_CASES = (
+    ("default", 2, 32, 0.8),                # T_out 42: runs of 2 with empty trailing runs; n_out < hop (T_out - 1): the crop is live
+    ("default", 2, 39, 1.25),               # T_out exactly 32: 32 runs of 1; n_out > hop (T_out - 1): the zero tail is live
+    ("default", 1, 32, 1.0),                # T_out 33: runs of 2, the last of 1; rate 1
+    ("small", 1, 1, 4.0),                   # T 2, T_out 1: one frame is an item; 31 empty runs
+    ("small", 1, 69, TS_SEMITONE_DOWN),     # T_out 75: runs of 3 (several frames a run), a non-dyadic rate
+    ("small", 1, 16, 0.25),                 # the slow end: T_out 68; alpha in {0, 1/4, 1/2, 3/4}
+    ("small", 1, 69, 4.0),                  # the fast end: T_out 18, runs of 1 with empty trailing runs; alpha in {0, 1/2}
+    ("two_tap", 1, 33, 1.25),               # two taps; T_out 28
+    ("odd_hop", 1, 2, 1.0),                 # n_fft 96 is no power of two; fewer frames than taps
+    ("odd_hop", 1, 34, 0.8),                # T_out 44: hop % 8 != 0, Ks 52 against 49 bins: a group that straddles `bins`
+    ("odd_hop", 1, 34, 1.25),               # T_out 28
+    ("three_tap", 1, 34, 0.8),              # T_out 44: an inexact advance_turns, a truncated advance_fixed
+    ("three_tap", 1, 34, 1.25),             # T_out 28
+    ("wide_hop", 1, 2, 4.0),                # T_out 1 at two taps
+    ("wide_hop", 1, 33, TS_SEMITONE_DOWN),  # r in {0, 512}; blockIdx.z = 1 in the inverse; T_out 37
+)
+# (config, M, lengths in mel frames, rates): the full M, 0, 1, inside a block, T_b on a 32-frame block edge, one past it; NaN past
+# each item's samples; a rate below 1 and a rate above 1
+TS_RAGGED = (("small", 69, (69, 0, 1, 20, 31, 32), (0.8, 1.25)), ("odd_hop", 34, (34, 0, 1, 20, 31, 32), (0.8, 1.25)))
+# (config, rate): ``ts_silence`` at the config's largest M
+TS_SILENCE = (("default", 0.8), ("small", TS_SEMITONE_DOWN), ("two_tap", 1.25), ("odd_hop", 0.8), ("three_tap", 0.8), ("three_tap", 1.25),
+              ("wide_hop", 1.0))
+# (config, M, rate): ``ts_small_angles`` -- start phases of a few 1e-5 rad, where the bar of acc[0] is llrintf's own half unit and
+# 2^32 x is no whole number: the only place a truncating ``fixed`` can show
+TS_SMALL_ANGLES = ("small", 8, 1.0)
+# fl(L / rate) is exactly 4.5 (L = 16, rate = fl(32 / 9)): rint's half-to-even decides n_out = 4; T_out 1
+TS_HALF = ("small", 1, 1, 32.0 / 9.0)
+TS_ATAN2_ULP = 4.0                                # allowed of atan2f (the module docstring says where both figures come from)
+TS_SINCOSPI_ULP = 2.0                             # allowed of sincospif
+TS_UNIT = 4294967296.0                            # 2^32 units are one turn
+TS_INV_2PI32 = np.float32(0.15915494309189535)    # the constant of ts::turns
+TS_FLOOR = 2.0 ** -126
 
 
 def case_id(case) -> str:
@@ -204,7 +296,7 @@ _cache: dict = {}
 
 def gl_model(name, **kw):
     from iris.griffin_lim import GriffinLim
-    return GriffinLim(**GL_CONFIGS[name], momentum=MOMENTUM, nnls_iters=NNLS_ITERS, **kw)
+    return GriffinLim(**TS_CONFIGS[name], momentum=MOMENTUM, nnls_iters=NNLS_ITERS, **kw)
 
 
 def gl_tables(name):
@@ -435,17 +527,34 @@ def invert_launch(logmel, phase, Tb, cfg, tab, nnls_iters, fma, mut=None):
 
 
 # ---- gl_istft_kernel -------------------------------------------------------------------------------------------------------------
-def istft_launch(c, Tb, T, cfg, tab, zero_tail, mut=None):
+def istft_launch(c, Tb, T, cfg, tab, zero_tail, mut=None, sample_count=None, Ly=None):
     """``c [T, Qp]`` (or ``[.., Q]``; rows from Tb on are never read) -> ``(y [Ly], written [Ly])``: what the launch stores and
-    where."""
+    where.  ``sample_count`` (the time stretch's IstftLaunch::sample_counts): the item owns that many samples of the ``Ly`` the
+    launch stores (default hop (T - 1)) and ``Tb`` frames as they stand, one frame included."""
     d = Design(cfg)
     tab = mutate_tables(tab, cfg, mut)
     H, K = d.hop, d.taps
-    Ly, Lyb = H * (T - 1), (H * (Tb - 1) if Tb else 0)
+    if sample_count is None:
+        assert Ly is None
+        Ly, Lyb = H * (T - 1), (H * (Tb - 1) if Tb else 0)
+    else:
+        Tb = min(max(int(Tb), 0), T)
+        if mut == "ts_istft_item_rule" and Tb < 2:
+            Tb = 0
+        Ly = H * (T - 1) if Ly is None else int(Ly)
+        by_frames = H * (Tb - 1) if Tb else 0
+        Lyb = min(max(int(sample_count), 0), Ly)
+        if mut == "ts_sample_count_ignored":
+            Lyb = min(by_frames, Ly)
+        elif mut == "ts_tail_dropped":
+            Lyb = min(Lyb, by_frames)
     y, written = np.zeros(Ly, np.float32), np.zeros(Ly, bool)
     if zero_tail:
         written[Lyb:] = True
     if Lyb == 0:
+        return y, written
+    if Tb == 0:                                                  # no frame exists: every chain and every wss is 0
+        written[:Lyb] = True
         return y, written
     trim = d.half - H if mut == "trim_short" else d.half
     j = np.arange(trim // H, (trim + Lyb - 1) // H + 1)                            # padded rows that hold a surviving sample
@@ -543,7 +652,7 @@ def dn_waveform_item(n, cfg, seed):
 def dn_wave(name, B, M, seed=0):
     """``[B, hop M]`` float32, the caller's own copy: item b is ``dn_waveform_item(hop M, cfg, seed + b)``."""
     if ("dnwav", name, B, M, seed) not in _cache:
-        cfg = GL_CONFIGS[name]
+        cfg = TS_CONFIGS[name]
         _cache[("dnwav", name, B, M, seed)] = np.stack([dn_waveform_item(cfg["hop_length"] * M, cfg, seed + b) for b in range(B)])
     return _cache[("dnwav", name, B, M, seed)].copy()
 
@@ -553,11 +662,11 @@ def dn_case_m(name):
     return max(M for n, _, M in DN_CASES if n == name)
 
 
-def dn_silence(name):
-    """``[2, hop M]``: item 0 is digital silence; item 1 has its middle 2 n_fft samples at 0.0f -- whole frames with mag == 0
-    beside live ones, and frames that are partly silent."""
-    cfg = GL_CONFIGS[name]
-    w = dn_wave(name, 2, dn_case_m(name), seed=20)
+def dn_silence(name, M=None):
+    """``[2, hop M]`` (M: that of the config's largest denoiser case): item 0 is digital silence; item 1 has its middle 2 n_fft
+    samples at 0.0f -- whole frames with mag == 0 beside live ones, and frames that are partly silent."""
+    cfg = TS_CONFIGS[name]
+    w = dn_wave(name, 2, dn_case_m(name) if M is None else M, seed=20)
     w[0] = 0
     mid = w.shape[1] // 2
     w[1, mid - cfg["n_fft"]:mid + cfg["n_fft"]] = 0
@@ -732,6 +841,205 @@ def dn_estimate_np(wav, cfg, tab, fma, mut=None):
     T = len(wav) // d.hop + 1
     mag = magnitude_launch(window_acc(wav, 0, T, cfg, tab, mut), cfg, fma)
     return mag, bias_reduce(mag, *dn_interior(cfg, T, mut), mut)
+
+
+# ---- the time stretch: stft_kernel<ts::Spectrum>, ts_step_kernel, ts_scan_kernel, gl_istft_kernel with sample_counts ---------------
+def ts_case_id(case) -> str:
+    return f"{case[0]}-B{case[1]}-M{case[2]}-r{case[3]:.4g}"
+
+
+def ts_silence(name):
+    """``dn_silence`` with item 1's first n_fft samples at 0.0f as well: item 0 is digital silence, item 1 has silent frames in
+    front (its start phase is fixed(turns(0, 0)) = 0) and in the middle, beside live ones."""
+    w = dn_silence(name, None if name in GL_CONFIGS else max(M for n, _, M, _ in TS_CASES if n == name))
+    w[1, :TS_CONFIGS[name]["n_fft"]] = 0
+    return w
+
+
+def ts_small_angles(name, M):
+    """``[1, hop M]``: the case waveform with its first n_fft / 2 samples -- all that frame 0 sees -- replaced by 0.5 at sample 0
+    and 0.5e-4 at sample 1.  Sample 0 sits on the window's peak, so c[0, k] = (-1)^k (0.5 + 0.5e-4 w_1 e^(-2 pi i k / n_fft)): an
+    angle of about -1e-4 sin(2 pi k / n_fft) rad in every even bin."""
+    w = dn_wave(name, 1, M, seed=21)
+    w[0, :TS_CONFIGS[name]["n_fft"] // 2] = 0
+    w[0, 0], w[0, 1] = 0.5, 0.5e-4
+    return w
+
+
+def ts_counts(m, T, hop, rate, mut=None):
+    """``Spectrum::item``: ``m`` an item's MEL frames (None: a dense call of T frames) -> ``(T_b, T_out_b, n_out_b)``."""
+    Tb = dn_item_frames(m, T)
+    q = np.float64(hop * (Tb - 1) if Tb else 0) / np.float64(rate)
+    n = int({"ts_n_out_truncated": np.trunc(q), "ts_n_out_half_up": np.floor(q + 0.5)}.get(mut, np.rint(q)))
+    return Tb, (int(np.ceil(np.float64(Tb) / np.float64(rate))) if Tb > 0 else 0), n
+
+
+def spectrum_launch(acc, cfg, mut=None):
+    """``acc`` of ``window_acc`` at y_org = 0 -> ``c [Tb, Q]`` exactly as ``Spectrum::bins4`` stores it."""
+    d = Design(cfg)
+    re, im, nyq = dn_parts(acc, d)
+    c = np.zeros((acc.shape[0], d.q), np.float32)
+    c[:, 0:2 * d.half:2], c[:, 1:2 * d.half:2], c[:, 2 * d.half] = re, im, nyq
+    if mut == "ts_nyquist_im_kept":                              # the sine column that carried the value, stored like an Im
+        c[:, 2 * d.half + 1] = -nyq
+    return c
+
+
+def u32(v):
+    """The distance from fp32(|v|) to the next fp32 value above it, as float64; 0 where v is 0."""
+    v = np.abs(np.asarray(v, dtype=np.float64))
+    return np.where(v == 0, 0.0, np.spacing(v.astype(np.float32)).astype(np.float64))
+
+
+def ts_turn_bar(theta):
+    """``e_turn`` of the module docstring: the error allowed of ``ts::turns`` at the float64 angle ``theta``, in turns."""
+    inv = 1.0 / (2.0 * np.pi)
+    return TS_ATAN2_ULP * u32(theta) * inv + np.abs(theta) * abs(float(TS_INV_2PI32) - inv) + 0.5 * u32(theta * float(TS_INV_2PI32))
+
+
+def ts_unit_diff(got, want):
+    """``got`` (uint32 values as int64) minus ``want`` (float64 units), as the wrapped signed difference modulo 2^32."""
+    diff = np.asarray(got, dtype=np.float64) - np.asarray(want, dtype=np.float64)
+    return diff - TS_UNIT * np.rint(diff / TS_UNIT)
+
+
+def ts_fixed(x32, mut=None):
+    """``ts::fixed``: fp32 turns -> uint32 units held in int64; the product by 2^32 is exact."""
+    assert x32.dtype == np.float32
+    v = x32.astype(np.float64) * TS_UNIT
+    return (np.trunc(v) if mut == "ts_fixed_truncated" else np.rint(v)).astype(np.int64) & 0xFFFFFFFF
+
+
+def ts_advance(d, mut=None):
+    """``(advance_fixed [bins] int64, advance_turns [bins] fp32)`` of ``ts::advance_fixed`` / ``ts::advance_turns``."""
+    r = np.arange(d.bins, dtype=np.int64) * d.hop
+    if mut != "ts_adv_no_modulo":
+        r = r % d.n_fft
+    fx = ((((r << 33) // d.n_fft) + 1) >> 1) if mut == "ts_adv_fixed_rounded" else (r << 32) // d.n_fft
+    return fx & 0xFFFFFFFF, r.astype(np.float32) / np.float32(d.n_fft)
+
+
+def ts_rows(c, Tb, To, rate, d, mut=None):
+    """``(alpha [To] fp32, re0, im0, re1, im1 [To, bins] fp32, exists [2, To])``: the two source rows of every output frame; a row
+    >= Tb is 0 and does not exist."""
+    t = np.arange(To)
+    if mut == "ts_alpha_f32":
+        step = t.astype(np.float32) * np.float32(rate)
+    else:
+        step = t.astype(np.float64) * np.float64(rate)
+    fl = np.floor(step)
+    i, alpha = fl.astype(np.int64), (step - fl).astype(np.float32)
+    rows = np.zeros((Tb + 2, 2 * d.bins), np.float32)
+    rows[:Tb] = np.asarray(c, dtype=np.float32)[:Tb, :2 * d.bins]
+    if mut == "ts_row_past_end_kept" and Tb:
+        rows[Tb] = rows[Tb - 1]
+    i = np.minimum(i, Tb)
+    r0, r1 = rows[i], rows[i + 1]
+    return alpha, r0[:, 0::2], r0[:, 1::2], r1[:, 0::2], r1[:, 1::2], np.stack([i < Tb, i + 1 < Tb])
+
+
+def step_launch(c, Tb, To, rate, cfg, mut=None):
+    """``c [.., Qp]`` (or ``[.., Q]``; only rows below Tb and columns below 2 bins are read) -> a dict:
+    ``mag [To, Ks]`` fp32, exact; ``inc_want``, ``inc_bar`` ``[To, Ks]`` float64 in units of 2^-32 turn (the module docstring
+    derives the bar; padding bins want 0 within 0); ``tiny [To, Ks]``: float64 re^2 + im^2 of either source row that exists below DN_TINY;
+    ``inc [To, Ks]`` int64: the header's line in fp32 with numpy's arctan2, for chaining on the CPU."""
+    d = Design(cfg)
+    alpha, re0, im0, re1, im1, exists = ts_rows(c, Tb, To, rate, d, mut)
+    a = np.broadcast_to(alpha[:, None], re0.shape)
+    m0 = np.sqrt(sum_sq(re0, im0, {"ts_mag_fma_re": 1, "ts_mag_fma_im": 2}.get(mut, 0)))
+    m1 = np.sqrt(sum_sq(re1, im1, {"ts_mag_fma_re": 1, "ts_mag_fma_im": 2}.get(mut, 0)))
+    if mut == "ts_lerp_fma_swapped":                             # (1 - alpha) m0 fused, alpha m1 rounded
+        mag = co.fmaf32(np.float32(1) - a, m0, a * m1)
+    else:
+        mag = co.fmaf32(a, m1, (np.float32(1) - a) * m0)
+    adv_fixed, adv32 = ts_advance(d, mut)
+    # the wanted increment and its bar, from float64
+    th0, th1 = np.arctan2(im0.astype(np.float64), re0.astype(np.float64)), np.arctan2(im1.astype(np.float64), re1.astype(np.float64))
+    inv = 1.0 / (2.0 * np.pi)
+    d1 = th1 * inv - th0 * inv
+    d2 = d1 - adv32.astype(np.float64)[None, :]
+    want = adv_fixed[None, :].astype(np.float64) + TS_UNIT * d2
+    bar = TS_UNIT * (ts_turn_bar(th1) + ts_turn_bar(th0) + 0.5 * u32(d1) + 0.5 * u32(d2)) + 0.5
+    bar = np.where((th0 == 0) & (th1 == 0), 0.0, bar)
+    # the same line in fp32
+    t0, t1 = np.arctan2(im0, re0) * TS_INV_2PI32, np.arctan2(im1, re1) * TS_INV_2PI32
+    dphi = t1 - t0 - adv32[None, :]
+    if mut != "ts_no_wrap":                                      # an equivalent form, not a mutation
+        dphi = dphi - np.rint(dphi)
+    assert dphi.dtype == np.float32
+    inc = (adv_fixed[None, :] + ts_fixed(dphi, mut)) & 0xFFFFFFFF
+    sq0 = re0.astype(np.float64) ** 2 + im0.astype(np.float64) ** 2
+    sq1 = re1.astype(np.float64) ** 2 + im1.astype(np.float64) ** 2
+    pad = lambda v, dt: np.concatenate([v.astype(dt), np.zeros((To, d.ks - d.bins), dt)], axis=1)
+    return {"mag": pad(mag, np.float32), "inc_want": pad(want, np.float64), "inc_bar": pad(bar, np.float64), "inc": pad(inc, np.int64),
+            "tiny": pad(((sq0 < DN_TINY) & exists[0][:, None]) | ((sq1 < DN_TINY) & exists[1][:, None]), bool), "alpha": alpha}
+
+
+def ts_sincospi(x):
+    """``(cospi x, sinpi x)`` in float64 for fp32 ``x`` in [-1, 1], the argument reduced exactly first."""
+    x = np.asarray(x, dtype=np.float64)
+    n = np.rint(x)
+    r = x - n                                                    # exact, [-1/2, 1/2]
+    sgn = 1.0 - 2.0 * np.mod(n, 2.0)
+    cos = np.where(np.abs(r) > 0.25, np.sin(np.pi * (0.5 - np.abs(r))), np.cos(np.pi * r))
+    return sgn * cos, sgn * np.sin(np.pi * r)
+
+
+def scan_launch(c_row0, mag, inc, To, cfg, acc0=None, mut=None):
+    """``c_row0 [>= Q]``: row 0 of the item's spectrum; ``mag [To, Ks]`` fp32 and ``inc [To, Ks]`` (uint32 values as int64): the
+    launch's own inputs; ``acc0 [Ks]``: the launch's own acc[0] (None: the fp32 line with numpy's arctan2) -> a dict:
+    ``acc0_want``, ``acc0_bar`` ``[Ks]`` float64 units; ``acc [To, Ks]`` int64, exact from ``inc`` and ``acc0``;
+    ``out_want``, ``out_bar`` ``[To, Qp]`` float64: mag (cospi x, sinpi x) on ``mag`` and ``acc``, interleaved, and its bar;
+    ``out_c [To, Qp]`` fp32: ``out_want`` rounded, for chaining on the CPU."""
+    import time_stretch_restatement as R
+    d = Design(cfg)
+    row = np.asarray(c_row0, dtype=np.float32)[:2 * d.bins]
+    re, im = row[0::2], row[1::2]
+    th = np.arctan2(im.astype(np.float64), re.astype(np.float64))
+    pad = lambda v, dt: np.concatenate([v.astype(dt), np.zeros(d.ks - d.bins, dt)])
+    want0 = pad(TS_UNIT * th / (2.0 * np.pi), np.float64)
+    bar0 = pad(np.where(th == 0, 0.0, TS_UNIT * ts_turn_bar(th) + 0.5), np.float64)
+    if acc0 is None:
+        acc0 = pad(np.zeros(d.bins, np.int64) if mut == "ts_start_phase_0" else ts_fixed(np.arctan2(im, re) * TS_INV_2PI32, mut), np.int64)
+    acc0 = np.asarray(acc0, dtype=np.int64)
+    inc = np.asarray(inc, dtype=np.int64)[:To]
+    if mut == "ts_scan_inclusive":
+        acc = (acc0[None, :] + np.cumsum(inc, axis=0)) & R.MASK
+    else:
+        acc = R.scan_fixed(acc0, inc)
+    if mut == "ts_unfixed_u32":
+        x = np.float32(2) * (acc.astype(np.float32) * np.float32(2.0 ** -32))
+    else:
+        x = np.float32(2) * R.unfixed(acc)
+    assert x.dtype == np.float32
+    cos, sin = ts_sincospi(x)
+    if mut == "ts_sin_cos_swapped":
+        cos, sin = sin, cos
+    m = np.asarray(mag, dtype=np.float32)[:To].astype(np.float64)
+    want, bar = np.empty((To, d.qp)), np.empty((To, d.qp))
+    for o, trig in ((0, cos), (1, sin)):
+        want[:, o::2] = m * trig
+        bar[:, o::2] = TS_SINCOSPI_ULP * np.abs(m) * u32(trig) + 0.5 * u32(m * trig) + TS_FLOOR
+    return {"acc0_want": want0, "acc0_bar": bar0, "acc0": acc0, "acc": acc, "out_want": want, "out_bar": bar, "out_c": want.astype(np.float32)}
+
+
+def ts_forward_np(wav, m, rate, cfg, tab, mut=None):
+    """One item through ``ts_forward``: ``wav [L]``, ``m`` its mel frames or None -> ``{"counts", "acc", "c", "step", "scan", "out"}``;
+    ``out [rint(L / rate)]`` is laid out by the dense call as the device's row is."""
+    d = Design(cfg)
+    L = len(wav)
+    T = L // d.hop + 1
+    _, T_out, n_out = ts_counts(None, T, d.hop, rate, mut)
+    Tb, To, n = ts_counts(m, T, d.hop, rate, mut)
+    out = {"counts": (Tb, To, n), "acc": None, "c": np.zeros((0, d.q), np.float32)}
+    if Tb:
+        out["acc"] = window_acc(np.asarray(wav)[:d.hop * (Tb - 1)], 0, Tb, cfg, tab, mut)
+        out["c"] = spectrum_launch(out["acc"], cfg, mut)
+    out["step"] = step_launch(out["c"], Tb, To, rate, cfg, mut)
+    out["scan"] = scan_launch(out["c"][0] if Tb else np.zeros(d.q, np.float32), out["step"]["mag"], out["step"]["inc"], To, cfg, mut=mut)
+    out["out"], written = istft_launch(out["scan"]["out_c"], To, T_out, cfg, tab, True, mut, sample_count=n, Ly=n_out)
+    assert written.all()
+    return out
 
 
 # ---- a forward on the CPU (the restatements fed with their own outputs) -------------------------------------------------------------

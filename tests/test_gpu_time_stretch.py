@@ -9,6 +9,10 @@ stay within ``4 * e32`` (another summation order, another atan2f).  ``out`` is t
 the float64 step on the ``c`` it stored itself.  The bars are measured when first asked for (they depend on the host BLAS's
 summation order); on the CPU e32 was 5.571e-05 for the waveform (bar 2.23e-04) -- the phases of near-empty bins, which the
 spectrum's own rounding moves, are in it -- 1.150e-07 for ``mag`` (bar 4.60e-07) and 1.370e-06 for ``out_c`` (bar 5.48e-06).
+
+These bars are relative to an array's maximum and say nothing of a quiet bin.  The per-launch claims -- each launch on its own
+input, ``==`` wherever the source fixes every rounding, ``inc``, ``acc[0]`` and ``out_c`` element by element to derived bars,
+the rows and columns that must stay unwritten -- are tests/test_gpu_time_stretch_chain.py's.
 """
 import sys
 from fractions import Fraction

@@ -211,7 +211,9 @@ PAIRS = [p for p in PAIRS if p not in INVISIBLE]
 def test_every_mutation_is_tried_somewhere():
     from test_oracle_denoiser_chain import DN_PAIRS                # the bias denoiser's wrong restatements are tried there
     assert all(m.startswith("dn_") for _, m in DN_PAIRS) and not any(m.startswith("dn_") for _, m in PAIRS)
-    assert {m for _, m in PAIRS} | {m for _, m in INVISIBLE} | {m for _, m in DN_PAIRS} == set(D.MUTATIONS)
+    from test_oracle_time_stretch_chain import TS_PAIRS           # and the time stretch's there
+    assert all(m.startswith("ts_") for _, m in TS_PAIRS) and not any(m.startswith("ts_") for _, m in PAIRS + DN_PAIRS)
+    assert {m for _, m in PAIRS} | {m for _, m in INVISIBLE} | {m for _, m in DN_PAIRS} | {m for _, m in TS_PAIRS} == set(D.MUTATIONS)
 
 
 def test_a_dropped_nyquist_column_is_invisible_in_the_log_mel_and_why():
