@@ -879,6 +879,45 @@ int32_t iris_time_stretch_forward_ragged(iris_time_stretch_handle* h, const floa
                                          int32_t* counts_out_dev /* [B] or NULL */, void* workspace_dev, uint64_t workspace_bytes,
                                          void* stream);
 
+/* Windows: the stretch on samples [origin, origin + Lw) of an utterance, for a caller that receives the waveform piece by piece.
+ * N = n_fft, H = hop_length, taps = N / H (>= 2 here), e = ceil(N / 2 / H).  origin = H m0, Lw = H Mw; `final` (0 or not) says that
+ * origin + Lw is the utterance's end -- only then are T, T_out and n_out known.  Input rows [f_lo, f_hi) are computable as for the
+ * denoiser's windows: f_lo = m0 ? m0 + e : 0, f_hi = final ? m0 + Mw + 1 : m0 + Mw - e + 1.  The caller carries one integer u, the
+ * next output frame (0 at the start), and the state.  Output frame t reads rows i and i + 1, i = floor((double)t * rate):
+ *     not final: t is computable iff i >= f_lo and i + 1 < f_hi;   final: iff t < T_out and i >= f_lo (rows >= T read as 0).
+ * The window computes frames [u, u_hi), the longest such run; floor(u rate) < f_lo is refused (samples were dropped too early).
+ * keep_from = H max(0, floor(u_hi rate) - e) is the first sample the next window must still hold.  Sample s lies in row
+ * j = floor((s + N / 2) / H) and is emitted by this window when each of frames j - taps + 1 .. j lies in [max(0, u - taps + 1),
+ * u_hi) or does not exist (negative, or -- only if final -- >= T_out), no earlier window emitted it (j >= u), and s < n_out
+ * (final; samples from min(n_out, H (T_out - 1) + N / 2) on are stored as 0.0f, the forward's tail rule) or s < rint((origin +
+ * Lw) / rate) (not final: the least n_out a continuation can have).  The emitted samples are one range, contiguous with the
+ * previous window's:
+ *     window_plan -> u_hi, out_lo (an index into the stretched utterance), out_count, keep_from.
+ * State (state_bytes; caller-owned, read and written in place by the scan's launch, never copied): acc [B][Ks] uint32, the phase
+ * at frame u_hi, then -- on the next 256 bytes -- tail [B][taps - 1][Qp], row q holding out_c of frame u_hi - (taps - 1) + q.
+ * Rows of negative frames, columns of acc from n_fft / 2 + 1 on and columns of tail from n_fft + 2 on are never read or
+ * written.  A state need not be initialised for u == 0; state_dev may be NULL only for a final window with u == 0.
+ * forward_window: wav_dev [B, Lw] -> out_dev [B, out_count], each sample bit for bit that of iris_time_stretch_forward on the whole
+ * utterance: the phase is an exact integer sum, a row's chain depends on its own n_fft samples and a sample's on its own taps
+ * frames, in a fixed order, whichever window they are computed in.  Dense only, one rate per utterance.  The forward's 4
+ * launches; 3 where frames advance but no sample is emitted yet; 2 (scan and inverse STFT) where a final window has samples
+ * left but no frame; none, and IRIS_HIFIGAN_OK, when B == 0 or u_hi == u and out_count == 0.  No copies, nothing allocated,
+ * asynchronous, safe in a stream capture.  After a window the workspace holds, in the window's own coordinates and each
+ * starting on 256 bytes at an offset that depends on (B, Lw, rate) alone: c [B][f_hi - f_lo][Qp], mag, inc, acc
+ * [B][u_hi - u][Ks] and out_c [B][n_tail + u_hi - u][Qp], n_tail = min(taps - 1, u), the carried rows first.
+ * Refusals are the forward's, and: origin or Lw negative or no multiple of hop_length, u < 0, u > 0 or a window that is not
+ * final without a state, floor(u rate) < f_lo -> IRIS_HIFIGAN_INVALID_ARGUMENT; origin above 2^60, u hop_length above 2^61,
+ * hop_length == n_fft -> IRIS_HIFIGAN_UNSUPPORTED.  No failing call launches. */
+int32_t iris_time_stretch_state_bytes(const iris_mel_frontend_config* cfg, int32_t B, uint64_t* bytes);
+int32_t iris_time_stretch_window_plan(const iris_mel_frontend_config* cfg, double rate, int64_t origin, int32_t Lw, int32_t final, int64_t u,
+                                      int64_t* u_hi, int64_t* out_lo, int64_t* out_count, int64_t* keep_from);
+int32_t iris_time_stretch_window_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, double rate, uint64_t* bytes);
+int32_t iris_time_stretch_window_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, double rate, int64_t origin,
+                                              int32_t final, int64_t u, int32_t* n);
+int32_t iris_time_stretch_forward_window(iris_time_stretch_handle* h, const float* wav_dev /* [B, Lw] */, int32_t B, int32_t Lw, int64_t origin,
+                                         int32_t final, double rate, int64_t u, void* state_dev, float* out_dev /* [B, out_count] */,
+                                         void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,9 @@
 // that stores the plain spectrum and the items' counts, the phase vocoder's step and scan, and the Griffin-Lim stage's
 // inverse STFT bounded by the items' sample counts.  The handle owns the packed windowed DFT, the packed windowed inverse DFT
 // and w^2; the rate is an argument of the forward.
+// forward_window is the same launches on a window of an utterance, with the phase and the last taps - 1 output frames carried
+// in a caller-owned state (ts::WindowPlan in csrc/time_stretch.h): a session that pushes consecutive windows reproduces the
+// whole-utterance forward bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -119,6 +122,111 @@ int ts_forward(const stft::Sizes& d, const TsTables& tb, const float* wav, int B
     return IRIS_HIFIGAN_OK;
 }
 
+// ---- windows -----------------------------------------------------------------------------------------------------------
+// The state: acc [B, Ks] (uint32), then tail [B, taps - 1, Qp], each starting on 256 bytes.
+struct TsState {
+    size_t acc, tail, floats;
+    TsState(const stft::Sizes& d, int B) {
+        WsTaker ws;
+        acc = ws.take((size_t)B * d.ks());
+        tail = ws.take((size_t)B * (d.taps() - 1) * d.qp());
+        floats = ws.off;
+    }
+};
+
+// The most output frames a window of Mw mel frames computes: its rows span at most Mw + 1 values of i(t), each of which at most
+// ceil(1 / rate) frames share, and one more frame may straddle the front.
+long long ts_window_frames(long long Mw, double rate) { return (long long)ceil((double)(Mw + 1) / rate) + 1; }
+
+// A window's buffers in the forward's order, sized by what any window of (B, Lw) at `rate` can hold, so that the layout does
+// not depend on u; each is dense in the rows the window has.
+struct TsWindowWorkspace {
+    size_t c, mag, inc, acc, out_c, floats;
+    TsWindowWorkspace(const stft::Sizes& d, int B, int Lw, double rate) {
+        const size_t F = (size_t)(Lw / d.hop + 1), n = (size_t)ts_window_frames(Lw / d.hop, rate);
+        WsTaker ws;
+        c = ws.take((size_t)B * F * d.qp());
+        mag = ws.take((size_t)B * n * d.ks());
+        inc = ws.take((size_t)B * n * d.ks());
+        acc = ws.take((size_t)B * n * d.ks());
+        out_c = ws.take((size_t)B * (n + d.taps() - 1) * d.qp());
+        floats = ws.off;
+    }
+};
+
+int ts_check_window(const stft::Sizes& d, int32_t B, int32_t Lw, double rate, int64_t origin, int64_t u) {
+    if (B < 0 || Lw < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (Lw % d.hop) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "Lw = %d is not a multiple of hop_length %d", Lw, d.hop);
+    if (origin < 0 || origin % d.hop)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin = %lld is not a multiple of hop_length %d at or above 0", (long long)origin, d.hop);
+    if (u < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "u = %lld is negative", (long long)u);
+    TRY(ts_check_rate(rate));
+    TRY(check_batch(B));
+    if (origin > ((int64_t)1 << 60)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "origin = %lld exceeds 2^60", (long long)origin);
+    if (u > ((int64_t)1 << 61) / d.hop) return fail(IRIS_HIFIGAN_UNSUPPORTED, "u = %lld: its samples exceed 2^61", (long long)u);
+    if (d.taps() < 2)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "hop_length %d equals n_fft: frames that do not overlap carry no tail, and no window form is built for them", d.hop);
+    const unsigned long long rows = (unsigned long long)ts_window_frames(Lw / d.hop, rate) + d.taps();
+    if ((unsigned long long)(B ? B : 1) * rows * d.qp() >= (1ull << 31))
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "B = %d, Lw = %d at rate %g: %llu frames of %d columns per item exceed 32-bit offsets", B, Lw, rate, rows, d.qp());
+    return IRIS_HIFIGAN_OK;
+}
+
+// The plan of a checked window, or the refusal of a u whose first row the window no longer holds.
+int ts_plan_window(const stft::Sizes& d, double rate, int64_t origin, int32_t Lw, int32_t final, int64_t u, ts::WindowPlan* out) {
+    const ts::WindowPlan p(d, rate, origin / d.hop, Lw / d.hop, final != 0, u);
+    if (p.dropped)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "frame u = %lld reads input row %lld, but the window [%lld, %lld) holds rows from %lld on: samples were dropped "
+                    "before keep_from", (long long)u, ts::source_row(u, rate), (long long)origin, (long long)origin + Lw, p.f_lo);
+    *out = p;
+    return IRIS_HIFIGAN_OK;
+}
+
+// Queues a window's launches (or, in a dry run, counts them): 4; 3 where frames advance but no sample is emitted yet; 2 (the
+// scan, which then only lays the tail out, and the inverse transform) where a final window has samples left and no frame.
+// The caller has checked that there is a frame or a sample.  `state` may be NULL only when u == 0.
+int ts_forward_window(const stft::Sizes& d, const TsTables& tb, const float* wav, int B, int Lw, const ts::WindowPlan& p, long long origin,
+                      long long u, double rate, float* state, float* out, float* ws, hipStream_t stream) {
+    const TsWindowWorkspace lay(d, B, Lw, rate);
+    const TsState sl(d, B);
+    const int F = (int)(p.f_hi - p.f_lo), n_new = (int)(p.u_hi - u), n_tail = (int)p.n_tail;
+    uint32_t* inc = reinterpret_cast<uint32_t*>(ws + lay.inc);
+    uint32_t* acc = reinterpret_cast<uint32_t*>(ws + lay.acc);
+    if (n_new > ts_window_frames(Lw / d.hop, rate)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "a window of %d samples plans %d frames, past its workspace", Lw, n_new);
+    uint32_t* acc_state = state ? reinterpret_cast<uint32_t*>(state + sl.acc) : nullptr;
+    float* tail_state = state ? state + sl.tail : nullptr;
+
+    if (n_new > 0) {
+        stft::StftLaunch st; memset(&st, 0, sizeof(st));
+        st.y = wav; st.wdft = (const f32x4*)tb.dft; st.L = Lw; st.T = F; st.y_org = (int)(p.f_lo * d.hop - origin);
+        ts::WindowSpectrum spec; memset(&spec, 0, sizeof(spec));
+        spec.c = ws + lay.c; spec.rate = rate; spec.hop = d.hop;
+        HIP_TRY(stft::launch_stft(st, spec, d, B, stream));
+
+        ts::StepLaunch sp; memset(&sp, 0, sizeof(sp));
+        sp.c = ws + lay.c; sp.mag = ws + lay.mag; sp.inc = inc; sp.rate = rate;
+        sp.T = F; sp.T_out = n_new; sp.Ks = d.ks(); sp.Qp = d.qp(); sp.bins = d.bins(); sp.hop = d.hop; sp.n_fft = d.n_fft;
+        sp.t_org = u; sp.f_lo = p.f_lo;
+        HIP_TRY(ts::launch_step(sp, B, stream));
+    }
+
+    ts::ScanLaunch sc; memset(&sc, 0, sizeof(sc));
+    sc.c = ws + lay.c; sc.mag = ws + lay.mag; sc.inc = inc; sc.acc = acc; sc.out_c = ws + lay.out_c;
+    sc.T = F; sc.T_out = n_new; sc.Ks = d.ks(); sc.Qp = d.qp(); sc.bins = d.bins();
+    sc.acc_in = u ? acc_state : nullptr; sc.acc_out = acc_state;
+    sc.tail_in = tail_state; sc.tail_out = n_new > 0 ? tail_state : nullptr;
+    sc.row_off = n_tail; sc.tail_rows = d.taps() - 1; sc.tail_keep = (int)p.n_keep;
+    HIP_TRY(ts::launch_scan(sc, B, stream));
+
+    if (p.out_count > 0) {
+        stft::IstftLaunch is; memset(&is, 0, sizeof(is));
+        is.c = ws + lay.out_c; is.widft = (const f32x4*)tb.idft; is.wsq = tb.wsq; is.T = n_tail + n_new; is.y = out;
+        is.Ly = (int)p.out_count; is.s_org = (int)(p.out_lo - (u - n_tail) * d.hop);
+        HIP_TRY(stft::launch_istft_slice(is, d, B, stream));
+    }
+    return IRIS_HIFIGAN_OK;
+}
+
 bool overlap(const float* a, size_t na, const float* b, size_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
@@ -215,6 +323,81 @@ int32_t iris_time_stretch_forward_ragged(iris_time_stretch_handle* h, const floa
                                          void* stream) {
     IRIS_ABI_BEGIN
     return ts_run(h, wav_dev, B, L, lengths_dev, rate, out_dev, counts_out_dev, workspace_dev, workspace_bytes, stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_time_stretch_state_bytes(const iris_mel_frontend_config* cfg, int32_t B, uint64_t* bytes) {
+    IRIS_ABI_BEGIN
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    stft::Sizes d;
+    TRY(ts_validate(cfg, &d));
+    TRY(ts_check_window(d, B, 0, 1.0, 0, 0));
+    *bytes = (uint64_t)TsState(d, B).floats * sizeof(float);
+    if (*bytes < 256) *bytes = 256;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_time_stretch_window_plan(const iris_mel_frontend_config* cfg, double rate, int64_t origin, int32_t Lw, int32_t final, int64_t u,
+                                      int64_t* u_hi, int64_t* out_lo, int64_t* out_count, int64_t* keep_from) {
+    IRIS_ABI_BEGIN
+    if (!u_hi || !out_lo || !out_count || !keep_from) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    stft::Sizes d;
+    TRY(ts_validate(cfg, &d));
+    TRY(ts_check_window(d, 1, Lw, rate, origin, u));
+    ts::WindowPlan p;
+    TRY(ts_plan_window(d, rate, origin, Lw, final, u, &p));
+    *u_hi = p.u_hi; *out_lo = p.out_lo; *out_count = p.out_count; *keep_from = p.keep_from;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_time_stretch_window_workspace_bytes(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, double rate, uint64_t* bytes) {
+    IRIS_ABI_BEGIN
+    if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    stft::Sizes d;
+    TRY(ts_validate(cfg, &d));
+    TRY(ts_check_window(d, B, Lw, rate, 0, 0));
+    *bytes = (uint64_t)TsWindowWorkspace(d, B, Lw, rate).floats * sizeof(float);
+    if (*bytes < 256) *bytes = 256;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_time_stretch_window_launch_count(const iris_mel_frontend_config* cfg, int32_t B, int32_t Lw, double rate, int64_t origin, int32_t final,
+                                              int64_t u, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    stft::Sizes d;
+    TRY(ts_validate(cfg, &d));
+    TRY(ts_check_window(d, B, Lw, rate, origin, u));
+    ts::WindowPlan p;
+    TRY(ts_plan_window(d, rate, origin, Lw, final, u, &p));
+    *n = 0;
+    if (B == 0 || (p.u_hi == u && p.out_count == 0)) return IRIS_HIFIGAN_OK;
+    return count_launches([&](float* fake) {
+        const TsTables tb = {fake, fake, fake};
+        return ts_forward_window(d, tb, fake, B, Lw, p, origin, u, rate, fake, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_time_stretch_forward_window(iris_time_stretch_handle* h, const float* wav_dev, int32_t B, int32_t Lw, int64_t origin, int32_t final,
+                                         double rate, int64_t u, void* state_dev, float* out_dev, void* workspace_dev, uint64_t workspace_bytes,
+                                         void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(ts_check_window(h->d, B, Lw, rate, origin, u));
+    ts::WindowPlan p;
+    TRY(ts_plan_window(h->d, rate, origin, Lw, final, u, &p));
+    if (!state_dev && (u > 0 || !final))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "no state: only a final window that starts at frame 0 (a whole utterance) carries nothing over");
+    if (B == 0 || (p.u_hi == u && p.out_count == 0)) return IRIS_HIFIGAN_OK;
+    if ((p.u_hi > u && !wav_dev) || !workspace_dev || (p.out_count && !out_dev)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (p.out_count && wav_dev && overlap(wav_dev, (size_t)B * Lw, out_dev, (size_t)B * p.out_count)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev aliases wav_dev");
+    ForwardScope scope(*h, workspace_bytes, TsWindowWorkspace(h->d, B, Lw, rate).floats);
+    TRY(scope.rc);
+    const TsTables tb = {h->blob + h->t.dft.w_off, h->blob + h->t.idft.w_off, h->blob + h->t.wsq_off};
+    return ts_forward_window(h->d, tb, wav_dev, B, Lw, p, origin, u, rate, (float*)state_dev, out_dev, (float*)workspace_dev, (hipStream_t)stream);
     IRIS_ABI_END
 }
 

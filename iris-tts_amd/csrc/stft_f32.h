@@ -205,6 +205,28 @@ inline int transform_validate(const Sizes& d) {
     return validate_frame_window(d);
 }
 
+// frames on either side whose window leaves the signal
+inline int edge_frames(const Sizes& d) { return (d.n_fft / 2 + d.hop - 1) / d.hop; }
+
+// The finality rule of "Windows" in denoiser.h for the window [H m0, H (m0 + Mw)): frames [f_lo, f_hi) are computable (f_lo is
+// clamped to f_hi when there is none) and samples [out_lo, out_lo + out_count) are final.  Frames before f_lo exist unless
+// m0 == 0, frames from f_hi on exist unless `final`, so a row j = floor((s + n_fft / 2) / H) is final when
+// j - taps + 1 >= f_lo (or m0 == 0) and j < f_hi (or final).
+struct Window {
+    long long f_lo, f_hi, out_lo, out_count;
+    Window(const Sizes& d, long long m0, long long Mw, bool final) {
+        const long long H = d.hop, half = d.n_fft / 2, e = edge_frames(d), o = H * m0, end = o + H * Mw;
+        f_lo = m0 ? m0 + e : 0;
+        f_hi = final ? m0 + Mw + 1 : m0 + Mw - e + 1;
+        if (f_hi < f_lo) f_hi = f_lo;
+        long long lo = o, hi = end;
+        if (m0 && (f_lo + d.taps() - 1) * H - half > lo) lo = (f_lo + d.taps() - 1) * H - half;
+        if (!final && f_hi * H - half < hi) hi = f_hi * H - half;
+        out_count = f_hi > f_lo && hi > lo ? hi - lo : 0;
+        out_lo = out_count ? lo : o;
+    }
+};
+
 }  // namespace stft
 }  // namespace iris
 

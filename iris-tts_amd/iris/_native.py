@@ -335,6 +335,11 @@ TIME_STRETCH_SYMBOLS = {
     "iris_time_stretch_destroy": (_i32, [_vp]),
     "iris_time_stretch_forward": (_i32, [_vp, _vp, _i32, _i32, _d, _vp, _vp, _u64, _vp]),
     "iris_time_stretch_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _d, _vp, _vp, _vp, _u64, _vp]),
+    "iris_time_stretch_state_bytes": (_i32, [_mfc, _i32, _u64p]),
+    "iris_time_stretch_window_plan": (_i32, [_mfc, _d, _i64, _i32, _i32, _i64, _i64p, _i64p, _i64p, _i64p]),
+    "iris_time_stretch_window_workspace_bytes": (_i32, [_mfc, _i32, _i32, _d, _u64p]),
+    "iris_time_stretch_window_launch_count": (_i32, [_mfc, _i32, _i32, _d, _i64, _i32, _i64, _ip]),
+    "iris_time_stretch_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _d, _i64, _vp, _vp, _vp, _u64, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

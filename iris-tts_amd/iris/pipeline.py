@@ -64,8 +64,15 @@ class MelToWavePipeline:
     through the phase vocoder and run the output stage afterwards as stand-alone launches, as for a denoiser; an item then
     has ``out_samples(hop * T_i)`` samples, and the ragged routes hand the stretch's ``counts`` on as sample lengths
     (``row_scale=1``).  The waveform must be whole frames of the stretch's own ``hop_length`` (``ValueError`` otherwise).
-    ``stream`` and ``session`` raise ``ValueError``: the phase accumulator is a running state and no chunked form is built.
-    With ``stretch=None`` nothing changes."""
+    ``stream`` and ``session`` raise ``ValueError`` for a plain ``ts.at(rate)``: the phase accumulator is a running state.
+    With ``stretch=None`` nothing changes.
+
+    ``stretch=ts.at(rate).chunked()`` (an ``iris.time_stretch.ChunkedStretch``, or any object with ``chunked_sessions = True``, a
+    ``forward_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: the vocoder's fp32 chunks
+    go through the chunked denoiser's session, if there is one, and then through ONE ``StretchSession``, which carries the
+    phase and the last output frames on the device.  Empty pieces are skipped and the last piece carries the halo; the
+    concatenation equals ``infer(mel)`` bit for bit.  It needs fp32 as the chunked denoiser does (``forward_pcm16`` as the
+    ``vocode`` is refused), and a plain denoiser beside it still refuses to stream."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -84,9 +91,13 @@ class MelToWavePipeline:
         self.config = config
         self._whole = vocode if getattr(vocode, "whole_utterance", False) else None
         self._chunked_denoiser = bool(getattr(denoiser, "chunked_sessions", False))
+        self._chunked_stretch = bool(getattr(stretch, "chunked_sessions", False))
         if self._chunked_denoiser and getattr(vocode, "__name__", "") == "forward_pcm16":
             raise ValueError("a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
                              "forward_pcm16 (no chunked PCM stage runs behind the denoiser)")
+        if self._chunked_stretch and getattr(vocode, "__name__", "") == "forward_pcm16":
+            raise ValueError("a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+                             "forward_pcm16 (no chunked PCM stage runs behind the stretch)")
         if self._whole is not None and hop_length is None:
             hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
@@ -119,28 +130,49 @@ class MelToWavePipeline:
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
-        if not self._chunked_denoiser:
+        sessions = self._open_sessions()
+        if not sessions:
             yield from self.streamer.stream(self.refine(mel))
             return
-        session = self.denoiser.open_session()
         for chunk in self.streamer.stream(self.refine(mel)):
-            piece = session.push(self._denoiser_input(chunk))
+            piece = self._push_through(sessions, self._denoiser_input(chunk))
             if piece.shape[1]:
                 yield piece
-        piece = session.flush()
-        if piece.shape[1]:
-            yield piece
+        yield from self._flush_through(sessions)
+
+    def _open_sessions(self) -> list:
+        """The sessions a chunk goes through on its way out, in order: the chunked denoiser's, then the chunked stretch's."""
+        sessions = [self.denoiser.open_session()] if self._chunked_denoiser else []
+        return sessions + ([self.stretch.open_session()] if self._chunked_stretch else [])
+
+    @staticmethod
+    def _push_through(sessions: list, piece: torch.Tensor) -> torch.Tensor:
+        """``piece`` through ``sessions`` in order; an empty piece is not pushed any further."""
+        for session in sessions:
+            if not piece.shape[1]:
+                break
+            piece = session.push(piece)
+        return piece
+
+    @staticmethod
+    def _flush_through(sessions: list) -> List[torch.Tensor]:
+        """Ends the utterance: each session is flushed in order, and what it held goes through the ones behind it first."""
+        out = []
+        for i, session in enumerate(sessions):
+            tail = session.flush()
+            out.append(MelToWavePipeline._push_through(sessions[i + 1:], tail) if i + 1 < len(sessions) else tail)
+        return [p for p in out if p.shape[1]]
 
     @staticmethod
     def _denoiser_input(chunk: torch.Tensor) -> torch.Tensor:
         if not chunk.is_floating_point():
-            raise ValueError(f"a chunked denoiser takes fp32 chunks, the vocoder returned {chunk.dtype}")
+            raise ValueError(f"a chunked denoiser or stretch takes fp32 chunks, the vocoder returned {chunk.dtype}")
         return chunk.float()
 
     def _refuse_chunked_denoiser(self) -> None:
-        if self.stretch is not None:
-            raise ValueError("a pipeline with a time stretch cannot be streamed: the phase accumulator runs through the whole "
-                             "utterance, and no chunked stretch is built; use infer / infer_batch")
+        if self.stretch is not None and not self._chunked_stretch:
+            raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
+                             "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
         if self.denoiser is not None and not self._chunked_denoiser:
             raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
                              "either side, and no chunked denoiser is built; use infer / infer_batch")
@@ -548,7 +580,8 @@ class PipelineSession:
 
     With a chunked denoiser (``MelToWavePipeline(denoiser=dn.chunked())``) every chunk goes through one ``DenoiserSession``
     on its way out: ``push`` and ``flush`` return its non-empty pieces -- the first short by the denoiser's halo, ``flush``
-    returning it -- and a chunk leaves that many samples later."""
+    returning it -- and a chunk leaves that many samples later.  With a chunked stretch (``stretch=ts.at(rate).chunked()``) they
+    then go through one ``StretchSession``, whose pieces ``push`` and ``flush`` return instead."""
 
     def __init__(self, pipeline: MelToWavePipeline, postnet_halo_frames: Optional[int] = None):
         sv = pipeline.streamer
@@ -583,7 +616,7 @@ class PipelineSession:
         self._refined = 0             # first raw frame not yet refined (== frames pushed into the inner session)
         self._lead = None             # (B, n_mels) of the utterance
         self._closed = False
-        self._denoise = pipeline.denoiser.open_session() if pipeline._chunked_denoiser else None
+        self._sessions = pipeline._open_sessions()
 
     @property
     def frames_received(self) -> int:
@@ -617,13 +650,12 @@ class PipelineSession:
         return self._denoised(self._inner.push(piece))
 
     def _denoised(self, chunks: List, final: bool = False) -> List:
-        """The vocoder's chunks through the denoiser session (if there is one); empty pieces are dropped."""
-        if self._denoise is None:
+        """The vocoder's chunks through the denoiser's and the stretch's sessions (if there are any); empty pieces are dropped."""
+        if not self._sessions:
             return chunks
-        pieces = [self._denoise.push(MelToWavePipeline._denoiser_input(c)) for c in chunks]
-        if final:
-            pieces.append(self._denoise.flush())
-        return [p for p in pieces if p.shape[1]]
+        pieces = [MelToWavePipeline._push_through(self._sessions, MelToWavePipeline._denoiser_input(c)) for c in chunks]
+        pieces = [p for p in pieces if p.shape[1]]
+        return pieces + MelToWavePipeline._flush_through(self._sessions) if final else pieces
 
     def push(self, mel_piece) -> List[torch.Tensor]:
         """Appends the raw ``mel_piece [B, n_mels, t]`` (t >= 0, host or device) and returns the waveform chunks

@@ -19,6 +19,11 @@ A forward is 4 launches on the current stream.  ``forward_device(lengths=)`` tak
 batch-of-one call, the rest of its row is 0, and ``counts`` holds the items' samples for the next stage.
 ``pitch_shift_device`` is librosa's structure for ``pitch_shift`` -- stretch by ``2 ** (-n_steps / 12)``, resample back -- on
 ``iris.resample.Resampler``.  ``MelToWavePipeline(..., stretch=ts.at(rate))`` runs the stretch behind the denoiser.
+
+Streaming: ``TimeStretch.open_session(rate)`` takes the waveform piece by piece (``StretchSession``: one ``forward_window`` per
+push, the same launches on a window of the utterance, the phase and the last ``n_fft / hop - 1`` output frames carried in a
+device state) and its output equals ``forward_device`` of the whole bit for bit; ``ts.at(rate).chunked()``
+(``ChunkedStretch``) is the opt-in with which a pipeline's ``stream`` / ``session`` run it behind the vocoder.
 """
 from __future__ import annotations
 
@@ -202,6 +207,194 @@ class TimeStretch(_NativeModel):
         """This stretch at one rate: what ``MelToWavePipeline(stretch=)`` takes."""
         return StretchAt(self, check_rate(rate))
 
+    # -- windows of an utterance -------------------------------------------------------------
+    def state_bytes(self, B: int) -> int:
+        lib = _native.load()
+        cfg, out = self.native_config(), ctypes.c_uint64()
+        _native.check("iris_time_stretch_state_bytes", lib.iris_time_stretch_state_bytes(ctypes.byref(cfg), int(B), ctypes.byref(out)))
+        return int(out.value)
+
+    def new_state(self, B: int) -> torch.Tensor:
+        """The state a sequence of ``forward_window`` calls carries (``iris_time_stretch_state_bytes``): the phase at the next
+        frame and the last ``n_fft / hop_length - 1`` output frames.  Uninitialised: the window with ``u == 0`` reads none of it."""
+        self._ensure()
+        return torch.empty(self.state_bytes(B), dtype=torch.uint8, device=self._device)
+
+    def _state_views(self, state: torch.Tensor, B: int):
+        """Test-only: ``(acc [B, Ks] as int64 in [0, 2^32), tail [B, taps - 1, Qp] fp32)``, views restated from ``TsState``."""
+        ks, qp, rows = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8, self.n_fft // self.hop_length - 1
+        tail_off = (B * ks + 63) // 64 * 64
+        acc = state.view(torch.int32)[:B * ks].view(B, ks).to(torch.int64) & 0xFFFFFFFF
+        return acc, state.view(torch.float32)[tail_off:tail_off + B * rows * qp].view(B, rows, qp)
+
+    def window_plan(self, rate, origin: int, Lw: int, final: bool, u: int):
+        """``(u_hi, out_lo, out_count, keep_from)`` of the window ``[origin, origin + Lw)`` for a caller whose next output frame
+        is ``u``: it computes frames ``[u, u_hi)`` and emits samples ``[out_lo, out_lo + out_count)`` of the stretched
+        utterance; the next window must still hold the input from ``keep_from`` on (``iris_time_stretch_window_plan``: the
+        rule is written down on the C side only).  Host only."""
+        lib = _native.load()
+        cfg, out = self.native_config(), [ctypes.c_int64() for _ in range(4)]
+        _native.check("iris_time_stretch_window_plan", lib.iris_time_stretch_window_plan(
+            ctypes.byref(cfg), ctypes.c_double(float(rate)), ctypes.c_int64(int(origin)), int(Lw), int(bool(final)), ctypes.c_int64(int(u)),
+            *[ctypes.byref(v) for v in out]))
+        return tuple(int(v.value) for v in out)
+
+    def window_workspace_bytes(self, B: int, Lw: int, rate=1.0) -> int:
+        return self._query("iris_time_stretch_window_workspace_bytes", B, Lw, rate=rate)
+
+    def window_launch_count(self, B: int, Lw: int, rate, origin: int, final: bool, u: int) -> int:
+        """Kernel launches of one ``forward_window``: 4; 3 where frames advance but no sample is emitted yet, 2 where a final
+        window has samples left but no frame, 0 where it has neither (a dry run on the host)."""
+        lib = _native.load()
+        cfg, n = self.native_config(), ctypes.c_int32()
+        _native.check("iris_time_stretch_window_launch_count", lib.iris_time_stretch_window_launch_count(
+            ctypes.byref(cfg), int(B), int(Lw), ctypes.c_double(float(rate)), ctypes.c_int64(int(origin)), int(bool(final)),
+            ctypes.c_int64(int(u)), ctypes.byref(n)))
+        return int(n.value)
+
+    def _window_workspace_layout(self, B: int, Lw: int, rate, frames: int, new: int, tail: int):
+        """``{buffer: (offset, shape)}``: ``TsWindowWorkspace`` restated for a window that computed ``frames`` input rows and
+        ``new`` output frames behind ``tail`` carried ones.  Offsets depend on (B, Lw, rate) alone.  Host only."""
+        ks, qp, taps = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8, self.n_fft // self.hop_length
+        F, n = Lw // self.hop_length + 1, math.ceil((Lw // self.hop_length + 1) / float(rate)) + 1
+        layout, off = {}, 0
+        for name, room, shape in (("c", B * F * qp, (B, frames, qp)), ("mag", B * n * ks, (B, new, ks)), ("inc", B * n * ks, (B, new, ks)),
+                                  ("acc", B * n * ks, (B, new, ks)), ("out_c", B * (n + taps - 1) * qp, (B, tail + new, qp))):
+            assert int(np.prod(shape)) <= room
+            layout[name] = (off, shape, room)
+            off += (room + 63) // 64 * 64
+        return layout
+
+    def forward_window(self, wav, rate, origin: int, final: bool, u: int, state: Optional[torch.Tensor]) -> torch.Tensor:
+        """``wav [B, Lw]`` fp32 = samples ``[origin, origin + Lw)`` of an utterance (both multiples of ``hop_length``) -> the
+        samples ``window_plan(rate, origin, Lw, final, u)`` names, ``[B, out_count]`` on the device, each bit for bit the sample
+        ``forward_device`` of the whole utterance returns there.  ``state`` (``new_state(B)``) is read and written in place;
+        None only for a final window with ``u == 0``.  Asynchronous, at most 4 launches, none when the plan is empty.
+        ``StretchSession`` keeps the bookkeeping."""
+        wav = self._wav_on_device(wav)
+        rate = check_rate(rate)
+        B, Lw = int(wav.shape[0]), int(wav.shape[1])
+        u_hi, _, count, _ = self.window_plan(rate, origin, Lw, final, u)
+        lib = self._ensure()
+        out = torch.empty((B, count), dtype=torch.float32, device=self._device)
+        if B == 0 or (u_hi == u and count == 0):
+            return out
+        wav = wav.to(self._device).contiguous()
+        need = self.window_workspace_bytes(B, Lw, rate)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
+        ws = self._workspace
+        with torch.cuda.device(self._device):
+            _native.check("iris_time_stretch_forward_window", lib.iris_time_stretch_forward_window(
+                self._handle, _ptr(wav), B, Lw, ctypes.c_int64(int(origin)), int(bool(final)), ctypes.c_double(rate), ctypes.c_int64(int(u)),
+                _ptr(state), _ptr(out), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device)))
+        return out
+
+    def open_session(self, rate) -> "StretchSession":
+        """A ``StretchSession`` at ``rate`` for one utterance (or a batch of equal lengths) that arrives piece by piece."""
+        return StretchSession(self, check_rate(rate))
+
+
+class StretchSession:
+    """Pushed input for a time stretch at ONE rate: the waveform of one utterance (or a batch of equal lengths) arrives piece by
+    piece (``push``), stretched samples leave as soon as every frame under them is computable, ``flush`` ends the utterance.
+    The concatenation of everything returned equals ``forward_device`` of the concatenated pieces bit for bit: the phase is an
+    exact integer sum carried in the state, an output frame depends on two input rows alone, and an output sample on its own
+    ``n_fft / hop`` output frames, of which the state keeps the last ``n_fft / hop - 1``.
+
+    ``ts``: a ``TimeStretch``, or any object with ``hop_length``, ``window_plan(rate, origin, Lw, final, u)``,
+    ``forward_window(wav, rate, origin, final, u, state)`` and ``new_state(B)``.  Each push runs ONE window over the whole
+    frames that are buffered, carries ``u`` (the next output frame) and the state tensor, and keeps the input from the plan's
+    ``keep_from`` on.  Pieces may be empty -- a piece shorter than the halo settles nothing and launches nothing -- and
+    ``flush`` returns what was waiting for context.  A piece need not be whole frames; the utterance must be by ``flush``."""
+
+    def __init__(self, ts, rate: float):
+        self._ts, self.rate = ts, float(rate)
+        self.hop_length = int(ts.hop_length)
+        self._buf: Optional[torch.Tensor] = None          # samples [self._base, self._total) of the utterance, [B, n]
+        self._base = 0
+        self._total = 0
+        self._emitted = 0
+        self._u = 0
+        self._state = None
+        self._closed = False
+
+    @property
+    def samples_received(self) -> int:
+        return self._total
+
+    @property
+    def samples_emitted(self) -> int:
+        return self._emitted
+
+    @property
+    def samples_buffered(self) -> int:
+        return self._total - self._base
+
+    @property
+    def frames_computed(self) -> int:
+        """``u``: the next output frame."""
+        return self._u
+
+    def _empty(self) -> torch.Tensor:
+        if self._buf is None:
+            return torch.empty((0, 0), dtype=torch.float32)
+        return self._buf.new_empty((self._buf.shape[0], 0))
+
+    def _advance(self, final: bool) -> torch.Tensor:
+        if self._buf is None:
+            return self._empty()
+        hop, held = self.hop_length, self._total - self._base
+        if final and held % hop:
+            raise ValueError(f"the utterance has {self._total} samples, no multiple of hop_length = {hop}; nothing is padded silently")
+        Lw = held // hop * hop
+        u_hi, lo, count, keep = self._ts.window_plan(self.rate, self._base, Lw, final, self._u)
+        if u_hi == self._u and count == 0:
+            return self._empty()                              # no frame and no sample: no launch
+        if count and lo != self._emitted:
+            raise RuntimeError(f"the window [{self._base}, {self._base + Lw}) emits samples from {lo} on, but {self._emitted} is due")
+        if self._state is None:
+            self._state = self._ts.new_state(int(self._buf.shape[0]))
+        out = self._ts.forward_window(self._buf[:, :Lw], self.rate, self._base, final, self._u, self._state)
+        self._emitted += count
+        self._u = u_hi
+        keep = max(self._base, min(keep, self._base + Lw))    # an origin at or below keep_from, a multiple of hop, inside what is held
+        if keep > self._base:
+            self._buf = self._buf[:, keep - self._base:]
+            self._base = keep
+        return out
+
+    def push(self, wav_piece, lengths=None) -> torch.Tensor:
+        """Appends ``wav_piece [B, n]`` fp32 (n >= 0) and returns the device tensor ``[B, m]`` of the stretched samples that
+        became final; ``m`` may be 0."""
+        if lengths is not None:
+            raise ValueError("a session takes items of one length: ragged batches stay on forward_device(lengths=)")
+        if self._closed:
+            raise RuntimeError("the session was flushed: open a new one for the next utterance")
+        if not isinstance(wav_piece, torch.Tensor):
+            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
+        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
+            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
+        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
+            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
+        if self._buf is None:
+            self._buf = wav_piece
+        elif wav_piece.shape[1]:
+            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
+        self._total += int(wav_piece.shape[1])
+        return self._advance(final=False)
+
+    def flush(self) -> torch.Tensor:
+        """Ends the utterance and returns the samples that were waiting for context: the right edge of this last window is
+        the true end, as in the one-shot forward.  Further calls return an empty tensor."""
+        if self._closed:
+            return self._empty()
+        out = self._advance(final=True)
+        self._closed = True
+        self._buf = None if self._buf is None else self._buf[:, :0]
+        self._base = self._total
+        return out
+
 
 class StretchAt:
     """``ts`` bound to a rate: ``forward_device(wav, lengths=) -> (out, counts)`` and ``out_samples(L)``."""
@@ -218,6 +411,25 @@ class StretchAt:
 
     def forward_device(self, wav, lengths=None):
         return self.ts.forward_device(wav, self.rate, lengths=lengths)
+
+    def chunked(self) -> "ChunkedStretch":
+        """This stretch as the opt-in a pipeline looks for before it streams (``ChunkedStretch``)."""
+        return ChunkedStretch(self)
+
+
+class ChunkedStretch(StretchAt):
+    """``ts.at(rate)`` with the promise a streaming pipeline asks for: ``MelToWavePipeline(..., stretch=ts.at(rate).chunked())``
+    lets ``stream`` and ``session`` run, every fp32 chunk -- the chunked denoiser's, where there is one -- going through one
+    ``StretchSession``.  The opt-in is explicit because the pieces such a pipeline yields no longer have the chunks' lengths;
+    a plain ``ts.at(rate)`` keeps refusing.  ``forward_device`` and ``out_samples`` are the whole-utterance ones."""
+
+    chunked_sessions = True
+
+    def __init__(self, at: StretchAt):
+        super().__init__(at.ts, at.rate)
+
+    def open_session(self) -> "StretchSession":
+        return StretchSession(self.ts, self.rate)
 
 
 def semitone_ratio(n_steps: float, max_den: int = 640) -> Fraction:

@@ -5,6 +5,12 @@
 (b) the same algorithm in torch ops (torch.stft, cumsum, torch.istft) on the same GPU.
 
     python tools/time_stretch_bench.py [--rate 1.0] [--iters 10] [--rounds 5] [--out profiles/time_stretch_bench.json]
+    python tools/time_stretch_bench.py --chunked 256 [--rate 0.9] [--out profiles/time_stretch_bench.json]
+
+``--chunked FRAMES`` times the chunked form instead: 1 x 1000 frames pushed into a ``StretchSession`` in pieces of FRAMES mel
+frames (and flushed) against the whole-utterance call on the same input, alternating in every round; the session's result is
+compared with the whole one bit for bit first.  With ``--out`` the record goes under ``"chunked"`` of that file, beside what
+it holds.
 
 Two shapes at n_fft 1024, hop 256: 1 x 1000 and 32 x 500 mel frames of vocoder output.  Device events around `iters`
 back-to-back calls, after a warm-up; the three alternate in every round and the median round is reported with the spread.
@@ -63,8 +69,45 @@ def _summary(name: str, samples) -> dict:
     return {f"{name}_ms": float(np.median(samples)), f"{name}_ms_min_max": [float(min(samples)), float(max(samples))]}
 
 
+def chunked(ts: TimeStretch, dev, frames: int, rate: float, iters: int, rounds: int) -> dict:
+    M, hop = 1000, ts.hop_length
+    rng = np.random.default_rng(M)
+    t = np.arange(hop * M) / 22050.0
+    wav = torch.from_numpy((0.5 * np.sin(2.0 * np.pi * 220.0 * t)[None, :] + 0.05 * rng.standard_normal((1, hop * M))).astype(np.float32)).to(dev)
+    pieces = [wav[:, at:at + hop * frames].contiguous() for at in range(0, hop * M, hop * frames)]
+    windows = []
+
+    def session():
+        s = ts.open_session(rate)
+        out = [s.push(p) for p in pieces] + [s.flush()]
+        return torch.cat(out, dim=1)
+
+    whole = lambda: ts.forward_device(wav, rate)[0]
+    if not torch.equal(session(), whole()):
+        sys.exit("the session's output differs from the whole-utterance call")
+    base = total = u = 0
+    for n, final in [(p.shape[1], False) for p in pieces] + [(0, True)]:                 # the windows the session ran, from the plan
+        total += n
+        u_hi, _, count, keep = ts.window_plan(rate, base, total - base, final, u)
+        if u_hi > u or count:
+            windows.append({"origin": base, "samples": total - base, "frames": u_hi - u, "emitted": count,
+                            "launches": ts.window_launch_count(1, total - base, rate, base, final, u)})
+        u, base = u_hi, max(base, min(keep, total))
+    for fn in (session, whole):
+        time_ms(fn, 2, dev)
+    a, b = [], []
+    for _ in range(rounds):
+        a.append(time_ms(session, iters, dev))
+        b.append(time_ms(whole, iters, dev))
+    extra = float(np.median(a) - np.median(b))
+    return {"shape": f"1x{M}", "rate": rate, "push_frames": frames, "pushes": len(pieces), "windows": windows, "iters": iters, "rounds": rounds,
+            **_summary("session", a), **_summary("whole", b), "extra_ms": extra, "extra_ms_per_window": extra / len(windows),
+            "bit_identical": True}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chunked", type=int, default=0, metavar="FRAMES")
     ap.add_argument("--rate", type=float, default=1.0)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
@@ -74,6 +117,17 @@ def main():
         sys.exit("time_stretch_bench needs a GPU")
     dev = torch.device("cuda", 0)
     ts = TimeStretch(1024, 256, device=dev)
+    if args.chunked:
+        rec = chunked(ts, dev, args.chunked, args.rate, args.iters, args.rounds)
+        print(json.dumps(rec))
+        if args.out:
+            path = Path(args.out)
+            out = json.loads(path.read_text()) if path.exists() else {"tool": "tools/time_stretch_bench.py", "gpu": torch.cuda.get_device_name(dev),
+                                                                      "config": ts.get_config()}
+            out["chunked"] = rec
+            path.parent.mkdir(parents=True, exist_ok=True)
+            path.write_text(json.dumps(out, indent=1) + "\n")
+        return
     dn = Denoiser(1024, 256, 1024, strength=0.0, device=dev)
     ref = TorchStretch(ts, dev)
     results = []
