@@ -918,6 +918,61 @@ int32_t iris_time_stretch_forward_window(iris_time_stretch_handle* h, const floa
                                          int32_t final, double rate, int64_t u, void* state_dev, float* out_dev /* [B, out_count] */,
                                          void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- Assemble: silence trim and sentence join, a ragged batch becomes one waveform (csrc/assemble.h) ----------------------
+ * Per item the decision of librosa.effects.trim(y, top_db=, ref=np.max, frame_length=F, hop_length=H), then one launch lays the
+ * trimmed items end to end with a pause between them and a short fade at every cut.  fp32; the host never reads a length.
+ * lengths_dev (may be NULL) and row_scale >= 1 as in iris_resampler_forward: item b owns L_b = min(L, lengths[b] * row_scale)
+ * samples; samples past that are never read (they may hold NaN).  csrc/assemble.h states every rule; in short:
+ *     T_b = L_b / H + 1 frames; frame t covers samples [t H - F / 2, t H + F / 2) (0 outside the item); mse[t] = sum(y^2) / F,
+ *         summed in a fixed fp32 order that depends on the item's own sample indices alone;
+ *     ref_b = max_t mse[t], or ref * ref where cfg.ref > 0;  frame t is non-silent iff
+ *         fmaxf(mse[t], 1e-10f) > fmaxf(ref_b, 1e-10f) * (float)pow(10, -top_db / 10)      (strict; an item of digital silence
+ *         keeps every frame with ref == 0, as in librosa);
+ *     t0 / t1 the first / last non-silent frame: start = t0 H, end = min(L_b, (t1 + 1) H) (none: 0, 0);
+ *         start' = max(0, start - pad), end' = min(L_b, end + pad), len_b = end' - start';
+ *     off_b = sum over a < b of (len_a + (len_a > 0 ? pause : 0)); total = off_B less the last pause; an empty item adds
+ *         neither samples nor a pause;
+ *     out[off_b + n] = (wav[b, start' + n] * a) * b2, a = n < fade ? ramp[n] : 1, b2 = len_b - 1 - n < fade ? ramp[len_b - 1 - n]
+ *         : 1, ramp[j] = 0.5 - 0.5 cos(pi (j + 0.5) / fade) (double, rounded once); pauses and [total, cap) are stored as 0.0f.
+ * forward: wav_dev [B, L] -> out_dev [cap], cap = B L + pause (B - 1) (out_capacity); every element of out_dev is stored exactly
+ * once, without atomics, and two runs give the same bits.  spans_out_dev [B][2] (or NULL) receives start', end';
+ * offsets_out_dev [B + 1] receives off_0 .. off_(B-1) and, last, total -- offsets_out_dev + B is the lengths pointer of a
+ * following iris_resampler_forward / iris_hifigan_op_pcm16 on out_dev as ONE row of cap samples (row_scale 1).  Item b's span
+ * and samples are those of its batch-of-one call.  Chaining: behind the vocoder with lengths in mel frames and row_scale =
+ * hop; behind iris_time_stretch_forward_ragged with its counts and row_scale = 1.
+ * trim_ragged: the same bounds with each item stored in its own row, out_dev [B, L], 0.0f behind len_b, and counts_out_dev [B] =
+ * len_b as the next stage's lengths (the same launches; the gather runs with one row per item and no pause).
+ * After a call the workspace holds, each starting on 256 bytes: mse [B][L / H + 1] fp32, of which row b is stored up to T_b,
+ * and spans [B][2] int32; nothing else is written.  3 launches, asynchronous on `stream`, nothing allocated, safe in a stream
+ * capture.
+ * frame_length odd or below 2, hop_length not dividing frame_length / 2, top_db <= 0 or not finite, ref < 0 or not finite, a
+ * negative pad / fade / pause, row_scale < 1, a negative shape, a NULL pointer and out_dev overlapping wav_dev return
+ * IRIS_HIFIGAN_INVALID_ARGUMENT; frame_length > 8192, fade > 65536, B > 4096 (the join stages the B + 1 offsets in LDS), and
+ * cap or B L above 2^31 - 1 IRIS_HIFIGAN_UNSUPPORTED; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call
+ * launches.  B == 0 or L == 0: nothing to do, IRIS_HIFIGAN_OK. */
+typedef struct iris_assemble_config {
+    int32_t frame_length, hop_length;
+    float top_db;
+    float ref;                  /* absolute reference amplitude; 0: the item's own maximum */
+    int32_t pad_samples, fade_samples, pause_samples;
+} iris_assemble_config;
+typedef struct iris_assemble_handle iris_assemble_handle;
+/* Host only (no device is needed); the launch count is a dry run of the forward's own code. */
+int32_t iris_assemble_out_capacity(const iris_assemble_config* cfg, int32_t B, int32_t L, int64_t* cap);
+int32_t iris_assemble_workspace_bytes(const iris_assemble_config* cfg, int32_t B, int32_t L, uint64_t* bytes);
+int32_t iris_assemble_launch_count(const iris_assemble_config* cfg, int32_t B, int32_t L, int32_t* n);
+/* create: on the current device, which becomes the handle's; it uploads the ramp. */
+int32_t iris_assemble_create(const iris_assemble_config* cfg, iris_assemble_handle** out);
+int32_t iris_assemble_destroy(iris_assemble_handle* h);
+int32_t iris_assemble_forward(iris_assemble_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                              const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* out_dev /* [cap] */,
+                              int32_t* spans_out_dev /* [B][2] or NULL */, int32_t* offsets_out_dev /* [B + 1] */,
+                              void* workspace_dev, uint64_t workspace_bytes, void* stream);
+int32_t iris_assemble_trim_ragged(iris_assemble_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                                  const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* out_dev /* [B, L] */,
+                                  int32_t* spans_out_dev /* [B][2] or NULL */, int32_t* counts_out_dev /* [B] */,
+                                  void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -342,6 +342,27 @@ TIME_STRETCH_SYMBOLS = {
     "iris_time_stretch_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _d, _i64, _vp, _vp, _vp, _u64, _vp]),
 }
 
+
+
+class AssembleConfig(ctypes.Structure):
+    """``iris_assemble_config``"""
+
+    _fields_ = [("frame_length", ctypes.c_int32), ("hop_length", ctypes.c_int32), ("top_db", ctypes.c_float), ("ref", ctypes.c_float),
+                ("pad_samples", ctypes.c_int32), ("fade_samples", ctypes.c_int32), ("pause_samples", ctypes.c_int32)]
+
+
+# silence trim and sentence join (iris.assemble): bound by load() like SYMBOLS
+_asc = _c.POINTER(AssembleConfig)
+ASSEMBLE_SYMBOLS = {
+    "iris_assemble_out_capacity": (_i32, [_asc, _i32, _i32, _i64p]),
+    "iris_assemble_workspace_bytes": (_i32, [_asc, _i32, _i32, _u64p]),
+    "iris_assemble_launch_count": (_i32, [_asc, _i32, _i32, _ip]),
+    "iris_assemble_create": (_i32, [_asc, _c.POINTER(_vp)]),
+    "iris_assemble_destroy": (_i32, [_vp]),
+    "iris_assemble_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "iris_assemble_trim_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -368,7 +389,7 @@ def load() -> ctypes.CDLL:
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
-                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS}.items():
+                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

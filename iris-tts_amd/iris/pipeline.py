@@ -72,15 +72,27 @@ class MelToWavePipeline:
     go through the chunked denoiser's session, if there is one, and then through ONE ``StretchSession``, which carries the
     phase and the last output frames on the device.  Empty pieces are skipped and the last piece carries the halo; the
     concatenation equals ``infer(mel)`` bit for bit.  It needs fp32 as the chunked denoiser does (``forward_pcm16`` as the
-    ``vocode`` is refused), and a plain denoiser beside it still refuses to stream."""
+    ``vocode`` is refused), and a plain denoiser beside it still refuses to stream.
+
+    ``assemble``: an ``iris.assemble.Assembler`` (or any object with ``join_device(wav [B, L], lengths=, row_scale=) -> (out
+    [cap], offsets [B + 1], spans [B, 2])``), or None.  With one, a batch is taken to be the sentences of one text:
+    ``infer_batch`` -- and so the batch routes of ``infer_from_phonemes`` and ``resynthesize`` -- return ``(waveform, spans)``
+    instead of a list: every item trimmed of its leading and trailing silence (``librosa.effects.trim``'s decision, on the
+    device) and laid end to end with the assembler's pause and fades, ``spans [B, 2]`` (device, int32) saying what was kept of
+    each item.  The join runs behind the denoiser and the stretch and in front of ``pcm16=`` / ``normalize=`` /
+    ``resampler=``, which then see ONE row: the peak is the joined utterance's.  Every launch is queued before the one
+    read-back, the total, which sizes the result.  ``infer`` treats every row of its mel as an item of such a batch; one row
+    is trimmed, a join of one.  ``stream`` and ``session`` refuse (``ValueError``): the reference level is the whole item's
+    maximum, and no chunked form is built.  With ``assemble=None`` nothing changes."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
                  group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None,
-                 denoiser=None, stretch=None):
+                 denoiser=None, stretch=None, assemble=None):
         self.postnet = postnet
         self.denoiser = denoiser
         self.stretch = stretch
+        self.assemble = assemble
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
@@ -170,6 +182,9 @@ class MelToWavePipeline:
         return chunk.float()
 
     def _refuse_chunked_denoiser(self) -> None:
+        if self.assemble is not None:
+            raise ValueError("a pipeline with assemble= cannot be streamed: the trim's reference level is the whole item's "
+                             "maximum, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
         if self.stretch is not None and not self._chunked_stretch:
             raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
                              "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
@@ -215,6 +230,8 @@ class MelToWavePipeline:
         if wav.shape[1] % sh:                                        # the padded row itself; its tail belongs to no item
             wav = torch.nn.functional.pad(wav, (0, sh - wav.shape[1] % sh))
         out, counts = self.stretch.forward_device(wav, lengths=[hop * r // sh for r in rows])
+        if self.assemble is not None:
+            return self._joined_output_stage(out, counts, 1, pcm16, normalize, resampler)
         return self._ragged_output_stage(out, counts, pcm16, normalize, resampler, hop=1,
                                          samples=[self.stretch.out_samples(hop * r) for r in rows])
 
@@ -235,6 +252,26 @@ class MelToWavePipeline:
             out = wav
         out = out[0] if normalize else out
         return [out[i, :n] for i, n in enumerate(samples)]
+
+    def _joined_output_stage(self, wav: torch.Tensor, lengths, row_scale: int, pcm16: bool, normalize: bool, resampler):
+        """A batch whose item i owns ``lengths[i] * row_scale`` samples through the assembler, then the output stage on the
+        joined row with the device's total as its length.  Returns ``(what infer returns for one row, cut at the total;
+        spans)``; the total is read back once, after everything is queued."""
+        out, offsets, spans = self.assemble.join_device(wav.float(), lengths=lengths, row_scale=row_scale)
+        row, total = out[None], offsets[-1:]
+        if resampler is not None:
+            res = resampler.forward(row, lengths=total, row_scale=1, pcm16=pcm16, normalize=normalize)
+        elif pcm16:
+            from .synthesis_output import pcm16_on_device
+            res = pcm16_on_device(row, normalize=normalize)        # the row is 0 behind the total: its peak is the utterance's
+        else:
+            res = row
+        n = int(total.item())
+        if resampler is not None:
+            n = resampler.out_range(0, n)[1]
+        if normalize:
+            return (res[0][0, :n], res[1]), spans
+        return res[0, :n], spans
 
     def _pcm16_fn(self) -> Callable:
         fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_pcm16", None)
@@ -261,13 +298,15 @@ class MelToWavePipeline:
         result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
-        if self.denoiser is not None or self.stretch is not None:
+        if self.denoiser is not None or self.stretch is not None or self.assemble is not None:
             mel = self.refine(mel)
             wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
             if self.denoiser is not None:
                 wav = self._denoise(wav)
             if self.stretch is not None:
                 wav = self.stretch.forward_device(wav.float())[0]
+            if self.assemble is not None:
+                return self._joined_output_stage(wav, None, 1, pcm16, normalize, resampler)
             return self._output_stage(wav, pcm16, normalize, resampler)
         if self._whole is not None:
             return self._vocode_whole(self.refine(mel), pcm16, normalize, resampler)
@@ -499,7 +538,8 @@ class MelToWavePipeline:
         ``pcm16=True``: int16 waveforms from ``GeneratorEngine.forward_pcm16``; with ``normalize=True`` each is scaled to
         0.95 at its own peak first.  ``resampler``: every waveform at its rate (``GeneratorEngine.forward_resampled`` with the
         same lengths: item i has ``resampler.out_range(0, hop * T_i)[1]`` samples, bit for bit its one-item conversion).
-        A whole-utterance vocoder with ``takes_lengths`` (``_vocode_whole_ragged``): ``hop * (T_i - 1)`` samples per item."""
+        A whole-utterance vocoder with ``takes_lengths`` (``_vocode_whole_ragged``): ``hop * (T_i - 1)`` samples per item.
+        With ``assemble=`` the result is ``(waveform, spans)``: the items trimmed and joined into one (the class docstring)."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
         mels = list(mels)
@@ -513,7 +553,7 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        if self.denoiser is not None or self.stretch is not None:
+        if self.denoiser is not None or self.stretch is not None or self.assemble is not None:
             frames = [int(t) for t in lengths]
             if ragged_whole:
                 rows = [max(t - 1, 0) for t in frames]
@@ -528,6 +568,8 @@ class MelToWavePipeline:
                 wav = self._denoise(wav, rows)
             if self.stretch is not None:
                 return self._stretch_ragged(wav.float(), rows, pcm16, normalize, resampler)
+            if self.assemble is not None:
+                return self._joined_output_stage(wav, rows, self.streamer.hop_length, pcm16, normalize, resampler)
             return self._ragged_output_stage(wav, rows, pcm16, normalize, resampler)
         if ragged_whole:
             return self._vocode_whole_ragged(padded, lengths, pcm16, normalize, resampler)

@@ -137,6 +137,24 @@ def check_pitch_steps(n_steps) -> float:
     return n
 
 
+def check_trim_db(top_db) -> float:
+    """``--trim_db``: a finite threshold above 0, in dB below the waveform's loudest frame."""
+    db = float(top_db)
+    if not 0.0 < db < float("inf"):                           # False for NaN too
+        raise ValueError(f"trim_db must be a finite threshold above 0 dB, got {top_db}")
+    return db
+
+
+def trim_silence(audio: np.ndarray, top_db: float, frame_length: int = 2048, hop_length: int = 512) -> np.ndarray:
+    """A float waveform ``[n]`` without its leading and trailing silence: ``librosa.effects.trim(audio, top_db=)``'s decision on
+    the device (``iris.assemble``)."""
+    from .assemble import Assembler
+    audio = to_mono_float32(audio)
+    if len(audio) == 0:
+        return audio
+    return Assembler(frame_length, hop_length, check_trim_db(top_db)).join(audio[None])[0].cpu().numpy()
+
+
 def tempo_and_pitch(audio: np.ndarray, tempo: Optional[float] = None, pitch_steps: Optional[float] = None, n_fft: int = 1024,
                     hop_length: int = 256) -> np.ndarray:
     """A float waveform ``[n]`` through the device phase vocoder (``iris.time_stretch``): first the pitch, at its own length,
@@ -204,7 +222,8 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
                   sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None,
-                  resample_to: Optional[int] = None, tempo: Optional[float] = None, pitch_steps: Optional[float] = None) -> np.ndarray:
+                  resample_to: Optional[int] = None, tempo: Optional[float] = None, pitch_steps: Optional[float] = None,
+                  trim_db: Optional[float] = None) -> np.ndarray:
     """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
     int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
     ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
@@ -214,7 +233,11 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
     the generator's 22 050 Hz on the GPU, ``iris.resample``) and the WAV header carries that rate; ``sample_rate`` keeps
     labelling only, as in the reference.
     ``tempo`` / ``pitch_steps``: the entry's float waveform goes through ``tempo_and_pitch`` (the device phase vocoder) before
-    it is normalised and written; an entry that returns 16-bit PCM is refused (``ValueError``), the stage takes fp32."""
+    it is normalised and written; an entry that returns 16-bit PCM is refused (``ValueError``), the stage takes fp32.
+    ``trim_db``: the entry's float waveform loses its leading and trailing silence first (``trim_silence``); an entry that
+    returns 16-bit PCM is refused in the same way."""
+    if trim_db is not None:
+        check_trim_db(trim_db)
     if tempo is not None:
         check_tempo(tempo)
     if pitch_steps is not None:
@@ -222,6 +245,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
     fn = resolve_vocoder_entry(vocoder_entry)
     if (tempo is not None or pitch_steps is not None) and getattr(fn, "returns_pcm16", False):
         raise ValueError("tempo / pitch_steps take the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
+    if trim_db is not None and getattr(fn, "returns_pcm16", False):
+        raise ValueError("trim_db takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
     if normalize_peak is not None:
@@ -242,6 +267,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
             raise ValueError(f"expected a single waveform after squeeze, got shape {audio.shape}")
     else:
         audio = to_mono_float32(audio)
+        if trim_db is not None:
+            audio = trim_silence(audio, trim_db)
         if tempo is not None or pitch_steps is not None:
             audio = tempo_and_pitch(audio, tempo, pitch_steps, hop_length=hop_length)
         if normalize_peak is not None:
@@ -270,6 +297,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="play RATE times as fast at the same pitch (0.25 .. 4; the device phase vocoder, iris.time_stretch)")
     parser.add_argument("--pitch_steps", type=float, default=None, metavar="N",
                         help="shift the pitch by N semitones at the same length (-12 .. 12, fractions allowed)")
+    parser.add_argument("--trim_db", type=float, default=None, metavar="DB",
+                        help="cut leading and trailing silence more than DB below the loudest frame (librosa.effects.trim's "
+                             "decision on the GPU, iris.assemble), before the other output options")
     return parser
 
 
@@ -283,7 +313,7 @@ def main(argv: Optional[list] = None) -> int:
             check_resample_to(args.resample_to)
         except ValueError as exc:
             parser.error(f"--{exc}")
-    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps)):
+    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps), ("trim_db", check_trim_db)):
         if getattr(args, name) is not None:
             try:
                 check(getattr(args, name))
@@ -296,7 +326,7 @@ def main(argv: Optional[list] = None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
     vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak,
-                  args.resample_to, args.tempo, args.pitch_steps)
+                  args.resample_to, args.tempo, args.pitch_steps, args.trim_db)
     return 0
 
 
