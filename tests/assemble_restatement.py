@@ -73,8 +73,9 @@ def join_offsets(lens, pause):
 
 
 # ---- fp32, the header's order -------------------------------------------------------------------------------------------
-def block_sums_f32(y, H):
-    """``S[j]`` for the blocks that hold a sample: 256 accumulators over i = m, m + 256, ..., quads, then the 64-lane tree."""
+def block_sums_f32(y, H, passes=None):
+    """``S[j]`` for the blocks that hold a sample: 256 accumulators over i = m, m + 256, ..., quads, then the 64-lane tree.
+    ``passes``: a deviation (``MUTATIONS``), the accumulate loop stopped after that many steps of 256."""
     y = np.asarray(y, dtype=np.float32)
     n_blk = -(-len(y) // H)
     rows = -(-H // 256)
@@ -84,7 +85,7 @@ def block_sums_f32(y, H):
         x[j, :len(seg)] = seg
     x = x.reshape(n_blk, rows, 256)
     acc = np.zeros((n_blk, 256), dtype=np.float32)
-    for r in range(rows):
+    for r in range(rows if passes is None else min(rows, passes)):
         acc = acc + x[:, r] * x[:, r]
     v = ((acc[:, 0::4] + acc[:, 1::4]) + acc[:, 2::4]) + acc[:, 3::4]
     o = 32
@@ -94,8 +95,9 @@ def block_sums_f32(y, H):
     return v[:, 0]
 
 
-def mse_f32(y, F, H):
-    S, R, T = block_sums_f32(y, H), F // H, frames_of(len(y), H)
+def mse_f32(y, F, H, passes=None, blocks=None):
+    """``blocks``: a deviation (``MUTATIONS``), a frame's sum cut to its first ``blocks`` block sums."""
+    S, R, T = block_sums_f32(y, H, passes), F // H, frames_of(len(y), H)
 
     def blk(j):
         return S[j] if 0 <= j < len(S) else np.float32(0.0)
@@ -103,7 +105,7 @@ def mse_f32(y, F, H):
     out = np.zeros(T, dtype=np.float32)
     for t in range(T):
         s = blk(t - R // 2)
-        for j in range(t - R // 2 + 1, t + R // 2):
+        for j in range(t - R // 2 + 1, t - R // 2 + (R if blocks is None else min(R, blocks))):
             s = np.float32(s + blk(j))
         out[t] = s / np.float32(F)
     return out
@@ -141,3 +143,142 @@ def join_f32(items, spans, fade, pause, cap):
         seg = faded_f32(y, sp, fade)
         out[o:o + len(seg)] = seg
     return out, offs
+
+
+# ---- the three launches as the device runs them, with one named deviation ------------------------------------------------
+KGATHER_RUN = 4096               # csrc/assemble.h kGatherRun: output positions of a gather block
+
+MUTATIONS = {                    # each a wrong kernel a reviewer could plausibly write; None is the header's own
+    "scan_drops_wave_sums": "gather scan: the sums of the waves in front are left out of the off of the items that waves 1-3 own",
+    "scan_per_rounds_down": "gather scan: per = max(1, B / 256), so items past 256 per are owned by nobody (their off reads 0)",
+    "total_from_last_owner": "gather scan: off[B] is the wave-level inclusive sum of the last thread that owns an item, not the run behind thread 255",
+    "item_of_strict": "gather item_of: off[mid] < p for off[mid] <= p",
+    "item_of_first_of_run": "gather item_of: the first of a run of equal offsets is returned, not the last",
+    "bounds_first_256": "bounds: the frame loops make one pass (t < 256 only)",
+    "ref_max_first_256": "bounds: the item's own maximum is taken over t < 256 only",
+    "first_last_wave0": "bounds: first and last are taken from wave 0's candidates only (t mod 256 < 64)",
+    "frame_sum_one_run": "energy: a frame adds min(R, kRunFrames) block sums, not R",
+    "accumulate_8_passes": "energy: a block's accumulate loop stops after 8 steps of 256 (2048 samples)",
+    "ramp_block_local": "gather sample: the ramps are looked up at the position inside the gather block's part of the item",
+}
+
+
+def energies_dev(items, F, H, mutation=None):
+    """``energy_kernel``: mse per item, fp32."""
+    passes = 8 if mutation == "accumulate_8_passes" else None
+    blocks = KRUN_FRAMES if mutation == "frame_sum_one_run" else None
+    return [mse_f32(y, F, H, passes=passes, blocks=blocks) for y in items]
+
+
+def bounds_dev(mse, lens, H, top_db, ref, pad, mutation=None):
+    """``bounds_kernel``: ``(start', end')`` per item.  Thread ``tid`` of 256 looks at t = tid, tid + 256, ...; wave w holds the
+    frames with ``t mod 256`` in [64 w, 64 w + 64)."""
+    amin, k, spans = np.float32(AMIN), k_of(top_db), []
+    for m, Lb in zip(mse, lens):
+        T = frames_of(Lb, H)
+        assert len(m) == T
+        seen = min(T, 256) if mutation == "bounds_first_256" else T
+        if ref is None:
+            ref_b = np.max(m[:min(T, 256) if mutation in ("bounds_first_256", "ref_max_first_256") else T], initial=np.float32(0.0))
+        else:
+            ref_b = np.float32(ref) * np.float32(ref)
+        thr = np.float32(np.maximum(ref_b, amin) * k)
+        loud = np.maximum(m, amin) > thr
+        loud[seen:] = False
+        if mutation == "first_last_wave0":
+            loud &= np.arange(T) % 256 < 64
+        idx = np.flatnonzero(loud)
+        start = end = 0
+        if idx.size:
+            start, end = int(idx[0]) * H, min(Lb, (int(idx[-1]) + 1) * H)
+        spans.append((max(0, start - pad), min(Lb, end + pad)))
+    return spans
+
+
+def scan_dev(lens, pause, mutation=None):
+    """The gather's scan of ``w_b = len_b + (len_b > 0 ? pause : 0)`` into ``off[0 .. B]``: 256 threads own ``per`` items each, an
+    inclusive scan inside each wave of 64, the sums of the waves in front added, ``off[B]`` the run behind thread 255.  A word
+    no thread stores reads as 0 here (on the device it is whatever the LDS held)."""
+    B = len(lens)
+    w = [int(n) + (pause if n else 0) for n in lens]
+    per = max(1, B // 256) if mutation == "scan_per_rounds_down" else (B + 255) // 256
+    lo = [min(t * per, B) for t in range(256)]
+    hi = [min(lo[t] + per, B) for t in range(256)]
+    mine = [sum(w[lo[t]:hi[t]]) for t in range(256)]
+    incl = [sum(mine[t - t % 64:t + 1]) for t in range(256)]
+    wave_sum = [incl[64 * v + 63] for v in range(4)]
+    off = [0] * (B + 1)
+    for t in range(256):
+        run = incl[t] - mine[t] + sum(wave_sum[:t // 64])
+        lost = sum(wave_sum[:t // 64]) if mutation == "scan_drops_wave_sums" else 0     # from the items' off, not from the total
+        for i in range(lo[t], hi[t]):
+            off[i] = run - lost
+            run += w[i]
+        if t == 255:
+            off[B] = run
+    if mutation == "total_from_last_owner":
+        off[B] = incl[max(t for t in range(256) if lo[t] < hi[t])] if B else 0
+    return off
+
+
+def gather_dev(wav, spans, off, fade, pause, cap, mutation=None):
+    """``gather_kernel``, the join form: ``(out [cap] fp32, offsets [B + 1])``.  A group of four positions takes its first
+    position's item where the whole group lies in front of the next item's start, and searches per position otherwise."""
+    B = len(spans)
+    off = np.asarray(off, dtype=np.int64)
+    start = np.array([s for s, _ in spans], dtype=np.int64)
+    length = np.array([e - s for s, e in spans], dtype=np.int64)
+    ramp = ramp_of(fade) if fade else np.ones(1, dtype=np.float32)
+
+    def item_of(p):
+        lo, hi = np.zeros(len(p), dtype=np.int64), np.full(len(p), B, dtype=np.int64)
+        while np.any(hi - lo > 1):
+            go = hi - lo > 1
+            mid = (lo + hi) >> 1
+            left = off[mid] < p if mutation == "item_of_strict" else off[mid] <= p
+            lo, hi = np.where(go & left, mid, lo), np.where(go & ~left, mid, hi)
+        if mutation == "item_of_first_of_run":
+            while True:
+                back = (lo > 0) & (off[np.maximum(lo - 1, 0)] == off[lo])
+                if not back.any():
+                    break
+                lo = lo - back
+        return lo
+
+    p = np.arange(cap, dtype=np.int64)
+    first = item_of(p - p % 4)                                       # the group's own search
+    nxt = np.where(first == B - 1, np.int64(0xffffffff), off[np.minimum(first + 1, B)])
+    b = np.where(p - p % 4 + 3 < nxt, first, item_of(p))
+    at, n = off[b], p - off[b]
+    inside = (n >= 0) & (n < length[b])                               # unsigned on the device: a negative n is far past len
+    n_in = np.where(inside, n, 0)
+    back = length[b] - 1 - n_in
+    n_up, n_down = n_in, back
+    if mutation == "ramp_block_local":
+        blk = p - p % KGATHER_RUN
+        n_up = p - np.maximum(at, blk)
+        n_down = np.minimum(at + length[b], blk + KGATHER_RUN) - 1 - p
+    up = np.where(n_up < fade, ramp[np.clip(n_up, 0, len(ramp) - 1)], np.float32(1.0)).astype(np.float32)
+    down = np.where(n_down < fade, ramp[np.clip(n_down, 0, len(ramp) - 1)], np.float32(1.0)).astype(np.float32)
+    src = np.asarray(wav, dtype=np.float32)[b, np.where(inside, start[b] + n_in, 0)] if wav.shape[1] else np.zeros(cap, np.float32)
+    out = np.where(inside, (src * up) * down, np.float32(0.0)).astype(np.float32)
+    total = int(off[B]) - (pause if off[B] else 0)
+    return out, [int(v) for v in off[:B]] + [total]
+
+
+STAGE_OF = {"frame_sum_one_run": 0, "accumulate_8_passes": 0, "bounds_first_256": 1, "ref_max_first_256": 1, "first_last_wave0": 1,
+            "scan_drops_wave_sums": 2, "scan_per_rounds_down": 2, "total_from_last_owner": 2, "item_of_strict": 3,
+            "item_of_first_of_run": 3, "ramp_block_local": 3}
+
+
+def device_f32(items, wav, F, H, top_db, ref, pad, fade, pause, cap, mutation=None, clean=None):
+    """The three launches on a batch: ``dict(mse32, spans, offsets, out)``.  ``mutation``: a key of ``MUTATIONS``.  ``clean``: the
+    result without a deviation, whose stages in front of the deviating one are taken over instead of being computed again."""
+    assert mutation is None or mutation in MUTATIONS
+    stage = STAGE_OF.get(mutation, 0)
+    lens = [len(y) for y in items]
+    mse = clean["mse32"] if clean and stage > 0 else energies_dev(items, F, H, mutation)
+    spans = clean["spans"] if clean and stage > 1 else bounds_dev(mse, lens, H, top_db, ref, pad, mutation)
+    off = clean["off"] if clean and stage > 2 else scan_dev([e - s for s, e in spans], pause, mutation)
+    out, offsets = gather_dev(wav, spans, off, fade, pause, cap, mutation)
+    return dict(mse32=mse, spans=spans, off=off, offsets=offsets, out=out)

@@ -24,7 +24,9 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 NAN = float("nan")
-CASE_IDS = [C.case_id(c) for c in C.CASES]
+ALL_CASES = C.CASES + C.WIDE_CASES
+CASE_IDS = [C.case_id(c) for c in ALL_CASES]
+WIDE = {c["name"] for c in C.WIDE_CASES}
 GUARD = 256                       # bytes behind the workspace's stated size that must stay as they were
 SENTINEL = -77
 TOO_SMALL = 5                     # IRIS_HIFIGAN_WORKSPACE_TOO_SMALL
@@ -68,7 +70,27 @@ def poisoned(c) -> dict:
     return _state[c["name"]]
 
 
-@pytest.mark.parametrize("c", C.CASES, ids=CASE_IDS)
+def batch_of_one_items(c):
+    """The items compared with their batch-of-one calls: all of them in the first list; in a wide case at most 16 -- the first
+    and the last, then the scan's thread and wave edges, then the neighbours of the long runs of empty items."""
+    B = len(c["items"])
+    if c["name"] not in WIDE or B <= 16:
+        return list(range(B))
+    lens = [len(y) for y in c["items"]]
+    want = [0, B - 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025]
+    for lo, hi in C.empty_runs(lens):
+        if hi - lo >= 40:
+            want += [lo - 1, hi]
+    for lo, hi in C.empty_runs(lens):
+        want += [lo - 1, hi]
+    picked = []
+    for b in want:
+        if 0 <= b < B and lens[b] and b not in picked:
+            picked.append(b)
+    return picked[:16]
+
+
+@pytest.mark.parametrize("c", ALL_CASES, ids=CASE_IDS)
 def test_bounds_energies_and_samples_match_the_restatements(c):
     got, ref, a = poisoned(c), C.reference(c), model(c)
     B, L = len(c["items"]), c["L"]
@@ -92,7 +114,7 @@ def test_bounds_energies_and_samples_match_the_restatements(c):
     assert (ws[~touched] == 0xFF).all()                                                                     # row rests, padding, the guard
 
 
-@pytest.mark.parametrize("c", C.CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("c", ALL_CASES, ids=CASE_IDS)
 def test_unpoisoned_call_repeats_and_items_are_their_batch_of_one_calls(c):
     got, a = poisoned(c), model(c)
     wav, lengths, row_scale = C.batch(c)
@@ -102,7 +124,8 @@ def test_unpoisoned_call_repeats_and_items_are_their_batch_of_one_calls(c):
     for x, y, z in zip(first, second, (got["out"], got["offsets"], got["spans"])):
         assert torch.equal(x, y) and torch.equal(x.view(torch.int32), z.view(torch.int32))                 # NaN tails change nothing
     offs = got["offsets"].cpu().tolist()
-    for b, y in enumerate(c["items"]):
+    for b in batch_of_one_items(c):
+        y = c["items"][b]
         if len(y) == 0:
             continue
         one, one_offs, one_span = a.join_device(y[None].copy())
@@ -113,7 +136,7 @@ def test_unpoisoned_call_repeats_and_items_are_their_batch_of_one_calls(c):
     assert trimmed.shape == (offs[-1],) and torch.equal(trimmed, got["out"][:offs[-1]]) and torch.equal(total_spans, got["spans"])
 
 
-@pytest.mark.parametrize("c", C.CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("c", ALL_CASES, ids=CASE_IDS)
 def test_trim_rows_are_the_joins_slices(c):
     a = model(c)
     wav, lengths, row_scale = C.batch(c, fill=NAN)
@@ -122,9 +145,45 @@ def test_trim_rows_are_the_joins_slices(c):
     got = poisoned(c)
     spans, offs = got["spans"].cpu().numpy(), got["offsets"].cpu().tolist()
     assert rows.shape == (B, L) and torch.equal(counts.cpu(), torch.from_numpy(spans[:, 1] - spans[:, 0]))
+    rows, out = rows.cpu(), got["out"].cpu()                                                  # (one copy each, not one per item)
     for b in range(B):
         n = int(spans[b, 1] - spans[b, 0])
-        assert torch.equal(rows[b, :n], got["out"][offs[b]:offs[b] + n]) and not rows[b, n:].any()
+        assert torch.equal(rows[b, :n], out[offs[b]:offs[b] + n]) and not rows[b, n:].any()
+
+
+@pytest.mark.parametrize("name", ["gather_seams", "batch_257"])
+def test_out_off_a_16_byte_boundary(name):
+    """The gather stores 16 bytes at a time only where ``out`` lies on 16 bytes.  With ``out`` 4, 8 and 12 bytes past such an
+    address both output forms give the aligned call's bits, store all of ``out`` and leave the words around it alone."""
+    c = next(c for c in C.WIDE_CASES if c["name"] == name)
+    a, aligned = model(c), poisoned(c)
+    wav, lengths, row_scale = C.batch(c, fill=NAN)
+    B, L = wav.shape
+    need = a.workspace_bytes(B, L)
+    wav_d, len_d = torch.from_numpy(wav).to(DEV), torch.from_numpy(lengths).to(DEV)
+    rows_aligned, counts_aligned = a.trim_device(wav_d, lengths=len_d, row_scale=row_scale)
+    lib, guard, mark = _native.load(), 64, 0x5EEDBEEF
+    forms = ((lib.iris_assemble_forward, a.capacity(B, L), B + 1, aligned["out"], aligned["offsets"]),
+             (lib.iris_assemble_trim_ragged, B * L, B, rows_aligned.reshape(-1), counts_aligned))
+    for fn, cap, n_ints, want, want_ints in forms:
+        assert want.data_ptr() % 16 == 0 and want.numel() == cap
+        for shift in (1, 2, 3):
+            buf = torch.full((guard + shift + cap + guard,), mark, dtype=torch.int32, device=DEV)
+            assert buf.data_ptr() % 16 == 0
+            out = buf[guard + shift:guard + shift + cap].view(torch.float32)
+            assert out.data_ptr() % 16 == 4 * shift
+            out.fill_(NAN)
+            ints = torch.full((n_ints,), SENTINEL, dtype=torch.int32, device=DEV)
+            spans = torch.full((B, 2), SENTINEL, dtype=torch.int32, device=DEV)
+            ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=DEV)
+            with torch.cuda.device(DEV):
+                _native.check(fn.__name__, fn(a._handle, ptr(wav_d), B, L, ptr(len_d), row_scale, ptr(out), ptr(spans), ptr(ints), ptr(ws),
+                                       ctypes.c_uint64(need), ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)))
+            torch.cuda.synchronize()
+            assert not torch.isnan(out).any()
+            assert torch.equal(out.view(torch.int32), want.view(torch.int32)), (fn.__name__, shift)
+            assert torch.equal(ints, want_ints) and torch.equal(spans, aligned["spans"])
+            assert (buf[:guard + shift] == mark).all() and (buf[guard + shift + cap:] == mark).all()
 
 
 def test_refusals_behind_the_handle():
