@@ -973,6 +973,57 @@ int32_t iris_assemble_trim_ragged(iris_assemble_handle* h, const float* wav_dev 
                                   int32_t* spans_out_dev /* [B][2] or NULL */, int32_t* counts_out_dev /* [B] */,
                                   void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- Loudness: ITU-R BS.1770-4 integrated loudness per item of a ragged batch, and the gain to a target (csrc/loudness.h) ----
+ * Mono fp32.  lengths_dev (may be NULL) and row_scale >= 1 as in iris_resampler_forward: item b owns L_b = min(L, lengths[b] *
+ * row_scale) samples; samples past that are never read (they may hold NaN).  The host never reads a length.  csrc/loudness.h
+ * states every rule and every order of summation; in short, all of it in fp64 with nothing contracted:
+ *     K-weighting: a high shelf and a high pass, derived for sample_rate on the host in double with K = tan(pi f0 / fs), as
+ *         libebur128 and pyloudnorm derive them (at 48000 the standard's table); state 0 at sample 0 of every item;
+ *     step = sample_rate / 10; block j covers filtered samples [j step, j step + 4 step); J_b = L_b >= 4 step ? (L_b - 4 step) /
+ *         step + 1 : 0; z_j = the block's mean square;
+ *     absolute gate z_j > 10^((-70 + 0.691) / 10); relative gate z_j > 0.1 * mean(z over the absolutely gated); ms_b = mean of
+ *         z_j over the blocks passing both (strict), 0 if none; integrated loudness = -0.691 + 10 log10(ms_b), the caller's to form;
+ *     g_b = sqrt(10^((target_lufs + 0.691) / 10) / ms_b), at most 10^(max_gain_db / 20) and, with peak_ceiling > 0, at most
+ *         peak_ceiling / max|y_b|; ms_b == 0 (too short, or nothing above the absolute gate): g_b = 1;
+ *     out[b, n] = wav[b, n] * (float)g_b for n < L_b, 0.0f behind L_b.
+ * normalize_ragged: wav_dev [B, L] -> out_dev [B, L], every element stored exactly once, without atomics; stats_out_dev [B][2]
+ * doubles = (ms_b, g_b).  4 launches.  measure_ragged: stats_out_dev only, no sample is stored; the first 3 of them.  Item b's
+ * results are those of its batch-of-one call, and two runs give the same bits.  Chaining: lengths and row_scale of the stage in
+ * front are those of the stage behind (iris_assemble_forward, iris_resampler_forward, iris_hifigan_op_pcm16).
+ * The recurrence is serial in time, so an item is cut into segments of 64 samples that run in parallel from state 0; their end
+ * states are scanned with powers of the 4 x 4 transition matrix, and every segment runs again from its true start state.
+ * After a call the workspace holds, each starting on 256 bytes: the segments' scanned end states [B][segs][4], their partial sums
+ * of squares [B][segs][2], the 100 ms sums [B][L / step + 1] (doubles) and the segments' peaks [B][segs] (fp32), segs = 128 *
+ * ceil(L / 8192); only what belongs to an item's own samples is written.  Asynchronous on `stream`, nothing allocated, safe in a
+ * stream capture.
+ * design: the handle's table of 144 doubles -- shelf (b0, b1, b2, a1, a2), high pass (b0, b1, b2, a1, a2), the absolute
+ * threshold, target_ms, the gain cap, peak_ceiling, two zeros, then A^(64 * 2^k) for k = 0 .. 7, row-major.  Host only.
+ * sample_rate outside 8000 .. 48000 or no multiple of 10, target_lufs outside -70 .. 0, max_gain_db outside 0 .. 120,
+ * peak_ceiling outside 0 .. 1, anything not finite, row_scale < 1, a negative shape, a NULL pointer, stats_out_dev or
+ * workspace_dev off 8 bytes and out_dev overlapping wav_dev return IRIS_HIFIGAN_INVALID_ARGUMENT; B > 65535 (grid.y) and B L
+ * above 2^31 - 1 IRIS_HIFIGAN_UNSUPPORTED; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches.
+ * B == 0 or L == 0: nothing to do, IRIS_HIFIGAN_OK. */
+typedef struct iris_loudness_config {
+    int32_t sample_rate;
+    float target_lufs;
+    float max_gain_db;          /* a cap on the boost */
+    float peak_ceiling;         /* amplitude in (0, 1]; 0: none */
+} iris_loudness_config;
+typedef struct iris_loudness_handle iris_loudness_handle;
+/* Host only (no device is needed); the launch count is a dry run of the call's own code (measure_only != 0: measure_ragged). */
+int32_t iris_loudness_design(const iris_loudness_config* cfg, double* out /* [n] */, uint64_t n /* 144 */);
+int32_t iris_loudness_workspace_bytes(const iris_loudness_config* cfg, int32_t B, int32_t L, uint64_t* bytes);
+int32_t iris_loudness_launch_count(const iris_loudness_config* cfg, int32_t B, int32_t L, int32_t measure_only, int32_t* n);
+/* create: on the current device, which becomes the handle's; it uploads the design table. */
+int32_t iris_loudness_create(const iris_loudness_config* cfg, iris_loudness_handle** out);
+int32_t iris_loudness_destroy(iris_loudness_handle* h);
+int32_t iris_loudness_normalize_ragged(iris_loudness_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                                       const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* out_dev /* [B, L] */,
+                                       double* stats_out_dev /* [B][2] */, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+int32_t iris_loudness_measure_ragged(iris_loudness_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                                     const int32_t* lengths_dev /* or NULL */, int32_t row_scale, double* stats_out_dev /* [B][2] */,
+                                     void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -363,6 +363,27 @@ ASSEMBLE_SYMBOLS = {
     "iris_assemble_trim_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
+
+class LoudnessConfig(ctypes.Structure):
+    """``iris_loudness_config``"""
+
+    _fields_ = [("sample_rate", ctypes.c_int32), ("target_lufs", ctypes.c_float), ("max_gain_db", ctypes.c_float),
+                ("peak_ceiling", ctypes.c_float)]
+
+
+# BS.1770 loudness and the gain to a target (iris.loudness): bound by load() like SYMBOLS
+LOUDNESS_DESIGN_DOUBLES = 144
+_ldc = _c.POINTER(LoudnessConfig)
+LOUDNESS_SYMBOLS = {
+    "iris_loudness_design": (_i32, [_ldc, _c.POINTER(_d), _u64]),
+    "iris_loudness_workspace_bytes": (_i32, [_ldc, _i32, _i32, _u64p]),
+    "iris_loudness_launch_count": (_i32, [_ldc, _i32, _i32, _i32, _ip]),
+    "iris_loudness_create": (_i32, [_ldc, _c.POINTER(_vp)]),
+    "iris_loudness_destroy": (_i32, [_vp]),
+    "iris_loudness_normalize_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_loudness_measure_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -389,7 +410,8 @@ def load() -> ctypes.CDLL:
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
-                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS}.items():
+                                      **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS,
+                                      **LOUDNESS_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -145,6 +145,26 @@ def check_trim_db(top_db) -> float:
     return db
 
 
+def check_lufs(target) -> float:
+    """``--lufs``: a finite target loudness in -70 .. 0 LUFS."""
+    lufs = float(target)
+    if not -70.0 <= lufs <= 0.0:                              # False for NaN too
+        raise ValueError(f"lufs must be a target loudness in -70 .. 0 LUFS, got {target}")
+    return lufs
+
+
+def level_to_lufs(audio: np.ndarray, target_lufs: float, sample_rate: int = 22050, peak_ceiling: Optional[float] = 1.0) -> np.ndarray:
+    """A float waveform ``[n]`` at ``target_lufs`` integrated loudness (ITU-R BS.1770-4, measured and applied on the device,
+    ``iris.loudness``); the gain stops where the sample peak would pass ``peak_ceiling``.  A waveform shorter than 400 ms, or
+    with nothing above -70 LUFS, is returned as it is."""
+    from .loudness import LoudnessNormalizer
+    audio = to_mono_float32(audio)
+    if len(audio) == 0:
+        return audio
+    stage = LoudnessNormalizer(sample_rate, check_lufs(target_lufs), peak_ceiling=peak_ceiling)
+    return stage.normalize_device(audio[None])[0][0].cpu().numpy()
+
+
 def trim_silence(audio: np.ndarray, top_db: float, frame_length: int = 2048, hop_length: int = 512) -> np.ndarray:
     """A float waveform ``[n]`` without its leading and trailing silence: ``librosa.effects.trim(audio, top_db=)``'s decision on
     the device (``iris.assemble``)."""
@@ -223,7 +243,7 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
                   sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None,
                   resample_to: Optional[int] = None, tempo: Optional[float] = None, pitch_steps: Optional[float] = None,
-                  trim_db: Optional[float] = None) -> np.ndarray:
+                  trim_db: Optional[float] = None, lufs: Optional[float] = None) -> np.ndarray:
     """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
     int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
     ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
@@ -235,7 +255,11 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
     ``tempo`` / ``pitch_steps``: the entry's float waveform goes through ``tempo_and_pitch`` (the device phase vocoder) before
     it is normalised and written; an entry that returns 16-bit PCM is refused (``ValueError``), the stage takes fp32.
     ``trim_db``: the entry's float waveform loses its leading and trailing silence first (``trim_silence``); an entry that
-    returns 16-bit PCM is refused in the same way."""
+    returns 16-bit PCM is refused in the same way.
+    ``lufs``: the float waveform -- behind the tempo and pitch stage, in front of ``normalize_peak`` -- is brought to this
+    integrated loudness (``level_to_lufs``, at ``resample_to`` where that is given); 16-bit PCM is refused in the same way."""
+    if lufs is not None:
+        check_lufs(lufs)
     if trim_db is not None:
         check_trim_db(trim_db)
     if tempo is not None:
@@ -247,6 +271,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
         raise ValueError("tempo / pitch_steps take the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     if trim_db is not None and getattr(fn, "returns_pcm16", False):
         raise ValueError("trim_db takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
+    if lufs is not None and getattr(fn, "returns_pcm16", False):
+        raise ValueError("lufs takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
     if normalize_peak is not None:
@@ -271,6 +297,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
             audio = trim_silence(audio, trim_db)
         if tempo is not None or pitch_steps is not None:
             audio = tempo_and_pitch(audio, tempo, pitch_steps, hop_length=hop_length)
+        if lufs is not None:
+            audio = level_to_lufs(audio, lufs, wav_rate)
         if normalize_peak is not None:
             audio = pcm16_from_float(audio, normalize=True, peak_target=normalize_peak)
     logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / wav_rate:.2f}s")
@@ -300,6 +328,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--trim_db", type=float, default=None, metavar="DB",
                         help="cut leading and trailing silence more than DB below the loudest frame (librosa.effects.trim's "
                              "decision on the GPU, iris.assemble), before the other output options")
+    parser.add_argument("--lufs", type=float, default=None, metavar="TARGET",
+                        help="bring the waveform to TARGET LUFS integrated loudness (-70 .. 0; ITU-R BS.1770-4 on the GPU, "
+                             "iris.loudness), behind --trim_db / --tempo / --pitch_steps")
     return parser
 
 
@@ -313,7 +344,7 @@ def main(argv: Optional[list] = None) -> int:
             check_resample_to(args.resample_to)
         except ValueError as exc:
             parser.error(f"--{exc}")
-    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps), ("trim_db", check_trim_db)):
+    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps), ("trim_db", check_trim_db), ("lufs", check_lufs)):
         if getattr(args, name) is not None:
             try:
                 check(getattr(args, name))
@@ -326,7 +357,7 @@ def main(argv: Optional[list] = None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
     vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak,
-                  args.resample_to, args.tempo, args.pitch_steps, args.trim_db)
+                  args.resample_to, args.tempo, args.pitch_steps, args.trim_db, args.lufs)
     return 0
 
 
