@@ -1024,6 +1024,52 @@ int32_t iris_loudness_measure_ragged(iris_loudness_handle* h, const float* wav_d
                                      const int32_t* lengths_dev /* or NULL */, int32_t row_scale, double* stats_out_dev /* [B][2] */,
                                      void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- Limiter: a look-ahead true-peak ceiling per item of a ragged batch, without turning the item down (csrc/limiter.h) ----
+ * Mono fp32.  lengths_dev (may be NULL) and row_scale >= 1 as in iris_loudness_normalize_ragged: item b owns L_b = min(L,
+ * lengths[b] * row_scale) samples; samples past that are never read (they may hold NaN); x[n] = 0 outside [0, L_b).  The host
+ * never reads a length.  csrc/limiter.h states every rule; in short, with ceiling c and lookahead A, all of it in fp32 with
+ * nothing contracted except the fmaf named here, and the one division in fp64:
+ *     u[n, q], q = 1, 2, 3 = the chain over j = 0 .. 11 ascending of acc = fmaf(x[n - 5 + j], bank[q][j], acc), acc = 0.0f, with
+ *         bank the Kaiser-windowed sinc of iris_resampler_* for 1 : 4 with 6 zeros and its default beta and rolloff: the three
+ *         points between sample n and n + 1;
+ *     p[n] = max(|x[n]|, |u[n-1, 1..3]|, |u[n, 1..3]|); tp_b = max p[n] over n < L_b, 0 for an empty item;
+ *     r[n] = p[n] > c ? (float)((double)c / (double)p[n]) : 1.0f inside [0, L_b), 1.0f outside;
+ *     m[n] = min r[n + k] over |k| <= A; d[n] = 1.0f - m[n];
+ *     s[n] = the chain over j = -A .. A ascending of acc = fmaf(d[n + j], w[j], acc), acc = 0.0f, w a Hann shape 0.5 (1 + cos(pi
+ *         j / (A + 1))) normalised to sum 1 in double and rounded to fp32 upward, so that the table's sum is never under 1 and
+ *         g[n] <= r[n] in exact arithmetic; g[n] = 1.0f - s[n], exactly 1 where nothing within 2A samples exceeds c;
+ *     out[b, n] = fminf(fmaxf(x[n] * g[n], -c), c) for n < L_b, 0.0f behind L_b: |out| <= c always.
+ * forward_ragged: wav_dev [B, L] -> out_dev [B, L], every element stored exactly once, without atomics; stats_out_dev [B][2]
+ * floats = (tp_b, min g[n] over n < L_b), (0, 1) for an empty item.  2 launches: one fused kernel over tiles of 2048 samples
+ * that stages x with a halo of 2A + 7 per side in LDS, and the reduction of the tiles' (max p, min g) per item.  measure_ragged:
+ * the same two, the same stats, and no sample is stored.  Item b's results are those of its batch-of-one call, and two runs give
+ * the same bits.  Chaining: lengths and row_scale of the stage in front are those of the stage behind.
+ * After a call the workspace holds the tiles' partials [B][ceil(L / 2048)][2] (fp32); only an item's own tiles, the first
+ * ceil(L_b / 2048), are written.  Asynchronous on `stream`, nothing allocated, safe in a stream capture.
+ * design: the handle's table of 36 + 2A + 1 floats -- bank[1..3][0..11], then w[-A .. A].  Host only.
+ * ceiling outside (0, 1] or not finite, lookahead outside 1 .. 256, row_scale < 1, a negative shape, a NULL pointer,
+ * stats_out_dev off 4 bytes, workspace_dev off 8 bytes and out_dev overlapping wav_dev return IRIS_HIFIGAN_INVALID_ARGUMENT;
+ * B > 65535 (grid.y) and B L above 2^31 - 1 IRIS_HIFIGAN_UNSUPPORTED; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No
+ * failing call launches.  B == 0 or L == 0: nothing to do, IRIS_HIFIGAN_OK. */
+typedef struct iris_limiter_config {
+    float ceiling;              /* amplitude in (0, 1] */
+    int32_t lookahead;          /* samples, 1 .. 256 */
+} iris_limiter_config;
+typedef struct iris_limiter_handle iris_limiter_handle;
+/* Host only (no device is needed); the launch count is a dry run of the call's own code (measure_only != 0: measure_ragged). */
+int32_t iris_limiter_design(const iris_limiter_config* cfg, float* out /* [n] */, uint64_t n /* 36 + 2 * lookahead + 1 */);
+int32_t iris_limiter_workspace_bytes(const iris_limiter_config* cfg, int32_t B, int32_t L, uint64_t* bytes);
+int32_t iris_limiter_launch_count(const iris_limiter_config* cfg, int32_t B, int32_t L, int32_t measure_only, int32_t* n);
+/* create: on the current device, which becomes the handle's; it uploads the design table. */
+int32_t iris_limiter_create(const iris_limiter_config* cfg, iris_limiter_handle** out);
+int32_t iris_limiter_destroy(iris_limiter_handle* h);
+int32_t iris_limiter_forward_ragged(iris_limiter_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                                    const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* out_dev /* [B, L] */,
+                                    float* stats_out_dev /* [B][2] */, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+int32_t iris_limiter_measure_ragged(iris_limiter_handle* h, const float* wav_dev /* [B, L] */, int32_t B, int32_t L,
+                                    const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* stats_out_dev /* [B][2] */,
+                                    void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -384,6 +384,27 @@ LOUDNESS_SYMBOLS = {
     "iris_loudness_measure_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
 }
 
+
+
+class LimiterConfig(ctypes.Structure):
+    """``iris_limiter_config``"""
+
+    _fields_ = [("ceiling", ctypes.c_float), ("lookahead", ctypes.c_int32)]
+
+
+# the look-ahead true-peak limiter (iris.limiter): bound by load() like SYMBOLS
+LIMITER_BANK_FLOATS = 36
+_lmc = _c.POINTER(LimiterConfig)
+LIMITER_SYMBOLS = {
+    "iris_limiter_design": (_i32, [_lmc, _fp, _u64]),
+    "iris_limiter_workspace_bytes": (_i32, [_lmc, _i32, _i32, _u64p]),
+    "iris_limiter_launch_count": (_i32, [_lmc, _i32, _i32, _i32, _ip]),
+    "iris_limiter_create": (_i32, [_lmc, _c.POINTER(_vp)]),
+    "iris_limiter_destroy": (_i32, [_vp]),
+    "iris_limiter_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "iris_limiter_measure_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -411,7 +432,7 @@ def load() -> ctypes.CDLL:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
                                       **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS,
-                                      **LOUDNESS_SYMBOLS}.items():
+                                      **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -18,8 +18,10 @@ The device never takes a logarithm.  A call is 4 launches on the current stream 
 an item's result is that of its batch-of-one call, and two calls agree bit for bit.
 
 ``MelToWavePipeline(..., loudness=LoudnessNormalizer(...))`` levels every sentence behind the denoiser and the stretch and in
-front of the join and the output stage.  Not built: a pooled gain over the whole batch, true-peak (oversampled) limiting,
-short-term / momentary loudness or loudness range, and a chunked form -- the measure is the whole item's.
+front of the join and the output stage.  ``peak_ceiling`` guards the sample peak by turning the whole item down; a true-peak
+(oversampled) ceiling that leaves the item at its target is the stage behind this one, ``iris.limiter.Limiter``
+(``MelToWavePipeline(..., loudness=LoudnessNormalizer(peak_ceiling=None), limiter=Limiter(...))``).  Not built: a pooled gain over
+the whole batch, short-term / momentary loudness or loudness range, and a chunked form -- the measure is the whole item's.
 """
 from __future__ import annotations
 

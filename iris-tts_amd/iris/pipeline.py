@@ -92,17 +92,26 @@ class MelToWavePipeline:
     each sentence is levelled, then trimmed, faded and joined -- and of ``pcm16=`` / ``normalize=`` / ``resampler=``, which
     run as stand-alone launches as for a denoiser.  The lengths are the ones the stage in front handed on (the batch's frames
     and the hop, or the stretch's device ``counts``).  ``stream`` and ``session`` refuse (``ValueError``): the measure is the
-    whole item's, and no chunked form is built.  With ``loudness=None`` nothing changes."""
+    whole item's, and no chunked form is built.  With ``loudness=None`` nothing changes.
+
+    ``limiter``: an ``iris.limiter.Limiter`` (or any object with ``limit_device(wav [B, L], lengths=, row_scale=) -> (out [B, L],
+    stats [B, 2])``), or None.  With one, the same routes hold every item under the limiter's true-peak ceiling by a look-ahead
+    gain that falls only around a peak -- so a ``LoudnessNormalizer(peak_ceiling=None)`` in front reaches its target -- behind
+    ``loudness=`` and in front of ``assemble=`` and of ``pcm16=`` / ``normalize=`` / ``resampler=``, which run as stand-alone
+    launches as for a denoiser.  It is handed the lengths and ``row_scale`` the stage in front passed on.  ``stream`` and
+    ``session`` refuse (``ValueError``): the gain looks ``2A + 7`` samples past a chunk's end, and no chunked form is built.  With
+    ``limiter=None`` nothing changes."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
                  group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None,
-                 denoiser=None, stretch=None, assemble=None, loudness=None):
+                 denoiser=None, stretch=None, assemble=None, loudness=None, limiter=None):
         self.postnet = postnet
         self.denoiser = denoiser
         self.stretch = stretch
         self.assemble = assemble
         self.loudness = loudness
+        self.limiter = limiter
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
@@ -198,6 +207,9 @@ class MelToWavePipeline:
         if self.loudness is not None:
             raise ValueError("a pipeline with loudness= cannot be streamed: the integrated loudness is the whole item's "
                              "measure, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
+        if self.limiter is not None:
+            raise ValueError("a pipeline with limiter= cannot be streamed: the gain at a sample looks 2 * lookahead + 7 samples "
+                             "past it, across a chunk's end, and no chunked form is built; use infer / infer_batch")
         if self.stretch is not None and not self._chunked_stretch:
             raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
                              "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
@@ -240,6 +252,13 @@ class MelToWavePipeline:
             return wav
         return self.loudness.normalize_device(wav.float(), lengths=lengths, row_scale=row_scale)[0]
 
+    def _limit(self, wav: torch.Tensor, lengths=None, row_scale: int = 1) -> torch.Tensor:
+        """The waveform through the limiter, if there is one, with the lengths ``_level`` was handed: every item under the
+        ceiling and 0 behind its own samples.  Nothing is read back."""
+        if self.limiter is None:
+            return wav
+        return self.limiter.limit_device(wav.float(), lengths=lengths, row_scale=row_scale)[0]
+
     def _stretch_ragged(self, wav: torch.Tensor, rows: Sequence[int], pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
         """A batch whose item i owns ``hop * rows[i]`` samples through ONE ragged stretch, then the output stage with the
         stretch's ``counts`` as sample lengths.  The host knows the counts from ``out_samples``: nothing synchronises."""
@@ -250,7 +269,7 @@ class MelToWavePipeline:
         if wav.shape[1] % sh:                                        # the padded row itself; its tail belongs to no item
             wav = torch.nn.functional.pad(wav, (0, sh - wav.shape[1] % sh))
         out, counts = self.stretch.forward_device(wav, lengths=[hop * r // sh for r in rows])
-        out = self._level(out, counts, 1)
+        out = self._limit(self._level(out, counts, 1), counts, 1)
         if self.assemble is not None:
             return self._joined_output_stage(out, counts, 1, pcm16, normalize, resampler)
         return self._ragged_output_stage(out, counts, pcm16, normalize, resampler, hop=1,
@@ -319,14 +338,14 @@ class MelToWavePipeline:
         result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
-        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None:
+        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None or self.limiter is not None:
             mel = self.refine(mel)
             wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
             if self.denoiser is not None:
                 wav = self._denoise(wav)
             if self.stretch is not None:
                 wav = self.stretch.forward_device(wav.float())[0]
-            wav = self._level(wav)
+            wav = self._limit(self._level(wav))
             if self.assemble is not None:
                 return self._joined_output_stage(wav, None, 1, pcm16, normalize, resampler)
             return self._output_stage(wav, pcm16, normalize, resampler)
@@ -575,7 +594,7 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None:
+        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None or self.limiter is not None:
             frames = [int(t) for t in lengths]
             if ragged_whole:
                 rows = [max(t - 1, 0) for t in frames]
@@ -590,7 +609,7 @@ class MelToWavePipeline:
                 wav = self._denoise(wav, rows)
             if self.stretch is not None:
                 return self._stretch_ragged(wav.float(), rows, pcm16, normalize, resampler)
-            wav = self._level(wav, rows, self.streamer.hop_length)
+            wav = self._limit(self._level(wav, rows, self.streamer.hop_length), rows, self.streamer.hop_length)
             if self.assemble is not None:
                 return self._joined_output_stage(wav, rows, self.streamer.hop_length, pcm16, normalize, resampler)
             return self._ragged_output_stage(wav, rows, pcm16, normalize, resampler)

@@ -165,6 +165,29 @@ def level_to_lufs(audio: np.ndarray, target_lufs: float, sample_rate: int = 2205
     return stage.normalize_device(audio[None])[0][0].cpu().numpy()
 
 
+LIMIT_DBTP_RANGE = (-20.0, 0.0)         # true-peak ceilings the command line takes
+
+
+def check_limit_dbtp(ceiling) -> float:
+    """``--limit_dbtp``: a finite true-peak ceiling in -20 .. 0 dBTP."""
+    db = float(ceiling)
+    if not LIMIT_DBTP_RANGE[0] <= db <= LIMIT_DBTP_RANGE[1]:  # False for NaN too
+        raise ValueError(f"limit_dbtp must be a true-peak ceiling in -20 .. 0 dBTP, got {ceiling}")
+    return db
+
+
+def limit_true_peak(audio: np.ndarray, ceiling_dbtp: float, sample_rate: int = 22050) -> np.ndarray:
+    """A float waveform ``[n]`` held under ``ceiling_dbtp`` by the device look-ahead limiter (``iris.limiter``, 1.5 ms of
+    lookahead, at most its 256 samples): the gain falls only around a peak, and a waveform under the ceiling is returned bit
+    for bit."""
+    from .limiter import MAX_LOOKAHEAD, Limiter
+    audio = to_mono_float32(audio)
+    if len(audio) == 0:
+        return audio
+    ms = min(1.5, 1000.0 * MAX_LOOKAHEAD / float(sample_rate))
+    return Limiter(sample_rate, check_limit_dbtp(ceiling_dbtp), ms).limit_device(audio[None])[0][0].cpu().numpy()
+
+
 def trim_silence(audio: np.ndarray, top_db: float, frame_length: int = 2048, hop_length: int = 512) -> np.ndarray:
     """A float waveform ``[n]`` without its leading and trailing silence: ``librosa.effects.trim(audio, top_db=)``'s decision on
     the device (``iris.assemble``)."""
@@ -243,7 +266,7 @@ def write_wav(path: Union[str, Path], audio: np.ndarray, sample_rate: int = 2205
 def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: str = DEFAULT_VOCODER_ENTRY,
                   sample_rate: int = 22050, hop_length: int = 256, normalize_peak: Optional[float] = None,
                   resample_to: Optional[int] = None, tempo: Optional[float] = None, pitch_steps: Optional[float] = None,
-                  trim_db: Optional[float] = None, lufs: Optional[float] = None) -> np.ndarray:
+                  trim_db: Optional[float] = None, lufs: Optional[float] = None, limit_dbtp: Optional[float] = None) -> np.ndarray:
     """mel ``[1, n_mels, T]`` or ``[n_mels, T]`` -> waveform written to ``output_wav``; returns the samples: float32, or
     int16 when the entry returned 16-bit PCM (``PCM16_VOCODER_ENTRY``), which is kept and written as it is.
     ``normalize_peak``: scale the utterance so that its peak is this value in (0, 1] -- the entry is then called with
@@ -257,9 +280,14 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
     ``trim_db``: the entry's float waveform loses its leading and trailing silence first (``trim_silence``); an entry that
     returns 16-bit PCM is refused in the same way.
     ``lufs``: the float waveform -- behind the tempo and pitch stage, in front of ``normalize_peak`` -- is brought to this
-    integrated loudness (``level_to_lufs``, at ``resample_to`` where that is given); 16-bit PCM is refused in the same way."""
+    integrated loudness (``level_to_lufs``, at ``resample_to`` where that is given); 16-bit PCM is refused in the same way.
+    ``limit_dbtp``: behind ``lufs``, the float waveform is held under this true-peak ceiling by the look-ahead limiter
+    (``limit_true_peak``); ``level_to_lufs`` then runs with no peak ceiling of its own, so the target is reached.  16-bit PCM
+    is refused in the same way."""
     if lufs is not None:
         check_lufs(lufs)
+    if limit_dbtp is not None:
+        check_limit_dbtp(limit_dbtp)
     if trim_db is not None:
         check_trim_db(trim_db)
     if tempo is not None:
@@ -273,6 +301,8 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
         raise ValueError("trim_db takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     if lufs is not None and getattr(fn, "returns_pcm16", False):
         raise ValueError("lufs takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
+    if limit_dbtp is not None and getattr(fn, "returns_pcm16", False):
+        raise ValueError("limit_dbtp takes the vocoder's float waveform: use an entry that returns float32 (not --pcm16)")
     mel = np.array(mel)
     logger.info(f"Using vocoder entry {vocoder_entry} ...")
     if normalize_peak is not None:
@@ -298,7 +328,9 @@ def vocode_to_wav(mel: np.ndarray, output_wav: Union[str, Path], vocoder_entry: 
         if tempo is not None or pitch_steps is not None:
             audio = tempo_and_pitch(audio, tempo, pitch_steps, hop_length=hop_length)
         if lufs is not None:
-            audio = level_to_lufs(audio, lufs, wav_rate)
+            audio = level_to_lufs(audio, lufs, wav_rate) if limit_dbtp is None else level_to_lufs(audio, lufs, wav_rate, peak_ceiling=None)
+        if limit_dbtp is not None:
+            audio = limit_true_peak(audio, limit_dbtp, wav_rate)
         if normalize_peak is not None:
             audio = pcm16_from_float(audio, normalize=True, peak_target=normalize_peak)
     logger.info(f"Generated audio: {audio.shape}, duration={len(audio) / wav_rate:.2f}s")
@@ -331,6 +363,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--lufs", type=float, default=None, metavar="TARGET",
                         help="bring the waveform to TARGET LUFS integrated loudness (-70 .. 0; ITU-R BS.1770-4 on the GPU, "
                              "iris.loudness), behind --trim_db / --tempo / --pitch_steps")
+    parser.add_argument("--limit_dbtp", type=float, default=None, metavar="DB",
+                        help="hold the waveform under a true-peak ceiling of DB dBTP (-20 .. 0; the look-ahead limiter on the GPU, "
+                             "iris.limiter), behind --lufs, which then reaches its target instead of stopping at the sample peak")
     return parser
 
 
@@ -344,7 +379,8 @@ def main(argv: Optional[list] = None) -> int:
             check_resample_to(args.resample_to)
         except ValueError as exc:
             parser.error(f"--{exc}")
-    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps), ("trim_db", check_trim_db), ("lufs", check_lufs)):
+    for name, check in (("tempo", check_tempo), ("pitch_steps", check_pitch_steps), ("trim_db", check_trim_db), ("lufs", check_lufs),
+                        ("limit_dbtp", check_limit_dbtp)):
         if getattr(args, name) is not None:
             try:
                 check(getattr(args, name))
@@ -357,7 +393,7 @@ def main(argv: Optional[list] = None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     mel = np.load(args.mel, allow_pickle=False)
     vocode_to_wav(mel, args.output_wav, args.vocoder_entry, args.sample_rate, args.hop_length, args.normalize_peak,
-                  args.resample_to, args.tempo, args.pitch_steps, args.trim_db, args.lufs)
+                  args.resample_to, args.tempo, args.pitch_steps, args.trim_db, args.lufs, args.limit_dbtp)
     return 0
 
 
