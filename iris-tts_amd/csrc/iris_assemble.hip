@@ -7,7 +7,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #include "assemble.h"
@@ -95,24 +94,17 @@ int as_forward(const AsPlan& p, const float* ramp, const float* wav, int B, int 
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
-}
-
 int as_run(iris_assemble_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, int32_t row_scale, float* out_dev, int rows,
            int32_t* spans_out_dev, int32_t* ints_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
-    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
-    if (row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale >= 1 is required, got %d", row_scale);
+    const RaggedWaveCall call = {wav_dev, B, L, row_scale, out_dev, true, ints_out_dev, 0, workspace_dev, 0, workspace_bytes};
     long long cap = 0;
-    TRY(as_check_shape(h->p, B, L, rows, &cap));
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    if (!wav_dev || !out_dev || !ints_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    if (overlap(wav_dev, (size_t)B * L, out_dev, (size_t)cap)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev overlaps wav_dev");
-    ForwardScope scope(*h, workspace_bytes, AsWorkspace(h->p, B, L).floats);
-    TRY(scope.rc);
-    return as_forward(h->p, h->blob + h->ramp_off, wav_dev, B, L, lengths_dev, row_scale, out_dev, (int)cap, rows, spans_out_dev, ints_out_dev,
-                      (float*)workspace_dev, (hipStream_t)stream);
+    return run_ragged_wave(h, call,
+        [&](size_t* out_floats, size_t* ws_floats) -> int {
+            TRY(as_check_shape(h->p, B, L, rows, &cap));
+            *out_floats = (size_t)cap; *ws_floats = AsWorkspace(h->p, B, L).floats;
+            return IRIS_HIFIGAN_OK; },
+        [&] { return as_forward(h->p, h->blob + h->ramp_off, wav_dev, B, L, lengths_dev, row_scale, out_dev, (int)cap, rows, spans_out_dev,
+                                ints_out_dev, (float*)workspace_dev, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -138,8 +130,7 @@ int32_t iris_assemble_workspace_bytes(const iris_assemble_config* cfg, int32_t B
     TRY(as_validate(cfg, &p));
     long long c = 0;
     TRY(as_check_shape(p, B, L, 0, &c));
-    *bytes = (uint64_t)AsWorkspace(p, B, L).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(AsWorkspace(p, B, L).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -151,9 +142,7 @@ int32_t iris_assemble_launch_count(const iris_assemble_config* cfg, int32_t B, i
     TRY(as_validate(cfg, &p));
     long long c = 0;
     TRY(as_check_shape(p, B, L, 0, &c));
-    *n = 0;
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
         return as_forward(p, fake, fake, B, L, nullptr, 1, fake, (int)c, 0, nullptr, reinterpret_cast<int32_t*>(fake), fake, nullptr); }, n);
     IRIS_ABI_END
 }
@@ -163,8 +152,8 @@ int32_t iris_assemble_create(const iris_assemble_config* cfg, iris_assemble_hand
     if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     AsPlan p;
     TRY(as_validate(cfg, &p));
-    std::unique_ptr<iris_assemble_handle> h(new (std::nothrow) iris_assemble_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_assemble_handle> h;
+    TRY(new_handle(&h));
     h->p = p;
     BlobBuilder bb(nullptr);
     h->ramp_off = bb.reserve(p.fade ? p.fade : 1);                 // (fade == 0: one unread word, so that there is a blob)

@@ -10,7 +10,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #define IRIS_MEL_NO_KERNEL               // this stage takes the front-end's config rules (mel_validate), not mel_kernel
@@ -114,11 +113,6 @@ int dn_check_interior(const mel::Design& d, int32_t L) {
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" {
@@ -133,8 +127,8 @@ int32_t iris_denoiser_create(const iris_mel_frontend_config* cfg, const float* b
         for (int k = 0; k < nb; ++k)
             if (!(bias_host[k] >= 0.f) || !isfinite(bias_host[k]))
                 return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bias[%d] = %g: a magnitude spectrum is finite and not negative", k, (double)bias_host[k]);
-    std::unique_ptr<iris_denoiser_handle> h(new (std::nothrow) iris_denoiser_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_denoiser_handle> h;
+    TRY(new_handle(&h));
     h->d = d;
     BlobBuilder bb(nullptr);
     stft::pack_tables(bb, d, true, h->t);
@@ -157,8 +151,7 @@ int32_t iris_denoiser_workspace_bytes(const iris_mel_frontend_config* cfg, int32
     mel::Design d;
     TRY(dn_validate(cfg, &d));
     TRY(dn_check_shape(d, B, L));
-    *bytes = (uint64_t)DnWorkspace(d, B, L).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(DnWorkspace(d, B, L).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -169,9 +162,7 @@ int32_t iris_denoiser_launch_count(const iris_mel_frontend_config* cfg, int32_t 
     mel::Design d;
     TRY(dn_validate(cfg, &d));
     TRY(dn_check_shape(d, B, L));
-    *n = 0;
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
         const DnTables tb = {fake, fake, fake, fake};
         return dn_forward(d, tb, fake, B, L, nullptr, 0.f, fake, fake, nullptr); }, n);
     IRIS_ABI_END
@@ -251,9 +242,7 @@ int32_t iris_denoiser_window_launch_count(const iris_mel_frontend_config* cfg, i
     TRY(dn_validate(cfg, &d));
     TRY(dn_check_window(d, B, Lw, origin));
     const dn::Window w(d, origin / d.hop, Lw / d.hop, final != 0);
-    *n = 0;
-    if (B == 0 || w.out_count == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0 || w.out_count == 0, [&](float* fake) {
         const DnTables tb = {fake, fake, fake, fake};
         return dn_forward_window(d, tb, fake, B, Lw, w, origin, 0.f, fake, fake, nullptr); }, n);
     IRIS_ABI_END

@@ -9,7 +9,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #define IRIS_MEL_NO_KERNEL               // this stage takes the front-end's design and filterbank, not mel_kernel
@@ -147,8 +146,8 @@ int32_t iris_griffin_lim_create(const iris_griffin_lim_config* cfg, const float*
     if (n_pinv != (uint64_t)nb * M)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "pinv(fb) [n_bins][n_mels] has %llu values, got %llu", (unsigned long long)nb * M,
                     (unsigned long long)n_pinv);
-    std::unique_ptr<iris_griffin_lim_handle> h(new (std::nothrow) iris_griffin_lim_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_griffin_lim_handle> h;
+    TRY(new_handle(&h));
     h->d = d;
     std::vector<float> fbank((size_t)M * nb), fbt((size_t)nb * M);
     mel::fill_filterbank(d, fbank.data());
@@ -177,8 +176,7 @@ int32_t iris_griffin_lim_workspace_bytes(const iris_griffin_lim_config* cfg, int
     gl::Design d;
     TRY(gl_validate(cfg, &d));
     TRY(gl_check_shape(B, T));
-    *bytes = (uint64_t)GlWorkspace(d, B, T).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(GlWorkspace(d, B, T).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -189,9 +187,7 @@ int32_t iris_griffin_lim_launch_count(const iris_griffin_lim_config* cfg, int32_
     gl::Design d;
     TRY(gl_validate(cfg, &d));
     TRY(gl_check_shape(B, T));
-    *n = 0;
-    if (B == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0, [&](float* fake) {
         const GlTables tb = {fake, fake, fake, fake, fake, fake};
         return gl_forward(d, tb, fake, fake, 0, 0, B, T, nullptr, fake, fake, nullptr); }, n);
     IRIS_ABI_END

@@ -8,7 +8,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #include "limiter.h"
@@ -39,13 +38,6 @@ int lm_validate(const iris_limiter_config* c, LmPlan* p) {
     if (c->lookahead < 1 || c->lookahead > limiter::kMaxLookahead)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "lookahead must lie in 1 .. %d samples, got %d", limiter::kMaxLookahead, c->lookahead);
     p->ceiling = c->ceiling; p->A = c->lookahead;
-    return IRIS_HIFIGAN_OK;
-}
-
-int lm_check_shape(int32_t B, int32_t L) {
-    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    TRY(check_batch(B));
-    if ((long long)B * L > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "B = %d, L = %d: %lld samples exceed 32-bit offsets", B, L, (long long)B * L);
     return IRIS_HIFIGAN_OK;
 }
 
@@ -81,25 +73,16 @@ int lm_forward(const LmPlan& p, const float* table, const float* wav, int B, int
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
-}
-
 int lm_run(iris_limiter_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, int32_t row_scale, float* out_dev, bool apply,
            float* stats_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
-    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
-    if (row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale >= 1 is required, got %d", row_scale);
-    TRY(lm_check_shape(B, L));
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    if (!wav_dev || (apply && !out_dev) || !stats_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    if ((uintptr_t)stats_out_dev & 3) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "stats_out_dev must lie on 4 bytes");
-    if ((uintptr_t)workspace_dev & 7) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "workspace_dev must lie on 8 bytes");
-    if (apply && overlap(wav_dev, (size_t)B * L, out_dev, (size_t)B * L)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev overlaps wav_dev");
-    ForwardScope scope(*h, workspace_bytes, LmWorkspace(B, L).floats);
-    TRY(scope.rc);
-    return lm_forward(h->p, h->blob, wav_dev, B, L, lengths_dev, row_scale, apply ? out_dev : nullptr, stats_out_dev, (float*)workspace_dev,
-                      (hipStream_t)stream);
+    const RaggedWaveCall call = {wav_dev, B, L, row_scale, out_dev, apply, stats_out_dev, 4, workspace_dev, 8, workspace_bytes};
+    return run_ragged_wave(h, call,
+        [&](size_t* out_floats, size_t* ws_floats) -> int {
+            TRY(check_wave_shape(B, L));
+            *out_floats = (size_t)B * L; *ws_floats = LmWorkspace(B, L).floats;
+            return IRIS_HIFIGAN_OK; },
+        [&] { return lm_forward(h->p, h->blob, wav_dev, B, L, lengths_dev, row_scale, apply ? out_dev : nullptr, stats_out_dev,
+                                (float*)workspace_dev, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -122,9 +105,8 @@ int32_t iris_limiter_workspace_bytes(const iris_limiter_config* cfg, int32_t B, 
     if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LmPlan p;
     TRY(lm_validate(cfg, &p));
-    TRY(lm_check_shape(B, L));
-    *bytes = (uint64_t)LmWorkspace(B, L).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    TRY(check_wave_shape(B, L));
+    *bytes = workspace_bytes_of(LmWorkspace(B, L).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -134,10 +116,9 @@ int32_t iris_limiter_launch_count(const iris_limiter_config* cfg, int32_t B, int
     if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LmPlan p;
     TRY(lm_validate(cfg, &p));
-    TRY(lm_check_shape(B, L));
-    *n = 0;
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) { return lm_forward(p, fake, fake, B, L, nullptr, 1, measure_only ? nullptr : fake, fake, fake, nullptr); }, n);
+    TRY(check_wave_shape(B, L));
+    return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
+        return lm_forward(p, fake, fake, B, L, nullptr, 1, measure_only ? nullptr : fake, fake, fake, nullptr); }, n);
     IRIS_ABI_END
 }
 
@@ -146,8 +127,8 @@ int32_t iris_limiter_create(const iris_limiter_config* cfg, iris_limiter_handle*
     if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LmPlan p;
     TRY(lm_validate(cfg, &p));
-    std::unique_ptr<iris_limiter_handle> h(new (std::nothrow) iris_limiter_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_limiter_handle> h;
+    TRY(new_handle(&h));
     h->p = p;
     std::vector<float> host((size_t)limiter::design_floats(p.A));
     TRY(lm_design(p, host.data()));

@@ -8,7 +8,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #include "loudness.h"
@@ -45,13 +44,6 @@ int ld_validate(const iris_loudness_config* c, LdPlan* p) {
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "peak_ceiling must be an amplitude in (0, 1], or 0 for none, got %g", (double)c->peak_ceiling);
     p->rate = c->sample_rate; p->step = c->sample_rate / 10;
     p->target = (double)c->target_lufs; p->max_gain = (double)c->max_gain_db; p->ceiling = (double)c->peak_ceiling;
-    return IRIS_HIFIGAN_OK;
-}
-
-int ld_check_shape(int32_t B, int32_t L) {
-    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    TRY(check_batch(B));
-    if ((long long)B * L > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "B = %d, L = %d: %lld samples exceed 32-bit offsets", B, L, (long long)B * L);
     return IRIS_HIFIGAN_OK;
 }
 
@@ -94,25 +86,16 @@ int ld_forward(const LdPlan& p, const double* design, const float* wav, int B, i
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
-}
-
 int ld_run(iris_loudness_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, int32_t row_scale, float* out_dev, bool apply,
            double* stats_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
-    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
-    if (row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale >= 1 is required, got %d", row_scale);
-    TRY(ld_check_shape(B, L));
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    if (!wav_dev || (apply && !out_dev) || !stats_out_dev || !workspace_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
-    if ((uintptr_t)stats_out_dev & 7) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "stats_out_dev must lie on 8 bytes");
-    if ((uintptr_t)workspace_dev & 7) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "workspace_dev must lie on 8 bytes");
-    if (apply && overlap(wav_dev, (size_t)B * L, out_dev, (size_t)B * L)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev overlaps wav_dev");
-    ForwardScope scope(*h, workspace_bytes, LdWorkspace(h->p, B, L).floats);
-    TRY(scope.rc);
-    return ld_forward(h->p, reinterpret_cast<const double*>(h->blob), wav_dev, B, L, lengths_dev, row_scale, apply ? out_dev : nullptr, stats_out_dev,
-                      (float*)workspace_dev, (hipStream_t)stream);
+    const RaggedWaveCall call = {wav_dev, B, L, row_scale, out_dev, apply, stats_out_dev, 8, workspace_dev, 8, workspace_bytes};
+    return run_ragged_wave(h, call,
+        [&](size_t* out_floats, size_t* ws_floats) -> int {
+            TRY(check_wave_shape(B, L));
+            *out_floats = (size_t)B * L; *ws_floats = LdWorkspace(h->p, B, L).floats;
+            return IRIS_HIFIGAN_OK; },
+        [&] { return ld_forward(h->p, reinterpret_cast<const double*>(h->blob), wav_dev, B, L, lengths_dev, row_scale, apply ? out_dev : nullptr,
+                                stats_out_dev, (float*)workspace_dev, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -135,9 +118,8 @@ int32_t iris_loudness_workspace_bytes(const iris_loudness_config* cfg, int32_t B
     if (!bytes) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LdPlan p;
     TRY(ld_validate(cfg, &p));
-    TRY(ld_check_shape(B, L));
-    *bytes = (uint64_t)LdWorkspace(p, B, L).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    TRY(check_wave_shape(B, L));
+    *bytes = workspace_bytes_of(LdWorkspace(p, B, L).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -147,10 +129,8 @@ int32_t iris_loudness_launch_count(const iris_loudness_config* cfg, int32_t B, i
     if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LdPlan p;
     TRY(ld_validate(cfg, &p));
-    TRY(ld_check_shape(B, L));
-    *n = 0;
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    TRY(check_wave_shape(B, L));
+    return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
         return ld_forward(p, reinterpret_cast<const double*>(fake), fake, B, L, nullptr, 1, measure_only ? nullptr : fake, reinterpret_cast<double*>(fake),
                           fake, nullptr); }, n);
     IRIS_ABI_END
@@ -161,8 +141,8 @@ int32_t iris_loudness_create(const iris_loudness_config* cfg, iris_loudness_hand
     if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     LdPlan p;
     TRY(ld_validate(cfg, &p));
-    std::unique_ptr<iris_loudness_handle> h(new (std::nothrow) iris_loudness_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_loudness_handle> h;
+    TRY(new_handle(&h));
     h->p = p;
     double design[loudness::kDesign];
     loudness::fill_design(p.rate, p.target, p.max_gain, p.ceiling, design);

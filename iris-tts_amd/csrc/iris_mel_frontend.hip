@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #define IRIS_STFT_NO_INVERSE             // this stage launches no inverse transform
@@ -120,8 +119,8 @@ int32_t iris_mel_frontend_create(const iris_mel_frontend_config* cfg, iris_mel_f
     if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     mel::Design d;
     TRY(mel_validate(cfg, &d));
-    std::unique_ptr<iris_mel_frontend_handle> h(new (std::nothrow) iris_mel_frontend_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_mel_frontend_handle> h;
+    TRY(new_handle(&h));
     h->d = d;
     std::vector<float> fbank((size_t)d.n_mels * d.bins());
     mel::fill_filterbank(d, fbank.data());
@@ -155,10 +154,8 @@ int32_t iris_mel_frontend_launch_count(const iris_mel_frontend_config* cfg, int3
     mel::Design d;
     TRY(mel_validate(cfg, &d));
     TRY(mel_check_shape(B, L));
-    *n = 0;
-    if (B == 0) return IRIS_HIFIGAN_OK;
     const PackedGemm none;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0, [&](float* fake) {
         return mel_forward(d, fake, none, none, fake, false, B, L, nullptr, nullptr, fake, nullptr, nullptr); }, n);
     IRIS_ABI_END
 }

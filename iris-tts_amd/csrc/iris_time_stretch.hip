@@ -11,7 +11,6 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
-#include <new>
 #include <vector>
 
 #include "stage_host.h"
@@ -227,11 +226,6 @@ int ts_forward_window(const stft::Sizes& d, const TsTables& tb, const float* wav
     return IRIS_HIFIGAN_OK;
 }
 
-bool overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
-}
-
 int ts_run(iris_time_stretch_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, double rate, float* out_dev,
            int32_t* counts_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
     if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
@@ -255,8 +249,8 @@ int32_t iris_time_stretch_create(const iris_mel_frontend_config* cfg, iris_time_
     if (!out) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
     stft::Sizes d;
     TRY(ts_validate(cfg, &d));
-    std::unique_ptr<iris_time_stretch_handle> h(new (std::nothrow) iris_time_stretch_handle);
-    if (!h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    std::unique_ptr<iris_time_stretch_handle> h;
+    TRY(new_handle(&h));
     h->d = d;
     BlobBuilder bb(nullptr);
     stft::pack_tables(bb, d, true, h->t);
@@ -290,8 +284,7 @@ int32_t iris_time_stretch_workspace_bytes(const iris_mel_frontend_config* cfg, i
     TRY(ts_validate(cfg, &d));
     TsShape s;
     TRY(ts_check_shape(d, B, L, rate, &s));
-    *bytes = (uint64_t)TsWorkspace(d, B, s).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(TsWorkspace(d, B, s).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -303,9 +296,7 @@ int32_t iris_time_stretch_launch_count(const iris_mel_frontend_config* cfg, int3
     TRY(ts_validate(cfg, &d));
     TsShape s;
     TRY(ts_check_shape(d, B, L, rate, &s));
-    *n = 0;
-    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
         const TsTables tb = {fake, fake, fake};
         return ts_forward(d, tb, fake, B, L, s, nullptr, rate, fake, nullptr, fake, nullptr); }, n);
     IRIS_ABI_END
@@ -332,8 +323,7 @@ int32_t iris_time_stretch_state_bytes(const iris_mel_frontend_config* cfg, int32
     stft::Sizes d;
     TRY(ts_validate(cfg, &d));
     TRY(ts_check_window(d, B, 0, 1.0, 0, 0));
-    *bytes = (uint64_t)TsState(d, B).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(TsState(d, B).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -358,8 +348,7 @@ int32_t iris_time_stretch_window_workspace_bytes(const iris_mel_frontend_config*
     stft::Sizes d;
     TRY(ts_validate(cfg, &d));
     TRY(ts_check_window(d, B, Lw, rate, 0, 0));
-    *bytes = (uint64_t)TsWindowWorkspace(d, B, Lw, rate).floats * sizeof(float);
-    if (*bytes < 256) *bytes = 256;
+    *bytes = workspace_bytes_of(TsWindowWorkspace(d, B, Lw, rate).floats);
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }
@@ -373,9 +362,7 @@ int32_t iris_time_stretch_window_launch_count(const iris_mel_frontend_config* cf
     TRY(ts_check_window(d, B, Lw, rate, origin, u));
     ts::WindowPlan p;
     TRY(ts_plan_window(d, rate, origin, Lw, final, u, &p));
-    *n = 0;
-    if (B == 0 || (p.u_hi == u && p.out_count == 0)) return IRIS_HIFIGAN_OK;
-    return count_launches([&](float* fake) {
+    return count_forward_launches(B == 0 || (p.u_hi == u && p.out_count == 0), [&](float* fake) {
         const TsTables tb = {fake, fake, fake};
         return ts_forward_window(d, tb, fake, B, Lw, p, origin, u, rate, fake, fake, fake, nullptr); }, n);
     IRIS_ABI_END

@@ -1,10 +1,15 @@
 // stage_host.h -- the host scaffold of the stages around the vocoder: the PostNet (iris_hifigan.hip), the VAE decoder
 // (iris_vae_decoder.hip), the text stage (iris_text_encoder.hip) and the DSP stages (stft_f32.h).  Each of them packs a weight blob, uploads it, lays
 // out a workspace, checks it in front of a forward and counts its launches in a dry run; that is written here once.
+// The waveform stages (iris_mel_frontend.hip, iris_griffin_lim.hip, iris_denoiser.hip, iris_time_stretch.hip, iris_assemble.hip,
+// iris_loudness.hip, iris_limiter.hip) also take from here what their entry points repeat: the handle's allocation, the bytes
+// of a workspace, the launch count of a forward that may be empty, the overlap test, the plain [B, L] shape check, and the
+// whole prologue of a forward on a ragged batch of waveforms (run_ragged_wave).
 // The vocoder's own create and forward (iris_hifigan.hip, generator_internal.h) do not use it.  Not installed.
 #pragma once
 #include <string.h>
 #include <memory>
+#include <new>
 #include <vector>
 
 #include "generator_internal.h"
@@ -96,6 +101,79 @@ template <class Fn> int count_launches(Fn run, int32_t* n) {
     TRY(rc);
     *n = d.n;
     return IRIS_HIFIGAN_OK;
+}
+
+// ---- the waveform stages (mel front-end, Griffin-Lim, denoiser, time stretch, assemble, loudness, limiter) ----------------------
+
+// What a *_launch_count answers behind its config and shape checks: 0 for a forward that returns before its first launch
+// (`empty`), else the launches of `run`, the forward in a dry run.
+template <class Fn> int count_forward_launches(bool empty, Fn run, int32_t* n) {
+    *n = 0;
+    if (empty) return IRIS_HIFIGAN_OK;
+    return count_launches(run, n);
+}
+
+// A handle of a stage, or the failure of the host allocation.
+template <class H> int new_handle(std::unique_ptr<H>* h) {
+    h->reset(new (std::nothrow) H);
+    if (!*h) return fail(IRIS_HIFIGAN_OUT_OF_MEMORY, "host allocation failed");
+    return IRIS_HIFIGAN_OK;
+}
+
+// What a *_workspace_bytes answers for a layout of `floats`: no workspace is smaller than one buffer's alignment.
+inline uint64_t workspace_bytes_of(size_t floats) {
+    const uint64_t bytes = (uint64_t)floats * sizeof(float);
+    return bytes < 256 ? 256 : bytes;
+}
+
+// Do the na floats at a and the nb floats at b share a byte?
+inline bool overlap(const float* a, size_t na, const float* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb * sizeof(float) && y < x + na * sizeof(float);
+}
+
+// A batch of B waveforms of L samples each whose kernels index the B L samples in 32 bits, one item per grid.y.
+inline int check_wave_shape(int32_t B, int32_t L) {
+    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    TRY(check_batch(B));
+    if ((long long)B * L > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "B = %d, L = %d: %lld samples exceed 32-bit offsets", B, L, (long long)B * L);
+    return IRIS_HIFIGAN_OK;
+}
+
+// The arguments of a forward on a ragged batch of waveforms (wav [B, L], item b owning lengths[b] * row_scale samples) that the
+// assemble, loudness and limiter stages check alike.  `stats`: the per-item results (statistics, or the join's integers);
+// `stats_align`, `workspace_align`: the bytes each must lie on, 0 for no demand beyond its type's.
+struct RaggedWaveCall {
+    const float* wav;
+    int32_t B, L, row_scale;
+    const float* out;
+    bool want_out;                  // false: a measuring call, `out` is not looked at
+    const void* stats;
+    int stats_align;
+    const void* workspace;
+    int workspace_align;
+    uint64_t workspace_bytes;
+};
+
+// Every check of such a forward in one order -- handle, row_scale, `shape`, the empty batch (OK, nothing is launched), NULL
+// pointers, alignment, overlap, workspace -- and then `forward` under the handle's device.  `shape(&out_floats, &ws_floats)`
+// is the stage's shape check; it says how many floats `out` holds and how many the workspace needs.
+template <class Shape, class Forward>
+int run_ragged_wave(const StageHandle* h, const RaggedWaveCall& c, Shape shape, Forward forward) {
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    if (c.row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale >= 1 is required, got %d", c.row_scale);
+    size_t out_floats = 0, ws_floats = 0;
+    TRY(shape(&out_floats, &ws_floats));
+    if (c.B == 0 || c.L == 0) return IRIS_HIFIGAN_OK;
+    if (!c.wav || (c.want_out && !c.out) || !c.stats || !c.workspace) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL device pointer");
+    if (c.stats_align && ((uintptr_t)c.stats & (uintptr_t)(c.stats_align - 1)))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "stats_out_dev must lie on %d bytes", c.stats_align);
+    if (c.workspace_align && ((uintptr_t)c.workspace & (uintptr_t)(c.workspace_align - 1)))
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "workspace_dev must lie on %d bytes", c.workspace_align);
+    if (c.want_out && overlap(c.wav, (size_t)c.B * c.L, c.out, out_floats)) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev overlaps wav_dev");
+    ForwardScope scope(*h, c.workspace_bytes, ws_floats);
+    TRY(scope.rc);
+    return forward();
 }
 
 }  // namespace iris

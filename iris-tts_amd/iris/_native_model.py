@@ -1,5 +1,7 @@
 """What the models around the vocoder share (``iris.encoder``, ``iris.vae``, ``iris.postnet``): weights kept in Keras
 layouts, ``.npz`` files, and a native handle with its workspace, both built on first use and dropped when a weight changes.
+``_DeviceStage`` is the base of the stages that have a config and no weights (``iris.mel``, ``iris.griffin_lim``,
+``iris.denoiser``, ``iris.time_stretch``, ``iris.assemble``, ``iris.loudness``, ``iris.limiter``).
 """
 from __future__ import annotations
 
@@ -20,6 +22,33 @@ def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
 
 def _stream(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _take_buffers(sizes):
+    """``WsTaker`` (csrc/stage_host.h): the buffers one behind the other, each rounded up to 64 floats."""
+    layout, off = {}, 0
+    for name, n in sizes:
+        layout[name] = (off, n)
+        off += (n + 63) & ~63
+    return layout, off
+
+
+def _take_shapes(shapes: dict):
+    """``_take_buffers`` for buffers of one word per element, named by shape: ``({buffer: (offset, shape)}, words)``."""
+    layout, total = _take_buffers((name, int(np.prod(shape))) for name, shape in shapes.items())
+    return {name: (layout[name][0], shape) for name, shape in shapes.items()}, total
+
+
+def _wave(wav, hop_length: Optional[int] = None, why: str = "") -> torch.Tensor:
+    """``wav`` as a ``[B, L]`` float32 tensor, from host or device, where it is.  ``hop_length``: ``L`` must be a multiple of
+    it; ``why`` is the calling stage's own sentence for that refusal."""
+    if not isinstance(wav, torch.Tensor):
+        wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
+    if hop_length and wav.shape[1] % hop_length:
+        raise ValueError(f"L = {wav.shape[1]} is not a multiple of hop_length = {hop_length}: {why}; nothing is padded silently")
+    return wav
 
 
 class _NativeModel:
@@ -104,9 +133,75 @@ class _NativeModel:
         _native.check(name, getattr(lib, name)(self._handle, B, n, ctypes.byref(out)))
         return int(out.value)
 
-    def _ws(self, B: int, n: int) -> torch.Tensor:
-        """The workspace, grown to what a forward of shape (B, n) needs."""
-        need = self.workspace_bytes(B, n)
+    def _grow(self, need: int) -> torch.Tensor:
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
         return self._workspace
+
+    def _ws(self, *shape) -> torch.Tensor:
+        """The workspace, grown to what a forward of ``shape`` -- whatever ``workspace_bytes`` takes -- needs."""
+        return self._grow(self.workspace_bytes(*shape))
+
+    _ws_for = _ws           # the name the stage classes had for it; earlier revisions of the stretch's GPU tests call it
+
+
+class _DeviceStage(_NativeModel):
+    """A stage that is a config and no weights: its host-only queries take ``native_config()`` by reference, its handle
+    is built on ``device`` (None: the current one) and owns whatever tables the library designs for the config."""
+
+    def __init__(self, device=None):
+        super().__init__()
+        self._want_device = None if device is None else torch.device(device)
+
+    # -- host-only queries -------------------------------------------------------------------
+    def _query_config(self):
+        return self.native_config()
+
+    def _query(self, what: str, *args) -> int:
+        """``iris_<_abi_name>_<what>(config, *args, &out)``: no device needed.  The symbol table (``iris._native``) says what
+        ``out`` and every argument are."""
+        name = f"iris_{self._abi_name}_{what}"
+        fn = getattr(_native.load(), name)
+        cfg, out = self._query_config(), fn.argtypes[-1]._type_()
+        args = [float(v) if t is ctypes.c_double else int(v) for t, v in zip(fn.argtypes[1:-1], args)]
+        _native.check(name, fn(ctypes.byref(cfg), *args, ctypes.byref(out)))
+        return int(out.value)
+
+    # -- the native handle -------------------------------------------------------------------
+    def _upload_blob(self) -> np.ndarray:
+        return np.zeros(0, dtype=np.float32)            # the library designs its own tables
+
+    def _create(self, lib, weights, n_weights, handle_ref) -> int:
+        cfg = self.native_config()
+        return getattr(lib, f"iris_{self._abi_name}_create")(ctypes.byref(cfg), handle_ref)
+
+    def _ensure(self):
+        if self._handle is None and self._want_device is not None:
+            with torch.cuda.device(self._want_device):
+                return super()._ensure()
+        return super()._ensure()
+
+    def close(self) -> None:
+        """Frees the native handle and the workspace; the next call builds them again."""
+        self._drop()
+
+    # -- what the calls take ------------------------------------------------------------------
+    def _ragged_wave(self, wav, lengths, row_scale):
+        """``(lib, wav, lengths, B, L)`` of a call on a ragged batch of waveforms: ``wav [B, L]`` fp32 and ``lengths`` (None,
+        a host sequence of integers or an integer tensor ``[B]``) on the handle's device, checked before any device work."""
+        wav = _wave(wav)
+        if isinstance(row_scale, bool) or int(row_scale) != row_scale or int(row_scale) < 1:
+            raise ValueError(f"row_scale must be an integer >= 1, got {row_scale!r}")
+        B = int(wav.shape[0])
+        if lengths is not None and not isinstance(lengths, torch.Tensor):
+            host = np.asarray(lengths)
+            if host.shape != (B,) or (host.size and not np.issubdtype(host.dtype, np.integer)):
+                raise ValueError(f"lengths must be {B} integers, got {host.dtype} {host.shape}")
+            lengths = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+        if lengths is not None and (tuple(lengths.shape) != (B,) or lengths.dtype not in (torch.int32, torch.int64)):
+            raise ValueError(f"lengths must be an integer tensor [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
+        lib = self._ensure()
+        wav = wav.to(self._device).contiguous()
+        if lengths is not None:
+            lengths = lengths.to(device=self._device, dtype=torch.int32).contiguous()
+        return lib, wav, lengths, B, int(wav.shape[1])

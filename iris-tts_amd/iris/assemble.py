@@ -25,14 +25,13 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream, _take_shapes
 
 
-class Assembler(_NativeModel):
+class Assembler(_DeviceStage):
     """Trim and join with fixed parameters, resident on one GPU (``device``, or the current one); the handle -- it owns the
     ramp -- is built on first use.  ``ref``: None for the item's own maximum (``ref=np.max``), or an absolute amplitude > 0.
     ``pad``: samples kept beyond the decision's bounds on either side; ``fade``: samples of the ramp at every cut;
@@ -42,7 +41,7 @@ class Assembler(_NativeModel):
 
     def __init__(self, frame_length: int = 2048, hop_length: int = 512, top_db: float = 60.0, ref: Optional[float] = None,
                  pad: int = 0, fade: int = 0, pause: int = 0, device: Optional[torch.device] = None):
-        super().__init__()
+        super().__init__(device)
         for name, v in (("frame_length", frame_length), ("hop_length", hop_length), ("pad", pad), ("fade", fade), ("pause", pause)):
             if isinstance(v, bool) or int(v) != v:
                 raise ValueError(f"{name} must be an integer, got {v!r}")
@@ -51,7 +50,6 @@ class Assembler(_NativeModel):
         self.frame_length, self.hop_length = int(frame_length), int(hop_length)
         self.top_db, self.ref = float(top_db), None if ref is None else float(ref)
         self.pad, self.fade, self.pause = int(pad), int(fade), int(pause)
-        self._want_device = None if device is None else torch.device(device)
         self.capacity(0, 0)                                    # the library's own refusals, before any device work
 
     def get_config(self) -> dict:
@@ -63,29 +61,21 @@ class Assembler(_NativeModel):
                                       self.pad, self.fade, self.pause)
 
     # -- host-only queries -------------------------------------------------------------------
-    def _query(self, name: str, B: int, L: int, ctype) -> int:
-        lib = _native.load()
-        cfg, out = self.native_config(), ctype()
-        _native.check(name, getattr(lib, name)(ctypes.byref(cfg), int(B), int(L), ctypes.byref(out)))
-        return int(out.value)
-
     def capacity(self, B: int, L: int) -> int:
         """``cap = B L + pause (B - 1)``: the samples ``join_device`` returns for a batch ``[B, L]`` (no device needed)."""
-        return self._query("iris_assemble_out_capacity", B, L, ctypes.c_int64)
+        return self._query("out_capacity", B, L)
 
     def launch_count(self, B: int, L: int) -> int:
         """Kernel launches of one call: 3 (a dry run on the host, no device needed)."""
-        return self._query("iris_assemble_launch_count", B, L, ctypes.c_int32)
+        return self._query("launch_count", B, L)
 
     def workspace_bytes(self, B: int, L: int) -> int:
-        return self._query("iris_assemble_workspace_bytes", B, L, ctypes.c_uint64)
+        return self._query("workspace_bytes", B, L)
 
     def _workspace_layout(self, B: int, L: int):
         """``({buffer: (offset, shape)}, words)``: ``AsWorkspace`` (csrc/iris_assemble.hip) restated -- ``mse [B, L // H + 1]`` fp32,
-        then ``spans [B, 2]`` int32, each rounded up to 64 words.  Host only."""
-        T = L // self.hop_length + 1
-        mse = (B * T + 63) // 64 * 64
-        return {"mse": (0, (B, T)), "spans": (mse, (B, 2))}, mse + (2 * B + 63) // 64 * 64
+        then ``spans [B, 2]`` int32.  Host only."""
+        return _take_shapes({"mse": (B, L // self.hop_length + 1), "spans": (B, 2)})
 
     def _read_buffers(self, B: int, L: int) -> dict:
         """Test-only: copies of ``mse`` (fp32; row b is stored up to ``T_b``) and ``spans`` as the last call of shape (B, L)
@@ -94,51 +84,6 @@ class Assembler(_NativeModel):
         (o_m, s_m), (o_s, s_s) = layout["mse"], layout["spans"]
         return {"mse": self._workspace.view(torch.float32)[o_m:o_m + s_m[0] * s_m[1]].view(s_m).clone(),
                 "spans": self._workspace.view(torch.int32)[o_s:o_s + 2 * B].view(s_s).clone()}
-
-    # -- the native handle -------------------------------------------------------------------
-    def _upload_blob(self) -> np.ndarray:
-        return np.zeros(0, dtype=np.float32)
-
-    def _create(self, lib, weights, n_weights, handle_ref) -> int:
-        cfg = self.native_config()
-        return lib.iris_assemble_create(ctypes.byref(cfg), handle_ref)
-
-    def _ensure(self):
-        if self._handle is None and self._want_device is not None:
-            with torch.cuda.device(self._want_device):
-                return super()._ensure()
-        return super()._ensure()
-
-    def close(self) -> None:
-        """Frees the native handle and the workspace; the next call builds them again."""
-        self._drop()
-
-    def _ws_for(self, B: int, L: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, L)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        return self._workspace
-
-    def _prepare(self, wav, lengths, row_scale):
-        if not isinstance(wav, torch.Tensor):
-            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
-        if wav.dim() != 2 or wav.dtype != torch.float32:
-            raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
-        if isinstance(row_scale, bool) or int(row_scale) != row_scale or int(row_scale) < 1:
-            raise ValueError(f"row_scale must be an integer >= 1, got {row_scale!r}")
-        B = int(wav.shape[0])
-        if lengths is not None and not isinstance(lengths, torch.Tensor):
-            host = np.asarray(lengths)
-            if host.shape != (B,) or (host.size and not np.issubdtype(host.dtype, np.integer)):
-                raise ValueError(f"lengths must be {B} integers, got {host.dtype} {host.shape}")
-            lengths = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
-        if lengths is not None and (tuple(lengths.shape) != (B,) or lengths.dtype not in (torch.int32, torch.int64)):
-            raise ValueError(f"lengths must be an integer tensor [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
-        lib = self._ensure()
-        wav = wav.to(self._device).contiguous()
-        if lengths is not None:
-            lengths = lengths.to(device=self._device, dtype=torch.int32).contiguous()
-        return lib, wav, lengths, B, int(wav.shape[1])
 
     # -- the calls ---------------------------------------------------------------------------
     def join_device(self, wav, lengths=None, row_scale: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -151,14 +96,14 @@ class Assembler(_NativeModel):
         item b owns ``min(L, lengths[b] * row_scale)`` samples -- mel frames and the vocoder's hop, or a stretch's ``counts``
         and 1 -- and nothing past them is read.  Item b's span and samples are those of its batch-of-one call.
         ``offsets[B:]`` is the ``lengths`` of a following ``Resampler.forward(out[None], lengths=, row_scale=1)``."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         cap = self.capacity(B, L)
         out = torch.empty((cap,), dtype=torch.float32, device=self._device)
         offsets = torch.empty((B + 1,), dtype=torch.int32, device=self._device)      # the stage stores every element itself
         spans = torch.empty((B, 2), dtype=torch.int32, device=self._device)
         if B == 0 or L == 0:
             return out.zero_(), offsets.zero_(), spans.zero_()
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_assemble_forward", lib.iris_assemble_forward(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(out), _ptr(spans), _ptr(offsets), _ptr(ws),
@@ -175,12 +120,12 @@ class Assembler(_NativeModel):
         """The same bounds with every item kept in its own row: ``(out [B, L], counts [B] int32)`` on the device,
         ``out[b, :counts[b]]`` item b's trimmed and faded samples, the rest of the row 0, ``counts`` the next stage's lengths
         (``row_scale=1``).  The same 3 launches; ``pause`` plays no part."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         out = torch.empty((B, L), dtype=torch.float32, device=self._device)
         counts = torch.empty((B,), dtype=torch.int32, device=self._device)
         if B == 0 or L == 0:
             return out, counts.zero_()
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_assemble_trim_ragged", lib.iris_assemble_trim_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(out), None, _ptr(counts), _ptr(ws),

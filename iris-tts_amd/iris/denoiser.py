@@ -33,11 +33,11 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream, _take_shapes, _wave
 from .vae import _lengths_on, check_lengths
 
 
-class Denoiser(_NativeModel):
+class Denoiser(_DeviceStage):
     """Spectral bias subtraction with fixed transform parameters, resident on one GPU (``device``, or the current one); the
     handle is built on first use.  ``bias``: ``[n_fft / 2 + 1]`` finite, non-negative magnitudes (host), or None for zeros --
     ``set_bias`` / ``from_vocoder`` install an estimate later.  ``strength``: the default multiple that is subtracted."""
@@ -46,7 +46,7 @@ class Denoiser(_NativeModel):
 
     def __init__(self, n_fft: int = 1024, hop_length: int = 256, win_length: int = 1024, strength: float = 0.1, bias=None,
                  device: Optional[torch.device] = None):
-        super().__init__()
+        super().__init__(device)
         for name, v in (("n_fft", n_fft), ("hop_length", hop_length), ("win_length", win_length)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name} must be a positive integer, got {v!r}")
@@ -54,7 +54,6 @@ class Denoiser(_NativeModel):
         self.strength = self._check_strength(strength)
         self._bias_host = None if bias is None else self._check_bias(bias)
         self._bias_dev: Optional[torch.Tensor] = None
-        self._want_device = None if device is None else torch.device(device)
 
     @property
     def n_bins(self) -> int:
@@ -83,33 +82,21 @@ class Denoiser(_NativeModel):
         return _native.MelFrontendConfig(22050, self.n_fft, self.hop_length, self.win_length, 1, 0, 0.0, 0.0)
 
     # -- host-only queries -------------------------------------------------------------------
-    def _query(self, name: str, *shape) -> int:
-        lib = _native.load()
-        out = ctypes.c_uint64() if name.endswith("bytes") else ctypes.c_int32()
-        cfg = self.native_config()
-        _native.check(name, getattr(lib, name)(ctypes.byref(cfg), *[int(v) for v in shape], ctypes.byref(out)))
-        return int(out.value)
-
     def launch_count(self, B: int, L: int) -> int:
         """Kernel launches of one ``forward_device``: 2 (a dry run on the host, no device needed)."""
-        return self._query("iris_denoiser_launch_count", B, L)
+        return self._query("launch_count", B, L)
 
     def estimate_launch_count(self, L: int) -> int:
         """Kernel launches of one ``estimate_bias``: 2 (likewise)."""
-        return self._query("iris_denoiser_estimate_launch_count", L)
+        return self._query("estimate_launch_count", L)
 
     def workspace_bytes(self, B: int, L: int) -> int:
-        return self._query("iris_denoiser_workspace_bytes", B, L)
+        return self._query("workspace_bytes", B, L)
 
     def _workspace_layout(self, B: int, L: int):
         """``({buffer: (offset, shape)}, floats)``: ``DnWorkspace`` (csrc/iris_denoiser.hip) restated -- c ``[B, T, Qp]`` and the
-        items' frame counts ``[B]`` (int32) in ``WsTaker`` order, each rounded up to 64 floats.  Host only."""
-        T, qp = L // self.hop_length + 1, (self.n_fft + 2 + 7) // 8 * 8
-        layout, off = {}, 0
-        for name, shape in (("c", (B, T, qp)), ("frames", (B,))):
-            layout[name] = (off, shape)
-            off += (int(np.prod(shape)) + 63) // 64 * 64
-        return layout, off
+        items' frame counts ``[B]`` (int32) in ``WsTaker`` order.  Host only."""
+        return _take_shapes({"c": (B, L // self.hop_length + 1, (self.n_fft + 2 + 7) // 8 * 8), "frames": (B,)})
 
     def _read_c(self, B: int, L: int) -> torch.Tensor:
         """Test-only: the view ``c [B, T, Qp]`` of the workspace as the last ``forward_device`` of shape (B, L) left it."""
@@ -144,16 +131,10 @@ class Denoiser(_NativeModel):
         cfg = self.native_config()
         return lib.iris_denoiser_create(ctypes.byref(cfg), weights if n_weights.value else None, handle_ref)
 
-    def _ensure(self):
-        if self._handle is None and self._want_device is not None:
-            with torch.cuda.device(self._want_device):
-                return super()._ensure()
-        return super()._ensure()
-
     def close(self) -> None:
         """Frees the native handle and the workspace; the next call builds them again (with the host bias of the constructor
         or the last host ``set_bias``; a device estimate has to be installed again)."""
-        self._drop()
+        super().close()
         self._bias_dev = None
 
     # -- the bias ----------------------------------------------------------------------------
@@ -182,14 +163,7 @@ class Denoiser(_NativeModel):
         self._bias_dev = dev
 
     def _wav_on_device(self, wav) -> torch.Tensor:
-        if not isinstance(wav, torch.Tensor):
-            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
-        if wav.dim() != 2 or wav.dtype != torch.float32:
-            raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
-        if wav.shape[1] % self.hop_length:
-            raise ValueError(f"L = {wav.shape[1]} is not a multiple of hop_length = {self.hop_length}: a vocoder emits hop_length "
-                             "samples per mel frame; nothing is padded silently")
-        return wav
+        return _wave(wav, self.hop_length, "a vocoder emits hop_length samples per mel frame")
 
     def estimate_bias(self, wav) -> torch.Tensor:
         """``wav [1, L]`` (or ``[L]``), host or device: the vocoder's output for a silent mel -> its bias, a device tensor
@@ -276,11 +250,11 @@ class Denoiser(_NativeModel):
         return int(lo.value), int(count.value)
 
     def window_workspace_bytes(self, B: int, Lw: int) -> int:
-        return self._query("iris_denoiser_window_workspace_bytes", B, Lw)
+        return self._query("window_workspace_bytes", B, Lw)
 
     def window_launch_count(self, B: int, Lw: int, origin: int, final: bool) -> int:
         """Kernel launches of one ``forward_window``: 2, or 0 where the window settles nothing (a dry run on the host)."""
-        return self._query("iris_denoiser_window_launch_count", B, Lw, origin, bool(final))
+        return self._query("window_launch_count", B, Lw, origin, bool(final))
 
     def forward_window(self, wav, origin: int, final: bool, strength: Optional[float] = None) -> torch.Tensor:
         """``wav [B, Lw]`` fp32 = samples ``[origin, origin + Lw)`` of an utterance (both multiples of ``hop_length``) -> the

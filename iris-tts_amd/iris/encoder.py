@@ -53,8 +53,8 @@ import torch
 
 from . import _native
 from ._engine import require_gpu
-from ._native_model import _NativeModel, _ptr, _stream
-from .vae import _read_buffers, _take_buffers
+from ._native_model import _NativeModel, _ptr, _stream, _take_buffers
+from .vae import _read_buffers
 
 DEFAULT_MAX_FRAMES = 65536          # frames of one utterance batch item that frame_conditioning accepts by default
 

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _NativeModel, _ptr, _stream, _take_shapes
 from .mel import MelFrontend
 from .vae import _lengths_on, check_lengths as _check_frame_counts
 
@@ -94,7 +94,7 @@ def check_lengths(lengths, B: int, T: int):
     return out
 
 
-class GriffinLim(_NativeModel):
+class GriffinLim(_DeviceStage):
     """The Griffin-Lim vocoder with fixed parameters (the reference script's), resident on one GPU.  Usable as the ``vocode``
     of ``MelToWavePipeline``; ``whole_utterance`` tells the pipeline that a mel cannot be cut into chunks (every frame's
     phase depends on the whole item) and that the output has ``hop * (T - 1)`` samples.
@@ -147,20 +147,15 @@ class GriffinLim(_NativeModel):
                                         self.fmin, 0.0 if self.fmax is None else self.fmax, self.nnls_iters, 0, self.momentum, step)
 
     # -- host-only queries -------------------------------------------------------------------
-    def _query(self, what: str, B: int, T: int, ctype) -> int:
-        lib = _native.load()
-        out = ctype()
-        cfg = self.native_config(with_step=False)
-        name = f"iris_griffin_lim_{what}"
-        _native.check(name, getattr(lib, name)(ctypes.byref(cfg), int(B), int(T), ctypes.byref(out)))
-        return int(out.value)
+    def _query_config(self):
+        return self.native_config(with_step=False)
 
     def launch_count(self, B: int, T: int) -> int:
         """Kernel launches of one ``forward_device``: ``2 * n_iter + 2`` (a dry run on the host, no device needed)."""
-        return self._query("launch_count", B, T, ctypes.c_int32)
+        return self._query("launch_count", B, T)
 
     def workspace_bytes(self, B: int, T: int) -> int:
-        return self._query("workspace_bytes", B, T, ctypes.c_uint64)
+        return self._query("workspace_bytes", B, T)
 
     def samples_of(self, frames: int) -> int:
         return self.hop_length * (int(frames) - 1)
@@ -185,6 +180,8 @@ class GriffinLim(_NativeModel):
     # -- the native handle -------------------------------------------------------------------
     def _upload_blob(self) -> np.ndarray:
         return self.inversion_tables()[0].reshape(-1)
+
+    _create = _NativeModel._create                     # iris_griffin_lim_create takes the array
 
     @staticmethod
     def _check_stream(seed, first_item, B: int) -> Tuple[int, int]:
@@ -295,13 +292,9 @@ class GriffinLim(_NativeModel):
 
     def _workspace_layout(self, B: int, T: int):
         """``({buffer: (offset, shape)}, floats)``: ``GlWorkspace`` (csrc/iris_griffin_lim.hip) restated -- S, c, r and the
-        in-loop waveform y in ``WsTaker`` order, each rounded up to 64 floats.  Host only."""
+        in-loop waveform y in ``WsTaker`` order.  Host only."""
         ks, qp = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8
-        layout, off = {}, 0
-        for name, shape in (("S", (B, T, ks)), ("c", (B, T, qp)), ("r", (B, T, qp)), ("y", (B, self.hop_length * (T - 1)))):
-            layout[name] = (off, shape)
-            off += (int(np.prod(shape)) + 63) // 64 * 64
-        return layout, off
+        return _take_shapes({"S": (B, T, ks), "c": (B, T, qp), "r": (B, T, qp), "y": (B, self.hop_length * (T - 1))})
 
     def _read_buffers(self, B: int, T: int) -> dict:
         """Test-only: the views ``S [B, T, Ks]``, ``c [B, T, Qp]``, ``r [B, T, Qp]`` and ``y [B, hop (T - 1)]`` of the workspace

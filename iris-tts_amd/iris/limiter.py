@@ -31,13 +31,13 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream
 
 TILE = 2048                                     # csrc/limiter.h: kTile, the output samples of a block
 MAX_LOOKAHEAD = 256                             # csrc/limiter.h: kMaxLookahead
 
 
-class Limiter(_NativeModel):
+class Limiter(_DeviceStage):
     """A limiter with fixed parameters, resident on one GPU (``device``, or the current one); the handle -- it owns the design
     table -- is built on first use.  ``ceiling_dbtp``: the true-peak ceiling in dB re full scale, at most 0; ``lookahead_ms``: how
     far ahead of a peak the gain starts to fall (and how far behind it has recovered), ``round(ms * rate / 1000)`` samples,
@@ -47,7 +47,7 @@ class Limiter(_NativeModel):
 
     def __init__(self, sample_rate: int = 22050, ceiling_dbtp: float = -1.0, lookahead_ms: float = 1.5,
                  device: Optional[torch.device] = None):
-        super().__init__()
+        super().__init__(device)
         if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or int(sample_rate) < 1:
             raise ValueError(f"sample_rate must be a positive integer, got {sample_rate!r}")
         if not float(ceiling_dbtp) <= 0.0:                      # False for NaN too
@@ -61,7 +61,6 @@ class Limiter(_NativeModel):
         if not 1 <= self.lookahead <= MAX_LOOKAHEAD:
             raise ValueError(f"lookahead_ms = {lookahead_ms!r} at {self.sample_rate} Hz is {self.lookahead} samples; 1 .. "
                              f"{MAX_LOOKAHEAD} are built")
-        self._want_device = None if device is None else torch.device(device)
         self.workspace_bytes(0, 0)                              # the library's own refusals, before any device work
 
     def get_config(self) -> dict:
@@ -81,61 +80,10 @@ class Limiter(_NativeModel):
 
     def launch_count(self, B: int, L: int, measure_only: bool = False) -> int:
         """Kernel launches of one call: 2, to limit or to measure (a dry run on the host, no device needed)."""
-        cfg, out = self.native_config(), ctypes.c_int32()
-        _native.check("iris_limiter_launch_count", _native.load().iris_limiter_launch_count(
-            ctypes.byref(cfg), int(B), int(L), int(bool(measure_only)), ctypes.byref(out)))
-        return int(out.value)
+        return self._query("launch_count", B, L, bool(measure_only))
 
     def workspace_bytes(self, B: int, L: int) -> int:
-        cfg, out = self.native_config(), ctypes.c_uint64()
-        _native.check("iris_limiter_workspace_bytes", _native.load().iris_limiter_workspace_bytes(
-            ctypes.byref(cfg), int(B), int(L), ctypes.byref(out)))
-        return int(out.value)
-
-    # -- the native handle -------------------------------------------------------------------
-    def _upload_blob(self) -> np.ndarray:
-        return np.zeros(0, dtype=np.float32)
-
-    def _create(self, lib, weights, n_weights, handle_ref) -> int:
-        cfg = self.native_config()
-        return lib.iris_limiter_create(ctypes.byref(cfg), handle_ref)
-
-    def _ensure(self):
-        if self._handle is None and self._want_device is not None:
-            with torch.cuda.device(self._want_device):
-                return super()._ensure()
-        return super()._ensure()
-
-    def close(self) -> None:
-        """Frees the native handle and the workspace; the next call builds them again."""
-        self._drop()
-
-    def _ws_for(self, B: int, L: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, L)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        return self._workspace
-
-    def _prepare(self, wav, lengths, row_scale):
-        if not isinstance(wav, torch.Tensor):
-            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
-        if wav.dim() != 2 or wav.dtype != torch.float32:
-            raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
-        if isinstance(row_scale, bool) or int(row_scale) != row_scale or int(row_scale) < 1:
-            raise ValueError(f"row_scale must be an integer >= 1, got {row_scale!r}")
-        B = int(wav.shape[0])
-        if lengths is not None and not isinstance(lengths, torch.Tensor):
-            host = np.asarray(lengths)
-            if host.shape != (B,) or (host.size and not np.issubdtype(host.dtype, np.integer)):
-                raise ValueError(f"lengths must be {B} integers, got {host.dtype} {host.shape}")
-            lengths = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
-        if lengths is not None and (tuple(lengths.shape) != (B,) or lengths.dtype not in (torch.int32, torch.int64)):
-            raise ValueError(f"lengths must be an integer tensor [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
-        lib = self._ensure()
-        wav = wav.to(self._device).contiguous()
-        if lengths is not None:
-            lengths = lengths.to(device=self._device, dtype=torch.int32).contiguous()
-        return lib, wav, lengths, B, int(wav.shape[1])
+        return self._query("workspace_bytes", B, L)
 
     def _empty_stats(self, B: int) -> torch.Tensor:
         stats = torch.empty((B, 2), dtype=torch.float32, device=self._device)
@@ -152,12 +100,12 @@ class Limiter(_NativeModel):
         ``lengths`` (a host sequence of integers or an integer tensor ``[B]``, which the host never reads) and ``row_scale``:
         item b owns ``min(L, lengths[b] * row_scale)`` samples, as in ``LoudnessNormalizer.normalize_device``, and nothing past
         them is read.  The same ``lengths`` and ``row_scale`` describe ``out`` to the next stage."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         out = torch.empty((B, L), dtype=torch.float32, device=self._device)          # the stage stores every element itself
         if B == 0 or L == 0:
             return out, self._empty_stats(B)
         stats = torch.empty((B, 2), dtype=torch.float32, device=self._device)
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_limiter_forward_ragged", lib.iris_limiter_forward_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(out), _ptr(stats), _ptr(ws),
@@ -166,11 +114,11 @@ class Limiter(_NativeModel):
 
     def true_peak_device(self, wav, lengths=None, row_scale: int = 1) -> torch.Tensor:
         """``stats [B, 2]`` fp32 of ``limit_device`` alone: the same 2 launches, and no sample is stored."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         if B == 0 or L == 0:
             return self._empty_stats(B)
         stats = torch.empty((B, 2), dtype=torch.float32, device=self._device)
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_limiter_measure_ragged", lib.iris_limiter_measure_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(stats), _ptr(ws),

@@ -32,12 +32,12 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream, _take_buffers
 
 SEG, CHUNK_SEGS = 64, 128                       # csrc/loudness.h: kSeg, kChunkSegs
 
 
-class LoudnessNormalizer(_NativeModel):
+class LoudnessNormalizer(_DeviceStage):
     """Loudness measurement and gain with fixed parameters, resident on one GPU (``device``, or the current one); the handle --
     it owns the filter design -- is built on first use.  ``target_lufs``: the integrated loudness every item is brought to;
     ``max_gain_db``: a cap on the boost; ``peak_ceiling``: None, or the sample peak in (0, 1] no item may exceed afterwards."""
@@ -46,7 +46,7 @@ class LoudnessNormalizer(_NativeModel):
 
     def __init__(self, sample_rate: int = 22050, target_lufs: float = -23.0, max_gain_db: float = 30.0,
                  peak_ceiling: Optional[float] = None, device: Optional[torch.device] = None):
-        super().__init__()
+        super().__init__(device)
         if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate:
             raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
         if peak_ceiling is not None and not 0.0 < float(peak_ceiling) <= 1.0:
@@ -54,7 +54,6 @@ class LoudnessNormalizer(_NativeModel):
         self.sample_rate = int(sample_rate)
         self.target_lufs, self.max_gain_db = float(target_lufs), float(max_gain_db)
         self.peak_ceiling = None if peak_ceiling is None else float(peak_ceiling)
-        self._want_device = None if device is None else torch.device(device)
         self.workspace_bytes(0, 0)                              # the library's own refusals, before any device work
 
     def get_config(self) -> dict:
@@ -76,29 +75,21 @@ class LoudnessNormalizer(_NativeModel):
 
     def launch_count(self, B: int, L: int, measure_only: bool = False) -> int:
         """Kernel launches of one call: 4, or 3 to measure (a dry run on the host, no device needed)."""
-        cfg, out = self.native_config(), ctypes.c_int32()
-        _native.check("iris_loudness_launch_count", _native.load().iris_loudness_launch_count(
-            ctypes.byref(cfg), int(B), int(L), int(bool(measure_only)), ctypes.byref(out)))
-        return int(out.value)
+        return self._query("launch_count", B, L, bool(measure_only))
 
     def workspace_bytes(self, B: int, L: int) -> int:
-        cfg, out = self.native_config(), ctypes.c_uint64()
-        _native.check("iris_loudness_workspace_bytes", _native.load().iris_loudness_workspace_bytes(
-            ctypes.byref(cfg), int(B), int(L), ctypes.byref(out)))
-        return int(out.value)
+        return self._query("workspace_bytes", B, L)
 
     def _workspace_layout(self, B: int, L: int):
         """``({buffer: (offset, shape, dtype)}, words)``: ``LdWorkspace`` (csrc/iris_loudness.hip) restated, offsets in 4-byte
-        words, each buffer rounded up to 64 of them.  Host only."""
+        words (a double is two).  Host only."""
         segs = -(-L // (SEG * CHUNK_SEGS)) * CHUNK_SEGS
         hop_cap = L // (self.sample_rate // 10) + 1
-        up = lambda n: (n + 63) // 64 * 64
-        layout, off = {}, 0
-        for name, shape, dtype, words in (("ends", (B, segs, 4), torch.float64, 2), ("parts", (B, segs, 2), torch.float64, 2),
-                                          ("hops", (B, hop_cap), torch.float64, 2), ("seg_peak", (B, segs), torch.float32, 1)):
-            layout[name] = (off, shape, dtype)
-            off += up(int(np.prod(shape)) * words)
-        return layout, off
+        bufs = {"ends": ((B, segs, 4), torch.float64), "parts": ((B, segs, 2), torch.float64),
+                "hops": ((B, hop_cap), torch.float64), "seg_peak": ((B, segs), torch.float32)}
+        layout, words = _take_buffers((name, int(np.prod(shape)) * (2 if dtype == torch.float64 else 1))
+                                      for name, (shape, dtype) in bufs.items())
+        return {name: (layout[name][0], *bufs[name]) for name in bufs}, words
 
     def _read_buffers(self, B: int, L: int) -> dict:
         """Test-only: copies of the workspace's buffers as the last call of shape (B, L) left them (only what belongs to an
@@ -110,51 +101,6 @@ class LoudnessNormalizer(_NativeModel):
             out[name] = self._workspace[4 * off:4 * (off + n)].view(dtype).view(shape).clone()
         return out
 
-    # -- the native handle -------------------------------------------------------------------
-    def _upload_blob(self) -> np.ndarray:
-        return np.zeros(0, dtype=np.float32)
-
-    def _create(self, lib, weights, n_weights, handle_ref) -> int:
-        cfg = self.native_config()
-        return lib.iris_loudness_create(ctypes.byref(cfg), handle_ref)
-
-    def _ensure(self):
-        if self._handle is None and self._want_device is not None:
-            with torch.cuda.device(self._want_device):
-                return super()._ensure()
-        return super()._ensure()
-
-    def close(self) -> None:
-        """Frees the native handle and the workspace; the next call builds them again."""
-        self._drop()
-
-    def _ws_for(self, B: int, L: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, L)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        return self._workspace
-
-    def _prepare(self, wav, lengths, row_scale):
-        if not isinstance(wav, torch.Tensor):
-            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
-        if wav.dim() != 2 or wav.dtype != torch.float32:
-            raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
-        if isinstance(row_scale, bool) or int(row_scale) != row_scale or int(row_scale) < 1:
-            raise ValueError(f"row_scale must be an integer >= 1, got {row_scale!r}")
-        B = int(wav.shape[0])
-        if lengths is not None and not isinstance(lengths, torch.Tensor):
-            host = np.asarray(lengths)
-            if host.shape != (B,) or (host.size and not np.issubdtype(host.dtype, np.integer)):
-                raise ValueError(f"lengths must be {B} integers, got {host.dtype} {host.shape}")
-            lengths = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
-        if lengths is not None and (tuple(lengths.shape) != (B,) or lengths.dtype not in (torch.int32, torch.int64)):
-            raise ValueError(f"lengths must be an integer tensor [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
-        lib = self._ensure()
-        wav = wav.to(self._device).contiguous()
-        if lengths is not None:
-            lengths = lengths.to(device=self._device, dtype=torch.int32).contiguous()
-        return lib, wav, lengths, B, int(wav.shape[1])
-
     # -- the calls ---------------------------------------------------------------------------
     def normalize_device(self, wav, lengths=None, row_scale: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """``wav [B, L]`` fp32, host or device -> ``(out [B, L] fp32, stats [B, 2] float64)`` on the device: item b scaled by
@@ -164,14 +110,14 @@ class LoudnessNormalizer(_NativeModel):
         ``lengths`` (a host sequence of integers or an integer tensor ``[B]``, which the host never reads) and ``row_scale``:
         item b owns ``min(L, lengths[b] * row_scale)`` samples -- mel frames and the vocoder's hop, or a stretch's ``counts``
         and 1 -- and nothing past them is read.  The same ``lengths`` and ``row_scale`` describe ``out`` to the next stage."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         out = torch.empty((B, L), dtype=torch.float32, device=self._device)          # the stage stores every element itself
         stats = torch.empty((B, 2), dtype=torch.float64, device=self._device)
         if B == 0 or L == 0:
             if B:
                 stats[:, 0], stats[:, 1] = 0.0, 1.0
             return out, stats
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_loudness_normalize_ragged", lib.iris_loudness_normalize_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(out), _ptr(stats), _ptr(ws),
@@ -180,13 +126,13 @@ class LoudnessNormalizer(_NativeModel):
 
     def measure_device(self, wav, lengths=None, row_scale: int = 1) -> torch.Tensor:
         """``stats [B, 2]`` float64 of ``normalize_device`` alone: the same first 3 launches, and no sample is stored."""
-        lib, wav, lengths, B, L = self._prepare(wav, lengths, row_scale)
+        lib, wav, lengths, B, L = self._ragged_wave(wav, lengths, row_scale)
         stats = torch.empty((B, 2), dtype=torch.float64, device=self._device)
         if B == 0 or L == 0:
             if B:
                 stats[:, 0], stats[:, 1] = 0.0, 1.0
             return stats
-        ws = self._ws_for(B, L)
+        ws = self._ws(B, L)
         with torch.cuda.device(self._device):
             _native.check("iris_loudness_measure_ragged", lib.iris_loudness_measure_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), int(row_scale), _ptr(stats), _ptr(ws),

@@ -26,10 +26,10 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream
 
 
-class MelFrontend(_NativeModel):
+class MelFrontend(_DeviceStage):
     """``compute_mel_spectrogram`` with fixed parameters, resident on one GPU.  The handle is built on first use."""
 
     _abi_name = "mel_frontend"
@@ -58,20 +58,12 @@ class MelFrontend(_NativeModel):
                                          self.fmin, 0.0 if self.fmax is None else self.fmax)
 
     # -- host-only queries -------------------------------------------------------------------
-    def _query(self, what: str, B: int, L: int, ctype) -> int:
-        lib = _native.load()
-        out = ctype()
-        cfg = self.native_config()
-        name = f"iris_mel_frontend_{what}"
-        _native.check(name, getattr(lib, name)(ctypes.byref(cfg), int(B), int(L), ctypes.byref(out)))
-        return int(out.value)
-
     def launch_count(self, B: int, L: int) -> int:
         """Kernel launches of one ``forward_device`` (a dry run on the host, no device needed)."""
-        return self._query("launch_count", B, L, ctypes.c_int32)
+        return self._query("launch_count", B, L)
 
     def workspace_bytes(self, B: int, L: int) -> int:
-        return self._query("workspace_bytes", B, L, ctypes.c_uint64)
+        return self._query("workspace_bytes", B, L)
 
     def frames_of(self, n_samples: int) -> int:
         return 1 + int(n_samples) // self.hop_length
@@ -92,13 +84,6 @@ class MelFrontend(_NativeModel):
         return dft, fb
 
     # -- the native handle -------------------------------------------------------------------
-    def _upload_blob(self) -> np.ndarray:
-        return np.zeros(0, dtype=np.float32)          # the library designs its own tables
-
-    def _create(self, lib, weights, n_weights, handle_ref) -> int:
-        cfg = self.native_config()
-        return lib.iris_mel_frontend_create(ctypes.byref(cfg), handle_ref)
-
     def _counts_dev(self, values, B: int, what: str) -> Optional[torch.Tensor]:
         if values is None:
             return None

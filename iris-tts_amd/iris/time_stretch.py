@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _DeviceStage, _ptr, _stream, _take_buffers, _take_shapes, _wave
 from .vae import _lengths_on, check_lengths
 
 RATE_RANGE = (0.25, 4.0)
@@ -50,7 +50,7 @@ def check_rate(rate) -> float:
     return r
 
 
-class TimeStretch(_NativeModel):
+class TimeStretch(_DeviceStage):
     """A phase vocoder with fixed transform parameters (librosa's defaults for this effect; 1024 / 256 works as well),
     resident on one GPU (``device``, or the current one); the handle is built on first use.  The rate belongs to a call."""
 
@@ -58,13 +58,12 @@ class TimeStretch(_NativeModel):
 
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, win_length: Optional[int] = None,
                  device: Optional[torch.device] = None):
-        super().__init__()
+        super().__init__(device)
         win_length = n_fft if win_length is None else win_length
         for name, v in (("n_fft", n_fft), ("hop_length", hop_length), ("win_length", win_length)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name} must be a positive integer, got {v!r}")
         self.n_fft, self.hop_length, self.win_length = int(n_fft), int(hop_length), int(win_length)
-        self._want_device = None if device is None else torch.device(device)
 
     @property
     def n_bins(self) -> int:
@@ -78,13 +77,6 @@ class TimeStretch(_NativeModel):
         return _native.MelFrontendConfig(22050, self.n_fft, self.hop_length, self.win_length, 1, 0, 0.0, 0.0)
 
     # -- host-only queries -------------------------------------------------------------------
-    def _query(self, name: str, *shape, rate) -> int:
-        lib = _native.load()
-        out = ctypes.c_uint64() if name.endswith("bytes") else ctypes.c_int32()
-        cfg = self.native_config()
-        _native.check(name, getattr(lib, name)(ctypes.byref(cfg), *[int(v) for v in shape], ctypes.c_double(float(rate)), ctypes.byref(out)))
-        return int(out.value)
-
     def out_frames_samples(self, L: int, rate) -> Tuple[int, int]:
         """``(T_out, n_out)`` of one item of ``L`` samples, from the library (the lines the device runs; no device needed)."""
         lib = _native.load()
@@ -100,22 +92,18 @@ class TimeStretch(_NativeModel):
 
     def launch_count(self, B: int, L: int, rate=1.0) -> int:
         """Kernel launches of one ``forward_device``: 4 (a dry run on the host, no device needed)."""
-        return self._query("iris_time_stretch_launch_count", B, L, rate=rate)
+        return self._query("launch_count", B, L, rate)
 
     def workspace_bytes(self, B: int, L: int, rate=1.0) -> int:
-        return self._query("iris_time_stretch_workspace_bytes", B, L, rate=rate)
+        return self._query("workspace_bytes", B, L, rate)
 
     def _workspace_layout(self, B: int, L: int, rate):
         """``({buffer: (offset, shape)}, floats)``: ``TsWorkspace`` (csrc/iris_time_stretch.hip) restated -- the taps, then the
-        items' ``frames``, ``frames_out`` and ``counts`` (int32), in ``WsTaker`` order, each rounded up to 64 floats.  Host only."""
+        items' ``frames``, ``frames_out`` and ``counts`` (int32), in ``WsTaker`` order.  Host only."""
         T, (T_out, _) = L // self.hop_length + 1, self.out_frames_samples(L, rate)
         ks, qp = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8
-        layout, off = {}, 0
-        for name, shape in (("c", (B, T, qp)), ("mag", (B, T_out, ks)), ("inc", (B, T_out, ks)), ("acc", (B, T_out, ks)),
-                            ("out_c", (B, T_out, qp)), ("frames", (B,)), ("frames_out", (B,)), ("counts", (B,))):
-            layout[name] = (off, shape)
-            off += (int(np.prod(shape)) + 63) // 64 * 64
-        return layout, off
+        return _take_shapes({"c": (B, T, qp), "mag": (B, T_out, ks), "inc": (B, T_out, ks), "acc": (B, T_out, ks),
+                             "out_c": (B, T_out, qp), "frames": (B,), "frames_out": (B,), "counts": (B,)})
 
     def _read_buffers(self, B: int, L: int, rate) -> dict:
         """Test-only: copies of the taps ``c``, ``mag``, ``out_c`` (fp32) and ``inc``, ``acc`` (as int64 in [0, 2^32)) and of the
@@ -131,39 +119,8 @@ class TimeStretch(_NativeModel):
                 out[name] = v.to(torch.int64) & 0xFFFFFFFF if name in ("inc", "acc") else v
         return out
 
-    # -- the native handle -------------------------------------------------------------------
-    def _upload_blob(self) -> np.ndarray:
-        return np.zeros(0, dtype=np.float32)
-
-    def _create(self, lib, weights, n_weights, handle_ref) -> int:
-        cfg = self.native_config()
-        return lib.iris_time_stretch_create(ctypes.byref(cfg), handle_ref)
-
-    def _ensure(self):
-        if self._handle is None and self._want_device is not None:
-            with torch.cuda.device(self._want_device):
-                return super()._ensure()
-        return super()._ensure()
-
-    def close(self) -> None:
-        """Frees the native handle and the workspace; the next call builds them again."""
-        self._drop()
-
-    def _ws_for(self, B: int, L: int, rate: float) -> torch.Tensor:
-        need = self.workspace_bytes(B, L, rate)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        return self._workspace
-
     def _wav_on_device(self, wav) -> torch.Tensor:
-        if not isinstance(wav, torch.Tensor):
-            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
-        if wav.dim() != 2 or wav.dtype != torch.float32:
-            raise ValueError(f"expected a waveform [B, L] float32, got {wav.dtype} {tuple(wav.shape)}")
-        if wav.shape[1] % self.hop_length:
-            raise ValueError(f"L = {wav.shape[1]} is not a multiple of hop_length = {self.hop_length}: a vocoder emits whole mel "
-                             "frames; nothing is padded silently")
-        return wav
+        return _wave(wav, self.hop_length, "a vocoder emits whole mel frames")
 
     # -- the forward -------------------------------------------------------------------------
     def forward_device(self, wav, rate, lengths=None):
@@ -189,7 +146,7 @@ class TimeStretch(_NativeModel):
         counts = torch.full((B,), n_out, dtype=torch.int32, device=self._device)
         if B == 0 or L == 0:
             return out, counts
-        ws = self._ws_for(B, L, rate)
+        ws = self._ws(B, L, rate)
         with torch.cuda.device(self._device):
             _native.check("iris_time_stretch_forward_ragged", lib.iris_time_stretch_forward_ragged(
                 self._handle, _ptr(wav), B, L, _ptr(lengths), ctypes.c_double(rate), _ptr(out), _ptr(counts), _ptr(ws),
@@ -209,10 +166,7 @@ class TimeStretch(_NativeModel):
 
     # -- windows of an utterance -------------------------------------------------------------
     def state_bytes(self, B: int) -> int:
-        lib = _native.load()
-        cfg, out = self.native_config(), ctypes.c_uint64()
-        _native.check("iris_time_stretch_state_bytes", lib.iris_time_stretch_state_bytes(ctypes.byref(cfg), int(B), ctypes.byref(out)))
-        return int(out.value)
+        return self._query("state_bytes", B)
 
     def new_state(self, B: int) -> torch.Tensor:
         """The state a sequence of ``forward_window`` calls carries (``iris_time_stretch_state_bytes``): the phase at the next
@@ -223,7 +177,7 @@ class TimeStretch(_NativeModel):
     def _state_views(self, state: torch.Tensor, B: int):
         """Test-only: ``(acc [B, Ks] as int64 in [0, 2^32), tail [B, taps - 1, Qp] fp32)``, views restated from ``TsState``."""
         ks, qp, rows = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8, self.n_fft // self.hop_length - 1
-        tail_off = (B * ks + 63) // 64 * 64
+        tail_off = _take_buffers((("acc", B * ks), ("tail", B * rows * qp)))[0]["tail"][0]
         acc = state.view(torch.int32)[:B * ks].view(B, ks).to(torch.int64) & 0xFFFFFFFF
         return acc, state.view(torch.float32)[tail_off:tail_off + B * rows * qp].view(B, rows, qp)
 
@@ -240,30 +194,23 @@ class TimeStretch(_NativeModel):
         return tuple(int(v.value) for v in out)
 
     def window_workspace_bytes(self, B: int, Lw: int, rate=1.0) -> int:
-        return self._query("iris_time_stretch_window_workspace_bytes", B, Lw, rate=rate)
+        return self._query("window_workspace_bytes", B, Lw, rate)
 
     def window_launch_count(self, B: int, Lw: int, rate, origin: int, final: bool, u: int) -> int:
         """Kernel launches of one ``forward_window``: 4; 3 where frames advance but no sample is emitted yet, 2 where a final
         window has samples left but no frame, 0 where it has neither (a dry run on the host)."""
-        lib = _native.load()
-        cfg, n = self.native_config(), ctypes.c_int32()
-        _native.check("iris_time_stretch_window_launch_count", lib.iris_time_stretch_window_launch_count(
-            ctypes.byref(cfg), int(B), int(Lw), ctypes.c_double(float(rate)), ctypes.c_int64(int(origin)), int(bool(final)),
-            ctypes.c_int64(int(u)), ctypes.byref(n)))
-        return int(n.value)
+        return self._query("window_launch_count", B, Lw, rate, origin, bool(final), u)
 
     def _window_workspace_layout(self, B: int, Lw: int, rate, frames: int, new: int, tail: int):
         """``{buffer: (offset, shape)}``: ``TsWindowWorkspace`` restated for a window that computed ``frames`` input rows and
         ``new`` output frames behind ``tail`` carried ones.  Offsets depend on (B, Lw, rate) alone.  Host only."""
         ks, qp, taps = (self.n_bins + 3) // 4 * 4, (self.n_fft + 2 + 7) // 8 * 8, self.n_fft // self.hop_length
         F, n = Lw // self.hop_length + 1, math.ceil((Lw // self.hop_length + 1) / float(rate)) + 1
-        layout, off = {}, 0
-        for name, room, shape in (("c", B * F * qp, (B, frames, qp)), ("mag", B * n * ks, (B, new, ks)), ("inc", B * n * ks, (B, new, ks)),
-                                  ("acc", B * n * ks, (B, new, ks)), ("out_c", B * (n + taps - 1) * qp, (B, tail + new, qp))):
-            assert int(np.prod(shape)) <= room
-            layout[name] = (off, shape, room)
-            off += (room + 63) // 64 * 64
-        return layout
+        bufs = {"c": (B * F * qp, (B, frames, qp)), "mag": (B * n * ks, (B, new, ks)), "inc": (B * n * ks, (B, new, ks)),
+                "acc": (B * n * ks, (B, new, ks)), "out_c": (B * (n + taps - 1) * qp, (B, tail + new, qp))}
+        assert all(int(np.prod(shape)) <= room for room, shape in bufs.values())
+        layout, _ = _take_buffers((name, room) for name, (room, _) in bufs.items())
+        return {name: (layout[name][0], shape, room) for name, (room, shape) in bufs.items()}
 
     def forward_window(self, wav, rate, origin: int, final: bool, u: int, state: Optional[torch.Tensor]) -> torch.Tensor:
         """``wav [B, Lw]`` fp32 = samples ``[origin, origin + Lw)`` of an utterance (both multiples of ``hop_length``) -> the
@@ -280,10 +227,7 @@ class TimeStretch(_NativeModel):
         if B == 0 or (u_hi == u and count == 0):
             return out
         wav = wav.to(self._device).contiguous()
-        need = self.window_workspace_bytes(B, Lw, rate)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=self._device)
-        ws = self._workspace
+        ws = self._grow(self.window_workspace_bytes(B, Lw, rate))
         with torch.cuda.device(self._device):
             _native.check("iris_time_stretch_forward_window", lib.iris_time_stretch_forward_window(
                 self._handle, _ptr(wav), B, Lw, ctypes.c_int64(int(origin)), int(bool(final)), ctypes.c_double(rate), ctypes.c_int64(int(u)),

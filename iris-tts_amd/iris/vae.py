@@ -58,7 +58,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native_model import _NativeModel, _ptr, _stream
+from ._native_model import _NativeModel, _ptr, _stream, _take_buffers
 
 
 def check_lengths(lengths, B: int, T: int, factor: int):
@@ -88,15 +88,6 @@ def _lengths_on(lengths, device) -> torch.Tensor:
     if not isinstance(lengths, torch.Tensor):
         lengths = torch.from_numpy(lengths)
     return lengths.to(device).contiguous()
-
-
-def _take_buffers(sizes):
-    """``WsTaker`` (csrc/stage_host.h): the buffers one behind the other, each rounded up to 64 floats."""
-    layout, off = {}, 0
-    for name, n in sizes:
-        layout[name] = (off, n)
-        off += (n + 63) & ~63
-    return layout, off
 
 
 def _read_buffers(model, layout, total):

@@ -68,7 +68,7 @@ def poisoned_forward(ts: TimeStretch, wav, rate, lengths=None):
     """A forward into a workspace that held NaN in every byte the layout names."""
     wav = wav if isinstance(wav, torch.Tensor) else torch.from_numpy(np.array(wav))      # a copy: the cases' arrays are read-only
     ts._ensure()
-    ts._ws_for(int(wav.shape[0]), int(wav.shape[1]), rate).view(torch.float32).fill_(NAN)
+    ts._ws(int(wav.shape[0]), int(wav.shape[1]), rate).view(torch.float32).fill_(NAN)
     return ts.forward_device(wav, rate, lengths=lengths)
 
 

@@ -61,7 +61,7 @@ def run(name, wav, rate, lengths=None):
     ts = model(name)
     B, L = wav.shape
     ts._ensure()
-    ts._ws_for(B, L, rate).view(torch.float32).fill_(NAN)
+    ts._ws(B, L, rate).view(torch.float32).fill_(NAN)
     t = torch.full((B, ts.out_samples(L, rate)), NAN, dtype=torch.float32, device=DEV)   # the block the next torch.empty most likely gets
     torch.cuda.synchronize()
     del t
