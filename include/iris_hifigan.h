@@ -1070,6 +1070,32 @@ int32_t iris_limiter_measure_ragged(iris_limiter_handle* h, const float* wav_dev
                                     const int32_t* lengths_dev /* or NULL */, int32_t row_scale, float* stats_out_dev /* [B][2] */,
                                     void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* Windows: the limiter on samples [origin, origin + Lw) of B utterances of one length, for a caller that receives the waveform
+ * piece by piece.  Any origin >= 0 and any Lw >= 0; `final` (0 or not) says that origin + Lw is the utterance's end, and the
+ * window starts its utterance when origin == 0.  out[n] reads x[n - R .. n + R] and nothing else, R = 2 * lookahead + 7, so a
+ * window settles the samples for which all of that lies inside the window or outside the utterance (where the whole-item call
+ * also uses x = 0 and r = 1):
+ *     window_range -> out_lo = origin + (origin > 0 ? R : 0) and out_count = max(0, origin + Lw - (final ? 0 : R) - out_lo).
+ * An interior window loses R samples on either side: 73 at the default 1.5 ms and 22.05 kHz, 519 at lookahead 256.
+ * forward_window: wav_dev [B, Lw] -> out_dev [B, out_count], packed rows, each sample bit for bit that of
+ * iris_limiter_forward_ragged on the whole utterance; with out_is_pcm16 != 0 out_dev is int16 and holds (int16) rintf(clamp(out,
+ * -1, 1) * 32767) of the same samples, the output stage's formula (the ceiling is at most 1, so the clamp never acts).
+ * stats_out_dev [B][2] = (max p, min g) over the window's settled samples: the running (max, min) over an utterance's windows is
+ * the whole-item call's stats.  Dense only; stateless; the same 2 launches with tiles over the settled samples, none when B == 0
+ * or out_count == 0 (IRIS_HIFIGAN_OK, nothing is looked at).  The workspace is that of a call of shape (B, Lw); afterwards it
+ * holds the partials [B][ceil(out_count / 2048)][2].  A negative origin or shape, a NULL pointer, out_dev off its type's
+ * bytes or overlapping wav_dev return IRIS_HIFIGAN_INVALID_ARGUMENT; origin + Lw beyond int64, B > 65535 and B Lw above 2^31 - 1
+ * IRIS_HIFIGAN_UNSUPPORTED; a short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches; nothing synchronises.
+ * The first three are host only; window_launch_count is a dry run. */
+int32_t iris_limiter_window_range(const iris_limiter_config* cfg, int64_t origin, int32_t Lw, int32_t final, int64_t* out_lo,
+                                  int64_t* out_count);
+int32_t iris_limiter_window_workspace_bytes(const iris_limiter_config* cfg, int32_t B, int32_t Lw, uint64_t* bytes);
+int32_t iris_limiter_window_launch_count(const iris_limiter_config* cfg, int32_t B, int32_t Lw, int64_t origin, int32_t final,
+                                         int32_t* n);
+int32_t iris_limiter_forward_window(iris_limiter_handle* h, const float* wav_dev /* [B, Lw] */, int32_t B, int32_t Lw, int64_t origin,
+                                    int32_t final, void* out_dev /* [B, out_count] fp32 or int16 */, int32_t out_is_pcm16,
+                                    float* stats_out_dev /* [B][2] */, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

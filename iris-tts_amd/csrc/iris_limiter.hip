@@ -1,7 +1,9 @@
 // iris_limiter.hip -- the iris_limiter_* entry points of include/iris_hifigan.h: a look-ahead true-peak limiter per item of a
 // ragged batch of waveforms (csrc/limiter.h holds the rules and the kernels).  forward_ragged is 2 launches: the fused tile
 // kernel, which stores the samples and every tile's (max p, min g), and the per-item reduction of those into stats.
-// measure_ragged is the same two without the samples.  The handle owns the design table (the interpolation bank and the
+// measure_ragged is the same two without the samples.  forward_window is the same two on a window of an utterance, storing the
+// samples the window settles (limiter::Window in csrc/limiter.h) as fp32 or as 16-bit PCM: a session that pushes consecutive
+// windows reproduces the whole-item call bit for bit.  The handle owns the design table (the interpolation bank and the
 // smoothing weights); the host never reads a length.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -58,17 +60,27 @@ struct LmWorkspace {
     }
 };
 
+// What a call runs on: a ragged batch of whole items [B, L], or a window [B, Lw] of B utterances (limiter::Window).
+struct LmRows {
+    int in_len;                 // L, or Lw
+    int offset, n_out;          // the row's sample that is output 0, and the outputs of a row: 0 and L, or the window's settled range
+    const int32_t* lengths;     // whole items only (device, or NULL); the host never reads it
+    int row_scale;
+    bool pcm16;                 // out is int16: windows only
+};
+
 // Queues the launches (or, in a dry run, counts them).  out == nullptr: measure only.
-int lm_forward(const LmPlan& p, const float* table, const float* wav, int B, int L, const int32_t* lengths, int row_scale, float* out, float* stats,
-               float* ws, hipStream_t stream) {
-    const LmWorkspace lay(B, L);
+int lm_forward(const LmPlan& p, const float* table, const float* wav, int B, const LmRows& r, void* out, float* stats, float* ws, hipStream_t stream) {
+    const LmWorkspace lay(B, r.n_out);
     limiter::TileLaunch tl; memset(&tl, 0, sizeof(tl));
-    tl.wav = wav; tl.lengths = lengths; tl.row_scale = row_scale; tl.table = table; tl.out = out; tl.parts = ws + lay.parts;
-    tl.L = L; tl.tiles = lay.tiles; tl.A = p.A; tl.ceiling = p.ceiling;
-    HIP_TRY(limiter::launch_tile(tl, B, stream));
+    tl.wav = wav; tl.lengths = r.lengths; tl.row_scale = r.row_scale; tl.table = table; tl.out = out; tl.parts = ws + lay.parts;
+    tl.in_len = tl.in_stride = r.in_len; tl.offset = r.offset; tl.n_out = tl.out_stride = r.n_out;
+    tl.tiles = lay.tiles; tl.A = p.A; tl.ceiling = p.ceiling;
+    HIP_TRY(limiter::launch_tile(tl, B, r.pcm16, stream));
 
     limiter::StatsLaunch st; memset(&st, 0, sizeof(st));
-    st.lengths = lengths; st.row_scale = row_scale; st.parts = tl.parts; st.stats = stats; st.L = L; st.tiles = lay.tiles;
+    st.lengths = r.lengths; st.row_scale = r.row_scale; st.parts = tl.parts; st.stats = stats;
+    st.in_len = r.in_len; st.offset = r.offset; st.n_out = r.n_out; st.tiles = lay.tiles;
     HIP_TRY(limiter::launch_stats(st, B, stream));
     return IRIS_HIFIGAN_OK;
 }
@@ -81,8 +93,21 @@ int lm_run(iris_limiter_handle* h, const float* wav_dev, int32_t B, int32_t L, c
             TRY(check_wave_shape(B, L));
             *out_floats = (size_t)B * L; *ws_floats = LmWorkspace(B, L).floats;
             return IRIS_HIFIGAN_OK; },
-        [&] { return lm_forward(h->p, h->blob, wav_dev, B, L, lengths_dev, row_scale, apply ? out_dev : nullptr, stats_out_dev,
-                                (float*)workspace_dev, (hipStream_t)stream); });
+        [&] { const LmRows rows = {L, 0, L, lengths_dev, row_scale, false};
+              return lm_forward(h->p, h->blob, wav_dev, B, rows, apply ? out_dev : nullptr, stats_out_dev, (float*)workspace_dev, (hipStream_t)stream); });
+}
+
+// A window's shape and place: [B, Lw] in 32-bit offsets, one item per grid.y, and origin + Lw an int64 sample index.
+int lm_check_window(int32_t B, int32_t Lw, int64_t origin) {
+    TRY(check_wave_shape(B, Lw));
+    if (origin < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin = %lld is negative", (long long)origin);
+    if (origin > INT64_MAX - (int64_t)Lw)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "origin = %lld, Lw = %d: the window's end exceeds int64 sample indexing", (long long)origin, Lw);
+    return IRIS_HIFIGAN_OK;
+}
+
+LmRows lm_window_rows(int32_t Lw, const limiter::Window& w, bool pcm16) {
+    return LmRows{Lw, w.offset, (int)w.out_count, nullptr, 1, pcm16};
 }
 
 }  // namespace
@@ -118,7 +143,8 @@ int32_t iris_limiter_launch_count(const iris_limiter_config* cfg, int32_t B, int
     TRY(lm_validate(cfg, &p));
     TRY(check_wave_shape(B, L));
     return count_forward_launches(B == 0 || L == 0, [&](float* fake) {
-        return lm_forward(p, fake, fake, B, L, nullptr, 1, measure_only ? nullptr : fake, fake, fake, nullptr); }, n);
+        const LmRows rows = {L, 0, L, nullptr, 1, false};
+        return lm_forward(p, fake, fake, B, rows, measure_only ? nullptr : fake, fake, fake, nullptr); }, n);
     IRIS_ABI_END
 }
 
@@ -154,6 +180,54 @@ int32_t iris_limiter_measure_ragged(iris_limiter_handle* h, const float* wav_dev
                                     float* stats_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
     IRIS_ABI_BEGIN
     return lm_run(h, wav_dev, B, L, lengths_dev, row_scale, nullptr, false, stats_out_dev, workspace_dev, workspace_bytes, stream);
+    IRIS_ABI_END
+}
+
+int32_t iris_limiter_window_range(const iris_limiter_config* cfg, int64_t origin, int32_t Lw, int32_t final, int64_t* out_lo, int64_t* out_count) {
+    IRIS_ABI_BEGIN
+    if (!out_lo || !out_count) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    LmPlan p;
+    TRY(lm_validate(cfg, &p));
+    TRY(lm_check_window(1, Lw, origin));
+    const limiter::Window w(p.A, origin, Lw, final != 0);
+    *out_lo = w.out_lo; *out_count = w.out_count;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_limiter_window_workspace_bytes(const iris_limiter_config* cfg, int32_t B, int32_t Lw, uint64_t* bytes) {
+    return iris_limiter_workspace_bytes(cfg, B, Lw, bytes);                  // the partials of at most ceil(Lw / kTile) tiles per item
+}
+
+int32_t iris_limiter_window_launch_count(const iris_limiter_config* cfg, int32_t B, int32_t Lw, int64_t origin, int32_t final, int32_t* n) {
+    IRIS_ABI_BEGIN
+    if (!n) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    LmPlan p;
+    TRY(lm_validate(cfg, &p));
+    TRY(lm_check_window(B, Lw, origin));
+    const limiter::Window w(p.A, origin, Lw, final != 0);
+    return count_forward_launches(B == 0 || w.out_count == 0, [&](float* fake) {
+        return lm_forward(p, fake, fake, B, lm_window_rows(Lw, w, false), fake, fake, fake, nullptr); }, n);
+    IRIS_ABI_END
+}
+
+int32_t iris_limiter_forward_window(iris_limiter_handle* h, const float* wav_dev, int32_t B, int32_t Lw, int64_t origin, int32_t final, void* out_dev,
+                                    int32_t out_is_pcm16, float* stats_out_dev, void* workspace_dev, uint64_t workspace_bytes, void* stream) {
+    IRIS_ABI_BEGIN
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    TRY(lm_check_window(B, Lw, origin));
+    const limiter::Window w(h->p.A, origin, Lw, final != 0);
+    if (w.out_count == 0) return IRIS_HIFIGAN_OK;                            // nothing is settled: nothing is looked at or launched
+    const bool pcm16 = out_is_pcm16 != 0;
+    if (out_dev && ((uintptr_t)out_dev & (pcm16 ? 1u : 3u))) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev must lie on %d bytes", pcm16 ? 2 : 4);
+    const RaggedWaveCall call = {wav_dev, B, Lw, 1, (const float*)out_dev, true, stats_out_dev, 4, workspace_dev, 8, workspace_bytes};
+    return run_ragged_wave(h, call,
+        [&](size_t* out_floats, size_t* ws_floats) -> int {
+            const size_t n = (size_t)B * (size_t)w.out_count;
+            *out_floats = pcm16 ? (n + 1) / 2 : n; *ws_floats = LmWorkspace(B, Lw).floats;      // what window_workspace_bytes states
+            return IRIS_HIFIGAN_OK; },
+        [&] { return lm_forward(h->p, h->blob, wav_dev, B, lm_window_rows(Lw, w, pcm16), out_dev, stats_out_dev, (float*)workspace_dev,
+                                (hipStream_t)stream); });
     IRIS_ABI_END
 }
 

@@ -52,11 +52,46 @@
 // barriers between the passes; a tile of 4096 would halve the halo's share (25 % of the work at A = 256, 3 % at A = 33) but
 // leave 2 blocks per CU at A = 256, and 1024 doubles the halo's share for nothing: the LDS is not the limit at 2048.  256
 // threads x 8 consecutive outputs is exactly one tile, which the register window of the smoothing needs.
+//
+// Windows (iris_limiter_*_window*): the same two launches on a piece of an utterance, for a caller that receives it piece by piece.
+// A window is wav [B, Lw], the samples [origin, origin + Lw) of B utterances of one length; it starts its utterance when origin
+// == 0 and ends it when `final` is set.  By the rules above out[n] reads x[n - R .. n + R] and nothing else, R = halo(A) = 2A + 7
+// (g reads m within A, m reads r within A, r reads u[n - 1] and u[n], u reads x[n - 5 .. n + 6]; R is the tile's halo, which has
+// one sample to spare on either side).  A sample is *settled* by a window when all of that lies inside the window or outside
+// the utterance, where the one-shot call also uses x = 0 and r = 1.  That is the finality rule, and struct Window below is the
+// one place it is written down:
+//     out_lo = origin + (origin > 0 ? R : 0);  out_hi = origin + Lw - (final ? 0 : R);  count = max(0, out_hi - out_lo)
+// so the last R samples of a window that is not final are held back for the next one, which must begin at or before
+// (first sample not yet settled) - R.
+// One kernel body serves both.  A launch names the input row (in_len readable samples, in_stride apart), the row's sample that
+// is output 0 (`offset`: 0 for a whole item, out_lo - origin for a window) and the outputs (n_out per row, out_stride apart:
+// a window's rows are packed, [B, count]).  Tile i owns outputs [i kTile, (i + 1) kTile) of the n_out, so a window's tiles cover
+// settled samples only, and a tile stages its halo from the window's own context instead of recomputing a tile that would be
+// thrown away.  forward_ragged / measure_ragged are the case offset = 0, in_len = in_stride = n_out = out_stride = L with
+// `lengths` as before: every index and every operation is then what it was, and so is every bit.
+// Two kinds of edge meet the staging (`lo`, `hi`: the slots that are samples of the row).  Beyond an end of the utterance --
+// slots in front of sample 0 of a window with origin == 0, slots behind L_b, or behind the last sample of a final window --
+// x = 0 and r = 1, as the rules say.  Beyond an end of a window that is not an end of the utterance lie real samples that the
+// kernel does not have; it stages 0 and r = 1 there too, and that is harmless only because of the finality rule: no settled
+// output reads such a slot, nor any r, m or d computed from one.  The tile's (max p, min g) are taken over its settled outputs
+// alone (`own`), never over the held-back samples that share the tile.
+// The tile seams of a window fall on other samples than those of the one-shot call.  The bits do not move: every rule is per
+// sample, a maximum and a minimum are exact, and every chain (u, s) has its one stated order whatever tile it is computed in.
+// The shortcut "no r < 1 within 2A of the tile -> g = 1.0f" holds too: where it does not fire in one tiling and fires in the
+// other, the chain it skips is fmaf(+0, w, +0) throughout and 1.0f - 0 = 1.0f.
+// The store is 16 bytes at a time where the OUTPUT ROW's own address at the tile's first output lies on 16 bytes -- out_lo is in
+// general no multiple of 4 and packed rows of `count` samples start anywhere -- and scalars otherwise.  tile_kernel<true> is the
+// same body with a 16-bit store: pcm::pcm16_of(out) of pcm_out.h, (int16) rintf(clamp(out, -1, 1) * 32767), 8 bytes at a time on
+// the same condition at 8 bytes.  |out| <= c <= 1, so that clamp never acts, and the result is the output stage's on the fp32
+// samples, bit for bit.  Window statistics are stats [B, 2] = (max p, min g) over the window's settled samples: the reduction
+// runs over the window's own ceil(count / kTile) tiles.  A window that settles nothing launches nothing.
+// Nothing about the speed of a window has been measured on a GPU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "device_info.h"
+#include "pcm_out.h"
 #include "resample.h"
 
 namespace iris {
@@ -101,14 +136,30 @@ __host__ __device__ inline int buf_floats(int A) {
 __host__ __device__ inline int w_floats(int A) { return (2 * A + 1 + 3) & ~3; }
 inline size_t lds_bytes(int A) { return (size_t)(x_floats(A) + 2 * buf_floats(A) + w_floats(A)) * sizeof(float); }
 
+// The samples of an utterance that a window [origin, origin + Lw) settles: the finality rule, written down here once.
+struct Window {
+    long long out_lo, out_count;    // an index into the utterance; a count that may be 0
+    int offset;                     // out_lo - origin: where the first settled sample lies in the window's row
+    Window(int A, long long origin, int Lw, bool final) {
+        const long long R = halo(A);
+        out_lo = origin + (origin > 0 ? R : 0);
+        const long long out_hi = origin + Lw - (final ? 0 : R);
+        out_count = out_hi > out_lo ? out_hi - out_lo : 0;
+        offset = (int)(out_lo - origin);
+    }
+};
+
 struct TileLaunch {
-    const float* wav;           // [B, L] fp32
+    const float* wav;           // [B] rows of in_stride fp32, of which [0, in_len) may be read
     const int32_t* lengths;     // ragged: rows of each item [B] (device), or nullptr
     int row_scale;
     const float* table;         // [kBank + 2A + 1]: the design table
-    float* out;                 // [B, L], or nullptr: measure only
+    void* out;                  // [B] rows of out_stride fp32 (or int16: tile_kernel<true>), or nullptr: measure only
     float* parts;               // [B][tiles][2]: max p, min g of the tile's own samples
-    int L, tiles, A;
+    int in_len, in_stride;      // a whole item: L, L;  a window: Lw, Lw
+    int offset;                 // the row's sample that is output 0: 0, or Window::offset
+    int n_out, out_stride;      // outputs of a row and the row's stride: L, L, or the window's count twice (rows are packed)
+    int tiles, A;               // tiles = ceil(n_out / kTile)
     float ceiling;
 };
 
@@ -126,46 +177,67 @@ __device__ __forceinline__ float block_extreme(float v, float* red) {
     return r;
 }
 
+typedef short mi16x4 __attribute__((ext_vector_type(4)));
+
+// Four consecutive outputs, of which the first n (1 .. 4) exist: one store of 16 bytes (8 as PCM) where `vec` says that the
+// row's own address allows it and all four exist, scalars otherwise.
+template <bool PCM>
+__device__ __forceinline__ void store4(void* row, int q, const mf32x4& y, int n, bool vec) {
+    if constexpr (PCM) {
+        int16_t* o = static_cast<int16_t*>(row) + q;
+        if (vec && n >= 4) {
+            *reinterpret_cast<mi16x4*>(o) = mi16x4{pcm::pcm16_of(y[0]), pcm::pcm16_of(y[1]), pcm::pcm16_of(y[2]), pcm::pcm16_of(y[3])};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < n) o[e] = pcm::pcm16_of(y[e]);
+        }
+    } else {
+        float* o = static_cast<float*>(row) + q;
+        if (vec && n >= 4) {
+            *reinterpret_cast<mf32x4*>(o) = y;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (e < n) o[e] = y[e];
+        }
+    }
+}
+
+template <bool PCM>
 __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x, A = a.A, H = halo(A);
-    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);
-    const long long t0 = (long long)blockIdx.x * kTile;
-    const int in_row = a.L - t0 < kTile ? (int)(a.L - t0) : kTile;                // outputs of this tile that exist (>= 1)
-    float* orow = a.out ? a.out + (size_t)b * a.L + t0 : nullptr;
-    const bool vec = orow && ((uintptr_t)orow & 15) == 0;
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.in_len);    // the row's samples [0, Lb) are the ones that exist here
+    const long long t0 = (long long)blockIdx.x * kTile;                // the tile's first output
+    const long long s0 = t0 + a.offset;                                // ... and the row's sample it is
+    const int in_row = a.n_out - t0 < kTile ? (int)(a.n_out - t0) : kTile;        // outputs of this tile that exist (>= 1)
+    constexpr size_t kOutBytes = PCM ? sizeof(int16_t) : sizeof(float);
+    char* orow = a.out ? static_cast<char*>(a.out) + ((size_t)b * a.out_stride + t0) * kOutBytes : nullptr;
+    const bool vec = orow && ((uintptr_t)orow & (4 * kOutBytes - 1)) == 0;        // the output row's own address
 
-    if (t0 >= Lb) {                                                 // behind the item: its zeros, no partials
+    if (s0 >= Lb) {                                                 // behind the item: its zeros, no partials
         if (!orow) return;
-        for (int q = 4 * tid; q < in_row; q += 4 * kThreads) {
-            if (vec && q + 3 < in_row) {
-                *reinterpret_cast<mf32x4*>(orow + q) = mf32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (q + e < in_row) orow[q + e] = 0.f;
-            }
-        }
+        for (int q = 4 * tid; q < in_row; q += 4 * kThreads) store4<PCM>(orow, q, mf32x4{0.f, 0.f, 0.f, 0.f}, in_row - q, vec);
         return;
     }
-    const int own = Lb - t0 < kTile ? (int)(Lb - t0) : kTile;       // the item's own samples in this tile (>= 1)
+    const int own = Lb - s0 < in_row ? (int)(Lb - s0) : in_row;     // the tile's outputs that are the item's own samples (>= 1)
 
-    float* xs = lds;                                                // slot i: sample t0 - H + i
+    float* xs = lds;                                                // slot i: the row's sample s0 - H + i
     float* P = xs + x_floats(A);
     float* Q = P + buf_floats(A);
     float* wl = Q + buf_floats(A);
     const int nx = kTile + 2 * H;
-    const int lo = t0 >= H ? 0 : (int)(H - t0);                     // slots [lo, hi) are the item's own samples
-    const int hi = own + H + (Lb - t0 - own < H ? (int)(Lb - t0 - own) : H);
+    const int lo = s0 >= H ? 0 : (int)(H - s0);                     // slots [lo, hi) are samples of the row that exist: the rest
+    const int hi = Lb - s0 + H < nx ? (int)(Lb - s0 + H) : nx;      // is 0 and r = 1, as beyond an end of the utterance
     {
-        const float* __restrict__ x = a.wav + (size_t)b * a.L;
-        for (int i = tid; i < nx; i += kThreads) xs[i] = (i >= lo && i < hi) ? x[t0 - H + i] : 0.f;
+        const float* __restrict__ x = a.wav + (size_t)b * a.in_stride;
+        for (int i = tid; i < nx; i += kThreads) xs[i] = (i >= lo && i < hi) ? x[s0 - H + i] : 0.f;
         for (int j = tid; j <= 2 * A; j += kThreads) wl[j] = a.table[kBank + j];
     }
     __syncthreads();
 
-    // v[k] = max_q |u[t0 - 2A - 1 + k, q]|, k <= kTile + 4A: the chain reads slots k + 1 .. k + 12
+    // v[k] = max_q |u[s0 - 2A - 1 + k, q]|, k <= kTile + 4A: the chain reads slots k + 1 .. k + 12
     {
         float c1[kBankTaps], c2[kBankTaps], c3[kBankTaps];
 #pragma unroll
@@ -184,7 +256,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
     }
     __syncthreads();
 
-    // r[k] for sample t0 - 2A + k, k < kTile + 4A: its x is slot k + 7, its two v are k and k + 1
+    // r[k] for sample s0 - 2A + k, k < kTile + 4A: its x is slot k + 7, its two v are k and k + 1
     const float c = a.ceiling;
     const int nr = kTile + 4 * A;
     float pmax = 0.f;
@@ -194,7 +266,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
         if (k + 7 >= lo && k + 7 < hi) {
             const float p = fmaxf(fabsf(xs[k + 7]), fmaxf(Q[k], Q[k + 1]));
             if (p > c) { r = (float)((double)c / (double)p); over = 1; }
-            if (k >= 2 * A && k < 2 * A + kTile) pmax = fmaxf(pmax, p);
+            if (k >= 2 * A && k < 2 * A + own) pmax = fmaxf(pmax, p);            // the tile's own outputs
         }
         P[k] = r;
     }
@@ -212,7 +284,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
             __syncthreads();
             float* t = cur; cur = oth; oth = t;
         }
-        // d for sample t0 - A + i, i < kTile + 2A: the minimum of r over slots i .. i + 2A
+        // d for sample s0 - A + i, i < kTile + 2A: the minimum of r over slots i .. i + 2A
         for (int i = tid; i < kTile + 2 * A; i += kThreads) oth[pad8(i)] = 1.0f - fminf(cur[i], cur[i + W - step]);
         __syncthreads();
         // s for the outputs 8 tid .. 8 tid + 7: the chain over d slots o .. o + 2A, a window of 8 in registers
@@ -257,13 +329,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
                 y[e] = fminf(fmaxf(xs[q + e + H] * g, -c), c);
             }
         }
-        if (!orow) continue;
-        if (vec && q + 3 < in_row) {
-            *reinterpret_cast<mf32x4*>(orow + q) = y;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (q + e < in_row) orow[q + e] = y[e];
-        }
+        if (orow) store4<PCM>(orow, q, y, in_row - q, vec);
     }
     gmin = block_extreme<false>(gmin, red);
     if (tid == 0) {
@@ -273,9 +339,10 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
     }
 }
 
-inline hipError_t launch_tile(const TileLaunch& a, int B, hipStream_t stream) {
+inline hipError_t launch_tile(const TileLaunch& a, int B, bool pcm16, hipStream_t stream) {
     const dim3 grid((unsigned)a.tiles, (unsigned)B), block(kThreads);
-    return ::iris::launch_kernel(tile_kernel, grid, block, lds_bytes(a.A), stream, a);
+    if (pcm16) return ::iris::launch_kernel_named("tile_kernel", tile_kernel<true>, grid, block, lds_bytes(a.A), stream, a);
+    return ::iris::launch_kernel_named("tile_kernel", tile_kernel<false>, grid, block, lds_bytes(a.A), stream, a);
 }
 
 struct StatsLaunch {
@@ -283,13 +350,15 @@ struct StatsLaunch {
     int row_scale;
     const float* parts;         // [B][tiles][2]
     float* stats;               // [B][2]: tp_b, min g
-    int L, tiles;
+    int in_len, offset, n_out;  // as in TileLaunch
+    int tiles;
 };
 
 __global__ void __launch_bounds__(64) stats_kernel(const StatsLaunch a) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);
-    const int own = (int)(((long long)Lb + kTile - 1) / kTile);     // the item's own tiles
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.in_len);
+    const int n = Lb - a.offset < a.n_out ? (Lb > a.offset ? Lb - a.offset : 0) : a.n_out;    // the row's outputs that are its own samples
+    const int own = (int)(((long long)n + kTile - 1) / kTile);      // the tiles that hold one
     const float* __restrict__ parts = a.parts + (size_t)b * a.tiles * 2;
     float tp = 0.f, g = 1.0f;
     for (int t = tid; t < own; t += 64) { tp = fmaxf(tp, parts[2 * t]); g = fminf(g, parts[2 * t + 1]); }

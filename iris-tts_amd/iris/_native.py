@@ -403,6 +403,10 @@ LIMITER_SYMBOLS = {
     "iris_limiter_destroy": (_i32, [_vp]),
     "iris_limiter_forward_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp]),
     "iris_limiter_measure_ragged": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
+    "iris_limiter_window_range": (_i32, [_lmc, _i64, _i32, _i32, _i64p, _i64p]),
+    "iris_limiter_window_workspace_bytes": (_i32, [_lmc, _i32, _i32, _u64p]),
+    "iris_limiter_window_launch_count": (_i32, [_lmc, _i32, _i32, _i64, _i32, _ip]),
+    "iris_limiter_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

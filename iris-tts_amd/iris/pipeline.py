@@ -99,8 +99,18 @@ class MelToWavePipeline:
     gain that falls only around a peak -- so a ``LoudnessNormalizer(peak_ceiling=None)`` in front reaches its target -- behind
     ``loudness=`` and in front of ``assemble=`` and of ``pcm16=`` / ``normalize=`` / ``resampler=``, which run as stand-alone
     launches as for a denoiser.  It is handed the lengths and ``row_scale`` the stage in front passed on.  ``stream`` and
-    ``session`` refuse (``ValueError``): the gain looks ``2A + 7`` samples past a chunk's end, and no chunked form is built.  With
-    ``limiter=None`` nothing changes."""
+    ``session`` refuse a plain limiter (``ValueError``): the gain looks ``2A + 7`` samples past a chunk's end.  With
+    ``limiter=None`` nothing changes.
+
+    ``limiter=lim.chunked()`` (an ``iris.limiter.ChunkedLimiter``, or any object with ``chunked_sessions = True``, a
+    ``limit_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: the fp32 chunks go through
+    the chunked denoiser's and the chunked stretch's sessions, if there are any, and then through ONE ``LimiterSession``, the
+    order in which ``infer`` applies the stages.  Empty pieces are skipped; the first piece is short by ``2A + 7`` samples (73 at
+    1.5 ms and 22.05 kHz) and the last carries them; the concatenation equals ``infer(mel)`` bit for bit, so a streamed
+    utterance is held under the ceiling.  With ``lim.chunked(pcm16=True)`` the limiter's kernel stores 16-bit PCM itself: the
+    pieces are int16 and their concatenation equals ``infer(mel, pcm16=True)``.  It needs fp32 as the chunked denoiser does
+    (``forward_pcm16`` as the ``vocode`` is refused); ``infer`` and ``infer_batch`` go through ``limit_device`` as before; and
+    ``assemble=`` and ``loudness=`` beside it still refuse to stream, their measures being the whole item's."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -129,6 +139,10 @@ class MelToWavePipeline:
         if self._chunked_stretch and getattr(vocode, "__name__", "") == "forward_pcm16":
             raise ValueError("a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
                              "forward_pcm16 (no chunked PCM stage runs behind the stretch)")
+        self._chunked_limiter = bool(getattr(limiter, "chunked_sessions", False))
+        if self._chunked_limiter and getattr(vocode, "__name__", "") == "forward_pcm16":
+            raise ValueError("a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+                             "forward_pcm16 (the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))")
         if self._whole is not None and hop_length is None:
             hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
@@ -157,7 +171,8 @@ class MelToWavePipeline:
     def stream(self, mel) -> Iterator[torch.Tensor]:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``.  Refused with a
         plain denoiser (``ValueError``): its frames reach ``n_fft / 2`` samples across a chunk seam.  With a chunked one the
-        pieces are the ``DenoiserSession``'s: the first short by its halo, the last carrying it, none empty."""
+        pieces are the ``DenoiserSession``'s: the first short by its halo, the last carrying it, none empty.  Likewise with
+        a chunked stretch and a chunked limiter, whose session comes last (int16 pieces with ``lim.chunked(pcm16=True)``)."""
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
@@ -172,9 +187,11 @@ class MelToWavePipeline:
         yield from self._flush_through(sessions)
 
     def _open_sessions(self) -> list:
-        """The sessions a chunk goes through on its way out, in order: the chunked denoiser's, then the chunked stretch's."""
+        """The sessions a chunk goes through on its way out, in the order ``infer`` applies the stages: the chunked denoiser's,
+        then the chunked stretch's, then the chunked limiter's."""
         sessions = [self.denoiser.open_session()] if self._chunked_denoiser else []
-        return sessions + ([self.stretch.open_session()] if self._chunked_stretch else [])
+        sessions += [self.stretch.open_session()] if self._chunked_stretch else []
+        return sessions + ([self.limiter.open_session()] if self._chunked_limiter else [])
 
     @staticmethod
     def _push_through(sessions: list, piece: torch.Tensor) -> torch.Tensor:
@@ -197,7 +214,7 @@ class MelToWavePipeline:
     @staticmethod
     def _denoiser_input(chunk: torch.Tensor) -> torch.Tensor:
         if not chunk.is_floating_point():
-            raise ValueError(f"a chunked denoiser or stretch takes fp32 chunks, the vocoder returned {chunk.dtype}")
+            raise ValueError(f"a chunked denoiser, stretch or limiter takes fp32 chunks, the vocoder returned {chunk.dtype}")
         return chunk.float()
 
     def _refuse_chunked_denoiser(self) -> None:
@@ -207,9 +224,10 @@ class MelToWavePipeline:
         if self.loudness is not None:
             raise ValueError("a pipeline with loudness= cannot be streamed: the integrated loudness is the whole item's "
                              "measure, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
-        if self.limiter is not None:
+        if self.limiter is not None and not self._chunked_limiter:
             raise ValueError("a pipeline with limiter= cannot be streamed: the gain at a sample looks 2 * lookahead + 7 samples "
-                             "past it, across a chunk's end, and no chunked form is built; use infer / infer_batch")
+                             "past it, across a chunk's end, and no chunked form is built into a plain limiter: pass "
+                             "limiter=lim.chunked(), or use infer / infer_batch")
         if self.stretch is not None and not self._chunked_stretch:
             raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
                              "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
@@ -633,8 +651,8 @@ class MelToWavePipeline:
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
         """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
         PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own.
-        Refused with a plain denoiser (``ValueError``), as ``stream`` is; with a chunked one the session's pieces are the
-        denoiser session's."""
+        Refused with a plain denoiser, stretch or limiter (``ValueError``), as ``stream`` is; with chunked ones the session's
+        pieces are those of the last of their sessions."""
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
@@ -665,7 +683,9 @@ class PipelineSession:
     With a chunked denoiser (``MelToWavePipeline(denoiser=dn.chunked())``) every chunk goes through one ``DenoiserSession``
     on its way out: ``push`` and ``flush`` return its non-empty pieces -- the first short by the denoiser's halo, ``flush``
     returning it -- and a chunk leaves that many samples later.  With a chunked stretch (``stretch=ts.at(rate).chunked()``) they
-    then go through one ``StretchSession``, whose pieces ``push`` and ``flush`` return instead."""
+    then go through one ``StretchSession``, whose pieces ``push`` and ``flush`` return instead.  With a chunked limiter
+    (``limiter=lim.chunked()``) one ``LimiterSession`` comes last: its pieces are what ``push`` and ``flush`` return, ``2A + 7``
+    samples later still, held under the ceiling, and int16 with ``lim.chunked(pcm16=True)``."""
 
     def __init__(self, pipeline: MelToWavePipeline, postnet_halo_frames: Optional[int] = None):
         sv = pipeline.streamer
