@@ -284,6 +284,13 @@ int32_t iris_hifigan_op_pcm16(const float* wav_dev, const int32_t* lengths_dev, 
                               int16_t* pcm_dev, float* peak_dev, int32_t B, int32_t L,
                               int32_t normalize, float peak_target, void* stream);
 
+/* fp32 wav_dev [B, L] -> G.711 bytes out_u8_dev [B, L] on a waveform that exists (csrc/pcm_out.h: g711_kernel, 16-byte loads and
+ * 4-byte stores with a scalar head and tail, so items need no alignment).  law: IRIS_OUT_ULAW or IRIS_OUT_ALAW, the rules stated
+ * at iris_resampler_forward_g711.  lengths_dev and row_scale as in iris_hifigan_op_pcm16; the rest of an item's row holds the
+ * law's code for 0.  Synchronises `stream`, as iris_hifigan_op_pcm16 does. */
+int32_t iris_hifigan_op_g711(const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, int32_t row_scale,
+                             int32_t law, uint8_t* out_u8_dev, void* stream);
+
 /* One grouped MRF step of the fp32 path -- the hot kernel -- on its own: the three ResBlock branches
  * (kernel sizes k[j] = 3, 7, 11; hifigan_pretrained.py:64-71,130-136) each run
  *     y_j = Conv1d_{k[j], dil[j]}(LeakyReLU(x_j)) (+ res_j)
@@ -435,6 +442,52 @@ int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, i
                                const int32_t* lengths_dev /* NULL = plain batch */, int32_t row_scale, int64_t origin,
                                float* out_f32_dev, int16_t* out_pcm_dev, float* peak_dev,
                                int32_t normalize, float peak_target, void* stream);
+
+/* Output forms of the entry points below.  G.711 (telephony: one byte per sample) is an integer function of the 16-bit sample
+ * s = (int16) rintf(clamp(out, -1, 1) * 32767), restated in numpy by iris.synthesis_output.ulaw_from_pcm16 / alaw_from_pcm16:
+ *   mu-law  sign = s < 0;  m = min(|s|, 32635) + 132 (|s| in 32 bits);  e = floor(log2 m) - 7;  mant = (m >> (e + 3)) & 15;
+ *           byte = ~(sign << 7 | e << 4 | mant) & 0xFF
+ *   A-law   a = s >> 3 (arithmetic);  a < 0: a = ~a, mask = 0x55, else mask = 0xD5;  seg = a < 32 ? 0 : floor(log2 a) - 4;
+ *           mant = seg < 2 ? (a >> 1) & 15 : (a >> seg) & 15;  byte = (seg << 4 | mant) ^ mask
+ * Sample 0 has the code 0xFF (mu-law) / 0xD5 (A-law), and that -- never byte 0, which decodes to -32 124 -- is what fills a
+ * ragged item's row behind its own samples.  The A-law rule is the common table-free encoder (CPython's audioop.lin2alaw on all
+ * 65 536 inputs); the mu-law rule is the G.711 one on the 16-bit magnitude and differs from audioop.lin2ulaw at 381 inputs. */
+enum {
+    IRIS_OUT_F32 = 0,
+    IRIS_OUT_PCM16 = 1,
+    IRIS_OUT_ULAW = 3,
+    IRIS_OUT_ALAW = 4
+};
+
+/* iris_resampler_forward in a fourth form, G.711 bytes: wav_dev [B, L] -> out_u8_dev [B, n_count], `law`
+ * IRIS_OUT_ULAW or IRIS_OUT_ALAW, everything else -- origin, lengths_dev, row_scale, the limits, the one launch -- as there.
+ * Bit for bit the law of the int16 form's samples; an item's row behind its own outputs holds the law's code for 0. */
+int32_t iris_resampler_forward_g711(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t L,
+                                    const int32_t* lengths_dev /* NULL = plain batch */, int32_t row_scale, int64_t origin,
+                                    int32_t law, uint8_t* out_u8_dev, void* stream);
+
+/* Windows: the resampler on samples [origin, origin + Lw) of B utterances of one length, for a caller that receives the
+ * waveform piece by piece (iris.resample.ResamplerSession).  With Hw = half_width and i0(n) = floor(n * down / up), output n
+ * reads x[i0(n) - Hw + 1 .. i0(n) + Hw] and nothing else.  n_next is the first output not yet emitted; `final` (0 or not) says
+ * that origin + Lw is the utterance's end.  The rule (csrc/resample.h: struct Window):
+ *     n_hi = ceil((origin + Lw) * up / down) if final, else ceil(max(0, origin + Lw - Hw) * up / down)
+ *            -- the outputs whose last tap lies inside the window;
+ *     the window emits [n_next, n_hi): max(0, n_hi - n_next) outputs;
+ *     keep_from = max(0, i0(n_hi) - Hw + 1): the first sample the next window must still hold.
+ * Precondition: origin == 0, or i0(n_next) - Hw + 1 >= origin -- the first tap of the first output is held; otherwise, or with
+ * origin, Lw outside [0, 2^40] or n_next outside [0, ceil((origin + Lw) * up / down)], IRIS_HIFIGAN_INVALID_ARGUMENT.  The window
+ * forms no sample in front of sample 0 and, when final, none past the end: those read as 0 exactly as the whole call reads them,
+ * so the concatenation of an utterance's windows is iris_resampler_forward of the whole, bit for bit, in every form.
+ * window_plan is host only.  forward_window: wav_dev [B, Lw] -> out_dev [B, n_hi - n_next], packed rows of fp32, int16 or
+ * bytes by out_form (IRIS_OUT_F32, _PCM16, _ULAW, _ALAW; there is no normalised form: the peak belongs to the whole item).  ONE
+ * launch of the whole call's kernel -- iris_resampler_forward is the case final, n_next = ceil(origin * up / down) of the same
+ * launch builder, without the precondition -- no workspace, nothing allocated, asynchronous on `stream`, safe inside a stream
+ * capture.  B == 0, Lw == 0 or a count of 0 launch nothing and return IRIS_HIFIGAN_OK; B > 65535 and Lw > 2^30 return
+ * IRIS_HIFIGAN_UNSUPPORTED; a NULL pointer or out_dev off its type's bytes IRIS_HIFIGAN_INVALID_ARGUMENT. */
+int32_t iris_resampler_window_plan(const iris_resampler_handle* h, int64_t origin, int64_t Lw, int64_t n_next, int32_t final,
+                                   int64_t* n_hi, int64_t* keep_from);
+int32_t iris_resampler_forward_window(iris_resampler_handle* h, const float* wav_dev /* [B, Lw] */, int32_t B, int32_t Lw,
+                                      int64_t origin, int64_t n_next, int32_t final, void* out_dev, int32_t out_form, void* stream);
 
 /* ---- VAE decoder in front of the PostNet (csrc/vae_decoder.h) ------------------------------------------
  * The inference half of the reference's TextConditionedVAE (src/iris/vae.py:448-482, generate()): frame-level text

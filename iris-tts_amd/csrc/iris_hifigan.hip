@@ -996,6 +996,21 @@ int32_t iris_hifigan_op_pcm16(const float* wav_dev, const int32_t* lengths_dev, 
     IRIS_ABI_END
 }
 
+int32_t iris_hifigan_op_g711(const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev, int32_t row_scale, int32_t law,
+                             uint8_t* out_u8_dev, void* stream_) {
+    IRIS_ABI_BEGIN
+    if (!wav_dev || !out_u8_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    if (B < 1 || L < 1 || B > 65535 || row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "bad g711 shape");
+    if (law != IRIS_OUT_ULAW && law != IRIS_OUT_ALAW)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "law must be IRIS_OUT_ULAW or IRIS_OUT_ALAW, got %d", law);
+    hipStream_t stream = (hipStream_t)stream_;
+    const pcm::G711Launch q{wav_dev, lengths_dev, row_scale, out_u8_dev, B, L};
+    HIP_TRY(pcm::launch_g711(q, law, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
 int32_t iris_hifigan_op_mrf_step(const float* const* x_dev, const float* const* w_host, const float* const* bias_host,
                                  const float* const* res_dev, float* const* y_dev, float* mean_dev,
                                  int32_t B, int32_t L, int32_t C, const int32_t* k, const int32_t* dil,
@@ -1243,6 +1258,53 @@ int resampler_plan(int32_t rate_in, int32_t rate_out, int32_t zeros, double beta
     return IRIS_HIFIGAN_OK;
 }
 
+static_assert(IRIS_OUT_F32 == pcm::OUT_F32 && IRIS_OUT_PCM16 == pcm::OUT_PCM16 && IRIS_OUT_ULAW == pcm::OUT_ULAW &&
+              IRIS_OUT_ALAW == pcm::OUT_ALAW, "the public output forms are pcm_out.h's");
+
+// What every device entry of the stage asks of its shape before it looks at anything else.
+int resampler_check(const iris_resampler_handle* h, int32_t B, int32_t L, int64_t origin) {
+    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
+    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (origin < 0 || origin > resample::kMaxOrigin)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin must lie in [0, 2^40], got %lld", (long long)origin);
+    return IRIS_HIFIGAN_OK;
+}
+
+int resampler_check_size(int32_t B, int32_t L, long long n_count) {
+    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
+    if (L > (1 << 30)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%d samples per item exceed 2^30", L);
+    if (n_count > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%lld outputs per item exceed 2^31 - 1", n_count);
+    return IRIS_HIFIGAN_OK;
+}
+
+// The one launch builder of the stage: the outputs [n_lo, n_lo + N) of wav [B, L], whose first sample is `origin` of its
+// utterance.  The caller names ONE output form afterwards (y, pcm, y + peak, or g711 + law).
+resample::ResampleLaunch resampler_launch(const iris_resampler_handle* h, const float* wav_dev, int B, int L, const int32_t* lengths_dev,
+                                          int row_scale, long long origin, long long n_lo, long long N) {
+    resample::ResampleLaunch a;
+    a.wav = wav_dev; a.lengths = lengths_dev; a.row_scale = lengths_dev ? row_scale : 1; a.bank = h->bank;
+    a.y = nullptr; a.pcm = nullptr; a.g711 = nullptr; a.law = 0; a.peak = nullptr;
+    a.B = B; a.L = L; a.N = (int)N;
+    a.up = h->d.up; a.down = h->d.down; a.taps = h->d.taps; a.half_width = h->d.half_width;
+    a.origin = origin; a.n_lo = n_lo;
+    return a;
+}
+
+// origin, Lw and n_next of a window, checked; *win is the rule's answer (csrc/resample.h: struct Window).
+int resampler_window(const iris_resampler_handle* h, int64_t origin, int64_t Lw, int64_t n_next, int32_t final, resample::Window* win) {
+    if (origin < 0 || Lw < 0 || origin > resample::kMaxOrigin || Lw > resample::kMaxOrigin)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin and Lw must lie in [0, 2^40], got %lld and %lld", (long long)origin, (long long)Lw);
+    const long long n_end = resample::ceil_div_ll((origin + Lw) * h->d.up, h->d.down);
+    if (n_next < 0 || n_next > n_end)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "n_next = %lld lies outside [0, %lld], the outputs up to the window's end", (long long)n_next, n_end);
+    *win = resample::Window(h->d, origin, Lw, n_next, final != 0);
+    if (!win->ok)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "the window starts at sample %lld, but output %lld reads from sample %lld on: keep the "
+                    "samples from the previous window's keep_from", (long long)origin, (long long)n_next,
+                    (long long)n_next * h->d.down / h->d.up - h->d.half_width + 1);
+    return IRIS_HIFIGAN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1317,10 +1379,7 @@ int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, i
                                int32_t row_scale, int64_t origin, float* out_f32_dev, int16_t* out_pcm_dev, float* peak_dev,
                                int32_t normalize, float peak_target, void* stream_) {
     IRIS_ABI_BEGIN
-    if (!h) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL handle");
-    if (B < 0 || L < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
-    if (origin < 0 || origin > resample::kMaxOrigin)
-        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "origin must lie in [0, 2^40], got %lld", (long long)origin);
+    TRY(resampler_check(h, B, L, origin));
     if (normalize && !(peak_target > 0.f && peak_target <= 1.f))
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "peak_target must lie in (0, 1], got %g", (double)peak_target);
     if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
@@ -1331,28 +1390,81 @@ int32_t iris_resampler_forward(iris_resampler_handle* h, const float* wav_dev, i
     if (!normalize && out_f32_dev && out_pcm_dev)
         return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "one output form per call: fp32 or int16 (both only when normalising)");
     if (lengths_dev && row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale must be >= 1, got %d", row_scale);
-    if (B > 65535) return fail(IRIS_HIFIGAN_UNSUPPORTED, "batch %d exceeds 65535 (grid.y)", B);
-    if (L > (1 << 30)) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%d samples per item exceed 2^30", L);
-    long long n_lo = 0, n_count = 0;
-    resample::out_range(h->d, origin, L, &n_lo, &n_count);
-    if (n_count > 0x7fffffffll) return fail(IRIS_HIFIGAN_UNSUPPORTED, "%lld outputs per item exceed 2^31 - 1", n_count);
+    // the whole call is the final window that starts its own outputs: n_next = ceil(origin * up / down)
+    const long long n_lo = resample::ceil_div_ll(origin * h->d.up, h->d.down);
+    const long long n_count = resample::Window(h->d, origin, L, n_lo, true).count;
+    TRY(resampler_check_size(B, L, n_count));
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
     hipStream_t stream = (hipStream_t)stream_;
     if (normalize) HIP_TRY(hipMemsetAsync(peak_dev, 0, sizeof(float) * B, stream));
     if (n_count == 0) return IRIS_HIFIGAN_OK;                       // (a short window between two output positions)
-    resample::ResampleLaunch a;
-    a.wav = wav_dev; a.lengths = lengths_dev; a.row_scale = lengths_dev ? row_scale : 1; a.bank = h->bank;
+    resample::ResampleLaunch a = resampler_launch(h, wav_dev, B, L, lengths_dev, row_scale, origin, n_lo, n_count);
     a.y = out_f32_dev; a.pcm = normalize ? nullptr : out_pcm_dev; a.peak = normalize ? reinterpret_cast<unsigned*>(peak_dev) : nullptr;
-    a.B = B; a.L = L; a.N = (int)n_count;
-    a.up = h->d.up; a.down = h->d.down; a.taps = h->d.taps; a.half_width = h->d.half_width;
-    a.origin = origin; a.n_lo = n_lo;
     HIP_TRY(resample::launch_resample(a, stream));
     if (normalize) {
         // every item's row is already 0 past its own outputs, so the plain form of the output stage converts it
         const pcm::PcmLaunch q{out_f32_dev, nullptr, 1, out_pcm_dev, peak_dev, B, (int)n_count, peak_target};
         HIP_TRY(pcm::launch_pcm_normalize(q, true, stream));
     }
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_resampler_forward_g711(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t L, const int32_t* lengths_dev,
+                                    int32_t row_scale, int64_t origin, int32_t law, uint8_t* out_u8_dev, void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(resampler_check(h, B, L, origin));
+    if (law != IRIS_OUT_ULAW && law != IRIS_OUT_ALAW)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "law must be IRIS_OUT_ULAW or IRIS_OUT_ALAW, got %d", law);
+    if (B == 0 || L == 0) return IRIS_HIFIGAN_OK;
+    if (!wav_dev || !out_u8_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    if (lengths_dev && row_scale < 1) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "row_scale must be >= 1, got %d", row_scale);
+    const long long n_lo = resample::ceil_div_ll(origin * h->d.up, h->d.down);
+    const long long n_count = resample::Window(h->d, origin, L, n_lo, true).count;
+    TRY(resampler_check_size(B, L, n_count));
+    if (n_count == 0) return IRIS_HIFIGAN_OK;
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    resample::ResampleLaunch a = resampler_launch(h, wav_dev, B, L, lengths_dev, row_scale, origin, n_lo, n_count);
+    a.g711 = out_u8_dev; a.law = law;
+    HIP_TRY(resample::launch_resample(a, (hipStream_t)stream_));
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_resampler_window_plan(const iris_resampler_handle* h, int64_t origin, int64_t Lw, int64_t n_next, int32_t final,
+                                   int64_t* n_hi, int64_t* keep_from) {
+    IRIS_ABI_BEGIN
+    if (!h || !n_hi || !keep_from) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    resample::Window win(h->d, 0, 0, 0, false);
+    TRY(resampler_window(h, origin, Lw, n_next, final, &win));
+    *n_hi = win.n_hi; *keep_from = win.keep_from;
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
+int32_t iris_resampler_forward_window(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t Lw, int64_t origin,
+                                      int64_t n_next, int32_t final, void* out_dev, int32_t out_form, void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(resampler_check(h, B, Lw, origin));
+    if (out_form != IRIS_OUT_F32 && out_form != IRIS_OUT_PCM16 && out_form != IRIS_OUT_ULAW && out_form != IRIS_OUT_ALAW)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_form must be IRIS_OUT_F32, _PCM16, _ULAW or _ALAW, got %d (a window has no "
+                    "normalised form: the peak is the whole item's)", out_form);
+    resample::Window win(h->d, 0, 0, 0, false);
+    TRY(resampler_window(h, origin, Lw, n_next, final, &win));
+    TRY(resampler_check_size(B, Lw, win.count));
+    if (B == 0 || Lw == 0 || win.count == 0) return IRIS_HIFIGAN_OK;            // nothing is final yet: no launch
+    if (!wav_dev || !out_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    const uintptr_t align = out_form == IRIS_OUT_F32 ? 4 : out_form == IRIS_OUT_PCM16 ? 2 : 1;
+    if ((uintptr_t)out_dev % align) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev is off its type's %d bytes", (int)align);
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    resample::ResampleLaunch a = resampler_launch(h, wav_dev, B, Lw, nullptr, 1, origin, n_next, win.count);
+    if (out_form == IRIS_OUT_F32)        a.y = static_cast<float*>(out_dev);
+    else if (out_form == IRIS_OUT_PCM16) a.pcm = static_cast<int16_t*>(out_dev);
+    else                                 { a.g711 = static_cast<uint8_t*>(out_dev); a.law = out_form; }
+    HIP_TRY(resample::launch_resample(a, (hipStream_t)stream_));
     return IRIS_HIFIGAN_OK;
     IRIS_ABI_END
 }

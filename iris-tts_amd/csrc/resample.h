@@ -12,14 +12,16 @@
 // A call sees L input samples whose first one has the global index `origin`; it produces the global outputs n with
 // origin <= n * down / up < origin + L, i.e. n_lo = ceil(origin * up / down) .. ceil((origin + L) * up / down) - 1, so
 // consecutive windows partition the output.  x outside the item's own samples (before `origin`, past the item's length)
-// reads as 0 and is never fetched: the bound comes from ragged_rows, not from memory.
+// reads as 0 and is never fetched: the bound comes from ragged_rows, not from memory.  (A window of a streamed utterance emits
+// another range, from another first output: struct Window below.)
 //
 // Kernel: grid (tiles, B); a 256-thread block computes kRun consecutive outputs of one item.  All 64-bit position
 // arithmetic happens once per block (the base output's i0 and phase); a lane steps from it in 32 bits.  The block stages
 // the input span of its run in LDS -- 16-byte loads from the first 16-byte boundary of the item's addresses, scalar and
 // bounded at the head, the tail and wherever the span leaves the item -- and each lane walks the fmaf chain of its outputs
-// (lane l owns outputs l, l + 256, ...: coalesced stores) with its phase row of the bank read as 16-byte loads (rows are
-// padded to a multiple of four floats; the bank, at most 640 KB and typically < 60 KB, stays in L2).
+// (lane l owns outputs l, l + 256, ...: coalesced stores; a G.711 form stores one byte per lane, 64 bytes per wave store --
+// packing four outputs per lane is not built and its worth not measured) with its phase row of the bank read as 16-byte
+// loads (rows are padded to a multiple of four floats; the bank, at most 640 KB and typically < 60 KB, stays in L2).
 // LDS reads are ds_read_b32 at a lane stride of down / up samples: below one when upsampling (neighbours share or
 // broadcast a word), 1.4 - 5.5 when downsampling, i.e. a 2- to 6-way conflict on the 32 banks of that instruction.
 #pragma once
@@ -106,6 +108,30 @@ inline void out_range(const Design& d, long long origin, long long L, long long*
     *n_count = ceil_div_ll((origin + L) * d.up, d.down) - lo;
 }
 
+// Windows (iris_resampler_window_plan / _forward_window): the utterance arrives piece by piece and a window holds its samples
+// [origin, origin + Lw).  Output n reads x[i0(n) - Hw + 1 .. i0(n) + Hw], i0(n) = floor(n * down / up), and nothing else, so it is
+// final once its last tap lies inside the window -- or the utterance has ended, where the whole call reads zeros too.  struct
+// Window is the one place that rule is written down: the window emits [n_next, n_hi),
+//     n_hi = ceil((origin + Lw) * up / down) if final, else ceil(max(0, origin + Lw - Hw) * up / down),
+// provided the first tap of n_next is still held (origin == 0, or i0(n_next) - Hw + 1 >= origin: `ok`), and the next window must
+// hold the samples from keep_from = max(0, i0(n_hi) - Hw + 1) on.  The kernel needs nothing new for it: a launch already names
+// origin and n_lo separately and bounds every load by the row, so a window is the launch (origin, n_lo = n_next, N = count), and
+// iris_resampler_forward is the final window with n_next = ceil(origin * up / down) whose `ok` nobody asks for (samples in front
+// of its origin read as 0, as they always did).
+struct Window {
+    long long n_hi, count, keep_from;
+    bool ok;
+    Window(const Design& d, long long origin, long long Lw, long long n_next, bool final) {
+        const long long end = origin + Lw, Hw = d.half_width;
+        const long long settled = final ? end : (end > Hw ? end - Hw : 0);
+        n_hi = ceil_div_ll(settled * d.up, d.down);
+        count = n_hi > n_next ? n_hi - n_next : 0;
+        const long long k = n_hi * d.down / d.up - Hw + 1;
+        keep_from = k > 0 ? k : 0;
+        ok = origin == 0 || n_next * d.down / d.up - Hw + 1 >= origin;
+    }
+};
+
 __host__ __device__ inline int row_stride(int taps) { return (taps + 3) & ~3; }     // floats per bank row on the device
 // floats of LDS a block needs: the span of a full run from the worst base phase, + 3 of alignment shift, whole 16-byte groups
 inline size_t lds_floats(int up, int down, int taps) {
@@ -120,6 +146,8 @@ struct ResampleLaunch {
     const float* bank;          // [up][row_stride(taps)] fp32, 16-byte aligned
     float* y;                   // [B, N] fp32 (OUT_F32, OUT_F32_PEAK)
     int16_t* pcm;               // [B, N] int16 (OUT_PCM16)
+    uint8_t* g711;              // [B, N] bytes (OUT_ULAW, OUT_ALAW: `law` says which)
+    int law;
     unsigned* peak;             // [B] bit patterns of the items' max |out| (OUT_F32_PEAK), zeroed on the stream
     int B, L, N;                // N outputs per item, global indices n_lo .. n_lo + N - 1
     int up, down, taps, half_width;
@@ -213,6 +241,11 @@ inline hipError_t launch_resample(const ResampleLaunch& a, hipStream_t stream) {
     const size_t lds = lds_floats(a.up, a.down, a.taps) * sizeof(float);
     if (a.peak) return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32_PEAK>, grid, block, lds, stream, a);
     if (a.pcm)  return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_PCM16>, grid, block, lds, stream, a);
+    if (a.g711 && a.law == pcm::OUT_ULAW)
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ULAW>, grid, block, lds, stream, a);
+    if (a.g711 && a.law == pcm::OUT_ALAW)
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ALAW>, grid, block, lds, stream, a);
+    if (a.g711 || !a.y) return hipErrorInvalidValue;
     return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32>, grid, block, lds, stream, a);
 }
 

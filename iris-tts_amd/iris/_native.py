@@ -141,6 +141,7 @@ SYMBOLS = {
     "iris_hifigan_op_conv_transpose1d": (_i32, [_vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _vp]),
     "iris_hifigan_op_conv_post": (_i32, [_vp, _vp, _vp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _f, _vp]),
     "iris_hifigan_op_pcm16": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _f, _vp]),
+    "iris_hifigan_op_g711": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "iris_hifigan_op_mrf_step": (_i32, [_c.POINTER(_vp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_vp), _c.POINTER(_vp), _vp,
                                        _i32, _i32, _i32, _c.POINTER(_i32), _c.POINTER(_i32), _f, _i32, _vp]),
     "iris_hifigan_op_mrf_pair": (_i32, [_c.POINTER(_vp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_fp), _c.POINTER(_fp),
@@ -171,6 +172,18 @@ RESAMPLER_SYMBOLS = {
     "iris_resampler_out_range": (_i32, [_vp, _i64, _i64, _i64p, _i64p]),
     "iris_resampler_forward": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _f, _vp]),
 }
+
+# its window form and its G.711 store form (iris.resample: ResamplerSession, forward(encoding=)): bound by load() like SYMBOLS,
+# and kept apart from RESAMPLER_SYMBOLS, which stays the stage's first six functions
+RESAMPLER_WINDOW_SYMBOLS = {
+    "iris_resampler_forward_g711": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i64, _i32, _vp, _vp]),
+    "iris_resampler_window_plan": (_i32, [_vp, _i64, _i64, _i64, _i32, _i64p, _i64p]),
+    "iris_resampler_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _vp, _i32, _vp]),
+}
+
+# output forms of the resampler's window and G.711 entry points (include/iris_hifigan.h: IRIS_OUT_*)
+OUT_F32, OUT_PCM16, OUT_ULAW, OUT_ALAW = 0, 1, 3, 4
+OUT_FORMS = {"f32": OUT_F32, "pcm16": OUT_PCM16, "ulaw": OUT_ULAW, "alaw": OUT_ALAW}
 
 
 
@@ -434,7 +447,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
     except OSError as exc:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
-    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
+    for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **RESAMPLER_WINDOW_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
                                       **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS,
                                       **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS}.items():
         try:

@@ -110,18 +110,29 @@ class MelToWavePipeline:
     utterance is held under the ceiling.  With ``lim.chunked(pcm16=True)`` the limiter's kernel stores 16-bit PCM itself: the
     pieces are int16 and their concatenation equals ``infer(mel, pcm16=True)``.  It needs fp32 as the chunked denoiser does
     (``forward_pcm16`` as the ``vocode`` is refused); ``infer`` and ``infer_batch`` go through ``limit_device`` as before; and
-    ``assemble=`` and ``loudness=`` beside it still refuse to stream, their measures being the whole item's."""
+    ``assemble=`` and ``loudness=`` beside it still refuse to stream, their measures being the whole item's.
+
+    ``output``: what ``iris.resample.Resampler.chunked(encoding)`` returns (a ``ChunkedResampler``, or any object with
+    ``chunked_sessions = True``, a ``forward(wav, lengths=, row_scale=)``, an ``out_range`` and an ``open_session() -> push /
+    flush``), or None: the output stage of a served utterance, the sample rate and the sample format a consumer takes -- 8 kHz
+    G.711 mu-law for a phone line is ``output=Resampler(8000).chunked("ulaw")``.  ``stream`` and ``session`` open its session
+    LAST, behind the limiter's, or directly behind the vocoder when no other session exists; the pieces are fp32, int16 or uint8
+    at ``output.rate_out`` and their concatenation equals ``infer(mel)`` bit for bit.  ``infer`` and ``infer_batch`` without
+    ``pcm16`` / ``normalize`` / ``resampler`` arguments apply the same resampler and encoding in one call behind the other
+    stages; those arguments beside ``output=`` are refused (``ValueError``), and so are ``lim.chunked(pcm16=True)`` and
+    ``forward_pcm16`` as the ``vocode``: the resampler reads fp32.  With ``output=None`` nothing changes."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
                  group_chunks: int = 1, config=None, acoustic=None, text=None, posterior=None, frontend=None,
-                 denoiser=None, stretch=None, assemble=None, loudness=None, limiter=None):
+                 denoiser=None, stretch=None, assemble=None, loudness=None, limiter=None, output=None):
         self.postnet = postnet
         self.denoiser = denoiser
         self.stretch = stretch
         self.assemble = assemble
         self.loudness = loudness
         self.limiter = limiter
+        self.output = output
         self.acoustic = acoustic
         self.text = text
         self.posterior = posterior
@@ -143,6 +154,15 @@ class MelToWavePipeline:
         if self._chunked_limiter and getattr(vocode, "__name__", "") == "forward_pcm16":
             raise ValueError("a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
                              "forward_pcm16 (the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))")
+        if output is not None:
+            if not getattr(output, "chunked_sessions", False):
+                raise ValueError("output= takes a resampler with its encoding: pass output=res.chunked(encoding), not the Resampler")
+            if getattr(vocode, "__name__", "") == "forward_pcm16":
+                raise ValueError("output= reads the fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 (the "
+                                 "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))")
+            if self._chunked_limiter and getattr(limiter, "pcm16", False):
+                raise ValueError("output= reads the fp32 waveform: pass limiter=lim.chunked(), not lim.chunked(pcm16=True) (the "
+                                 "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))")
         if self._whole is not None and hop_length is None:
             hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
@@ -172,7 +192,8 @@ class MelToWavePipeline:
         """Yields ``[B, hop*chunk]`` device tensors in order; their concatenation equals ``infer(mel)``.  Refused with a
         plain denoiser (``ValueError``): its frames reach ``n_fft / 2`` samples across a chunk seam.  With a chunked one the
         pieces are the ``DenoiserSession``'s: the first short by its halo, the last carrying it, none empty.  Likewise with
-        a chunked stretch and a chunked limiter, whose session comes last (int16 pieces with ``lim.chunked(pcm16=True)``)."""
+        a chunked stretch and a chunked limiter (int16 pieces with ``lim.chunked(pcm16=True)``); the session of ``output=``
+        comes last of all, and its pieces are at its rate and in its encoding."""
         self._refuse_chunked_denoiser()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
@@ -188,10 +209,21 @@ class MelToWavePipeline:
 
     def _open_sessions(self) -> list:
         """The sessions a chunk goes through on its way out, in the order ``infer`` applies the stages: the chunked denoiser's,
-        then the chunked stretch's, then the chunked limiter's."""
+        then the chunked stretch's, then the chunked limiter's, then the output stage's."""
         sessions = [self.denoiser.open_session()] if self._chunked_denoiser else []
         sessions += [self.stretch.open_session()] if self._chunked_stretch else []
-        return sessions + ([self.limiter.open_session()] if self._chunked_limiter else [])
+        sessions += [self.limiter.open_session()] if self._chunked_limiter else []
+        return sessions + ([self.output.open_session()] if self.output is not None else [])
+
+    def _output_args(self, pcm16: bool, normalize: bool, resampler):
+        """``resampler`` for the output stage of ``infer`` / ``infer_batch``: the caller's, or ``output=`` -- beside which the
+        caller names none, and no ``pcm16`` / ``normalize`` either."""
+        if self.output is None:
+            return resampler
+        if pcm16 or normalize or resampler is not None:
+            raise ValueError("this pipeline has output=: it decides the rate and the encoding, so pcm16=, normalize= and "
+                             "resampler= are not taken beside it")
+        return self.output
 
     @staticmethod
     def _push_through(sessions: list, piece: torch.Tensor) -> torch.Tensor:
@@ -353,10 +385,15 @@ class MelToWavePipeline:
 
         ``resampler`` (an ``iris.resample.Resampler``): the waveform at its rate instead of 22 050 Hz
         (``GeneratorEngine.forward_resampled``) -- fp32 chunked like the plain path, each window at its own origin, so the
-        result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward."""
+        result equals the one-shot conversion bit for bit; with ``pcm16`` the refined mel goes through ONE forward.
+
+        With ``output=`` the arguments are refused and the result is the fp32 waveform -- behind every other stage -- through
+        ``output.forward``: its rate, its encoding, what ``stream`` yields piece by piece."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
-        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None or self.limiter is not None:
+        resampler = self._output_args(pcm16, normalize, resampler)
+        if (self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None
+                or self.limiter is not None or self.output is not None):
             mel = self.refine(mel)
             wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
             if self.denoiser is not None:
@@ -589,7 +626,7 @@ class MelToWavePipeline:
 
     def infer_batch(self, mels: Sequence, pcm16: bool = False, normalize: bool = False, resampler=None) -> List[torch.Tensor]:
         """Utterances of different lengths, ``mels[i]`` = ``[n_mels, T_i]`` (host or device) -> one waveform
-        ``[hop * T_i]`` per utterance, with ONE PostNet pass and ONE vocoder forward for the whole list: the mels are padded
+        ``[hop * T_i]`` per utterance (with ``output=``: at its rate and in its encoding), with ONE PostNet pass and ONE vocoder forward for the whole list: the mels are padded
         to the longest (``pack_mels``) and both stages bound every layer of item i by ``T_i`` (``forward_device(...,
         lengths=)``, ``vocode(..., lengths=)``), so item i is bit for bit ``infer(mels[i][None])[0]`` -- padding alone would
         let the padded frames reach the last frames of every short item (``iris.batching``).  The stages must take
@@ -601,6 +638,7 @@ class MelToWavePipeline:
         With ``assemble=`` the result is ``(waveform, spans)``: the items trimmed and joined into one (the class docstring)."""
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
+        resampler = self._output_args(pcm16, normalize, resampler)
         mels = list(mels)
         if not mels:
             return []
@@ -612,7 +650,8 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        if self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None or self.limiter is not None:
+        if (self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None
+                or self.limiter is not None or self.output is not None):
             frames = [int(t) for t in lengths]
             if ragged_whole:
                 rows = [max(t - 1, 0) for t in frames]

@@ -10,6 +10,23 @@ The filter is defined once, in the library (``include/iris_hifigan.h``): with ``
 ``i0 = floor(n * down / up)``, ``p = (n * down) mod up``, and ``x`` outside the item's own samples reading as 0.
 ``design_bank`` fetches the bank from the library's host-only function (no GPU needed), ``resample_host`` restates the
 chain in numpy with an exact fused multiply-add, and ``Resampler`` runs the device kernel; the two agree bit for bit.
+
+Streaming.  Output ``n`` reads ``x[i0(n) - Hw + 1 .. i0(n) + Hw]`` (``Hw = half_width``) and nothing else, so the stage is chunked
+exactly.  A window holds samples ``[origin, origin + Lw)`` of an utterance, ``n_next`` is the first output not yet emitted, and
+
+    ``n_hi = ceil((origin + Lw) * up / down)`` if ``final`` else ``ceil(max(0, origin + Lw - Hw) * up / down)``
+
+-- the outputs whose last tap lies inside the window; the window emits ``[n_next, n_hi)`` provided ``origin == 0`` or
+``i0(n_next) - Hw + 1 >= origin``, and the next window must still hold the samples from ``keep_from = max(0, i0(n_hi) - Hw + 1)``
+on (``window_plan``; the rule is written down once, in csrc/resample.h, ``struct Window``).  ``Resampler.forward_window`` is ONE
+launch of the whole call's kernel on such a window, ``ResamplerSession`` keeps the two numbers and the held samples, and the
+concatenation of its pieces equals ``Resampler.forward`` of the whole bit for bit -- as fp32, as int16, and as G.711 mu-law or
+A-law bytes (``encoding=``: telephony, one byte per sample, the integer rules of ``iris.synthesis_output.ulaw_from_pcm16`` /
+``alaw_from_pcm16`` applied to the int16 sample by the kernel's store).  ``res.chunked(encoding)`` (``ChunkedResampler``) is the
+opt-in with which ``MelToWavePipeline(output=)`` runs such a session last of all.  Per-chunk ``forward(origin=running)`` calls do
+NOT concatenate to the whole: they take the samples in front of ``origin`` for zeros.
+
+Not built: ragged sessions, and a normalised form in windows (the peak belongs to the whole item).
 """
 from __future__ import annotations
 
@@ -49,6 +66,20 @@ def out_range(up: int, down: int, origin: int, L: int) -> Tuple[int, int]:
     ``n`` with ``origin <= n * down / up < origin + L`` (Python integers: nothing wraps)."""
     n_lo = _ceil_div(int(origin) * up, down)
     return n_lo, _ceil_div((int(origin) + int(L)) * up, down) - n_lo
+
+
+def window_plan(up: int, down: int, half_width: int, origin: int, Lw: int, n_next: int, final: bool) -> Tuple[int, int]:
+    """``(n_hi, keep_from)`` of the window ``[origin, origin + Lw)``: the host restatement of ``iris_resampler_window_plan``
+    (module docstring) in Python integers: planning without a device, and a fake resampler built on ``resample_host``.
+    ``ValueError`` where the precondition fails."""
+    origin, Lw, n_next, hw = int(origin), int(Lw), int(n_next), int(half_width)
+    end = origin + Lw
+    if origin < 0 or Lw < 0 or not 0 <= n_next <= _ceil_div(end * up, down):
+        raise ValueError(f"a window needs origin >= 0, Lw >= 0 and n_next within its outputs, got {origin}, {Lw}, {n_next}")
+    if origin and n_next * down // up - hw + 1 < origin:
+        raise ValueError(f"the window starts at sample {origin}, but output {n_next} reads from sample {n_next * down // up - hw + 1} on")
+    n_hi = _ceil_div((end if final else max(0, end - hw)) * up, down)
+    return n_hi, max(0, n_hi * down // up - hw + 1)
 
 
 def fmaf32(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
@@ -155,15 +186,31 @@ class Resampler:
         return int(n_lo.value), int(n_count.value)
 
     def forward(self, wav, lengths=None, row_scale: int = 1, origin: int = 0, pcm16: bool = False, normalize: bool = False,
-                peak_target: float = 0.95):
+                peak_target: float = 0.95, encoding: Optional[str] = None):
         """``wav``: fp32 device tensor ``[B, L]`` whose first column has the utterance-global index ``origin`` ->
         ``[B, n_count]`` (``out_range(origin, L)``): fp32, or int16 with ``pcm16=True`` (bit for bit
         ``pcm16_from_float`` of the fp32 result).  ``normalize=True`` (with pcm16) scales every item to ``peak_target`` at
         its own peak first and returns ``(pcm, peaks)``, ``peaks`` the fp32 tensor [B] of the items' max |out|.
         ``lengths`` (a sequence or an integer tensor [B]) and ``row_scale``: item b owns
-        ``min(L, lengths[b] * row_scale)`` samples; the rest is never read and its outputs past its own count are 0."""
+        ``min(L, lengths[b] * row_scale)`` samples; the rest is never read and its outputs past its own count are 0.
+        ``encoding``: ``"f32"`` and ``"pcm16"`` say what ``pcm16=`` says; ``"ulaw"`` / ``"alaw"`` return uint8, the G.711 byte of
+        every int16 sample, stored by the same launch (``iris_resampler_forward_g711``) -- an item's row past its own count
+        then holds the law's code for 0 -- and refuse ``normalize=True``."""
         import torch
 
+        g711 = None
+        if encoding is not None:
+            if encoding not in _native.OUT_FORMS:
+                raise ValueError(f"encoding must be one of {tuple(_native.OUT_FORMS)}, got {encoding!r}")
+            if encoding in ("ulaw", "alaw"):
+                if normalize or pcm16:
+                    raise ValueError("a G.711 encoding has no normalised form and is no 16-bit PCM: pass neither normalize=True nor "
+                                     "pcm16=True beside it")
+                g711 = _native.OUT_FORMS[encoding]
+            elif pcm16 and encoding == "f32":
+                raise ValueError("encoding='f32' contradicts pcm16=True")
+            else:
+                pcm16 = pcm16 or encoding == "pcm16"
         if normalize and not pcm16:
             raise ValueError("normalize=True goes with pcm16=True")
         if normalize and not 0.0 < float(peak_target) <= 1.0:
@@ -188,6 +235,15 @@ class Resampler:
             if tuple(lengths_dev.shape) != (B,):
                 raise ValueError(f"lengths must have shape [{B}], got {list(lengths_dev.shape)}")
         n_count = self.out_range(origin, L)[1] if B and L else 0
+        if g711 is not None:
+            out = torch.empty((B, n_count), dtype=torch.uint8, device=self.device)
+            if B and L and n_count:
+                _native.check("iris_resampler_forward_g711", self.lib.iris_resampler_forward_g711(
+                    self._handle, ctypes.c_void_p(wav.data_ptr()), B, L,
+                    ctypes.c_void_p(lengths_dev.data_ptr() if lengths_dev is not None else None), int(row_scale),
+                    ctypes.c_int64(int(origin)), g711, ctypes.c_void_p(out.data_ptr()),
+                    ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return out
         out = torch.empty((B, n_count), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
         f32 = torch.empty((B, n_count), dtype=torch.float32, device=self.device) if normalize else None
         peaks = torch.zeros((B,), dtype=torch.float32, device=self.device) if normalize else None
@@ -207,6 +263,180 @@ class Resampler:
         return (out, peaks) if normalize else out
 
     __call__ = forward
+
+    # -- windows of an utterance -------------------------------------------------------------
+    def window_plan(self, origin: int, Lw: int, n_next: int, final: bool) -> Tuple[int, int]:
+        """``(n_hi, keep_from)``: the window ``[origin, origin + Lw)`` emits the outputs ``[n_next, n_hi)`` and the next window
+        must hold the samples from ``keep_from`` on (``iris_resampler_window_plan``: the rule of the module docstring, written
+        down on the C side only).  Host only; a violated precondition is a ``NativeCallError`` (invalid argument)."""
+        n_hi, keep = ctypes.c_int64(), ctypes.c_int64()
+        _native.check("iris_resampler_window_plan", self.lib.iris_resampler_window_plan(
+            self._handle, ctypes.c_int64(int(origin)), ctypes.c_int64(int(Lw)), ctypes.c_int64(int(n_next)), int(bool(final)),
+            ctypes.byref(n_hi), ctypes.byref(keep)))
+        return int(n_hi.value), int(keep.value)
+
+    def forward_window(self, wav, origin: int, n_next: int, final: bool, encoding: str = "f32"):
+        """``wav [B, Lw]`` fp32 = samples ``[origin, origin + Lw)`` of B utterances of one length -> ``[B, n_hi - n_next]`` on the
+        device: the outputs ``window_plan`` names, each bit for bit the one ``forward`` of the whole utterance returns there, as
+        fp32, int16 (``"pcm16"``) or G.711 bytes (``"ulaw"``, ``"alaw"``).  Stateless, asynchronous on the current stream, ONE
+        launch of ``forward``'s kernel, no workspace; none at all when nothing is final yet.  ``ResamplerSession`` keeps the
+        bookkeeping."""
+        import torch
+
+        if encoding not in _native.OUT_FORMS:
+            raise ValueError(f"encoding must be one of {tuple(_native.OUT_FORMS)}, got {encoding!r}")
+        if not isinstance(wav, torch.Tensor):
+            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
+        if wav.dim() != 2 or wav.dtype != torch.float32:
+            raise ValueError(f"expected an fp32 waveform [B, Lw], got {wav.dtype} {tuple(wav.shape)}")
+        B, Lw = int(wav.shape[0]), int(wav.shape[1])
+        count = max(0, self.window_plan(origin, Lw, n_next, final)[0] - int(n_next))
+        out = torch.empty((B, count), dtype=_torch_dtype(encoding), device=self.device)
+        if B and Lw and count:
+            wav = wav.to(self.device).contiguous()
+            with torch.cuda.device(self.device):
+                _native.check("iris_resampler_forward_window", self.lib.iris_resampler_forward_window(
+                    self._handle, ctypes.c_void_p(wav.data_ptr()), B, Lw, ctypes.c_int64(int(origin)), ctypes.c_int64(int(n_next)),
+                    int(bool(final)), ctypes.c_void_p(out.data_ptr()), _native.OUT_FORMS[encoding],
+                    ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return out
+
+    def open_session(self, encoding: str = "f32") -> "ResamplerSession":
+        """A ``ResamplerSession`` for one utterance (or a batch of equal lengths) that arrives piece by piece."""
+        return ResamplerSession(self, encoding)
+
+    def chunked(self, encoding: str = "f32") -> "ChunkedResampler":
+        """This resampler as the output stage a streaming pipeline takes (``MelToWavePipeline(output=res.chunked("ulaw"))``)."""
+        return ChunkedResampler(self, encoding)
+
+
+ENCODINGS = ("f32", "pcm16", "ulaw", "alaw")
+
+
+def _torch_dtype(encoding: str):
+    import torch
+    return {"f32": torch.float32, "pcm16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}[encoding]
+
+
+class ResamplerSession:
+    """Pushed input for a resampler: the waveform of ONE utterance (or a batch of equal lengths) arrives piece by piece
+    (``push``), converted samples leave as soon as their last tap has arrived, ``flush`` ends the utterance.  The concatenation
+    of everything returned equals ``Resampler.forward`` of the concatenated pieces bit for bit, in the session's ``encoding``
+    (``"f32"``, ``"pcm16"``, ``"ulaw"``, ``"alaw"``), and has ``ceil(L * up / down)`` samples.
+
+    ``res``: a ``Resampler``, or any object with ``window_plan(origin, Lw, n_next, final) -> (n_hi, keep_from)`` and
+    ``forward_window(wav, origin, n_next, final, encoding=) -> [B, n_hi - n_next]``.  Each push is ONE window over what is held:
+    the samples from the last window's ``keep_from`` on and the piece just pushed.  The session's whole state is those samples
+    and the count ``n_next`` (``samples_emitted``), so ``samples_buffered`` stays under ``2 Hw + ceil(down / up)`` plus the piece
+    just pushed.  Pieces may have any length, 0 included.
+
+    Latency: output n leaves with the push that brings ``samples_received`` to ``i0(n) + Hw + 1``: ``Hw`` input samples, 45 at
+    8 kHz from 22.05 kHz (2 ms).  ``flush`` returns the outputs that were waiting for them."""
+
+    def __init__(self, res, encoding: str = "f32"):
+        if encoding not in ENCODINGS:
+            raise ValueError(f"encoding must be one of {ENCODINGS}, got {encoding!r}")
+        self._res, self.encoding = res, encoding
+        self._buf = None              # samples [self._base, self._total) of the utterance, [B, n]
+        self._base = 0
+        self._total = 0
+        self._next = 0                # the first output not yet emitted
+        self._closed = False
+
+    @property
+    def samples_received(self) -> int:
+        return self._total
+
+    @property
+    def samples_emitted(self) -> int:
+        return self._next
+
+    @property
+    def samples_buffered(self) -> int:
+        return self._total - self._base
+
+    def _empty(self):
+        import torch
+        dtype = _torch_dtype(self.encoding)
+        if self._buf is None:
+            return torch.empty((0, 0), dtype=dtype)
+        return self._buf.new_empty((self._buf.shape[0], 0), dtype=dtype)
+
+    def _advance(self, final: bool):
+        if self._buf is None:
+            return self._empty()
+        n_hi, keep_from = self._res.window_plan(self._base, self._total - self._base, self._next, final)
+        if n_hi > self._next:
+            out = self._res.forward_window(self._buf, self._base, self._next, final, encoding=self.encoding)
+            self._next = n_hi
+        else:
+            out = self._empty()                                   # nothing became final: no launch
+        keep_from = min(max(keep_from, self._base), self._total)  # the next window's left-hand taps
+        if keep_from > self._base:
+            self._buf = self._buf[:, keep_from - self._base:]
+            self._base = keep_from
+        return out
+
+    def push(self, wav_piece, lengths=None):
+        """Appends ``wav_piece [B, n]`` fp32 (n >= 0) and returns the tensor ``[B, m]`` of the outputs that became final; ``m``
+        may be 0, and then nothing was launched."""
+        import torch
+
+        if lengths is not None:
+            raise ValueError("a session takes items of one length: ragged batches stay on forward(lengths=)")
+        if self._closed:
+            raise RuntimeError("the session was flushed: open a new one for the next utterance")
+        if not isinstance(wav_piece, torch.Tensor):
+            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
+        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
+            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
+        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
+            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
+        if self._buf is None:
+            self._buf = wav_piece
+        elif wav_piece.shape[1]:
+            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
+        self._total += int(wav_piece.shape[1])
+        return self._advance(final=False)
+
+    def flush(self):
+        """Ends the utterance and returns the outputs that were waiting for their last taps: past the end they read zeros,
+        as in the one-shot call.  Further calls return an empty tensor."""
+        if self._closed:
+            return self._empty()
+        out = self._advance(final=True)
+        self._closed = True
+        self._buf = None if self._buf is None else self._buf[:, :0]
+        self._base = self._total
+        return out
+
+
+class ChunkedResampler:
+    """``res`` with an encoding, as the output stage of a pipeline: ``MelToWavePipeline(..., output=res.chunked("ulaw"))`` lets
+    ``stream`` and ``session`` run one ``ResamplerSession`` last of all, and ``infer`` / ``infer_batch`` call ``forward``, which is
+    ``res.forward(..., encoding=)``.  The pieces are fp32, int16 or uint8 at ``rate_out``."""
+
+    chunked_sessions = True
+
+    def __init__(self, res, encoding: str = "f32"):
+        if encoding not in ENCODINGS:
+            raise ValueError(f"encoding must be one of {ENCODINGS}, got {encoding!r}")
+        self.res, self.encoding = res, encoding
+
+    @property
+    def rate_out(self) -> int:
+        return self.res.rate_out
+
+    def out_range(self, origin: int, L: int) -> Tuple[int, int]:
+        return self.res.out_range(origin, L)
+
+    def forward(self, wav, lengths=None, row_scale: int = 1, origin: int = 0, pcm16: bool = False, normalize: bool = False):
+        if pcm16 or normalize:
+            raise ValueError("an output stage stores its own encoding: pcm16= and normalize= do not go with it")
+        return self.res.forward(wav, lengths=lengths, row_scale=row_scale, origin=origin, encoding=self.encoding)
+
+    def open_session(self) -> ResamplerSession:
+        return ResamplerSession(self.res, self.encoding)
 
 
 _shared: dict = {}

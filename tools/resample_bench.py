@@ -13,7 +13,15 @@ For each configuration (fp32 at 1 x 1000 frames, bf16 at 32 x 500 frames) and ea
            numpy in float32 -- `host_resampler` says which; neither is the bit-exact resample_host, which is far slower).
 Each figure is the median of R rounds of N calls.  Prints one JSON object.
 
-usage: python tools/resample_bench.py [--out FILE] [--rounds R]
+--chunked FRAMES measures the streamed form instead (no vocoder is built): a random waveform of 1 x 1000 frames of 256 samples to
+--rate (8000 Hz) in --encoding (f32, pcm16, ulaw, alaw):
+  whole_call      Resampler.forward of the whole waveform, device and wall time per call
+  window          ONE Resampler.forward_window on the window a ResamplerSession holds after a push of FRAMES frames (the piece and
+                  the samples kept from the window before), device and wall time per call: the cost a chunk pays
+  session_pass    the whole waveform pushed through a ResamplerSession FRAMES frames at a time and flushed, wall time per pass and
+                  per window (torch.cat of the held samples and the plan's two host calls included)
+
+usage: python tools/resample_bench.py [--out FILE] [--rounds R] [--chunked FRAMES [--encoding E] [--rate HZ]]
 """
 import argparse
 import ctypes
@@ -60,12 +68,57 @@ def host_resample(wav, rate_out, bank, up, down):
     return np.stack([np.einsum("nt,nt->n", w[idx], rows) for w in wav])
 
 
+def chunked(args, dev):
+    hop, frames = 256, 1000
+    L, step, enc = hop * frames, hop * args.chunked, args.encoding
+    rs = Resampler(args.rate, device=dev)
+    wav = torch.from_numpy(np.random.default_rng(7).uniform(-1.0, 1.0, (1, L)).astype(np.float32)).to(dev)
+    n_next, origin = rs.window_plan(0, step, 0, False)          # what the first push emits and keeps
+    window = wav[:, origin:2 * step].contiguous()
+    n_hi = rs.window_plan(origin, window.shape[1], n_next, False)[0]
+
+    def whole():
+        return rs.forward(wav, encoding=enc)
+
+    def one_window():
+        return rs.forward_window(window, origin, n_next, False, encoding=enc)
+
+    def session_pass():
+        session = rs.open_session(enc)
+        out = [session.push(wav[:, at:at + step]) for at in range(0, L, step)]
+        return out + [session.flush()]
+
+    assert torch.equal(torch.cat(session_pass(), dim=1), whole())
+    windows = -(-L // step) + 1
+    passes = wall_ms(session_pass, 3, args.rounds)
+    result = {"tool": "tools/resample_bench.py --chunked", "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
+              "rate_out": args.rate, "encoding": enc, "samples_in": L, "samples_out": rs.out_range(0, L)[1], "chunk_frames": args.chunked,
+              "window_samples_in": int(window.shape[1]), "window_samples_out": n_hi - n_next, "windows_per_pass": windows,
+              "whole_call": {"device": device_ms(whole, 20, args.rounds), "wall": wall_ms(whole, 20, args.rounds)},
+              "window": {"device": device_ms(one_window, 50, args.rounds), "wall": wall_ms(one_window, 50, args.rounds)},
+              "session_pass": {"wall": passes, "wall_per_window_median_ms": passes["median_ms"] / windows}}
+    rs.close()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--chunked", type=int, default=None, metavar="FRAMES", help="measure the streamed form at FRAMES frames per push")
+    ap.add_argument("--encoding", type=str, default="f32", choices=["f32", "pcm16", "ulaw", "alaw"], help="with --chunked")
+    ap.add_argument("--rate", type=int, default=8000, help="with --chunked: the output rate")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if args.chunked is not None:
+        if args.chunked < 1:
+            ap.error("--chunked takes a positive number of frames")
+        result = chunked(args, dev)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+        print(json.dumps(result))
+        return 0
     lib = _native.load()
     cfg = GeneratorConfig()
     eng = GeneratorEngine(cfg, seeded_state_dict(cfg, seed=2025, gain=1.18, post_gain=20.0), dev)
