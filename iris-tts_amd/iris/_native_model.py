@@ -167,6 +167,15 @@ class _DeviceStage(_NativeModel):
         _native.check(name, fn(ctypes.byref(cfg), *args, ctypes.byref(out)))
         return int(out.value)
 
+    def _window_range(self, origin: int, Lw: int, final: bool):
+        """``iris_<_abi_name>_window_range(config, origin, Lw, final, &out_lo, &out_count)``: the samples of an utterance the
+        window ``[origin, origin + Lw)`` settles.  No device needed."""
+        name = f"iris_{self._abi_name}_window_range"
+        cfg, lo, count = self._query_config(), ctypes.c_int64(), ctypes.c_int64()
+        _native.check(name, getattr(_native.load(), name)(
+            ctypes.byref(cfg), ctypes.c_int64(int(origin)), int(Lw), int(bool(final)), ctypes.byref(lo), ctypes.byref(count)))
+        return int(lo.value), int(count.value)
+
     # -- the native handle -------------------------------------------------------------------
     def _upload_blob(self) -> np.ndarray:
         return np.zeros(0, dtype=np.float32)            # the library designs its own tables

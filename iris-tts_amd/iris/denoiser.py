@@ -34,6 +34,7 @@ import torch
 
 from . import _native
 from ._native_model import _DeviceStage, _ptr, _stream, _take_shapes, _wave
+from ._window_session import _RangeSession
 from .vae import _lengths_on, check_lengths
 
 
@@ -243,11 +244,7 @@ class Denoiser(_DeviceStage):
         """``(out_lo, out_count)``: the samples of an utterance that the window ``[origin, origin + Lw)`` settles -- those whose
         ``n_fft / hop_length`` frames each lie inside the window or do not exist (``iris_denoiser_window_range``: the finality
         rule, written down on the C side only).  ``final``: the window ends where the utterance ends.  Host only."""
-        lib = _native.load()
-        cfg, lo, count = self.native_config(), ctypes.c_int64(), ctypes.c_int64()
-        _native.check("iris_denoiser_window_range", lib.iris_denoiser_window_range(
-            ctypes.byref(cfg), ctypes.c_int64(int(origin)), int(Lw), int(bool(final)), ctypes.byref(lo), ctypes.byref(count)))
-        return int(lo.value), int(count.value)
+        return self._window_range(origin, Lw, final)
 
     def window_workspace_bytes(self, B: int, Lw: int) -> int:
         return self._query("window_workspace_bytes", B, Lw)
@@ -286,113 +283,28 @@ class Denoiser(_DeviceStage):
         return ChunkedDenoiser(self)
 
 
-class DenoiserSession:
-    """Pushed input for a denoiser: the waveform of ONE utterance (or a batch of equal lengths) arrives piece by piece
-    (``push``), denoised samples leave as soon as they are final, ``flush`` ends the utterance.  The concatenation of everything
-    returned equals ``forward_device`` of the concatenated pieces bit for bit: a sample is the sum over its ``n_fft / hop``
-    frames, each a fixed-order sum over its own ``n_fft`` samples, so it is final once those samples have arrived -- or lie
-    past an end of the utterance, where the one-shot reads zeros too (``Denoiser.window_range``).
+class DenoiserSession(_RangeSession):
+    """Pushed input for a denoiser (``_WindowSession``: ``push`` pieces ``[B, hop * m]``, ``flush`` at the end).  The
+    concatenation of everything returned equals ``forward_device`` of the concatenated pieces bit for bit: a sample is the sum
+    over its ``n_fft / hop`` frames, each a fixed-order sum over its own ``n_fft`` samples, so it is final once those samples
+    have arrived -- or lie past an end of the utterance, where the one-shot reads zeros too (``Denoiser.window_range``).
 
     ``dn``: a ``Denoiser``, or any object with ``hop_length``, ``window_range(origin, Lw, final) -> (out_lo, out_count)`` and
-    ``forward_window(wav, origin, final, strength=) -> [B, out_count]``.  Each push runs ONE window over what is buffered and
-    keeps only the input tail the next window needs: ``halo = (left, right)`` samples, asked of ``window_range`` (768 and 768 at
-    1024 / 256, three frames each; 128 and 128 at 256 / 128), so ``samples_buffered`` stays within ``left + right`` plus the
-    piece just pushed, and the frames inside that tail are the only work done twice.
+    ``forward_window(wav, origin, final, strength=) -> [B, out_count]``.  A window starts on a multiple of ``hop_length`` and
+    the session keeps only the input tail the next one needs: ``halo = (left, right)`` samples, asked of ``window_range`` (768
+    and 768 at 1024 / 256, three frames each; 128 and 128 at 256 / 128), so ``samples_buffered`` stays within ``left + right``
+    plus the piece just pushed, and the frames inside that tail are the only work done twice.
 
     Latency: sample s leaves with the push that brings ``samples_received`` to ``s + right``.  Pieces therefore do not have
     the lengths of the pushes: the first is short by ``right`` samples (or empty, and then nothing is launched) and ``flush``
     returns the last ``right``."""
 
     def __init__(self, dn, strength: Optional[float] = None):
-        self._dn, self.strength = dn, strength
-        self.hop_length = int(dn.hop_length)
-        self.halo = self._measure_halo()
-        self._buf: Optional[torch.Tensor] = None          # samples [self._base, self._total) of the utterance, [B, n]
-        self._base = 0
-        self._total = 0
-        self._emitted = 0
-        self._closed = False
+        self.strength, self.hop_length = strength, int(dn.hop_length)
+        super().__init__(dn, step=self.hop_length, piece_multiple=self.hop_length)
 
-    def _measure_halo(self):
-        """``(left, right)``: what an interior window loses on either side, read off two windows long enough to settle
-        something -- one that starts inside an utterance and ends with it, one that starts with it and ends inside."""
-        hop, span = self.hop_length, self.hop_length
-        while True:
-            (lo_l, n_l), (lo_r, n_r) = self._dn.window_range(hop, span, True), self._dn.window_range(0, span, False)
-            if n_l and n_r:
-                return lo_l - hop, span - (lo_r + n_r)
-            if span > 1 << 28:
-                raise ValueError("window_range settles no sample of any window: no halo can be derived")
-            span *= 2
-
-    @property
-    def samples_received(self) -> int:
-        return self._total
-
-    @property
-    def samples_emitted(self) -> int:
-        return self._emitted
-
-    @property
-    def samples_buffered(self) -> int:
-        return self._total - self._base
-
-    def _empty(self) -> torch.Tensor:
-        if self._buf is None:
-            return torch.empty((0, 0), dtype=torch.float32)
-        return self._buf.new_empty((self._buf.shape[0], 0))
-
-    def _advance(self, final: bool) -> torch.Tensor:
-        if self._buf is None:
-            return self._empty()
-        lo, count = self._dn.window_range(self._base, self._total - self._base, final)
-        if count == 0 or lo + count <= self._emitted:
-            return self._empty()                              # nothing new is final: no launch
-        if lo > self._emitted:
-            raise RuntimeError(f"the window [{self._base}, {self._total}) settles samples from {lo} on, but {self._emitted} is due")
-        out = self._dn.forward_window(self._buf, self._base, final, strength=self.strength)
-        piece = out[:, self._emitted - lo:] if self._emitted > lo else out
-        self._emitted = lo + count
-        # the next window: the last origin (a multiple of hop) whose first final sample is not past the next one due
-        hop = self.hop_length
-        keep_from = max(self._base, (self._emitted - self.halo[0]) // hop * hop)
-        if keep_from > self._base:
-            self._buf = self._buf[:, keep_from - self._base:]
-            self._base = keep_from
-        return piece
-
-    def push(self, wav_piece, lengths=None) -> torch.Tensor:
-        """Appends ``wav_piece [B, hop * m]`` fp32 (m >= 0) and returns the device tensor ``[B, n]`` of the samples that became
-        final; ``n`` may be 0, and then nothing was launched."""
-        if lengths is not None:
-            raise ValueError("a session takes items of one length: ragged batches stay on forward_device(lengths=)")
-        if self._closed:
-            raise RuntimeError("the session was flushed: open a new one for the next utterance")
-        if not isinstance(wav_piece, torch.Tensor):
-            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
-        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
-            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
-        if wav_piece.shape[1] % self.hop_length:
-            raise ValueError(f"a piece of {wav_piece.shape[1]} samples is not a multiple of hop_length = {self.hop_length}")
-        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
-            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
-        if self._buf is None:
-            self._buf = wav_piece
-        elif wav_piece.shape[1]:
-            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
-        self._total += int(wav_piece.shape[1])
-        return self._advance(final=False)
-
-    def flush(self) -> torch.Tensor:
-        """Ends the utterance and returns the samples that were waiting for context: the right edge of this last window is
-        the true end, as in the one-shot forward.  Further calls return an empty tensor."""
-        if self._closed:
-            return self._empty()
-        out = self._advance(final=True)
-        self._closed = True
-        self._buf = None if self._buf is None else self._buf[:, :0]
-        self._base = self._total
-        return out
+    def _forward_window(self, final: bool) -> torch.Tensor:
+        return self._stage.forward_window(self._buf, self._base, final, strength=self.strength)
 
 
 class ChunkedDenoiser:

@@ -39,6 +39,7 @@ import torch
 
 from . import _native
 from ._native_model import _DeviceStage, _ptr, _stream, _wave
+from ._window_session import _RangeSession
 
 TILE = 2048                                     # csrc/limiter.h: kTile, the output samples of a block
 MAX_LOOKAHEAD = 256                             # csrc/limiter.h: kMaxLookahead
@@ -146,11 +147,7 @@ class Limiter(_DeviceStage):
         ``2A + 7`` samples on either side each lie inside the window or outside the utterance (``iris_limiter_window_range``: the
         finality rule, written down on the C side only).  ``final``: the window ends where the utterance ends; a window with
         ``origin == 0`` starts it.  Any ``origin >= 0`` and ``Lw >= 0``: there is no hop to respect.  Host only."""
-        lib = _native.load()
-        cfg, lo, count = self.native_config(), ctypes.c_int64(), ctypes.c_int64()
-        _native.check("iris_limiter_window_range", lib.iris_limiter_window_range(
-            ctypes.byref(cfg), ctypes.c_int64(int(origin)), int(Lw), int(bool(final)), ctypes.byref(lo), ctypes.byref(count)))
-        return int(lo.value), int(count.value)
+        return self._window_range(origin, Lw, final)
 
     def window_workspace_bytes(self, B: int, Lw: int) -> int:
         return self._query("window_workspace_bytes", B, Lw)
@@ -191,18 +188,17 @@ class Limiter(_DeviceStage):
         return ChunkedLimiter(self, pcm16=pcm16)
 
 
-class LimiterSession:
-    """Pushed input for a limiter: the waveform of ONE utterance (or a batch of equal lengths) arrives piece by piece
-    (``push``), limited samples leave as soon as they are settled, ``flush`` ends the utterance.  The concatenation of everything
+class LimiterSession(_RangeSession):
+    """Pushed input for a limiter (``_WindowSession``: ``push`` pieces, ``flush`` at the end).  The concatenation of everything
     returned equals ``limit_device`` of the concatenated pieces bit for bit -- with ``pcm16=True`` it is int16 and equals
     ``pcm16_on_device`` of that: a sample's gain reads ``R = 2A + 7`` samples on either side and nothing else, every chain in its
     one order, so it is settled once those have arrived -- or lie past an end of the utterance, where the one-shot call reads
     zeros too (``Limiter.window_range``).
 
     ``lim``: a ``Limiter``, or any object with ``window_range(origin, Lw, final) -> (out_lo, out_count)`` and
-    ``forward_window(wav, origin, final, pcm16=) -> (out [B, out_count], stats [B, 2])``.  Each push runs ONE window over what is
-    buffered and keeps only the input the next window needs, from ``samples_emitted - R`` on, so ``samples_buffered`` stays within
-    ``2R`` plus the piece just pushed; ``halo = (R, R)`` is asked of ``window_range``.  Pieces may have any length, 0 included.
+    ``forward_window(wav, origin, final, pcm16=) -> (out [B, out_count], stats [B, 2])``.  The session keeps only the input the
+    next window needs, from ``samples_emitted - R`` on, so ``samples_buffered`` stays within ``2R`` plus the piece just pushed;
+    ``halo = (R, R)`` is asked of ``window_range``.  Pieces may have any length, 0 included.
 
     Latency: sample s leaves with the push that brings ``samples_received`` to ``s + R + 1``.  The first piece is therefore short
     by ``R`` samples (or empty, and then nothing is launched) and ``flush`` returns the last ``R``: 73 at 1.5 ms and 22.05 kHz.
@@ -211,39 +207,12 @@ class LimiterSession:
     ``torch.minimum`` with no read-back; ``(0, 1)`` before any window (None before any push), and after ``flush`` the one-shot
     call's ``stats`` bit for bit."""
 
+    _ragged_call = "limit_device(lengths=)"
+
     def __init__(self, lim, pcm16: bool = False):
-        self._lim, self.pcm16 = lim, bool(pcm16)
-        self.halo = self._measure_halo()
-        self._buf: Optional[torch.Tensor] = None          # samples [self._base, self._total) of the utterance, [B, n]
-        self._base = 0
-        self._total = 0
-        self._emitted = 0
-        self._closed = False
+        self.pcm16 = bool(pcm16)
+        super().__init__(lim, step=1, dtype=torch.int16 if self.pcm16 else torch.float32)
         self._stats: Optional[torch.Tensor] = None
-
-    def _measure_halo(self) -> Tuple[int, int]:
-        """``(left, right)``: what an interior window loses on either side, read off two windows long enough to settle
-        something -- one that starts inside an utterance and ends with it, one that starts with it and ends inside."""
-        span = 1
-        while True:
-            (lo_l, n_l), (lo_r, n_r) = self._lim.window_range(1, span, True), self._lim.window_range(0, span, False)
-            if n_l and n_r:
-                return lo_l - 1, span - (lo_r + n_r)
-            if span > 1 << 28:
-                raise ValueError("window_range settles no sample of any window: no halo can be derived")
-            span *= 2
-
-    @property
-    def samples_received(self) -> int:
-        return self._total
-
-    @property
-    def samples_emitted(self) -> int:
-        return self._emitted
-
-    @property
-    def samples_buffered(self) -> int:
-        return self._total - self._base
 
     @property
     def stats(self) -> Optional[torch.Tensor]:
@@ -251,63 +220,13 @@ class LimiterSession:
             return torch.tensor([0.0, 1.0], dtype=torch.float32, device=self._buf.device).repeat(self._buf.shape[0], 1)
         return self._stats
 
-    def _empty(self) -> torch.Tensor:
-        dtype = torch.int16 if self.pcm16 else torch.float32
-        if self._buf is None:
-            return torch.empty((0, 0), dtype=dtype)
-        return self._buf.new_empty((self._buf.shape[0], 0), dtype=dtype)
-
-    def _advance(self, final: bool) -> torch.Tensor:
-        if self._buf is None:
-            return self._empty()
-        lo, count = self._lim.window_range(self._base, self._total - self._base, final)
-        if count == 0 or lo + count <= self._emitted:
-            return self._empty()                              # nothing new is settled: no launch
-        if lo > self._emitted:
-            raise RuntimeError(f"the window [{self._base}, {self._total}) settles samples from {lo} on, but {self._emitted} is due")
-        out, stats = self._lim.forward_window(self._buf, self._base, final, pcm16=self.pcm16)
+    def _forward_window(self, final: bool) -> torch.Tensor:
+        out, stats = self._stage.forward_window(self._buf, self._base, final, pcm16=self.pcm16)
         # a window that still starts at sample 0 settles [0, ...) again; its stats then cover samples already counted, which
         # a maximum and a minimum do not mind
         if self._stats is not None:
             stats = torch.stack([torch.maximum(self._stats[:, 0], stats[:, 0]), torch.minimum(self._stats[:, 1], stats[:, 1])], dim=1)
         self._stats = stats
-        piece = out[:, self._emitted - lo:] if self._emitted > lo else out
-        self._emitted = lo + count
-        keep_from = max(self._base, self._emitted - self.halo[0])            # the next window's left-hand context
-        if keep_from > self._base:
-            self._buf = self._buf[:, keep_from - self._base:]
-            self._base = keep_from
-        return piece
-
-    def push(self, wav_piece, lengths=None) -> torch.Tensor:
-        """Appends ``wav_piece [B, n]`` fp32 (n >= 0) and returns the device tensor ``[B, m]`` of the samples that became
-        settled; ``m`` may be 0, and then nothing was launched."""
-        if lengths is not None:
-            raise ValueError("a session takes items of one length: ragged batches stay on limit_device(lengths=)")
-        if self._closed:
-            raise RuntimeError("the session was flushed: open a new one for the next utterance")
-        if not isinstance(wav_piece, torch.Tensor):
-            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
-        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
-            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
-        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
-            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
-        if self._buf is None:
-            self._buf = wav_piece
-        elif wav_piece.shape[1]:
-            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
-        self._total += int(wav_piece.shape[1])
-        return self._advance(final=False)
-
-    def flush(self) -> torch.Tensor:
-        """Ends the utterance and returns the samples that were waiting for context: the right edge of this last window is
-        the true end, as in the one-shot call.  Further calls return an empty tensor."""
-        if self._closed:
-            return self._empty()
-        out = self._advance(final=True)
-        self._closed = True
-        self._buf = None if self._buf is None else self._buf[:, :0]
-        self._base = self._total
         return out
 
 

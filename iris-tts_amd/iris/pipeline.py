@@ -20,6 +20,18 @@ import torch
 from .batching import pack_mels, split_waveforms
 from .streaming import StreamingSession, StreamingVocoder
 
+# why each chunked stage refuses a pipeline built on ``forward_pcm16``: its session reads the vocoder's fp32 chunks
+_NEEDS_FP32 = {
+    "denoiser": "a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+                "forward_pcm16 (no chunked PCM stage runs behind the denoiser)",
+    "stretch": "a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+               "forward_pcm16 (no chunked PCM stage runs behind the stretch)",
+    "limiter": "a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
+               "forward_pcm16 (the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))",
+    "output": "output= reads the fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 (the "
+              "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))",
+}
+
 
 class MelToWavePipeline:
     """``postnet``: an ``iris.postnet.PostNet`` (or any callable mapping a device mel ``[B, n_mels, T]`` to a
@@ -142,27 +154,16 @@ class MelToWavePipeline:
             config = getattr(getattr(vocode, "__self__", None), "cfg", None)
         self.config = config
         self._whole = vocode if getattr(vocode, "whole_utterance", False) else None
-        self._chunked_denoiser = bool(getattr(denoiser, "chunked_sessions", False))
-        self._chunked_stretch = bool(getattr(stretch, "chunked_sessions", False))
-        if self._chunked_denoiser and getattr(vocode, "__name__", "") == "forward_pcm16":
-            raise ValueError("a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-                             "forward_pcm16 (no chunked PCM stage runs behind the denoiser)")
-        if self._chunked_stretch and getattr(vocode, "__name__", "") == "forward_pcm16":
-            raise ValueError("a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-                             "forward_pcm16 (no chunked PCM stage runs behind the stretch)")
-        self._chunked_limiter = bool(getattr(limiter, "chunked_sessions", False))
-        if self._chunked_limiter and getattr(vocode, "__name__", "") == "forward_pcm16":
-            raise ValueError("a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-                             "forward_pcm16 (the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))")
-        if output is not None:
-            if not getattr(output, "chunked_sessions", False):
-                raise ValueError("output= takes a resampler with its encoding: pass output=res.chunked(encoding), not the Resampler")
-            if getattr(vocode, "__name__", "") == "forward_pcm16":
-                raise ValueError("output= reads the fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 (the "
-                                 "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))")
-            if self._chunked_limiter and getattr(limiter, "pcm16", False):
-                raise ValueError("output= reads the fp32 waveform: pass limiter=lim.chunked(), not lim.chunked(pcm16=True) (the "
-                                 "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))")
+        # the stages that stream, in the order ``infer`` applies them: what ``_open_sessions`` opens
+        self._chunked = {name: stage for name, stage in (("denoiser", denoiser), ("stretch", stretch), ("limiter", limiter),
+                                                         ("output", output)) if getattr(stage, "chunked_sessions", False)}
+        if self._chunked and getattr(vocode, "__name__", "") == "forward_pcm16":
+            raise ValueError(_NEEDS_FP32[next(iter(self._chunked))])         # the first of them speaks
+        if output is not None and "output" not in self._chunked:
+            raise ValueError("output= takes a resampler with its encoding: pass output=res.chunked(encoding), not the Resampler")
+        if output is not None and getattr(self._chunked.get("limiter"), "pcm16", False):
+            raise ValueError("output= reads the fp32 waveform: pass limiter=lim.chunked(), not lim.chunked(pcm16=True) (the "
+                             "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))")
         if self._whole is not None and hop_length is None:
             hop_length = int(vocode.hop_length)
         self.streamer = StreamingVocoder(vocode, hop_length=hop_length, chunk_frames=chunk_frames,
@@ -194,7 +195,7 @@ class MelToWavePipeline:
         pieces are the ``DenoiserSession``'s: the first short by its halo, the last carrying it, none empty.  Likewise with
         a chunked stretch and a chunked limiter (int16 pieces with ``lim.chunked(pcm16=True)``); the session of ``output=``
         comes last of all, and its pieces are at its rate and in its encoding."""
-        self._refuse_chunked_denoiser()
+        self._refuse_unstreamable()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         sessions = self._open_sessions()
@@ -202,7 +203,7 @@ class MelToWavePipeline:
             yield from self.streamer.stream(self.refine(mel))
             return
         for chunk in self.streamer.stream(self.refine(mel)):
-            piece = self._push_through(sessions, self._denoiser_input(chunk))
+            piece = self._push_through(sessions, self._session_input(chunk))
             if piece.shape[1]:
                 yield piece
         yield from self._flush_through(sessions)
@@ -210,10 +211,7 @@ class MelToWavePipeline:
     def _open_sessions(self) -> list:
         """The sessions a chunk goes through on its way out, in the order ``infer`` applies the stages: the chunked denoiser's,
         then the chunked stretch's, then the chunked limiter's, then the output stage's."""
-        sessions = [self.denoiser.open_session()] if self._chunked_denoiser else []
-        sessions += [self.stretch.open_session()] if self._chunked_stretch else []
-        sessions += [self.limiter.open_session()] if self._chunked_limiter else []
-        return sessions + ([self.output.open_session()] if self.output is not None else [])
+        return [stage.open_session() for stage in self._chunked.values()]
 
     def _output_args(self, pcm16: bool, normalize: bool, resampler):
         """``resampler`` for the output stage of ``infer`` / ``infer_batch``: the caller's, or ``output=`` -- beside which the
@@ -244,26 +242,27 @@ class MelToWavePipeline:
         return [p for p in out if p.shape[1]]
 
     @staticmethod
-    def _denoiser_input(chunk: torch.Tensor) -> torch.Tensor:
+    def _session_input(chunk: torch.Tensor) -> torch.Tensor:
         if not chunk.is_floating_point():
             raise ValueError(f"a chunked denoiser, stretch or limiter takes fp32 chunks, the vocoder returned {chunk.dtype}")
         return chunk.float()
 
-    def _refuse_chunked_denoiser(self) -> None:
+    def _refuse_unstreamable(self) -> None:
+        """``ValueError`` where a stage of this pipeline has no chunked form, or has one that was not opted into."""
         if self.assemble is not None:
             raise ValueError("a pipeline with assemble= cannot be streamed: the trim's reference level is the whole item's "
                              "maximum, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
         if self.loudness is not None:
             raise ValueError("a pipeline with loudness= cannot be streamed: the integrated loudness is the whole item's "
                              "measure, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
-        if self.limiter is not None and not self._chunked_limiter:
+        if self.limiter is not None and "limiter" not in self._chunked:
             raise ValueError("a pipeline with limiter= cannot be streamed: the gain at a sample looks 2 * lookahead + 7 samples "
                              "past it, across a chunk's end, and no chunked form is built into a plain limiter: pass "
                              "limiter=lim.chunked(), or use infer / infer_batch")
-        if self.stretch is not None and not self._chunked_stretch:
+        if self.stretch is not None and "stretch" not in self._chunked:
             raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
                              "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
-        if self.denoiser is not None and not self._chunked_denoiser:
+        if self.denoiser is not None and "denoiser" not in self._chunked:
             raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
                              "either side, and no chunked denoiser is built; use infer / infer_batch")
 
@@ -692,7 +691,7 @@ class MelToWavePipeline:
         PostNet's receptive field on either side, for a callable that has no ``receptive_field_frames`` of its own.
         Refused with a plain denoiser, stretch or limiter (``ValueError``), as ``stream`` is; with chunked ones the session's
         pieces are those of the last of their sessions."""
-        self._refuse_chunked_denoiser()
+        self._refuse_unstreamable()
         if self._whole is not None:
             raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         return PipelineSession(self, postnet_halo_frames)
@@ -790,13 +789,14 @@ class PipelineSession:
         keep_from = max(0, stop - hp)                             # the next window's left-hand context
         self._raw = [buf[:, :, keep_from - self._base:]]
         self._base = keep_from
-        return self._denoised(self._inner.push(piece))
+        return self._through_sessions(self._inner.push(piece))
 
-    def _denoised(self, chunks: List, final: bool = False) -> List:
-        """The vocoder's chunks through the denoiser's and the stretch's sessions (if there are any); empty pieces are dropped."""
+    def _through_sessions(self, chunks: List, final: bool = False) -> List:
+        """The vocoder's chunks through the sessions of the chunked stages (if there are any; ``MelToWavePipeline._open_sessions``
+        has the order), drained at the end with ``final``; empty pieces are dropped."""
         if not self._sessions:
             return chunks
-        pieces = [MelToWavePipeline._push_through(self._sessions, MelToWavePipeline._denoiser_input(c)) for c in chunks]
+        pieces = [MelToWavePipeline._push_through(self._sessions, MelToWavePipeline._session_input(c)) for c in chunks]
         pieces = [p for p in pieces if p.shape[1]]
         return pieces + MelToWavePipeline._flush_through(self._sessions) if final else pieces
 
@@ -824,7 +824,7 @@ class PipelineSession:
         if self._closed:
             return []
         out = self._advance(final=True)
-        out += self._denoised(self._inner.flush(), final=True)
+        out += self._through_sessions(self._inner.flush(), final=True)
         self._closed = True
         self._raw = []
         return out

@@ -34,8 +34,10 @@ import ctypes
 from typing import Optional, Tuple
 
 import numpy as np
+import torch
 
 from . import _native
+from ._window_session import _WindowSession
 
 DEFAULT_RATE_IN = 22050
 
@@ -145,8 +147,6 @@ class Resampler:
 
     def __init__(self, rate_out: int, rate_in: int = DEFAULT_RATE_IN, device=None, zeros: Optional[int] = None,
                  beta: Optional[float] = None, rolloff: Optional[float] = None):
-        import torch
-
         from ._engine import require_gpu
 
         self.lib = _native.load()
@@ -196,8 +196,6 @@ class Resampler:
         ``encoding``: ``"f32"`` and ``"pcm16"`` say what ``pcm16=`` says; ``"ulaw"`` / ``"alaw"`` return uint8, the G.711 byte of
         every int16 sample, stored by the same launch (``iris_resampler_forward_g711``) -- an item's row past its own count
         then holds the law's code for 0 -- and refuse ``normalize=True``."""
-        import torch
-
         g711 = None
         if encoding is not None:
             if encoding not in _native.OUT_FORMS:
@@ -281,8 +279,6 @@ class Resampler:
         fp32, int16 (``"pcm16"``) or G.711 bytes (``"ulaw"``, ``"alaw"``).  Stateless, asynchronous on the current stream, ONE
         launch of ``forward``'s kernel, no workspace; none at all when nothing is final yet.  ``ResamplerSession`` keeps the
         bookkeeping."""
-        import torch
-
         if encoding not in _native.OUT_FORMS:
             raise ValueError(f"encoding must be one of {tuple(_native.OUT_FORMS)}, got {encoding!r}")
         if not isinstance(wav, torch.Tensor):
@@ -314,13 +310,12 @@ ENCODINGS = ("f32", "pcm16", "ulaw", "alaw")
 
 
 def _torch_dtype(encoding: str):
-    import torch
     return {"f32": torch.float32, "pcm16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}[encoding]
 
 
-class ResamplerSession:
-    """Pushed input for a resampler: the waveform of ONE utterance (or a batch of equal lengths) arrives piece by piece
-    (``push``), converted samples leave as soon as their last tap has arrived, ``flush`` ends the utterance.  The concatenation
+class ResamplerSession(_WindowSession):
+    """Pushed input for a resampler (``_WindowSession``: ``push`` pieces, ``flush`` at the end); converted samples leave as soon
+    as their last tap has arrived -- past the end of the utterance the taps read zeros, as in the one-shot call.  The concatenation
     of everything returned equals ``Resampler.forward`` of the concatenated pieces bit for bit, in the session's ``encoding``
     (``"f32"``, ``"pcm16"``, ``"ulaw"``, ``"alaw"``), and has ``ceil(L * up / down)`` samples.
 
@@ -333,82 +328,26 @@ class ResamplerSession:
     Latency: output n leaves with the push that brings ``samples_received`` to ``i0(n) + Hw + 1``: ``Hw`` input samples, 45 at
     8 kHz from 22.05 kHz (2 ms).  ``flush`` returns the outputs that were waiting for them."""
 
+    _ragged_call = "forward(lengths=)"
+
     def __init__(self, res, encoding: str = "f32"):
         if encoding not in ENCODINGS:
             raise ValueError(f"encoding must be one of {ENCODINGS}, got {encoding!r}")
+        super().__init__(dtype=_torch_dtype(encoding))
         self._res, self.encoding = res, encoding
-        self._buf = None              # samples [self._base, self._total) of the utterance, [B, n]
-        self._base = 0
-        self._total = 0
         self._next = 0                # the first output not yet emitted
-        self._closed = False
-
-    @property
-    def samples_received(self) -> int:
-        return self._total
 
     @property
     def samples_emitted(self) -> int:
         return self._next
 
-    @property
-    def samples_buffered(self) -> int:
-        return self._total - self._base
-
-    def _empty(self):
-        import torch
-        dtype = _torch_dtype(self.encoding)
-        if self._buf is None:
-            return torch.empty((0, 0), dtype=dtype)
-        return self._buf.new_empty((self._buf.shape[0], 0), dtype=dtype)
-
-    def _advance(self, final: bool):
-        if self._buf is None:
-            return self._empty()
+    def _window(self, final: bool):
         n_hi, keep_from = self._res.window_plan(self._base, self._total - self._base, self._next, final)
-        if n_hi > self._next:
-            out = self._res.forward_window(self._buf, self._base, self._next, final, encoding=self.encoding)
-            self._next = n_hi
-        else:
-            out = self._empty()                                   # nothing became final: no launch
-        keep_from = min(max(keep_from, self._base), self._total)  # the next window's left-hand taps
-        if keep_from > self._base:
-            self._buf = self._buf[:, keep_from - self._base:]
-            self._base = keep_from
-        return out
-
-    def push(self, wav_piece, lengths=None):
-        """Appends ``wav_piece [B, n]`` fp32 (n >= 0) and returns the tensor ``[B, m]`` of the outputs that became final; ``m``
-        may be 0, and then nothing was launched."""
-        import torch
-
-        if lengths is not None:
-            raise ValueError("a session takes items of one length: ragged batches stay on forward(lengths=)")
-        if self._closed:
-            raise RuntimeError("the session was flushed: open a new one for the next utterance")
-        if not isinstance(wav_piece, torch.Tensor):
-            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
-        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
-            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
-        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
-            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
-        if self._buf is None:
-            self._buf = wav_piece
-        elif wav_piece.shape[1]:
-            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
-        self._total += int(wav_piece.shape[1])
-        return self._advance(final=False)
-
-    def flush(self):
-        """Ends the utterance and returns the outputs that were waiting for their last taps: past the end they read zeros,
-        as in the one-shot call.  Further calls return an empty tensor."""
-        if self._closed:
-            return self._empty()
-        out = self._advance(final=True)
-        self._closed = True
-        self._buf = None if self._buf is None else self._buf[:, :0]
-        self._base = self._total
-        return out
+        if n_hi <= self._next:
+            return self._empty(), keep_from                       # nothing became final: no launch
+        out = self._res.forward_window(self._buf, self._base, self._next, final, encoding=self.encoding)
+        self._next = n_hi
+        return out, keep_from                                     # the next window's left-hand taps
 
 
 class ChunkedResampler:

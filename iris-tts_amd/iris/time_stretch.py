@@ -37,6 +37,7 @@ import torch
 
 from . import _native
 from ._native_model import _DeviceStage, _ptr, _stream, _take_buffers, _take_shapes, _wave
+from ._window_session import _WindowSession
 from .vae import _lengths_on, check_lengths
 
 RATE_RANGE = (0.25, 4.0)
@@ -239,12 +240,12 @@ class TimeStretch(_DeviceStage):
         return StretchSession(self, check_rate(rate))
 
 
-class StretchSession:
-    """Pushed input for a time stretch at ONE rate: the waveform of one utterance (or a batch of equal lengths) arrives piece by
-    piece (``push``), stretched samples leave as soon as every frame under them is computable, ``flush`` ends the utterance.
-    The concatenation of everything returned equals ``forward_device`` of the concatenated pieces bit for bit: the phase is an
-    exact integer sum carried in the state, an output frame depends on two input rows alone, and an output sample on its own
-    ``n_fft / hop`` output frames, of which the state keeps the last ``n_fft / hop - 1``.
+class StretchSession(_WindowSession):
+    """Pushed input for a time stretch at ONE rate (``_WindowSession``: ``push`` pieces, ``flush`` at the end); stretched samples
+    leave as soon as every frame under them is computable.  The concatenation of everything returned equals ``forward_device``
+    of the concatenated pieces bit for bit: the phase is an exact integer sum carried in the state, an output frame depends on
+    two input rows alone, and an output sample on its own ``n_fft / hop`` output frames, of which the state keeps the last
+    ``n_fft / hop - 1``.
 
     ``ts``: a ``TimeStretch``, or any object with ``hop_length``, ``window_plan(rate, origin, Lw, final, u)``,
     ``forward_window(wav, rate, origin, final, u, state)`` and ``new_state(B)``.  Each push runs ONE window over the whole
@@ -253,48 +254,30 @@ class StretchSession:
     ``flush`` returns what was waiting for context.  A piece need not be whole frames; the utterance must be by ``flush``."""
 
     def __init__(self, ts, rate: float):
+        super().__init__()
         self._ts, self.rate = ts, float(rate)
         self.hop_length = int(ts.hop_length)
-        self._buf: Optional[torch.Tensor] = None          # samples [self._base, self._total) of the utterance, [B, n]
-        self._base = 0
-        self._total = 0
         self._emitted = 0
         self._u = 0
         self._state = None
-        self._closed = False
-
-    @property
-    def samples_received(self) -> int:
-        return self._total
 
     @property
     def samples_emitted(self) -> int:
         return self._emitted
 
     @property
-    def samples_buffered(self) -> int:
-        return self._total - self._base
-
-    @property
     def frames_computed(self) -> int:
         """``u``: the next output frame."""
         return self._u
 
-    def _empty(self) -> torch.Tensor:
-        if self._buf is None:
-            return torch.empty((0, 0), dtype=torch.float32)
-        return self._buf.new_empty((self._buf.shape[0], 0))
-
-    def _advance(self, final: bool) -> torch.Tensor:
-        if self._buf is None:
-            return self._empty()
+    def _window(self, final: bool) -> Tuple[torch.Tensor, int]:
         hop, held = self.hop_length, self._total - self._base
         if final and held % hop:
             raise ValueError(f"the utterance has {self._total} samples, no multiple of hop_length = {hop}; nothing is padded silently")
         Lw = held // hop * hop
         u_hi, lo, count, keep = self._ts.window_plan(self.rate, self._base, Lw, final, self._u)
         if u_hi == self._u and count == 0:
-            return self._empty()                              # no frame and no sample: no launch
+            return self._empty(), self._base                  # no frame and no sample: no launch
         if count and lo != self._emitted:
             raise RuntimeError(f"the window [{self._base}, {self._base + Lw}) emits samples from {lo} on, but {self._emitted} is due")
         if self._state is None:
@@ -302,42 +285,7 @@ class StretchSession:
         out = self._ts.forward_window(self._buf[:, :Lw], self.rate, self._base, final, self._u, self._state)
         self._emitted += count
         self._u = u_hi
-        keep = max(self._base, min(keep, self._base + Lw))    # an origin at or below keep_from, a multiple of hop, inside what is held
-        if keep > self._base:
-            self._buf = self._buf[:, keep - self._base:]
-            self._base = keep
-        return out
-
-    def push(self, wav_piece, lengths=None) -> torch.Tensor:
-        """Appends ``wav_piece [B, n]`` fp32 (n >= 0) and returns the device tensor ``[B, m]`` of the stretched samples that
-        became final; ``m`` may be 0."""
-        if lengths is not None:
-            raise ValueError("a session takes items of one length: ragged batches stay on forward_device(lengths=)")
-        if self._closed:
-            raise RuntimeError("the session was flushed: open a new one for the next utterance")
-        if not isinstance(wav_piece, torch.Tensor):
-            wav_piece = torch.from_numpy(np.ascontiguousarray(np.asarray(wav_piece, dtype=np.float32)))
-        if wav_piece.dim() != 2 or wav_piece.dtype != torch.float32:
-            raise ValueError(f"expected a waveform piece [B, n] float32, got {wav_piece.dtype} {tuple(wav_piece.shape)}")
-        if self._buf is not None and wav_piece.shape[0] != self._buf.shape[0]:
-            raise ValueError(f"every piece of an utterance has the same batch size: {self._buf.shape[0]}, got {wav_piece.shape[0]}")
-        if self._buf is None:
-            self._buf = wav_piece
-        elif wav_piece.shape[1]:
-            self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
-        self._total += int(wav_piece.shape[1])
-        return self._advance(final=False)
-
-    def flush(self) -> torch.Tensor:
-        """Ends the utterance and returns the samples that were waiting for context: the right edge of this last window is
-        the true end, as in the one-shot forward.  Further calls return an empty tensor."""
-        if self._closed:
-            return self._empty()
-        out = self._advance(final=True)
-        self._closed = True
-        self._buf = None if self._buf is None else self._buf[:, :0]
-        self._base = self._total
-        return out
+        return out, min(keep, self._base + Lw)                # an origin at or below keep_from, a multiple of hop, inside the window
 
 
 class StretchAt:

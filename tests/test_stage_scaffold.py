@@ -9,13 +9,15 @@ import pytest
 import torch
 
 from iris import _native
+from iris._window_session import _WindowSession
 from iris.assemble import Assembler
-from iris.denoiser import Denoiser
+from iris.denoiser import Denoiser, DenoiserSession
 from iris.griffin_lim import GriffinLim
-from iris.limiter import Limiter
+from iris.limiter import Limiter, LimiterSession
 from iris.loudness import LoudnessNormalizer
 from iris.mel import MelFrontend
-from iris.time_stretch import TimeStretch
+from iris.resample import ResamplerSession
+from iris.time_stretch import StretchSession, TimeStretch
 
 B, HOPS = 2, 4
 
@@ -81,6 +83,17 @@ def test_ragged_wave_refusals_are_one_text(cls, call, monkeypatch):
 def test_no_stage_keeps_a_copy_of_the_base(cls):
     own = set(vars(cls))
     allowed = {"close"} if cls is Denoiser else set()
-    assert not (own & {"_ensure", "close", "_ws_for", "_prepare", "_ws", "_query"}) - allowed, sorted(own)
+    assert not (own & {"_ensure", "close", "_ws_for", "_prepare", "_ws", "_query", "_window_range"}) - allowed, sorted(own)
     if cls not in (GriffinLim, Denoiser):                                   # these two hand an array to their create
         assert "_create" not in own and "_upload_blob" not in own
+
+
+@pytest.mark.parametrize("cls", [DenoiserSession, StretchSession, LimiterSession, ResamplerSession], ids=lambda c: c.__name__)
+def test_no_session_keeps_a_copy_of_the_base(cls):
+    """The four chunked stages' sessions share ``iris._window_session._WindowSession``: the buffer, ``push`` and ``flush`` are its."""
+    own = set(vars(cls))
+    assert issubclass(cls, _WindowSession)
+    assert not own & {"push", "flush", "samples_received", "samples_buffered", "_empty", "_advance"}, sorted(own)
+    assert cls.push is _WindowSession.push and cls.flush is _WindowSession.flush
+    if cls in (DenoiserSession, LimiterSession):                            # one plan form, one halo
+        assert "_measure_halo" not in own and "_window" not in own
