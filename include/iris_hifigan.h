@@ -1149,6 +1149,44 @@ int32_t iris_limiter_forward_window(iris_limiter_handle* h, const float* wav_dev
                                     int32_t final, void* out_dev /* [B, out_count] fp32 or int16 */, int32_t out_is_pcm16,
                                     float* stats_out_dev /* [B][2] */, void* workspace_dev, uint64_t workspace_bytes, void* stream);
 
+/* ---- Groups of windows: many streaming sessions in one call (iris.stream_group) -------------------------------------------
+ * forward_window takes one origin and one `final` for its whole batch; a group call takes them per row, so the windows of B
+ * DIFFERENT utterances -- each at its own position -- cost the launches of one.  Row b of wav_dev [B, in_stride] holds samples
+ * [origin_b, origin_b + Lw_b) of its own utterance in its first Lw_b slots (Lw_b <= in_stride; the rest of the row is never
+ * read).  What a row settles is the existing rule applied to its own item -- iris_limiter_window_range(origin_b, Lw_b, final_b),
+ * iris_resampler_window_plan(origin_b, Lw_b, n_next_b, final_b) -- and goes to the first count_b slots of row b of out_dev
+ * [B, out_stride]; the slots behind count_b hold the value of sample 0: 0.0f, int16 0, 0xFF as mu-law, 0xD5 as A-law.  Every
+ * slot of out_dev is stored exactly once.  out_stride below any count_b is IRIS_HIFIGAN_INVALID_ARGUMENT.
+ * Row b's count_b values -- and the limiter's stats -- are bit for bit those of the B = 1 forward_window call of the same item,
+ * in every output form.
+ * The descriptors are host arrays and travel BY VALUE in the kernel argument, indexed by the block's row: there is no device
+ * descriptor buffer, no copy and nothing allocated, so the calls are asynchronous on `stream` and safe inside a stream capture,
+ * as forward_window is -- and a call takes at most IRIS_WINDOW_GROUP_MAX rows (a kernel argument has 4 KB); B above it returns
+ * IRIS_HIFIGAN_UNSUPPORTED and the caller splits.
+ * Limiter: 2 launches, the tile kernel over grid.x = the largest tile count of the rows and the stats reduction over each row's
+ * own tiles.  A row with count_b == 0 is legal: its output row is all padding and its stats are (0, 1).  When EVERY count is 0
+ * nothing is launched and neither out_dev nor stats_out_dev is written, as forward_window leaves them for an empty window.  The
+ * workspace is that of a call of shape (B, in_stride): windows_workspace_bytes.  windows_launch_count is a dry run: 2, or 0.
+ * Resampler: ONE launch, no workspace; every row must meet window_plan's precondition, and one that does not fails the whole
+ * call.  When every count is 0 nothing is launched.
+ * Errors as the window entry points: a negative shape, origin or Lw_b, Lw_b > in_stride, a NULL pointer, out_dev off its type's
+ * bytes, the limiter's out_dev overlapping wav_dev, the resampler's origin, Lw or n_next outside its bounds return
+ * IRIS_HIFIGAN_INVALID_ARGUMENT; B in_stride or B out_stride above 2^31 - 1 IRIS_HIFIGAN_UNSUPPORTED; a short workspace
+ * IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches. */
+#define IRIS_WINDOW_GROUP_MAX 64
+typedef struct iris_limiter_window_item { int64_t origin; int32_t Lw; int32_t final; } iris_limiter_window_item;
+typedef struct iris_resampler_window_item { int64_t origin; int64_t n_next; int32_t Lw; int32_t final; } iris_resampler_window_item;
+int32_t iris_limiter_windows_workspace_bytes(const iris_limiter_config* cfg, int32_t B, int32_t in_stride, uint64_t* bytes);
+int32_t iris_limiter_windows_launch_count(const iris_limiter_config* cfg, int32_t B, const iris_limiter_window_item* items_host /* [B] */,
+                                          int32_t* n);
+int32_t iris_limiter_forward_windows(iris_limiter_handle* h, const float* wav_dev /* [B, in_stride] */, int32_t B, int32_t in_stride,
+                                     const iris_limiter_window_item* items_host /* [B] */, void* out_dev /* [B, out_stride] fp32 or int16 */,
+                                     int32_t out_stride, int32_t out_is_pcm16, float* stats_out_dev /* [B][2] */, void* workspace_dev,
+                                     uint64_t workspace_bytes, void* stream);
+int32_t iris_resampler_forward_windows(iris_resampler_handle* h, const float* wav_dev /* [B, in_stride] */, int32_t B, int32_t in_stride,
+                                       const iris_resampler_window_item* items_host /* [B] */, void* out_dev /* [B, out_stride] */,
+                                       int32_t out_stride, int32_t out_form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1469,4 +1469,48 @@ int32_t iris_resampler_forward_window(iris_resampler_handle* h, const float* wav
     IRIS_ABI_END
 }
 
+int32_t iris_resampler_forward_windows(iris_resampler_handle* h, const float* wav_dev, int32_t B, int32_t in_stride,
+                                       const iris_resampler_window_item* items_host, void* out_dev, int32_t out_stride, int32_t out_form,
+                                       void* stream_) {
+    IRIS_ABI_BEGIN
+    TRY(resampler_check(h, B, in_stride, 0));
+    if (out_stride < 0) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "negative shape");
+    if (out_form != IRIS_OUT_F32 && out_form != IRIS_OUT_PCM16 && out_form != IRIS_OUT_ULAW && out_form != IRIS_OUT_ALAW)
+        return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_form must be IRIS_OUT_F32, _PCM16, _ULAW or _ALAW, got %d (a window has no "
+                    "normalised form: the peak is the whole item's)", out_form);
+    if (B > resample::kGroupMax)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "a group call takes at most %d windows, got %d: split the group", resample::kGroupMax, B);
+    if ((long long)B * in_stride > 0x7fffffffll || (long long)B * out_stride > 0x7fffffffll)
+        return fail(IRIS_HIFIGAN_UNSUPPORTED, "B = %d rows of %d and %d samples exceed 2^31 - 1", B, in_stride, out_stride);
+    if (B > 0 && !items_host) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "items_host is NULL");
+    resample::ResampleItem items[resample::kGroupMax];
+    long long most = 0;
+    for (int b = 0; b < B; ++b) {                                   // every row is a window of its own: the rule is struct Window's
+        const iris_resampler_window_item& it = items_host[b];
+        if (it.Lw < 0 || it.Lw > in_stride)
+            return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "item %d: Lw = %d lies outside [0, in_stride = %d]", b, it.Lw, in_stride);
+        TRY(resampler_check(h, 1, it.Lw, it.origin));
+        resample::Window win(h->d, 0, 0, 0, false);
+        TRY(resampler_window(h, it.origin, it.Lw, it.n_next, it.final, &win));
+        TRY(resampler_check_size(1, it.Lw, win.count));
+        if (win.count > out_stride)
+            return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "item %d emits %lld outputs, out_stride = %d holds fewer", b, win.count, out_stride);
+        items[b] = resample::ResampleItem{it.origin, it.n_next, (int)win.count, it.Lw};
+        if (win.count > most) most = win.count;
+    }
+    if (B == 0 || most == 0) return IRIS_HIFIGAN_OK;                // nothing is final yet: no launch
+    if (!wav_dev || !out_dev) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "NULL argument");
+    const uintptr_t align = out_form == IRIS_OUT_F32 ? 4 : out_form == IRIS_OUT_PCM16 ? 2 : 1;
+    if ((uintptr_t)out_dev % align) return fail(IRIS_HIFIGAN_INVALID_ARGUMENT, "out_dev is off its type's %d bytes", (int)align);
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail(IRIS_HIFIGAN_HIP_ERROR, "cannot select device %d: %s", h->device, hipGetErrorString(guard.err));
+    resample::ResampleLaunch a = resampler_launch(h, wav_dev, B, in_stride, nullptr, 1, 0, 0, out_stride);
+    if (out_form == IRIS_OUT_F32)        a.y = static_cast<float*>(out_dev);
+    else if (out_form == IRIS_OUT_PCM16) a.pcm = static_cast<int16_t*>(out_dev);
+    else                                 { a.g711 = static_cast<uint8_t*>(out_dev); a.law = out_form; }
+    HIP_TRY(resample::launch_resample_group(a, items, (hipStream_t)stream_));
+    return IRIS_HIFIGAN_OK;
+    IRIS_ABI_END
+}
+
 }  // extern "C"

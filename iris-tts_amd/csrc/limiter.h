@@ -86,10 +86,23 @@
 // samples, bit for bit.  Window statistics are stats [B, 2] = (max p, min g) over the window's settled samples: the reduction
 // runs over the window's own ceil(count / kTile) tiles.  A window that settles nothing launches nothing.
 // Nothing about the speed of a window has been measured on a GPU.
+//
+// Groups of windows (iris_limiter_forward_windows): the rows of one call are windows of DIFFERENT utterances, each with its own
+// origin, length and `final`.  The same body again, tile_kernel<PCM, true>: what the launch names once for every row above --
+// `offset`, n_out, in_len, and the row's tile count -- it names per row, in TileItem item[kGroupMax] that travels by value in the
+// kernel argument behind the TileLaunch and is indexed by blockIdx.y (uniform: scalar loads from the kernarg segment, no
+// descriptor buffer, no copy, capture-safe; 64 items are 1 KB of the 4 KB a kernel argument may have, hence the cap).  The host
+// fills an item from limiter::Window and nothing else.  Rows are in_stride / out_stride apart, grid.x is the largest tile count
+// of the group, and parts are [B][grid.x][2].  A block at or past its row's own tile count stores zeros and returns, writing no
+// partials; every block stores zeros behind its row's n_out within its tile, and the blocks of the LAST column go on to
+// out_stride, so every slot of out [B, out_stride] is stored exactly once.  Whether a store is 16 bytes or scalars is decided
+// from the row's own address, as it always was.  The stats reduction runs over each row's own tiles; a row that settles nothing
+// gets (0, 1).  Registers, LDS and the private segment of the group forms: DESIGN.md, "Concurrent streams".
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include "device_info.h"
 #include "pcm_out.h"
 #include "resample.h"
@@ -149,6 +162,14 @@ struct Window {
     }
 };
 
+constexpr int kGroupMax = 64;    // IRIS_WINDOW_GROUP_MAX: the items of a group call, by value in the kernel argument
+
+// What a group call names per row where a TileLaunch names it once.
+struct TileItem {
+    int offset, n_out, in_len;  // as in TileLaunch, of this row
+    int tiles;                  // ceil(n_out / kTile): the blocks of the row that compute
+};
+
 struct TileLaunch {
     const float* wav;           // [B] rows of in_stride fp32, of which [0, in_len) may be read
     const int32_t* lengths;     // ragged: rows of each item [B] (device), or nullptr
@@ -159,9 +180,16 @@ struct TileLaunch {
     int in_len, in_stride;      // a whole item: L, L;  a window: Lw, Lw
     int offset;                 // the row's sample that is output 0: 0, or Window::offset
     int n_out, out_stride;      // outputs of a row and the row's stride: L, L, or the window's count twice (rows are packed)
-    int tiles, A;               // tiles = ceil(n_out / kTile)
+    int tiles, A;               // tiles = ceil(n_out / kTile); a group: the largest of its rows', the stride of parts
     float ceiling;
 };
+
+struct TileGroupLaunch {
+    TileLaunch a;               // in_stride, out_stride, tiles and what the rows share; in_len, offset and n_out are the items'
+    TileItem item[kGroupMax];
+};
+template <bool GROUP> struct TileArg { typedef TileLaunch type; };
+template <> struct TileArg<true> { typedef TileGroupLaunch type; };
 
 // The largest (MAX) or smallest value the block's threads bring; every thread gets it.  red: 4 words of LDS.
 template <bool MAX>
@@ -202,23 +230,35 @@ __device__ __forceinline__ void store4(void* row, int q, const mf32x4& y, int n,
     }
 }
 
-template <bool PCM>
-__global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
+template <bool GROUP> __device__ __forceinline__ const TileLaunch& shared_of(const typename TileArg<GROUP>::type& arg) {
+    if constexpr (GROUP) return arg.a;
+    else                 return arg;
+}
+
+template <bool PCM, bool GROUP>
+__global__ void __launch_bounds__(kThreads) tile_kernel(const typename TileArg<GROUP>::type arg) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float red[4];
+    const TileLaunch& a = shared_of<GROUP>(arg);
     const int b = blockIdx.y, tid = threadIdx.x, A = a.A, H = halo(A);
-    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.in_len);    // the row's samples [0, Lb) are the ones that exist here
+    int offset = a.offset, n_out = a.n_out, in_len = a.in_len, tiles = a.tiles;
+    if constexpr (GROUP) { const TileItem it = arg.item[b]; offset = it.offset; n_out = it.n_out; in_len = it.in_len; tiles = it.tiles; }
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, in_len);      // the row's samples [0, Lb) are the ones that exist here
     const long long t0 = (long long)blockIdx.x * kTile;                // the tile's first output
-    const long long s0 = t0 + a.offset;                                // ... and the row's sample it is
-    const int in_row = a.n_out - t0 < kTile ? (int)(a.n_out - t0) : kTile;        // outputs of this tile that exist (>= 1)
+    const long long s0 = t0 + offset;                                  // ... and the row's sample it is
+    const int in_row = n_out - t0 < kTile ? (int)(n_out - t0) : kTile;            // outputs of this tile that exist (>= 1; a group: maybe none)
+    // the slots of the output row this block stores: its tile's outputs, and in a group also the zeros behind the row's own
+    // outputs -- within the tile, and from the last column on to the end of the row
+    int slots = in_row;
+    if constexpr (GROUP) slots = (blockIdx.x + 1 == gridDim.x || a.out_stride - t0 < kTile) ? (int)(a.out_stride - t0) : kTile;
     constexpr size_t kOutBytes = PCM ? sizeof(int16_t) : sizeof(float);
     char* orow = a.out ? static_cast<char*>(a.out) + ((size_t)b * a.out_stride + t0) * kOutBytes : nullptr;
     const bool vec = orow && ((uintptr_t)orow & (4 * kOutBytes - 1)) == 0;        // the output row's own address
 
-    if (s0 >= Lb) {                                                 // behind the item: its zeros, no partials
+    if (s0 >= Lb || (GROUP && (int)blockIdx.x >= tiles)) {          // behind the item, or the row's own tiles: zeros, no partials
         if (!orow) return;
-        for (int q = 4 * tid; q < in_row; q += 4 * kThreads) store4<PCM>(orow, q, mf32x4{0.f, 0.f, 0.f, 0.f}, in_row - q, vec);
+        for (int q = 4 * tid; q < slots; q += 4 * kThreads) store4<PCM>(orow, q, mf32x4{0.f, 0.f, 0.f, 0.f}, slots - q, vec);
         return;
     }
     const int own = Lb - s0 < in_row ? (int)(Lb - s0) : in_row;     // the tile's outputs that are the item's own samples (>= 1)
@@ -318,7 +358,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
     }
 
     float gmin = 1.0f;
-    for (int q = 4 * tid; q < in_row; q += 4 * kThreads) {
+    for (int q = 4 * tid; q < slots; q += 4 * kThreads) {
         mf32x4 y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -329,7 +369,7 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
                 y[e] = fminf(fmaxf(xs[q + e + H] * g, -c), c);
             }
         }
-        if (orow) store4<PCM>(orow, q, y, in_row - q, vec);
+        if (orow) store4<PCM>(orow, q, y, slots - q, vec);
     }
     gmin = block_extreme<false>(gmin, red);
     if (tid == 0) {
@@ -339,10 +379,19 @@ __global__ void __launch_bounds__(kThreads) tile_kernel(const TileLaunch a) {
     }
 }
 
-inline hipError_t launch_tile(const TileLaunch& a, int B, bool pcm16, hipStream_t stream) {
+// items: nullptr, or the B <= kGroupMax rows of a group, whose in_len, offset and n_out replace a's.
+inline hipError_t launch_tile(const TileLaunch& a, const TileItem* items, int B, bool pcm16, hipStream_t stream) {
     const dim3 grid((unsigned)a.tiles, (unsigned)B), block(kThreads);
-    if (pcm16) return ::iris::launch_kernel_named("tile_kernel", tile_kernel<true>, grid, block, lds_bytes(a.A), stream, a);
-    return ::iris::launch_kernel_named("tile_kernel", tile_kernel<false>, grid, block, lds_bytes(a.A), stream, a);
+    if (items) {
+        if (B > kGroupMax) return hipErrorInvalidValue;
+        TileGroupLaunch g; memset(&g, 0, sizeof(g));
+        g.a = a;
+        for (int b = 0; b < B; ++b) g.item[b] = items[b];
+        if (pcm16) return ::iris::launch_kernel_named("tile_kernel", tile_kernel<true, true>, grid, block, lds_bytes(a.A), stream, g);
+        return ::iris::launch_kernel_named("tile_kernel", tile_kernel<false, true>, grid, block, lds_bytes(a.A), stream, g);
+    }
+    if (pcm16) return ::iris::launch_kernel_named("tile_kernel", tile_kernel<true, false>, grid, block, lds_bytes(a.A), stream, a);
+    return ::iris::launch_kernel_named("tile_kernel", tile_kernel<false, false>, grid, block, lds_bytes(a.A), stream, a);
 }
 
 struct StatsLaunch {
@@ -354,10 +403,21 @@ struct StatsLaunch {
     int tiles;
 };
 
-__global__ void __launch_bounds__(64) stats_kernel(const StatsLaunch a) {
+struct StatsGroupLaunch {
+    StatsLaunch a;              // parts, stats and the stride `tiles`; in_len, offset and n_out are the items'
+    TileItem item[kGroupMax];
+};
+template <bool GROUP> struct StatsArg { typedef StatsLaunch type; };
+template <> struct StatsArg<true> { typedef StatsGroupLaunch type; };
+
+template <bool GROUP>
+__global__ void __launch_bounds__(64) stats_kernel(const typename StatsArg<GROUP>::type arg) {
+    const StatsLaunch& a = [&]() -> const StatsLaunch& { if constexpr (GROUP) return arg.a; else return arg; }();
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.in_len);
-    const int n = Lb - a.offset < a.n_out ? (Lb > a.offset ? Lb - a.offset : 0) : a.n_out;    // the row's outputs that are its own samples
+    int offset = a.offset, n_out = a.n_out, in_len = a.in_len;
+    if constexpr (GROUP) { const TileItem it = arg.item[b]; offset = it.offset; n_out = it.n_out; in_len = it.in_len; }
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, in_len);
+    const int n = Lb - offset < n_out ? (Lb > offset ? Lb - offset : 0) : n_out;    // the row's outputs that are its own samples
     const int own = (int)(((long long)n + kTile - 1) / kTile);      // the tiles that hold one
     const float* __restrict__ parts = a.parts + (size_t)b * a.tiles * 2;
     float tp = 0.f, g = 1.0f;
@@ -366,8 +426,15 @@ __global__ void __launch_bounds__(64) stats_kernel(const StatsLaunch a) {
     if (tid == 0) { a.stats[2 * b] = tp; a.stats[2 * b + 1] = g; }
 }
 
-inline hipError_t launch_stats(const StatsLaunch& a, int B, hipStream_t stream) {
-    return ::iris::launch_kernel(stats_kernel, dim3((unsigned)B), dim3(64), 0, stream, a);
+inline hipError_t launch_stats(const StatsLaunch& a, const TileItem* items, int B, hipStream_t stream) {
+    if (items) {
+        if (B > kGroupMax) return hipErrorInvalidValue;
+        StatsGroupLaunch g; memset(&g, 0, sizeof(g));
+        g.a = a;
+        for (int b = 0; b < B; ++b) g.item[b] = items[b];
+        return ::iris::launch_kernel_named("stats_kernel", stats_kernel<true>, dim3((unsigned)B), dim3(64), 0, stream, g);
+    }
+    return ::iris::launch_kernel_named("stats_kernel", stats_kernel<false>, dim3((unsigned)B), dim3(64), 0, stream, a);
 }
 
 }  // namespace limiter

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include <vector>
 #include "device_info.h"
 #include "pcm_out.h"
@@ -157,31 +158,61 @@ struct ResampleLaunch {
 typedef float rf32x4 __attribute__((ext_vector_type(4)));
 typedef float rf32x2 __attribute__((ext_vector_type(2)));
 
-template <int OUT>
-__global__ void __launch_bounds__(256) resample_kernel(const ResampleLaunch a) {
+// Groups of windows (iris_resampler_forward_windows): the rows of one launch are windows of DIFFERENT utterances.  What the launch
+// names once for every row -- origin, n_lo, the row's outputs and its readable samples -- resample_kernel<OUT, true> reads per
+// row from ResampleItem item[kGroupMax], which travels by value in the kernel argument behind the ResampleLaunch and is indexed
+// by blockIdx.y (uniform: scalar loads from the kernarg segment; no descriptor buffer, no copy, capture-safe; 64 items are 1.5 KB
+// of the 4 KB a kernel argument may have, hence the cap).  The host fills an item from struct Window and nothing else.  L and N
+// stay what they were, the strides of the input and the output rows; grid.x covers the largest count of the group; a block
+// behind its row's own count stores the code of sample 0 and returns, and the blocks of the last column go on to the end of the
+// row, so every slot of out [B, N] is stored exactly once.  The same body: every index and operation of a row's own outputs is
+// what the one-window launch does.
+constexpr int kGroupMax = 64;
+struct ResampleItem {
+    long long origin, n_lo;     // as in ResampleLaunch, of this row
+    int count, in_len;          // the row's outputs [n_lo, n_lo + count) and its readable samples [0, in_len)
+};
+struct ResampleGroupLaunch {
+    ResampleLaunch a;           // L = in_stride, N = out_stride and what the rows share; origin and n_lo are the items'
+    ResampleItem item[kGroupMax];
+};
+template <bool GROUP> struct ResampleArg { typedef ResampleLaunch type; };
+template <> struct ResampleArg<true> { typedef ResampleGroupLaunch type; };
+template <bool GROUP> __device__ __forceinline__ const ResampleLaunch& shared_of(const typename ResampleArg<GROUP>::type& arg) {
+    if constexpr (GROUP) return arg.a;
+    else                 return arg;
+}
+
+template <int OUT, bool GROUP>
+__global__ void __launch_bounds__(256) resample_kernel(const typename ResampleArg<GROUP>::type arg) {
     extern __shared__ __attribute__((aligned(16))) float xs[];
+    const ResampleLaunch& a = shared_of<GROUP>(arg);
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int Lb = ragged_rows(a.lengths, b, a.row_scale, a.L);
+    long long origin = a.origin, n_lo = a.n_lo;
+    int n_item = a.N, in_len = a.L;                             // the row's own outputs and readable samples
+    if constexpr (GROUP) { const ResampleItem it = arg.item[b]; origin = it.origin; n_lo = it.n_lo; n_item = it.count; in_len = it.in_len; }
+    const int Lb = ragged_rows(a.lengths, b, a.row_scale, in_len);
     const int run0 = (int)blockIdx.x * kRun;                    // < N < 2^31
     const int up = a.up, down = a.down, taps = a.taps;
     // the one 64-bit step: base output of the block, its integer position and phase; the item's own output count
-    const long long nb = a.n_lo + run0;
+    const long long nb = n_lo + run0;
     const long long qb = nb * down;
     const long long i0b = qb / up;
     const int pb = (int)(qb - i0b * up);
-    const long long own = (a.origin + Lb) * (long long)up;
-    long long cnt = (own + down - 1) / down - a.n_lo;           // outputs of this item; the rest of its row is 0
-    if (cnt > a.N) cnt = a.N;
+    const long long own = (origin + Lb) * (long long)up;
+    long long cnt = (own + down - 1) / down - n_lo;             // outputs of this item; the rest of its row is 0
+    if (cnt > n_item) cnt = n_item;
     int valid = (int)((cnt - run0 < kRun) ? cnt - run0 : kRun);  // outputs of this block that are the item's own
     if (valid < 0) valid = 0;
-    const int in_block = a.N - run0 < kRun ? a.N - run0 : kRun;  // outputs of this block that exist
+    int in_block = a.N - run0 < kRun ? a.N - run0 : kRun;        // slots of the row this block stores
+    if constexpr (GROUP) { if (blockIdx.x + 1 == gridDim.x) in_block = a.N - run0; }     // the last column: on to the row's end
 
     const float* __restrict__ w = a.wav + (size_t)b * a.L;
     int shift = 0;
     if (valid > 0) {
         // LDS slot m holds item sample first + m, where first is a multiple of four floats away from a 16-byte boundary of
         // the item's addresses; the span's own first sample (item index a0, possibly negative) sits in slot `shift`.
-        const int a0 = (int)(i0b - (long long)a.half_width + 1 - a.origin);         // >= -taps, <= L
+        const int a0 = (int)(i0b - (long long)a.half_width + 1 - origin);           // >= -taps, <= L
         shift = (int)(((uintptr_t)w >> 2) + (unsigned)a0) & 3;      // (two's complement: right for a negative a0 too)
         const int first = a0 - shift;
         const int span = (int)(((long long)pb + (long long)(valid - 1) * down) / up) + taps + shift;
@@ -239,14 +270,34 @@ inline hipError_t launch_resample(const ResampleLaunch& a, hipStream_t stream) {
     if (a.B < 1 || a.B > 65535 || a.L < 1 || a.N < 1) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(((long long)a.N + kRun - 1) / kRun), (unsigned)a.B), block(256);
     const size_t lds = lds_floats(a.up, a.down, a.taps) * sizeof(float);
-    if (a.peak) return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32_PEAK>, grid, block, lds, stream, a);
-    if (a.pcm)  return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_PCM16>, grid, block, lds, stream, a);
+    if (a.peak) return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32_PEAK, false>, grid, block, lds, stream, a);
+    if (a.pcm)  return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_PCM16, false>, grid, block, lds, stream, a);
     if (a.g711 && a.law == pcm::OUT_ULAW)
-        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ULAW>, grid, block, lds, stream, a);
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ULAW, false>, grid, block, lds, stream, a);
     if (a.g711 && a.law == pcm::OUT_ALAW)
-        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ALAW>, grid, block, lds, stream, a);
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ALAW, false>, grid, block, lds, stream, a);
     if (a.g711 || !a.y) return hipErrorInvalidValue;
-    return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32>, grid, block, lds, stream, a);
+    return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32, false>, grid, block, lds, stream, a);
+}
+
+// A group: a.B <= kGroupMax rows, a.L and a.N the strides of the input and the output rows, items[b] what row b names itself.
+// One output form, as above, and no peak.  The largest count of the group must be >= 1.
+inline hipError_t launch_resample_group(const ResampleLaunch& a, const ResampleItem* items, hipStream_t stream) {
+    if (a.B < 1 || a.B > kGroupMax || a.L < 1 || a.N < 1 || a.peak) return hipErrorInvalidValue;
+    ResampleGroupLaunch g; memset(&g, 0, sizeof(g));
+    g.a = a;
+    int most = 0;
+    for (int b = 0; b < a.B; ++b) { g.item[b] = items[b]; if (items[b].count > most) most = items[b].count; }
+    if (most < 1 || most > a.N) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((long long)most + kRun - 1) / kRun), (unsigned)a.B), block(256);
+    const size_t lds = lds_floats(a.up, a.down, a.taps) * sizeof(float);
+    if (a.pcm)  return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_PCM16, true>, grid, block, lds, stream, g);
+    if (a.g711 && a.law == pcm::OUT_ULAW)
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ULAW, true>, grid, block, lds, stream, g);
+    if (a.g711 && a.law == pcm::OUT_ALAW)
+        return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_ALAW, true>, grid, block, lds, stream, g);
+    if (a.g711 || !a.y) return hipErrorInvalidValue;
+    return ::iris::launch_kernel_named("resample_kernel", resample_kernel<pcm::OUT_F32, true>, grid, block, lds, stream, g);
 }
 
 }  // namespace resample

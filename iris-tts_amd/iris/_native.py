@@ -422,6 +422,30 @@ LIMITER_SYMBOLS = {
     "iris_limiter_forward_window": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _u64, _vp]),
 }
 
+
+class LimiterWindowItem(ctypes.Structure):
+    """``iris_limiter_window_item``"""
+
+    _fields_ = [("origin", ctypes.c_int64), ("Lw", ctypes.c_int32), ("final", ctypes.c_int32)]
+
+
+class ResamplerWindowItem(ctypes.Structure):
+    """``iris_resampler_window_item``"""
+
+    _fields_ = [("origin", ctypes.c_int64), ("n_next", ctypes.c_int64), ("Lw", ctypes.c_int32), ("final", ctypes.c_int32)]
+
+
+# groups of windows, one utterance per row (iris.stream_group): bound by load() like SYMBOLS, and kept apart from LIMITER_SYMBOLS
+# and RESAMPLER_WINDOW_SYMBOLS, which stay the one-utterance forms
+WINDOW_GROUP_MAX = 64                           # include/iris_hifigan.h: IRIS_WINDOW_GROUP_MAX
+_lwi, _rwi = _c.POINTER(LimiterWindowItem), _c.POINTER(ResamplerWindowItem)
+WINDOW_GROUP_SYMBOLS = {
+    "iris_limiter_windows_workspace_bytes": (_i32, [_lmc, _i32, _i32, _u64p]),
+    "iris_limiter_windows_launch_count": (_i32, [_lmc, _i32, _lwi, _ip]),
+    "iris_limiter_forward_windows": (_i32, [_vp, _vp, _i32, _i32, _lwi, _vp, _i32, _i32, _vp, _vp, _u64, _vp]),
+    "iris_resampler_forward_windows": (_i32, [_vp, _vp, _i32, _i32, _rwi, _vp, _i32, _i32, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -449,7 +473,7 @@ def load() -> ctypes.CDLL:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **RESAMPLER_WINDOW_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
                                       **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS,
-                                      **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS}.items():
+                                      **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS, **WINDOW_GROUP_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

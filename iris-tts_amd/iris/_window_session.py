@@ -6,6 +6,7 @@ one window per push over everything held, only what is settled leaves, and no sa
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -51,7 +52,10 @@ class _WindowSession:
     def _advance(self, final: bool) -> torch.Tensor:
         if self._buf is None:
             return self._empty()
-        piece, keep_from = self._window(final)
+        return self._keep(*self._window(final))
+
+    def _keep(self, piece: torch.Tensor, keep_from: int) -> torch.Tensor:
+        """What follows a window: drops the samples in front of ``keep_from`` and hands ``piece`` on."""
         keep_from = min(max(keep_from, self._base), self._total)
         if keep_from > self._base:
             self._buf = self._buf[:, keep_from - self._base:]
@@ -61,6 +65,11 @@ class _WindowSession:
     def push(self, wav_piece, lengths=None) -> torch.Tensor:
         """Appends ``wav_piece [B, n]`` fp32 (n >= 0, host or device) and returns the device tensor ``[B, m]`` of what became
         settled; ``m`` may be 0, and then nothing was launched."""
+        self._append(wav_piece, lengths)
+        return self._advance(final=False)
+
+    def _append(self, wav_piece, lengths=None) -> None:
+        """The checks of ``push`` and the piece behind what is held; no window runs."""
         if lengths is not None:
             raise ValueError(f"a session takes items of one length: ragged batches stay on {self._ragged_call}")
         if self._closed:
@@ -78,7 +87,6 @@ class _WindowSession:
         elif wav_piece.shape[1]:
             self._buf = torch.cat([self._buf, wav_piece.to(self._buf.device)], dim=1)
         self._total += int(wav_piece.shape[1])
-        return self._advance(final=False)
 
     def flush(self) -> torch.Tensor:
         """Ends the utterance and returns what was waiting for context: the right edge of this last window is the true end,
@@ -86,17 +94,24 @@ class _WindowSession:
         if self._closed:
             return self._empty()
         out = self._advance(final=True)
+        self._close()
+        return out
+
+    def _close(self) -> None:
         self._closed = True
         self._buf = None if self._buf is None else self._buf[:, :0]
         self._base = self._total
-        return out
 
 
 class _RangeSession(_WindowSession):
     """A ``_WindowSession`` over a stage whose plan is ``window_range(origin, Lw, final) -> (out_lo, out_count)``, the samples
     a window settles, with origins on multiples of ``step`` (the denoiser's hop; 1 for the limiter).  ``halo = (left, right)``
     is what an interior window loses on either side; a window may settle samples that have left already, which are cut off.
-    A stage's session supplies ``_forward_window(final) -> out [B, out_count]``."""
+    A stage's session supplies ``_forward_window(final) -> out [B, out_count]``.
+
+    ``_window`` is three steps, so that something else may run the window -- ``iris.stream_group`` runs those of many sessions
+    in one call: ``_plan`` says which window is due and whether it launches, ``_forward_window`` runs it, ``_take`` books what
+    came back.  The rules are in ``_plan`` and ``_take`` alone."""
 
     def __init__(self, stage, step: int, dtype: torch.dtype = torch.float32, piece_multiple: int = 1):
         super().__init__(dtype, piece_multiple)
@@ -123,14 +138,24 @@ class _RangeSession(_WindowSession):
     def _forward_window(self, final: bool) -> torch.Tensor:
         raise NotImplementedError
 
-    def _window(self, final: bool) -> Tuple[torch.Tensor, int]:
+    def _plan(self, final: bool) -> SimpleNamespace:
+        """The window over everything held: ``origin``, ``Lw``, ``final``, the range ``lo``, ``count`` it settles, and
+        ``launch``: whether that holds a sample not yet emitted."""
         lo, count = self._stage.window_range(self._base, self._total - self._base, final)
-        if count == 0 or lo + count <= self._emitted:
-            return self._empty(), self._base                  # nothing new is settled: no launch
-        if lo > self._emitted:
+        launch = not (count == 0 or lo + count <= self._emitted)
+        if launch and lo > self._emitted:
             raise RuntimeError(f"the window [{self._base}, {self._total}) settles samples from {lo} on, but {self._emitted} is due")
-        out = self._forward_window(final)
-        piece = out[:, self._emitted - lo:] if self._emitted > lo else out
-        self._emitted = lo + count
+        return SimpleNamespace(origin=self._base, Lw=self._total - self._base, final=bool(final), lo=lo, count=count, launch=launch)
+
+    def _take(self, plan: SimpleNamespace, out) -> Tuple[torch.Tensor, int]:
+        """``(piece, keep_from)`` of the planned window, whose forward returned ``out [B, count]`` (None: it did not launch)."""
+        if not plan.launch:
+            return self._empty(), self._base                  # nothing new is settled: no launch
+        piece = out[:, self._emitted - plan.lo:] if self._emitted > plan.lo else out
+        self._emitted = plan.lo + plan.count
         # the next window: the last origin (a multiple of step) whose first settled sample is not past the next one due
         return piece, (self._emitted - self.halo[0]) // self._step * self._step
+
+    def _window(self, final: bool) -> Tuple[torch.Tensor, int]:
+        plan = self._plan(final)
+        return self._take(plan, self._forward_window(final) if plan.launch else None)

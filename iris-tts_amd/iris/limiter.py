@@ -27,7 +27,7 @@ launches -- one kernel body -- on a window of the utterance, with tiles over the
 ``pcm16_on_device`` of those samples.  ``lim.chunked()`` (``ChunkedLimiter``) is the opt-in with which a pipeline's ``stream`` /
 ``session`` run it last of all.  How fast a window is has not been measured on a GPU.
 
-Not built: ragged sessions, separate attack and release times (they need a recursion), stereo linking and dither.
+Many sessions in one call: ``Limiter.forward_windows`` and ``iris.stream_group``.  Not built: separate attack and release times (they need a recursion), stereo linking and dither.
 """
 from __future__ import annotations
 
@@ -179,6 +179,54 @@ class Limiter(_DeviceStage):
                 _ptr(stats), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device)))
         return out, stats
 
+    # -- groups of windows: one utterance per row ----------------------------------------------
+    def _window_items(self, items):
+        """``items``: a sequence of ``(origin, Lw, final)`` -> the C array ``iris_limiter_forward_windows`` takes."""
+        arr = (_native.LimiterWindowItem * max(len(items), 1))()
+        for b, (origin, Lw, final) in enumerate(items):
+            arr[b].origin, arr[b].Lw, arr[b].final = int(origin), int(Lw), int(bool(final))
+        return arr
+
+    def windows_workspace_bytes(self, B: int, in_stride: int) -> int:
+        return self._query("windows_workspace_bytes", B, in_stride)
+
+    def windows_launch_count(self, items) -> int:
+        """Kernel launches of one ``forward_windows``: 2, or 0 where no row settles anything (a dry run on the host)."""
+        items = list(items)
+        cfg, n = self.native_config(), ctypes.c_int32()
+        _native.check("iris_limiter_windows_launch_count", _native.load().iris_limiter_windows_launch_count(
+            ctypes.byref(cfg), len(items), self._window_items(items), ctypes.byref(n)))
+        return int(n.value)
+
+    def forward_windows(self, wav, items, pcm16: bool = False, out_stride: Optional[int] = None):
+        """Windows of ``B`` DIFFERENT utterances in one call (``iris_limiter_forward_windows``): row b of ``wav [B, in_stride]``
+        fp32 holds samples ``[origin_b, origin_b + Lw_b)`` of its own utterance in its first ``Lw_b`` slots, ``items[b] =
+        (origin_b, Lw_b, final_b)`` -> ``(out [B, out_stride], stats [B, 2], counts)``: the first ``counts[b] =
+        window_range(*items[b])[1]`` slots of row b are bit for bit ``forward_window`` of that item alone, the rest of the row is
+        0, and ``stats[b]`` is that call's too (``(0, 1)`` for a row that settles nothing).  ``out_stride``: the largest count
+        unless given.  The same 2 launches as one window, the descriptors by value in the kernel argument: nothing is copied or
+        allocated natively.  At most ``_native.WINDOW_GROUP_MAX`` rows (the library refuses more; ``iris.stream_group`` splits).
+        How fast a group call is: DESIGN.md, "Concurrent streams"."""
+        wav, items = _wave(wav), [(int(o), int(n), bool(f)) for o, n, f in items]
+        B, in_stride = int(wav.shape[0]), int(wav.shape[1])
+        if len(items) != B:
+            raise ValueError(f"{B} rows but {len(items)} items")
+        counts = [self.window_range(o, n, f)[1] for o, n, f in items]
+        most = max(counts, default=0)
+        out_stride = most if out_stride is None else int(out_stride)
+        lib = self._ensure()
+        out = torch.empty((B, out_stride), dtype=torch.int16 if pcm16 else torch.float32, device=self._device)
+        if B == 0 or most == 0:
+            return out.zero_(), self._empty_stats(B), counts
+        wav = wav.to(self._device).contiguous()
+        stats = torch.empty((B, 2), dtype=torch.float32, device=self._device)
+        ws = self._grow(self.windows_workspace_bytes(B, in_stride))
+        with torch.cuda.device(self._device):
+            _native.check("iris_limiter_forward_windows", lib.iris_limiter_forward_windows(
+                self._handle, _ptr(wav), B, in_stride, self._window_items(items), _ptr(out), out_stride, int(bool(pcm16)),
+                _ptr(stats), _ptr(ws), ctypes.c_uint64(ws.numel()), _stream(self._device)))
+        return out, stats, counts
+
     def open_session(self, pcm16: bool = False) -> "LimiterSession":
         """A ``LimiterSession`` for one utterance (or a batch of equal lengths) that arrives piece by piece."""
         return LimiterSession(self, pcm16=pcm16)
@@ -220,14 +268,20 @@ class LimiterSession(_RangeSession):
             return torch.tensor([0.0, 1.0], dtype=torch.float32, device=self._buf.device).repeat(self._buf.shape[0], 1)
         return self._stats
 
-    def _forward_window(self, final: bool) -> torch.Tensor:
-        out, stats = self._stage.forward_window(self._buf, self._base, final, pcm16=self.pcm16)
+    def _forward_window(self, final: bool):
+        return self._stage.forward_window(self._buf, self._base, final, pcm16=self.pcm16)
+
+    def _take(self, plan, result):
+        """``result``: the ``(out, stats)`` of the planned window, from ``forward_window`` or as a row of ``forward_windows``."""
+        if not plan.launch:
+            return super()._take(plan, None)
+        out, stats = result
         # a window that still starts at sample 0 settles [0, ...) again; its stats then cover samples already counted, which
         # a maximum and a minimum do not mind
         if self._stats is not None:
             stats = torch.stack([torch.maximum(self._stats[:, 0], stats[:, 0]), torch.minimum(self._stats[:, 1], stats[:, 1])], dim=1)
         self._stats = stats
-        return out
+        return super()._take(plan, out)
 
 
 class ChunkedLimiter:

@@ -773,23 +773,43 @@ class PipelineSession:
         """Frames held between calls: raw ones (with the left-hand PostNet context) + refined ones in the vocoder session."""
         return (self._total - self._base) + (self._inner._total - self._inner._base)
 
-    def _advance(self, final: bool) -> List:
-        """Refines every frame that is final now and hands it to the vocoder session."""
+    def _plan_refine(self, final: bool) -> Optional[tuple]:
+        """``(win_start, stop)``: the raw window ``[win_start, frames_received)`` whose refinement makes the frames ``[first not
+        yet refined, stop)`` final -- or None: nothing is final, or (before the end) it would not complete a chunk.  The PostNet
+        runs only when its output completes a chunk: the vocoder session emits ``[s, s + chunk)`` once it holds refined frames up
+        to ``s + chunk + hv``, and those are final ``hp`` raw frames later."""
         hp = self.postnet_halo_frames
+        if not final and self._total - hp < self._inner.frames_emitted + self.chunk_frames + self.halo_frames:
+            return None
         stop = self._total if final else self._total - hp        # refined frames [self._refined, stop) are final
         if stop <= self._refined:
-            return []
-        buf = self._raw[0] if len(self._raw) == 1 else torch.cat(self._raw, dim=2)
-        win_start = max(0, self._refined - hp)
-        window = buf[:, :, win_start - self._base:]
-        if self._refine is not None:
-            window = self._refine(window)
+            return None
+        return max(0, self._refined - hp), stop
+
+    def _raw_window(self, plan: tuple) -> torch.Tensor:
+        self._raw = [self._raw[0] if len(self._raw) == 1 else torch.cat(self._raw, dim=2)]
+        return self._raw[0][:, :, plan[0] - self._base:]
+
+    def _take_refined(self, plan: tuple, window: torch.Tensor) -> torch.Tensor:
+        """The final frames of the refined window; the raw frames the next window no longer needs are dropped."""
+        win_start, stop = plan
         piece = window[:, :, self._refined - win_start:stop - win_start]
         self._refined = stop
-        keep_from = max(0, stop - hp)                             # the next window's left-hand context
-        self._raw = [buf[:, :, keep_from - self._base:]]
+        keep_from = max(0, stop - self.postnet_halo_frames)      # the next window's left-hand context
+        self._raw = [self._raw[0][:, :, keep_from - self._base:]]
         self._base = keep_from
-        return self._through_sessions(self._inner.push(piece))
+        return piece
+
+    def _advance(self, final: bool) -> List:
+        """Refines every frame that is final now and hands it to the vocoder session: plan, forward, take
+        (``iris.stream_group`` plans for many sessions and runs ONE ragged pass)."""
+        plan = self._plan_refine(final)
+        if plan is None:
+            return []
+        window = self._raw_window(plan)
+        if self._refine is not None:
+            window = self._refine(window)
+        return self._through_sessions(self._inner.push(self._take_refined(plan, window)))
 
     def _through_sessions(self, chunks: List, final: bool = False) -> List:
         """The vocoder's chunks through the sessions of the chunked stages (if there are any; ``MelToWavePipeline._open_sessions``
@@ -803,6 +823,11 @@ class PipelineSession:
     def push(self, mel_piece) -> List[torch.Tensor]:
         """Appends the raw ``mel_piece [B, n_mels, t]`` (t >= 0, host or device) and returns the waveform chunks
         ``[B, hop * chunk]`` that became computable, in order (possibly none)."""
+        self._append(mel_piece)
+        return self._advance(final=False)
+
+    def _append(self, mel_piece) -> None:
+        """The checks of ``push`` and the piece behind what is held; nothing runs."""
         if self._closed:
             raise RuntimeError("the session was flushed: start a new one for the next utterance")
         mel_piece = self._pipeline._to_device(mel_piece)
@@ -812,11 +837,6 @@ class PipelineSession:
             self._lead = tuple(mel_piece.shape[:2])
             self._raw.append(mel_piece)
             self._total += int(mel_piece.shape[2])
-        # the PostNet runs only when its output completes a chunk: the vocoder session emits [s, s + chunk) once it holds
-        # refined frames up to s + chunk + hv, and those are final hp raw frames later
-        if self._total - self.postnet_halo_frames < self._inner.frames_emitted + self.chunk_frames + self.halo_frames:
-            return []
-        return self._advance(final=False)
 
     def flush(self) -> List[torch.Tensor]:
         """Ends the utterance: refines the frames that were waiting for context -- the right edge of this last window is the

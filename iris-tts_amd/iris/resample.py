@@ -26,11 +26,12 @@ A-law bytes (``encoding=``: telephony, one byte per sample, the integer rules of
 opt-in with which ``MelToWavePipeline(output=)`` runs such a session last of all.  Per-chunk ``forward(origin=running)`` calls do
 NOT concatenate to the whole: they take the samples in front of ``origin`` for zeros.
 
-Not built: ragged sessions, and a normalised form in windows (the peak belongs to the whole item).
+Many sessions in one launch: ``Resampler.forward_windows`` and ``iris.stream_group``.  Not built: a normalised form in windows (the peak belongs to the whole item).
 """
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -297,6 +298,40 @@ class Resampler:
                     ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return out
 
+    def forward_windows(self, wav, items, encoding: str = "f32", out_stride: Optional[int] = None):
+        """Windows of ``B`` DIFFERENT utterances in ONE launch (``iris_resampler_forward_windows``): row b of ``wav [B, in_stride]``
+        fp32 holds samples ``[origin_b, origin_b + Lw_b)`` of its own utterance in its first ``Lw_b`` slots, ``items[b] =
+        (origin_b, Lw_b, n_next_b, final_b)`` -> ``(out [B, out_stride], counts)``: the first ``counts[b] = n_hi_b - n_next_b``
+        slots of row b are bit for bit ``forward_window`` of that item alone, in ``encoding``, and the rest of the row holds
+        the code of sample 0 (0, 0, 0xFF, 0xD5).  ``out_stride``: the largest count unless given.  An item that fails
+        ``window_plan``'s precondition fails the whole call.  The descriptors travel by value in the kernel argument: nothing
+        is copied or allocated natively.  At most ``_native.WINDOW_GROUP_MAX`` rows (``iris.stream_group`` splits)."""
+        if encoding not in _native.OUT_FORMS:
+            raise ValueError(f"encoding must be one of {tuple(_native.OUT_FORMS)}, got {encoding!r}")
+        if not isinstance(wav, torch.Tensor):
+            wav = torch.from_numpy(np.ascontiguousarray(np.asarray(wav, dtype=np.float32)))
+        if wav.dim() != 2 or wav.dtype != torch.float32:
+            raise ValueError(f"expected an fp32 waveform [B, in_stride], got {wav.dtype} {tuple(wav.shape)}")
+        items = [(int(o), int(n), int(k), bool(f)) for o, n, k, f in items]
+        B, in_stride = int(wav.shape[0]), int(wav.shape[1])
+        if len(items) != B:
+            raise ValueError(f"{B} rows but {len(items)} items")
+        counts = [max(0, self.window_plan(o, n, k, f)[0] - k) for o, n, k, f in items]
+        most = max(counts, default=0)
+        out_stride = most if out_stride is None else int(out_stride)
+        out = torch.empty((B, out_stride), dtype=_torch_dtype(encoding), device=self.device)
+        if B == 0 or most == 0:
+            return out.fill_(_ZERO_CODE[encoding]), counts
+        arr = (_native.ResamplerWindowItem * B)()
+        for b, (o, n, k, f) in enumerate(items):
+            arr[b].origin, arr[b].n_next, arr[b].Lw, arr[b].final = o, k, n, int(f)
+        wav = wav.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _native.check("iris_resampler_forward_windows", self.lib.iris_resampler_forward_windows(
+                self._handle, ctypes.c_void_p(wav.data_ptr()), B, in_stride, arr, ctypes.c_void_p(out.data_ptr()), out_stride,
+                _native.OUT_FORMS[encoding], ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return out, counts
+
     def open_session(self, encoding: str = "f32") -> "ResamplerSession":
         """A ``ResamplerSession`` for one utterance (or a batch of equal lengths) that arrives piece by piece."""
         return ResamplerSession(self, encoding)
@@ -307,6 +342,9 @@ class Resampler:
 
 
 ENCODINGS = ("f32", "pcm16", "ulaw", "alaw")
+
+
+_ZERO_CODE = {"f32": 0, "pcm16": 0, "ulaw": 0xFF, "alaw": 0xD5}      # what sample 0 is in each encoding: a row's padding
 
 
 def _torch_dtype(encoding: str):
@@ -341,13 +379,24 @@ class ResamplerSession(_WindowSession):
     def samples_emitted(self) -> int:
         return self._next
 
-    def _window(self, final: bool):
+    def _plan(self, final: bool) -> SimpleNamespace:
+        """The window over everything held: ``origin``, ``Lw``, ``n_next``, ``final``, what ``window_plan`` answers for it, and
+        ``launch``: whether an output became final.  (``iris.stream_group`` runs the planned windows of many sessions at once.)"""
         n_hi, keep_from = self._res.window_plan(self._base, self._total - self._base, self._next, final)
-        if n_hi <= self._next:
-            return self._empty(), keep_from                       # nothing became final: no launch
-        out = self._res.forward_window(self._buf, self._base, self._next, final, encoding=self.encoding)
-        self._next = n_hi
-        return out, keep_from                                     # the next window's left-hand taps
+        return SimpleNamespace(origin=self._base, Lw=self._total - self._base, n_next=self._next, final=bool(final), n_hi=n_hi,
+                               keep_from=keep_from, launch=n_hi > self._next)
+
+    def _take(self, plan: SimpleNamespace, out):
+        """``(piece, keep_from)`` of the planned window, whose forward returned ``out [B, n_hi - n_next]`` (None: no launch)."""
+        if not plan.launch:
+            return self._empty(), plan.keep_from                  # nothing became final: no launch
+        self._next = plan.n_hi
+        return out, plan.keep_from                                # the next window's left-hand taps
+
+    def _window(self, final: bool):
+        plan = self._plan(final)
+        out = self._res.forward_window(self._buf, self._base, self._next, final, encoding=self.encoding) if plan.launch else None
+        return self._take(plan, out)
 
 
 class ChunkedResampler:

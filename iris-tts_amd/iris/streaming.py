@@ -217,28 +217,46 @@ class StreamingSession:
                 self._pieces = [np.concatenate(self._pieces, axis=2)]
         return self._pieces[0]
 
+    def _plan_chunk(self, final: bool) -> Optional[Chunk]:
+        """The next chunk and the window it is vocoded from, or None while the chunk, or its right-hand context, is incomplete."""
+        if self._next >= self._total:
+            return None
+        stop = min(self._next + self.chunk_frames, self._total)
+        whole = stop - self._next == self.chunk_frames
+        if not final and (not whole or self._total < stop + self.halo_frames):
+            return None
+        return Chunk(self._next, stop, max(0, self._next - self.halo_frames), min(self._total, stop + self.halo_frames))
+
+    def _chunk_window(self, c: Chunk):
+        """The mel of the planned chunk's window, ``[B, n_mels, win_stop - win_start]``."""
+        return self._cat()[:, :, c.win_start - self._base:c.win_stop - self._base]
+
+    def _take_chunk(self, c: Chunk, wav):
+        """The chunk's own samples of its window's waveform; the frames the next chunk no longer needs are dropped."""
+        piece = wav[:, c.emit_slice(self.hop_length)]
+        self._next = c.stop
+        keep_from = max(0, self._next - self.halo_frames)        # the next chunk's left-hand context
+        if keep_from > self._base:
+            self._pieces = [self._cat()[:, :, keep_from - self._base:]]
+            self._base = keep_from
+        return piece
+
     def _emit_ready(self, final: bool) -> List:
+        """Plan, forward, take, chunk by chunk (``iris.stream_group`` plans the chunks of many sessions and runs ONE forward)."""
         out = []
-        while self._next < self._total:
-            stop = min(self._next + self.chunk_frames, self._total)
-            whole = stop - self._next == self.chunk_frames
-            if not final and (not whole or self._total < stop + self.halo_frames):
-                break                                             # the chunk, or its right-hand context, is still incomplete
-            win_start = max(0, self._next - self.halo_frames)
-            win_stop = min(self._total, stop + self.halo_frames)
-            buf = self._cat()
-            wav = self.forward(buf[:, :, win_start - self._base:win_stop - self._base])
-            out.append(wav[:, (self._next - win_start) * self.hop_length:(stop - win_start) * self.hop_length])
-            self._next = stop
-            keep_from = max(0, self._next - self.halo_frames)    # the next chunk's left-hand context
-            if keep_from > self._base:
-                self._pieces = [buf[:, :, keep_from - self._base:]]
-                self._base = keep_from
-        return out
+        while True:
+            c = self._plan_chunk(final)
+            if c is None:
+                return out
+            out.append(self._take_chunk(c, self.forward(self._chunk_window(c))))
 
     def push(self, mel_piece) -> List:
         """Appends ``mel_piece [B, n_mels, t]`` (t >= 0) and returns the waveform chunks ``[B, hop * chunk]`` that became
         computable, in order (possibly none)."""
+        self._append(mel_piece)
+        return self._emit_ready(final=False)
+
+    def _append(self, mel_piece) -> None:
         if self._closed:
             raise RuntimeError("the session was flushed: start a new one for the next utterance")
         if mel_piece.ndim != 3:
@@ -248,7 +266,6 @@ class StreamingSession:
         if mel_piece.shape[2] > 0:
             self._pieces.append(mel_piece)
             self._total += int(mel_piece.shape[2])
-        return self._emit_ready(final=False)
 
     def flush(self) -> List:
         """Ends the utterance: returns the chunks that were waiting for context (the last one may be shorter than
