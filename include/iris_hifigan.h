@@ -1187,6 +1187,46 @@ int32_t iris_resampler_forward_windows(iris_resampler_handle* h, const float* wa
                                        const iris_resampler_window_item* items_host /* [B] */, void* out_dev /* [B, out_stride] */,
                                        int32_t out_stride, int32_t out_form, void* stream);
 
+/* ---- Spectral distance: the sums behind the multi-resolution STFT distance and the SNR of two waveforms (csrc/spectral_distance.h) ----
+ * ref_dev and test_dev [B, L], mono fp32, share lengths_dev (may be NULL) and row_scale >= 1 as in iris_loudness_normalize_ragged:
+ * item b owns n_b = min(L, lengths[b] * row_scale) samples of both; samples past that are never read (they may hold NaN).  The
+ * host never reads a length.  resolutions [n_res][3] = (n_fft, hop, win), 1 .. 4 of them, is a host array.  Per resolution, with
+ * N = n_fft, H = hop, K = N / 2 + 1:
+ *     the transform of csrc/stft_f32.h on both signals (center=True, constant padding, periodic Hann of win centred in N); item b
+ *         has T_b = 1 + n_b / H frames (0 for n_b == 0) and ALL of its n_b samples are read -- n_b need not be a multiple of H;
+ *     A (of ref) and B (of test) = sqrtf(re re + im im), fp32, bins 0 .. N / 2;
+ *     over the item's T_b K cells, each term in fp64 from the two fp32 values:  d2 = sum (A - B)^2;  a2 = sum A^2;
+ *         l1 = sum |log(max(A, 1e-5)) - log(max(B, 1e-5))| (the mel front-end's clip, the logarithm in double).
+ * Over the item's n_b samples x (ref), y (test):  e2 = sum (x - y)^2 and x2 = sum x^2 in fp64; emax = max |x - y| in fp32.
+ * spec_out_dev [B][n_res][3] = (d2, a2, l1) and wave_out_dev [B][3] = (e2, x2, (double)emax), doubles; frames_out_dev [B][n_res] =
+ * T_b.  An item with n_b == 0 has frames 0 and every sum 0.  The caller finishes them: spectral convergence sqrt(d2 / a2), log-STFT
+ * L1 l1 / (T_b K), SNR 10 log10(x2 / e2) dB.  csrc/spectral_distance.h states the order of every sum: fixed tiles of 8 frames and
+ * chunks of 4096 samples counted from the item's own start, a fixed thread map and tree, no atomics -- item b's results are those
+ * of its batch-of-one call on its own n_b samples, and two runs give the same bits.
+ * 3 n_res + 2 launches: per resolution the transform of ref, of test, and the tile sums; the chunk sums; the sums of an item's
+ * partials.  After a call the workspace holds, each starting on 256 bytes: the two magnitude buffers [B][1 + L / H][Ks] of the
+ * LAST resolution (fp32, Ks = K rounded up to 4, sized for the largest), every resolution's tile sums [B][ceil((1 + L / H) / 8)][3]
+ * and the chunk sums [B][ceil(L / 4096)][3] (doubles); only what belongs to an item's own frames and samples is written.
+ * test_dev may be ref_dev.  Asynchronous on `stream`, nothing allocated, safe in a stream capture.
+ * The handle owns one packed windowed DFT per resolution and no inverse table.
+ * n_res outside 1 .. 4, a size below 1, win > n_fft, hop not dividing n_fft, row_scale < 1, a negative shape, a NULL pointer,
+ * spec_out_dev, wave_out_dev or workspace_dev off 8 bytes return IRIS_HIFIGAN_INVALID_ARGUMENT; n_fft above 4096 or no multiple
+ * of 32, hop no multiple of 4, a frame window beyond the LDS, B > 65535 (grid.y) and B L above 2^31 - 1 IRIS_HIFIGAN_UNSUPPORTED; a
+ * short workspace IRIS_HIFIGAN_WORKSPACE_TOO_SMALL.  No failing call launches.  B == 0 or L == 0: nothing to do, nothing is
+ * written, IRIS_HIFIGAN_OK. */
+typedef struct iris_spectral_distance_handle iris_spectral_distance_handle;
+/* Host only (no device is needed); the launch count is a dry run of the forward's own code. */
+int32_t iris_spectral_distance_workspace_bytes(const int32_t* resolutions /* [n_res][3] */, int32_t n_res, int32_t B, int32_t L,
+                                               uint64_t* bytes);
+int32_t iris_spectral_distance_launch_count(const int32_t* resolutions /* [n_res][3] */, int32_t n_res, int32_t B, int32_t L, int32_t* n);
+/* create: on the current device, which becomes the handle's; it packs and uploads the tables. */
+int32_t iris_spectral_distance_create(const int32_t* resolutions /* [n_res][3] */, int32_t n_res, iris_spectral_distance_handle** out);
+int32_t iris_spectral_distance_destroy(iris_spectral_distance_handle* h);
+int32_t iris_spectral_distance_forward(iris_spectral_distance_handle* h, const float* ref_dev /* [B, L] */, const float* test_dev /* [B, L] */,
+                                       int32_t B, int32_t L, const int32_t* lengths_dev /* or NULL */, int32_t row_scale,
+                                       double* spec_out_dev /* [B][n_res][3] */, double* wave_out_dev /* [B][3] */,
+                                       int32_t* frames_out_dev /* [B][n_res] */, void* workspace_dev, uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,7 @@ struct Magnitude {
     }
 };
 
+#ifndef IRIS_DN_POLICIES_ONLY            // a translation unit that takes the policies alone (spectral_distance.h) carries no estimator
 struct ReduceLaunch {
     const float* mag;         // [T, Ks]
     float* bias;              // [bins] out
@@ -121,6 +122,7 @@ inline hipError_t launch_bias_reduce(const ReduceLaunch& a, hipStream_t stream) 
     const dim3 grid((unsigned)((a.bins + kReduceThreads - 1) / kReduceThreads)), block(kReduceThreads);
     return launch_kernel_named("dn_bias_reduce_kernel", dn_bias_reduce_kernel, grid, block, 0, stream, a);
 }
+#endif
 
 }  // namespace dn
 }  // namespace iris

@@ -2,7 +2,7 @@
 // (iris_vae_decoder.hip), the text stage (iris_text_encoder.hip) and the DSP stages (stft_f32.h).  Each of them packs a weight blob, uploads it, lays
 // out a workspace, checks it in front of a forward and counts its launches in a dry run; that is written here once.
 // The waveform stages (iris_mel_frontend.hip, iris_griffin_lim.hip, iris_denoiser.hip, iris_time_stretch.hip, iris_assemble.hip,
-// iris_loudness.hip, iris_limiter.hip) also take from here what their entry points repeat: the handle's allocation, the bytes
+// iris_loudness.hip, iris_limiter.hip, iris_spectral_distance.hip) also take from here what their entry points repeat: the handle's allocation, the bytes
 // of a workspace, the launch count of a forward that may be empty, the overlap test, the plain [B, L] shape check, and the
 // whole prologue of a forward on a ragged batch of waveforms (run_ragged_wave).
 // The vocoder's own create and forward (iris_hifigan.hip, generator_internal.h) do not use it.  Not installed.

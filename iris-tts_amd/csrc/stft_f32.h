@@ -1,6 +1,7 @@
 // stft_f32.h -- the two fp32 transforms the DSP stages share, with everything that belongs to a transform and to no one stage:
-// the windowed forward DFT of the mel front-end (mel_frontend.h), Griffin-Lim (griffin_lim.h) and the bias denoiser
-// (denoiser.h), and the windowed inverse STFT of the last two.  N = n_fft, H = hop, K = N / 2 + 1 bins, T frames.
+// the windowed forward DFT of the mel front-end (mel_frontend.h), the spectral distance (spectral_distance.h), Griffin-Lim
+// (griffin_lim.h) and the bias denoiser (denoiser.h), and the windowed inverse STFT of the last two.  N = n_fft, H = hop,
+// K = N / 2 + 1 bins, T frames.
 //
 //   frames   center=True, pad_mode="constant": frame t covers samples [t H - N / 2, t H + N / 2) of the item, 0 outside its own
 //            [0, n); an item of n samples has 1 + n / H frames
@@ -232,6 +233,7 @@ struct Window {
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "device_info.h"
 #include "gemm_tile_f32.h"
 
@@ -294,6 +296,13 @@ struct StftLaunch {
 //   void item(int b, int Tb) const             once per item, from one thread (dn::Subtract stores T_b)
 //   void bins4(a, row, bin0, re, im, nyq) const   four bins of frame `row` = b T + t: 8 consecutive floats of an interleaved
 //                                              row; where bin0 == 0, nyq is bin n_fft / 2 of that frame (decode_bins)
+//   int samples(int b, int L) const            optional (sd::Magnitude): the item owns that many samples n_b, ALL of them read,
+//                                              and T_b = 1 + n_b / H frames (0 for n_b == 0) -- n_b need not be a multiple of H;
+//                                              a.lengths and kExtraFrames are then not looked at.  A policy without it compiles
+//                                              to the frame rule of "Ragged batches" above, as before the trait existed.
+template <class Policy, class = void> struct owns_samples : std::false_type {};
+template <class Policy> struct owns_samples<Policy, std::void_t<decltype(&Policy::samples)>> : std::true_type {};
+
 template <class Policy>
 __global__ void __launch_bounds__(64 * kWaves) stft_kernel(const StftLaunch a, const Policy p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -303,10 +312,16 @@ __global__ void __launch_bounds__(64 * kWaves) stft_kernel(const StftLaunch a, c
     const int b = blockIdx.y, i0 = blockIdx.x * kRows;
     const int ct = blockIdx.z * kWaves + wave;               // wave-uniform
     const int H = a.hop, Cp = (H + 7) & ~7, S = Cp + 4, half = a.n_fft >> 1;
-    const int Tb = item_frames(a.lengths, b, a.T, Policy::kExtraFrames);
+    int Tb, Lb = 0;
+    if constexpr (owns_samples<Policy>::value) {
+        Lb = p.samples(b, a.L);
+        Tb = Lb > 0 ? 1 + Lb / H : 0;
+    } else {
+        Tb = item_frames(a.lengths, b, a.T, Policy::kExtraFrames);
+    }
     if (blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) p.item(b, Tb);
     if (i0 >= Tb) return;                                    // block-uniform: all 32 frames lie past the item
-    const int Lb = a.lengths ? H * (Tb - 1) : a.L;           // H (T - 1) of a dense whole utterance as well
+    if constexpr (!owns_samples<Policy>::value) Lb = a.lengths ? H * (Tb - 1) : a.L;     // H (T - 1) of a dense whole utterance as well
 
     stage_window(lds, a.y + (size_t)b * a.L, (long long)a.y_org + (long long)i0 * H - half, Lb, H, a.taps);
     __syncthreads();

@@ -446,6 +446,16 @@ WINDOW_GROUP_SYMBOLS = {
     "iris_resampler_forward_windows": (_i32, [_vp, _vp, _i32, _i32, _rwi, _vp, _i32, _i32, _vp]),
 }
 
+# the spectral-distance stage (iris.metrics): bound by load() like SYMBOLS; its config is a host array [n_res][3] of int32
+SPECTRAL_DISTANCE_MAX_RES = 4                   # csrc/spectral_distance.h: kMaxRes
+SPECTRAL_DISTANCE_SYMBOLS = {
+    "iris_spectral_distance_workspace_bytes": (_i32, [_ip, _i32, _i32, _i32, _u64p]),
+    "iris_spectral_distance_launch_count": (_i32, [_ip, _i32, _i32, _i32, _ip]),
+    "iris_spectral_distance_create": (_i32, [_ip, _i32, _c.POINTER(_vp)]),
+    "iris_spectral_distance_destroy": (_i32, [_vp]),
+    "iris_spectral_distance_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -473,7 +483,7 @@ def load() -> ctypes.CDLL:
         raise NativeLibraryError(f"could not load {path}: {exc}") from exc
     for name, (restype, argtypes) in {**SYMBOLS, **RESAMPLER_SYMBOLS, **RESAMPLER_WINDOW_SYMBOLS, **VAE_SYMBOLS, **VAE_ENCODER_SYMBOLS, **VAE_POSTERIOR_SYMBOLS, **VAE_LOSSES_SYMBOLS, **TEXT_SYMBOLS, **MEL_SYMBOLS,
                                       **GRIFFIN_LIM_SYMBOLS, **DENOISER_SYMBOLS, **TIME_STRETCH_SYMBOLS, **ASSEMBLE_SYMBOLS,
-                                      **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS, **WINDOW_GROUP_SYMBOLS}.items():
+                                      **LOUDNESS_SYMBOLS, **LIMITER_SYMBOLS, **WINDOW_GROUP_SYMBOLS, **SPECTRAL_DISTANCE_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:

@@ -1,7 +1,7 @@
 """What the models around the vocoder share (``iris.encoder``, ``iris.vae``, ``iris.postnet``): weights kept in Keras
 layouts, ``.npz`` files, and a native handle with its workspace, both built on first use and dropped when a weight changes.
 ``_DeviceStage`` is the base of the stages that have a config and no weights (``iris.mel``, ``iris.griffin_lim``,
-``iris.denoiser``, ``iris.time_stretch``, ``iris.assemble``, ``iris.loudness``, ``iris.limiter``).
+``iris.denoiser``, ``iris.time_stretch``, ``iris.assemble``, ``iris.loudness``, ``iris.limiter``, ``iris.metrics``).
 """
 from __future__ import annotations
 
