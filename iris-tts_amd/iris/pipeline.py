@@ -12,7 +12,7 @@ piece by piece from a producer that is still running, and refines and vocodes ea
 """
 from __future__ import annotations
 
-from typing import Callable, Iterator, List, Optional, Sequence
+from typing import Callable, Iterator, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -20,17 +20,54 @@ import torch
 from .batching import pack_mels, split_waveforms
 from .streaming import StreamingSession, StreamingVocoder
 
-# why each chunked stage refuses a pipeline built on ``forward_pcm16``: its session reads the vocoder's fp32 chunks
-_NEEDS_FP32 = {
-    "denoiser": "a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-                "forward_pcm16 (no chunked PCM stage runs behind the denoiser)",
-    "stretch": "a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-               "forward_pcm16 (no chunked PCM stage runs behind the stretch)",
-    "limiter": "a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not "
-               "forward_pcm16 (the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))",
-    "output": "output= reads the fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 (the "
-              "output stage stores 16-bit PCM itself: output=res.chunked('pcm16'))",
-}
+
+class _Waves(NamedTuple):
+    """A ragged batch of waveforms, as ``forward_device(lengths=)``, ``normalize_device``, ``limit_device``, ``join_device`` and
+    ``Resampler.forward`` take one: item i owns ``lengths[i] * row_scale`` samples of ``wav [B, L]`` and is 0 behind them.
+    ``lengths``: None for whole rows, a host sequence, or a device tensor; ``samples``: the items' counts where the host knows
+    them (None: whole rows, or a length only the device has)."""
+    wav: torch.Tensor
+    lengths: object = None
+    row_scale: int = 1
+    samples: Optional[Sequence[int]] = None
+
+
+class _WaveStage(NamedTuple):
+    name: str                       # the pipeline's attribute and constructor argument
+    step: Optional[str]             # the method ``_chain`` calls, ``_Waves -> _Waves`` (None: the stage belongs to ``_finish``)
+    unstreamable: Optional[str]     # why ``stream`` / ``session`` refuse it (a stage with a chunked form: unless it was opted into)
+    needs_fp32: Optional[str]       # why its chunked form refuses a pipeline built on ``forward_pcm16`` (None: no chunked form)
+    speaks: int = 0                 # where several stages refuse to stream, the one with the lowest number says why
+
+
+# the stages behind the vocoder, in the order ``infer`` applies them; the next wave stage is one entry here and its step method
+_WAVE_STAGES = (
+    _WaveStage("denoiser", "_denoise",
+               "a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on either side, "
+               "and no chunked denoiser is built; use infer / infer_batch",
+               "a chunked denoiser takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 "
+               "(no chunked PCM stage runs behind the denoiser)", speaks=5),
+    _WaveStage("stretch", "_stretch",
+               "a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole utterance; "
+               "pass stretch=ts.at(rate).chunked(), or use infer / infer_batch",
+               "a chunked stretch takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 "
+               "(no chunked PCM stage runs behind the stretch)", speaks=4),
+    _WaveStage("loudness", "_level",
+               "a pipeline with loudness= cannot be streamed: the integrated loudness is the whole item's measure, known only "
+               "when the item has ended, and no chunked form is built; use infer / infer_batch", None, speaks=2),
+    _WaveStage("limiter", "_limit",
+               "a pipeline with limiter= cannot be streamed: the gain at a sample looks 2 * lookahead + 7 samples past it, across "
+               "a chunk's end, and no chunked form is built into a plain limiter: pass limiter=lim.chunked(), or use infer / "
+               "infer_batch",
+               "a chunked limiter takes the vocoder's fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 "
+               "(the limiter's own session stores 16-bit PCM: limiter=lim.chunked(pcm16=True))", speaks=3),
+    _WaveStage("assemble", None,
+               "a pipeline with assemble= cannot be streamed: the trim's reference level is the whole item's maximum, known only "
+               "when the item has ended, and no chunked form is built; use infer / infer_batch", None, speaks=1),
+    _WaveStage("output", None, None,
+               "output= reads the fp32 waveform: build the pipeline on engine.forward, not forward_pcm16 (the output stage "
+               "stores 16-bit PCM itself: output=res.chunked('pcm16'))"),
+)
 
 
 class MelToWavePipeline:
@@ -52,87 +89,71 @@ class MelToWavePipeline:
     says ``takes_lengths`` (``GriffinLim(..., ragged=True)``: ``forward_device(mel, lengths=)``, item i bit for bit its own
     ``infer``); one that does not raises ``NotImplementedError``.
 
-    ``denoiser``: an ``iris.denoiser.Denoiser`` (or any object with ``forward_device(wav [B, L], lengths=) -> [B, L]``), or
-    None.  With one, ``infer``, ``infer_batch`` and every ``infer_from_*`` / ``resynthesize*`` route take the vocoder's fp32
-    waveform through it -- in the ragged routes with the batch's lengths -- and run the output stage afterwards as
-    stand-alone launches: ``pcm16=`` / ``normalize=`` through ``synthesis_output.pcm16_on_device``, ``resampler=`` through
-    ``Resampler.forward``.  ``stream`` and ``session`` raise ``ValueError`` for a plain ``Denoiser``: a chunk seam needs the
-    frames on either side of it.  With ``denoiser=None`` nothing changes.
+    The wave stages -- ``denoiser``, ``stretch``, ``loudness``, ``limiter``, ``assemble``, ``output`` (the table ``_WAVE_STAGES``)
+    -- are each None, and then nothing changes, or set.  With any of them ``infer``, ``infer_batch`` and every ``infer_from_*`` /
+    ``resynthesize*`` route take the vocoder's fp32 waveform through the stages that are set, in that order, and run the output
+    stage afterwards as stand-alone launches: ``pcm16=`` / ``normalize=`` through ``synthesis_output.pcm16_on_device``,
+    ``resampler=`` through ``Resampler.forward``.  In the ragged routes every stage is handed the lengths and the ``row_scale``
+    the stage in front passed on: the batch's frames (``hop * (T_i - 1)`` from a whole-utterance vocoder: its rows) and the
+    hop, or behind a stretch its device ``counts`` and ``row_scale=1``; nothing is read back.  ``stream`` and ``session``
+    refuse a stage as it is (``ValueError``).  The chunked form opts in with ``.chunked()``: any object with
+    ``chunked_sessions = True``, the stage's own whole-utterance method and an ``open_session() -> push / flush``.  Then every fp32
+    chunk the vocoder emits goes through ONE session per chunked stage, in the order ``infer`` applies the stages; what becomes
+    final is yielded (empty pieces are skipped), the end of the utterance drains the sessions, and the concatenation equals
+    ``infer(mel)`` bit for bit -- the sessions' seams are exact -- but the pieces are no longer all ``[B, hop * chunk]``: each
+    session's first piece is short by its halo and its last carries it.  A chunked stage needs fp32: a pipeline built on
+    ``forward_pcm16`` refuses it (``ValueError``), and so does a stream handed an integer chunk; a whole-utterance vocoder stays
+    refused; a stage beside it that was not opted in, or has no chunked form, still refuses to stream; ``infer``,
+    ``infer_batch`` and the ragged routes go through the whole-utterance method as before.
 
-    ``denoiser=dn.chunked()`` (an ``iris.denoiser.ChunkedDenoiser``, or any object with ``chunked_sessions = True``, a
-    ``forward_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: every fp32 chunk the
-    vocoder emits is pushed into ONE ``DenoiserSession``, what becomes final is yielded (empty pieces are skipped) and the
-    end of the utterance drains it.  The concatenation equals ``infer(mel)`` bit for bit -- the session's seams are exact --
-    but the pieces are no longer all ``[B, hop * chunk]``: the first is short by the denoiser's right-hand halo
-    (``n_fft / hop - 1`` frames: 3 at 1024 / 256) and the last carries it.  Added latency: a sample leaves that halo after
-    its chunk does, on top of ``hv + hp`` -- a chunk shorter than the halo yields nothing until a later chunk covers it.
-    ``infer``, ``infer_batch`` and the ragged routes go through ``forward_device`` as before.  Such a denoiser needs fp32: a
-    pipeline built on ``forward_pcm16`` refuses it (``ValueError``), and so does a stream handed an integer chunk; a
-    whole-utterance vocoder stays refused.
+    ``denoiser``: an ``iris.denoiser.Denoiser`` (or any object with ``forward_device(wav [B, L], lengths=) -> [B, L]``;
+    ``lengths``: the items' rows, ``hop`` samples each).  Not streamed as it is: a chunk seam needs the frames on either side
+    of it.  ``denoiser=dn.chunked()`` (an ``iris.denoiser.ChunkedDenoiser``): one ``DenoiserSession``; its halo is the
+    right-hand ``n_fft / hop - 1`` frames (3 at 1024 / 256).  Added latency: a sample leaves that halo after its chunk does, on
+    top of ``hv + hp`` -- a chunk shorter than the halo yields nothing until a later chunk covers it.
 
     ``stretch``: what ``iris.time_stretch.TimeStretch.at(rate)`` returns (or any object with ``hop_length``, ``out_samples(L)``
-    and ``forward_device(wav [B, L], lengths=) -> (out [B, n_out], counts [B])``), or None.  With one, ``infer``, ``infer_batch``
-    and every ``infer_from_*`` / ``resynthesize*`` route take the fp32 waveform -- the denoiser's, where there is one --
-    through the phase vocoder and run the output stage afterwards as stand-alone launches, as for a denoiser; an item then
-    has ``out_samples(hop * T_i)`` samples, and the ragged routes hand the stretch's ``counts`` on as sample lengths
-    (``row_scale=1``).  The waveform must be whole frames of the stretch's own ``hop_length`` (``ValueError`` otherwise).
-    ``stream`` and ``session`` raise ``ValueError`` for a plain ``ts.at(rate)``: the phase accumulator is a running state.
-    With ``stretch=None`` nothing changes.
-
-    ``stretch=ts.at(rate).chunked()`` (an ``iris.time_stretch.ChunkedStretch``, or any object with ``chunked_sessions = True``, a
-    ``forward_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: the vocoder's fp32 chunks
-    go through the chunked denoiser's session, if there is one, and then through ONE ``StretchSession``, which carries the
-    phase and the last output frames on the device.  Empty pieces are skipped and the last piece carries the halo; the
-    concatenation equals ``infer(mel)`` bit for bit.  It needs fp32 as the chunked denoiser does (``forward_pcm16`` as the
-    ``vocode`` is refused), and a plain denoiser beside it still refuses to stream.
-
-    ``assemble``: an ``iris.assemble.Assembler`` (or any object with ``join_device(wav [B, L], lengths=, row_scale=) -> (out
-    [cap], offsets [B + 1], spans [B, 2])``), or None.  With one, a batch is taken to be the sentences of one text:
-    ``infer_batch`` -- and so the batch routes of ``infer_from_phonemes`` and ``resynthesize`` -- return ``(waveform, spans)``
-    instead of a list: every item trimmed of its leading and trailing silence (``librosa.effects.trim``'s decision, on the
-    device) and laid end to end with the assembler's pause and fades, ``spans [B, 2]`` (device, int32) saying what was kept of
-    each item.  The join runs behind the denoiser and the stretch and in front of ``pcm16=`` / ``normalize=`` /
-    ``resampler=``, which then see ONE row: the peak is the joined utterance's.  Every launch is queued before the one
-    read-back, the total, which sizes the result.  ``infer`` treats every row of its mel as an item of such a batch; one row
-    is trimmed, a join of one.  ``stream`` and ``session`` refuse (``ValueError``): the reference level is the whole item's
-    maximum, and no chunked form is built.  With ``assemble=None`` nothing changes.
+    and ``forward_device(wav [B, L], lengths=) -> (out [B, n_out], counts [B])``): the phase vocoder, on the denoiser's waveform
+    where there is one.  An item then has ``out_samples(hop * T_i)`` samples -- the host knows the counts from ``out_samples``,
+    nothing synchronises -- and in the ragged routes the waveform must be whole frames of the stretch's own ``hop_length``
+    (``ValueError`` otherwise; nothing is padded silently).  Not streamed as it is: the phase accumulator is a running state.
+    ``stretch=ts.at(rate).chunked()`` (an ``iris.time_stretch.ChunkedStretch``): one ``StretchSession``, which carries the
+    phase and the last output frames on the device; the last piece carries the halo.
 
     ``loudness``: an ``iris.loudness.LoudnessNormalizer`` (or any object with ``normalize_device(wav [B, L], lengths=,
-    row_scale=) -> (out [B, L], stats [B, 2])``), or None.  With one, ``infer``, ``infer_batch`` and the batch routes of
-    ``infer_from_phonemes`` / ``resynthesize`` bring every item to the normalizer's target loudness (ITU-R BS.1770-4, measured
-    and applied on the device, per item, no read-back) behind the denoiser and the stretch and in front of ``assemble=`` --
-    each sentence is levelled, then trimmed, faded and joined -- and of ``pcm16=`` / ``normalize=`` / ``resampler=``, which
-    run as stand-alone launches as for a denoiser.  The lengths are the ones the stage in front handed on (the batch's frames
-    and the hop, or the stretch's device ``counts``).  ``stream`` and ``session`` refuse (``ValueError``): the measure is the
-    whole item's, and no chunked form is built.  With ``loudness=None`` nothing changes.
+    row_scale=) -> (out [B, L], stats [B, 2])``): every item at the normalizer's target loudness (ITU-R BS.1770-4, measured
+    and applied on the device, per item, no read-back) in ``infer``, ``infer_batch`` and the batch routes of
+    ``infer_from_phonemes`` / ``resynthesize`` -- each sentence is levelled, then trimmed, faded and joined.  Never streamed:
+    the measure is the whole item's, and no chunked form is built.
 
     ``limiter``: an ``iris.limiter.Limiter`` (or any object with ``limit_device(wav [B, L], lengths=, row_scale=) -> (out [B, L],
-    stats [B, 2])``), or None.  With one, the same routes hold every item under the limiter's true-peak ceiling by a look-ahead
-    gain that falls only around a peak -- so a ``LoudnessNormalizer(peak_ceiling=None)`` in front reaches its target -- behind
-    ``loudness=`` and in front of ``assemble=`` and of ``pcm16=`` / ``normalize=`` / ``resampler=``, which run as stand-alone
-    launches as for a denoiser.  It is handed the lengths and ``row_scale`` the stage in front passed on.  ``stream`` and
-    ``session`` refuse a plain limiter (``ValueError``): the gain looks ``2A + 7`` samples past a chunk's end.  With
-    ``limiter=None`` nothing changes.
+    stats [B, 2])``): every item under the limiter's true-peak ceiling by a look-ahead gain that falls only around a peak -- so a
+    ``LoudnessNormalizer(peak_ceiling=None)`` in front reaches its target.  Not streamed as it is: the gain looks ``2A + 7``
+    samples past a chunk's end.  ``limiter=lim.chunked()`` (an ``iris.limiter.ChunkedLimiter``): one ``LimiterSession``; the
+    first piece is short by ``2A + 7`` samples (73 at 1.5 ms and 22.05 kHz) and the last carries them, so a streamed utterance
+    is held under the ceiling.  With ``lim.chunked(pcm16=True)`` the limiter's kernel stores 16-bit PCM itself: the pieces are
+    int16 and their concatenation equals ``infer(mel, pcm16=True)``.
 
-    ``limiter=lim.chunked()`` (an ``iris.limiter.ChunkedLimiter``, or any object with ``chunked_sessions = True``, a
-    ``limit_device`` and an ``open_session() -> push / flush``) lets ``stream`` and ``session`` run: the fp32 chunks go through
-    the chunked denoiser's and the chunked stretch's sessions, if there are any, and then through ONE ``LimiterSession``, the
-    order in which ``infer`` applies the stages.  Empty pieces are skipped; the first piece is short by ``2A + 7`` samples (73 at
-    1.5 ms and 22.05 kHz) and the last carries them; the concatenation equals ``infer(mel)`` bit for bit, so a streamed
-    utterance is held under the ceiling.  With ``lim.chunked(pcm16=True)`` the limiter's kernel stores 16-bit PCM itself: the
-    pieces are int16 and their concatenation equals ``infer(mel, pcm16=True)``.  It needs fp32 as the chunked denoiser does
-    (``forward_pcm16`` as the ``vocode`` is refused); ``infer`` and ``infer_batch`` go through ``limit_device`` as before; and
-    ``assemble=`` and ``loudness=`` beside it still refuse to stream, their measures being the whole item's.
+    ``assemble``: an ``iris.assemble.Assembler`` (or any object with ``join_device(wav [B, L], lengths=, row_scale=) -> (out
+    [cap], offsets [B + 1], spans [B, 2])``).  With one, a batch is taken to be the sentences of one text: ``infer_batch`` --
+    and so the batch routes of ``infer_from_phonemes`` and ``resynthesize`` -- return ``(waveform, spans)`` instead of a list:
+    every item trimmed of its leading and trailing silence (``librosa.effects.trim``'s decision, on the device) and laid end to
+    end with the assembler's pause and fades, ``spans [B, 2]`` (device, int32) saying what was kept of each item.  ``pcm16=`` /
+    ``normalize=`` / ``resampler=`` then see ONE row: the peak is the joined utterance's.  Every launch is queued before the one
+    read-back, the total, which sizes the result.  ``infer`` treats every row of its mel as an item of such a batch; one row is
+    trimmed, a join of one.  Never streamed: the reference level is the whole item's maximum, and no chunked form is built.
 
     ``output``: what ``iris.resample.Resampler.chunked(encoding)`` returns (a ``ChunkedResampler``, or any object with
     ``chunked_sessions = True``, a ``forward(wav, lengths=, row_scale=)``, an ``out_range`` and an ``open_session() -> push /
-    flush``), or None: the output stage of a served utterance, the sample rate and the sample format a consumer takes -- 8 kHz
-    G.711 mu-law for a phone line is ``output=Resampler(8000).chunked("ulaw")``.  ``stream`` and ``session`` open its session
-    LAST, behind the limiter's, or directly behind the vocoder when no other session exists; the pieces are fp32, int16 or uint8
-    at ``output.rate_out`` and their concatenation equals ``infer(mel)`` bit for bit.  ``infer`` and ``infer_batch`` without
-    ``pcm16`` / ``normalize`` / ``resampler`` arguments apply the same resampler and encoding in one call behind the other
-    stages; those arguments beside ``output=`` are refused (``ValueError``), and so are ``lim.chunked(pcm16=True)`` and
-    ``forward_pcm16`` as the ``vocode``: the resampler reads fp32.  With ``output=None`` nothing changes."""
+    flush``): the output stage of a served utterance, the sample rate and the sample format a consumer takes -- 8 kHz G.711
+    mu-law for a phone line is ``output=Resampler(8000).chunked("ulaw")``.  ``stream`` and ``session`` open its session LAST,
+    behind the limiter's, or directly behind the vocoder when no other session exists; the pieces are fp32, int16 or uint8 at
+    ``output.rate_out``.  ``infer`` and ``infer_batch`` without ``pcm16`` / ``normalize`` / ``resampler`` arguments apply the
+    same resampler and encoding in one call behind the other stages; those arguments beside ``output=`` are refused
+    (``ValueError``), and so are ``lim.chunked(pcm16=True)`` and ``forward_pcm16`` as the ``vocode``: the resampler reads fp32.
+
+    Not built: a chunked loudness stage and a chunked assembler (above), and no chunked PCM stage behind a chunked denoiser or
+    stretch -- 16-bit pieces come from ``lim.chunked(pcm16=True)`` or ``output=res.chunked('pcm16')``."""
 
     def __init__(self, postnet: Optional[Callable], vocode: Callable, device: Optional[torch.device] = None,
                  hop_length: Optional[int] = None, chunk_frames: int = 256, halo_frames: Optional[int] = None,
@@ -155,10 +176,10 @@ class MelToWavePipeline:
         self.config = config
         self._whole = vocode if getattr(vocode, "whole_utterance", False) else None
         # the stages that stream, in the order ``infer`` applies them: what ``_open_sessions`` opens
-        self._chunked = {name: stage for name, stage in (("denoiser", denoiser), ("stretch", stretch), ("limiter", limiter),
-                                                         ("output", output)) if getattr(stage, "chunked_sessions", False)}
+        self._chunked = {s.name: getattr(self, s.name) for s in _WAVE_STAGES
+                         if s.needs_fp32 and getattr(getattr(self, s.name), "chunked_sessions", False)}
         if self._chunked and getattr(vocode, "__name__", "") == "forward_pcm16":
-            raise ValueError(_NEEDS_FP32[next(iter(self._chunked))])         # the first of them speaks
+            raise ValueError(next(s.needs_fp32 for s in _WAVE_STAGES if s.name in self._chunked))      # the first of them speaks
         if output is not None and "output" not in self._chunked:
             raise ValueError("output= takes a resampler with its encoding: pass output=res.chunked(encoding), not the Resampler")
         if output is not None and getattr(self._chunked.get("limiter"), "pcm16", False):
@@ -196,8 +217,6 @@ class MelToWavePipeline:
         a chunked stretch and a chunked limiter (int16 pieces with ``lim.chunked(pcm16=True)``); the session of ``output=``
         comes last of all, and its pieces are at its rate and in its encoding."""
         self._refuse_unstreamable()
-        if self._whole is not None:
-            raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         sessions = self._open_sessions()
         if not sessions:
             yield from self.streamer.stream(self.refine(mel))
@@ -213,15 +232,17 @@ class MelToWavePipeline:
         then the chunked stretch's, then the chunked limiter's, then the output stage's."""
         return [stage.open_session() for stage in self._chunked.values()]
 
-    def _output_args(self, pcm16: bool, normalize: bool, resampler):
-        """``resampler`` for the output stage of ``infer`` / ``infer_batch``: the caller's, or ``output=`` -- beside which the
-        caller names none, and no ``pcm16`` / ``normalize`` either."""
+    def _output_args(self, pcm16: bool, normalize: bool, resampler) -> tuple:
+        """``(pcm16, normalize, resampler)`` for the output stage of ``infer`` / ``infer_batch``: the caller's, or ``output=`` as
+        the resampler -- beside which the caller names none, and no ``pcm16`` / ``normalize`` either."""
+        if normalize and not pcm16:
+            raise ValueError("normalize=True goes with pcm16=True")
         if self.output is None:
-            return resampler
+            return pcm16, normalize, resampler
         if pcm16 or normalize or resampler is not None:
             raise ValueError("this pipeline has output=: it decides the rate and the encoding, so pcm16=, normalize= and "
                              "resampler= are not taken beside it")
-        return self.output
+        return pcm16, normalize, self.output
 
     @staticmethod
     def _push_through(sessions: list, piece: torch.Tensor) -> torch.Tensor:
@@ -247,134 +268,143 @@ class MelToWavePipeline:
             raise ValueError(f"a chunked denoiser, stretch or limiter takes fp32 chunks, the vocoder returned {chunk.dtype}")
         return chunk.float()
 
-    def _refuse_unstreamable(self) -> None:
-        """``ValueError`` where a stage of this pipeline has no chunked form, or has one that was not opted into."""
-        if self.assemble is not None:
-            raise ValueError("a pipeline with assemble= cannot be streamed: the trim's reference level is the whole item's "
-                             "maximum, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
-        if self.loudness is not None:
-            raise ValueError("a pipeline with loudness= cannot be streamed: the integrated loudness is the whole item's "
-                             "measure, known only when the item has ended, and no chunked form is built; use infer / infer_batch")
-        if self.limiter is not None and "limiter" not in self._chunked:
-            raise ValueError("a pipeline with limiter= cannot be streamed: the gain at a sample looks 2 * lookahead + 7 samples "
-                             "past it, across a chunk's end, and no chunked form is built into a plain limiter: pass "
-                             "limiter=lim.chunked(), or use infer / infer_batch")
-        if self.stretch is not None and "stretch" not in self._chunked:
-            raise ValueError("a pipeline with a plain time stretch cannot be streamed: the phase accumulator runs through the whole "
-                             "utterance; pass stretch=ts.at(rate).chunked(), or use infer / infer_batch")
-        if self.denoiser is not None and "denoiser" not in self._chunked:
-            raise ValueError("a pipeline with a denoiser cannot be streamed: a chunk seam needs n_fft / 2 samples of context on "
-                             "either side, and no chunked denoiser is built; use infer / infer_batch")
+    def _refuse_unstreamable(self, whole: Optional[Exception] = None) -> None:
+        """``ValueError`` where a stage of this pipeline has no chunked form, or has one that was not opted into; of several, the
+        one the table lets speak first (``speaks``).  Then the refusal of a whole-utterance vocoder: ``NotImplementedError``, or
+        ``whole`` (``StreamGroup`` has its own)."""
+        refused = [s for s in _WAVE_STAGES if s.unstreamable and getattr(self, s.name) is not None and s.name not in self._chunked]
+        if refused:
+            raise ValueError(min(refused, key=lambda s: s.speaks).unstreamable)
+        if self._whole is not None:
+            raise whole or NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample "
+                                               "depends on every frame")
 
-    def _vocode_whole(self, mel: torch.Tensor, pcm16: bool, normalize: bool, resampler):
-        """One call of a whole-utterance vocoder, then ``_output_stage`` on its waveform."""
-        return self._output_stage(self._whole.forward_device(mel), pcm16, normalize, resampler)
+    # -- the whole-utterance route: vocode, the chain of wave stages, finish -- every step ``_Waves -> _Waves`` -----------------
+    def _has_wave_stage(self) -> bool:
+        return any(getattr(self, s.name) is not None for s in _WAVE_STAGES)
 
-    @staticmethod
-    def _output_stage(wav: torch.Tensor, pcm16: bool, normalize: bool, resampler):
-        """The stand-alone output stages on a waveform that exists, whose length is the tensor's own: ``Resampler.forward``, or
-        ``synthesis_output.pcm16_on_device`` (``(pcm, peaks)`` with ``normalize``)."""
-        if resampler is not None:
-            return resampler.forward(wav, pcm16=pcm16, normalize=normalize)
-        if not pcm16:
-            return wav
-        from .synthesis_output import pcm16_on_device
-        return pcm16_on_device(wav, normalize=normalize)
+    def _vocode(self, mel: torch.Tensor, frames=None, forward: Optional[Callable] = None) -> _Waves:
+        """The refined ``mel`` through the vocoder, and the only place that turns frames into rows.  ``frames=None``: whole
+        rows, chunked by the streamer (a whole-utterance vocoder takes the mel in one call).  ``frames``: item i's frame count,
+        ONE ragged forward; item i owns ``hop`` samples per row, ``T_i`` rows -- ``T_i - 1`` from a whole-utterance vocoder, which
+        takes ``lengths=`` if it says ``takes_lengths`` and else has been handed items of one length (an item of one frame is
+        refused by the vocoder itself).  ``forward``: a fused route's launch in place of the streamer's (``_fused_forward``)."""
+        if frames is None:
+            return _Waves(self._whole.forward_device(mel) if self._whole is not None else (forward or self.streamer.infer)(mel))
+        rows = [int(t) for t in frames]
+        if self._whole is None:
+            wav = (forward or self.streamer.forward)(mel, lengths=frames)
+        else:
+            ragged = getattr(self._whole, "takes_lengths", False)
+            wav = self._whole.forward_device(mel, lengths=rows) if ragged else self._whole.forward_device(mel)
+            rows = [max(t - 1, 0) for t in rows]
+        hop = self.streamer.hop_length
+        return _Waves(wav, rows, hop, [hop * r for r in rows])
 
-    def _vocode_whole_ragged(self, padded: torch.Tensor, lengths, pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
-        """A batch through a whole-utterance vocoder that takes ``lengths``: ONE ``forward_device(padded, lengths=)``, whose
-        rows are 0 past ``hop * (T_i - 1)`` -- so an item's peak is its own -- then the output stage over the whole batch
-        and a list cut at each item's own count.  An item of one frame is refused by the vocoder, as ``infer`` refuses it."""
-        frames = [int(t) for t in lengths]
-        rows = [max(t - 1, 0) for t in frames]
-        return self._ragged_output_stage(self._whole.forward_device(padded, lengths=frames), rows, pcm16, normalize, resampler)
+    def _chain(self, waves: _Waves) -> _Waves:
+        """The wave stages that are set, in the table's order."""
+        for stage in _WAVE_STAGES:
+            if stage.step is not None and getattr(self, stage.name) is not None:
+                waves = getattr(self, stage.step)(waves)
+        return waves
 
-    def _denoise(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
-        """The vocoder's waveform through the denoiser (``lengths``: the items' mel frames, ``hop`` samples each)."""
-        wav = wav.float()
-        return self.denoiser.forward_device(wav) if lengths is None else self.denoiser.forward_device(wav, lengths=lengths)
+    def _denoise(self, waves: _Waves) -> _Waves:
+        """Through the denoiser; its ``lengths`` are rows of ``hop`` samples, the vocoder's (it is the first stage)."""
+        wav = waves.wav.float()
+        return waves._replace(wav=self.denoiser.forward_device(wav) if waves.lengths is None
+                              else self.denoiser.forward_device(wav, lengths=waves.lengths))
 
-    def _level(self, wav: torch.Tensor, lengths=None, row_scale: int = 1) -> torch.Tensor:
-        """The waveform through the loudness stage, if there is one: item i, ``lengths[i] * row_scale`` samples of its row (all of
-        it without ``lengths``), at the target loudness and 0 behind.  ``lengths`` may be a device tensor; nothing is read back."""
-        if self.loudness is None:
-            return wav
-        return self.loudness.normalize_device(wav.float(), lengths=lengths, row_scale=row_scale)[0]
-
-    def _limit(self, wav: torch.Tensor, lengths=None, row_scale: int = 1) -> torch.Tensor:
-        """The waveform through the limiter, if there is one, with the lengths ``_level`` was handed: every item under the
-        ceiling and 0 behind its own samples.  Nothing is read back."""
-        if self.limiter is None:
-            return wav
-        return self.limiter.limit_device(wav.float(), lengths=lengths, row_scale=row_scale)[0]
-
-    def _stretch_ragged(self, wav: torch.Tensor, rows: Sequence[int], pcm16: bool, normalize: bool, resampler) -> List[torch.Tensor]:
-        """A batch whose item i owns ``hop * rows[i]`` samples through ONE ragged stretch, then the output stage with the
-        stretch's ``counts`` as sample lengths.  The host knows the counts from ``out_samples``: nothing synchronises."""
-        hop, sh = self.streamer.hop_length, int(self.stretch.hop_length)
-        for i, r in enumerate(rows):
-            if hop * r % sh:
-                raise ValueError(f"item {i}: {hop * r} samples are not whole frames of the stretch's hop_length = {sh}; nothing is padded silently")
+    def _stretch(self, waves: _Waves) -> _Waves:
+        """Through the stretch.  A ragged batch goes through ONE call and leaves with the stretch's device ``counts`` as sample
+        lengths; the host knows the counts from ``out_samples``: nothing synchronises."""
+        wav = waves.wav.float()
+        if waves.lengths is None:
+            return _Waves(self.stretch.forward_device(wav)[0])
+        sh = int(self.stretch.hop_length)
+        for i, n in enumerate(waves.samples):
+            if n % sh:
+                raise ValueError(f"item {i}: {n} samples are not whole frames of the stretch's hop_length = {sh}; nothing is padded silently")
         if wav.shape[1] % sh:                                        # the padded row itself; its tail belongs to no item
             wav = torch.nn.functional.pad(wav, (0, sh - wav.shape[1] % sh))
-        out, counts = self.stretch.forward_device(wav, lengths=[hop * r // sh for r in rows])
-        out = self._limit(self._level(out, counts, 1), counts, 1)
+        out, counts = self.stretch.forward_device(wav, lengths=[n // sh for n in waves.samples])
+        return _Waves(out, counts, 1, [self.stretch.out_samples(n) for n in waves.samples])
+
+    def _level(self, waves: _Waves) -> _Waves:
+        """Through the loudness stage: every item at the target loudness and 0 behind its own samples.  Nothing is read back."""
+        return waves._replace(wav=self.loudness.normalize_device(waves.wav.float(), lengths=waves.lengths, row_scale=waves.row_scale)[0])
+
+    def _limit(self, waves: _Waves) -> _Waves:
+        """Through the limiter: every item under the ceiling and 0 behind its own samples.  Nothing is read back."""
+        return waves._replace(wav=self.limiter.limit_device(waves.wav.float(), lengths=waves.lengths, row_scale=waves.row_scale)[0])
+
+    def _finish(self, waves: _Waves, pcm16: bool, normalize: bool, resampler, as_list: bool = False):
+        """The assembler, if there is one -- the batch becomes ONE row with the device's total as its length, 0 behind it, so its
+        peak is the utterance's -- then the stand-alone output stage, then the cut."""
+        spans = None
         if self.assemble is not None:
-            return self._joined_output_stage(out, counts, 1, pcm16, normalize, resampler)
-        return self._ragged_output_stage(out, counts, pcm16, normalize, resampler, hop=1,
-                                         samples=[self.stretch.out_samples(hop * r) for r in rows])
+            out, offsets, spans = self.assemble.join_device(waves.wav.float(), lengths=waves.lengths, row_scale=waves.row_scale)
+            waves = _Waves(out[None], offsets[-1:])
+        return self._cut(self._output_stage(waves, pcm16, normalize, resampler), waves, normalize, resampler, as_list, spans)
 
-    def _ragged_output_stage(self, wav: torch.Tensor, rows, pcm16: bool, normalize: bool, resampler, hop: Optional[int] = None,
-                             samples: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
-        """The output stage over a batch whose item i owns ``hop * rows[i]`` samples and is 0 behind them, cut per item.
-        ``hop``: the vocoder's, unless the caller's rows are in another unit; ``samples``: the items' counts on the host where
-        ``rows`` is a device tensor."""
-        hop = self.streamer.hop_length if hop is None else hop
-        samples = [hop * r for r in rows] if samples is None else list(samples)
+    @staticmethod
+    def _output_stage(waves: _Waves, pcm16: bool, normalize: bool, resampler):
+        """The stand-alone output stage on a waveform that exists: ``Resampler.forward`` with the batch's lengths, or
+        ``synthesis_output.pcm16_on_device`` (``(pcm, peaks)`` with ``normalize``), or the waveform as it is."""
         if resampler is not None:
-            out = resampler.forward(wav, lengths=rows, row_scale=hop, pcm16=pcm16, normalize=normalize)
-            samples = [resampler.out_range(0, n)[1] for n in samples]
-        elif pcm16:
-            from .synthesis_output import pcm16_on_device
-            out = pcm16_on_device(wav, normalize=normalize)
-        else:
-            out = wav
-        out = out[0] if normalize else out
-        return [out[i, :n] for i, n in enumerate(samples)]
+            ragged = {} if waves.lengths is None else {"lengths": waves.lengths, "row_scale": waves.row_scale}
+            return resampler.forward(waves.wav, **ragged, pcm16=pcm16, normalize=normalize)
+        if not pcm16:
+            return waves.wav
+        from .synthesis_output import pcm16_on_device
+        return pcm16_on_device(waves.wav, normalize=normalize)
 
-    def _joined_output_stage(self, wav: torch.Tensor, lengths, row_scale: int, pcm16: bool, normalize: bool, resampler):
-        """A batch whose item i owns ``lengths[i] * row_scale`` samples through the assembler, then the output stage on the
-        joined row with the device's total as its length.  Returns ``(what infer returns for one row, cut at the total;
-        spans)``; the total is read back once, after everything is queued."""
-        out, offsets, spans = self.assemble.join_device(wav.float(), lengths=lengths, row_scale=row_scale)
-        row, total = out[None], offsets[-1:]
-        if resampler is not None:
-            res = resampler.forward(row, lengths=total, row_scale=1, pcm16=pcm16, normalize=normalize)
-        elif pcm16:
-            from .synthesis_output import pcm16_on_device
-            res = pcm16_on_device(row, normalize=normalize)        # the row is 0 behind the total: its peak is the utterance's
-        else:
-            res = row
-        n = int(total.item())
-        if resampler is not None:
-            n = resampler.out_range(0, n)[1]
-        if normalize:
-            return (res[0][0, :n], res[1]), spans
-        return res[0, :n], spans
+    @staticmethod
+    def _cut(result, waves: _Waves, normalize: bool, resampler, as_list: bool, spans=None):
+        """What the caller gets of ``result``, the output of the batch ``waves``: with ``spans`` ``(the joined row -- what
+        ``infer`` returns for one row -- cut at the total, spans)``, the total read back once, after everything is queued; a list
+        cut at each item's own count; or the rows as they are."""
+        def count(n):
+            return n if resampler is None else resampler.out_range(0, n)[1]
+        out = result[0] if normalize else result
+        if spans is not None:
+            row = out[0, :count(int(waves.lengths.item()))]
+            return ((row, result[1]) if normalize else row), spans
+        if not as_list:
+            return result
+        if waves.samples is None:
+            return list(out.unbind(0))
+        return [out[i, :count(n)] for i, n in enumerate(waves.samples)]
 
-    def _pcm16_fn(self) -> Callable:
-        fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_pcm16", None)
-        if fn is None:
-            raise ValueError("pcm16=True needs a vocoder with a device output stage: construct the pipeline with a bound "
-                             "GeneratorEngine.forward")
-        return fn
+    # -- the fused routes: no wave stage, so the vocoder's last launch does the conversion --------------------------------------
+    def _streamer_with(self, forward: Optional[Callable] = None, resampler=None) -> StreamingVocoder:
+        """This pipeline's streamer with another forward, or with a resampler behind its own."""
+        sv = self.streamer
+        return StreamingVocoder(forward or sv.forward, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames,
+                                halo_frames=sv.halo_frames, group_chunks=sv.group_chunks, config=self.config, resampler=resampler)
 
-    def _resampled_fn(self) -> Callable:
-        fn = getattr(getattr(self.streamer.forward, "__self__", None), "forward_resampled", None)
-        if fn is None:
+    def _fused_forward(self, ragged: bool, pcm16: bool, normalize: bool, resampler) -> Optional[Callable]:
+        """What ``_vocode`` runs in place of the streamer's forward (None: fp32 at the vocoder's rate, nothing to fuse):
+        ``GeneratorEngine.forward_pcm16`` or ``forward_resampled`` -- ONE forward for a ragged batch, for ``normalize`` (the peak is
+        the whole utterance's) and for resampled PCM; chunked like the fp32 path otherwise, each resampled window at its own
+        origin.  A vocoder without that forward is refused here, before anything runs."""
+        if resampler is None and not pcm16:
+            return None
+        engine = getattr(self.streamer.forward, "__self__", None)
+        if resampler is None:
+            fwd = getattr(engine, "forward_pcm16", None)
+            if fwd is None:
+                raise ValueError("pcm16=True needs a vocoder with a device output stage: construct the pipeline with a bound "
+                                 "GeneratorEngine.forward")
+            if ragged or normalize:
+                return lambda mel, **lengths: fwd(mel, **lengths, normalize=normalize)
+            return self._streamer_with(fwd).infer
+        fwd = getattr(engine, "forward_resampled", None)
+        if fwd is None:
             raise ValueError("resampler= needs a vocoder with a device resampling stage: construct the pipeline with a bound "
                              "GeneratorEngine.forward")
-        return fn
+        if ragged or pcm16:
+            return lambda mel, **lengths: fwd(mel, resampler, **lengths, pcm16=pcm16, normalize=normalize)
+        return self._streamer_with(resampler=resampler).infer
 
     def infer(self, mel, pcm16: bool = False, normalize: bool = False, resampler=None):
         """The whole utterance.  ``pcm16=True``: an int16 device tensor, converted by the vocoder's last launch
@@ -388,38 +418,11 @@ class MelToWavePipeline:
 
         With ``output=`` the arguments are refused and the result is the fp32 waveform -- behind every other stage -- through
         ``output.forward``: its rate, its encoding, what ``stream`` yields piece by piece."""
-        if normalize and not pcm16:
-            raise ValueError("normalize=True goes with pcm16=True")
-        resampler = self._output_args(pcm16, normalize, resampler)
-        if (self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None
-                or self.limiter is not None or self.output is not None):
-            mel = self.refine(mel)
-            wav = self._whole.forward_device(mel) if self._whole is not None else self.streamer.infer(mel)
-            if self.denoiser is not None:
-                wav = self._denoise(wav)
-            if self.stretch is not None:
-                wav = self.stretch.forward_device(wav.float())[0]
-            wav = self._limit(self._level(wav))
-            if self.assemble is not None:
-                return self._joined_output_stage(wav, None, 1, pcm16, normalize, resampler)
-            return self._output_stage(wav, pcm16, normalize, resampler)
-        if self._whole is not None:
-            return self._vocode_whole(self.refine(mel), pcm16, normalize, resampler)
-        if resampler is not None:
-            fwd = self._resampled_fn()
-            if pcm16:
-                return fwd(self.refine(mel), resampler, pcm16=True, normalize=normalize)
-            sv = self.streamer
-            return StreamingVocoder(sv.forward, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames,
-                                    halo_frames=sv.halo_frames, group_chunks=sv.group_chunks, config=self.config, resampler=resampler).infer(self.refine(mel))
-        if not pcm16:
-            return self.streamer.infer(self.refine(mel))
-        fwd = self._pcm16_fn()
-        if normalize:
-            return fwd(self.refine(mel), normalize=True)
-        sv = self.streamer
-        return StreamingVocoder(fwd, hop_length=sv.hop_length, chunk_frames=sv.chunk_frames, halo_frames=sv.halo_frames,
-                                group_chunks=sv.group_chunks, config=self.config).infer(self.refine(mel))
+        out_args = self._output_args(pcm16, normalize, resampler)
+        if self._has_wave_stage() or self._whole is not None:
+            return self._finish(self._chain(self._vocode(self.refine(mel))), *out_args)
+        forward = self._fused_forward(False, *out_args)
+        return self._vocode(self.refine(mel), forward=forward).wav
 
     __call__ = infer
 
@@ -633,11 +636,10 @@ class MelToWavePipeline:
         ``pcm16=True``: int16 waveforms from ``GeneratorEngine.forward_pcm16``; with ``normalize=True`` each is scaled to
         0.95 at its own peak first.  ``resampler``: every waveform at its rate (``GeneratorEngine.forward_resampled`` with the
         same lengths: item i has ``resampler.out_range(0, hop * T_i)[1]`` samples, bit for bit its one-item conversion).
-        A whole-utterance vocoder with ``takes_lengths`` (``_vocode_whole_ragged``): ``hop * (T_i - 1)`` samples per item.
+        A whole-utterance vocoder with ``takes_lengths`` (``_vocode``): ``hop * (T_i - 1)`` samples per item, its rows 0 past
+        them -- so an item's peak is its own.
         With ``assemble=`` the result is ``(waveform, spans)``: the items trimmed and joined into one (the class docstring)."""
-        if normalize and not pcm16:
-            raise ValueError("normalize=True goes with pcm16=True")
-        resampler = self._output_args(pcm16, normalize, resampler)
+        out_args = self._output_args(pcm16, normalize, resampler)
         mels = list(mels)
         if not mels:
             return []
@@ -649,42 +651,15 @@ class MelToWavePipeline:
         padded = self._to_device(padded)
         if self.postnet is not None:
             padded = self._refine_fn()(padded, lengths=lengths)
-        if (self.denoiser is not None or self.stretch is not None or self.assemble is not None or self.loudness is not None
-                or self.limiter is not None or self.output is not None):
-            frames = [int(t) for t in lengths]
-            if ragged_whole:
-                rows = [max(t - 1, 0) for t in frames]
-                wav = self._whole.forward_device(padded, lengths=frames)
-            elif self._whole is not None:
-                rows = [max(frames[0] - 1, 0)] * len(frames)
-                wav = self._whole.forward_device(padded)
-            else:
-                rows = frames
-                wav = self.streamer.forward(padded, lengths=lengths)
-            if self.denoiser is not None:
-                wav = self._denoise(wav, rows)
-            if self.stretch is not None:
-                return self._stretch_ragged(wav.float(), rows, pcm16, normalize, resampler)
-            wav = self._limit(self._level(wav, rows, self.streamer.hop_length), rows, self.streamer.hop_length)
-            if self.assemble is not None:
-                return self._joined_output_stage(wav, rows, self.streamer.hop_length, pcm16, normalize, resampler)
-            return self._ragged_output_stage(wav, rows, pcm16, normalize, resampler)
-        if ragged_whole:
-            return self._vocode_whole_ragged(padded, lengths, pcm16, normalize, resampler)
-        if self._whole is not None:
-            out = self._vocode_whole(padded, pcm16, normalize, resampler)
-            return list((out[0] if normalize else out).unbind(0))
-        if resampler is not None:
-            wav = self._resampled_fn()(padded, resampler, lengths=lengths, pcm16=pcm16, normalize=normalize)
-            wav = wav[0] if normalize else wav
-            hop = self.streamer.hop_length
-            return [wav[i, :resampler.out_range(0, hop * int(t))[1]] for i, t in enumerate(lengths)]
-        if pcm16:
-            wav = self._pcm16_fn()(padded, lengths=lengths, normalize=normalize)
-            wav = wav[0] if normalize else wav
-        else:
-            wav = self.streamer.forward(padded, lengths=lengths)
-        return split_waveforms(wav, lengths, self.streamer.hop_length)
+        if self._has_wave_stage():
+            return self._finish(self._chain(self._vocode(padded, lengths)), *out_args, as_list=True)
+        if self._whole is not None:                                  # items of one length and no stage behind: whole rows, as ``infer``
+            return self._finish(self._vocode(padded, lengths if ragged_whole else None), *out_args, as_list=True)
+        pcm16, normalize, resampler = out_args
+        waves = self._vocode(padded, lengths, self._fused_forward(True, *out_args))
+        if resampler is None:                                        # at the vocoder's rate: cut with its check of the row's length
+            return split_waveforms(waves.wav[0] if normalize else waves.wav, lengths, self.streamer.hop_length)
+        return self._cut(waves.wav, waves, normalize, resampler, as_list=True)
 
     def session(self, postnet_halo_frames: Optional[int] = None) -> "PipelineSession":
         """A new ``PipelineSession`` for ONE utterance whose mel is still being produced.  ``postnet_halo_frames``: the
@@ -692,8 +667,6 @@ class MelToWavePipeline:
         Refused with a plain denoiser, stretch or limiter (``ValueError``), as ``stream`` is; with chunked ones the session's
         pieces are those of the last of their sessions."""
         self._refuse_unstreamable()
-        if self._whole is not None:
-            raise NotImplementedError("a whole-utterance vocoder (Griffin-Lim) cannot be streamed: every sample depends on every frame")
         return PipelineSession(self, postnet_halo_frames)
 
 

@@ -103,9 +103,8 @@ class StreamGroup:
             if getattr(pipeline, name) is not None:
                 raise ValueError(f"a StreamGroup does not take a pipeline with {name}=: its measure is the whole item's, and no "
                                  "chunked form is built")
-        pipeline._refuse_unstreamable()                          # a plain limiter: limiter=lim.chunked()
-        if pipeline._whole is not None:
-            raise ValueError("a StreamGroup does not take a whole-utterance vocode (Griffin-Lim): every sample depends on every frame")
+        pipeline._refuse_unstreamable(whole=ValueError(           # a plain limiter (limiter=lim.chunked()), then the vocoder
+            "a StreamGroup does not take a whole-utterance vocode (Griffin-Lim): every sample depends on every frame"))
         dtype = getattr(getattr(pipeline.streamer.forward, "__self__", None), "default_dtype", "f32")
         if dtype != "f32":
             raise ValueError(f"a StreamGroup needs the fp32 engine as its vocode: only it has a ragged forward, got dtype {dtype!r}")
